@@ -2,10 +2,17 @@
 """bench.py -- IQ Msamples/s -> decoded bits on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--samples S] [--workload miller|manchester|all|classic1k]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the whole hot path (envelope -> threshold -> edges -> Miller/Manchester -> framing) over the
 rank's batch of synthetic IQ, input already resident in HBM.  At N=1 the workload is BASELINE.json configs[1]: Miller-only
 decode of 1e8 synthetic IQ samples @ 2 Msps.
+
+A plain run sets up, warms up, times exactly K steps and prints the headline (ms_per_step, Msamples/s); no launch of its
+timed steps carries HIP events.  --full adds everything else, as the --no-* switches leave it: the threshold launches timed
+by events (roofline), the other way of stepping, the per-stage split of one extra step, parity against the C oracle, the
+CPU baseline, end to end, the other configurations and the stress captures.  --dump-outputs DIR writes what the last timed
+step handed its caller (dump_outputs).
 
 N > 1: one process per GPU.  Launched by ``python -m torch.distributed.run ... bench.py --gpus N`` the ranks read RANK /
 LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment; launched as plain ``python bench.py --gpus N`` this process spawns
@@ -44,7 +51,7 @@ def parse():
     ap.add_argument('--workload', default=None, choices=['miller', 'manchester', 'all', 'classic1k'],
                     help="BASELINE.json configs[1] / [2] / both decoders at 2 Msps, or configs[3] / [4]: the MIFARE Classic 1K "
                          "transaction of outputs/1k_with_enc.out at 10 Msps, 1e9 samples per GPU (a 1e8-sample capture tiled).  Default: miller; "
-                         "with --gpus N > 1 and no --workload the line also carries configs[4] (classic1k, 1e9 samples per GPU) under other_configs")
+                         "with --full, --gpus N > 1 and no --workload the line also carries configs[4] (classic1k, 1e9 samples per GPU) under other_configs")
     ap.add_argument('--input-kind', default='iq', choices=['iq', 'env', 'i16'],
                     help="what the caller hands over: fc32 IQ (8 B/sample, BASELINE's metric), the float32 envelope that the reference's own "
                          "transition_sink.work receives (4 B/sample, transition_sink.py:13-18), or 16-bit PCM as the WAV branch reads it (2 B/sample)")
@@ -56,8 +63,13 @@ def parse():
     ap.add_argument('--primary', default=None, choices=['sync', 'ahead'], help='what the headline steps are (default: sync on one GPU, ahead with several -- a rank\'s time shard is a stream, '
                     'its boundary protocol is paid once per shard; the per-step protocol is then the figure beside it) -- sync: every step a fresh stream pushed synchronously '
                     '(the threshold kernel with the machine to itself); ahead: consecutive batches of one stream, submitted ahead (nfc_submit_device / nfc_wait). '
-                    'The other one is measured beside it unless --no-extras')
+                    'With --full the other one is measured beside it unless --no-extras')
     ap.add_argument('--sync-steps', action='store_true', help='(same as --primary sync --no-extras for the stepping: kept for the profiling scripts)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64; dump_outputs)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check everything beside the headline (roofline, parity, CPU baseline, extras; the --no-* switches '
+                         'trim it); without it the run does only the warm-up and the timed steps')
     a = ap.parse_args()
     a.workload_given = a.workload is not None
     a.workload = a.workload or 'miller'
@@ -243,7 +255,7 @@ class Resident(object):
 # ---------------------------------------------------------------------------------------------------------------------
 # one configuration on this rank
 # ---------------------------------------------------------------------------------------------------------------------
-def run_config(a, workload, n, steps, warmup, rank, world, local, comm, backend, want_parity, chunk=0, kind='iq'):
+def run_config(a, workload, n, steps, warmup, rank, world, local, comm, backend, want_parity, chunk=0, kind='iq', dump_dir=None):
     import numpy as np
     from usrp_nfc_amd import api, sharding, synth
     ndev = max(1, api.device_count())
@@ -323,6 +335,7 @@ def run_config(a, workload, n, steps, warmup, rank, world, local, comm, backend,
         """warm-up + exactly `steps` timed steps in the given mode, bracketed by barrier + device sync; max over ranks"""
         acc = {'kernel_ms': [], 'n_pass': [], 'n_ahead': 0, 'mode': mode}
         redo[0] = 0
+        timed_every = 8 if a.full else 0   # (a plain run: no launch carries events)
         if mode == 'ahead' and sharded:
             def shard(count, timed_every):
                 redo[0] += sharding.decode_shard(ctx, comm, push_overlap, lambda: stream_steps(count, timed_every, acc),
@@ -332,13 +345,13 @@ def run_config(a, workload, n, steps, warmup, rank, world, local, comm, backend,
             redo[0] = 0
             barrier()
             t0 = time.perf_counter()
-            shard(steps, 8)
+            shard(steps, timed_every)
         elif mode == 'ahead':
             ctx.reset()
             stream_steps(warmup, 0, acc)
             barrier()
             t0 = time.perf_counter()
-            stream_steps(steps, 8, acc)
+            stream_steps(steps, timed_every, acc)
         else:
             for _ in range(warmup):
                 one_step()
@@ -350,8 +363,8 @@ def run_config(a, workload, n, steps, warmup, rank, world, local, comm, backend,
                 # (<= 32 steps: 10 of the driver's 20).  Not every one: a timed launch costs its step 14 us -- measured, round 6, 20 steps
                 # on one box: 0.2545 / 0.2464 / 0.2432 ms per step with every / every 2nd / every 4th launch timed, the launches themselves
                 # 0.139 ms whichever (NFC_BENCH_TIMED_STRIDE=1 times them all)
-                stride = int(os.environ.get('NFC_BENCH_TIMED_STRIDE', '0')) or (8 if steps > 32 else 2)
-                timed = (k % 8 == 3) if stride == 8 else (k % stride == stride - 1)   # (stride 8: not the region's very first launch)
+                stride = (int(os.environ.get('NFC_BENCH_TIMED_STRIDE', '0')) or (8 if steps > 32 else 2)) if timed_every else 0
+                timed = bool(stride) and ((k % 8 == 3) if stride == 8 else (k % stride == stride - 1))   # (stride 8: not the region's very first launch)
                 if stride > 1 and (timed or (k and ((k - 1) % 8 == 3 if stride == 8 else (k - 1) % stride == stride - 1))):
                     ctx.set_timing(1 if timed else 0)
                 elif stride == 1 and k == 0:
@@ -387,15 +400,18 @@ def run_config(a, workload, n, steps, warmup, rank, world, local, comm, backend,
     primary = a.primary or ('ahead' if world > 1 else 'sync')
     ahead = primary == 'ahead' and not a.sync_steps
     # (the region that lands beside the headline goes first: the headline's steps then run on a machine that is already at its clocks)
-    other = None if (a.no_extras or a.sync_steps) else region('sync' if ahead else 'ahead')
+    other = None if (not a.full or a.no_extras or a.sync_steps) else region('sync' if ahead else 'ahead')
     prim = region('ahead' if ahead else 'sync')
     dt, kernel_ms, n_pass = prim['dt'], prim['kernel_ms'], prim['n_pass']
     redo[0] = prim['redo']
-    ctx.set_timing(2)   # one more, untimed, step for the per-stage split reported beside the headline (synchronous: stream markers)
-    if ahead and not sharded:
-        ctx.push_device(res.buf, n)
-    else:
-        one_step()   # (with several ranks: the whole protocol once more on a fresh stream -- every rank's context then holds the decode of ITS shard)
+    if dump_dir and rank == 0:   # (the headline's call only: rank_main's other configurations pass none)
+        dump_outputs(ctx, dump_dir)
+    if a.full:
+        ctx.set_timing(2)   # one more, untimed, step for the per-stage split reported beside the headline (synchronous: stream markers)
+        if ahead and not sharded:
+            ctx.push_device(res.buf, n)
+        else:
+            one_step()   # (with several ranks: the whole protocol once more on a fresh stream -- every rank's context then holds the decode of ITS shard)
     st = ctx.stats()
     cnt = ctx.counts()
     n_edges = int(cnt.n_edges)
@@ -405,16 +421,10 @@ def run_config(a, workload, n, steps, warmup, rank, world, local, comm, backend,
         # it travel to rank 0 (JSON over the communicator), which checks every one against the oracle (sharded_parity)
         gathered = comm.gather_objects(result_digest(ctx.edges(), ctx.symbols(0), ctx.symbols(1), ctx.packets()))
     ov_used = None
-    if world > 1:   # the warm-up length every rank ended on (rank 0 has none)
+    if a.full and world > 1:   # the warm-up length every rank ended on (rank 0 has none)
         ov_used = comm.gather_objects(int(getattr(ctx, 'overlap_used', 0) or 0))
     out = None
     if rank == 0:
-        k_avg = float(np.mean(kernel_ms)) if kernel_ms else float('nan')
-        thr_bytes = float(bps) * n                       # SURVEY.md 8(d): 8 B per sample (fc32 IQ; 4 / 2 for the other input kinds) read by the envelope + threshold kernel ...
-        edge_bytes = 16.0 * n_edges                      # ... 16 B per emitted edge (the nfc_edge record) in SURVEY's count; the edge
-        stored_bytes = 6.0 * n_edges                     # stage now keeps 6 B per entry (u32 position + u16 code), records built on read
-        achieved = thr_bytes / (k_avg * 1e-3) / 1e9
-        traffic, tsrc = hbm_traffic(workload, n, kind)
         out = {
             'ms_per_step': dt / steps * 1e3,
             'value': world * n * steps / dt / 1e6,
@@ -429,7 +439,15 @@ def run_config(a, workload, n, steps, warmup, rank, world, local, comm, backend,
                        # several ranks: what the boundary protocol adds to a step when it is run PER STEP (prime, warm-up on the overlap,
                        # state export, all-gather, verify) -- the per-step region's step less the device time of the own chunk alone
                        'protocol_us_per_step': ((((other if ahead else prim)['dt'] / steps * 1e3) - st.ms_total) * 1e3
-                                                if sharded and (other or not ahead) and st.ms_total > 0 else None)},
+                                                if a.full and sharded and (other or not ahead) and st.ms_total > 0 else None)}}
+    if rank == 0 and a.full:
+        k_avg = float(np.mean(kernel_ms)) if kernel_ms else float('nan')
+        thr_bytes = float(bps) * n                       # SURVEY.md 8(d): 8 B per sample (fc32 IQ; 4 / 2 for the other input kinds) read by the envelope + threshold kernel ...
+        edge_bytes = 16.0 * n_edges                      # ... 16 B per emitted edge (the nfc_edge record) in SURVEY's count; the edge
+        stored_bytes = 6.0 * n_edges                     # stage now keeps 6 B per entry (u32 position + u16 code), records built on read
+        achieved = thr_bytes / (k_avg * 1e-3) / 1e9
+        traffic, tsrc = hbm_traffic(workload, n, kind)
+        out.update({
             # (kernel: the fused envelope + gated-mean threshold kernel, a time chunk per workgroup; k_threshold_lean / k_threshold where it does not apply)
             'roofline': {'bound': 'hbm', 'kernel': 'k_threshold_wg',
                          'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBS,
@@ -459,7 +477,7 @@ def run_config(a, workload, n, steps, warmup, rank, world, local, comm, backend,
             ('one_batch_at_a_time' if ahead else 'submitted_ahead'): (summary(other) if other else None),
             'stage_ms_extra_step': {'total_device': st.ms_total, 'threshold': st.ms_threshold, 'edges': st.ms_edges,
                                     'decode': st.ms_decode, 'used_sequential': int(st.used_sequential)},
-        }
+        })
         if want_parity:
             out['parity'] = parity_check(workload, own, flags, n, True, kind)
             if gathered is not None:
@@ -617,6 +635,48 @@ def result_digest(edges, sym0, sym1, packets):
             'symbols': h(np.asarray(sym0, np.uint8)) + h(np.asarray(sym1, np.uint8)),
             'packets': h(np.array([t for t, b in packets], 'i1'), np.array([len(b) for t, b in packets], '<i4'),
                          np.array([bit for t, b in packets for bit in b], np.uint8))}
+
+
+DUMP_SEED = 20261016
+DUMP_CAPS = {'edges': 500_000, 'symbols_tag': 2_000_000, 'symbols_reader': 2_000_000, 'packets': 250_000, 'packet_bits': 4_000_000}   # rows: <= 54 MB in all
+
+
+def dump_outputs(ctx, out_dir):
+    """What the context's last batch handed its caller, as DIR/<name>.npy: integers as float64 (positions beyond 2**24) or
+    float32 (bits and symbols), exact either way.
+      edges           (n, 4) float64: idx, d, v, t of every transition (nfc_read_edges)
+      symbols_tag     float32: the Manchester decoder's symbols (type 0)    symbols_reader: the Miller decoder's (type 1)
+      packets         (p, 3) float64: closing edge index, type, number of bits of every closed packet, in stream order
+      packet_bits     float32: those packets' bits, one after the other
+      counts          float64: the lengths of the five above before sampling
+    An array longer than its DUMP_CAPS entry is a fixed sample of its rows (DUMP_SEED; the same rows for the same length).  An
+    empty one (the symbols of a decoder the workload does not run) has no file -- one left in DIR by an earlier dump is
+    removed --: counts holds its length, 0."""
+    import numpy as np
+    e = ctx.edges()
+    tabs = [ctx.packet_table(t) for t in (0, 1)]
+    bits = [ctx.packet_bits(t) for t in (0, 1)]
+    tab = np.concatenate(tabs)
+    ptype = np.repeat([0, 1], [len(tabs[0]), len(tabs[1])])
+    order = np.argsort(tab['idx'], kind='stable')   # (one edge feeds one decoder: the closing indices of the two types never tie)
+    lens = tab['n_bits'][order].astype(np.int64)
+    starts = tab['bit_off'][order].astype(np.int64) + np.where(ptype[order] == 1, len(bits[0]), 0)
+    ends = np.cumsum(lens)
+    arrays = {'edges': np.stack([e['idx'], e['d'], e['v'], e['t']], axis=1).astype(np.float64),
+              'symbols_tag': ctx.symbols(0).astype(np.float32), 'symbols_reader': ctx.symbols(1).astype(np.float32),
+              'packets': np.stack([tab['idx'][order], ptype[order], lens], axis=1).astype(np.float64),
+              'packet_bits': np.concatenate(bits)[np.repeat(starts - (ends - lens), lens) + np.arange(int(ends[-1]) if len(ends) else 0)].astype(np.float32)}
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, 'counts.npy'), np.array([len(arrays[k]) for k in DUMP_CAPS], np.float64))
+    for name, x in arrays.items():
+        path = os.path.join(out_dir, name + '.npy')
+        if not len(x):
+            if os.path.exists(path):
+                os.remove(path)
+            continue
+        if len(x) > DUMP_CAPS[name]:
+            x = x[np.sort(np.random.default_rng(DUMP_SEED).choice(len(x), DUMP_CAPS[name], replace=False))]
+        np.save(path, x)
 
 
 SHARDED_PARITY_CAP = 800_000_000   # samples of the whole capture the stitched parity leg regenerates and decodes on rank 0's host
@@ -819,16 +879,17 @@ def rank_main(a):
     kind = a.input_kind
     if kind != 'iq' and world > 1:
         raise SystemExit('bench: --input-kind %s is a one-GPU figure (the sharded runs take fc32 IQ, BASELINE.json\'s metric)' % kind)
-    out, own, flags = run_config(a, a.workload, n, a.steps, a.warmup, rank, world, local, comm, backend, not a.no_parity, a.chunk, kind)
+    out, own, flags = run_config(a, a.workload, n, a.steps, a.warmup, rank, world, local, comm, backend, a.full and not a.no_parity, a.chunk, kind,
+                                 a.dump_outputs)
     if rank == 0:
         line = {'metric': 'IQ Msamples/s -> decoded bits (2 Msps stream)' if a.workload != 'classic1k' else 'IQ Msamples/s -> decoded bits (10 Msps stream)',
                 'value': out['value'], 'unit': 'Msamples/s', 'n_gpus': comm.world, 'steps': a.steps, 'warmup': a.warmup,
                 'ms_per_step': out['ms_per_step'], 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
                 'dtype': 'f32 envelope / f64 window sums / u8 symbols', 'data': 'synthetic'}
         line.update({k: v for k, v in out.items() if k not in ('value', 'ms_per_step')})
-        if not a.no_cpu_baseline and world == 1:   # the CPU baseline is timed on rank 0 of the 1-GPU run only
+        if a.full and not a.no_cpu_baseline and world == 1:   # the CPU baseline is timed on rank 0 of the 1-GPU run only
             line['cpu_baseline'] = cpu_baseline(own, flags, stream_params(a.workload), kind)
-        if world == 1 and not a.no_extras and a.workload == 'miller' and n == 100_000_000 and kind == 'iq':
+        if a.full and world == 1 and not a.no_extras and a.workload == 'miller' and n == 100_000_000 and kind == 'iq':
             # the figures SURVEY.md 8(d) asks for beside the headline, measured in this same invocation
             line['end_to_end'] = end_to_end(a.workload, own, flags)
             # (inside the object the driver's record keeps whole: VERDICT r05 item 6)
@@ -858,7 +919,7 @@ def rank_main(a):
             for e in line['stress']:
                 e['vs_clean_step'] = e['ms_per_step'] / clean
     own = None   # (the capture's host copy is not needed any more)
-    if world > 1 and not a.workload_given and not a.samples and not a.no_extras:
+    if a.full and world > 1 and not a.workload_given and not a.samples and not a.no_extras:
         # BASELINE.json configs[4]: the -t all decode of the MIFARE Classic 1K capture at 10 Msps, 1e9 samples per GPU, time-sharded
         # over the same ranks (every rank in step: the protocol's collectives run inside)
         st4 = min(a.steps, 10)

@@ -342,7 +342,7 @@ def test_bench_spawns_two_ranks_on_one_gpu():
     env = dict(os.environ, NFC_BENCH_BACKEND='host')
     env.pop('WORLD_SIZE', None)
     r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--samples', '2e6', '--steps', '3', '--warmup', '1',
-                        '--no-cpu-baseline', '--no-extras'], capture_output=True, text=True, timeout=600, cwd=root, env=env)
+                        '--full', '--no-cpu-baseline', '--no-extras'], capture_output=True, text=True, timeout=600, cwd=root, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line['n_gpus'] == 2 and line['config']['exchange'] == 'host' and line['config']['boundary_redos'] == 0
@@ -365,7 +365,7 @@ def test_bench_eight_ranks_of_configs4_on_one_gpu():
     env = dict(os.environ, NFC_BENCH_BACKEND='host')
     env.pop('WORLD_SIZE', None)
     r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '8', '--workload', 'classic1k', '--samples', '2e7', '--steps', '2',
-                        '--warmup', '1', '--no-cpu-baseline', '--no-extras'], capture_output=True, text=True, timeout=1500, cwd=root, env=env)
+                        '--warmup', '1', '--full', '--no-cpu-baseline', '--no-extras'], capture_output=True, text=True, timeout=1500, cwd=root, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line['n_gpus'] == 8 and line['config']['exchange'] == 'host'
@@ -628,7 +628,7 @@ def test_bench_capture_slices_agree_on_the_samples_they_share():
 
 
 def test_bench_parity_legs_of_an_eight_gpu_run_fit_the_drivers_clock():
-    # The driver runs `python bench.py --gpus 8 --steps K --warmup W` (no --workload) inside a 1 800 s limit.  Beside the GPU work that
+    # `python bench.py --gpus 8 --steps K --warmup W --full` (no --workload) has to fit a 1 800 s limit.  Beside the GPU work that
     # run checks EVERY rank against the pinned C oracle on rank 0's host (bench.sharded_parity): the 8 x 1e8-sample Miller capture is
     # REGENERATED shard by shard and decoded by one core, then configs[4]'s 8 x 1e9-sample tiled capture is decoded tile by tile.  Both
     # legs are linear in the sample count: timed here at a fraction of the size, extrapolated, and held against a budget that leaves

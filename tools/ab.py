@@ -7,7 +7,7 @@
     tools/ab.py kstat <workload> [--rounds N] [--bench "args"] lib1.so lib2.so ...                  ... per-kernel time per step under rocprofv3 (tools/kstats.sh)
     tools/ab.py stress <stress_hover|stress_dropouts_steps|stress_dropouts> "VAR=val ..." ...       a stress capture's steps (tools/stress_step.py)
 
-Every variant is one `python3 bench.py --workload W --steps 40 --warmup 10 --no-cpu-baseline --no-parity --no-extras` (classic1k: 6 / 2
+Every variant is one `python3 bench.py --workload W --steps 40 --warmup 10 --full --no-cpu-baseline --no-parity --no-extras` (classic1k: 6 / 2
 steps, parity kept); one line per run: ms per step, the threshold kernel's event-timed launch, roofline.frac, launches per step, the cut.
 Variants ALTERNATE within a round (a box's clocks drift over a call): compare neighbours, not columns."""
 import json
@@ -20,7 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def bench(workload, extra_args, env_add, label):
     c1k = workload == 'classic1k'
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--workload', workload, '--no-cpu-baseline']
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--workload', workload, '--full', '--no-cpu-baseline']
     cmd += ['--steps', '6', '--warmup', '2', '--no-extras'] if c1k else ['--steps', '40', '--warmup', '10', '--no-parity', '--no-extras']
     cmd += extra_args
     env = dict(os.environ)

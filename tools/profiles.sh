@@ -5,22 +5,22 @@ tag=${1:-r06}
 out=gpurun_out/prof
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
-timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o $tag -- python3 bench.py --steps 100 --warmup 20 --no-cpu-baseline --no-parity --no-extras --sync-steps > $out/${tag}_bench_under_rocprof.json 2> $out/stats.log
+timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o $tag -- python3 bench.py --steps 100 --warmup 20 --full --no-cpu-baseline --no-parity --no-extras --sync-steps > $out/${tag}_bench_under_rocprof.json 2> $out/stats.log
 # the same with batches submitted ahead (--primary ahead): the threshold stage of batch k + 1 beside the later stages of batch k
-timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_ahead -o ${tag}a -- python3 bench.py --steps 100 --warmup 20 --no-cpu-baseline --no-parity --no-extras --primary ahead > $out/${tag}_bench_ahead_under_rocprof.json 2> $out/stats_ahead.log
+timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_ahead -o ${tag}a -- python3 bench.py --steps 100 --warmup 20 --full --no-cpu-baseline --no-parity --no-extras --primary ahead > $out/${tag}_bench_ahead_under_rocprof.json 2> $out/stats_ahead.log
 python3 tools/timeline2.py $out/stats_ahead/${tag}a_kernel_trace.csv 60 22 > $out/${tag}_timeline_ahead.txt 2>&1
 # counter passes, per workload (configs[1], [2], [3]): FETCH_SIZE, WRITE_SIZE and the SQ instruction counters each in a pass of its own
 for wl in miller manchester classic1k env; do
   extra=""; [ $wl = classic1k ] && extra="--samples 1e9"
   wlarg="--workload $wl"; [ $wl = env ] && wlarg="--input-kind env"
-  timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $out/fetch_$wl -o p -- python3 bench.py $wlarg $extra --steps 2 --warmup 0 --no-cpu-baseline --no-parity --no-extras --sync-steps > /dev/null 2> $out/fetch_$wl.log
-  timeout 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $out/write_$wl -o p -- python3 bench.py $wlarg $extra --steps 2 --warmup 0 --no-cpu-baseline --no-parity --no-extras --sync-steps > /dev/null 2> $out/write_$wl.log
-  timeout 600 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR --kernel-trace --output-format csv -d $out/sq_$wl -o p -- python3 bench.py $wlarg $extra --steps 4 --warmup 1 --no-cpu-baseline --no-parity --no-extras --sync-steps > /dev/null 2> $out/sq_$wl.log
-  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_$wl -o ${tag}_$wl -- python3 bench.py $wlarg $extra --steps 20 --warmup 5 --no-cpu-baseline --no-parity --no-extras --sync-steps > $out/${tag}_bench_${wl}_under_rocprof.json 2> $out/stats_$wl.log
+  timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $out/fetch_$wl -o p -- python3 bench.py $wlarg $extra --steps 2 --warmup 0 --full --no-cpu-baseline --no-parity --no-extras --sync-steps > /dev/null 2> $out/fetch_$wl.log
+  timeout 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $out/write_$wl -o p -- python3 bench.py $wlarg $extra --steps 2 --warmup 0 --full --no-cpu-baseline --no-parity --no-extras --sync-steps > /dev/null 2> $out/write_$wl.log
+  timeout 600 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR --kernel-trace --output-format csv -d $out/sq_$wl -o p -- python3 bench.py $wlarg $extra --steps 4 --warmup 1 --full --no-cpu-baseline --no-parity --no-extras --sync-steps > /dev/null 2> $out/sq_$wl.log
+  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_$wl -o ${tag}_$wl -- python3 bench.py $wlarg $extra --steps 20 --warmup 5 --full --no-cpu-baseline --no-parity --no-extras --sync-steps > $out/${tag}_bench_${wl}_under_rocprof.json 2> $out/stats_$wl.log
 done
 # the other input kinds of the boundary on configs[1]: the float32 envelope (what transition_sink.work receives) and 16-bit PCM
 for kd in i16; do
-  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_$kd -o ${tag}_$kd -- python3 bench.py --input-kind $kd --steps 20 --warmup 5 --no-cpu-baseline --no-parity --no-extras --sync-steps > $out/${tag}_bench_${kd}_under_rocprof.json 2> $out/stats_$kd.log
+  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_$kd -o ${tag}_$kd -- python3 bench.py --input-kind $kd --steps 20 --warmup 5 --full --no-cpu-baseline --no-parity --no-extras --sync-steps > $out/${tag}_bench_${kd}_under_rocprof.json 2> $out/stats_$kd.log
 done
 # what a read-only kernel with the threshold kernel's access pattern reaches on this box (tools/ubench/stream_chunks.hip)
 [ -x tools/ubench/stream_chunks ] && tools/ubench/stream_chunks > $out/${tag}_stream_ceiling.txt 2>&1
@@ -43,14 +43,14 @@ fi
   echo "# python tools/ab.py env manchester --rounds 2 NFC_WG_FLAGS=0 NFC_WG_FLAGS=1"; python3 tools/ab.py env manchester --rounds 2 "NFC_WG_FLAGS=0" "NFC_WG_FLAGS=1";
   echo "# python tools/ab.py env classic1k --rounds 2 --bench '--samples 1e9 --steps 10 --warmup 2' NFC_WG_FLAGS=0 NFC_WG_FLAGS=1   (eight rows per step, the staging ring)"; python3 tools/ab.py env classic1k --rounds 2 --bench "--samples 1e9 --steps 10 --warmup 2" "NFC_WG_FLAGS=0" "NFC_WG_FLAGS=1";
   if [ -f scratch/r6/wgprof.so ]; then echo "# where a wave waits (a -DNFC_WG_PROF -DNFC_TEST_HOOKS build, NFC_DEBUG_CLK=1: s_memtime ticks per wave of a chunk): the barrier form, then NFC_WG_FLAGS=1";
-    NFC_DEBUG_CLK=1 NFC_AMD_LIB=scratch/r6/wgprof.so python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-parity --no-extras --sync-steps 2>&1 | grep "wg kernel" | tail -1;
-    NFC_WG_FLAGS=1 NFC_DEBUG_CLK=1 NFC_AMD_LIB=scratch/r6/wgprof.so python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-parity --no-extras --sync-steps 2>&1 | grep "wg kernel" | tail -1; fi; } > $out/${tag}_wg_flags_ab.txt 2>&1
+    NFC_DEBUG_CLK=1 NFC_AMD_LIB=scratch/r6/wgprof.so python3 bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-parity --no-extras --sync-steps 2>&1 | grep "wg kernel" | tail -1;
+    NFC_WG_FLAGS=1 NFC_DEBUG_CLK=1 NFC_AMD_LIB=scratch/r6/wgprof.so python3 bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-parity --no-extras --sync-steps 2>&1 | grep "wg kernel" | tail -1; fi; } > $out/${tag}_wg_flags_ab.txt 2>&1
 # the re-runs that evaluate failed rounds in place (k_threshold_wg<KIND, 4, true>) against k_threshold re-running everything: same call, alternating
 { echo "# python tools/ab.py stress stress_dropouts_steps NFC_WG_EX=0 NFC_WG_EX=1024 NFC_WG_EX=0 NFC_WG_EX=1024   (ms per batch, threshold launches, chunks re-run)"; python3 tools/ab.py stress stress_dropouts_steps "NFC_WG_EX=0" "NFC_WG_EX=1024" "NFC_WG_EX=0" "NFC_WG_EX=1024";
   echo "# ... the capture where EVERY chunk fails, with the limit of a machine-full lifted: python tools/ab.py stress stress_hover NFC_WG_EX=1024 NFC_WG_EX=100000"; python3 tools/ab.py stress stress_hover "NFC_WG_EX=1024" "NFC_WG_EX=100000";
   if [ -f scratch/r6/exprintf.so ]; then echo "# NFC_AMD_LIB=<-DNFC_TEST_HOOKS -DNFC_EX_PRINTF build> python tools/stress_step.py stress_dropouts_steps | python tools/exrounds_summary.py"; NFC_AMD_LIB=scratch/r6/exprintf.so python3 tools/stress_step.py stress_dropouts_steps 2>&1 | python3 tools/exrounds_summary.py; fi; } > $out/${tag}_rerun_in_place_ab.txt 2>&1
 for nm in stress_dropouts_steps stress_hover; do tools/stress_timeline.sh $nm > $out/${tag}_timeline_$nm.txt 2>&1; done
-timeout 600 python3 bench.py > $out/${tag}_bench.json 2> $out/bench.log
+timeout 600 python3 bench.py --full > $out/${tag}_bench.json 2> $out/bench.log
 python3 - <<PY
 import csv, json, collections
 out = "$out"; tag = "$tag"
@@ -86,7 +86,7 @@ for wl, ns in (("miller", 100000000), ("manchester", 100000000), ("classic1k", 1
         recs.append({"workload": "miller" if wl == "env" else wl, "input_kind": "env" if wl == "env" else "iq", "samples": ns, "kernel": ", ".join(k.replace("void nfc::", "").split("(")[0] for k in kname), "FETCH_SIZE_kb": round(f), "WRITE_SIZE_kb": round(w),
                      "correction": "FETCH_SIZE x2 (gfx950: TCC_EA0_RDREQ counted at 64 B per 128-B request, MI355X_MICROARCH.md section HBM); WRITE_SIZE as reported",
                      "bytes_per_launch": int((2 * f + w) * 1024),
-                     "command": "rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -- python3 bench.py --workload %s%s --steps 2 --warmup 0 --no-cpu-baseline --no-parity --no-extras --sync-steps   (and the same with --pmc WRITE_SIZE); median over the launches" % (wl, " --samples 1e9" if wl == "classic1k" else "")})
+                     "command": "rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -- python3 bench.py --workload %s%s --steps 2 --warmup 0 --full --no-cpu-baseline --no-parity --no-extras --sync-steps   (and the same with --pmc WRITE_SIZE); median over the launches" % (wl, " --samples 1e9" if wl == "classic1k" else "")})
     except Exception as e:
         print("no traffic record for", wl, e)
 rec = recs

@@ -4,7 +4,7 @@ tag=$1; envs=$2; w=${3:-miller}
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 out=gpurun_out/sqc_$tag
 export $envs
-timeout 400 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY --kernel-trace --output-format csv -d $out -o p -- python3 bench.py --workload $w ${SQC_ARGS:-} --steps 4 --warmup 1 --no-cpu-baseline --no-parity --no-extras --sync-steps > /dev/null 2> $out.log
+timeout 400 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY --kernel-trace --output-format csv -d $out -o p -- python3 bench.py --workload $w ${SQC_ARGS:-} --steps 4 --warmup 1 --full --no-cpu-baseline --no-parity --no-extras --sync-steps > /dev/null 2> $out.log
 python3 - <<PY
 import csv, collections
 rows = list(csv.DictReader(open("$out/p_counter_collection.csv")))
