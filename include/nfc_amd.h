@@ -48,7 +48,12 @@ typedef enum {
     NFC_IN_IQ_F32 = 0,      /* interleaved float32 I,Q; x = fl(fl(I*I)+fl(Q*Q))  (uhd branch, usrp_src.py:31) */
     NFC_IN_ENV_F32 = 1,     /* float32 envelope already computed; x = sample                                    */
     NFC_IN_REAL_F32_SQ = 2, /* float32 real sample, Q = 0; x = fl(s*s)              (wav branch, decoder.py:25-28) */
-    NFC_IN_I16_SQ = 3       /* int16 PCM; s = fl(pcm / 32767) (or fl(pcm * i16_scale)); x = fl(s*s)  (wavfile_source + wav branch) */
+    NFC_IN_I16_SQ = 3,      /* int16 PCM; s = fl(pcm / 32767) (or fl(pcm * i16_scale)); x = fl(s*s)  (wavfile_source + wav branch) */
+    NFC_IN_IQ_I16 = 4       /* complex int16 (sc16): two little-endian int16 per sample, I first -- std::complex<int16_t>, UHD's sc16
+                             * host buffers, 4 bytes per sample.  I and Q converted as the PCM kind converts a sample (i16_scale), THEN
+                             * x = fl(fl(I*I)+fl(Q*Q)) -- the fc32 kind's envelope of the converted pair, bit for bit.  UHD's own
+                             * sc16 -> fc32 conversion (what cpu_format="fc32", usrp_src.py:19-22, runs on the host) is third party
+                             * and absent from the reference tree: that scaling is UNPINNED, as wavfile_source's is */
 } nfc_input_kind;
 
 /* nfc_params.flags */
@@ -66,11 +71,12 @@ typedef struct {
     int32_t enable_tag;    /* Manchester decoder present      (background.py:21) */
     int32_t input_kind;    /* nfc_input_kind */
     int32_t device;        /* HIP device ordinal */
-    float i16_scale;       /* NFC_IN_I16_SQ only.  0: GNU Radio's wavfile_source normalisation, s = fl((float)pcm / 32767.0f) -- what
+    float i16_scale;       /* NFC_IN_I16_SQ and NFC_IN_IQ_I16 (each of I, Q).  0: GNU Radio's wavfile_source normalisation, s = fl((float)pcm / 32767.0f) -- what
                             * decoder.py:25 feeds the path (gr-blocks wavfile_source_impl.cc divides 16-bit samples by 0x7FFF; GNU Radio
                             * is third party and absent from the reference tree, so this boundary is UNPINNED: SURVEY.md 8c).  > 0: s =
                             * fl((float)pcm * i16_scale) for a source normalised differently (1/32768 is a power of two; 1/32767 is not:
-                            * fl(s*s) then rounds differently near the thresholds) */
+                            * fl(s*s) then rounds differently near the thresholds).  NFC_IN_IQ_I16: at most 2^48 (NFC_ERR_ARG beyond),
+                            * which keeps every envelope finite */
     uint32_t flags;
     int32_t chunk_samples; /* samples per time chunk of the threshold kernel; 0 -> default */
     int32_t reserved;

@@ -5,13 +5,13 @@ import numpy as np
 
 from . import _lib
 from ._lib import (EDGE_DTYPE, NFC_FLAG_FORCE_SEQUENTIAL, NFC_FLAG_NO_EDGES, NFC_IN_ENV_F32, NFC_IN_I16_SQ,
-                   NFC_IN_IQ_F32, NFC_IN_REAL_F32_SQ, PACKET_DTYPE)
+                   NFC_IN_IQ_F32, NFC_IN_IQ_I16, NFC_IN_REAL_F32_SQ, PACKET_DTYPE)
 
-__all__ = ['NfcContext', 'NfcError', 'DeviceBuffer', 'host_decode_lut', 'NFC_IN_IQ_F32', 'NFC_IN_ENV_F32', 'NFC_IN_REAL_F32_SQ',
-           'NFC_IN_I16_SQ', 'NFC_FLAG_FORCE_SEQUENTIAL', 'NFC_FLAG_NO_EDGES']
+__all__ = ['NfcContext', 'NfcError', 'DeviceBuffer', 'host_decode_lut', 'host_envelope', 'NFC_IN_IQ_F32', 'NFC_IN_ENV_F32',
+           'NFC_IN_REAL_F32_SQ', 'NFC_IN_I16_SQ', 'NFC_IN_IQ_I16', 'NFC_FLAG_FORCE_SEQUENTIAL', 'NFC_FLAG_NO_EDGES']
 
 _KIND_DTYPE = {NFC_IN_IQ_F32: (np.float32, 2), NFC_IN_ENV_F32: (np.float32, 1),
-               NFC_IN_REAL_F32_SQ: (np.float32, 1), NFC_IN_I16_SQ: (np.int16, 1)}
+               NFC_IN_REAL_F32_SQ: (np.float32, 1), NFC_IN_I16_SQ: (np.int16, 1), NFC_IN_IQ_I16: (np.int16, 2)}
 
 
 class NfcError(RuntimeError):
@@ -61,7 +61,8 @@ class NfcContext(object):
 
     # -- input ---------------------------------------------------------------
     def push(self, samples):
-        """Host array: float32 IQ interleaved / complex64, float32 envelope or real, or int16 PCM."""
+        """Host array: float32 IQ interleaved / complex64, float32 envelope or real, int16 PCM, or complex int16 (sc16: I,Q
+        interleaved -- 2n values -- or an (n, 2) array)."""
         dt, per = _KIND_DTYPE[self.input_kind]
         a = np.asarray(samples)
         if a.dtype == np.complex64 and per == 2:
@@ -313,6 +314,34 @@ class PinnedArray(object):
 def device_count():
     """HIP devices this process sees (nfc_device_count; 0 without a GPU)."""
     return int(_lib.load().nfc_device_count())
+
+
+def host_i16_to_float(v, i16_scale=0.0):
+    """int16 -> float32 as the kernels convert it (threshold.hip.h: i16_to_float): 0 -> fl(v / 32767), > 0 -> fl(v * i16_scale)."""
+    v = np.asarray(v).astype(np.float32)
+    if i16_scale > 0:
+        return v * np.float32(i16_scale)
+    return v / np.float32(32767.0)   # (IEEE float32 division: what the kernels' fma form equals for every int16)
+
+
+def host_envelope(x, kind, i16_scale=0.0):
+    """The envelope the kernels compute from a host array of input kind `kind`, as a numpy float32 copy (one value per sample):
+    fl(fl(I*I) + fl(Q*Q)) for the IQ kinds -- complex int16 after converting I and Q as the PCM kind converts a sample --,
+    fl(s*s) for the real kinds, the samples themselves for the envelope kind.  What a time shard's carrier level
+    (sharding.carrier_level) is computed from."""
+    dt, per = _KIND_DTYPE[kind]
+    a = np.asarray(x)
+    if a.dtype == np.complex64 and per == 2:
+        a = a.view(np.float32)
+    a = np.ascontiguousarray(a, dtype=dt).reshape(-1)
+    if kind == NFC_IN_ENV_F32:
+        return a.copy()
+    if kind in (NFC_IN_I16_SQ, NFC_IN_IQ_I16):
+        a = host_i16_to_float(a, i16_scale)
+    if per == 1:
+        return a * a
+    i, q = a[0::2], a[1::2]
+    return (i * i) + (q * q)
 
 
 def host_decode_lut(ptype, cur, d, samp_rate=2e6, max_len=50):

@@ -32,6 +32,10 @@
 #include "../../include/nfc_amd.h"
 #include "scan.hip.h"
 
+#ifndef NFC_HDR_KERNEL_LINKAGE   // (threshold.hip.h: `static` in a second translation unit)
+#define NFC_HDR_KERNEL_LINKAGE
+#endif
+
 namespace nfc {
 
 // carried transition_sink variables (device resident, host mirrored)
@@ -408,7 +412,7 @@ __device__ __forceinline__ void edge_reduce_super(const EdgeArgs &A, size_t nwor
         supers[super] = t;
     }
 }
-__global__ __launch_bounds__(ER_BLOCK) void k_edge_reduce(EdgeArgs A, size_t nwords, EdgeAgg *partials, EdgeAgg *supers) {
+NFC_HDR_KERNEL_LINKAGE __global__ __launch_bounds__(ER_BLOCK) void k_edge_reduce(EdgeArgs A, size_t nwords, EdgeAgg *partials, EdgeAgg *supers) {
     edge_reduce_super(A, nwords, blockIdx.x, partials, supers);
 }
 
@@ -663,7 +667,7 @@ __device__ __forceinline__ void write_edges_tile(const EdgeArgs &A, size_t nword
     }
     TP_DONE(0);   // 5: the stores
 }
-__global__ __launch_bounds__(SCAN_BLOCK) void k_write_edges(EdgeArgs A, size_t nwords, const EdgeAgg *partials, const EdgeAgg *supers, uint32_t *epos,
+NFC_HDR_KERNEL_LINKAGE __global__ __launch_bounds__(SCAN_BLOCK) void k_write_edges(EdgeArgs A, size_t nwords, const EdgeAgg *partials, const EdgeAgg *supers, uint32_t *epos,
                                                            uint16_t *ecode, uint32_t cap, bool own_prefix, uint32_t *total_out,
                                                            Last2 *last2_total, EdgeCarry *carry_out) {
     write_edges_tile(A, nwords, partials, supers, epos, ecode, cap, own_prefix, total_out, last2_total, carry_out, blockIdx.x, gridDim.x);

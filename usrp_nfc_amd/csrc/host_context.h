@@ -371,6 +371,24 @@ int batch_ok(nfc_ctx *c, bool with_mirror) {
         if (int rc__ = batch_ok((c), (with_mirror))) return rc__;  \
     } while (0)
 
+// The threshold-stage kernels of an input kind.  The complex int16 kind's live in a translation unit of their own (nfc_iq16.hip):
+// nfc_amd.hip reaches them by pointer (iq16.h) and instantiates none of them.
+template <int KIND, bool GRING>
+ThrKernel thr_kern() {
+    if constexpr (KIND == IN_IQ_I16) return iq16::threshold_kernel(GRING);
+    else return k_threshold<KIND, 4, GRING>;
+}
+template <int KIND, bool BLK16>
+ThrKernel lean_kern() {
+    if constexpr (KIND == IN_IQ_I16) return iq16::lean_kernel(BLK16);
+    else return k_threshold_lean<KIND, 4, BLK16>;
+}
+template <int KIND, int NR, bool EX = false>
+ThrKernel wg_kern() {
+    if constexpr (KIND == IN_IQ_I16) return EX ? iq16::wg_ex_kernel() : iq16::wg_kernel(NR);
+    else return k_threshold_wg<KIND, NR, EX>;
+}
+
 // Timed launches (nfc_set_timing >= 1) hand the kernel its own start / stop events (hipExtLaunchKernelGGL): the
 // events take the kernel's begin and end, not the position of a marker in the stream, so they neither measure nor add
 // inter-launch gaps.
@@ -379,13 +397,9 @@ void launch_threshold(nfc_ctx *c, const ThrArgs &A, uint32_t nwork, hipEvent_t e
     const uint32_t wpb = c->gring ? 4u : (uint32_t)c->wpb;
     const uint32_t blocks = (nwork + wpb - 1) / wpb;
     const size_t lds = c->gring ? 0 : (size_t)wpb * c->Lpad * c->lds_per_slot;
-    if (e0) {
-        if (c->gring) NFC_LAUNCH_EXT((k_threshold<KIND, 4, true>), dim3(blocks), dim3(64 * wpb), lds, c->st, e0, e1, 0, A);
-        else NFC_LAUNCH_EXT((k_threshold<KIND, 4, false>), dim3(blocks), dim3(64 * wpb), lds, c->st, e0, e1, 0, A);
-        return;
-    }
-    if (c->gring) NFC_LAUNCH((k_threshold<KIND, 4, true>), dim3(blocks), dim3(64 * wpb), lds, c->st, A);
-    else NFC_LAUNCH((k_threshold<KIND, 4, false>), dim3(blocks), dim3(64 * wpb), lds, c->st, A);
+    const ThrKernel kern = c->gring ? thr_kern<KIND, true>() : thr_kern<KIND, false>();
+    if (e0) NFC_LAUNCH_EXT(kern, dim3(blocks), dim3(64 * wpb), lds, c->st, e0, e1, 0, A);
+    else NFC_LAUNCH(kern, dim3(blocks), dim3(64 * wpb), lds, c->st, A);
 }
 // Pass 0 with the LDS ring: the lean optimistic kernel (threshold_lean.hip.h); chunks it gives up on are re-run by k_threshold.
 // ... or, where it applies, with a chunk per workgroup (threshold_wg.hip.h)
@@ -412,19 +426,21 @@ void launch_wg(nfc_ctx *c, const ThrArgs &A, uint32_t nwork, hipEvent_t e0, hipE
         if (e0) NFC_LAUNCH_EXT(kern, dim3(nwork), dim3(256), lds, c->st, e0, e1, 0, B);
         else NFC_LAUNCH(kern, dim3(nwork), dim3(256), lds, c->st, B);
     };
-    if (c->wg_ex_launch) return go(k_threshold_wg<KIND, 4, true>);
+    if (c->wg_ex_launch) return go(wg_kern<KIND, 4, true>());
 #ifdef NFC_TEST_HOOKS
-    if (c->wg_flags) {   // (NFC_WG_FLAGS=1: per-wave counters instead of a round's first barrier -- built and measured, threshold_wg.hip.h)
-        if constexpr (KIND == IN_IQ_F32 || KIND == IN_ENV_F32) {
-            if (c->wg_nr == 8) return go(k_threshold_wg<KIND, 8, false, true>);
+    if constexpr (KIND != IN_IQ_I16) {   // (not instantiated for the complex int16 kind: nfc_create leaves wg_flags 0 for it)
+        if (c->wg_flags) {   // (NFC_WG_FLAGS=1: per-wave counters instead of a round's first barrier -- built and measured, threshold_wg.hip.h)
+            if constexpr (KIND == IN_IQ_F32 || KIND == IN_ENV_F32) {
+                if (c->wg_nr == 8) return go(k_threshold_wg<KIND, 8, false, true>);
+            }
+            return go(k_threshold_wg<KIND, 4, false, true>);
         }
-        return go(k_threshold_wg<KIND, 4, false, true>);
     }
 #endif
-    if constexpr (KIND == IN_IQ_F32 || KIND == IN_ENV_F32) {   // (the kinds eight rows per step are instantiated for: nfc_create chooses wg_nr)
-        if (c->wg_nr == 8) return go(k_threshold_wg<KIND, 8>);
+    if constexpr (KIND == IN_IQ_F32 || KIND == IN_ENV_F32 || KIND == IN_IQ_I16) {   // (the kinds eight rows per step are instantiated for: nfc_create chooses wg_nr)
+        if (c->wg_nr == 8) return go(wg_kern<KIND, 8>());
     }
-    go(k_threshold_wg<KIND, 4>);
+    go(wg_kern<KIND, 4>());
 }
 template <int KIND>
 void launch_lean(nfc_ctx *c, const ThrArgs &A, uint32_t nwork, hipEvent_t e0, hipEvent_t e1) {
@@ -438,8 +454,8 @@ void launch_lean(nfc_ctx *c, const ThrArgs &A, uint32_t nwork, hipEvent_t e0, hi
         else NFC_LAUNCH(kern, dim3(blocks), dim3(64 * wpb), lds, c->st, A);
     };
     const bool b16 = (1 << c->nfold) == 16;
-    if (b16) go(k_threshold_lean<KIND, 4, true>);
-    else go(k_threshold_lean<KIND, 4, false>);
+    if (b16) go(lean_kern<KIND, true>());
+    else go(lean_kern<KIND, false>());
 }
 void launch_threshold_kind(nfc_ctx *c, const ThrArgs &A, uint32_t nwork, bool lean = false, hipEvent_t *own_events = nullptr) {
     const bool timed = !own_events && c->timing >= 1 && c->n_kev < 6;
@@ -454,6 +470,7 @@ void launch_threshold_kind(nfc_ctx *c, const ThrArgs &A, uint32_t nwork, bool le
         case NFC_IN_IQ_F32: launch_lean<IN_IQ_F32>(c, A, nwork, e0, e1); break;
         case NFC_IN_ENV_F32: launch_lean<IN_ENV_F32>(c, A, nwork, e0, e1); break;
         case NFC_IN_REAL_F32_SQ: launch_lean<IN_REAL_F32_SQ>(c, A, nwork, e0, e1); break;
+        case NFC_IN_IQ_I16: launch_lean<IN_IQ_I16>(c, A, nwork, e0, e1); break;
         default: launch_lean<IN_I16_SQ>(c, A, nwork, e0, e1); break;
         }
         return;
@@ -462,6 +479,7 @@ void launch_threshold_kind(nfc_ctx *c, const ThrArgs &A, uint32_t nwork, bool le
     case NFC_IN_IQ_F32: launch_threshold<IN_IQ_F32>(c, A, nwork, e0, e1); break;
     case NFC_IN_ENV_F32: launch_threshold<IN_ENV_F32>(c, A, nwork, e0, e1); break;
     case NFC_IN_REAL_F32_SQ: launch_threshold<IN_REAL_F32_SQ>(c, A, nwork, e0, e1); break;
+    case NFC_IN_IQ_I16: launch_threshold<IN_IQ_I16>(c, A, nwork, e0, e1); break;
     default: launch_threshold<IN_I16_SQ>(c, A, nwork, e0, e1); break;
     }
 }
@@ -495,6 +513,11 @@ void launch_fill_kind(nfc_ctx *c, const void *in, uint32_t n, int nchunks, int r
     case NFC_IN_IQ_F32: NFC_LAUNCH((k_fill<IN_IQ_F32>), dim3(1), dim3(FILL_BLOCK), (size_t)c->Lpad * 4, c->st, in, n, c->i16_scale, c->L, ring, cr, eci, ver, nchunks, sum, init, &((DevState *)c->d_state.p)->seq[0], c->batch_seq, fresh); break;
     case NFC_IN_ENV_F32: NFC_LAUNCH((k_fill<IN_ENV_F32>), dim3(1), dim3(FILL_BLOCK), (size_t)c->Lpad * 4, c->st, in, n, c->i16_scale, c->L, ring, cr, eci, ver, nchunks, sum, init, &((DevState *)c->d_state.p)->seq[0], c->batch_seq, fresh); break;
     case NFC_IN_REAL_F32_SQ: NFC_LAUNCH((k_fill<IN_REAL_F32_SQ>), dim3(1), dim3(FILL_BLOCK), (size_t)c->Lpad * 4, c->st, in, n, c->i16_scale, c->L, ring, cr, eci, ver, nchunks, sum, init, &((DevState *)c->d_state.p)->seq[0], c->batch_seq, fresh); break;
+    case NFC_IN_IQ_I16: {
+        const FillKernel kf = iq16::fill_kernel();
+        NFC_LAUNCH(kf, dim3(1), dim3(FILL_BLOCK), (size_t)c->Lpad * 4, c->st, in, n, c->i16_scale, c->L, ring, cr, eci, ver, nchunks, sum, init, &((DevState *)c->d_state.p)->seq[0], c->batch_seq, fresh);
+        break;
+    }
     default: NFC_LAUNCH((k_fill<IN_I16_SQ>), dim3(1), dim3(FILL_BLOCK), (size_t)c->Lpad * 4, c->st, in, n, c->i16_scale, c->L, ring, cr, eci, ver, nchunks, sum, init, &((DevState *)c->d_state.p)->seq[0], c->batch_seq, fresh); break;
     }
 }
@@ -503,6 +526,11 @@ void launch_seq_kind(nfc_ctx *c, const SeqArgs &A) {
     case NFC_IN_IQ_F32: NFC_LAUNCH((k_threshold_seq<IN_IQ_F32>), dim3(1), dim3(64), 0, c->st, A); break;
     case NFC_IN_ENV_F32: NFC_LAUNCH((k_threshold_seq<IN_ENV_F32>), dim3(1), dim3(64), 0, c->st, A); break;
     case NFC_IN_REAL_F32_SQ: NFC_LAUNCH((k_threshold_seq<IN_REAL_F32_SQ>), dim3(1), dim3(64), 0, c->st, A); break;
+    case NFC_IN_IQ_I16: {
+        const SeqKernel ks = iq16::seq_kernel();
+        NFC_LAUNCH(ks, dim3(1), dim3(64), 0, c->st, A);
+        break;
+    }
     default: NFC_LAUNCH((k_threshold_seq<IN_I16_SQ>), dim3(1), dim3(64), 0, c->st, A); break;
     }
 }

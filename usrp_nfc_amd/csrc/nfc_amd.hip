@@ -50,6 +50,7 @@
 #endif
 #include "threshold_lean.hip.h"
 #include "threshold_wg.hip.h"
+#include "iq16.h"   // (the complex int16 kind's kernels: nfc_iq16.hip)
 #include "tx.hip.h"
 
 using namespace nfc;
@@ -70,6 +71,7 @@ const void *wg_ex_kernel_of(int kind) {
     case NFC_IN_IQ_F32: return (const void *)k_threshold_wg<IN_IQ_F32, 4, true>;
     case NFC_IN_ENV_F32: return (const void *)k_threshold_wg<IN_ENV_F32, 4, true>;
     case NFC_IN_REAL_F32_SQ: return (const void *)k_threshold_wg<IN_REAL_F32_SQ, 4, true>;
+    case NFC_IN_IQ_I16: return (const void *)iq16::wg_ex_kernel();
     default: return (const void *)k_threshold_wg<IN_I16_SQ, 4, true>;
     }
 }
@@ -79,17 +81,20 @@ const void *wg_flags_kernel_of(int kind, int nr) {
     case NFC_IN_IQ_F32: return nr == 8 ? (const void *)k_threshold_wg<IN_IQ_F32, 8, false, true> : (const void *)k_threshold_wg<IN_IQ_F32, 4, false, true>;
     case NFC_IN_ENV_F32: return nr == 8 ? (const void *)k_threshold_wg<IN_ENV_F32, 8, false, true> : (const void *)k_threshold_wg<IN_ENV_F32, 4, false, true>;
     case NFC_IN_REAL_F32_SQ: return (const void *)k_threshold_wg<IN_REAL_F32_SQ, 4, false, true>;
+    case NFC_IN_IQ_I16: return nullptr;   // (no such form of the complex int16 kind: nfc_create never asks for it, see wg_flags)
     default: return (const void *)k_threshold_wg<IN_I16_SQ, 4, false, true>;
     }
 }
 #endif
 const void *wg_kernel_of(int kind, int nr) {
     // (six instantiations for pass 0: four rows per step for every input kind, eight for the two kinds a long-window capture arrives in;
-    // wg_ex_kernel_of above: the four that re-run chunks with failed rounds evaluated in place)
+    // wg_ex_kernel_of above: the four that re-run chunks with failed rounds evaluated in place.  The complex int16 kind's three --
+    // four and eight rows, the re-run form -- are nfc_iq16.hip's)
     switch (kind) {
     case NFC_IN_IQ_F32: return nr == 8 ? (const void *)k_threshold_wg<IN_IQ_F32, 8> : (const void *)k_threshold_wg<IN_IQ_F32, 4>;
     case NFC_IN_ENV_F32: return nr == 8 ? (const void *)k_threshold_wg<IN_ENV_F32, 8> : (const void *)k_threshold_wg<IN_ENV_F32, 4>;
     case NFC_IN_REAL_F32_SQ: return (const void *)k_threshold_wg<IN_REAL_F32_SQ, 4>;
+    case NFC_IN_IQ_I16: return (const void *)iq16::wg_kernel(nr);
     default: return (const void *)k_threshold_wg<IN_I16_SQ, 4>;
     }
 }
@@ -125,7 +130,10 @@ int nfc_create(const nfc_params *p, nfc_ctx **out) {
     if (!(p->samp_rate > 0)) return fail(nullptr, NFC_ERR_ARG, "samp_rate must be positive");
     if (p->av_window < 1 || p->av_window > 30000) return fail(nullptr, NFC_ERR_ARG, "av_window must be in [1, 30000]");
     if (p->max_len < 1 || p->max_len > 4000) return fail(nullptr, NFC_ERR_ARG, "max_len must be in [1, 4000]");
-    if (p->input_kind < 0 || p->input_kind > 3) return fail(nullptr, NFC_ERR_ARG, "unknown input_kind");
+    if (p->input_kind < 0 || p->input_kind > 4) return fail(nullptr, NFC_ERR_ARG, "unknown input_kind");
+    // (complex int16: |I|, |Q| <= 2^15, so the envelope 2 (2^15 s)^2 stays finite -- and the kernels need no guard for it -- up to s = 2^48)
+    if (p->input_kind == NFC_IN_IQ_I16 && p->i16_scale > 281474976710656.0f)
+        return fail(nullptr, NFC_ERR_ARG, "i16_scale must be at most 2^48 for complex int16 input");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(nullptr, NFC_ERR_DEVICE, "no HIP device: this library has no CPU fallback");
@@ -233,7 +241,7 @@ int nfc_create(const nfc_params *p, nfc_ctx **out) {
     c->eps = 0.01f;  // certification margin of the speculative pass, relative to the window sum
     if (const char *e = NFC_ENV("NFC_EPS")) c->eps = (float)atof(e);
     c->i16_scale = p->i16_scale > 0.f ? p->i16_scale : -1.0f;   // (0: GNU Radio's wavfile_source normalisation, sample / 32767; threshold.hip.h: i16_to_float)
-    static const size_t bps[4] = {8, 4, 4, 2};
+    static const size_t bps[5] = {8, 4, 4, 2, 4};
     c->in_bytes_per_sample = bps[p->input_kind];
     memset(&c->h_carry, 0, sizeof c->h_carry);
     c->h_carry.ss_emin = 255;
@@ -278,9 +286,9 @@ int nfc_create(const nfc_params *p, nfc_ctx **out) {
         c->wg_lds_base = (size_t)c->Lpad * 4 + WG_SHARED_BYTES;
         // rows per step: eight where that leaves a superstep of at least two rounds within 0.8 windows (measured: at av_window 10000
         // eight rows gain 2 % over four; at 2000 more rows with one-round supersteps lose to four rows with two), else four; a round
-        // (four steps) must fit the window, max_len must lie within one step.  Eight rows are instantiated for fc32 IQ and the
+        // (four steps) must fit the window, max_len must lie within one step.  Eight rows are instantiated for fc32 and sc16 IQ and the
         // float32 envelope -- what a capture at a rate that wants such a window arrives as.
-        const bool nr8_kind = p->input_kind == NFC_IN_IQ_F32 || p->input_kind == NFC_IN_ENV_F32;
+        const bool nr8_kind = p->input_kind == NFC_IN_IQ_F32 || p->input_kind == NFC_IN_ENV_F32 || p->input_kind == NFC_IN_IQ_I16;
         c->wg_nr = (nr8_kind && 0.8 * c->L / (double)wg_round_samples(8) >= 1.5) ? 8 : 4;
         if (const char *e = NFC_ENV("NFC_WG_NR")) {
             const int v = atoi(e);
@@ -292,8 +300,12 @@ int nfc_create(const nfc_params *p, nfc_ctx **out) {
         if (c->wg_ok) {
             const void *kern = wg_kernel_of(p->input_kind, c->wg_nr);
 #ifdef NFC_TEST_HOOKS
-            if (const char *e = getenv("NFC_WG_FLAGS")) c->wg_flags = atoi(e) != 0;
+            if (const char *e = getenv("NFC_WG_FLAGS")) c->wg_flags = atoi(e) != 0 && p->input_kind != NFC_IN_IQ_I16;   // (no such form of the complex int16 kind)
             if (c->wg_flags) kern = wg_flags_kernel_of(p->input_kind, c->wg_nr);
+            if (!kern) {
+                nfc_destroy(c);
+                return fail(nullptr, NFC_ERR_INTERNAL, "no workgroup kernel for input kind %d", p->input_kind);
+            }
 #endif
             if (c->wg_lds > 64 * 1024) CRT(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->wg_lds));
             int per_cu_wg = 0;
@@ -387,6 +399,9 @@ int nfc_create(const nfc_params *p, nfc_ctx **out) {
         CRT(hipFuncSetAttribute((const void *)k_threshold_lean<IN_REAL_F32_SQ, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         CRT(hipFuncSetAttribute((const void *)k_threshold_lean<IN_I16_SQ, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         CRT(hipFuncSetAttribute((const void *)k_threshold_lean<IN_I16_SQ, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        CRT(hipFuncSetAttribute((const void *)iq16::threshold_kernel(false), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        CRT(hipFuncSetAttribute((const void *)iq16::lean_kernel(true), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        CRT(hipFuncSetAttribute((const void *)iq16::lean_kernel(false), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     }
     // decoder LUTs
     DecoderTables t = build_tables(p->samp_rate, c->mx);

@@ -22,7 +22,10 @@ namespace nfc {
 #ifdef NFC_TAIL_PROF
 // (a profiling build: s_memtime stamps of every workgroup's thread 0, [kernel][workgroup][stamp]; read by nfc_debug_tail_prof)
 constexpr int TP_WGS = 4096;
-__device__ unsigned long long g_tail_prof[4 * TP_WGS * 8];
+#ifndef NFC_HDR_KERNEL_LINKAGE   // (threshold.hip.h: `static` in a second translation unit)
+#define NFC_HDR_KERNEL_LINKAGE
+#endif
+NFC_HDR_KERNEL_LINKAGE __device__ unsigned long long g_tail_prof[4 * TP_WGS * 8];
 #define TP_DECL() unsigned long long tp_t[8]; int tp_n = 0; tp_t[tp_n++] = clock64()
 #define TP_MARK() tp_t[tp_n++] = clock64()
 #define TP_DONE(slot)                                                                                             \

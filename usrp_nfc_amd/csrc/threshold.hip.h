@@ -40,7 +40,14 @@ constexpr int LL_NONE = -(1 << 30);  // "no such sample" (batch-local index)
 constexpr int MAX_FIX_ITERS = 80;
 constexpr float RND_SUM = 2.44140625e-04f;   // 2^-12: margin for the accumulated rounding of the f32 running sum
 
-enum : int { IN_IQ_F32 = 0, IN_ENV_F32 = 1, IN_REAL_F32_SQ = 2, IN_I16_SQ = 3 };
+enum : int { IN_IQ_F32 = 0, IN_ENV_F32 = 1, IN_REAL_F32_SQ = 2, IN_I16_SQ = 3, IN_IQ_I16 = 4 };
+
+// The non-template kernels of these headers (and the profiling builds' __device__ counters) are defined once, in nfc_amd.hip; a
+// second translation unit that includes the headers for kernel templates of its own (nfc_iq16.hip) defines this as `static`, so that
+// its copies stay its own -- the nfc_debug_* readers see nfc_amd.hip's.
+#ifndef NFC_HDR_KERNEL_LINKAGE
+#define NFC_HDR_KERNEL_LINKAGE
+#endif
 
 // Carried stream state (device resident; mirrored to the host after each batch).
 struct Carry {
@@ -277,6 +284,23 @@ __host__ __device__ __forceinline__ float i16_to_float(int v, float i16_scale) {
     return (float)v * i16_scale;
 }
 
+// Complex int16 (sc16: I in the low half of the dword, Q in the high half -- std::complex<int16_t>, UHD's sc16 host buffers):
+// both halves converted as the PCM kind converts a sample, THEN the fc32 kind's envelope of the pair, x = fl(fl(I*I) + fl(Q*Q)).
+// The pair goes through packed f32 arithmetic (v_pk_mul_f32 / v_pk_fma_f32: each half rounds as the scalar op does), the two
+// sign-extending conversions take the halves straight out of the dword.
+typedef float iq16_f2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ float iq16_env(uint32_t w, float i16_scale) {
+    iq16_f2 v = {(float)(int)(int16_t)(w & 0xFFFFu), (float)((int)w >> 16)};
+    if (i16_scale < 0.f) {   // i16_to_float's default: fl(v / 32767) as fma(v', 2^-15 + 2^-30, v'), v' = v * 2^-15
+        const iq16_f2 vp = v * 3.0517578125e-05f;
+        v = __builtin_elementwise_fma(vp, (iq16_f2)(3.0517578125e-05f + 9.31322574615478515625e-10f), vp);
+    } else {
+        v = v * i16_scale;
+    }
+    const iq16_f2 sq = v * v;
+    return sq.x + sq.y;
+}
+
 // Envelope of one sample (gnuradio complex_to_mag_squared; compiled with
 // -ffp-contract=off so the products and the sum round separately).
 template <int KIND>
@@ -290,6 +314,8 @@ __device__ __forceinline__ float envelope_at(const void *in, size_t m, float i16
     } else if (KIND == IN_REAL_F32_SQ) {
         const float s = ((const float *)in)[m];
         return s * s;
+    } else if (KIND == IN_IQ_I16) {
+        return iq16_env(((const uint32_t *)in)[m], i16_scale);
     } else {
         const float s = i16_to_float((int)((const int16_t *)in)[m], i16_scale);
         return s * s;
@@ -301,6 +327,7 @@ __device__ __forceinline__ float envelope_at(const void *in, size_t m, float i16
 template <int KIND> struct RawOf { using T = float; };
 template <> struct RawOf<IN_IQ_F32> { using T = float2; };
 template <> struct RawOf<IN_I16_SQ> { using T = int16_t; };
+template <> struct RawOf<IN_IQ_I16> { using T = uint32_t; };   // (the I,Q pair as one dword)
 template <int KIND>
 __device__ __forceinline__ typename RawOf<KIND>::T load_raw(const void *in, size_t m) {
     return ((const typename RawOf<KIND>::T *)in)[m];
@@ -314,6 +341,8 @@ __device__ __forceinline__ float env_of(typename RawOf<KIND>::T v, float i16_sca
         return v;
     } else if constexpr (KIND == IN_REAL_F32_SQ) {
         return v * v;
+    } else if constexpr (KIND == IN_IQ_I16) {
+        return iq16_env(v, i16_scale);
     } else {
         const float s = i16_to_float((int)v, i16_scale);
         return s * s;
@@ -323,6 +352,7 @@ template <int KIND>
 __device__ __forceinline__ typename RawOf<KIND>::T raw_zero() {
     if constexpr (KIND == IN_IQ_F32) return make_float2(0.f, 0.f);
     else if constexpr (KIND == IN_I16_SQ) return (int16_t)0;
+    else if constexpr (KIND == IN_IQ_I16) return 0u;
     else return 0.f;
 }
 
@@ -384,7 +414,7 @@ __device__ __forceinline__ float resolve_slot(const ThrArgs &A, int c, int s, bo
 }
 
 #ifdef NFC_GEN_PROF
-__device__ unsigned long long g_row_iters[2];   // (a profiling build: rows walked by row_exact, iterations they took)
+NFC_HDR_KERNEL_LINKAGE __device__ unsigned long long g_row_iters[2];   // (a profiling build: rows walked by row_exact, iterations they took)
 #endif
 // One 64-sample row (lane l = sample m), exact: iterate the accept mask to its fixed point.
 // Updates ss0, w_nl, w_kl; returns the classification through low/pos ballots.
@@ -667,7 +697,7 @@ __device__ __forceinline__ void chunk_publish(const ThrArgs &A, uint32_t c, int 
 // GRING: the ring lives in global memory (one row of A.gring per chunk) instead of LDS -- for windows whose LDS ring would
 // leave a SIMD with one or two waves; its old values are then asked for one step ahead, like the input.
 #ifdef NFC_GEN_PROF
-__device__ unsigned long long g_gen_prof[8192 * 8];
+NFC_HDR_KERNEL_LINKAGE __device__ unsigned long long g_gen_prof[8192 * 8];   // (nfc_iq16.hip's kernels count into that unit's own copy, which nfc_debug_gen_prof does not read)
 #define GP_T() clock64()
 #else
 #define GP_T() 0ull
@@ -1297,7 +1327,7 @@ struct CertLaunch {
 
 // the certification's grid: a workgroup per pending chunk, and one more that resolves the end-of-batch state
 inline uint32_t cert_grid(uint32_t pending) { return pending + 1u; }
-__global__ __launch_bounds__(256) void k_certify(ThrArgs A, uint8_t *cert, CertInfo *dbg, float *ring_next, Carry *carry,
+NFC_HDR_KERNEL_LINKAGE __global__ __launch_bounds__(256) void k_certify(ThrArgs A, uint8_t *cert, CertInfo *dbg, float *ring_next, Carry *carry,
                                                  CertSummary *sum) {
     // (the workgroup that resolves the end-of-batch state -- one chain of look-backs, as long as the rest of the launch is wide -- goes first)
     const uint32_t nb = gridDim.x, bid = ring_next ? (blockIdx.x == 0 ? nb - 1u : blockIdx.x - 1u) : blockIdx.x;
@@ -1559,7 +1589,7 @@ __global__ __launch_bounds__(FILL_BLOCK) void k_fill(const void *in, uint32_t n,
 
 // After the passes converged: the ring at the end of the batch (look-back over all
 // chunks) and its sum become the carried state.
-__global__ __launch_bounds__(FIN_BLOCK) void k_finalize_state(ThrArgs A, float *ring_next, Carry *carry) {
+NFC_HDR_KERNEL_LINKAGE __global__ __launch_bounds__(FIN_BLOCK) void k_finalize_state(ThrArgs A, float *ring_next, Carry *carry) {
     finalize_state(A, ring_next, carry, nullptr);
 }
 

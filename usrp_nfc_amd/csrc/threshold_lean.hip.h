@@ -113,6 +113,8 @@ __device__ __forceinline__ void lean_take(float (&x)[4], float i16_scale) {
             if constexpr (KIND == IN_I16_SQ) {
                 const float sv = i16_to_float(__float_as_int(w[j]), i16_scale);   // (global_load_sshort sign-extends into the register)
                 x[j] = sv * sv;
+            } else if constexpr (KIND == IN_IQ_I16) {
+                x[j] = iq16_env(__float_as_uint(w[j]), i16_scale);   // (one dword: I low, Q high -- the loads of the 4-byte kinds)
             } else if constexpr (KIND == IN_ENV_F32) {
                 x[j] = w[j];          // the envelope itself (what transition_sink.work receives, transition_sink.py:13-18)
             } else {
@@ -121,7 +123,7 @@ __device__ __forceinline__ void lean_take(float (&x)[4], float i16_scale) {
         }
     }
 }
-template <int KIND> struct LeanRaw { static constexpr int BYTES = (KIND == IN_IQ_F32) ? 8 : (KIND == IN_I16_SQ) ? 2 : 4; };
+template <int KIND> struct LeanRaw { static constexpr int BYTES = (KIND == IN_IQ_F32) ? 8 : (KIND == IN_I16_SQ) ? 2 : 4; };   // (IN_IQ_I16: 4, an I,Q pair of int16)
 typedef __attribute__((address_space(3))) float lean_lds_f;
 typedef __attribute__((address_space(1))) uint32_t lean_g_u32;   // (an address computed from integers must not become a flat access)
 typedef uint32_t lean_u32x4 __attribute__((ext_vector_type(4)));

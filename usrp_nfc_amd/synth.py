@@ -248,3 +248,10 @@ def envelope_f32(iq):
     i = iq[0::2]
     q = iq[1::2]
     return (i * i) + (q * q)
+
+
+def quantise_sc16(iq, full_scale=32767.0):
+    """Interleaved float32 IQ -> complex int16 (sc16) as a radio's ADC path would deliver it: round to nearest (ties to even),
+    clip to the int16 range.  full_scale: the int16 value of 1.0 (the carrier of these workloads has amplitude 0.5)."""
+    v = np.rint(np.asarray(iq, np.float64) * float(full_scale))
+    return np.clip(v, -32768, 32767).astype(np.int16)

@@ -42,7 +42,9 @@ class transition_sink(_Base):
 
     def __init__(self, samp_rate, callback, lo_val=0.1, hi_val=1.1, av_window=2000, max_len=50,
                  batch=1 << 22, device=0, input_kind=api.NFC_IN_ENV_F32, i16_scale=0.0, flush_ms=50.0, flush_calls=0):
-        _Base.__init__(self, name="transition_sink", in_sig=[numpy.float32 if input_kind != api.NFC_IN_I16_SQ else numpy.int16], out_sig=None)
+        # (complex int16: 4-byte items of two int16, what uhd.usrp_source emits with cpu_format="sc16")
+        sig = {api.NFC_IN_I16_SQ: numpy.int16, api.NFC_IN_IQ_I16: (numpy.int16, 2)}.get(input_kind, numpy.float32)
+        _Base.__init__(self, name="transition_sink", in_sig=[sig], out_sig=None)
         self._callback = callback
         self._batch = max(1, int(batch))
         self._flush_s = float(flush_ms) * 1e-3 if flush_ms else 0.0
@@ -51,7 +53,8 @@ class transition_sink(_Base):
         self._nbuf = 0
         self._ncalls = 0
         self._t_last = time.monotonic()
-        self._dtype = numpy.int16 if input_kind == api.NFC_IN_I16_SQ else numpy.float32
+        self._dtype = numpy.int16 if input_kind in (api.NFC_IN_I16_SQ, api.NFC_IN_IQ_I16) else numpy.float32
+        self._per = 2 if input_kind == api.NFC_IN_IQ_I16 else 1   # values per sample (an item)
         back = getattr(callback, '__self__', None)
         self._back = back if hasattr(back, '_deliver') else None
         if self._back is not None:
@@ -66,16 +69,17 @@ class transition_sink(_Base):
     # GNU Radio gateway contract (transition_sink.py:37-39, 107, 125)
     def work(self, input_items, output_items):
         a = numpy.asarray(input_items[0], dtype=self._dtype)
-        if a.size:
-            self._buf.append(a.copy())
-            self._nbuf += a.size
+        n = a.size // self._per
+        if n:
+            self._buf.append(a.reshape(-1).copy())
+            self._nbuf += n
             self._ncalls += 1
             if (self._nbuf >= self._batch or (self._flush_calls and self._ncalls >= self._flush_calls)
                     or (self._flush_s and time.monotonic() - self._t_last >= self._flush_s)):
                 self.flush()
         elif self._flush_s == 0.0 and self._batch == 1:
             self._callback([])   # the reference calls back on an empty call too (transition_sink.py:101)
-        return int(a.size)
+        return int(n)
 
     def flush(self):
         self._t_last = time.monotonic()
@@ -88,7 +92,7 @@ class transition_sink(_Base):
 
     def push_now(self, x):
         """One batch through the GPU path right away (decoder.run feeds whole pieces of a recording this way)."""
-        self._ctx.push(x)
+        self._ctx.push(x)   # (any layout NfcContext.push takes: complex int16 as 2n values or (n, 2))
         # one callback per batch, even if empty (transition_sink.py:101)
         self._callback(self._ctx.transitions() if self._want_list else [])
         if self._back is not None:
