@@ -49,11 +49,19 @@ typedef enum {
     NFC_IN_ENV_F32 = 1,     /* float32 envelope already computed; x = sample                                    */
     NFC_IN_REAL_F32_SQ = 2, /* float32 real sample, Q = 0; x = fl(s*s)              (wav branch, decoder.py:25-28) */
     NFC_IN_I16_SQ = 3,      /* int16 PCM; s = fl(pcm / 32767) (or fl(pcm * i16_scale)); x = fl(s*s)  (wavfile_source + wav branch) */
-    NFC_IN_IQ_I16 = 4       /* complex int16 (sc16): two little-endian int16 per sample, I first -- std::complex<int16_t>, UHD's sc16
+    NFC_IN_IQ_I16 = 4,      /* complex int16 (sc16): two little-endian int16 per sample, I first -- std::complex<int16_t>, UHD's sc16
                              * host buffers, 4 bytes per sample.  I and Q converted as the PCM kind converts a sample (i16_scale), THEN
                              * x = fl(fl(I*I)+fl(Q*Q)) -- the fc32 kind's envelope of the converted pair, bit for bit.  UHD's own
                              * sc16 -> fc32 conversion (what cpu_format="fc32", usrp_src.py:19-22, runs on the host) is third party
                              * and absent from the reference tree: that scaling is UNPINNED, as wavfile_source's is */
+    NFC_IN_IQ_I8 = 5,       /* complex int8 (sc8): two int8 per sample, I first -- std::complex<int8_t>, a HackRF's only format
+                             * (hackrf_transfer -r, SoapySDR CS8) and UHD's sc8, 2 bytes per sample.  s = fl(q * scale) for I and Q
+                             * each, THEN x = fl(fl(I*I)+fl(Q*Q)) -- the fc32 kind's envelope of the converted pair, bit for bit */
+    NFC_IN_IQ_U8 = 6        /* complex uint8 (cu8): two offset-binary bytes per sample, I first -- what rtl_sdr records, 2 bytes per
+                             * sample.  s = fl((u - 127.5f) * scale) (u - 127.5 is exact), THEN x as for sc8.  The offset is fixed.
+                             * Both 8-bit kinds: scale from i16_scale, see there.  The third-party conversions of such captures --
+                             * UHD's sc8 -> fc32, gr-osmosdr's HackRF source and its RTL-SDR source (which subtracts 127.4) -- are
+                             * absent from the reference tree: they are UNPINNED, as wavfile_source's scaling is */
 } nfc_input_kind;
 
 /* nfc_params.flags */
@@ -76,7 +84,9 @@ typedef struct {
                             * is third party and absent from the reference tree, so this boundary is UNPINNED: SURVEY.md 8c).  > 0: s =
                             * fl((float)pcm * i16_scale) for a source normalised differently (1/32768 is a power of two; 1/32767 is not:
                             * fl(s*s) then rounds differently near the thresholds).  NFC_IN_IQ_I16: at most 2^48 (NFC_ERR_ARG beyond),
-                            * which keeps every envelope finite */
+                            * which keeps every envelope finite.  NFC_IN_IQ_I8 / NFC_IN_IQ_U8 (each of I, Q): a value that is not
+                            * positive means 2^-7 (exact, NOT / 32767); at most 2^56 (NFC_ERR_ARG beyond: |I|, |Q| <= 2^7 scale keeps
+                            * every envelope finite) */
     uint32_t flags;
     int32_t chunk_samples; /* samples per time chunk of the threshold kernel; 0 -> default */
     int32_t reserved;

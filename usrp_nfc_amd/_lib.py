@@ -10,7 +10,7 @@ import numpy as np
 
 from . import build as _build
 
-NFC_IN_IQ_F32, NFC_IN_ENV_F32, NFC_IN_REAL_F32_SQ, NFC_IN_I16_SQ, NFC_IN_IQ_I16 = 0, 1, 2, 3, 4
+NFC_IN_IQ_F32, NFC_IN_ENV_F32, NFC_IN_REAL_F32_SQ, NFC_IN_I16_SQ, NFC_IN_IQ_I16, NFC_IN_IQ_I8, NFC_IN_IQ_U8 = 0, 1, 2, 3, 4, 5, 6
 NFC_FLAG_FORCE_SEQUENTIAL, NFC_FLAG_NO_EDGES = 1, 2
 ABI_VERSION = 4   # NFC_AMD_ABI_VERSION of the header these structures mirror
 

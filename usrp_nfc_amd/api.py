@@ -5,13 +5,15 @@ import numpy as np
 
 from . import _lib
 from ._lib import (EDGE_DTYPE, NFC_FLAG_FORCE_SEQUENTIAL, NFC_FLAG_NO_EDGES, NFC_IN_ENV_F32, NFC_IN_I16_SQ,
-                   NFC_IN_IQ_F32, NFC_IN_IQ_I16, NFC_IN_REAL_F32_SQ, PACKET_DTYPE)
+                   NFC_IN_IQ_F32, NFC_IN_IQ_I8, NFC_IN_IQ_I16, NFC_IN_IQ_U8, NFC_IN_REAL_F32_SQ, PACKET_DTYPE)
 
 __all__ = ['NfcContext', 'NfcError', 'DeviceBuffer', 'host_decode_lut', 'host_envelope', 'NFC_IN_IQ_F32', 'NFC_IN_ENV_F32',
-           'NFC_IN_REAL_F32_SQ', 'NFC_IN_I16_SQ', 'NFC_IN_IQ_I16', 'NFC_FLAG_FORCE_SEQUENTIAL', 'NFC_FLAG_NO_EDGES']
+           'NFC_IN_REAL_F32_SQ', 'NFC_IN_I16_SQ', 'NFC_IN_IQ_I16', 'NFC_IN_IQ_I8', 'NFC_IN_IQ_U8', 'NFC_FLAG_FORCE_SEQUENTIAL',
+           'NFC_FLAG_NO_EDGES']
 
 _KIND_DTYPE = {NFC_IN_IQ_F32: (np.float32, 2), NFC_IN_ENV_F32: (np.float32, 1),
-               NFC_IN_REAL_F32_SQ: (np.float32, 1), NFC_IN_I16_SQ: (np.int16, 1), NFC_IN_IQ_I16: (np.int16, 2)}
+               NFC_IN_REAL_F32_SQ: (np.float32, 1), NFC_IN_I16_SQ: (np.int16, 1), NFC_IN_IQ_I16: (np.int16, 2),
+               NFC_IN_IQ_I8: (np.int8, 2), NFC_IN_IQ_U8: (np.uint8, 2)}
 
 
 class NfcError(RuntimeError):
@@ -61,8 +63,8 @@ class NfcContext(object):
 
     # -- input ---------------------------------------------------------------
     def push(self, samples):
-        """Host array: float32 IQ interleaved / complex64, float32 envelope or real, int16 PCM, or complex int16 (sc16: I,Q
-        interleaved -- 2n values -- or an (n, 2) array)."""
+        """Host array: float32 IQ interleaved / complex64, float32 envelope or real, int16 PCM, or complex int16 / int8 / uint8
+        (sc16, sc8, cu8: I,Q interleaved -- 2n values -- or an (n, 2) array)."""
         dt, per = _KIND_DTYPE[self.input_kind]
         a = np.asarray(samples)
         if a.dtype == np.complex64 and per == 2:
@@ -324,11 +326,21 @@ def host_i16_to_float(v, i16_scale=0.0):
     return v / np.float32(32767.0)   # (IEEE float32 division: what the kernels' fma form equals for every int16)
 
 
+def host_iq8_to_float(v, kind, scale=0.0):
+    """Complex 8-bit -> float32, I and Q each, as nfc_amd.h defines it: sc8 fl(q * s), cu8 fl((u - 127.5) * s) (u - 127.5 is exact);
+    s = scale where it is positive, else 2^-7."""
+    s = np.float32(scale if scale > 0 else 2.0 ** -7)
+    if kind == NFC_IN_IQ_I8:
+        return np.asarray(v).astype(np.int8).astype(np.float32) * s
+    u = np.asarray(v).astype(np.uint8).astype(np.float32)
+    return (u - np.float32(127.5)) * s
+
+
 def host_envelope(x, kind, i16_scale=0.0):
     """The envelope the kernels compute from a host array of input kind `kind`, as a numpy float32 copy (one value per sample):
-    fl(fl(I*I) + fl(Q*Q)) for the IQ kinds -- complex int16 after converting I and Q as the PCM kind converts a sample --,
-    fl(s*s) for the real kinds, the samples themselves for the envelope kind.  What a time shard's carrier level
-    (sharding.carrier_level) is computed from."""
+    fl(fl(I*I) + fl(Q*Q)) for the IQ kinds -- complex int16 after converting I and Q as the PCM kind converts a sample, complex
+    8-bit after host_iq8_to_float --, fl(s*s) for the real kinds, the samples themselves for the envelope kind.  What a time
+    shard's carrier level (sharding.carrier_level) is computed from."""
     dt, per = _KIND_DTYPE[kind]
     a = np.asarray(x)
     if a.dtype == np.complex64 and per == 2:
@@ -338,6 +350,8 @@ def host_envelope(x, kind, i16_scale=0.0):
         return a.copy()
     if kind in (NFC_IN_I16_SQ, NFC_IN_IQ_I16):
         a = host_i16_to_float(a, i16_scale)
+    if kind in (NFC_IN_IQ_I8, NFC_IN_IQ_U8):
+        a = host_iq8_to_float(a, kind, i16_scale)
     if per == 1:
         return a * a
     i, q = a[0::2], a[1::2]

@@ -144,7 +144,8 @@ struct nfc_ctx {
     bool spin_wait = true;   // a batch's end is seen in the mirror's stamp word, not waited for on the stream (NFC_SPIN_WAIT=0; host_threshold.h)
     uint64_t selmask;
     float eps;               // certification margin of the speculative pass, relative to the window sum (1 %; host_threshold.h: eps_adapt says why it stays there)
-    float i16_scale;
+    float i16_scale;         // the kernels' conversion argument: the int16 kinds' scale, -1 for sample / 32767 (i16_to_float); the complex 8-bit
+                             // kinds' route and scale (iq8_kernel_arg, threshold.hip.h: iq8_env)
     size_t in_bytes_per_sample;
     hipStream_t st = nullptr;
     hipStream_t own_st = nullptr;   // the stream the context created (st may be the caller's: nfc_set_stream)
@@ -371,21 +372,25 @@ int batch_ok(nfc_ctx *c, bool with_mirror) {
         if (int rc__ = batch_ok((c), (with_mirror))) return rc__;  \
     } while (0)
 
-// The threshold-stage kernels of an input kind.  The complex int16 kind's live in a translation unit of their own (nfc_iq16.hip):
-// nfc_amd.hip reaches them by pointer (iq16.h) and instantiates none of them.
+// The threshold-stage kernels of an input kind.  The complex int16 kind's live in a translation unit of their own (nfc_iq16.hip),
+// and so do the complex 8-bit kinds' (nfc_iq8.hip): nfc_amd.hip reaches them by pointer (iq16.h, iq8.h) and instantiates none of them.
+constexpr bool is_iq8(int kind) { return kind == IN_IQ_I8 || kind == IN_IQ_U8; }
 template <int KIND, bool GRING>
 ThrKernel thr_kern() {
     if constexpr (KIND == IN_IQ_I16) return iq16::threshold_kernel(GRING);
+    else if constexpr (is_iq8(KIND)) return iq8::threshold_kernel(KIND, GRING);
     else return k_threshold<KIND, 4, GRING>;
 }
 template <int KIND, bool BLK16>
 ThrKernel lean_kern() {
     if constexpr (KIND == IN_IQ_I16) return iq16::lean_kernel(BLK16);
+    else if constexpr (is_iq8(KIND)) return iq8::lean_kernel(KIND, BLK16);
     else return k_threshold_lean<KIND, 4, BLK16>;
 }
 template <int KIND, int NR, bool EX = false>
 ThrKernel wg_kern() {
     if constexpr (KIND == IN_IQ_I16) return EX ? iq16::wg_ex_kernel() : iq16::wg_kernel(NR);
+    else if constexpr (is_iq8(KIND)) return EX ? iq8::wg_ex_kernel(KIND) : iq8::wg_kernel(KIND, NR);
     else return k_threshold_wg<KIND, NR, EX>;
 }
 
@@ -428,7 +433,7 @@ void launch_wg(nfc_ctx *c, const ThrArgs &A, uint32_t nwork, hipEvent_t e0, hipE
     };
     if (c->wg_ex_launch) return go(wg_kern<KIND, 4, true>());
 #ifdef NFC_TEST_HOOKS
-    if constexpr (KIND != IN_IQ_I16) {   // (not instantiated for the complex int16 kind: nfc_create leaves wg_flags 0 for it)
+    if constexpr (KIND != IN_IQ_I16 && !is_iq8(KIND)) {   // (not instantiated for the complex integer kinds: nfc_create leaves wg_flags 0 for them)
         if (c->wg_flags) {   // (NFC_WG_FLAGS=1: per-wave counters instead of a round's first barrier -- built and measured, threshold_wg.hip.h)
             if constexpr (KIND == IN_IQ_F32 || KIND == IN_ENV_F32) {
                 if (c->wg_nr == 8) return go(k_threshold_wg<KIND, 8, false, true>);
@@ -437,7 +442,7 @@ void launch_wg(nfc_ctx *c, const ThrArgs &A, uint32_t nwork, hipEvent_t e0, hipE
         }
     }
 #endif
-    if constexpr (KIND == IN_IQ_F32 || KIND == IN_ENV_F32 || KIND == IN_IQ_I16) {   // (the kinds eight rows per step are instantiated for: nfc_create chooses wg_nr)
+    if constexpr (KIND == IN_IQ_F32 || KIND == IN_ENV_F32 || KIND == IN_IQ_I16 || is_iq8(KIND)) {   // (the kinds eight rows per step are instantiated for: nfc_create chooses wg_nr)
         if (c->wg_nr == 8) return go(wg_kern<KIND, 8>());
     }
     go(wg_kern<KIND, 4>());
@@ -471,6 +476,8 @@ void launch_threshold_kind(nfc_ctx *c, const ThrArgs &A, uint32_t nwork, bool le
         case NFC_IN_ENV_F32: launch_lean<IN_ENV_F32>(c, A, nwork, e0, e1); break;
         case NFC_IN_REAL_F32_SQ: launch_lean<IN_REAL_F32_SQ>(c, A, nwork, e0, e1); break;
         case NFC_IN_IQ_I16: launch_lean<IN_IQ_I16>(c, A, nwork, e0, e1); break;
+        case NFC_IN_IQ_I8: launch_lean<IN_IQ_I8>(c, A, nwork, e0, e1); break;
+        case NFC_IN_IQ_U8: launch_lean<IN_IQ_U8>(c, A, nwork, e0, e1); break;
         default: launch_lean<IN_I16_SQ>(c, A, nwork, e0, e1); break;
         }
         return;
@@ -480,6 +487,8 @@ void launch_threshold_kind(nfc_ctx *c, const ThrArgs &A, uint32_t nwork, bool le
     case NFC_IN_ENV_F32: launch_threshold<IN_ENV_F32>(c, A, nwork, e0, e1); break;
     case NFC_IN_REAL_F32_SQ: launch_threshold<IN_REAL_F32_SQ>(c, A, nwork, e0, e1); break;
     case NFC_IN_IQ_I16: launch_threshold<IN_IQ_I16>(c, A, nwork, e0, e1); break;
+    case NFC_IN_IQ_I8: launch_threshold<IN_IQ_I8>(c, A, nwork, e0, e1); break;
+    case NFC_IN_IQ_U8: launch_threshold<IN_IQ_U8>(c, A, nwork, e0, e1); break;
     default: launch_threshold<IN_I16_SQ>(c, A, nwork, e0, e1); break;
     }
 }
@@ -518,6 +527,16 @@ void launch_fill_kind(nfc_ctx *c, const void *in, uint32_t n, int nchunks, int r
         NFC_LAUNCH(kf, dim3(1), dim3(FILL_BLOCK), (size_t)c->Lpad * 4, c->st, in, n, c->i16_scale, c->L, ring, cr, eci, ver, nchunks, sum, init, &((DevState *)c->d_state.p)->seq[0], c->batch_seq, fresh);
         break;
     }
+    case NFC_IN_IQ_I8: {
+        const FillKernel kf = iq8::fill_kernel(IN_IQ_I8);
+        NFC_LAUNCH(kf, dim3(1), dim3(FILL_BLOCK), (size_t)c->Lpad * 4, c->st, in, n, c->i16_scale, c->L, ring, cr, eci, ver, nchunks, sum, init, &((DevState *)c->d_state.p)->seq[0], c->batch_seq, fresh);
+        break;
+    }
+    case NFC_IN_IQ_U8: {
+        const FillKernel kf = iq8::fill_kernel(IN_IQ_U8);
+        NFC_LAUNCH(kf, dim3(1), dim3(FILL_BLOCK), (size_t)c->Lpad * 4, c->st, in, n, c->i16_scale, c->L, ring, cr, eci, ver, nchunks, sum, init, &((DevState *)c->d_state.p)->seq[0], c->batch_seq, fresh);
+        break;
+    }
     default: NFC_LAUNCH((k_fill<IN_I16_SQ>), dim3(1), dim3(FILL_BLOCK), (size_t)c->Lpad * 4, c->st, in, n, c->i16_scale, c->L, ring, cr, eci, ver, nchunks, sum, init, &((DevState *)c->d_state.p)->seq[0], c->batch_seq, fresh); break;
     }
 }
@@ -528,6 +547,16 @@ void launch_seq_kind(nfc_ctx *c, const SeqArgs &A) {
     case NFC_IN_REAL_F32_SQ: NFC_LAUNCH((k_threshold_seq<IN_REAL_F32_SQ>), dim3(1), dim3(64), 0, c->st, A); break;
     case NFC_IN_IQ_I16: {
         const SeqKernel ks = iq16::seq_kernel();
+        NFC_LAUNCH(ks, dim3(1), dim3(64), 0, c->st, A);
+        break;
+    }
+    case NFC_IN_IQ_I8: {
+        const SeqKernel ks = iq8::seq_kernel(IN_IQ_I8);
+        NFC_LAUNCH(ks, dim3(1), dim3(64), 0, c->st, A);
+        break;
+    }
+    case NFC_IN_IQ_U8: {
+        const SeqKernel ks = iq8::seq_kernel(IN_IQ_U8);
         NFC_LAUNCH(ks, dim3(1), dim3(64), 0, c->st, A);
         break;
     }

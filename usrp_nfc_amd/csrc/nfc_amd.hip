@@ -51,6 +51,7 @@
 #include "threshold_lean.hip.h"
 #include "threshold_wg.hip.h"
 #include "iq16.h"   // (the complex int16 kind's kernels: nfc_iq16.hip)
+#include "iq8.h"    // (the complex 8-bit kinds' kernels: nfc_iq8.hip)
 #include "tx.hip.h"
 
 using namespace nfc;
@@ -72,6 +73,8 @@ const void *wg_ex_kernel_of(int kind) {
     case NFC_IN_ENV_F32: return (const void *)k_threshold_wg<IN_ENV_F32, 4, true>;
     case NFC_IN_REAL_F32_SQ: return (const void *)k_threshold_wg<IN_REAL_F32_SQ, 4, true>;
     case NFC_IN_IQ_I16: return (const void *)iq16::wg_ex_kernel();
+    case NFC_IN_IQ_I8: return (const void *)iq8::wg_ex_kernel(IN_IQ_I8);
+    case NFC_IN_IQ_U8: return (const void *)iq8::wg_ex_kernel(IN_IQ_U8);
     default: return (const void *)k_threshold_wg<IN_I16_SQ, 4, true>;
     }
 }
@@ -82,6 +85,8 @@ const void *wg_flags_kernel_of(int kind, int nr) {
     case NFC_IN_ENV_F32: return nr == 8 ? (const void *)k_threshold_wg<IN_ENV_F32, 8, false, true> : (const void *)k_threshold_wg<IN_ENV_F32, 4, false, true>;
     case NFC_IN_REAL_F32_SQ: return (const void *)k_threshold_wg<IN_REAL_F32_SQ, 4, false, true>;
     case NFC_IN_IQ_I16: return nullptr;   // (no such form of the complex int16 kind: nfc_create never asks for it, see wg_flags)
+    case NFC_IN_IQ_I8:
+    case NFC_IN_IQ_U8: return nullptr;    // (nor of the complex 8-bit kinds)
     default: return (const void *)k_threshold_wg<IN_I16_SQ, 4, false, true>;
     }
 }
@@ -89,14 +94,28 @@ const void *wg_flags_kernel_of(int kind, int nr) {
 const void *wg_kernel_of(int kind, int nr) {
     // (six instantiations for pass 0: four rows per step for every input kind, eight for the two kinds a long-window capture arrives in;
     // wg_ex_kernel_of above: the four that re-run chunks with failed rounds evaluated in place.  The complex int16 kind's three --
-    // four and eight rows, the re-run form -- are nfc_iq16.hip's)
+    // four and eight rows, the re-run form -- are nfc_iq16.hip's, the complex 8-bit kinds' three each nfc_iq8.hip's)
     switch (kind) {
     case NFC_IN_IQ_F32: return nr == 8 ? (const void *)k_threshold_wg<IN_IQ_F32, 8> : (const void *)k_threshold_wg<IN_IQ_F32, 4>;
     case NFC_IN_ENV_F32: return nr == 8 ? (const void *)k_threshold_wg<IN_ENV_F32, 8> : (const void *)k_threshold_wg<IN_ENV_F32, 4>;
     case NFC_IN_REAL_F32_SQ: return (const void *)k_threshold_wg<IN_REAL_F32_SQ, 4>;
     case NFC_IN_IQ_I16: return (const void *)iq16::wg_kernel(nr);
+    case NFC_IN_IQ_I8: return (const void *)iq8::wg_kernel(IN_IQ_I8, nr);
+    case NFC_IN_IQ_U8: return (const void *)iq8::wg_kernel(IN_IQ_U8, nr);
     default: return (const void *)k_threshold_wg<IN_I16_SQ, 4>;
     }
+}
+// The complex 8-bit kinds' kernel argument (threshold.hip.h: iq8_env).  scale: i16_scale, 2^-7 where it is not positive.  A power of
+// two 2^k takes the integer route, -2^(2k), where every nonzero value of the definition is a normal float: the smallest nonzero square
+// is 2^(2k) (sc8, |q| = 1) or 2^(2k-2) (cu8, |u - 127.5| = 1/2), so k >= -63 (sc8) or k >= -62 (cu8); above, the scale is at most
+// 2^56, and the largest envelope, 2^15 2^(2k), is at most 2^127.  Any other scale takes the float route: the scale itself.
+float iq8_kernel_arg(int kind, float i16_scale) {
+    const float s = i16_scale > 0.f ? i16_scale : 0.0078125f;
+    int e = 0;
+    const float mant = frexpf(s, &e);   // s = mant 2^e, mant in [0.5, 1)
+    const int k = e - 1, kmin = kind == NFC_IN_IQ_I8 ? -63 : -62;
+    if (mant == 0.5f && k >= kmin && k <= 56) return -ldexpf(1.0f, 2 * k);
+    return s;
 }
 }  // namespace
 
@@ -130,10 +149,13 @@ int nfc_create(const nfc_params *p, nfc_ctx **out) {
     if (!(p->samp_rate > 0)) return fail(nullptr, NFC_ERR_ARG, "samp_rate must be positive");
     if (p->av_window < 1 || p->av_window > 30000) return fail(nullptr, NFC_ERR_ARG, "av_window must be in [1, 30000]");
     if (p->max_len < 1 || p->max_len > 4000) return fail(nullptr, NFC_ERR_ARG, "max_len must be in [1, 4000]");
-    if (p->input_kind < 0 || p->input_kind > 4) return fail(nullptr, NFC_ERR_ARG, "unknown input_kind");
+    if (p->input_kind < 0 || p->input_kind > 6) return fail(nullptr, NFC_ERR_ARG, "unknown input_kind");
     // (complex int16: |I|, |Q| <= 2^15, so the envelope 2 (2^15 s)^2 stays finite -- and the kernels need no guard for it -- up to s = 2^48)
     if (p->input_kind == NFC_IN_IQ_I16 && p->i16_scale > 281474976710656.0f)
         return fail(nullptr, NFC_ERR_ARG, "i16_scale must be at most 2^48 for complex int16 input");
+    // (complex 8-bit: |I|, |Q| <= 2^7 s -- sc8's -128, cu8's 127.5 --, so the envelope 2 (2^7 s)^2 stays finite up to s = 2^56)
+    if ((p->input_kind == NFC_IN_IQ_I8 || p->input_kind == NFC_IN_IQ_U8) && p->i16_scale > 72057594037927936.0f)
+        return fail(nullptr, NFC_ERR_ARG, "i16_scale must be at most 2^56 for complex 8-bit input");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(nullptr, NFC_ERR_DEVICE, "no HIP device: this library has no CPU fallback");
@@ -241,7 +263,8 @@ int nfc_create(const nfc_params *p, nfc_ctx **out) {
     c->eps = 0.01f;  // certification margin of the speculative pass, relative to the window sum
     if (const char *e = NFC_ENV("NFC_EPS")) c->eps = (float)atof(e);
     c->i16_scale = p->i16_scale > 0.f ? p->i16_scale : -1.0f;   // (0: GNU Radio's wavfile_source normalisation, sample / 32767; threshold.hip.h: i16_to_float)
-    static const size_t bps[5] = {8, 4, 4, 2, 4};
+    if (p->input_kind == NFC_IN_IQ_I8 || p->input_kind == NFC_IN_IQ_U8) c->i16_scale = iq8_kernel_arg(p->input_kind, p->i16_scale);   // (not the -1 above)
+    static const size_t bps[7] = {8, 4, 4, 2, 4, 2, 2};
     c->in_bytes_per_sample = bps[p->input_kind];
     memset(&c->h_carry, 0, sizeof c->h_carry);
     c->h_carry.ss_emin = 255;
@@ -286,9 +309,10 @@ int nfc_create(const nfc_params *p, nfc_ctx **out) {
         c->wg_lds_base = (size_t)c->Lpad * 4 + WG_SHARED_BYTES;
         // rows per step: eight where that leaves a superstep of at least two rounds within 0.8 windows (measured: at av_window 10000
         // eight rows gain 2 % over four; at 2000 more rows with one-round supersteps lose to four rows with two), else four; a round
-        // (four steps) must fit the window, max_len must lie within one step.  Eight rows are instantiated for fc32 and sc16 IQ and the
-        // float32 envelope -- what a capture at a rate that wants such a window arrives as.
-        const bool nr8_kind = p->input_kind == NFC_IN_IQ_F32 || p->input_kind == NFC_IN_ENV_F32 || p->input_kind == NFC_IN_IQ_I16;
+        // (four steps) must fit the window, max_len must lie within one step.  Eight rows are instantiated for fc32, sc16, sc8 and cu8 IQ
+        // and the float32 envelope -- what a capture at a rate that wants such a window arrives as.
+        const bool nr8_kind = p->input_kind == NFC_IN_IQ_F32 || p->input_kind == NFC_IN_ENV_F32 || p->input_kind == NFC_IN_IQ_I16 ||
+                              p->input_kind == NFC_IN_IQ_I8 || p->input_kind == NFC_IN_IQ_U8;
         c->wg_nr = (nr8_kind && 0.8 * c->L / (double)wg_round_samples(8) >= 1.5) ? 8 : 4;
         if (const char *e = NFC_ENV("NFC_WG_NR")) {
             const int v = atoi(e);
@@ -300,7 +324,8 @@ int nfc_create(const nfc_params *p, nfc_ctx **out) {
         if (c->wg_ok) {
             const void *kern = wg_kernel_of(p->input_kind, c->wg_nr);
 #ifdef NFC_TEST_HOOKS
-            if (const char *e = getenv("NFC_WG_FLAGS")) c->wg_flags = atoi(e) != 0 && p->input_kind != NFC_IN_IQ_I16;   // (no such form of the complex int16 kind)
+            if (const char *e = getenv("NFC_WG_FLAGS"))   // (no such form of the complex integer kinds)
+                c->wg_flags = atoi(e) != 0 && p->input_kind != NFC_IN_IQ_I16 && p->input_kind != NFC_IN_IQ_I8 && p->input_kind != NFC_IN_IQ_U8;
             if (c->wg_flags) kern = wg_flags_kernel_of(p->input_kind, c->wg_nr);
             if (!kern) {
                 nfc_destroy(c);
@@ -402,6 +427,11 @@ int nfc_create(const nfc_params *p, nfc_ctx **out) {
         CRT(hipFuncSetAttribute((const void *)iq16::threshold_kernel(false), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         CRT(hipFuncSetAttribute((const void *)iq16::lean_kernel(true), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         CRT(hipFuncSetAttribute((const void *)iq16::lean_kernel(false), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        for (int k : {IN_IQ_I8, IN_IQ_U8}) {
+            CRT(hipFuncSetAttribute((const void *)iq8::threshold_kernel(k, false), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            CRT(hipFuncSetAttribute((const void *)iq8::lean_kernel(k, true), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            CRT(hipFuncSetAttribute((const void *)iq8::lean_kernel(k, false), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        }
     }
     // decoder LUTs
     DecoderTables t = build_tables(p->samp_rate, c->mx);

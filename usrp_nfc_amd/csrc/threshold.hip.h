@@ -40,7 +40,7 @@ constexpr int LL_NONE = -(1 << 30);  // "no such sample" (batch-local index)
 constexpr int MAX_FIX_ITERS = 80;
 constexpr float RND_SUM = 2.44140625e-04f;   // 2^-12: margin for the accumulated rounding of the f32 running sum
 
-enum : int { IN_IQ_F32 = 0, IN_ENV_F32 = 1, IN_REAL_F32_SQ = 2, IN_I16_SQ = 3, IN_IQ_I16 = 4 };
+enum : int { IN_IQ_F32 = 0, IN_ENV_F32 = 1, IN_REAL_F32_SQ = 2, IN_I16_SQ = 3, IN_IQ_I16 = 4, IN_IQ_I8 = 5, IN_IQ_U8 = 6 };
 
 // The non-template kernels of these headers (and the profiling builds' __device__ counters) are defined once, in nfc_amd.hip; a
 // second translation unit that includes the headers for kernel templates of its own (nfc_iq16.hip) defines this as `static`, so that
@@ -301,6 +301,56 @@ __device__ __forceinline__ float iq16_env(uint32_t w, float i16_scale) {
     return sq.x + sq.y;
 }
 
+// Complex 8-bit IQ (sc8: two int8; cu8: two offset-binary bytes; I in the low byte of the sample's ushort, which the kernels load
+// zero-extended).  The definition (nfc_amd.h): s = fl(q * scale) (sc8) or s = fl((u - 127.5f) * scale) (cu8), I and Q each, THEN
+// the fc32 kind's x = fl(fl(I*I) + fl(Q*Q)).  The kernels' argument (the i16_scale of ThrArgs / SeqArgs / k_fill; nfc_create:
+// iq8_kernel_arg) chooses one of two routes for a whole launch -- a uniform branch:
+//  * arg > 0, the float route: arg is the scale, and the definition is computed step by step (packed f32, as iq16_env).
+//  * arg < 0, the integer route, for a scale 2^k with every nonzero value of the definition a normal float: -arg = 2^(2k).  Then
+//    I, Q, their squares and the sum are exact, and x is an exact multiple of 2^(2k) that one rounding of an exact value yields:
+//      sc8: x = fl((qI^2 + qQ^2) * 2^(2k)), qI^2 + qQ^2 <= 2^15 -- v_dot4c_i32_i8 of the pair with itself (the upper bytes are 0);
+//      cu8: (u - 127.5)^2 = 16256.25 - u (255 - u) and 255 - u = ~u, so with p = uI ~uI + uQ ~uQ (v_dot4_u32_u8 of the pair and
+//           its complement) x = fl(32512.5 2^(2k) - p 2^(2k)): one fma, whose exact result (a multiple of 2^(2k-1) below 2^15 2^(2k))
+//           is representable, so the fma returns it.
+//    3.5 VALU per sample in k_threshold_wg's take (the ISA, tests/iq8_bench.py) against the float route's six (sc8) or seven (cu8).
+template <int KIND>
+__device__ __forceinline__ float iq8_env_int(uint32_t w, float m2) {   // m2 = 2^(2k)
+    if constexpr (KIND == IN_IQ_I8) {
+        return (float)__builtin_amdgcn_sdot4((int)w, (int)w, 0, false) * m2;
+    } else {
+        const uint32_t p = __builtin_amdgcn_udot4(w, w ^ 0xFFFFu, 0u, false);
+        return fmaf(-(float)p, m2, 32512.5f * m2);
+    }
+}
+template <int KIND>
+__device__ __forceinline__ float iq8_env_float(uint32_t w, float scale) {
+    iq16_f2 v;
+    if constexpr (KIND == IN_IQ_I8) {
+        v = (iq16_f2){(float)(int)(int8_t)(w & 0xFFu), (float)(int)(int8_t)((w >> 8) & 0xFFu)};
+    } else {
+        v = (iq16_f2){(float)(w & 0xFFu), (float)((w >> 8) & 0xFFu)} - 127.5f;   // (exact)
+    }
+    v = v * scale;
+    const iq16_f2 sq = v * v;
+    return sq.x + sq.y;
+}
+template <int KIND>
+__device__ __forceinline__ float iq8_env(uint32_t w, float arg) {
+    return arg < 0.f ? iq8_env_int<KIND>(w, -arg) : iq8_env_float<KIND>(w, arg);
+}
+// ... for the N samples of a step: one branch around all of them
+template <int KIND, int N>
+__device__ __forceinline__ void iq8_env_step(const float (&w)[N], float (&x)[N], float arg) {
+    if (arg < 0.f) {
+        const float m2 = -arg;
+#pragma unroll
+        for (int j = 0; j < N; j++) x[j] = iq8_env_int<KIND>(__float_as_uint(w[j]), m2);
+    } else {
+#pragma unroll
+        for (int j = 0; j < N; j++) x[j] = iq8_env_float<KIND>(__float_as_uint(w[j]), arg);
+    }
+}
+
 // Envelope of one sample (gnuradio complex_to_mag_squared; compiled with
 // -ffp-contract=off so the products and the sum round separately).
 template <int KIND>
@@ -316,6 +366,8 @@ __device__ __forceinline__ float envelope_at(const void *in, size_t m, float i16
         return s * s;
     } else if (KIND == IN_IQ_I16) {
         return iq16_env(((const uint32_t *)in)[m], i16_scale);
+    } else if constexpr (KIND == IN_IQ_I8 || KIND == IN_IQ_U8) {
+        return iq8_env<KIND>(((const uint16_t *)in)[m], i16_scale);
     } else {
         const float s = i16_to_float((int)((const int16_t *)in)[m], i16_scale);
         return s * s;
@@ -328,6 +380,8 @@ template <int KIND> struct RawOf { using T = float; };
 template <> struct RawOf<IN_IQ_F32> { using T = float2; };
 template <> struct RawOf<IN_I16_SQ> { using T = int16_t; };
 template <> struct RawOf<IN_IQ_I16> { using T = uint32_t; };   // (the I,Q pair as one dword)
+template <> struct RawOf<IN_IQ_I8> { using T = uint16_t; };    // (the I,Q pair of bytes as one ushort)
+template <> struct RawOf<IN_IQ_U8> { using T = uint16_t; };
 template <int KIND>
 __device__ __forceinline__ typename RawOf<KIND>::T load_raw(const void *in, size_t m) {
     return ((const typename RawOf<KIND>::T *)in)[m];
@@ -343,6 +397,8 @@ __device__ __forceinline__ float env_of(typename RawOf<KIND>::T v, float i16_sca
         return v * v;
     } else if constexpr (KIND == IN_IQ_I16) {
         return iq16_env(v, i16_scale);
+    } else if constexpr (KIND == IN_IQ_I8 || KIND == IN_IQ_U8) {
+        return iq8_env<KIND>(v, i16_scale);
     } else {
         const float s = i16_to_float((int)v, i16_scale);
         return s * s;
@@ -353,6 +409,7 @@ __device__ __forceinline__ typename RawOf<KIND>::T raw_zero() {
     if constexpr (KIND == IN_IQ_F32) return make_float2(0.f, 0.f);
     else if constexpr (KIND == IN_I16_SQ) return (int16_t)0;
     else if constexpr (KIND == IN_IQ_I16) return 0u;
+    else if constexpr (KIND == IN_IQ_I8 || KIND == IN_IQ_U8) return (uint16_t)0;
     else return 0.f;
 }
 

@@ -63,6 +63,11 @@ __device__ __forceinline__ void lean_load_step(const void *p) {   // the 256 sam
         if constexpr (K == 1) LEAN_LOAD4("global_load_dwordx2", "a[8:9]", "a[10:11]", "a[12:13]", "a[14:15]", 512, LEAN_CLOB1);
         if constexpr (K == 2) LEAN_LOAD4("global_load_dwordx2", "a[16:17]", "a[18:19]", "a[20:21]", "a[22:23]", 512, LEAN_CLOB2);
         if constexpr (K == 3) LEAN_LOAD4("global_load_dwordx2", "a[24:25]", "a[26:27]", "a[28:29]", "a[30:31]", 512, LEAN_CLOB3);
+    } else if constexpr (KIND == IN_IQ_I8 || KIND == IN_IQ_U8) {   // (the I,Q pair of bytes, zero-extended: iq8_env)
+        if constexpr (K == 0) LEAN_LOAD4("global_load_ushort", "a0", "a1", "a2", "a3", 128, LEAN_CLOB0);
+        if constexpr (K == 1) LEAN_LOAD4("global_load_ushort", "a8", "a9", "a10", "a11", 128, LEAN_CLOB1);
+        if constexpr (K == 2) LEAN_LOAD4("global_load_ushort", "a16", "a17", "a18", "a19", 128, LEAN_CLOB2);
+        if constexpr (K == 3) LEAN_LOAD4("global_load_ushort", "a24", "a25", "a26", "a27", 128, LEAN_CLOB3);
     } else if constexpr (KIND == IN_I16_SQ) {
         if constexpr (K == 0) LEAN_LOAD4("global_load_sshort", "a0", "a1", "a2", "a3", 128, LEAN_CLOB0);
         if constexpr (K == 1) LEAN_LOAD4("global_load_sshort", "a8", "a9", "a10", "a11", 128, LEAN_CLOB1);
@@ -108,6 +113,10 @@ __device__ __forceinline__ void lean_take(float (&x)[4], float i16_scale) {
         if constexpr (K == 1) LEAN_TAKE4("a8", "a9", "a10", "a11");
         if constexpr (K == 2) LEAN_TAKE4("a16", "a17", "a18", "a19");
         if constexpr (K == 3) LEAN_TAKE4("a24", "a25", "a26", "a27");
+        if constexpr (KIND == IN_IQ_I8 || KIND == IN_IQ_U8) {
+            iq8_env_step<KIND>(w, x, i16_scale);   // (the four samples of the step on one route: threshold.hip.h)
+            return;
+        }
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             if constexpr (KIND == IN_I16_SQ) {
@@ -123,7 +132,7 @@ __device__ __forceinline__ void lean_take(float (&x)[4], float i16_scale) {
         }
     }
 }
-template <int KIND> struct LeanRaw { static constexpr int BYTES = (KIND == IN_IQ_F32) ? 8 : (KIND == IN_I16_SQ) ? 2 : 4; };   // (IN_IQ_I16: 4, an I,Q pair of int16)
+template <int KIND> struct LeanRaw { static constexpr int BYTES = (KIND == IN_IQ_F32) ? 8 : (KIND == IN_I16_SQ || KIND == IN_IQ_I8 || KIND == IN_IQ_U8) ? 2 : 4; };   // (IN_IQ_I16: 4, an I,Q pair of int16; the 8-bit IQ kinds: 2, a pair of bytes)
 typedef __attribute__((address_space(3))) float lean_lds_f;
 typedef __attribute__((address_space(1))) uint32_t lean_g_u32;   // (an address computed from integers must not become a flat access)
 typedef uint32_t lean_u32x4 __attribute__((ext_vector_type(4)));

@@ -132,6 +132,9 @@ __device__ __forceinline__ void wg_load_step(uint32_t voff, const char *base) {
         if constexpr (NR == 4) WG_LD4("global_load_dwordx2", "a[0:1]", "a[2:3]", "a[4:5]", "a[6:7]", 512, WG_A03, WG_A47);
         if constexpr (NR == 8)
             WG_LD8("global_load_dwordx2", "a[0:1]", "a[2:3]", "a[4:5]", "a[6:7]", "a[8:9]", "a[10:11]", "a[12:13]", "a[14:15]", 512, WG_A03, WG_A47, WG_A8B, WG_ACF);
+    } else if constexpr (KIND == IN_IQ_I8 || KIND == IN_IQ_U8) {   // (the I,Q pair of bytes, zero-extended: iq8_env)
+        if constexpr (NR == 4) WG_LD4("global_load_ushort", "a0", "a1", "a2", "a3", 128, WG_A03);
+        if constexpr (NR == 8) WG_LD8("global_load_ushort", "a0", "a1", "a2", "a3", "a4", "a5", "a6", "a7", 128, WG_A03, WG_A47);
     } else if constexpr (KIND == IN_I16_SQ) {
         if constexpr (NR == 4) WG_LD4("global_load_sshort", "a0", "a1", "a2", "a3", 128, WG_A03);
         if constexpr (NR == 8) WG_LD8("global_load_sshort", "a0", "a1", "a2", "a3", "a4", "a5", "a6", "a7", 128, WG_A03, WG_A47);
@@ -169,6 +172,10 @@ __device__ __forceinline__ void wg_take(float (&x)[NR], float i16_scale) {
         float w[NR];
         WG_RD4("s_waitcnt vmcnt(0)\n\t", "a0", "a1", "a2", "a3", 0);
         if constexpr (NR == 8) WG_RD4("", "a4", "a5", "a6", "a7", 4);
+        if constexpr (KIND == IN_IQ_I8 || KIND == IN_IQ_U8) {
+            iq8_env_step<KIND>(w, x, i16_scale);   // (the step's samples on one route: threshold.hip.h)
+            return;
+        }
 #pragma unroll
         for (int j = 0; j < NR; j++) {
             if constexpr (KIND == IN_I16_SQ) {

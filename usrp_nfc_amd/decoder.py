@@ -9,10 +9,12 @@ wiring: source -> envelope -> ``transition_sink(samp_rate, background.append, hi
   ``usrp_nfc.py`` can ``self.connect(decoder(...))`` unchanged.
 * Without GNU Radio (this image) ``src`` may be a 16-bit mono WAV path, a raw float32 file, a raw complex64 IQ
   file (``.fc32`` / ``.cfile`` / ``.iq``), a raw complex int16 IQ file (``.sc16`` / ``.cs16`` / ``.ci16``: what
-  ``uhd_rx_cfile -s`` and ``rx_samples_to_file --type short`` record, I first), or a numpy
-  array, and ``run()`` streams it through the GPU path offline: a real recording is squared like the
-  reference's WAV branch (float_to_complex with Q = 0, then |.|^2), complex64 / interleaved IQ takes
-  the UHD branch's |IQ|^2 -- complex int16 too (an int16 array of shape (n, 2)), converted on the GPU (``iq16_scale``).
+  ``uhd_rx_cfile -s`` and ``rx_samples_to_file --type short`` record, I first), a raw complex int8 IQ file
+  (``.cs8`` / ``.sc8`` / ``.ci8``: what ``hackrf_transfer -r`` records), a raw complex uint8 IQ file (``.cu8``: what
+  ``rtl_sdr`` records), or a numpy array, and ``run()`` streams it through the GPU path offline: a real recording is
+  squared like the reference's WAV branch (float_to_complex with Q = 0, then |.|^2), complex64 / interleaved IQ takes
+  the UHD branch's |IQ|^2 -- complex int16 too (an int16 array of shape (n, 2)), converted on the GPU (``iq16_scale``),
+  and complex int8 / uint8 (an int8 / uint8 array of shape (n, 2)), converted on the GPU (``iq8_scale``).
 """
 import wave
 
@@ -30,13 +32,16 @@ except Exception:
     _blocks = None
 
 
-def _load_source(src, wav_scale, iq16_scale=0.0):
+def _load_source(src, wav_scale, iq16_scale=0.0, iq8_scale=0.0):
     """-> (array, input_kind, i16_scale)"""
     if isinstance(src, numpy.ndarray):
         if src.dtype == numpy.complex64:
             return src.view(numpy.float32), api.NFC_IN_IQ_F32, 0.0
         if src.dtype == numpy.int16 and src.ndim == 2 and src.shape[1] == 2:   # complex int16, one row per sample
             return numpy.ascontiguousarray(src).reshape(-1), api.NFC_IN_IQ_I16, iq16_scale
+        if src.dtype in (numpy.int8, numpy.uint8) and src.ndim == 2 and src.shape[1] == 2:   # complex int8 / uint8, one row per sample
+            kind = api.NFC_IN_IQ_I8 if src.dtype == numpy.int8 else api.NFC_IN_IQ_U8
+            return numpy.ascontiguousarray(src).reshape(-1), kind, iq8_scale
         if src.dtype == numpy.int16:
             return src, api.NFC_IN_I16_SQ, wav_scale
         return numpy.ascontiguousarray(src, numpy.float32), api.NFC_IN_REAL_F32_SQ, 0.0
@@ -53,12 +58,20 @@ def _load_source(src, wav_scale, iq16_scale=0.0):
         return numpy.fromfile(src, dtype=numpy.float32), api.NFC_IN_IQ_F32, 0.0
     if str(src).lower().endswith(('.sc16', '.cs16', '.ci16')):   # raw interleaved complex int16 (little-endian, I first)
         return numpy.fromfile(src, dtype='<i2').astype(numpy.int16, copy=False), api.NFC_IN_IQ_I16, iq16_scale
+    if str(src).lower().endswith(('.cs8', '.sc8', '.ci8')):   # raw interleaved complex int8 (I first: a HackRF's samples)
+        return numpy.fromfile(src, dtype=numpy.int8), api.NFC_IN_IQ_I8, iq8_scale
+    if str(src).lower().endswith('.cu8'):   # raw interleaved complex uint8, offset binary (I first: an RTL-SDR's samples)
+        return numpy.fromfile(src, dtype=numpy.uint8), api.NFC_IN_IQ_U8, iq8_scale
     return numpy.fromfile(src, dtype=numpy.float32), api.NFC_IN_REAL_F32_SQ, 0.0
 
 
 def _hi_val(kind):
     """1.1 for IQ from the radio (the UHD branch, decoder.py:23), 1.09 for the WAV branch (decoder.py:29)."""
-    return 1.1 if kind in (api.NFC_IN_IQ_F32, api.NFC_IN_IQ_I16) else 1.09
+    return 1.1 if kind in _IQ_KINDS else 1.09
+
+
+_IQ_KINDS = (api.NFC_IN_IQ_F32, api.NFC_IN_IQ_I16, api.NFC_IN_IQ_I8, api.NFC_IN_IQ_U8)
+_SCALED_KINDS = (api.NFC_IN_I16_SQ, api.NFC_IN_IQ_I16, api.NFC_IN_IQ_I8, api.NFC_IN_IQ_U8)   # (the kinds i16_scale converts)
 
 
 if _gr is not None:
@@ -85,21 +98,23 @@ else:
     class decoder(object):
         def __init__(self, src="uhd", dst=None, repeat=False, reader=True, tag=True, samp_rate=2e6, emulator=None,
                      wav_scale=0.0, fsm=None, batch=1 << 22, device=0, lo_val=0.1, av_window=2000, max_len=50, keep=None,
-                     iq16_scale=0.0):
+                     iq16_scale=0.0, iq8_scale=0.0):
             """wav_scale: int16 PCM -> float.  0 (default): GNU Radio's wavfile_source normalisation, sample / 32767 (what the
             reference's WAV branch feeds the path, decoder.py:25; third party, unpinned: nfc_amd.h); > 0: sample * wav_scale.
             lo_val / av_window / max_len: transition_sink's keyword arguments (transition_sink.py:12), e.g. scaled with the rate.
             iq16_scale: complex int16 -> float, I and Q each, with wav_scale's meaning (0: / 32767; UHD's own sc16 -> fc32 scaling
-            is third party and unpinned: nfc_amd.h)."""
+            is third party and unpinned: nfc_amd.h).
+            iq8_scale: complex int8 / uint8 -> float, I and Q each: sc8 q * s, cu8 (u - 127.5) * s with s = iq8_scale, or 2^-7 where
+            it is not positive (the third-party 8-bit conversions are unpinned: nfc_amd.h)."""
             if isinstance(src, str) and src == "uhd":
                 raise RuntimeError('the UHD source needs GNU Radio + UHD; pass a recording or an array')
-            data, kind, scale = _load_source(src, wav_scale, iq16_scale)
+            data, kind, scale = _load_source(src, wav_scale, iq16_scale, iq8_scale)
             self._data = data
-            self._per = 2 if kind in (api.NFC_IN_IQ_F32, api.NFC_IN_IQ_I16) else 1
+            self._per = 2 if kind in _IQ_KINDS else 1
             hi_val = _hi_val(kind)   # decoder.py:23 / :29
             self._back = background(reader, tag, emulator, fsm=fsm, keep=keep)
             self._trans = transition_sink(samp_rate, self._back.append, lo_val=lo_val, hi_val=hi_val, av_window=av_window, max_len=max_len,
-                                          batch=batch, device=device, input_kind=kind, i16_scale=scale if kind in (api.NFC_IN_I16_SQ, api.NFC_IN_IQ_I16) else 0.0)
+                                          batch=batch, device=device, input_kind=kind, i16_scale=scale if kind in _SCALED_KINDS else 0.0)
             self._batch = int(batch)
 
         def run(self):

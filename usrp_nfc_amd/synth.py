@@ -255,3 +255,17 @@ def quantise_sc16(iq, full_scale=32767.0):
     clip to the int16 range.  full_scale: the int16 value of 1.0 (the carrier of these workloads has amplitude 0.5)."""
     v = np.rint(np.asarray(iq, np.float64) * float(full_scale))
     return np.clip(v, -32768, 32767).astype(np.int16)
+
+
+def quantise_sc8(iq, full_scale=127.0):
+    """Interleaved float32 IQ -> complex int8 (sc8), as a HackRF delivers it: round to nearest (ties to even), clip to the int8
+    range.  full_scale: the int8 value of 1.0 (the carrier of these workloads has amplitude 0.5)."""
+    v = np.rint(np.asarray(iq, np.float64) * float(full_scale))
+    return np.clip(v, -128, 127).astype(np.int8)
+
+
+def quantise_cu8(iq, full_scale=127.0):
+    """Interleaved float32 IQ -> complex uint8 (cu8, offset binary), as an RTL-SDR delivers it: 127.5 + v * full_scale rounded to
+    nearest (ties to even), clipped to 0 .. 255."""
+    v = np.rint(127.5 + np.asarray(iq, np.float64) * float(full_scale))
+    return np.clip(v, 0, 255).astype(np.uint8)

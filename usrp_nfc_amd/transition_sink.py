@@ -42,8 +42,10 @@ class transition_sink(_Base):
 
     def __init__(self, samp_rate, callback, lo_val=0.1, hi_val=1.1, av_window=2000, max_len=50,
                  batch=1 << 22, device=0, input_kind=api.NFC_IN_ENV_F32, i16_scale=0.0, flush_ms=50.0, flush_calls=0):
-        # (complex int16: 4-byte items of two int16, what uhd.usrp_source emits with cpu_format="sc16")
-        sig = {api.NFC_IN_I16_SQ: numpy.int16, api.NFC_IN_IQ_I16: (numpy.int16, 2)}.get(input_kind, numpy.float32)
+        # (complex int16: 4-byte items of two int16, what uhd.usrp_source emits with cpu_format="sc16"; complex int8 / uint8: 2-byte
+        # items of two bytes, what a CS8 source -- a HackRF through SoapySDR, uhd.usrp_source with cpu_format="sc8" -- or an RTL-SDR emits)
+        sig = {api.NFC_IN_I16_SQ: numpy.int16, api.NFC_IN_IQ_I16: (numpy.int16, 2), api.NFC_IN_IQ_I8: (numpy.int8, 2),
+               api.NFC_IN_IQ_U8: (numpy.uint8, 2)}.get(input_kind, numpy.float32)
         _Base.__init__(self, name="transition_sink", in_sig=[sig], out_sig=None)
         self._callback = callback
         self._batch = max(1, int(batch))
@@ -53,8 +55,9 @@ class transition_sink(_Base):
         self._nbuf = 0
         self._ncalls = 0
         self._t_last = time.monotonic()
-        self._dtype = numpy.int16 if input_kind in (api.NFC_IN_I16_SQ, api.NFC_IN_IQ_I16) else numpy.float32
-        self._per = 2 if input_kind == api.NFC_IN_IQ_I16 else 1   # values per sample (an item)
+        self._dtype = {api.NFC_IN_I16_SQ: numpy.int16, api.NFC_IN_IQ_I16: numpy.int16, api.NFC_IN_IQ_I8: numpy.int8,
+                       api.NFC_IN_IQ_U8: numpy.uint8}.get(input_kind, numpy.float32)
+        self._per = 2 if input_kind in (api.NFC_IN_IQ_I16, api.NFC_IN_IQ_I8, api.NFC_IN_IQ_U8) else 1   # values per sample (an item)
         back = getattr(callback, '__self__', None)
         self._back = back if hasattr(back, '_deliver') else None
         if self._back is not None:
