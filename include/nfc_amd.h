@@ -32,6 +32,7 @@ extern "C" {
 /* 2: nfc_stats grew (ran_ahead, redone_total, ring_slots_carried); i16_scale == 0 means sample / 32767 (GNU Radio's wavfile_source), not / 32768 */
 /* 3: nfc_stats.reserved0 became decode_respeculated (same layout); the raw float32 envelope takes the fast threshold kernels */
 /* 4: nfc_stats grew (device_allocs, tail_fused, chunks_rerun_in_place) */
+/* (still 4, no structure changed: the input kinds NFC_IN_IQ_I16, NFC_IN_IQ_I8, NFC_IN_IQ_U8; nfc_record_pcm16_device, nfc_host_record_pcm16, nfc_record_tap) */
 #define NFC_AMD_ABI_VERSION 4
 
 typedef enum {
@@ -334,6 +335,37 @@ int nfc_tx_sample_count(const nfc_tx_run *runs, size_t n_runs, double samp_rate,
 int nfc_tx_render_device(int device, const nfc_tx_run *runs, size_t n_runs, double samp_rate, int carrier, double freq,
                          float amp, uint64_t first_index, void *dev_out, size_t cap_samples, size_t *n_samples,
                          float *kernel_ms);
+
+/* ---- recording: a float per sample -> 16-bit PCM on the device ---------------------------------------------------
+ * What the reference writes through GNU Radio's wavfile_sink (16 bits, one channel): usrp_src.py:35-37 records the envelope
+ * |IQ|^2 of the live capture (decoder(src="uhd", dst=path), usrp_nfc.py -o) -- the recording decoder(src=path) reads back --
+ * and record.py:10-19 the real part of a complex stream (what the emulators transmit, usrp_nfc.py:59-60,95-96).
+ * THE CONVERSION, for a float32 value x and a float32 gain, in this order:
+ *   1. v = fl(x * gain): one float32 product (no contraction);
+ *   2. NaN becomes 0;
+ *   3. v is clamped to [-32767, 32767] (so +-Inf become +-32767);
+ *   4. v is rounded to the nearest integer, halves away from zero (lroundf, exactly: 0.49999997 gives 0);
+ *   5. the result is stored as little-endian int16.
+ * gain must be finite and > 0 (NFC_ERR_ARG otherwise); 32767 is the inverse of NFC_IN_I16_SQ's default i16_scale = 0 (/ 32767).
+ * Modelled on gr-blocks' wavfile_sink for 16 bits (times 0x7FFF, clamp to +-0x7FFF, round to nearest); GNU Radio is third party
+ * and absent from the reference tree, so this boundary is UNPINNED, as wavfile_source's is.
+ * x comes from one of two taps: */
+typedef enum {
+    NFC_REC_ENVELOPE = 0, /* the envelope the threshold kernels compute for input_kind and i16_scale (any nfc_input_kind; i16_scale as in
+                           * nfc_params, with the same limits and NFC_ERR_ARG beyond them) */
+    NFC_REC_REAL_PART = 1 /* the real part of an interleaved complex64 sample (complex_to_real, record.py:18): NFC_IN_IQ_F32 only,
+                           * NFC_ERR_ARG with any other kind */
+} nfc_record_tap;
+/* Converts n samples at dev_samples (device memory, of input_kind) into n int16 at dev_pcm_out (device memory); both 16-byte
+ * aligned (NFC_ERR_ARG otherwise).  No context: like nfc_tx_render_device.  stream == NULL: the result is complete when the call
+ * returns.  A stream of nfc_stream_create: the kernel is only enqueued there and nfc_stream_sync completes it.  kernel_ms (NULL, or
+ * the kernel's duration by HIP events) implies the wait.  n == 0 succeeds and does nothing; n > 2^30 is NFC_ERR_ARG (nfc_push's
+ * per-call limit).  Every argument is checked before the device is touched.  Nothing is written beyond dev_pcm_out[n). */
+int nfc_record_pcm16_device(int device, int tap, int input_kind, float i16_scale, const void *dev_samples, size_t n,
+                            float gain, void *dev_pcm_out /* n int16 */, void *stream /* hipStream_t or NULL */,
+                            float *kernel_ms /* NULL, or the kernel's duration by HIP events */);
+/* steps 1-5 above on the host: the twin of the kernel's conversion, as nfc_host_i16_to_float is of the PCM kind's */
+int16_t nfc_host_record_pcm16(float x, float gain);
 
 /* Device memory helpers so that a caller without HIP bindings (ctypes) can keep its input
  * resident in HBM and use nfc_push_device. */

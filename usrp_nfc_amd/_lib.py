@@ -12,6 +12,7 @@ from . import build as _build
 
 NFC_IN_IQ_F32, NFC_IN_ENV_F32, NFC_IN_REAL_F32_SQ, NFC_IN_I16_SQ, NFC_IN_IQ_I16, NFC_IN_IQ_I8, NFC_IN_IQ_U8 = 0, 1, 2, 3, 4, 5, 6
 NFC_FLAG_FORCE_SEQUENTIAL, NFC_FLAG_NO_EDGES = 1, 2
+NFC_REC_ENVELOPE, NFC_REC_REAL_PART = 0, 1   # nfc_record_tap
 ABI_VERSION = 4   # NFC_AMD_ABI_VERSION of the header these structures mirror
 
 
@@ -68,7 +69,8 @@ SYMBOLS = ['nfc_abi_version', 'nfc_device_count', 'nfc_create', 'nfc_destroy', '
            'nfc_device_alloc', 'nfc_device_free', 'nfc_device_upload', 'nfc_device_download', 'nfc_stream_create', 'nfc_stream_destroy',
            'nfc_stream_sync', 'nfc_device_download_async', 'nfc_device_fill', 'nfc_host_alloc_pinned', 'nfc_host_free_pinned', 'nfc_host_decode_lut', 'nfc_host_miller_classes', 'nfc_host_decode_steps', 'nfc_host_i16_to_float', 'nfc_plan_row_cut',
            'nfc_fsm_create', 'nfc_fsm_destroy', 'nfc_fsm_reset', 'nfc_fsm_process', 'nfc_fsm_process_packets', 'nfc_fsm_process_outgoing', 'nfc_fsm_set_keys',
-           'nfc_command_count', 'nfc_command_get', 'nfc_crc_a', 'nfc_tx_encode', 'nfc_tx_sample_count', 'nfc_tx_render_device']
+           'nfc_command_count', 'nfc_command_get', 'nfc_crc_a', 'nfc_tx_encode', 'nfc_tx_sample_count', 'nfc_tx_render_device',
+           'nfc_record_pcm16_device', 'nfc_host_record_pcm16']
 
 _libs = {}
 
@@ -155,6 +157,9 @@ def load(path=None):
     L.nfc_tx_sample_count.argtypes = [vp, sz, C.c_double, C.POINTER(C.c_uint64)]
     L.nfc_tx_render_device.argtypes = [C.c_int, vp, sz, C.c_double, C.c_int, C.c_double, C.c_float, C.c_uint64, vp, sz, psz,
                                        C.POINTER(C.c_float)]
+    L.nfc_record_pcm16_device.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, vp, sz, C.c_float, vp, vp, C.POINTER(C.c_float)]
+    L.nfc_host_record_pcm16.argtypes = [C.c_float, C.c_float]
+    L.nfc_host_record_pcm16.restype = C.c_int16
     for name in SYMBOLS:
         getattr(L, name)
     _libs[path] = L

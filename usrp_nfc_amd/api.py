@@ -5,11 +5,12 @@ import numpy as np
 
 from . import _lib
 from ._lib import (EDGE_DTYPE, NFC_FLAG_FORCE_SEQUENTIAL, NFC_FLAG_NO_EDGES, NFC_IN_ENV_F32, NFC_IN_I16_SQ,
-                   NFC_IN_IQ_F32, NFC_IN_IQ_I8, NFC_IN_IQ_I16, NFC_IN_IQ_U8, NFC_IN_REAL_F32_SQ, PACKET_DTYPE)
+                   NFC_IN_IQ_F32, NFC_IN_IQ_I8, NFC_IN_IQ_I16, NFC_IN_IQ_U8, NFC_IN_REAL_F32_SQ, NFC_REC_ENVELOPE,
+                   NFC_REC_REAL_PART, PACKET_DTYPE)
 
 __all__ = ['NfcContext', 'NfcError', 'DeviceBuffer', 'host_decode_lut', 'host_envelope', 'NFC_IN_IQ_F32', 'NFC_IN_ENV_F32',
            'NFC_IN_REAL_F32_SQ', 'NFC_IN_I16_SQ', 'NFC_IN_IQ_I16', 'NFC_IN_IQ_I8', 'NFC_IN_IQ_U8', 'NFC_FLAG_FORCE_SEQUENTIAL',
-           'NFC_FLAG_NO_EDGES']
+           'NFC_FLAG_NO_EDGES', 'NFC_REC_ENVELOPE', 'NFC_REC_REAL_PART', 'host_record_pcm16', 'record_pcm16_device', 'record_pcm16']
 
 _KIND_DTYPE = {NFC_IN_IQ_F32: (np.float32, 2), NFC_IN_ENV_F32: (np.float32, 1),
                NFC_IN_REAL_F32_SQ: (np.float32, 1), NFC_IN_I16_SQ: (np.int16, 1), NFC_IN_IQ_I16: (np.int16, 2),
@@ -276,6 +277,14 @@ class DeviceBuffer(object):
         if a.nbytes and self.L.nfc_device_upload(device, self.ptr, a.ctypes.data, a.nbytes) != 0:
             raise NfcError('nfc_device_upload failed')
 
+    def upload(self, host_array):
+        """Overwrite the buffer's first bytes with a host array (nfc_device_upload)."""
+        a = np.ascontiguousarray(host_array)
+        if a.nbytes > self.nbytes:
+            raise NfcError('DeviceBuffer.upload: %d bytes do not fit %d' % (a.nbytes, self.nbytes))
+        if a.nbytes and self.L.nfc_device_upload(self.device, self.ptr, a.ctypes.data, a.nbytes) != 0:
+            raise NfcError('nfc_device_upload failed')
+
     def download(self, nbytes=None):
         """The buffer's first nbytes (default: all) as a uint8 array (nfc_device_download)."""
         n = self.nbytes if nbytes is None else int(nbytes)
@@ -356,6 +365,63 @@ def host_envelope(x, kind, i16_scale=0.0):
         return a * a
     i, q = a[0::2], a[1::2]
     return (i * i) + (q * q)
+
+
+def host_record_pcm16(x, gain=32767.0):
+    """float32 -> int16 PCM as the recording kernel converts it (nfc_amd.h, csrc/record.hip.h: pcm16_of): v = fl(x * gain), NaN -> 0,
+    clamp to [-32767, 32767], round to nearest with halves away from zero.  The numpy twin of nfc_host_record_pcm16."""
+    with np.errstate(over='ignore', invalid='ignore'):
+        v = np.asarray(x, dtype=np.float32) * np.float32(gain)
+    v = np.where(np.isnan(v), np.float32(0), v)
+    v = np.clip(v, np.float32(-32767), np.float32(32767))
+    t = np.trunc(v)
+    t = np.where(np.abs(v - t) >= np.float32(0.5), t + np.copysign(np.float32(1), v), t)   # (v - t is exact)
+    return t.astype(np.int16)
+
+
+def _as_pointer(p):
+    """A DeviceBuffer, a ctypes pointer (DeviceBuffer.ptr, a stream of nfc_stream_create), an integer address or None -> c_void_p."""
+    if isinstance(p, DeviceBuffer):
+        return p.ptr
+    if isinstance(p, C.c_void_p):
+        return p
+    return C.c_void_p(int(p or 0))
+
+
+def record_pcm16_device(dev_ptr, n, out_ptr, kind, i16_scale=0.0, gain=32767.0, tap=NFC_REC_ENVELOPE, device=0, stream=None,
+                        timed=False):
+    """n samples of input kind `kind` at dev_ptr (device memory) -> n int16 PCM at out_ptr (device memory), both 16-byte aligned
+    (nfc_record_pcm16_device).  tap: NFC_REC_ENVELOPE, the envelope the threshold kernels compute for the kind and i16_scale, or
+    NFC_REC_REAL_PART, the real part of complex64.  stream: None, or an integer hipStream_t (the work is then only enqueued).
+    -> the kernel's duration in ms when timed, else None."""
+    L = _lib.load()
+    src, dst, st = _as_pointer(dev_ptr), _as_pointer(out_ptr), _as_pointer(stream)
+    ms = C.c_float(0)
+    rc = L.nfc_record_pcm16_device(int(device), int(tap), int(kind), float(i16_scale), src, int(n), float(gain), dst, st,
+                                   C.byref(ms) if timed else None)
+    if rc != 0:
+        raise NfcError('nfc_record_pcm16_device: %s (status %d)' % (L.nfc_last_error(None).decode(), rc))
+    return float(ms.value) if timed else None
+
+
+def record_pcm16(x, kind, i16_scale=0.0, gain=32767.0, tap=NFC_REC_ENVELOPE, device=0):
+    """Upload a host array of input kind `kind`, convert it on the GPU, download: the int16 PCM, one value per sample."""
+    dt, per = _KIND_DTYPE[kind]
+    a = np.asarray(x)
+    if a.dtype == np.complex64 and per == 2:
+        a = a.view(np.float32)
+    a = np.ascontiguousarray(a, dtype=dt).reshape(-1)
+    n = a.size // per
+    if n == 0:
+        return np.zeros(0, np.int16)
+    src = DeviceBuffer(a[:n * per], device)
+    dst = DeviceBuffer(np.zeros(0, np.int16), device, nbytes=2 * n)
+    try:
+        record_pcm16_device(src, n, dst, kind, i16_scale, gain, tap, device)
+        return dst.download(2 * n).view(np.int16)
+    finally:
+        src.free()
+        dst.free()
 
 
 def host_decode_lut(ptype, cur, d, samp_rate=2e6, max_len=50):

@@ -53,6 +53,7 @@
 #include "iq16.h"   // (the complex int16 kind's kernels: nfc_iq16.hip)
 #include "iq8.h"    // (the complex 8-bit kinds' kernels: nfc_iq8.hip)
 #include "tx.hip.h"
+#include "record.hip.h"   // (the recording kernel: nfc_record.hip)
 
 using namespace nfc;
 
@@ -117,6 +118,18 @@ float iq8_kernel_arg(int kind, float i16_scale) {
     if (mant == 0.5f && k >= kmin && k <= 56) return -ldexpf(1.0f, 2 * k);
     return s;
 }
+// The kernels' conversion argument for an input kind and the caller's i16_scale (nfc_params.i16_scale) -- what nfc_create puts into the
+// context and nfc_record_pcm16_device hands its kernel: the int16 kinds' scale, or -1 for sample / 32767 (threshold.hip.h: i16_to_float);
+// the complex 8-bit kinds' route and scale (iq8_kernel_arg).  Returns null, or what is wrong with the scale.
+const char *kernel_scale_arg(int kind, float i16_scale, float *arg) {
+    // (complex int16: |I|, |Q| <= 2^15, so the envelope 2 (2^15 s)^2 stays finite -- and the kernels need no guard for it -- up to s = 2^48)
+    if (kind == NFC_IN_IQ_I16 && i16_scale > 281474976710656.0f) return "i16_scale must be at most 2^48 for complex int16 input";
+    // (complex 8-bit: |I|, |Q| <= 2^7 s -- sc8's -128, cu8's 127.5 --, so the envelope 2 (2^7 s)^2 stays finite up to s = 2^56)
+    if ((kind == NFC_IN_IQ_I8 || kind == NFC_IN_IQ_U8) && i16_scale > 72057594037927936.0f) return "i16_scale must be at most 2^56 for complex 8-bit input";
+    *arg = i16_scale > 0.f ? i16_scale : -1.0f;   // (0: GNU Radio's wavfile_source normalisation, sample / 32767; threshold.hip.h: i16_to_float)
+    if (kind == NFC_IN_IQ_I8 || kind == NFC_IN_IQ_U8) *arg = iq8_kernel_arg(kind, i16_scale);   // (not the -1 above)
+    return nullptr;
+}
 }  // namespace
 
 extern "C" {
@@ -150,12 +163,8 @@ int nfc_create(const nfc_params *p, nfc_ctx **out) {
     if (p->av_window < 1 || p->av_window > 30000) return fail(nullptr, NFC_ERR_ARG, "av_window must be in [1, 30000]");
     if (p->max_len < 1 || p->max_len > 4000) return fail(nullptr, NFC_ERR_ARG, "max_len must be in [1, 4000]");
     if (p->input_kind < 0 || p->input_kind > 6) return fail(nullptr, NFC_ERR_ARG, "unknown input_kind");
-    // (complex int16: |I|, |Q| <= 2^15, so the envelope 2 (2^15 s)^2 stays finite -- and the kernels need no guard for it -- up to s = 2^48)
-    if (p->input_kind == NFC_IN_IQ_I16 && p->i16_scale > 281474976710656.0f)
-        return fail(nullptr, NFC_ERR_ARG, "i16_scale must be at most 2^48 for complex int16 input");
-    // (complex 8-bit: |I|, |Q| <= 2^7 s -- sc8's -128, cu8's 127.5 --, so the envelope 2 (2^7 s)^2 stays finite up to s = 2^56)
-    if ((p->input_kind == NFC_IN_IQ_I8 || p->input_kind == NFC_IN_IQ_U8) && p->i16_scale > 72057594037927936.0f)
-        return fail(nullptr, NFC_ERR_ARG, "i16_scale must be at most 2^56 for complex 8-bit input");
+    float scale_arg = 0.f;
+    if (const char *bad = kernel_scale_arg(p->input_kind, p->i16_scale, &scale_arg)) return fail(nullptr, NFC_ERR_ARG, "%s", bad);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(nullptr, NFC_ERR_DEVICE, "no HIP device: this library has no CPU fallback");
@@ -262,8 +271,7 @@ int nfc_create(const nfc_params *p, nfc_ctx **out) {
     }
     c->eps = 0.01f;  // certification margin of the speculative pass, relative to the window sum
     if (const char *e = NFC_ENV("NFC_EPS")) c->eps = (float)atof(e);
-    c->i16_scale = p->i16_scale > 0.f ? p->i16_scale : -1.0f;   // (0: GNU Radio's wavfile_source normalisation, sample / 32767; threshold.hip.h: i16_to_float)
-    if (p->input_kind == NFC_IN_IQ_I8 || p->input_kind == NFC_IN_IQ_U8) c->i16_scale = iq8_kernel_arg(p->input_kind, p->i16_scale);   // (not the -1 above)
+    c->i16_scale = scale_arg;   // (kernel_scale_arg)
     static const size_t bps[7] = {8, 4, 4, 2, 4, 2, 2};
     c->in_bytes_per_sample = bps[p->input_kind];
     memset(&c->h_carry, 0, sizeof c->h_carry);
@@ -1344,6 +1352,54 @@ int nfc_host_alloc_pinned(size_t bytes, void **out) {
 }
 
 int nfc_host_free_pinned(void *p) { return hipHostFree(p) == hipSuccess ? NFC_OK : NFC_ERR_DEVICE; }
+
+int nfc_record_pcm16_device(int device, int tap, int input_kind, float i16_scale, const void *dev_samples, size_t n, float gain,
+                            void *dev_pcm_out, void *stream, float *kernel_ms) {
+    // (every argument check comes before anything touches the device)
+    if (tap != NFC_REC_ENVELOPE && tap != NFC_REC_REAL_PART) return fail(nullptr, NFC_ERR_ARG, "nfc_record_pcm16_device: unknown tap %d", tap);
+    if (input_kind < 0 || input_kind > 6) return fail(nullptr, NFC_ERR_ARG, "nfc_record_pcm16_device: unknown input_kind");
+    if (tap == NFC_REC_REAL_PART && input_kind != NFC_IN_IQ_F32)
+        return fail(nullptr, NFC_ERR_ARG, "nfc_record_pcm16_device: the real-part tap takes complex float32 input (NFC_IN_IQ_F32) only");
+    if (!(gain > 0.f) || !std::isfinite(gain)) return fail(nullptr, NFC_ERR_ARG, "nfc_record_pcm16_device: gain must be finite and positive");
+    if (n > ((size_t)1 << 30)) return fail(nullptr, NFC_ERR_ARG, "nfc_record_pcm16_device: at most 2^30 samples per call");
+    float scale_arg = 0.f;
+    if (const char *bad = kernel_scale_arg(input_kind, i16_scale, &scale_arg)) return fail(nullptr, NFC_ERR_ARG, "nfc_record_pcm16_device: %s", bad);
+    if (n && (!dev_samples || !dev_pcm_out)) return fail(nullptr, NFC_ERR_ARG, "nfc_record_pcm16_device: null buffer");
+    if ((((uintptr_t)dev_samples | (uintptr_t)dev_pcm_out) & 15u) != 0)
+        return fail(nullptr, NFC_ERR_ARG, "nfc_record_pcm16_device: input and output must be 16-byte aligned");
+    if (kernel_ms) *kernel_ms = 0.f;
+    if (n == 0) return NFC_OK;
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, NFC_ERR_DEVICE, "hipSetDevice(%d) failed", device);
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0)
+        return fail(nullptr, NFC_ERR_DEVICE, "nfc_record_pcm16_device: no compute-unit count for device %d", device);
+    bool nontemporal = false;
+#ifdef NFC_TEST_HOOKS
+    if (const char *e = getenv("NFC_REC_NT")) nontemporal = atoi(e) != 0;   // (the load-policy A/B of tests/record_bench.py: the test build only)
+#endif
+    hipStream_t st = (hipStream_t)stream;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    int rc = NFC_OK;
+    auto bad = [&](hipError_t e, const char *what) {
+        if (e == hipSuccess) return false;
+        rc = fail(nullptr, NFC_ERR_DEVICE, "nfc_record_pcm16_device: %s: %s", what, hipGetErrorString(e));
+        return true;
+    };
+    do {
+        if (kernel_ms && (bad(hipEventCreate(&e0), "event") || bad(hipEventCreate(&e1), "event"))) break;
+        launch_error() = LaunchError{};
+        rec::launch(input_kind, tap, dev_samples, n, scale_arg, gain, dev_pcm_out, cus, nontemporal, st, e0, e1);
+        if (bad(launch_error().err, "launch")) break;
+        // (the caller's stream: only enqueued there, nfc_stream_sync completes it -- unless the duration is asked for)
+        if ((!st || kernel_ms) && bad(hipStreamSynchronize(st), "kernel")) break;
+        if (kernel_ms && bad(hipEventElapsedTime(kernel_ms, e0, e1), "event")) break;
+    } while (0);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    return rc;
+}
+
+int16_t nfc_host_record_pcm16(float x, float gain) { return pcm16_of(x, gain); }
 
 float nfc_host_i16_to_float(int16_t pcm, float i16_scale) { return i16_to_float((int)pcm, i16_scale > 0.f ? i16_scale : -1.0f); }
 

@@ -15,6 +15,11 @@ wiring: source -> envelope -> ``transition_sink(samp_rate, background.append, hi
   squared like the reference's WAV branch (float_to_complex with Q = 0, then |.|^2), complex64 / interleaved IQ takes
   the UHD branch's |IQ|^2 -- complex int16 too (an int16 array of shape (n, 2)), converted on the GPU (``iq16_scale``),
   and complex int8 / uint8 (an int8 / uint8 array of shape (n, 2)), converted on the GPU (``iq8_scale``).
+  ``dst`` (``usrp_nfc.py -o``): with an IQ source -- the stand-ins for the UHD branch, whose ``usrp_src`` writes its envelope to a
+  16-bit mono WAV (usrp_src.py:35-37) -- ``run()`` also records the envelope |IQ|^2 to that WAV, converted on the GPU
+  (``record_gain``; include/nfc_amd.h: nfc_record_pcm16_device) from the very buffer the batch is decoded from.  The file is what
+  ``decoder(src=path)`` reads back.  With a recording as the source ``dst`` is ignored, as the reference ignores it
+  (decoder.py:24-29 has no sink there).
 """
 import wave
 
@@ -72,6 +77,7 @@ def _hi_val(kind):
 
 _IQ_KINDS = (api.NFC_IN_IQ_F32, api.NFC_IN_IQ_I16, api.NFC_IN_IQ_I8, api.NFC_IN_IQ_U8)
 _SCALED_KINDS = (api.NFC_IN_I16_SQ, api.NFC_IN_IQ_I16, api.NFC_IN_IQ_I8, api.NFC_IN_IQ_U8)   # (the kinds i16_scale converts)
+_RECORDED_KINDS = _IQ_KINDS + (api.NFC_IN_ENV_F32,)   # (the kinds `dst` records: the UHD branch's stand-ins and a ready envelope)
 
 
 if _gr is not None:
@@ -98,14 +104,16 @@ else:
     class decoder(object):
         def __init__(self, src="uhd", dst=None, repeat=False, reader=True, tag=True, samp_rate=2e6, emulator=None,
                      wav_scale=0.0, fsm=None, batch=1 << 22, device=0, lo_val=0.1, av_window=2000, max_len=50, keep=None,
-                     iq16_scale=0.0, iq8_scale=0.0):
+                     iq16_scale=0.0, iq8_scale=0.0, record_gain=32767.0):
             """wav_scale: int16 PCM -> float.  0 (default): GNU Radio's wavfile_source normalisation, sample / 32767 (what the
             reference's WAV branch feeds the path, decoder.py:25; third party, unpinned: nfc_amd.h); > 0: sample * wav_scale.
             lo_val / av_window / max_len: transition_sink's keyword arguments (transition_sink.py:12), e.g. scaled with the rate.
             iq16_scale: complex int16 -> float, I and Q each, with wav_scale's meaning (0: / 32767; UHD's own sc16 -> fc32 scaling
             is third party and unpinned: nfc_amd.h).
             iq8_scale: complex int8 / uint8 -> float, I and Q each: sc8 q * s, cu8 (u - 127.5) * s with s = iq8_scale, or 2^-7 where
-            it is not positive (the third-party 8-bit conversions are unpinned: nfc_amd.h)."""
+            it is not positive (the third-party 8-bit conversions are unpinned: nfc_amd.h).
+            dst / record_gain: a 16-bit mono WAV that run() records the envelope to, pcm = round(envelope * record_gain) clamped to
+            +-32767 (nfc_amd.h; 32767 is the inverse of wav_scale's default) -- IQ sources only, see the module's text."""
             if isinstance(src, str) and src == "uhd":
                 raise RuntimeError('the UHD source needs GNU Radio + UHD; pass a recording or an array')
             data, kind, scale = _load_source(src, wav_scale, iq16_scale, iq8_scale)
@@ -116,12 +124,45 @@ else:
             self._trans = transition_sink(samp_rate, self._back.append, lo_val=lo_val, hi_val=hi_val, av_window=av_window, max_len=max_len,
                                           batch=batch, device=device, input_kind=kind, i16_scale=scale if kind in _SCALED_KINDS else 0.0)
             self._batch = int(batch)
+            self._dst = dst if (dst is not None and kind in _RECORDED_KINDS) else None
+            self._rec = (kind, scale if kind in _SCALED_KINDS else 0.0, float(record_gain), int(device), samp_rate)
 
         def run(self):
             """Stream the source through the path (what ``tb.run()`` does in usrp_nfc.py:170)."""
+            if self._dst is not None:
+                return self._run_recording()
             step = self._batch * self._per
             for i in range(0, len(self._data), step):
                 self._trans.push_now(self._data[i:i + step])
+            return self._back
+
+        def _run_recording(self):
+            """run() with ``dst``: each batch is uploaded once, decoded from the device buffer (push_device) and converted to PCM by
+            the record kernel from the same buffer; the PCM comes back and goes into the WAV."""
+            from .record import record
+            kind, scale, gain, device, samp_rate = self._rec
+            data = numpy.ascontiguousarray(self._data, dtype=api._KIND_DTYPE[kind][0]).reshape(-1)
+            step = self._batch * self._per
+            wav = record(self._dst, samp_rate, gain, device)
+            src = pcm = None
+            try:
+                nmax = min(step, len(data)) // self._per
+                src = api.DeviceBuffer(numpy.zeros(0, data.dtype), device, nbytes=nmax * self._per * data.itemsize)
+                pcm = api.DeviceBuffer(numpy.zeros(0, numpy.int16), device, nbytes=2 * nmax)
+                for i in range(0, len(data), step):
+                    piece = data[i:i + step]
+                    n = len(piece) // self._per
+                    if n == 0:
+                        continue
+                    src.upload(piece[:n * self._per])
+                    self._trans.push_device_now(src, n)
+                    api.record_pcm16_device(src, n, pcm, kind, scale, gain, api.NFC_REC_ENVELOPE, device)
+                    wav.write_pcm(pcm.download(2 * n).view(numpy.int16))
+            finally:
+                wav.close()
+                for b in (src, pcm):
+                    if b is not None:
+                        b.free()
             return self._back
 
         @property

@@ -96,6 +96,15 @@ class transition_sink(_Base):
     def push_now(self, x):
         """One batch through the GPU path right away (decoder.run feeds whole pieces of a recording this way)."""
         self._ctx.push(x)   # (any layout NfcContext.push takes: complex int16 as 2n values or (n, 2))
+        self._hand_over()
+
+    def push_device_now(self, dev_ptr, n):
+        """The same for a batch that is already in device memory (16-byte aligned): decoder.run with ``dst`` uploads a batch once,
+        decodes it here and records it from the same buffer."""
+        self._ctx.push_device(dev_ptr, n)
+        self._hand_over()
+
+    def _hand_over(self):
         # one callback per batch, even if empty (transition_sink.py:101)
         self._callback(self._ctx.transitions() if self._want_list else [])
         if self._back is not None:
