@@ -33,6 +33,7 @@ extern "C" {
 /* 3: nfc_stats.reserved0 became decode_respeculated (same layout); the raw float32 envelope takes the fast threshold kernels */
 /* 4: nfc_stats grew (device_allocs, tail_fused, chunks_rerun_in_place) */
 /* (still 4, no structure changed: the input kinds NFC_IN_IQ_I16, NFC_IN_IQ_I8, NFC_IN_IQ_U8; nfc_record_pcm16_device, nfc_host_record_pcm16, nfc_record_tap) */
+/* (still 4, only new types and functions: the multi-stream context nfc_multi, its configuration, statistics and functions) */
 #define NFC_AMD_ABI_VERSION 4
 
 typedef enum {
@@ -366,6 +367,65 @@ int nfc_record_pcm16_device(int device, int tap, int input_kind, float i16_scale
                             float *kernel_ms /* NULL, or the kernel's duration by HIP events */);
 /* steps 1-5 above on the host: the twin of the kernel's conversion, as nfc_host_i16_to_float is of the PCM kind's */
 int16_t nfc_host_record_pcm16(float x, float gain);
+
+/* ---- many independent streams in one launch: a lane per stream ------------------------------------------------------
+ * A context (nfc_ctx) is one stream, and its kernels make one LONG stream fast.  A caller with many SHORT streams -- a directory of
+ * recorded transactions, a rack of SDR channels that each deliver a few thousand samples per scheduler call -- pays a context's whole
+ * launch sequence per stream and push.  nfc_multi holds K streams that share one nfc_params and carries every stream's state across
+ * pushes; one push hands every stream its next piece, and ONE kernel launch walks them all, a GPU lane per stream running
+ * transition_sink.py:55-99 literally (the fp64 window sum in the reference's own order), the routed decoder and the packet framing.
+ * The reference has no counterpart (one flowgraph, one stream).  A push lasts as long as the longest stream's lane, however many
+ * streams there are: measured with captures of 32 768 samples (README.md) it LOSES against a loop over an nfc_ctx at 64 streams (2 x
+ * slower), wins 7 x at 1 024 and 51 x at 16 384, and pays from about 130 streams on (interpolated between those runs).
+ *
+ * PARITY.  After any sequence of pushes, stream k's outputs of the last push -- counts, edges with the 64-bit stream index in idx,
+ * symbols per type, packets, packet bits -- and its state (the nfc_get_state triple) equal those of an nfc_ctx with the same
+ * nfc_params after an nfc_push of the same samples; an nfc_ctx is in turn pinned to the reference.  The fill phase may span pushes.
+ * n[k] == 0 leaves stream k untouched and its outputs empty.  A state exported here and imported into an nfc_ctx (or the other way)
+ * continues identically.
+ * INPUT.  All seven nfc_input_kinds, i16_scale and its limits as in nfc_create.  dev_base is 16-byte aligned; first_sample[k] is
+ * arbitrary (a stream's start has the alignment of one sample, no more); the ranges of different streams may overlap.
+ * REJECTED, with NFC_ERR_ARG, before the device is touched, the offending name in the message: a non-zero nfc_params.flags or
+ * chunk_samples; n_streams or max_push_samples out of range; n[k] > max_push_samples; non-zero reserved fields; a cap_* above 2^26
+ * entries (four times what the longest push can produce of anything).  Device memory the configuration cannot get: NFC_ERR_NOMEM.
+ * CAPACITIES.  Outputs go to per-stream slabs sized at create, so a push never fails because a stream produced more than its slab
+ * holds: the counts are the true totals, what is stored (and read) is the first cap_* entries, the stream's flag bits say which array
+ * was cut, nfc_multi_stats.n_streams_truncated counts such streams, and the stream's carried state has advanced exactly -- it does
+ * not depend on what was stored.  Defaults (a 0 in the configuration): max_push_samples / 4 + 64 edges, as many symbols per type and
+ * packet bits per type, max_push_samples / 16 + 16 packets per type -- twice the densest capture of this tree's generators.  An open
+ * packet longer than cap_pending_bits sets NFC_MULTI_PENDING_OVERFLOW on the stream: its packets are undefined until it is reset;
+ * no other stream is affected.
+ * There is no CPU fallback: create fails without a GPU.  The product build reads no environment variable.  Not thread-safe. */
+typedef struct nfc_multi nfc_multi;            /* K streams, one parameter set; not thread-safe */
+typedef struct {
+    uint32_t n_streams;          /* 1 .. 65536 */
+    uint32_t max_push_samples;   /* longest piece ONE stream gets in one push: 1 .. 2^24 */
+    uint32_t cap_edges, cap_symbols, cap_packets, cap_packet_bits;  /* per stream and push; 0: default from max_push_samples */
+    uint32_t cap_pending_bits;   /* bits of an open packet carried per stream; 0: 4096 */
+    uint32_t reserved[9];        /* must be 0 */
+} nfc_multi_config;              /* 64 bytes */
+enum { NFC_MULTI_TRUNC_EDGES = 1, NFC_MULTI_TRUNC_SYMBOLS = 2, NFC_MULTI_TRUNC_PACKETS = 4, NFC_MULTI_TRUNC_BITS = 8,
+       NFC_MULTI_PENDING_OVERFLOW = 16 /* sticky until the stream is reset */ };
+typedef struct { double ms_kernels; uint64_t n_samples, bytes_in; uint32_t n_launches, n_streams_truncated; uint32_t reserved[8]; } nfc_multi_stats;
+
+int  nfc_multi_create(const nfc_params *p, const nfc_multi_config *c, nfc_multi **out);
+void nfc_multi_destroy(nfc_multi *m);
+const char *nfc_multi_last_error(const nfc_multi *m);   /* m may be NULL: message of the last failed create */
+/* stream k consumes n[k] samples (0 allowed) that start first_sample[k] SAMPLES behind dev_base; n and first_sample are host arrays of n_streams */
+int nfc_multi_push_device(nfc_multi *m, const void *dev_base, const uint64_t *first_sample, const uint32_t *n);
+int nfc_multi_push(nfc_multi *m, const void *const *host_ptrs, const uint32_t *n);   /* staged to the device, then the same */
+/* Outputs of the LAST push, per stream; the readers return what the slab stores (at most cap_* entries, see CAPACITIES). */
+int nfc_multi_get_counts(nfc_multi *m, uint32_t stream, nfc_counts *out, uint32_t *flags_out);
+int nfc_multi_read_edges(nfc_multi *m, uint32_t stream, size_t first, nfc_edge *out, size_t cap, size_t *n_out);
+int nfc_multi_read_symbols(nfc_multi *m, uint32_t stream, int type, size_t first, uint8_t *out, size_t cap, size_t *n_out);
+int nfc_multi_read_packets(nfc_multi *m, uint32_t stream, int type, nfc_packet *out, size_t cap, size_t *n_out);
+int nfc_multi_read_packet_bits(nfc_multi *m, uint32_t stream, int type, size_t first, uint8_t *out, size_t cap, size_t *n_out);
+/* one stream's boundary state, in the form an nfc_ctx exports and imports it */
+int nfc_multi_get_state(nfc_multi *m, uint32_t stream, nfc_state_header *hdr, float *ring, size_t ring_cap, uint8_t *pending, size_t pending_cap);
+int nfc_multi_set_state(nfc_multi *m, uint32_t stream, const nfc_state_header *hdr, const float *ring, size_t ring_len, const uint8_t *pending, size_t pending_len);
+int nfc_multi_reset(nfc_multi *m, int64_t stream /* -1: every stream */);
+int nfc_multi_get_stats(nfc_multi *m, nfc_multi_stats *out);
+int nfc_multi_set_timing(nfc_multi *m, int on);   /* HIP events around the push's launches -> ms_kernels */
 
 /* Device memory helpers so that a caller without HIP bindings (ctypes) can keep its input
  * resident in HBM and use nfc_push_device. */

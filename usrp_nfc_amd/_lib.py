@@ -14,6 +14,8 @@ NFC_IN_IQ_F32, NFC_IN_ENV_F32, NFC_IN_REAL_F32_SQ, NFC_IN_I16_SQ, NFC_IN_IQ_I16,
 NFC_FLAG_FORCE_SEQUENTIAL, NFC_FLAG_NO_EDGES = 1, 2
 NFC_REC_ENVELOPE, NFC_REC_REAL_PART = 0, 1   # nfc_record_tap
 ABI_VERSION = 4   # NFC_AMD_ABI_VERSION of the header these structures mirror
+# per-stream flags of a multi-stream context (nfc_multi_get_counts)
+NFC_MULTI_TRUNC_EDGES, NFC_MULTI_TRUNC_SYMBOLS, NFC_MULTI_TRUNC_PACKETS, NFC_MULTI_TRUNC_BITS, NFC_MULTI_PENDING_OVERFLOW = 1, 2, 4, 8, 16
 
 
 class Params(C.Structure):
@@ -36,6 +38,16 @@ class Stats(C.Structure):
                 ('ms_threshold_kernel', C.c_double * 6), ('n_threshold_timed', C.c_uint32), ('chunk_samples', C.c_uint32),
                 ('ran_ahead', C.c_uint32), ('redone_total', C.c_uint32), ('ring_slots_carried', C.c_uint32), ('decode_respeculated', C.c_uint32),
                 ('device_allocs', C.c_uint32), ('tail_fused', C.c_uint32), ('chunks_rerun_in_place', C.c_uint32)]
+
+
+class MultiConfig(C.Structure):   # nfc_multi_config
+    _fields_ = [('n_streams', C.c_uint32), ('max_push_samples', C.c_uint32), ('cap_edges', C.c_uint32), ('cap_symbols', C.c_uint32),
+                ('cap_packets', C.c_uint32), ('cap_packet_bits', C.c_uint32), ('cap_pending_bits', C.c_uint32), ('reserved', C.c_uint32 * 9)]
+
+
+class MultiStats(C.Structure):   # nfc_multi_stats
+    _fields_ = [('ms_kernels', C.c_double), ('n_samples', C.c_uint64), ('bytes_in', C.c_uint64), ('n_launches', C.c_uint32),
+                ('n_streams_truncated', C.c_uint32), ('reserved', C.c_uint32 * 8)]
 
 
 class Frame(C.Structure):   # nfc_frame
@@ -70,7 +82,10 @@ SYMBOLS = ['nfc_abi_version', 'nfc_device_count', 'nfc_create', 'nfc_destroy', '
            'nfc_stream_sync', 'nfc_device_download_async', 'nfc_device_fill', 'nfc_host_alloc_pinned', 'nfc_host_free_pinned', 'nfc_host_decode_lut', 'nfc_host_miller_classes', 'nfc_host_decode_steps', 'nfc_host_i16_to_float', 'nfc_plan_row_cut',
            'nfc_fsm_create', 'nfc_fsm_destroy', 'nfc_fsm_reset', 'nfc_fsm_process', 'nfc_fsm_process_packets', 'nfc_fsm_process_outgoing', 'nfc_fsm_set_keys',
            'nfc_command_count', 'nfc_command_get', 'nfc_crc_a', 'nfc_tx_encode', 'nfc_tx_sample_count', 'nfc_tx_render_device',
-           'nfc_record_pcm16_device', 'nfc_host_record_pcm16']
+           'nfc_record_pcm16_device', 'nfc_host_record_pcm16',
+           'nfc_multi_create', 'nfc_multi_destroy', 'nfc_multi_last_error', 'nfc_multi_push_device', 'nfc_multi_push', 'nfc_multi_get_counts',
+           'nfc_multi_read_edges', 'nfc_multi_read_symbols', 'nfc_multi_read_packets', 'nfc_multi_read_packet_bits', 'nfc_multi_get_state',
+           'nfc_multi_set_state', 'nfc_multi_reset', 'nfc_multi_get_stats', 'nfc_multi_set_timing']
 
 _libs = {}
 
@@ -160,6 +175,24 @@ def load(path=None):
     L.nfc_record_pcm16_device.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, vp, sz, C.c_float, vp, vp, C.POINTER(C.c_float)]
     L.nfc_host_record_pcm16.argtypes = [C.c_float, C.c_float]
     L.nfc_host_record_pcm16.restype = C.c_int16
+    u32 = C.c_uint32
+    L.nfc_multi_create.argtypes = [C.POINTER(Params), C.POINTER(MultiConfig), C.POINTER(vp)]
+    L.nfc_multi_destroy.argtypes = [vp]
+    L.nfc_multi_destroy.restype = None
+    L.nfc_multi_last_error.argtypes = [vp]
+    L.nfc_multi_last_error.restype = C.c_char_p
+    L.nfc_multi_push_device.argtypes = [vp, vp, vp, vp]
+    L.nfc_multi_push.argtypes = [vp, vp, vp]
+    L.nfc_multi_get_counts.argtypes = [vp, u32, C.POINTER(Counts), C.POINTER(u32)]
+    L.nfc_multi_read_edges.argtypes = [vp, u32, sz, vp, sz, psz]
+    L.nfc_multi_read_symbols.argtypes = [vp, u32, C.c_int, sz, vp, sz, psz]
+    L.nfc_multi_read_packets.argtypes = [vp, u32, C.c_int, vp, sz, psz]
+    L.nfc_multi_read_packet_bits.argtypes = [vp, u32, C.c_int, sz, vp, sz, psz]
+    L.nfc_multi_get_state.argtypes = [vp, u32, C.POINTER(StateHeader), vp, sz, vp, sz]
+    L.nfc_multi_set_state.argtypes = [vp, u32, C.POINTER(StateHeader), vp, sz, vp, sz]
+    L.nfc_multi_reset.argtypes = [vp, C.c_int64]
+    L.nfc_multi_get_stats.argtypes = [vp, C.POINTER(MultiStats)]
+    L.nfc_multi_set_timing.argtypes = [vp, C.c_int]
     for name in SYMBOLS:
         getattr(L, name)
     _libs[path] = L

@@ -1,16 +1,20 @@
-"""Python face of the C-ABI: one NfcContext = one stream (include/nfc_amd.h)."""
+"""Python face of the C-ABI: one NfcContext = one stream, one NfcMultiContext = many streams decoded in one launch
+(include/nfc_amd.h)."""
 import ctypes as C
 
 import numpy as np
 
 from . import _lib
 from ._lib import (EDGE_DTYPE, NFC_FLAG_FORCE_SEQUENTIAL, NFC_FLAG_NO_EDGES, NFC_IN_ENV_F32, NFC_IN_I16_SQ,
-                   NFC_IN_IQ_F32, NFC_IN_IQ_I8, NFC_IN_IQ_I16, NFC_IN_IQ_U8, NFC_IN_REAL_F32_SQ, NFC_REC_ENVELOPE,
+                   NFC_IN_IQ_F32, NFC_IN_IQ_I8, NFC_IN_IQ_I16, NFC_IN_IQ_U8, NFC_IN_REAL_F32_SQ, NFC_MULTI_PENDING_OVERFLOW,
+                   NFC_MULTI_TRUNC_BITS, NFC_MULTI_TRUNC_EDGES, NFC_MULTI_TRUNC_PACKETS, NFC_MULTI_TRUNC_SYMBOLS, NFC_REC_ENVELOPE,
                    NFC_REC_REAL_PART, PACKET_DTYPE)
 
 __all__ = ['NfcContext', 'NfcError', 'DeviceBuffer', 'host_decode_lut', 'host_envelope', 'NFC_IN_IQ_F32', 'NFC_IN_ENV_F32',
            'NFC_IN_REAL_F32_SQ', 'NFC_IN_I16_SQ', 'NFC_IN_IQ_I16', 'NFC_IN_IQ_I8', 'NFC_IN_IQ_U8', 'NFC_FLAG_FORCE_SEQUENTIAL',
-           'NFC_FLAG_NO_EDGES', 'NFC_REC_ENVELOPE', 'NFC_REC_REAL_PART', 'host_record_pcm16', 'record_pcm16_device', 'record_pcm16']
+           'NFC_FLAG_NO_EDGES', 'NFC_REC_ENVELOPE', 'NFC_REC_REAL_PART', 'host_record_pcm16', 'record_pcm16_device', 'record_pcm16',
+           'NfcMultiContext', 'NfcMultiStream', 'NFC_MULTI_TRUNC_EDGES', 'NFC_MULTI_TRUNC_SYMBOLS', 'NFC_MULTI_TRUNC_PACKETS',
+           'NFC_MULTI_TRUNC_BITS', 'NFC_MULTI_PENDING_OVERFLOW']
 
 _KIND_DTYPE = {NFC_IN_IQ_F32: (np.float32, 2), NFC_IN_ENV_F32: (np.float32, 1),
                NFC_IN_REAL_F32_SQ: (np.float32, 1), NFC_IN_I16_SQ: (np.int16, 1), NFC_IN_IQ_I16: (np.int16, 2),
@@ -260,6 +264,201 @@ class NfcContext(object):
         estimated carrier level, idle state machine, decoders reset.  Pushing an overlap region that ends
         where the chunk starts then converges to the true boundary state (multi-GPU)."""
         self._chk(self.L.nfc_prime(self.h, int(start_index), float(np.float32(level))), 'nfc_prime')
+
+
+_MULTI_FLAG_NAMES = ((NFC_MULTI_TRUNC_EDGES, 'NFC_MULTI_TRUNC_EDGES'), (NFC_MULTI_TRUNC_SYMBOLS, 'NFC_MULTI_TRUNC_SYMBOLS'),
+                     (NFC_MULTI_TRUNC_PACKETS, 'NFC_MULTI_TRUNC_PACKETS'), (NFC_MULTI_TRUNC_BITS, 'NFC_MULTI_TRUNC_BITS'),
+                     (NFC_MULTI_PENDING_OVERFLOW, 'NFC_MULTI_PENDING_OVERFLOW'))
+
+
+class NfcMultiContext(object):
+    """n_streams independent streams with one parameter set, decoded in one kernel launch per push -- a GPU lane per stream
+    (nfc_multi, include/nfc_amd.h).  The keywords are NfcContext's; cap_*: entries stored per stream and push (0: the defaults
+    from max_push_samples).  Stream k's outputs and state are what an NfcContext with the same arguments gives for the same
+    samples; ``stream(k)`` is the view that reads them."""
+
+    def __init__(self, n_streams, max_push_samples, samp_rate=2e6, lo_val=0.1, hi_val=1.1, av_window=2000, max_len=50, reader=True,
+                 tag=True, input_kind=NFC_IN_IQ_F32, device=0, i16_scale=0.0, flags=0, chunk_samples=0, cap_edges=0, cap_symbols=0,
+                 cap_packets=0, cap_packet_bits=0, cap_pending_bits=0, lib_path=None, _reserved=0):
+        self.L = _lib.load(lib_path)
+        self.h = C.c_void_p()
+        self.input_kind = input_kind
+        self.factor = 1e6 / samp_rate
+        self.av_window = int(av_window)
+        self.device = int(device)
+        p = _params(samp_rate, lo_val, hi_val, av_window, max_len, reader, tag, input_kind, device, i16_scale, flags, chunk_samples)
+        c = _lib.MultiConfig(int(n_streams), int(max_push_samples), int(cap_edges), int(cap_symbols), int(cap_packets),
+                             int(cap_packet_bits), int(cap_pending_bits))
+        c.reserved[0] = int(_reserved)   # (must be 0: the argument only lets a test see the library refuse it)
+        rc = self.L.nfc_multi_create(C.byref(p), C.byref(c), C.byref(self.h))
+        if rc != 0:
+            self.h = None
+            raise NfcError('nfc_multi_create: %s (status %d)' % (self.L.nfc_multi_last_error(None).decode(), rc))
+        self.n_streams = int(n_streams)
+        self.max_push_samples = int(max_push_samples)
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.L.nfc_multi_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __len__(self):
+        return self.n_streams
+
+    def _chk(self, rc, what):
+        if rc != 0:
+            raise NfcError('%s: %s (status %d)' % (what, self.L.nfc_multi_last_error(self.h).decode(), rc))
+
+    def push(self, arrays):
+        """One host array per stream, in the layouts NfcContext.push takes for the kind; an empty array (or None) gives the stream
+        nothing.  -> the samples consumed per stream."""
+        if len(arrays) != self.n_streams:
+            raise NfcError('push: %d arrays for %d streams' % (len(arrays), self.n_streams))
+        dt, per = _KIND_DTYPE[self.input_kind]
+        keep, ptrs, n = [], (C.c_void_p * self.n_streams)(), np.zeros(self.n_streams, np.uint32)
+        for k, a in enumerate(arrays):
+            a = np.zeros(0, dt) if a is None else np.asarray(a)
+            if a.dtype == np.complex64 and per == 2:
+                a = a.view(np.float32)
+            a = np.ascontiguousarray(a, dtype=dt).reshape(-1)
+            keep.append(a)
+            n[k] = a.size // per
+            ptrs[k] = a.ctypes.data if n[k] else None
+        self._chk(self.L.nfc_multi_push(self.h, ptrs, n.ctypes.data), 'nfc_multi_push')
+        return n
+
+    def push_device(self, buf_or_ptr, first_sample, n):
+        """Stream k takes n[k] samples that start first_sample[k] samples behind the device pointer (16-byte aligned)."""
+        first = np.ascontiguousarray(first_sample, np.uint64)
+        n = np.ascontiguousarray(n, np.uint32)
+        if first.size != self.n_streams or n.size != self.n_streams:
+            raise NfcError('push_device: first_sample and n hold %d / %d entries for %d streams' % (first.size, n.size, self.n_streams))
+        self._chk(self.L.nfc_multi_push_device(self.h, _as_pointer(buf_or_ptr), first.ctypes.data, n.ctypes.data), 'nfc_multi_push_device')
+        return n
+
+    def stream(self, k, allow_truncated=False):
+        if not 0 <= int(k) < self.n_streams:
+            raise NfcError('stream %d out of range (n_streams %d)' % (k, self.n_streams))
+        return NfcMultiStream(self, int(k), allow_truncated)
+
+    def reset(self, stream=-1):
+        """A new stream in place of stream k (default: of every one), keeping the device buffers."""
+        self._chk(self.L.nfc_multi_reset(self.h, int(stream)), 'nfc_multi_reset')
+
+    def stats(self):
+        s = _lib.MultiStats()
+        self._chk(self.L.nfc_multi_get_stats(self.h, C.byref(s)), 'nfc_multi_get_stats')
+        return s
+
+    def set_timing(self, on):
+        """HIP events around the push's launch: stats().ms_kernels."""
+        self._chk(self.L.nfc_multi_set_timing(self.h, int(bool(on))), 'nfc_multi_set_timing')
+
+
+class NfcMultiStream(object):
+    """One stream of an NfcMultiContext: the reading side of an NfcContext (counts, edges, transitions, symbols, packets, state), so
+    that background._deliver(view) works unchanged.  Reading an array that the stream's slab cut short raises NfcError naming the
+    flag, unless allow_truncated: then what was stored -- the first cap_* entries -- comes back."""
+
+    def __init__(self, multi, k, allow_truncated=False):
+        self.m, self.k, self.allow_truncated = multi, k, allow_truncated
+        self.factor = multi.factor
+
+    def _counts(self):
+        c, f = _lib.Counts(), C.c_uint32(0)
+        self.m._chk(self.m.L.nfc_multi_get_counts(self.m.h, self.k, C.byref(c), C.byref(f)), 'nfc_multi_get_counts')
+        return c, int(f.value)
+
+    def counts(self):
+        return self._counts()[0]
+
+    def flags(self):
+        return self._counts()[1]
+
+    def _stored(self, total, bit, allow):
+        """How many of `total` entries to read; a cut array raises unless allowed."""
+        f = self.flags()
+        bad = f & (bit | NFC_MULTI_PENDING_OVERFLOW if bit in (NFC_MULTI_TRUNC_PACKETS, NFC_MULTI_TRUNC_BITS) else bit)
+        if bad and not (self.allow_truncated if allow is None else allow):
+            raise NfcError('stream %d: %s (pass allow_truncated=True for what was stored)'
+                           % (self.k, ' | '.join(nm for v, nm in _MULTI_FLAG_NAMES if bad & v)))
+        return int(total)
+
+    def _read(self, fn, total, dtype, *lead):
+        out = np.zeros(int(total), dtype)
+        got = C.c_size_t(0)
+        if total:
+            self.m._chk(fn(self.m.h, self.k, *lead, out.ctypes.data, out.size, C.byref(got)), fn.__name__)
+        return out[:got.value]
+
+    def edges(self, allow_truncated=None):
+        n = self._stored(self.counts().n_edges, NFC_MULTI_TRUNC_EDGES, allow_truncated)
+        return self._read(self.m.L.nfc_multi_read_edges, n, EDGE_DTYPE, 0)
+
+    def transitions(self, allow_truncated=None):
+        e = self.edges(allow_truncated)
+        f = self.factor
+        return [((int(v), int(d) * f), int(t)) for v, d, t in zip(e['v'], e['d'], e['t'])]
+
+    def symbols(self, ptype, allow_truncated=None):
+        n = self._stored(self.counts().n_symbols[ptype], NFC_MULTI_TRUNC_SYMBOLS, allow_truncated)
+        return self._read(self.m.L.nfc_multi_read_symbols, n, np.uint8, ptype, 0)
+
+    def packet_table(self, ptype, allow_truncated=None):
+        n = self._stored(self.counts().n_packets[ptype], NFC_MULTI_TRUNC_PACKETS, allow_truncated)
+        out = np.zeros(n, PACKET_DTYPE)
+        got = C.c_size_t(0)
+        if n:
+            self.m._chk(self.m.L.nfc_multi_read_packets(self.m.h, self.k, ptype, out.ctypes.data, out.size, C.byref(got)), 'nfc_multi_read_packets')
+        return out[:got.value]
+
+    def packet_bits(self, ptype, allow_truncated=None):
+        """The per-type bit array the packet table's bit_off / n_bits index."""
+        n = self._stored(self.counts().n_packet_bits[ptype], NFC_MULTI_TRUNC_BITS, allow_truncated)
+        return self._read(self.m.L.nfc_multi_read_packet_bits, n, np.uint8, ptype, 0)
+
+    def packets(self, allow_truncated=None):
+        """Closed packets of both types in stream order: [(type, [bits]), ...] (NfcContext.packets)."""
+        items = []
+        for t in (0, 1):
+            tab = self.packet_table(t, allow_truncated)
+            if not len(tab):
+                continue
+            bits = self.packet_bits(t, allow_truncated)
+            for p in tab:
+                o = int(p['bit_off'])
+                if o + int(p['n_bits']) <= len(bits):   # (a cut bit array: the packets it still holds whole)
+                    items.append((int(p['idx']), t, bits[o:o + int(p['n_bits'])].tolist()))
+        items.sort(key=lambda r: r[0])
+        return [(t, b) for _, t, b in items]
+
+    def get_state(self):
+        """(header, ring float32[av_window], [pending bits type 0, pending bits type 1]) -- NfcContext.get_state's."""
+        L, h = self.m.L, _lib.StateHeader()
+        self.m._chk(L.nfc_multi_get_state(self.m.h, self.k, C.byref(h), None, 0, None, 0), 'nfc_multi_get_state')
+        ring = np.zeros(h.av_window, np.float32)
+        p0, p1 = int(h.n_pending_bits[0]), int(h.n_pending_bits[1])
+        pend = np.zeros(p0 + p1, np.uint8)
+        self.m._chk(L.nfc_multi_get_state(self.m.h, self.k, C.byref(h), ring.ctypes.data, ring.size, pend.ctypes.data, pend.size),
+                    'nfc_multi_get_state')
+        return h, ring, [pend[:p0].copy(), pend[p0:].copy()]
+
+    def set_state(self, header, ring, pending=None):
+        ring = np.ascontiguousarray(ring, np.float32)
+        pend = np.zeros(0, np.uint8) if pending is None else np.ascontiguousarray(np.concatenate(pending), np.uint8)
+        self.m._chk(self.m.L.nfc_multi_set_state(self.m.h, self.k, C.byref(header), ring.ctypes.data, ring.size, pend.ctypes.data, pend.size),
+                    'nfc_multi_set_state')
+
+    def reset(self):
+        self.m.reset(self.k)
 
 
 class DeviceBuffer(object):

@@ -23,13 +23,15 @@ class _Recorder(object):
 
 
 class background(object):
-    def __init__(self, reader=False, tag=False, emulator=None, fsm=None, keep=None, samp_rate=2e6, max_len=50, device=0):
+    def __init__(self, reader=False, tag=False, emulator=None, fsm=None, keep=None, samp_rate=2e6, max_len=50, device=0, attached=False):
         """keep: how many packets / symbols of the stream stay in ``self.packets`` / ``self.symbols`` -- None: everything (offline
         decodes, tests), 0: nothing (the reference keeps nothing: a long live capture must not grow without bound), N: the last N.
         samp_rate, max_len: only for transition lists that did NOT come from this package's transition_sink (``append`` below):
-        their durations are microseconds, the device decoders count samples (the reference's defaults, transition_sink.py:12)."""
+        their durations are microseconds, the device decoders count samples (the reference's defaults, transition_sink.py:12).
+        attached: a device context of this package decodes for this object and its owner calls ``deliver`` (decoder.decode_many, a
+        multi-stream context's view per channel: INTEGRATION.md): ``append`` then only records, as under this package's transition_sink."""
         import collections
-        self._attached = False       # this package's transition_sink feeds this object (it decodes on the device and delivers itself)
+        self._attached = bool(attached)   # this package's transition_sink feeds this object (it decodes on the device and delivers itself)
         self._foreign = None         # the context that decodes lists handed to append() by anybody else
         self._foreign_args = dict(samp_rate=float(samp_rate), max_len=int(max_len), device=int(device))
         self._n_foreign = 0
@@ -59,6 +61,11 @@ class background(object):
                 else:
                     fsm = _own_fsm.fsm()
         self._fsm = fsm
+
+    @property
+    def fsm(self):
+        """The protocol machine the packets go to."""
+        return self._fsm
 
     # -- reference surface ---------------------------------------------------------
     def append(self, transitions):
@@ -115,6 +122,11 @@ class background(object):
             pass
 
     # -- GPU delivery (called by transition_sink after each batch) ---------------------
+    def deliver(self, ctx):
+        """Hand on what ``ctx`` -- an NfcContext, or a stream view of an NfcMultiContext -- decoded in its last push: symbols and
+        packets are kept as ``keep`` says, every packet goes to ``fsm.process_bits``.  For a ``background(attached=True)``."""
+        self._deliver(ctx)
+
     def _deliver(self, ctx):
         if self._keep != 0:
             for t in (PacketType.TAG_TO_READER, PacketType.READER_TO_TAG):

@@ -1,0 +1,701 @@
+// nfc_multi.hip -- the multi-stream context (nfc_multi, include/nfc_amd.h) in a translation unit of its own: K independent streams
+// with one parameter set, decoded a lane per stream by k_multi<KIND> (multi.hip.h), and the C-ABI around it.  The non-template
+// kernels of threshold.hip.h / edges.hip.h are nfc_amd.hip's: here they are `static` (NFC_HDR_KERNEL_LINKAGE) and never launched.
+//
+// A push: the streams' (first_sample, n) and the lane order go up in one copy, ONE launch walks every stream, one copy brings
+// all counts and flags back to pinned memory, one wait.  Everything else stays in the per-stream slabs until it is read.
+#include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#define NFC_HDR_KERNEL_LINKAGE static
+#include "../../include/nfc_amd.h"
+#include "launch_check.h"
+#include "decoder_tables.h"
+#include "multi.hip.h"
+#include "scale_arg.h"
+
+using namespace nfc;
+using namespace nfc::multi;
+
+static_assert(sizeof(nfc_multi_config) == 64, "nfc_multi_config is 64 bytes");
+static_assert(F_EDGES == NFC_MULTI_TRUNC_EDGES && F_SYMBOLS == NFC_MULTI_TRUNC_SYMBOLS && F_PACKETS == NFC_MULTI_TRUNC_PACKETS &&
+                  F_BITS == NFC_MULTI_TRUNC_BITS && F_PENDING == NFC_MULTI_PENDING_OVERFLOW,
+              "the kernel's flag bits are the header's");
+
+struct nfc_multi {
+    nfc_params P;
+    uint32_t K = 0, max_push = 0;
+    int L = 0, mx = 0, nd = 0;
+    float scale = 0.f;
+    size_t bps = 0;   // input bytes per sample
+    Caps C;
+    Args A;           // everything of the launch that does not change from push to push
+    hipStream_t st = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    int timing = 0;
+    std::vector<void *> dev;   // every device allocation
+    uint8_t *h_up = nullptr;   // pinned: first_sample (u64) | n (u32) | order (u32), K each
+    uint8_t *d_up = nullptr;
+    uint32_t *h_counts = nullptr;   // pinned mirror of the counts
+    uint8_t *d_blob = nullptr, *h_blob = nullptr;   // one stream's state (k_multi_state_io)
+    size_t blob_bytes = 0;
+    uint8_t *h_stage = nullptr, *d_stage = nullptr;   // nfc_multi_push: the host arrays packed, and their place on the device
+    size_t stage_cap = 0;
+    uint8_t *h_read = nullptr;   // pinned staging of the readers
+    size_t read_cap = 0;
+    std::vector<uint64_t> nseen, g0;   // samples consumed so far / before the last push, per stream
+    std::vector<uint32_t> last_n;
+    std::vector<std::pair<void *, size_t>> guards;   // (slab, row stride in bytes) -- rows end in GUARD_BYTES of the guard word
+    std::vector<size_t> guard_row;                   // payload bytes per row
+    uint8_t canon[16];
+    bool have_outputs = false;
+    nfc_multi_stats stats;
+    std::string err;
+    LaunchError launch_err;
+};
+
+namespace {
+std::string g_multi_create_error;
+
+int mfail(nfc_multi *m, int code, const char *fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    if (m) m->err = buf;
+    else g_multi_create_error = buf;
+    return code;
+}
+
+#define MCHK(m, call)                                                                                                       \
+    do {                                                                                                                    \
+        hipError_t e__ = (call);                                                                                            \
+        if (e__ != hipSuccess) return mfail((m), NFC_ERR_DEVICE, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e__), __FILE__, __LINE__); \
+    } while (0)
+
+using MultiKernel = void (*)(Args);
+MultiKernel kernel_of(int kind) {
+    switch (kind) {
+    case NFC_IN_IQ_F32: return k_multi<IN_IQ_F32>;
+    case NFC_IN_ENV_F32: return k_multi<IN_ENV_F32>;
+    case NFC_IN_REAL_F32_SQ: return k_multi<IN_REAL_F32_SQ>;
+    case NFC_IN_IQ_I16: return k_multi<IN_IQ_I16>;
+    case NFC_IN_IQ_I8: return k_multi<IN_IQ_I8>;
+    case NFC_IN_IQ_U8: return k_multi<IN_IQ_U8>;
+    default: return k_multi<IN_I16_SQ>;
+    }
+}
+
+int launch_ok(nfc_multi *m) {
+    LaunchError &le = launch_error();
+    if (le.err == hipSuccess) return NFC_OK;
+    const LaunchError e = le;
+    le = LaunchError{};
+    return mfail(m, NFC_ERR_DEVICE, "kernel launch failed: %s (%s:%d)", hipGetErrorString(e.err), e.file, e.line);
+}
+
+// a slab of K rows, each `row` payload bytes and GUARD_BYTES of the guard word behind them
+template <class T>
+int alloc_slab(nfc_multi *m, T **out, size_t row_bytes) {
+    const size_t stride = row_bytes + GUARD_BYTES, total = stride * m->K;
+    void *p = nullptr;
+    if (hipMalloc(&p, total) != hipSuccess) {
+        (void)hipGetLastError();
+        return mfail(nullptr, NFC_ERR_NOMEM, "nfc_multi_create: no device memory for a slab of %zu bytes (n_streams %u)", total, m->K);
+    }
+    m->dev.push_back(p);
+    m->guards.emplace_back(p, stride);
+    m->guard_row.push_back(row_bytes);
+    *out = (T *)p;
+    return NFC_OK;
+}
+template <class T>
+int alloc_plain(nfc_multi *m, T **out, size_t bytes) {
+    void *p = nullptr;
+    if (hipMalloc(&p, std::max<size_t>(bytes, 16)) != hipSuccess) {
+        (void)hipGetLastError();
+        return mfail(nullptr, NFC_ERR_NOMEM, "nfc_multi_create: no device memory for %zu bytes (n_streams %u)", bytes, m->K);
+    }
+    m->dev.push_back(p);
+    *out = (T *)p;
+    return NFC_OK;
+}
+
+__global__ __launch_bounds__(256) void k_multi_guard_fill(uint8_t *slab, size_t stride, size_t row, uint32_t K) {
+    const size_t words = (size_t)K * (GUARD_BYTES / 4), step = (size_t)gridDim.x * 256;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < words; i += step) {
+        const size_t k = i / (GUARD_BYTES / 4), w = i % (GUARD_BYTES / 4);
+        uint8_t *g = slab + k * stride + row + w * 4;
+        for (int b = 0; b < 4; b++) g[b] = (uint8_t)(GUARD_WORD >> (8 * b));   // (a row's end is only as aligned as its entries)
+    }
+}
+__global__ __launch_bounds__(256) void k_multi_guard_check(const uint8_t *slab, size_t stride, size_t row, uint32_t K, uint32_t *bad) {
+    const size_t words = (size_t)K * (GUARD_BYTES / 4), step = (size_t)gridDim.x * 256;
+    uint32_t mine = 0;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < words; i += step) {
+        const size_t k = i / (GUARD_BYTES / 4), w = i % (GUARD_BYTES / 4);
+        const uint8_t *g = slab + k * stride + row + w * 4;
+        for (int b = 0; b < 4; b++) mine += g[b] != (uint8_t)(GUARD_WORD >> (8 * b));
+    }
+    if (mine) atomicAdd(bad, mine);
+}
+
+int ensure_read(nfc_multi *m, size_t bytes) {
+    if (m->read_cap >= bytes) return NFC_OK;
+    if (m->h_read) (void)hipHostFree(m->h_read);
+    m->h_read = nullptr;
+    m->read_cap = 0;
+    const size_t cap = bytes + bytes / 2 + 4096;
+    MCHK(m, hipHostMalloc((void **)&m->h_read, cap, hipHostMallocDefault));
+    m->read_cap = cap;
+    return NFC_OK;
+}
+
+// [first, first + n) of a stream's row, n cut to what the slab stores and the caller's room
+int read_row(nfc_multi *m, const void *slab, size_t stride_entries, size_t esz, uint32_t stream, size_t stored, size_t first, void *out,
+             size_t cap, size_t *n_out) {
+    size_t n = 0;
+    if (first < stored) n = std::min(cap, stored - first);
+    if (n && !out) return mfail(m, NFC_ERR_ARG, "null output");
+    if (n) {
+        if (int rc = ensure_read(m, n * esz)) return rc;
+        MCHK(m, hipMemcpyAsync(m->h_read, (const char *)slab + ((size_t)stream * stride_entries + first) * esz, n * esz, hipMemcpyDeviceToHost, m->st));
+        MCHK(m, hipStreamSynchronize(m->st));
+        memcpy(out, m->h_read, n * esz);
+    }
+    if (n_out) *n_out = n;
+    return NFC_OK;
+}
+
+int check_stream(nfc_multi *m, uint32_t stream, bool outputs) {
+    if (stream >= m->K) return mfail(m, NFC_ERR_ARG, "stream %u out of range (n_streams %u)", stream, m->K);
+    if (outputs && !m->have_outputs) return mfail(m, NFC_ERR_STATE, "no completed push");
+    if (hipSetDevice(m->P.device) != hipSuccess) return mfail(m, NFC_ERR_DEVICE, "hipSetDevice failed");
+    return NFC_OK;
+}
+
+int state_io(nfc_multi *m, uint32_t k, int set) {
+    NFC_LAUNCH(k_multi_state_io, dim3(1), dim3(256), 0, m->st, m->A.S, m->C, m->K, k, m->L, set, m->d_blob);
+    return launch_ok(m);
+}
+}  // namespace
+
+extern "C" {
+
+const char *nfc_multi_last_error(const nfc_multi *m) { return m ? m->err.c_str() : g_multi_create_error.c_str(); }
+
+void nfc_multi_destroy(nfc_multi *m) {
+    if (!m) return;
+    (void)hipSetDevice(m->P.device);
+    if (m->st) (void)hipStreamSynchronize(m->st);
+    for (void *p : m->dev) (void)hipFree(p);
+    if (m->d_stage) (void)hipFree(m->d_stage);
+    for (uint8_t *p : {m->h_up, (uint8_t *)m->h_counts, m->h_blob, m->h_stage, m->h_read})
+        if (p) (void)hipHostFree(p);
+    for (hipEvent_t e : m->ev)
+        if (e) (void)hipEventDestroy(e);
+    if (m->st) (void)hipStreamDestroy(m->st);
+    delete m;
+}
+
+int nfc_multi_create(const nfc_params *p, const nfc_multi_config *c, nfc_multi **out) {
+    if (!p || !c || !out) return mfail(nullptr, NFC_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (!(p->samp_rate > 0)) return mfail(nullptr, NFC_ERR_ARG, "samp_rate must be positive");
+    if (p->av_window < 1 || p->av_window > 30000) return mfail(nullptr, NFC_ERR_ARG, "av_window must be in [1, 30000]");
+    if (p->max_len < 1 || p->max_len > 4000) return mfail(nullptr, NFC_ERR_ARG, "max_len must be in [1, 4000]");
+    if (p->input_kind < 0 || p->input_kind > 6) return mfail(nullptr, NFC_ERR_ARG, "unknown input_kind");
+    if (p->flags != 0) return mfail(nullptr, NFC_ERR_ARG, "nfc_params.flags must be 0 for a multi-stream context");
+    if (p->chunk_samples != 0) return mfail(nullptr, NFC_ERR_ARG, "nfc_params.chunk_samples must be 0 for a multi-stream context");
+    if (c->n_streams < 1 || c->n_streams > 65536) return mfail(nullptr, NFC_ERR_ARG, "n_streams must be in [1, 65536]");
+    if (c->max_push_samples < 1 || c->max_push_samples > (1u << 24)) return mfail(nullptr, NFC_ERR_ARG, "max_push_samples must be in [1, 2^24]");
+    for (int i = 0; i < 9; i++)
+        if (c->reserved[i] != 0) return mfail(nullptr, NFC_ERR_ARG, "nfc_multi_config.reserved must be 0");
+    // A caller's capacity is bounded so that a row stride (uint32, in entries: Caps) cannot wrap and rows of different streams
+    // cannot overlap: 2^26 entries is four times what the longest push (2^24 samples) can produce of anything.
+    {
+        const struct { const char *name; uint32_t v; } caps[] = {{"cap_edges", c->cap_edges}, {"cap_symbols", c->cap_symbols}, {"cap_packets", c->cap_packets},
+                                                                 {"cap_packet_bits", c->cap_packet_bits}, {"cap_pending_bits", c->cap_pending_bits}};
+        for (const auto &cp : caps)
+            if (cp.v > MAX_CAP) return mfail(nullptr, NFC_ERR_ARG, "%s = %u exceeds %u", cp.name, cp.v, MAX_CAP);
+    }
+    float scale_arg = 0.f;
+    if (const char *bad = kernel_scale_arg(p->input_kind, p->i16_scale, &scale_arg)) return mfail(nullptr, NFC_ERR_ARG, "%s", bad);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return mfail(nullptr, NFC_ERR_DEVICE, "no HIP device: this library has no CPU fallback");
+    if (p->device < 0 || p->device >= ndev) return mfail(nullptr, NFC_ERR_ARG, "device %d out of range (%d devices)", p->device, ndev);
+    if (hipSetDevice(p->device) != hipSuccess) return mfail(nullptr, NFC_ERR_DEVICE, "hipSetDevice failed");
+
+    nfc_multi *m = new nfc_multi();
+    m->P = *p;
+    m->K = c->n_streams;
+    m->max_push = c->max_push_samples;
+    m->L = p->av_window;
+    m->mx = p->max_len;
+    m->nd = m->mx + 1;
+    m->scale = scale_arg;
+    static const size_t bps[7] = {8, 4, 4, 2, 4, 2, 2};
+    m->bps = bps[p->input_kind];
+    memset(&m->stats, 0, sizeof m->stats);
+    const uint32_t K = m->K;
+    // Capacities per stream and push.  Entries are 6-13 % of the samples on every capture of this tree's generators (the densest:
+    // 0.133 edges and 0.10 symbols of one type per sample): a quarter of the samples is room to spare.  A non-empty packet takes a
+    // start bit, a bit and the symbol that closes it: at most a third of the symbols close one -- a sixteenth of the samples.
+    const uint32_t dflt = m->max_push / 4 + 64;
+    Caps &C = m->C;
+    C.edges = c->cap_edges ? c->cap_edges : dflt;
+    C.symbols = c->cap_symbols ? c->cap_symbols : dflt;
+    C.bits = c->cap_packet_bits ? c->cap_packet_bits : dflt;
+    C.packets = c->cap_packets ? c->cap_packets : m->max_push / 16 + 16;
+    C.pending = c->cap_pending_bits ? c->cap_pending_bits : 4096;
+    // (row strides in entries: the guard behind a row is GUARD_BYTES whatever the entry size -- alloc_slab)
+    C.s_epos = C.edges + GUARD_BYTES / 4;
+    C.s_ecode = C.edges + GUARD_BYTES / 2;
+    C.s_symbols = C.symbols + GUARD_BYTES;
+    C.s_bits = C.bits + GUARD_BYTES;
+    C.s_packets = C.packets + GUARD_BYTES / 8;
+    C.s_pending = C.pending + GUARD_BYTES;
+
+#define CRT(call)                                                                                              \
+    do {                                                                                                       \
+        hipError_t e__ = (call);                                                                               \
+        if (e__ != hipSuccess) {                                                                               \
+            const int rc__ = mfail(nullptr, e__ == hipErrorOutOfMemory ? NFC_ERR_NOMEM : NFC_ERR_DEVICE, "nfc_multi_create: %s failed: %s", #call, hipGetErrorString(e__)); \
+            (void)hipGetLastError();                                                                           \
+            nfc_multi_destroy(m);                                                                              \
+            return rc__;                                                                                       \
+        }                                                                                                      \
+    } while (0)
+#define CRC(call)                      \
+    do {                               \
+        const int rc__ = (call);       \
+        if (rc__) {                    \
+            nfc_multi_destroy(m);      \
+            return rc__;               \
+        }                              \
+    } while (0)
+
+    CRT(hipStreamCreateWithFlags(&m->st, hipStreamNonBlocking));
+    CRT(hipEventCreate(&m->ev[0]));
+    CRT(hipEventCreate(&m->ev[1]));
+    Args &A = m->A;
+    memset(&A, 0, sizeof A);
+    State &S = A.S;
+    Out &O = A.O;
+    CRC(alloc_plain(m, &S.ss, (size_t)K * 8));
+    CRC(alloc_plain(m, &S.slot, (size_t)K * 4));
+    CRC(alloc_plain(m, &S.filled, (size_t)K * 4));
+    CRC(alloc_plain(m, &S.edge, (size_t)K * 4));
+    CRC(alloc_plain(m, &S.dec, (size_t)K * 4));
+    CRC(alloc_plain(m, &S.npend[0], (size_t)K * 4));
+    CRC(alloc_plain(m, &S.npend[1], (size_t)K * 4));
+    CRC(alloc_plain(m, &S.flags, (size_t)K * 4));
+    CRC(alloc_plain(m, &S.ring, (size_t)K * 4 * (size_t)m->L));
+    CRC(alloc_plain(m, &O.counts, (size_t)K * CNT_WORDS * 4));
+    CRC(alloc_plain(m, &m->d_up, (size_t)K * 16));
+    m->blob_bytes = sizeof(IoHeader) + (size_t)m->L * 4 + 2 * (size_t)C.pending;
+    CRC(alloc_plain(m, &m->d_blob, m->blob_bytes));
+    for (int t = 0; t < 2; t++) {
+        CRC(alloc_slab(m, &S.pending[t], (size_t)C.pending));
+        CRC(alloc_slab(m, &O.sym[t], (size_t)C.symbols));
+        CRC(alloc_slab(m, &O.bits[t], (size_t)C.bits));
+        CRC(alloc_slab(m, &O.close[t], (size_t)C.packets * 8));
+    }
+    CRC(alloc_slab(m, &O.epos, (size_t)C.edges * 4));
+    CRC(alloc_slab(m, &O.ecode, (size_t)C.edges * 2));
+    CRT(hipHostMalloc((void **)&m->h_up, (size_t)K * 16, hipHostMallocDefault));
+    CRT(hipHostMalloc((void **)&m->h_counts, (size_t)K * CNT_WORDS * 4, hipHostMallocDefault));
+    CRT(hipHostMalloc((void **)&m->h_blob, m->blob_bytes, hipHostMallocDefault));
+    memset(m->h_counts, 0, (size_t)K * CNT_WORDS * 4);
+
+    // decoder LUTs in the walking form: next state | out byte << 8 per (LUT row, state)
+    {
+        const DecoderTables t = build_tables(p->samp_rate, m->mx);
+        std::vector<uint16_t> mils(t.miller_map.size() * 16), mans(t.manch_map.size() * 8);
+        for (size_t i = 0; i < t.miller_map.size(); i++)
+            for (int s = 0; s < 16; s++) mils[i * 16 + s] = (uint16_t)(((t.miller_map[i] >> (4 * s)) & 15u) | (t.miller_out[i * 16 + s] << 8));
+        for (size_t i = 0; i < t.manch_map.size(); i++)
+            for (int s = 0; s < 8; s++) mans[i * 8 + s] = (uint16_t)(((t.manch_map[i] >> (4 * s)) & 15u) | (t.manch_out[i * 8 + s] << 8));
+        uint16_t *d_mil = nullptr, *d_man = nullptr;
+        CRC(alloc_plain(m, &d_mil, mils.size() * 2));
+        CRC(alloc_plain(m, &d_man, mans.size() * 2));
+        CRT(hipMemcpy(d_mil, mils.data(), mils.size() * 2, hipMemcpyHostToDevice));
+        CRT(hipMemcpy(d_man, mans.data(), mans.size() * 2, hipMemcpyHostToDevice));
+        A.mil_step = d_mil;
+        A.man_step = d_man;
+        // the carried Miller state is published as the canonical state of its class, as nfc_get_state publishes it (decoder_tables.h)
+        const MillerQuotient q = miller_quotient(t);
+        for (int k = 0; k < 16; k++) m->canon[k] = q.ok ? q.canon[k] : (uint8_t)k;
+    }
+    A.first = (const uint64_t *)m->d_up;
+    A.n = (const uint32_t *)(m->d_up + (size_t)K * 8);
+    A.order = (const uint32_t *)(m->d_up + (size_t)K * 12);
+    A.K = K;
+    A.L = m->L;
+    A.mx = m->mx;
+    A.nd = m->nd;
+    A.reader = p->enable_reader != 0;
+    A.tag = p->enable_tag != 0;
+    A.scale = m->scale;
+    A.lo = p->lo_val;
+    A.hi = p->hi_val;
+    A.hi_plus = p->hi_val + 0.1;   // transition_sink.py:63
+    {   // the products that decide a comparison against lo / hi without the division (nfc_create: the same bands)
+        const double eps = std::ldexp(1.0, -48);
+        A.lo_a = p->lo_val - std::fabs(p->lo_val) * eps;
+        A.lo_b = p->lo_val + std::fabs(p->lo_val) * eps;
+        A.hi_a = p->hi_val - std::fabs(p->hi_val) * eps;
+        A.hi_b = p->hi_val + std::fabs(p->hi_val) * eps;
+        auto sane = [](double v) { return v == 0 || (std::fabs(v) > 1e-100 && std::fabs(v) < 1e100); };
+        A.bands_ok = sane(p->lo_val) && sane(p->hi_val) && std::isfinite(p->lo_val) && std::isfinite(p->hi_val);
+    }
+    A.C = C;
+    m->nseen.assign(K, 0);
+    m->g0.assign(K, 0);
+    m->last_n.assign(K, 0);
+
+    LaunchScope scope(&m->launch_err);
+    for (size_t i = 0; i < m->guards.size(); i++)
+        NFC_LAUNCH(k_multi_guard_fill, dim3(std::min<uint32_t>(1024, (K * 4 + 255) / 256)), dim3(256), 0, m->st, (uint8_t *)m->guards[i].first,
+                   m->guards[i].second, m->guard_row[i], K);
+    NFC_LAUNCH(k_multi_reset, dim3(1024), dim3(256), 0, m->st, S, K, 0u, K, m->L, O.counts);
+    CRC(launch_ok(nullptr));
+    CRT(hipStreamSynchronize(m->st));
+#undef CRT
+#undef CRC
+    *out = m;
+    return NFC_OK;
+}
+
+int nfc_multi_push_device(nfc_multi *m, const void *dev_base, const uint64_t *first_sample, const uint32_t *n) {
+    if (!m) return NFC_ERR_ARG;
+    LaunchScope scope(&m->launch_err);
+    if (!first_sample || !n) return mfail(m, NFC_ERR_ARG, "null first_sample / n");
+    const uint32_t K = m->K;
+    uint64_t total = 0;
+    uint32_t nmax = 0, nmin = UINT32_MAX;
+    for (uint32_t k = 0; k < K; k++) {
+        if (n[k] > m->max_push) return mfail(m, NFC_ERR_ARG, "n[%u] = %u exceeds max_push_samples = %u", k, n[k], m->max_push);
+        total += n[k];
+        nmax = std::max(nmax, n[k]);
+        nmin = std::min(nmin, n[k]);
+    }
+    if (total && !dev_base) return mfail(m, NFC_ERR_ARG, "null dev_base");
+    if ((uintptr_t)dev_base & 15u) return mfail(m, NFC_ERR_ARG, "dev_base must be 16-byte aligned");
+    if (hipSetDevice(m->P.device) != hipSuccess) return mfail(m, NFC_ERR_DEVICE, "hipSetDevice failed");
+    uint64_t *hf = (uint64_t *)m->h_up;
+    uint32_t *hn = (uint32_t *)(m->h_up + (size_t)K * 8), *ho = (uint32_t *)(m->h_up + (size_t)K * 12);
+    memcpy(hf, first_sample, (size_t)K * 8);
+    memcpy(hn, n, (size_t)K * 4);
+    // Lanes of a wave walk until the longest of their streams ends: streams go to lanes by length, longest first, in classes of
+    // 512 samples and in the caller's order within a class (so streams of one length keep their neighbours, and the window rows
+    // their consecutive addresses).  The public stream index stays the caller's: `order` only says which lane walks it.
+    if ((nmax + 511) / 512 == (nmin + 511) / 512) {
+        for (uint32_t k = 0; k < K; k++) ho[k] = k;
+    } else {
+        const uint32_t classes = (nmax + 511) / 512 + 1;
+        std::vector<uint32_t> at(classes + 1, 0);
+        for (uint32_t k = 0; k < K; k++) at[classes - 1 - (n[k] + 511) / 512 + 1]++;
+        for (uint32_t i = 0; i < classes; i++) at[i + 1] += at[i];
+        for (uint32_t k = 0; k < K; k++) ho[at[classes - 1 - (n[k] + 511) / 512]++] = k;
+    }
+    MCHK(m, hipMemcpyAsync(m->d_up, m->h_up, (size_t)K * 16, hipMemcpyHostToDevice, m->st));
+    Args A = m->A;
+    A.in = dev_base;
+    const dim3 grid((K + MB - 1) / MB), block(MB);
+    if (m->timing) NFC_LAUNCH_EXT(kernel_of(m->P.input_kind), grid, block, 0, m->st, m->ev[0], m->ev[1], 0, A);
+    else NFC_LAUNCH(kernel_of(m->P.input_kind), grid, block, 0, m->st, A);
+    MCHK(m, hipMemcpyAsync(m->h_counts, A.O.counts, (size_t)K * CNT_WORDS * 4, hipMemcpyDeviceToHost, m->st));
+    MCHK(m, hipStreamSynchronize(m->st));
+    if (int rc = launch_ok(m)) return rc;
+    uint32_t cut = 0;
+    for (uint32_t k = 0; k < K; k++) {
+        m->g0[k] = m->nseen[k];
+        m->nseen[k] += n[k];
+        m->last_n[k] = n[k];
+        cut += (m->h_counts[(size_t)k * CNT_WORDS + CNT_FLAGS] & 15u) != 0;
+    }
+    m->have_outputs = true;
+    m->stats.ms_kernels = 0;
+    if (m->timing) {
+        float ms = 0.f;
+        MCHK(m, hipEventElapsedTime(&ms, m->ev[0], m->ev[1]));
+        m->stats.ms_kernels = ms;
+    }
+    m->stats.n_samples = total;
+    m->stats.bytes_in = total * m->bps;
+    m->stats.n_launches = 1;
+    m->stats.n_streams_truncated = cut;
+    return NFC_OK;
+}
+
+int nfc_multi_push(nfc_multi *m, const void *const *host_ptrs, const uint32_t *n) {
+    if (!m) return NFC_ERR_ARG;
+    if (!host_ptrs || !n) return mfail(m, NFC_ERR_ARG, "null host_ptrs / n");
+    const uint32_t K = m->K;
+    uint64_t total = 0;
+    for (uint32_t k = 0; k < K; k++) {
+        if (n[k] > m->max_push) return mfail(m, NFC_ERR_ARG, "n[%u] = %u exceeds max_push_samples = %u", k, n[k], m->max_push);
+        if (n[k] && !host_ptrs[k]) return mfail(m, NFC_ERR_ARG, "host_ptrs[%u] is null", k);
+        total += n[k];
+    }
+    if (hipSetDevice(m->P.device) != hipSuccess) return mfail(m, NFC_ERR_DEVICE, "hipSetDevice failed");
+    const size_t bytes = (size_t)total * m->bps;
+    if (m->stage_cap < bytes) {
+        if (m->h_stage) (void)hipHostFree(m->h_stage);
+        if (m->d_stage) (void)hipFree(m->d_stage);
+        m->h_stage = m->d_stage = nullptr;
+        m->stage_cap = 0;
+        const size_t cap = bytes + bytes / 4 + 4096;
+        MCHK(m, hipHostMalloc((void **)&m->h_stage, cap, hipHostMallocDefault));
+        if (hipMalloc((void **)&m->d_stage, cap) != hipSuccess) {
+            (void)hipGetLastError();
+            return mfail(m, NFC_ERR_NOMEM, "no device memory to stage %zu input bytes", cap);
+        }
+        m->stage_cap = cap;
+    }
+    std::vector<uint64_t> first(K);
+    uint64_t at = 0;
+    for (uint32_t k = 0; k < K; k++) {
+        first[k] = at;
+        if (n[k]) memcpy(m->h_stage + at * m->bps, host_ptrs[k], (size_t)n[k] * m->bps);
+        at += n[k];
+    }
+    if (bytes) MCHK(m, hipMemcpyAsync(m->d_stage, m->h_stage, bytes, hipMemcpyHostToDevice, m->st));
+    return nfc_multi_push_device(m, bytes ? m->d_stage : nullptr, first.data(), n);
+}
+
+int nfc_multi_get_counts(nfc_multi *m, uint32_t stream, nfc_counts *out, uint32_t *flags_out) {
+    if (!m) return NFC_ERR_ARG;
+    if (!out) return mfail(m, NFC_ERR_ARG, "null output");
+    if (stream >= m->K) return mfail(m, NFC_ERR_ARG, "stream %u out of range (n_streams %u)", stream, m->K);
+    if (!m->have_outputs) return mfail(m, NFC_ERR_STATE, "no completed push");
+    const uint32_t *c = m->h_counts + (size_t)stream * CNT_WORDS;
+    memset(out, 0, sizeof *out);
+    out->n_samples = m->last_n[stream];
+    out->n_edges = c[CNT_EDGES];
+    out->n_symbols[0] = c[CNT_SYM0];
+    out->n_symbols[1] = c[CNT_SYM1];
+    out->n_packets[0] = c[CNT_PK0];
+    out->n_packets[1] = c[CNT_PK1];
+    out->n_packet_bits[0] = c[CNT_PKBITS0];
+    out->n_packet_bits[1] = c[CNT_PKBITS1];
+    if (flags_out) *flags_out = c[CNT_FLAGS];
+    return NFC_OK;
+}
+
+int nfc_multi_read_edges(nfc_multi *m, uint32_t stream, size_t first, nfc_edge *out, size_t cap, size_t *n_out) {
+    if (!m) return NFC_ERR_ARG;
+    LaunchScope scope(&m->launch_err);
+    if (int rc = check_stream(m, stream, true)) return rc;
+    const size_t stored = std::min<size_t>(m->h_counts[(size_t)stream * CNT_WORDS + CNT_EDGES], m->C.edges);
+    size_t n = 0;
+    if (first < stored) n = std::min(cap, stored - first);
+    if (n && !out) return mfail(m, NFC_ERR_ARG, "null output");
+    if (n_out) *n_out = n;
+    if (!n) return NFC_OK;
+    if (int rc = ensure_read(m, n * 6 + 16)) return rc;
+    uint32_t *pos = (uint32_t *)m->h_read;
+    uint16_t *code = (uint16_t *)(m->h_read + n * 4);
+    MCHK(m, hipMemcpyAsync(pos, m->A.O.epos + (size_t)stream * m->C.s_epos + first, n * 4, hipMemcpyDeviceToHost, m->st));
+    MCHK(m, hipMemcpyAsync(code, m->A.O.ecode + (size_t)stream * m->C.s_ecode + first, n * 2, hipMemcpyDeviceToHost, m->st));
+    MCHK(m, hipStreamSynchronize(m->st));
+    const uint64_t g0 = m->g0[stream];
+    for (size_t i = 0; i < n; i++) {   // edges.hip.h: edge_code, and back
+        const uint32_t li = code[i] & 0x3FFFu;
+        nfc_edge e;
+        memset(&e, 0, sizeof e);
+        e.idx = g0 + pos[i];
+        e.d = (int32_t)(li % (uint32_t)m->nd);
+        e.v = (int8_t)((int)(li / (uint32_t)m->nd) - 1);
+        e.t = (int8_t)((int)(code[i] >> 14) - 1);
+        out[i] = e;
+    }
+    return NFC_OK;
+}
+
+int nfc_multi_read_symbols(nfc_multi *m, uint32_t stream, int type, size_t first, uint8_t *out, size_t cap, size_t *n_out) {
+    if (!m) return NFC_ERR_ARG;
+    if (type < 0 || type > 1) return mfail(m, NFC_ERR_ARG, "type must be 0 or 1");
+    if (int rc = check_stream(m, stream, true)) return rc;
+    const size_t stored = std::min<size_t>(m->h_counts[(size_t)stream * CNT_WORDS + CNT_SYM0 + type], m->C.symbols);
+    return read_row(m, m->A.O.sym[type], m->C.s_symbols, 1, stream, stored, first, out, cap, n_out);
+}
+
+int nfc_multi_read_packets(nfc_multi *m, uint32_t stream, int type, nfc_packet *out, size_t cap, size_t *n_out) {
+    if (!m) return NFC_ERR_ARG;
+    if (type < 0 || type > 1) return mfail(m, NFC_ERR_ARG, "type must be 0 or 1");
+    if (int rc = check_stream(m, stream, true)) return rc;
+    const size_t stored = std::min<size_t>(m->h_counts[(size_t)stream * CNT_WORDS + CNT_PK0 + type], m->C.packets);
+    const size_t n = std::min(cap, stored);
+    if (n && !out) return mfail(m, NFC_ERR_ARG, "null output");
+    if (n_out) *n_out = n;
+    if (!n) return NFC_OK;
+    if (int rc = ensure_read(m, n * 8)) return rc;
+    MCHK(m, hipMemcpyAsync(m->h_read, m->A.O.close[type] + (size_t)stream * m->C.s_packets, n * 8, hipMemcpyDeviceToHost, m->st));
+    MCHK(m, hipStreamSynchronize(m->st));
+    const uint32_t *cl = (const uint32_t *)m->h_read;
+    uint32_t prev = 0;
+    for (size_t i = 0; i < n; i++) {
+        nfc_packet p;
+        p.idx = m->g0[stream] + cl[2 * i + 1];
+        p.bit_off = prev;
+        p.n_bits = cl[2 * i] - prev;
+        p.type = type;
+        out[i] = p;
+        prev = cl[2 * i];
+    }
+    return NFC_OK;
+}
+
+int nfc_multi_read_packet_bits(nfc_multi *m, uint32_t stream, int type, size_t first, uint8_t *out, size_t cap, size_t *n_out) {
+    if (!m) return NFC_ERR_ARG;
+    if (type < 0 || type > 1) return mfail(m, NFC_ERR_ARG, "type must be 0 or 1");
+    if (int rc = check_stream(m, stream, true)) return rc;
+    const size_t stored = std::min<size_t>(m->h_counts[(size_t)stream * CNT_WORDS + CNT_BITS0 + type], m->C.bits);
+    return read_row(m, m->A.O.bits[type], m->C.s_bits, 1, stream, stored, first, out, cap, n_out);
+}
+
+int nfc_multi_get_state(nfc_multi *m, uint32_t stream, nfc_state_header *h, float *ring, size_t ring_cap, uint8_t *pending, size_t pending_cap) {
+    if (!m) return NFC_ERR_ARG;
+    LaunchScope scope(&m->launch_err);
+    if (!h) return mfail(m, NFC_ERR_ARG, "null header");
+    if (int rc = check_stream(m, stream, false)) return rc;
+    if (int rc = state_io(m, stream, 0)) return rc;
+    MCHK(m, hipMemcpyAsync(m->h_blob, m->d_blob, m->blob_bytes, hipMemcpyDeviceToHost, m->st));
+    MCHK(m, hipStreamSynchronize(m->st));
+    const IoHeader *io = (const IoHeader *)m->h_blob;
+    memset(h, 0, sizeof *h);
+    h->n_seen = m->nseen[stream];
+    h->ss = io->ss;
+    h->last_low = -1;
+    h->filled = io->filled;
+    h->stable = io->filled >= m->L;
+    h->cur_state = (int32_t)(io->edge & 3u);
+    h->last_bit = (int32_t)((io->edge >> 2) & 3u) - 1;
+    h->dur = (int32_t)(io->edge >> 4);
+    h->miller_state = m->canon[io->dec & 15u];
+    h->manch_state = (int32_t)((io->dec >> 4) & 7u);
+    h->pkt_started[0] = (int32_t)((io->dec >> 8) & 1u);
+    h->pkt_started[1] = (int32_t)((io->dec >> 9) & 1u);
+    h->n_pending_bits[0] = io->npend[0];
+    h->n_pending_bits[1] = io->npend[1];
+    h->av_window = m->L;
+    const size_t p0 = io->npend[0], p1 = io->npend[1];
+    if (ring && ring_cap < (size_t)m->L) return mfail(m, NFC_ERR_ARG, "ring buffer too small");
+    if (pending && pending_cap < p0 + p1) return mfail(m, NFC_ERR_ARG, "pending-bit buffer too small");
+    if (pending && (p0 > m->C.pending || p1 > m->C.pending))
+        return mfail(m, NFC_ERR_STATE, "stream %u: an open packet outgrew cap_pending_bits (NFC_MULTI_PENDING_OVERFLOW): reset the stream", stream);
+    const uint8_t *b = m->h_blob + sizeof(IoHeader);
+    if (ring) memcpy(ring, b, (size_t)m->L * 4);
+    b += (size_t)m->L * 4;
+    if (pending && p0) memcpy(pending, b, p0);
+    if (pending && p1) memcpy(pending + p0, b + m->C.pending, p1);
+    return NFC_OK;
+}
+
+int nfc_multi_set_state(nfc_multi *m, uint32_t stream, const nfc_state_header *h, const float *ring, size_t ring_len, const uint8_t *pending,
+                        size_t pending_len) {
+    if (!m) return NFC_ERR_ARG;
+    LaunchScope scope(&m->launch_err);
+    if (!h || !ring) return mfail(m, NFC_ERR_ARG, "null header / ring");
+    if (int rc = check_stream(m, stream, false)) return rc;
+    if (h->av_window != m->L || ring_len != (size_t)m->L) return mfail(m, NFC_ERR_ARG, "state was taken with another av_window");
+    if (h->dur < 0 || h->dur > m->mx || h->last_bit < -1 || h->last_bit > 1 || h->cur_state < 0 || h->cur_state > 2)
+        return mfail(m, NFC_ERR_ARG, "edge-timing state out of range (dur %d, last_bit %d, cur_state %d)", h->dur, h->last_bit, h->cur_state);
+    if (h->filled < 0 || h->filled > m->L || (h->stable != 0) != (h->filled == m->L)) return mfail(m, NFC_ERR_ARG, "filled / stable out of range");
+    if (h->miller_state < 0 || h->miller_state > 15 || h->manch_state < 0 || h->manch_state > 7) return mfail(m, NFC_ERR_ARG, "decoder state out of range");
+    const size_t p0 = h->n_pending_bits[0], p1 = h->n_pending_bits[1];
+    if (p0 + p1 != pending_len || ((p0 + p1) && !pending)) return mfail(m, NFC_ERR_ARG, "pending bits do not match the header");
+    if (p0 > m->C.pending || p1 > m->C.pending) return mfail(m, NFC_ERR_ARG, "pending bits exceed cap_pending_bits = %u", m->C.pending);
+    MCHK(m, hipStreamSynchronize(m->st));
+    memset(m->h_blob, 0, m->blob_bytes);
+    IoHeader *io = (IoHeader *)m->h_blob;
+    io->ss = h->ss;
+    io->filled = h->filled;
+    // (the slot of the first stable sample while the window fills; of the next sample afterwards)
+    io->slot = (uint32_t)((h->n_seen - (h->stable ? 0u : (uint64_t)h->filled)) % (uint64_t)m->L);
+    io->edge = pack_edge(h->cur_state, h->last_bit, h->dur);
+    io->dec = pack_dec(m->canon[h->miller_state], h->manch_state, h->pkt_started[0] != 0, h->pkt_started[1] != 0);
+    io->npend[0] = (uint32_t)p0;
+    io->npend[1] = (uint32_t)p1;
+    io->flags = 0;
+    uint8_t *b = m->h_blob + sizeof(IoHeader);
+    memcpy(b, ring, (size_t)m->L * 4);
+    b += (size_t)m->L * 4;
+    if (p0) memcpy(b, pending, p0);
+    if (p1) memcpy(b + m->C.pending, pending + p0, p1);
+    MCHK(m, hipMemcpyAsync(m->d_blob, m->h_blob, m->blob_bytes, hipMemcpyHostToDevice, m->st));
+    if (int rc = state_io(m, stream, 1)) return rc;
+    MCHK(m, hipStreamSynchronize(m->st));
+    m->nseen[stream] = h->n_seen;
+    m->g0[stream] = h->n_seen;
+    m->last_n[stream] = 0;
+    memset(m->h_counts + (size_t)stream * CNT_WORDS, 0, CNT_WORDS * 4);
+    return NFC_OK;
+}
+
+int nfc_multi_reset(nfc_multi *m, int64_t stream) {
+    if (!m) return NFC_ERR_ARG;
+    LaunchScope scope(&m->launch_err);
+    if (stream < -1 || stream >= (int64_t)m->K) return mfail(m, NFC_ERR_ARG, "stream %lld out of range (n_streams %u)", (long long)stream, m->K);
+    if (hipSetDevice(m->P.device) != hipSuccess) return mfail(m, NFC_ERR_DEVICE, "hipSetDevice failed");
+    const uint32_t k0 = stream < 0 ? 0u : (uint32_t)stream, k1 = stream < 0 ? m->K : (uint32_t)stream + 1u;
+    const size_t work = (size_t)(k1 - k0) * (size_t)m->L;
+    NFC_LAUNCH(k_multi_reset, dim3((unsigned)std::min<size_t>(1024, (work + 255) / 256)), dim3(256), 0, m->st, m->A.S, m->K, k0, k1, m->L, m->A.O.counts);
+    if (int rc = launch_ok(m)) return rc;
+    MCHK(m, hipStreamSynchronize(m->st));
+    for (uint32_t k = k0; k < k1; k++) {
+        m->nseen[k] = m->g0[k] = 0;
+        m->last_n[k] = 0;
+        memset(m->h_counts + (size_t)k * CNT_WORDS, 0, CNT_WORDS * 4);
+    }
+    if (stream < 0) m->have_outputs = false;
+    return NFC_OK;
+}
+
+int nfc_multi_get_stats(nfc_multi *m, nfc_multi_stats *out) {
+    if (!m) return NFC_ERR_ARG;
+    if (!out) return mfail(m, NFC_ERR_ARG, "null output");
+    *out = m->stats;
+    return NFC_OK;
+}
+
+int nfc_multi_set_timing(nfc_multi *m, int on) {
+    if (!m) return NFC_ERR_ARG;
+    m->timing = on != 0;
+    return NFC_OK;
+}
+
+}  // extern "C"
+
+#ifdef NFC_TEST_HOOKS
+// Test support, in the test build only and not part of the C-ABI: the damaged bytes among the guards behind every stream's row of
+// every slab (0: intact).
+extern "C" int nfc_debug_multi_guards(nfc_multi *m) {
+    if (!m || hipSetDevice(m->P.device) != hipSuccess) return -1;
+    LaunchScope scope(&m->launch_err);
+    uint32_t *bad = nullptr;   // (a word of its own: the state blob stays the state calls')
+    if (hipMalloc((void **)&bad, 16) != hipSuccess) return -1;
+    struct Free { void *p; ~Free() { (void)hipFree(p); } } free_bad{bad};
+    if (hipMemsetAsync(bad, 0, 4, m->st) != hipSuccess) return -1;
+    for (size_t i = 0; i < m->guards.size(); i++)
+        NFC_LAUNCH(k_multi_guard_check, dim3(std::min<uint32_t>(1024, (m->K * 4 + 255) / 256)), dim3(256), 0, m->st, (const uint8_t *)m->guards[i].first,
+                   m->guards[i].second, m->guard_row[i], m->K, bad);
+    uint32_t h = 0;
+    if (launch_ok(m) || hipMemcpyAsync(m->h_blob, bad, 4, hipMemcpyDeviceToHost, m->st) != hipSuccess || hipStreamSynchronize(m->st) != hipSuccess) return -1;
+    memcpy(&h, m->h_blob, 4);
+    return (int)h;
+}
+#endif   // NFC_TEST_HOOKS

@@ -80,6 +80,56 @@ _SCALED_KINDS = (api.NFC_IN_I16_SQ, api.NFC_IN_IQ_I16, api.NFC_IN_IQ_I8, api.NFC
 _RECORDED_KINDS = _IQ_KINDS + (api.NFC_IN_ENV_F32,)   # (the kinds `dst` records: the UHD branch's stand-ins and a ready envelope)
 
 
+def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None, keep=None, device=0, **sink_kwargs):
+    """Decode many recordings at once: every source is a stream of one api.NfcMultiContext, a GPU lane each, one kernel launch per
+    round of pieces (include/nfc_amd.h: nfc_multi) -- what a loop of ``decoder(src=s).run()`` does capture by capture.
+
+    sources: paths or arrays as ``decoder(src=...)`` takes them, all of ONE input kind (mixed kinds raise ValueError).  hi_val is
+    chosen as ``decoder`` chooses it.  sink_kwargs: ``lo_val`` / ``av_window`` / ``max_len`` (transition_sink's), ``wav_scale`` /
+    ``iq16_scale`` / ``iq8_scale`` (decoder's), ``max_push_samples`` (default 2^18): the longest piece one stream gets per launch --
+    longer captures are streamed in pieces.  fsm_factory: called once per source for its protocol machine (default: background's).
+    -> one ``background`` per source, in order: ``decode_many(srcs)[i].packets`` and its fsm's command trace are what
+    ``decoder(src=srcs[i]).run()`` gives."""
+    scales = {k: sink_kwargs.pop(k, 0.0) for k in ('wav_scale', 'iq16_scale', 'iq8_scale')}
+    max_push = int(sink_kwargs.pop('max_push_samples', 1 << 18))
+    sink = {k: sink_kwargs.pop(k) for k in ('lo_val', 'av_window', 'max_len') if k in sink_kwargs}
+    if sink_kwargs:
+        raise TypeError('decode_many: unexpected keyword arguments %s' % sorted(sink_kwargs))
+    loaded = [_load_source(s, scales['wav_scale'], scales['iq16_scale'], scales['iq8_scale']) for s in sources]
+    kinds = sorted(set(k for _, k, _ in loaded))
+    if len(kinds) > 1:
+        raise ValueError('decode_many: the sources are of different input kinds %s: decode each kind in a call of its own' % kinds)
+    backs = [background(reader, tag, None, fsm=fsm_factory() if fsm_factory else None, keep=keep, samp_rate=samp_rate,
+                        max_len=sink.get('max_len', 50), device=device, attached=True) for _ in loaded]
+    if not loaded:
+        return backs
+    kind, scale = kinds[0], loaded[0][2]
+    dt, per = api._KIND_DTYPE[kind]
+    data = [numpy.ascontiguousarray(d, dtype=dt).reshape(-1) for d, _, _ in loaded]
+    for g0 in range(0, len(data), 65536):   # (a context holds at most 65536 streams)
+        group = data[g0:g0 + 65536]
+        lens = numpy.array([len(d) // per for d in group], numpy.int64)
+        starts = numpy.concatenate([[0], numpy.cumsum(lens)[:-1]]).astype(numpy.int64)
+        piece = int(max(1, min(max_push, lens.max())))
+        flat = numpy.concatenate([d[:n * per] for d, n in zip(group, lens)]) if lens.sum() else numpy.zeros(0, dt)
+        buf = api.DeviceBuffer(flat, device, nbytes=max(16, flat.nbytes))
+        try:
+            with api.NfcMultiContext(len(group), piece, samp_rate=samp_rate, hi_val=_hi_val(kind), reader=reader, tag=tag, input_kind=kind,
+                                     device=device, i16_scale=scale if kind in _SCALED_KINDS else 0.0, **sink) as m:
+                done = numpy.zeros(len(group), numpy.int64)
+                while True:
+                    n = numpy.minimum(lens - done, piece)
+                    if not n.any():
+                        break
+                    m.push_device(buf, starts + done, n)
+                    done += n
+                    for k in numpy.nonzero(n)[0]:
+                        backs[g0 + int(k)].deliver(m.stream(int(k)))
+        finally:
+            buf.free()
+    return backs
+
+
 if _gr is not None:
 
     class decoder(_gr.hier_block2):
