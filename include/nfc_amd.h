@@ -34,6 +34,8 @@ extern "C" {
 /* 4: nfc_stats grew (device_allocs, tail_fused, chunks_rerun_in_place) */
 /* (still 4, no structure changed: the input kinds NFC_IN_IQ_I16, NFC_IN_IQ_I8, NFC_IN_IQ_U8; nfc_record_pcm16_device, nfc_host_record_pcm16, nfc_record_tap) */
 /* (still 4, only new types and functions: the multi-stream context nfc_multi, its configuration, statistics and functions) */
+/* (still 4, only new names: nfc_multi_fetch, nfc_multi_fetched, nfc_multi_get_counts_all, NFC_MULTI_FETCH_*, NFC_MF_*; two reserved words
+ *  of nfc_multi_stats are now n_fetches and n_reads_device, its size unchanged) */
 #define NFC_AMD_ABI_VERSION 4
 
 typedef enum {
@@ -406,7 +408,12 @@ typedef struct {
 } nfc_multi_config;              /* 64 bytes */
 enum { NFC_MULTI_TRUNC_EDGES = 1, NFC_MULTI_TRUNC_SYMBOLS = 2, NFC_MULTI_TRUNC_PACKETS = 4, NFC_MULTI_TRUNC_BITS = 8,
        NFC_MULTI_PENDING_OVERFLOW = 16 /* sticky until the stream is reset */ };
-typedef struct { double ms_kernels; uint64_t n_samples, bytes_in; uint32_t n_launches, n_streams_truncated; uint32_t reserved[8]; } nfc_multi_stats;
+typedef struct {
+    double ms_kernels; uint64_t n_samples, bytes_in;
+    uint32_t n_launches, n_streams_truncated;   /* of the push (a fetch does not touch them) */
+    uint32_t n_fetches, n_reads_device;         /* since the last push: nfc_multi_fetch calls that succeeded; reader calls that went to the device */
+    uint32_t reserved[6];
+} nfc_multi_stats;               /* 64 bytes */
 
 int  nfc_multi_create(const nfc_params *p, const nfc_multi_config *c, nfc_multi **out);
 void nfc_multi_destroy(nfc_multi *m);
@@ -414,12 +421,62 @@ const char *nfc_multi_last_error(const nfc_multi *m);   /* m may be NULL: messag
 /* stream k consumes n[k] samples (0 allowed) that start first_sample[k] SAMPLES behind dev_base; n and first_sample are host arrays of n_streams */
 int nfc_multi_push_device(nfc_multi *m, const void *dev_base, const uint64_t *first_sample, const uint32_t *n);
 int nfc_multi_push(nfc_multi *m, const void *const *host_ptrs, const uint32_t *n);   /* staged to the device, then the same */
-/* Outputs of the LAST push, per stream; the readers return what the slab stores (at most cap_* entries, see CAPACITIES). */
+/* Outputs of the LAST push, per stream; the readers return what the slab stores (at most cap_* entries, see CAPACITIES).  Each read is a
+ * copy from the device and a wait, unless an nfc_multi_fetch (below) since the push covers the array: then it is host memory. */
 int nfc_multi_get_counts(nfc_multi *m, uint32_t stream, nfc_counts *out, uint32_t *flags_out);
 int nfc_multi_read_edges(nfc_multi *m, uint32_t stream, size_t first, nfc_edge *out, size_t cap, size_t *n_out);
 int nfc_multi_read_symbols(nfc_multi *m, uint32_t stream, int type, size_t first, uint8_t *out, size_t cap, size_t *n_out);
 int nfc_multi_read_packets(nfc_multi *m, uint32_t stream, int type, nfc_packet *out, size_t cap, size_t *n_out);
 int nfc_multi_read_packet_bits(nfc_multi *m, uint32_t stream, int type, size_t first, uint8_t *out, size_t cap, size_t *n_out);
+/* every stream's counts (and flags) of the last push in one call: the loop of nfc_multi_get_counts over host memory, no device work */
+int nfc_multi_get_counts_all(nfc_multi *m, nfc_counts *out /* n_streams */, uint32_t *flags_out /* n_streams, may be NULL */);
+
+/* ---- the fetch: every stream's outputs of the last push packed on the GPU, ONE copy to the host --------------------------------
+ * A reader call above is a copy from the stream's slab row and a wait: a round trip per stream and array.  nfc_multi_fetch compacts what
+ * EVERY stream stored in the last push into one packed device buffer (two kernel launches: a scan of the stored amounts, a gather of
+ * the slab rows), brings that buffer to pinned host memory in one copy, and hands out pointers into it.  Until the next push the
+ * readers above then serve the arrays the fetch covered from that host copy -- the same first / cap / n_out semantics, the same
+ * bytes, no device call -- and take the device path (counted in nfc_multi_stats.n_reads_device) for arrays it did not cover.
+ * STORED AMOUNT.  Stream k's part of an array is exactly what its reader returns with first = 0 and unlimited cap: min(count, cap_*)
+ * entries (the bit rows: what nfc_multi_read_packet_bits returns).  A truncated stream contributes its stored prefix, a stream that
+ * got n[k] == 0 in the push (or was reset since) nothing.
+ * PACKING.  Tight, at entry granularity, no padding between streams: off[a] (n_streams + 1 entries) is the exclusive prefix of the
+ * stored amounts of array a, stream k's entries are [off[a][k], off[a][k + 1]).  Arrays `what` does not ask for are empty: their off
+ * is all zero and their pointers may be NULL (they are NULL too when no stream stored anything: n_launches == 0, nothing copied).
+ * NFC_MULTI_FETCH_PACKETS stands for the packet tables AND the bit arrays of both types.
+ * EDGES come as the two arrays the slabs hold: edge idx = base[k] + edge_pos, code & 0x3FFF = (v + 1) * edge_code_nd + d,
+ * code >> 14 = t + 1 -- v, d, t as in nfc_edge.  packets[t] are nfc_packet records exactly as nfc_multi_read_packets gives them:
+ * idx in the stream's own count of samples, bit_off relative to the stream's own part of packet_bits[t].
+ * LIFETIME.  Every pointer in nfc_multi_fetched refers to pinned host memory owned by the context and is valid until the next
+ * nfc_multi_push / _push_device, nfc_multi_fetch, nfc_multi_reset (of any stream), nfc_multi_set_state or nfc_multi_destroy of that
+ * context; each of those also ends the readers' use of the host copy.
+ * ERRORS.  what == 0 or bits outside NFC_MULTI_FETCH_ALL: NFC_ERR_ARG naming `what`; no completed push: NFC_ERR_STATE; buffers that
+ * cannot be had: NFC_ERR_NOMEM, the context and its slabs intact (the readers go on from the device); totals of the device's scan that
+ * differ from the host's: NFC_ERR_INTERNAL.  The buffers are sized from the amounts stored (grown geometrically), never for the
+ * capacities.
+ * COST, measured with captures of 32 768 samples (README.md, profiles/multi_fetch_bench.json): at 16 384 streams a fetch of everything
+ * copies 271.4 MB (14.3 % of the slabs' room) in 7.09 ms, its two kernels taking 0.534 ms; reading every stream's packets costs 140.7 us per
+ * stream from the device, 94.2 us through the per-stream Python view after a fetch and 56.5 us through NfcMultiFetch.packets_all(). */
+enum { NFC_MULTI_FETCH_EDGES = 1, NFC_MULTI_FETCH_SYMBOLS = 2, NFC_MULTI_FETCH_PACKETS = 4 /* tables AND bit arrays, both types */,
+       NFC_MULTI_FETCH_ALL = 7 };
+enum { NFC_MF_EDGES = 0, NFC_MF_SYM0, NFC_MF_SYM1, NFC_MF_PK0, NFC_MF_PK1, NFC_MF_BITS0, NFC_MF_BITS1, NFC_MF_ARRAYS = 7 };
+typedef struct {
+    uint32_t what, n_streams;
+    uint32_t edge_code_nd;               /* code & 0x3FFF = (v + 1) * nd + d, code >> 14 = t + 1 (edges.hip.h: edge_code) */
+    uint32_t n_launches;                 /* of this fetch: 0 when nothing was stored at all */
+    const uint64_t *off[NFC_MF_ARRAYS];  /* n_streams + 1 entries each: stream k's entries are [off[a][k], off[a][k+1]) of array a */
+    const uint64_t *base;                /* n_streams: stream index of the push's first sample (edge idx = base[k] + pos) */
+    const uint32_t *edge_pos;            /* batch-local sample position */
+    const uint16_t *edge_code;
+    const uint8_t  *symbols[2];
+    const nfc_packet *packets[2];        /* exactly what nfc_multi_read_packets gives: bit_off relative to the stream's own bit row */
+    const uint8_t  *packet_bits[2];
+    uint64_t bytes_copied;               /* device -> host, of this fetch */
+    double ms_kernels;                   /* with nfc_multi_set_timing(on): the fetch's launches by HIP events; else 0 */
+    uint64_t reserved[4];
+} nfc_multi_fetched;
+int nfc_multi_fetch(nfc_multi *m, uint32_t what, nfc_multi_fetched *out /* may be NULL */);
+
 /* one stream's boundary state, in the form an nfc_ctx exports and imports it */
 int nfc_multi_get_state(nfc_multi *m, uint32_t stream, nfc_state_header *hdr, float *ring, size_t ring_cap, uint8_t *pending, size_t pending_cap);
 int nfc_multi_set_state(nfc_multi *m, uint32_t stream, const nfc_state_header *hdr, const float *ring, size_t ring_len, const uint8_t *pending, size_t pending_len);

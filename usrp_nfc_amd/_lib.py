@@ -16,6 +16,9 @@ NFC_REC_ENVELOPE, NFC_REC_REAL_PART = 0, 1   # nfc_record_tap
 ABI_VERSION = 4   # NFC_AMD_ABI_VERSION of the header these structures mirror
 # per-stream flags of a multi-stream context (nfc_multi_get_counts)
 NFC_MULTI_TRUNC_EDGES, NFC_MULTI_TRUNC_SYMBOLS, NFC_MULTI_TRUNC_PACKETS, NFC_MULTI_TRUNC_BITS, NFC_MULTI_PENDING_OVERFLOW = 1, 2, 4, 8, 16
+# what nfc_multi_fetch brings to the host (PACKETS: the packet tables and the bit arrays), and its arrays in the order of off[]
+NFC_MULTI_FETCH_EDGES, NFC_MULTI_FETCH_SYMBOLS, NFC_MULTI_FETCH_PACKETS, NFC_MULTI_FETCH_ALL = 1, 2, 4, 7
+NFC_MF_EDGES, NFC_MF_SYM0, NFC_MF_SYM1, NFC_MF_PK0, NFC_MF_PK1, NFC_MF_BITS0, NFC_MF_BITS1, NFC_MF_ARRAYS = 0, 1, 2, 3, 4, 5, 6, 7
 
 
 class Params(C.Structure):
@@ -47,7 +50,14 @@ class MultiConfig(C.Structure):   # nfc_multi_config
 
 class MultiStats(C.Structure):   # nfc_multi_stats
     _fields_ = [('ms_kernels', C.c_double), ('n_samples', C.c_uint64), ('bytes_in', C.c_uint64), ('n_launches', C.c_uint32),
-                ('n_streams_truncated', C.c_uint32), ('reserved', C.c_uint32 * 8)]
+                ('n_streams_truncated', C.c_uint32), ('n_fetches', C.c_uint32), ('n_reads_device', C.c_uint32), ('reserved', C.c_uint32 * 6)]
+
+
+class MultiFetched(C.Structure):   # nfc_multi_fetched
+    _fields_ = [('what', C.c_uint32), ('n_streams', C.c_uint32), ('edge_code_nd', C.c_uint32), ('n_launches', C.c_uint32),
+                ('off', C.c_void_p * 7), ('base', C.c_void_p), ('edge_pos', C.c_void_p), ('edge_code', C.c_void_p),
+                ('symbols', C.c_void_p * 2), ('packets', C.c_void_p * 2), ('packet_bits', C.c_void_p * 2), ('bytes_copied', C.c_uint64),
+                ('ms_kernels', C.c_double), ('reserved', C.c_uint64 * 4)]
 
 
 class Frame(C.Structure):   # nfc_frame
@@ -73,6 +83,8 @@ TX_RUN_DTYPE = np.dtype([('level', '<i4'), ('pad', '<i4'), ('dur_us', '<f8')])  
 NFC_TX_SAME, NFC_TX_MANCHESTER, NFC_TX_MILLER = 0, 1, 2
 EDGE_DTYPE = np.dtype([('idx', '<u8'), ('d', '<i4'), ('v', 'i1'), ('t', 'i1'), ('pad', '<i2')])
 PACKET_DTYPE = np.dtype([('idx', '<u8'), ('bit_off', '<u8'), ('n_bits', '<u4'), ('type', '<i4')])
+COUNTS_DTYPE = np.dtype([('n_samples', '<u8'), ('n_edges', '<u8'), ('n_symbols', '<u8', (2,)), ('n_packets', '<u8', (2,)),
+                         ('n_packet_bits', '<u8', (2,))])   # nfc_counts
 
 # every symbol include/nfc_amd.h declares
 SYMBOLS = ['nfc_abi_version', 'nfc_device_count', 'nfc_create', 'nfc_destroy', 'nfc_last_error', 'nfc_push',
@@ -85,7 +97,7 @@ SYMBOLS = ['nfc_abi_version', 'nfc_device_count', 'nfc_create', 'nfc_destroy', '
            'nfc_record_pcm16_device', 'nfc_host_record_pcm16',
            'nfc_multi_create', 'nfc_multi_destroy', 'nfc_multi_last_error', 'nfc_multi_push_device', 'nfc_multi_push', 'nfc_multi_get_counts',
            'nfc_multi_read_edges', 'nfc_multi_read_symbols', 'nfc_multi_read_packets', 'nfc_multi_read_packet_bits', 'nfc_multi_get_state',
-           'nfc_multi_set_state', 'nfc_multi_reset', 'nfc_multi_get_stats', 'nfc_multi_set_timing']
+           'nfc_multi_set_state', 'nfc_multi_reset', 'nfc_multi_get_stats', 'nfc_multi_set_timing', 'nfc_multi_fetch', 'nfc_multi_get_counts_all']
 
 _libs = {}
 
@@ -193,6 +205,8 @@ def load(path=None):
     L.nfc_multi_reset.argtypes = [vp, C.c_int64]
     L.nfc_multi_get_stats.argtypes = [vp, C.POINTER(MultiStats)]
     L.nfc_multi_set_timing.argtypes = [vp, C.c_int]
+    L.nfc_multi_fetch.argtypes = [vp, u32, C.POINTER(MultiFetched)]
+    L.nfc_multi_get_counts_all.argtypes = [vp, vp, vp]
     for name in SYMBOLS:
         getattr(L, name)
     _libs[path] = L

@@ -5,7 +5,9 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (EDGE_DTYPE, NFC_FLAG_FORCE_SEQUENTIAL, NFC_FLAG_NO_EDGES, NFC_IN_ENV_F32, NFC_IN_I16_SQ,
+from ._lib import (COUNTS_DTYPE, EDGE_DTYPE, NFC_MF_ARRAYS, NFC_MF_BITS0, NFC_MF_BITS1, NFC_MF_EDGES, NFC_MF_PK0, NFC_MF_PK1, NFC_MF_SYM0,
+                   NFC_MF_SYM1, NFC_MULTI_FETCH_ALL, NFC_MULTI_FETCH_EDGES, NFC_MULTI_FETCH_PACKETS, NFC_MULTI_FETCH_SYMBOLS,
+                   NFC_FLAG_FORCE_SEQUENTIAL, NFC_FLAG_NO_EDGES, NFC_IN_ENV_F32, NFC_IN_I16_SQ,
                    NFC_IN_IQ_F32, NFC_IN_IQ_I8, NFC_IN_IQ_I16, NFC_IN_IQ_U8, NFC_IN_REAL_F32_SQ, NFC_MULTI_PENDING_OVERFLOW,
                    NFC_MULTI_TRUNC_BITS, NFC_MULTI_TRUNC_EDGES, NFC_MULTI_TRUNC_PACKETS, NFC_MULTI_TRUNC_SYMBOLS, NFC_REC_ENVELOPE,
                    NFC_REC_REAL_PART, PACKET_DTYPE)
@@ -14,7 +16,9 @@ __all__ = ['NfcContext', 'NfcError', 'DeviceBuffer', 'host_decode_lut', 'host_en
            'NFC_IN_REAL_F32_SQ', 'NFC_IN_I16_SQ', 'NFC_IN_IQ_I16', 'NFC_IN_IQ_I8', 'NFC_IN_IQ_U8', 'NFC_FLAG_FORCE_SEQUENTIAL',
            'NFC_FLAG_NO_EDGES', 'NFC_REC_ENVELOPE', 'NFC_REC_REAL_PART', 'host_record_pcm16', 'record_pcm16_device', 'record_pcm16',
            'NfcMultiContext', 'NfcMultiStream', 'NFC_MULTI_TRUNC_EDGES', 'NFC_MULTI_TRUNC_SYMBOLS', 'NFC_MULTI_TRUNC_PACKETS',
-           'NFC_MULTI_TRUNC_BITS', 'NFC_MULTI_PENDING_OVERFLOW']
+           'NFC_MULTI_TRUNC_BITS', 'NFC_MULTI_PENDING_OVERFLOW', 'NfcMultiFetch', 'NFC_MULTI_FETCH_EDGES', 'NFC_MULTI_FETCH_SYMBOLS',
+           'NFC_MULTI_FETCH_PACKETS', 'NFC_MULTI_FETCH_ALL', 'NFC_MF_EDGES', 'NFC_MF_SYM0', 'NFC_MF_SYM1', 'NFC_MF_PK0', 'NFC_MF_PK1',
+           'NFC_MF_BITS0', 'NFC_MF_BITS1', 'NFC_MF_ARRAYS', 'COUNTS_DTYPE', 'COUNTS_FLAGS_DTYPE']
 
 _KIND_DTYPE = {NFC_IN_IQ_F32: (np.float32, 2), NFC_IN_ENV_F32: (np.float32, 1),
                NFC_IN_REAL_F32_SQ: (np.float32, 1), NFC_IN_I16_SQ: (np.int16, 1), NFC_IN_IQ_I16: (np.int16, 2),
@@ -271,6 +275,18 @@ _MULTI_FLAG_NAMES = ((NFC_MULTI_TRUNC_EDGES, 'NFC_MULTI_TRUNC_EDGES'), (NFC_MULT
                      (NFC_MULTI_PENDING_OVERFLOW, 'NFC_MULTI_PENDING_OVERFLOW'))
 
 
+COUNTS_FLAGS_DTYPE = np.dtype(COUNTS_DTYPE.descr + [('flags', '<u4')])   # NfcMultiContext.counts_all
+
+
+def _flag_names(bits):
+    return ' | '.join(nm for v, nm in _MULTI_FLAG_NAMES if bits & v)
+
+
+def _trunc_mask(bit):
+    """The flags that make an array of kind `bit` unreliable: its own, and for packets and their bits an overflowed open packet."""
+    return bit | NFC_MULTI_PENDING_OVERFLOW if bit in (NFC_MULTI_TRUNC_PACKETS, NFC_MULTI_TRUNC_BITS) else bit
+
+
 class NfcMultiContext(object):
     """n_streams independent streams with one parameter set, decoded in one kernel launch per push -- a GPU lane per stream
     (nfc_multi, include/nfc_amd.h).  The keywords are NfcContext's; cap_*: entries stored per stream and push (0: the defaults
@@ -349,6 +365,27 @@ class NfcMultiContext(object):
             raise NfcError('stream %d out of range (n_streams %d)' % (k, self.n_streams))
         return NfcMultiStream(self, int(k), allow_truncated)
 
+    def fetch(self, what=NFC_MULTI_FETCH_ALL, copy=True, allow_truncated=False):
+        """Everything the streams stored in the last push, packed on the GPU and brought to the host in ONE copy (nfc_multi_fetch):
+        -> NfcMultiFetch.  what: NFC_MULTI_FETCH_* bits (PACKETS: the packet tables and the bit arrays).  Until the next push the
+        stream views read the arrays `what` covers from that host copy, without a device call.
+        copy=True (default): the arrays are numpy copies and stay valid.  copy=False: they are views of the context's pinned
+        memory, valid only until the next push, fetch, reset (of any stream), set_state or close of this context -- reading them
+        afterwards reads freed or rewritten memory."""
+        f = _lib.MultiFetched()
+        self._chk(self.L.nfc_multi_fetch(self.h, int(what), C.byref(f)), 'nfc_multi_fetch')
+        return NfcMultiFetch(self, f, copy, allow_truncated)
+
+    def counts_all(self):
+        """Every stream's counts and flags of the last push from one call: a COUNTS_FLAGS_DTYPE array of n_streams records."""
+        cnt, flags = np.zeros(self.n_streams, COUNTS_DTYPE), np.zeros(self.n_streams, np.uint32)
+        self._chk(self.L.nfc_multi_get_counts_all(self.h, cnt.ctypes.data, flags.ctypes.data), 'nfc_multi_get_counts_all')
+        out = np.zeros(self.n_streams, COUNTS_FLAGS_DTYPE)
+        for name in COUNTS_DTYPE.names:
+            out[name] = cnt[name]
+        out['flags'] = flags
+        return out
+
     def reset(self, stream=-1):
         """A new stream in place of stream k (default: of every one), keeping the device buffers."""
         self._chk(self.L.nfc_multi_reset(self.h, int(stream)), 'nfc_multi_reset')
@@ -383,14 +420,14 @@ class NfcMultiStream(object):
     def flags(self):
         return self._counts()[1]
 
-    def _stored(self, total, bit, allow):
-        """How many of `total` entries to read; a cut array raises unless allowed."""
-        f = self.flags()
-        bad = f & (bit | NFC_MULTI_PENDING_OVERFLOW if bit in (NFC_MULTI_TRUNC_PACKETS, NFC_MULTI_TRUNC_BITS) else bit)
+    def _stored(self, field, ptype, bit, allow):
+        """How many entries of the array to read (counts.field, [ptype]), from ONE counts call; a cut array raises unless allowed."""
+        c, f = self._counts()
+        bad = f & _trunc_mask(bit)
         if bad and not (self.allow_truncated if allow is None else allow):
-            raise NfcError('stream %d: %s (pass allow_truncated=True for what was stored)'
-                           % (self.k, ' | '.join(nm for v, nm in _MULTI_FLAG_NAMES if bad & v)))
-        return int(total)
+            raise NfcError('stream %d: %s (pass allow_truncated=True for what was stored)' % (self.k, _flag_names(bad)))
+        total = getattr(c, field)
+        return int(total if ptype is None else total[ptype])
 
     def _read(self, fn, total, dtype, *lead):
         out = np.zeros(int(total), dtype)
@@ -400,7 +437,7 @@ class NfcMultiStream(object):
         return out[:got.value]
 
     def edges(self, allow_truncated=None):
-        n = self._stored(self.counts().n_edges, NFC_MULTI_TRUNC_EDGES, allow_truncated)
+        n = self._stored('n_edges', None, NFC_MULTI_TRUNC_EDGES, allow_truncated)
         return self._read(self.m.L.nfc_multi_read_edges, n, EDGE_DTYPE, 0)
 
     def transitions(self, allow_truncated=None):
@@ -409,11 +446,11 @@ class NfcMultiStream(object):
         return [((int(v), int(d) * f), int(t)) for v, d, t in zip(e['v'], e['d'], e['t'])]
 
     def symbols(self, ptype, allow_truncated=None):
-        n = self._stored(self.counts().n_symbols[ptype], NFC_MULTI_TRUNC_SYMBOLS, allow_truncated)
+        n = self._stored('n_symbols', ptype, NFC_MULTI_TRUNC_SYMBOLS, allow_truncated)
         return self._read(self.m.L.nfc_multi_read_symbols, n, np.uint8, ptype, 0)
 
     def packet_table(self, ptype, allow_truncated=None):
-        n = self._stored(self.counts().n_packets[ptype], NFC_MULTI_TRUNC_PACKETS, allow_truncated)
+        n = self._stored('n_packets', ptype, NFC_MULTI_TRUNC_PACKETS, allow_truncated)
         out = np.zeros(n, PACKET_DTYPE)
         got = C.c_size_t(0)
         if n:
@@ -422,7 +459,7 @@ class NfcMultiStream(object):
 
     def packet_bits(self, ptype, allow_truncated=None):
         """The per-type bit array the packet table's bit_off / n_bits index."""
-        n = self._stored(self.counts().n_packet_bits[ptype], NFC_MULTI_TRUNC_BITS, allow_truncated)
+        n = self._stored('n_packet_bits', ptype, NFC_MULTI_TRUNC_BITS, allow_truncated)
         return self._read(self.m.L.nfc_multi_read_packet_bits, n, np.uint8, ptype, 0)
 
     def packets(self, allow_truncated=None):
@@ -459,6 +496,134 @@ class NfcMultiStream(object):
 
     def reset(self):
         self.m.reset(self.k)
+
+
+class NfcMultiFetch(object):
+    """What every stream of an NfcMultiContext stored in its last push, in packed host arrays (NfcMultiContext.fetch).
+
+    off[a] (a: NFC_MF_EDGES, NFC_MF_SYM0, NFC_MF_SYM1, NFC_MF_PK0, NFC_MF_PK1, NFC_MF_BITS0, NFC_MF_BITS1): n_streams + 1 offsets, stream
+    k's entries of array a are [off[a][k], off[a][k + 1]) -- ``numpy.split(array, off[a][1:-1])`` is the per-stream view.  base[k]: the
+    stream's sample count before the push.  edge_pos / edge_code: the edges as the device keeps them (``edges(k)`` expands them);
+    symbols[t], packet_table[t] (PACKET_DTYPE, bit_off relative to the stream's own part of packet_bits[t]), packet_bits[t] (a stream's
+    part is its bit row as stored: the closed packets' bits, then those of a packet still open at the push's end, which
+    ``packet_bits_of`` leaves out as NfcMultiStream.packet_bits does).  Arrays the fetch did not ask for are empty.  counts: the
+    COUNTS_FLAGS_DTYPE records of NfcMultiContext.counts_all.  flags[k]: the stream's NFC_MULTI_* flags; the per-stream accessors raise NfcError for an
+    array its stream cut short unless allow_truncated (theirs, else the fetch's): then the stored prefix comes back.
+    With fetch(copy=False) every array is a view of the context's pinned memory: see NfcMultiContext.fetch for how long it lives."""
+
+    def __init__(self, multi, f, copy, allow_truncated=False):
+        K = int(f.n_streams)
+        self.what, self.n_streams, self.nd, self.factor = int(f.what), K, int(f.edge_code_nd), multi.factor
+        self.n_launches, self.bytes_copied, self.ms_kernels = int(f.n_launches), int(f.bytes_copied), float(f.ms_kernels)
+        self.allow_truncated = allow_truncated
+
+        def arr(ptr, n, dtype):
+            dtype = np.dtype(dtype)
+            if not ptr or not n:
+                return np.zeros(0, dtype)
+            a = np.frombuffer((C.c_char * (int(n) * dtype.itemsize)).from_address(ptr), dtype)
+            return a.copy() if copy else a
+
+        self.off = [arr(f.off[a], K + 1, '<u8') for a in range(NFC_MF_ARRAYS)]
+        tot = [int(o[K]) for o in self.off]
+        self.base = arr(f.base, K, '<u8')
+        self.edge_pos = arr(f.edge_pos, tot[NFC_MF_EDGES], '<u4')
+        self.edge_code = arr(f.edge_code, tot[NFC_MF_EDGES], '<u2')
+        self.symbols = [arr(f.symbols[t], tot[NFC_MF_SYM0 + t], np.uint8) for t in (0, 1)]
+        self.packet_table = [arr(f.packets[t], tot[NFC_MF_PK0 + t], PACKET_DTYPE) for t in (0, 1)]
+        self.packet_bits = [arr(f.packet_bits[t], tot[NFC_MF_BITS0 + t], np.uint8) for t in (0, 1)]
+        self.counts = multi.counts_all()   # (the true totals, whatever was stored)
+        self.flags = self.counts['flags']
+
+    def _need(self, bit, name):
+        if not self.what & bit:
+            raise NfcError('this fetch did not ask for the %s (what = %d)' % (name, self.what))
+
+    def _allowed(self, k, bit, allow):
+        bad = int(self.flags[k]) & _trunc_mask(bit)
+        if bad and not (self.allow_truncated if allow is None else allow):
+            raise NfcError('stream %d: %s (pass allow_truncated=True for what was stored)' % (k, _flag_names(bad)))
+
+    def _slice(self, a, array, k):
+        return array[int(self.off[a][k]):int(self.off[a][k + 1])]
+
+    def edges(self, k, allow_truncated=None):
+        """Stream k's edges as an EDGE_DTYPE array: NfcMultiStream.edges()."""
+        self._need(NFC_MULTI_FETCH_EDGES, 'edges')
+        self._allowed(k, NFC_MULTI_TRUNC_EDGES, allow_truncated)
+        pos, code = self._slice(NFC_MF_EDGES, self.edge_pos, k), self._slice(NFC_MF_EDGES, self.edge_code, k).astype(np.int32)
+        out = np.zeros(len(pos), EDGE_DTYPE)
+        li = code & 0x3FFF   # edges.hip.h: edge_code, and back
+        out['idx'] = self.base[k] + pos.astype(np.uint64)
+        out['d'] = li % self.nd
+        out['v'] = li // self.nd - 1
+        out['t'] = (code >> 14) - 1
+        return out
+
+    def transitions(self, k, allow_truncated=None):
+        e = self.edges(k, allow_truncated)
+        f = self.factor
+        return [((int(v), int(d) * f), int(t)) for v, d, t in zip(e['v'], e['d'], e['t'])]
+
+    def symbols_of(self, k, ptype, allow_truncated=None):
+        self._need(NFC_MULTI_FETCH_SYMBOLS, 'symbols')
+        self._allowed(k, NFC_MULTI_TRUNC_SYMBOLS, allow_truncated)
+        return self._slice(NFC_MF_SYM0 + ptype, self.symbols[ptype], k)
+
+    def packet_table_of(self, k, ptype, allow_truncated=None):
+        self._need(NFC_MULTI_FETCH_PACKETS, 'packets')
+        self._allowed(k, NFC_MULTI_TRUNC_PACKETS, allow_truncated)
+        return self._slice(NFC_MF_PK0 + ptype, self.packet_table[ptype], k)
+
+    def packet_bits_of(self, k, ptype, allow_truncated=None):
+        self._need(NFC_MULTI_FETCH_PACKETS, 'packets')
+        self._allowed(k, NFC_MULTI_TRUNC_BITS, allow_truncated)
+        return self._slice(NFC_MF_BITS0 + ptype, self.packet_bits[ptype], k)[:int(self.counts['n_packet_bits'][k][ptype])]
+
+    def packets_of(self, k, allow_truncated=None):
+        """Stream k's closed packets of both types in stream order, [(type, [bits]), ...]: NfcMultiStream.packets(), with its rule for
+        a cut bit array (the packets it still holds whole)."""
+        items = []
+        for t in (0, 1):
+            tab = self.packet_table_of(k, t, allow_truncated)
+            if not len(tab):
+                continue
+            bits = self.packet_bits_of(k, t, allow_truncated)
+            for p in tab:
+                o = int(p['bit_off'])
+                if o + int(p['n_bits']) <= len(bits):
+                    items.append((int(p['idx']), t, bits[o:o + int(p['n_bits'])].tolist()))
+        items.sort(key=lambda r: r[0])
+        return [(t, b) for _, t, b in items]
+
+    def packets_all(self, allow_truncated=None):
+        """[packets_of(k) for every stream], built from the packed arrays with numpy: no call into the library per stream."""
+        self._need(NFC_MULTI_FETCH_PACKETS, 'packets')
+        K = self.n_streams
+        if not (self.allow_truncated if allow_truncated is None else allow_truncated):
+            cut = np.nonzero(self.flags & (NFC_MULTI_TRUNC_PACKETS | NFC_MULTI_TRUNC_BITS | NFC_MULTI_PENDING_OVERFLOW))[0]
+            if len(cut):
+                raise NfcError('stream %d: %s (pass allow_truncated=True for what was stored)' % (int(cut[0]), _flag_names(int(self.flags[cut[0]]))))
+        cols = []
+        for t in (0, 1):
+            tab = self.packet_table[t]
+            if not len(tab):
+                continue
+            stream = np.repeat(np.arange(K, dtype=np.int64), np.diff(self.off[NFC_MF_PK0 + t]).astype(np.int64))
+            bo = self.off[NFC_MF_BITS0 + t].astype(np.int64)
+            a = bo[stream] + tab['bit_off'].astype(np.int64)
+            b = a + tab['n_bits'].astype(np.int64)
+            whole = b <= np.minimum(bo[stream + 1], bo[stream] + self.counts['n_packet_bits'][stream, t].astype(np.int64))   # (a cut bit array: the packets it still holds whole)
+            cols.append((stream[whole], tab['idx'][whole].astype(np.int64), np.full(int(whole.sum()), t, np.int64), a[whole], b[whole]))
+        out = [[] for _ in range(K)]
+        if not cols:
+            return out
+        stream, idx, typ, a, b = (np.concatenate(c) for c in zip(*cols))
+        order = np.lexsort((typ, idx, stream))   # per stream by the closing sample, type 0 first on a tie: packets_of's order
+        bits = self.packet_bits
+        for s, t, i, j in zip(stream[order].tolist(), typ[order].tolist(), a[order].tolist(), b[order].tolist()):
+            out[s].append((t, bits[t][i:j].tolist()))
+        return out
 
 
 class DeviceBuffer(object):

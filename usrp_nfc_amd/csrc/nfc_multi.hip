@@ -3,7 +3,8 @@
 // kernels of threshold.hip.h / edges.hip.h are nfc_amd.hip's: here they are `static` (NFC_HDR_KERNEL_LINKAGE) and never launched.
 //
 // A push: the streams' (first_sample, n) and the lane order go up in one copy, ONE launch walks every stream, one copy brings
-// all counts and flags back to pinned memory, one wait.  Everything else stays in the per-stream slabs until it is read.
+// all counts and flags back to pinned memory, one wait.  Everything else stays in the per-stream slabs until it is read -- stream by
+// stream from the slabs, or after an nfc_multi_fetch (multi_fetch.hip.h: two launches, one copy) from the packed host copy.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -21,6 +22,7 @@
 #include "launch_check.h"
 #include "decoder_tables.h"
 #include "multi.hip.h"
+#include "multi_fetch.hip.h"
 #include "scale_arg.h"
 
 using namespace nfc;
@@ -30,6 +32,9 @@ static_assert(sizeof(nfc_multi_config) == 64, "nfc_multi_config is 64 bytes");
 static_assert(F_EDGES == NFC_MULTI_TRUNC_EDGES && F_SYMBOLS == NFC_MULTI_TRUNC_SYMBOLS && F_PACKETS == NFC_MULTI_TRUNC_PACKETS &&
                   F_BITS == NFC_MULTI_TRUNC_BITS && F_PENDING == NFC_MULTI_PENDING_OVERFLOW,
               "the kernel's flag bits are the header's");
+static_assert(MF_EDGES == NFC_MULTI_FETCH_EDGES && MF_SYMBOLS == NFC_MULTI_FETCH_SYMBOLS && MF_PACKETS == NFC_MULTI_FETCH_PACKETS &&
+                  MF_ARRAYS == NFC_MF_ARRAYS && sizeof(nfc_packet) == 24 && sizeof(nfc_multi_stats) == 64,
+              "the fetch kernels' arrays and records are the header's");
 
 struct nfc_multi {
     nfc_params P;
@@ -58,6 +63,14 @@ struct nfc_multi {
     std::vector<size_t> guard_row;                   // payload bytes per row
     uint8_t canon[16];
     bool have_outputs = false;
+    // the fetch (multi_fetch.hip.h): the packed buffer on the device and its pinned twin, the prefix tables, what the host copy holds
+    uint8_t *d_fetch = nullptr, *h_fetch = nullptr;
+    size_t d_fetch_cap = 0, h_fetch_cap = 0;
+    uint64_t *d_ftable = nullptr, *h_ftable = nullptr;   // [MF_ARRAYS][K + 1]; the host's is followed by base[K]
+    uint32_t fetched = 0;                                // NFC_MULTI_FETCH_* bits the host copy serves; 0: none (a push, a reset)
+    FetchLayout flay;                                    // of the last fetch that copied anything
+    bool fetch_guarded = false;                          // d_fetch holds guards at flay's places
+    nfc_multi_fetched fout;
     nfc_multi_stats stats;
     std::string err;
     LaunchError launch_err;
@@ -169,6 +182,7 @@ int read_row(nfc_multi *m, const void *slab, size_t stride_entries, size_t esz, 
     if (n && !out) return mfail(m, NFC_ERR_ARG, "null output");
     if (n) {
         if (int rc = ensure_read(m, n * esz)) return rc;
+        m->stats.n_reads_device++;
         MCHK(m, hipMemcpyAsync(m->h_read, (const char *)slab + ((size_t)stream * stride_entries + first) * esz, n * esz, hipMemcpyDeviceToHost, m->st));
         MCHK(m, hipStreamSynchronize(m->st));
         memcpy(out, m->h_read, n * esz);
@@ -181,6 +195,72 @@ int check_stream(nfc_multi *m, uint32_t stream, bool outputs) {
     if (stream >= m->K) return mfail(m, NFC_ERR_ARG, "stream %u out of range (n_streams %u)", stream, m->K);
     if (outputs && !m->have_outputs) return mfail(m, NFC_ERR_STATE, "no completed push");
     if (hipSetDevice(m->P.device) != hipSuccess) return mfail(m, NFC_ERR_DEVICE, "hipSetDevice failed");
+    return NFC_OK;
+}
+
+// ---- the fetch ----
+const uint64_t *foff(const nfc_multi *m, int a) { return m->h_ftable + (size_t)a * ((size_t)m->K + 1); }
+
+// whether the host copy of the last fetch serves the arrays `bit` stands for
+bool served(const nfc_multi *m, uint32_t bit) { return (m->fetched & bit) != 0; }
+
+size_t up16(size_t v) { return (v + 15u) & ~(size_t)15u; }
+
+// the pinned and the device buffer for `bytes`, grown geometrically (ensure_read); a failure leaves the context as it was, less the
+// buffer that was too small
+int ensure_fetch(nfc_multi *m, size_t bytes) {
+    if (m->h_fetch_cap < bytes) {
+        if (m->h_fetch) (void)hipHostFree(m->h_fetch);
+        m->h_fetch = nullptr;
+        m->h_fetch_cap = 0;
+        const size_t cap = bytes + bytes / 2 + 4096;
+        if (hipHostMalloc((void **)&m->h_fetch, cap, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            m->h_fetch = nullptr;
+            return mfail(m, NFC_ERR_NOMEM, "nfc_multi_fetch: no pinned host memory for %zu bytes", cap);
+        }
+        m->h_fetch_cap = cap;
+    }
+    if (m->d_fetch_cap < bytes) {
+        if (m->d_fetch) (void)hipFree(m->d_fetch);
+        m->d_fetch = nullptr;
+        m->d_fetch_cap = 0;
+        m->fetch_guarded = false;
+        const size_t cap = bytes + bytes / 2 + 4096;
+        if (hipMalloc((void **)&m->d_fetch, cap) != hipSuccess) {
+            (void)hipGetLastError();
+            m->d_fetch = nullptr;
+            return mfail(m, NFC_ERR_NOMEM, "nfc_multi_fetch: no device memory for %zu bytes", cap);
+        }
+        m->d_fetch_cap = cap;
+    }
+    return NFC_OK;
+}
+
+int ensure_ftable(nfc_multi *m) {
+    const size_t T = (size_t)m->K + 1;
+    if (!m->h_ftable && hipHostMalloc((void **)&m->h_ftable, (MF_ARRAYS * T + m->K) * 8, hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        m->h_ftable = nullptr;
+        return mfail(m, NFC_ERR_NOMEM, "nfc_multi_fetch: no pinned host memory for the offset tables (n_streams %u)", m->K);
+    }
+    if (!m->d_ftable && hipMalloc((void **)&m->d_ftable, MF_ARRAYS * T * 8) != hipSuccess) {
+        (void)hipGetLastError();
+        m->d_ftable = nullptr;
+        return mfail(m, NFC_ERR_NOMEM, "nfc_multi_fetch: no device memory for the offset tables (n_streams %u)", m->K);
+    }
+    return NFC_OK;
+}
+
+// rows [first, first + n) of stream k's part of a packed byte array, n cut as read_row cuts it
+int read_fetched(nfc_multi *m, int a, const uint8_t *section, uint32_t stream, size_t first, uint8_t *out, size_t cap, size_t *n_out) {
+    const uint64_t *off = foff(m, a);
+    const size_t stored = (size_t)(off[stream + 1] - off[stream]);
+    size_t n = 0;
+    if (first < stored) n = std::min(cap, stored - first);
+    if (n && !out) return mfail(m, NFC_ERR_ARG, "null output");
+    if (n) memcpy(out, section + off[stream] + first, n);
+    if (n_out) *n_out = n;
     return NFC_OK;
 }
 
@@ -200,7 +280,9 @@ void nfc_multi_destroy(nfc_multi *m) {
     if (m->st) (void)hipStreamSynchronize(m->st);
     for (void *p : m->dev) (void)hipFree(p);
     if (m->d_stage) (void)hipFree(m->d_stage);
-    for (uint8_t *p : {m->h_up, (uint8_t *)m->h_counts, m->h_blob, m->h_stage, m->h_read})
+    if (m->d_fetch) (void)hipFree(m->d_fetch);
+    if (m->d_ftable) (void)hipFree(m->d_ftable);
+    for (uint8_t *p : {m->h_up, (uint8_t *)m->h_counts, m->h_blob, m->h_stage, m->h_read, m->h_fetch, (uint8_t *)m->h_ftable})
         if (p) (void)hipHostFree(p);
     for (hipEvent_t e : m->ev)
         if (e) (void)hipEventDestroy(e);
@@ -248,6 +330,8 @@ int nfc_multi_create(const nfc_params *p, const nfc_multi_config *c, nfc_multi *
     static const size_t bps[7] = {8, 4, 4, 2, 4, 2, 2};
     m->bps = bps[p->input_kind];
     memset(&m->stats, 0, sizeof m->stats);
+    memset(&m->fout, 0, sizeof m->fout);
+    memset(&m->flay, 0, sizeof m->flay);
     const uint32_t K = m->K;
     // Capacities per stream and push.  Entries are 6-13 % of the samples on every capture of this tree's generators (the densest:
     // 0.133 edges and 0.10 symbols of one type per sample): a quarter of the samples is room to spare.  A non-empty packet takes a
@@ -394,6 +478,7 @@ int nfc_multi_push_device(nfc_multi *m, const void *dev_base, const uint64_t *fi
     if (total && !dev_base) return mfail(m, NFC_ERR_ARG, "null dev_base");
     if ((uintptr_t)dev_base & 15u) return mfail(m, NFC_ERR_ARG, "dev_base must be 16-byte aligned");
     if (hipSetDevice(m->P.device) != hipSuccess) return mfail(m, NFC_ERR_DEVICE, "hipSetDevice failed");
+    m->fetched = 0;   // the host copy is the last push's
     uint64_t *hf = (uint64_t *)m->h_up;
     uint32_t *hn = (uint32_t *)(m->h_up + (size_t)K * 8), *ho = (uint32_t *)(m->h_up + (size_t)K * 12);
     memcpy(hf, first_sample, (size_t)K * 8);
@@ -437,6 +522,7 @@ int nfc_multi_push_device(nfc_multi *m, const void *dev_base, const uint64_t *fi
     m->stats.bytes_in = total * m->bps;
     m->stats.n_launches = 1;
     m->stats.n_streams_truncated = cut;
+    m->stats.n_fetches = m->stats.n_reads_device = 0;
     return NFC_OK;
 }
 
@@ -495,6 +581,139 @@ int nfc_multi_get_counts(nfc_multi *m, uint32_t stream, nfc_counts *out, uint32_
     return NFC_OK;
 }
 
+int nfc_multi_get_counts_all(nfc_multi *m, nfc_counts *out, uint32_t *flags_out) {
+    if (!m) return NFC_ERR_ARG;
+    if (!out) return mfail(m, NFC_ERR_ARG, "null output");
+    if (!m->have_outputs) return mfail(m, NFC_ERR_STATE, "no completed push");
+    for (uint32_t k = 0; k < m->K; k++) {
+        const uint32_t *c = m->h_counts + (size_t)k * CNT_WORDS;
+        nfc_counts &o = out[k];
+        o.n_samples = m->last_n[k];
+        o.n_edges = c[CNT_EDGES];
+        o.n_symbols[0] = c[CNT_SYM0];
+        o.n_symbols[1] = c[CNT_SYM1];
+        o.n_packets[0] = c[CNT_PK0];
+        o.n_packets[1] = c[CNT_PK1];
+        o.n_packet_bits[0] = c[CNT_PKBITS0];
+        o.n_packet_bits[1] = c[CNT_PKBITS1];
+        if (flags_out) flags_out[k] = c[CNT_FLAGS];
+    }
+    return NFC_OK;
+}
+
+int nfc_multi_fetch(nfc_multi *m, uint32_t what, nfc_multi_fetched *out) {
+    if (!m) return NFC_ERR_ARG;
+    LaunchScope scope(&m->launch_err);
+    if (what == 0 || (what & ~(uint32_t)NFC_MULTI_FETCH_ALL)) return mfail(m, NFC_ERR_ARG, "what = %u: a non-empty set of NFC_MULTI_FETCH_* bits is expected", what);
+    if (!m->have_outputs) return mfail(m, NFC_ERR_STATE, "no completed push");
+    if (hipSetDevice(m->P.device) != hipSuccess) return mfail(m, NFC_ERR_DEVICE, "hipSetDevice failed");
+    m->fetched = 0;
+    if (int rc = ensure_ftable(m)) return rc;
+    const uint32_t K = m->K;
+    const size_t T = (size_t)K + 1;
+    // the same table the scan kernel forms, from the pinned mirror of the counts: it sizes the buffers and is the caller's off[]
+    uint64_t *tab = m->h_ftable, *base = m->h_ftable + MF_ARRAYS * T;
+    Amounts run = {0, 0, 0, 0, 0, 0, 0};
+    bool based = false;
+    for (uint32_t k = 0; k < K; k++) {
+        const Amounts s = stored_amounts(m->h_counts + (size_t)k * CNT_WORDS, m->C, what);
+        tab[0 * T + k] = run.a0;
+        tab[1 * T + k] = run.a1;
+        tab[2 * T + k] = run.a2;
+        tab[3 * T + k] = run.a3;
+        tab[4 * T + k] = run.a4;
+        tab[5 * T + k] = run.a5;
+        tab[6 * T + k] = run.a6;
+#define X(f) run.f += s.f;
+        MF_EACH(X)
+#undef X
+        base[k] = m->g0[k];
+        based = based || m->g0[k] != 0;
+    }
+    const uint64_t total[MF_ARRAYS] = {run.a0, run.a1, run.a2, run.a3, run.a4, run.a5, run.a6};
+    for (int a = 0; a < MF_ARRAYS; a++) tab[a * T + K] = total[a];
+    nfc_multi_fetched &f = m->fout;
+    memset(&f, 0, sizeof f);
+    f.what = what;
+    f.n_streams = K;
+    f.edge_code_nd = (uint32_t)m->nd;
+    for (int a = 0; a < MF_ARRAYS; a++) f.off[a] = foff(m, a);
+    f.base = base;
+    uint64_t any = 0;
+    for (int a = 0; a < MF_ARRAYS; a++) any |= total[a];
+    if (any) {
+        // sections: each starts on 16 bytes and is followed by GUARD_BYTES of the guard word
+        FetchLayout F;
+        size_t at = MF_HEADER_BYTES;
+#define SECTION(name, entries, esz)            \
+    F.at_##name = at;                          \
+    F.end_##name = at + (size_t)(entries) * (esz); \
+    at = up16(F.end_##name + GUARD_BYTES);
+        SECTION(epos, total[0], 4)
+        SECTION(ecode, total[0], 2)
+        SECTION(sym0, total[1], 1)
+        SECTION(sym1, total[2], 1)
+        SECTION(pk0, total[3], sizeof(nfc_packet))
+        SECTION(pk1, total[4], sizeof(nfc_packet))
+        SECTION(bits0, total[5], 1)
+        SECTION(bits1, total[6], 1)
+#undef SECTION
+        F.total = run;
+        const size_t bytes = at;
+        if (int rc = ensure_fetch(m, bytes)) return rc;
+        GatherArgs G;
+        G.O = m->A.O;
+        G.C = m->C;
+        G.K = K;
+        G.table = m->d_ftable;
+        G.packed = m->d_fetch;
+        G.F = F;
+        const unsigned wgs = std::min<unsigned>(MF_GATHER_MAX_WG, (K + MF_GATHER_THREADS / 64 - 1) / (MF_GATHER_THREADS / 64));
+        if (m->timing) MCHK(m, hipEventRecord(m->ev[0], m->st));
+        NFC_LAUNCH(k_multi_fetch_scan, dim3(1), dim3(MF_SCAN_THREADS), 0, m->st, (const uint32_t *)m->A.O.counts, m->C, K, what, m->d_ftable, m->d_fetch, F);
+        NFC_LAUNCH(k_multi_fetch_gather, dim3(wgs), dim3(MF_GATHER_THREADS), 0, m->st, G);
+        if (m->timing) MCHK(m, hipEventRecord(m->ev[1], m->st));
+        m->flay = F;
+        m->fetch_guarded = true;
+        MCHK(m, hipMemcpyAsync(m->h_fetch, m->d_fetch, bytes, hipMemcpyDeviceToHost, m->st));
+        MCHK(m, hipStreamSynchronize(m->st));
+        if (int rc = launch_ok(m)) return rc;
+        const uint64_t *dev_total = (const uint64_t *)m->h_fetch;
+        for (int a = 0; a < MF_ARRAYS; a++)
+            if (dev_total[a] != total[a])
+                return mfail(m, NFC_ERR_INTERNAL, "nfc_multi_fetch: the device's total of array %d is %llu, the host's %llu", a, (unsigned long long)dev_total[a],
+                             (unsigned long long)total[a]);
+        if (m->timing) {
+            float ms = 0.f;
+            MCHK(m, hipEventElapsedTime(&ms, m->ev[0], m->ev[1]));
+            f.ms_kernels = ms;
+        }
+        f.n_launches = 2;
+        f.bytes_copied = bytes;
+        uint8_t *h = m->h_fetch;
+        f.edge_pos = (const uint32_t *)(h + F.at_epos);
+        f.edge_code = (const uint16_t *)(h + F.at_ecode);
+        f.symbols[0] = h + F.at_sym0;
+        f.symbols[1] = h + F.at_sym1;
+        f.packets[0] = (const nfc_packet *)(h + F.at_pk0);
+        f.packets[1] = (const nfc_packet *)(h + F.at_pk1);
+        f.packet_bits[0] = h + F.at_bits0;
+        f.packet_bits[1] = h + F.at_bits1;
+        // the gather left the packets' idx batch-local: the stream's base is added here, over the few packets there are
+        if (based)
+            for (int t = 0; t < 2; t++) {
+                nfc_packet *pk = (nfc_packet *)(h + (t ? F.at_pk1 : F.at_pk0));
+                const uint64_t *off = foff(m, NFC_MF_PK0 + t);
+                for (uint32_t k = 0; k < K; k++)
+                    for (uint64_t i = off[k]; i < off[k + 1]; i++) pk[i].idx += base[k];
+            }
+    }
+    m->fetched = what;
+    m->stats.n_fetches++;
+    if (out) *out = f;
+    return NFC_OK;
+}
+
 int nfc_multi_read_edges(nfc_multi *m, uint32_t stream, size_t first, nfc_edge *out, size_t cap, size_t *n_out) {
     if (!m) return NFC_ERR_ARG;
     LaunchScope scope(&m->launch_err);
@@ -505,12 +724,23 @@ int nfc_multi_read_edges(nfc_multi *m, uint32_t stream, size_t first, nfc_edge *
     if (n && !out) return mfail(m, NFC_ERR_ARG, "null output");
     if (n_out) *n_out = n;
     if (!n) return NFC_OK;
-    if (int rc = ensure_read(m, n * 6 + 16)) return rc;
-    uint32_t *pos = (uint32_t *)m->h_read;
-    uint16_t *code = (uint16_t *)(m->h_read + n * 4);
-    MCHK(m, hipMemcpyAsync(pos, m->A.O.epos + (size_t)stream * m->C.s_epos + first, n * 4, hipMemcpyDeviceToHost, m->st));
-    MCHK(m, hipMemcpyAsync(code, m->A.O.ecode + (size_t)stream * m->C.s_ecode + first, n * 2, hipMemcpyDeviceToHost, m->st));
-    MCHK(m, hipStreamSynchronize(m->st));
+    const uint32_t *pos;
+    const uint16_t *code;
+    if (served(m, NFC_MULTI_FETCH_EDGES)) {
+        const uint64_t at = foff(m, NFC_MF_EDGES)[stream] + first;
+        pos = m->fout.edge_pos + at;
+        code = m->fout.edge_code + at;
+    } else {
+        if (int rc = ensure_read(m, n * 6 + 16)) return rc;
+        uint32_t *dpos = (uint32_t *)m->h_read;
+        uint16_t *dcode = (uint16_t *)(m->h_read + n * 4);
+        m->stats.n_reads_device++;
+        MCHK(m, hipMemcpyAsync(dpos, m->A.O.epos + (size_t)stream * m->C.s_epos + first, n * 4, hipMemcpyDeviceToHost, m->st));
+        MCHK(m, hipMemcpyAsync(dcode, m->A.O.ecode + (size_t)stream * m->C.s_ecode + first, n * 2, hipMemcpyDeviceToHost, m->st));
+        MCHK(m, hipStreamSynchronize(m->st));
+        pos = dpos;
+        code = dcode;
+    }
     const uint64_t g0 = m->g0[stream];
     for (size_t i = 0; i < n; i++) {   // edges.hip.h: edge_code, and back
         const uint32_t li = code[i] & 0x3FFFu;
@@ -529,6 +759,7 @@ int nfc_multi_read_symbols(nfc_multi *m, uint32_t stream, int type, size_t first
     if (!m) return NFC_ERR_ARG;
     if (type < 0 || type > 1) return mfail(m, NFC_ERR_ARG, "type must be 0 or 1");
     if (int rc = check_stream(m, stream, true)) return rc;
+    if (served(m, NFC_MULTI_FETCH_SYMBOLS)) return read_fetched(m, NFC_MF_SYM0 + type, m->fout.symbols[type], stream, first, out, cap, n_out);
     const size_t stored = std::min<size_t>(m->h_counts[(size_t)stream * CNT_WORDS + CNT_SYM0 + type], m->C.symbols);
     return read_row(m, m->A.O.sym[type], m->C.s_symbols, 1, stream, stored, first, out, cap, n_out);
 }
@@ -542,7 +773,12 @@ int nfc_multi_read_packets(nfc_multi *m, uint32_t stream, int type, nfc_packet *
     if (n && !out) return mfail(m, NFC_ERR_ARG, "null output");
     if (n_out) *n_out = n;
     if (!n) return NFC_OK;
+    if (served(m, NFC_MULTI_FETCH_PACKETS)) {
+        memcpy(out, m->fout.packets[type] + foff(m, NFC_MF_PK0 + type)[stream], n * sizeof(nfc_packet));
+        return NFC_OK;
+    }
     if (int rc = ensure_read(m, n * 8)) return rc;
+    m->stats.n_reads_device++;
     MCHK(m, hipMemcpyAsync(m->h_read, m->A.O.close[type] + (size_t)stream * m->C.s_packets, n * 8, hipMemcpyDeviceToHost, m->st));
     MCHK(m, hipStreamSynchronize(m->st));
     const uint32_t *cl = (const uint32_t *)m->h_read;
@@ -563,6 +799,7 @@ int nfc_multi_read_packet_bits(nfc_multi *m, uint32_t stream, int type, size_t f
     if (!m) return NFC_ERR_ARG;
     if (type < 0 || type > 1) return mfail(m, NFC_ERR_ARG, "type must be 0 or 1");
     if (int rc = check_stream(m, stream, true)) return rc;
+    if (served(m, NFC_MULTI_FETCH_PACKETS)) return read_fetched(m, NFC_MF_BITS0 + type, m->fout.packet_bits[type], stream, first, out, cap, n_out);
     const size_t stored = std::min<size_t>(m->h_counts[(size_t)stream * CNT_WORDS + CNT_BITS0 + type], m->C.bits);
     return read_row(m, m->A.O.bits[type], m->C.s_bits, 1, stream, stored, first, out, cap, n_out);
 }
@@ -638,6 +875,9 @@ int nfc_multi_set_state(nfc_multi *m, uint32_t stream, const nfc_state_header *h
     if (p1) memcpy(b + m->C.pending, pending + p0, p1);
     MCHK(m, hipMemcpyAsync(m->d_blob, m->h_blob, m->blob_bytes, hipMemcpyHostToDevice, m->st));
     if (int rc = state_io(m, stream, 1)) return rc;
+    // the stream's outputs of the last push are void: its counts go to 0 on the device as in the mirror (a later fetch scans them)
+    m->fetched = 0;
+    MCHK(m, hipMemsetAsync(m->A.O.counts + (size_t)stream * CNT_WORDS, 0, CNT_WORDS * 4, m->st));
     MCHK(m, hipStreamSynchronize(m->st));
     m->nseen[stream] = h->n_seen;
     m->g0[stream] = h->n_seen;
@@ -651,6 +891,7 @@ int nfc_multi_reset(nfc_multi *m, int64_t stream) {
     LaunchScope scope(&m->launch_err);
     if (stream < -1 || stream >= (int64_t)m->K) return mfail(m, NFC_ERR_ARG, "stream %lld out of range (n_streams %u)", (long long)stream, m->K);
     if (hipSetDevice(m->P.device) != hipSuccess) return mfail(m, NFC_ERR_DEVICE, "hipSetDevice failed");
+    m->fetched = 0;
     const uint32_t k0 = stream < 0 ? 0u : (uint32_t)stream, k1 = stream < 0 ? m->K : (uint32_t)stream + 1u;
     const size_t work = (size_t)(k1 - k0) * (size_t)m->L;
     NFC_LAUNCH(k_multi_reset, dim3((unsigned)std::min<size_t>(1024, (work + 255) / 256)), dim3(256), 0, m->st, m->A.S, m->K, k0, k1, m->L, m->A.O.counts);
@@ -696,6 +937,16 @@ extern "C" int nfc_debug_multi_guards(nfc_multi *m) {
     uint32_t h = 0;
     if (launch_ok(m) || hipMemcpyAsync(m->h_blob, bad, 4, hipMemcpyDeviceToHost, m->st) != hipSuccess || hipStreamSynchronize(m->st) != hipSuccess) return -1;
     memcpy(&h, m->h_blob, 4);
+    if (m->fetch_guarded) {   // and the guard bytes behind the sections of the fetch's packed buffer, where the last fetch put them
+        const FetchLayout &F = m->flay;
+        const uint64_t ends[MF_SECTIONS] = {F.end_epos, F.end_ecode, F.end_sym0, F.end_sym1, F.end_pk0, F.end_pk1, F.end_bits0, F.end_bits1};
+        uint8_t g[MF_SECTIONS][GUARD_BYTES];
+        for (int s = 0; s < MF_SECTIONS; s++)
+            if (hipMemcpyAsync(g[s], m->d_fetch + ends[s], GUARD_BYTES, hipMemcpyDeviceToHost, m->st) != hipSuccess) return -1;
+        if (hipStreamSynchronize(m->st) != hipSuccess) return -1;
+        for (int s = 0; s < MF_SECTIONS; s++)
+            for (int b = 0; b < GUARD_BYTES; b++) h += g[s][b] != (uint8_t)(GUARD_WORD >> (8 * (b & 3)));
+    }
     return (int)h;
 }
 #endif   // NFC_TEST_HOOKS

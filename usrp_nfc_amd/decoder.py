@@ -80,7 +80,7 @@ _SCALED_KINDS = (api.NFC_IN_I16_SQ, api.NFC_IN_IQ_I16, api.NFC_IN_IQ_I8, api.NFC
 _RECORDED_KINDS = _IQ_KINDS + (api.NFC_IN_ENV_F32,)   # (the kinds `dst` records: the UHD branch's stand-ins and a ready envelope)
 
 
-def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None, keep=None, device=0, **sink_kwargs):
+def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None, keep=None, device=0, push_stats=None, **sink_kwargs):
     """Decode many recordings at once: every source is a stream of one api.NfcMultiContext, a GPU lane each, one kernel launch per
     round of pieces (include/nfc_amd.h: nfc_multi) -- what a loop of ``decoder(src=s).run()`` does capture by capture.
 
@@ -88,6 +88,9 @@ def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None,
     chosen as ``decoder`` chooses it.  sink_kwargs: ``lo_val`` / ``av_window`` / ``max_len`` (transition_sink's), ``wav_scale`` /
     ``iq16_scale`` / ``iq8_scale`` (decoder's), ``max_push_samples`` (default 2^18): the longest piece one stream gets per launch --
     longer captures are streamed in pieces.  fsm_factory: called once per source for its protocol machine (default: background's).
+    After every push the streams' outputs come to the host in ONE fetch (api.NfcMultiContext.fetch: the packets, and the symbols
+    unless ``keep`` is 0) and are delivered from that host copy.  push_stats: a list that gets one ``(n_fetches, n_reads_device)``
+    per push, read from the context's statistics after the push's delivery (one fetch and no read from the device are expected).
     -> one ``background`` per source, in order: ``decode_many(srcs)[i].packets`` and its fsm's command trace are what
     ``decoder(src=srcs[i]).run()`` gives."""
     scales = {k: sink_kwargs.pop(k, 0.0) for k in ('wav_scale', 'iq16_scale', 'iq8_scale')}
@@ -123,8 +126,12 @@ def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None,
                         break
                     m.push_device(buf, starts + done, n)
                     done += n
+                    m.fetch(api.NFC_MULTI_FETCH_PACKETS | (api.NFC_MULTI_FETCH_SYMBOLS if keep != 0 else 0), copy=False)
                     for k in numpy.nonzero(n)[0]:
                         backs[g0 + int(k)].deliver(m.stream(int(k)))
+                    if push_stats is not None:
+                        st = m.stats()
+                        push_stats.append((int(st.n_fetches), int(st.n_reads_device)))
         finally:
             buf.free()
     return backs
