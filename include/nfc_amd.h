@@ -36,6 +36,8 @@ extern "C" {
 /* (still 4, only new types and functions: the multi-stream context nfc_multi, its configuration, statistics and functions) */
 /* (still 4, only new names: nfc_multi_fetch, nfc_multi_fetched, nfc_multi_get_counts_all, NFC_MULTI_FETCH_*, NFC_MF_*; two reserved words
  *  of nfc_multi_stats are now n_fetches and n_reads_device, its size unchanged) */
+/* (still 4, only new names: nfc_raw_frame, NFC_RAW_*, nfc_get_frame_counts, nfc_read_frames, nfc_read_frame_bytes, nfc_multi_frames,
+ *  nfc_multi_fetch_frames, nfc_host_frames, nfc_fsm_process_frames) */
 #define NFC_AMD_ABI_VERSION 4
 
 typedef enum {
@@ -476,6 +478,74 @@ typedef struct {
     uint64_t reserved[4];
 } nfc_multi_fetched;
 int nfc_multi_fetch(nfc_multi *m, uint32_t what, nfc_multi_fetched *out /* may be NULL */);
+
+/* ---- frames assembled on the GPU: closed packets -> bytes, parity verdict, CRC_A --------------------------------------------
+ * The bit-level, packet-parallel part of fsm.process_bits, per closed non-empty packet: the frame-end repair (fsm.py:49-66), nine
+ * bits to a byte plus the odd-parity check (fsm.py:28-47) and the ISO 14443-3 CRC_A (utilities.py:30-41).  Two kernel launches
+ * (csrc/frames.hip.h, nfc_frames.hip): a scan over the packet closes gives every frame its place, then a lane per frame reads its
+ * nine-bit fields from the bit array the decode stage left (packed 32 to a word, or a byte per bit) and writes the record, the bytes
+ * and the parity bits.  What stays on the host is the sequential protocol machine: nfc_fsm_process_frames.
+ * REPAIR, with rem = n_bits % 9 and start_bit = (type == 0 ? 1 : 0):
+ *   rem 0: nothing;  rem 8: the last byte's parity bit is start_bit;  rem 1: the last bit is dropped, NFC_FRAME_EXTRA_ERROR iff it
+ *   differs from start_bit;  rem 2..7: rem bits are dropped, NFC_FRAME_MANY_MORE_ERROR.
+ * bytes[type]: eight data bits, least significant first; par[type]: the ninth bit as received, a byte each; both indexed by byte_off.
+ * They are stored for EVERY frame, parity errors included: a CRYPTO1 session checks parity after decryption and needs the on-air bits.
+ * NFC_RAW_PARITY_OK: n_bytes > 0 and no byte has popcount(byte) & 1 == par (the negation of fsm.py:224-228's "PARITY ERROR");
+ * NFC_RAW_CRC_A_OK: parity holds and the last two bytes are the CRC_A of those before them;
+ * NFC_RAW_CUT (multi-stream only): the stream's bit slab was truncated before this packet's end: n_bytes is 0, nothing is written. */
+enum { NFC_RAW_PARITY_OK = 0x100, NFC_RAW_CRC_A_OK = 0x200, NFC_RAW_CUT = 0x400 };  /* beside NFC_FRAME_EXTRA_ERROR (1), NFC_FRAME_MANY_MORE_ERROR (2): same values, same meaning */
+typedef struct nfc_raw_frame {     /* 32 bytes; one per closed, non-empty packet, in the packet table's order */
+    uint64_t idx;                  /* nfc_packet.idx */
+    uint32_t byte_off;             /* first byte in bytes[type] / par[type] */
+    uint32_t n_bits;               /* nfc_packet.n_bits, before the repair */
+    uint32_t n_bytes;              /* after the repair: (n_bits + 1) / 9 when n_bits % 9 == 8, else n_bits / 9; may be 0 */
+    uint32_t flags;
+    int32_t  type;
+    uint32_t reserved;             /* 0 */
+} nfc_raw_frame;
+/* Single context.  Assembly is lazy, like the symbol arrays: the first of these calls after a batch launches the two kernels on the
+ * context's stream; a batch whose frames nobody reads launches nothing.  Valid exactly where nfc_read_packets is (after nfc_push_edges
+ * too); NFC_ERR_STATE with no completed batch.  n_frames[t] == nfc_counts.n_packets[t].  Copies go through pinned staging. */
+int nfc_get_frame_counts(nfc_ctx *ctx, uint64_t n_frames[2], uint64_t n_bytes[2]);
+int nfc_read_frames(nfc_ctx *ctx, int type, nfc_raw_frame *out, size_t cap, size_t *n_out);
+int nfc_read_frame_bytes(nfc_ctx *ctx, int type, size_t first, uint8_t *bytes_out, uint8_t *par_out /* may be NULL */, size_t cap, size_t *n_out);
+/* The kernels' twin on the CPU (no GPU needed): the frames of n packets of ONE type (rows of nfc_read_packets; a row of another type is
+ * NFC_ERR_ARG) over that type's bit array, a byte per bit.  out: n records; bytes / par: cap entries each (NFC_ERR_ARG when the frames
+ * need more); *used: entries written. */
+int nfc_host_frames(const nfc_packet *packets, size_t n, const uint8_t *bits, int type, nfc_raw_frame *out, uint8_t *bytes, uint8_t *par,
+                    size_t cap, size_t *used);
+/* nfc_fsm_process_packets over frames: `frames` holds both types merged by idx, as the rows of nfc_fsm_process_packets are; its outputs
+ * and the machine's state afterwards are IDENTICAL to nfc_fsm_process_packets on the packets the frames came from, through CRYPTO1
+ * sessions and nested authentications.  Outside a session it uses the assembled bytes and the parity verdict and touches no bits;
+ * inside one it rebuilds the on-air bits from bytes and par and takes the route of nfc_fsm_process.  A frame with NFC_RAW_CUT is
+ * NFC_ERR_ARG (its bits are not there). */
+int nfc_fsm_process_frames(nfc_fsm *f, const nfc_raw_frame *frames, size_t n, const uint8_t *bytes0, const uint8_t *par0,
+                           const uint8_t *bytes1, const uint8_t *par1, nfc_frame *frames_out, uint8_t *bytes_out, size_t bytes_cap,
+                           size_t *bytes_used, uint16_t *enc_out);
+/* Multi-stream: the scan, the assembly of every stream's frames into ONE packed buffer, one copy and one wait.  Stream k's frames of
+ * type t are frames[t][frame_off[t][k] .. frame_off[t][k + 1]) and its bytes bytes[t] / par[t][byte_off[t][k] .. byte_off[t][k + 1]);
+ * a frame's byte_off is relative to the stream's own part, its idx is in the stream's own sample count (base[k] added on the host).
+ * A stream contributes the packets its slab stores (at most cap_packets); a frame whose bits the slab cut carries NFC_RAW_CUT.
+ * The call owns its buffers: it does not end the lifetime of an nfc_multi_fetch's pointers or the readers' host copy, and the reverse
+ * holds too; nfc_multi_fetch, NFC_MULTI_FETCH_ALL and nfc_multi_stats are untouched.  The pointers live until the next nfc_multi_push /
+ * _push_device, nfc_multi_fetch_frames, nfc_multi_reset, nfc_multi_set_state or nfc_multi_destroy.  No completed push: NFC_ERR_STATE;
+ * nothing stored: no launch and no copy (n_launches == 0, NULL arrays); device totals that differ from the host's: NFC_ERR_INTERNAL.
+ * COST, measured with captures of 32 768 samples (README.md, profiles/frames_bench.json): at 16 384 streams the call and a vectorised
+ * CRC mask cost 0.105 us per capture (16.65 MB copied, the two kernels 0.727 ms) against 55.4 us for nfc_multi_fetch(PACKETS) and a
+ * Python list of bits per packet; a single context's 1e8-sample batch: frames + nfc_fsm_process_frames 6.04 ms against 8.90 ms for
+ * the packet tables, the bits and nfc_fsm_process_packets, the two kernels 0.100 ms. */
+typedef struct {
+    uint32_t n_streams, n_launches;
+    const uint64_t *frame_off[2];        /* n_streams + 1 entries each */
+    const uint64_t *byte_off[2];
+    const uint64_t *base;                /* n_streams */
+    const nfc_raw_frame *frames[2];
+    const uint8_t *bytes[2], *par[2];
+    uint64_t bytes_copied;               /* device -> host, of this call */
+    double ms_kernels;                   /* with nfc_multi_set_timing(on): the two launches by HIP events; else 0 */
+    uint64_t reserved[4];
+} nfc_multi_frames;
+int nfc_multi_fetch_frames(nfc_multi *m, nfc_multi_frames *out);
 
 /* one stream's boundary state, in the form an nfc_ctx exports and imports it */
 int nfc_multi_get_state(nfc_multi *m, uint32_t stream, nfc_state_header *hdr, float *ring, size_t ring_cap, uint8_t *pending, size_t pending_cap);

@@ -60,6 +60,12 @@ class MultiFetched(C.Structure):   # nfc_multi_fetched
                 ('ms_kernels', C.c_double), ('reserved', C.c_uint64 * 4)]
 
 
+class MultiFrames(C.Structure):   # nfc_multi_frames
+    _fields_ = [('n_streams', C.c_uint32), ('n_launches', C.c_uint32), ('frame_off', C.c_void_p * 2), ('byte_off', C.c_void_p * 2),
+                ('base', C.c_void_p), ('frames', C.c_void_p * 2), ('bytes', C.c_void_p * 2), ('par', C.c_void_p * 2),
+                ('bytes_copied', C.c_uint64), ('ms_kernels', C.c_double), ('reserved', C.c_uint64 * 4)]
+
+
 class Frame(C.Structure):   # nfc_frame
     _fields_ = [('cmd', C.c_int32), ('type', C.c_int32), ('byte_off', C.c_uint32), ('n_bytes', C.c_uint16),
                 ('n_header', C.c_uint16), ('n_extra', C.c_uint16), ('n_crc', C.c_uint16), ('flags', C.c_uint32),
@@ -83,6 +89,10 @@ TX_RUN_DTYPE = np.dtype([('level', '<i4'), ('pad', '<i4'), ('dur_us', '<f8')])  
 NFC_TX_SAME, NFC_TX_MANCHESTER, NFC_TX_MILLER = 0, 1, 2
 EDGE_DTYPE = np.dtype([('idx', '<u8'), ('d', '<i4'), ('v', 'i1'), ('t', 'i1'), ('pad', '<i2')])
 PACKET_DTYPE = np.dtype([('idx', '<u8'), ('bit_off', '<u8'), ('n_bits', '<u4'), ('type', '<i4')])
+# nfc_raw_frame: a frame as the GPU assembles it, and its flags beside FRAME_EXTRA_ERROR (1) / FRAME_MANY_MORE_ERROR (2)
+RAW_FRAME_DTYPE = np.dtype([('idx', '<u8'), ('byte_off', '<u4'), ('n_bits', '<u4'), ('n_bytes', '<u4'), ('flags', '<u4'), ('type', '<i4'),
+                            ('reserved', '<u4')])
+NFC_RAW_PARITY_OK, NFC_RAW_CRC_A_OK, NFC_RAW_CUT = 0x100, 0x200, 0x400
 COUNTS_DTYPE = np.dtype([('n_samples', '<u8'), ('n_edges', '<u8'), ('n_symbols', '<u8', (2,)), ('n_packets', '<u8', (2,)),
                          ('n_packet_bits', '<u8', (2,))])   # nfc_counts
 
@@ -97,7 +107,8 @@ SYMBOLS = ['nfc_abi_version', 'nfc_device_count', 'nfc_create', 'nfc_destroy', '
            'nfc_record_pcm16_device', 'nfc_host_record_pcm16',
            'nfc_multi_create', 'nfc_multi_destroy', 'nfc_multi_last_error', 'nfc_multi_push_device', 'nfc_multi_push', 'nfc_multi_get_counts',
            'nfc_multi_read_edges', 'nfc_multi_read_symbols', 'nfc_multi_read_packets', 'nfc_multi_read_packet_bits', 'nfc_multi_get_state',
-           'nfc_multi_set_state', 'nfc_multi_reset', 'nfc_multi_get_stats', 'nfc_multi_set_timing', 'nfc_multi_fetch', 'nfc_multi_get_counts_all']
+           'nfc_multi_set_state', 'nfc_multi_reset', 'nfc_multi_get_stats', 'nfc_multi_set_timing', 'nfc_multi_fetch', 'nfc_multi_get_counts_all',
+           'nfc_get_frame_counts', 'nfc_read_frames', 'nfc_read_frame_bytes', 'nfc_host_frames', 'nfc_fsm_process_frames', 'nfc_multi_fetch_frames']
 
 _libs = {}
 
@@ -207,6 +218,12 @@ def load(path=None):
     L.nfc_multi_set_timing.argtypes = [vp, C.c_int]
     L.nfc_multi_fetch.argtypes = [vp, u32, C.POINTER(MultiFetched)]
     L.nfc_multi_get_counts_all.argtypes = [vp, vp, vp]
+    L.nfc_get_frame_counts.argtypes = [vp, vp, vp]
+    L.nfc_read_frames.argtypes = [vp, C.c_int, vp, sz, psz]
+    L.nfc_read_frame_bytes.argtypes = [vp, C.c_int, sz, vp, vp, sz, psz]
+    L.nfc_host_frames.argtypes = [vp, sz, vp, C.c_int, vp, vp, vp, sz, psz]
+    L.nfc_fsm_process_frames.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp, sz, psz, vp]
+    L.nfc_multi_fetch_frames.argtypes = [vp, C.POINTER(MultiFrames)]
     for name in SYMBOLS:
         getattr(L, name)
     _libs[path] = L

@@ -10,7 +10,7 @@ from ._lib import (COUNTS_DTYPE, EDGE_DTYPE, NFC_MF_ARRAYS, NFC_MF_BITS0, NFC_MF
                    NFC_FLAG_FORCE_SEQUENTIAL, NFC_FLAG_NO_EDGES, NFC_IN_ENV_F32, NFC_IN_I16_SQ,
                    NFC_IN_IQ_F32, NFC_IN_IQ_I8, NFC_IN_IQ_I16, NFC_IN_IQ_U8, NFC_IN_REAL_F32_SQ, NFC_MULTI_PENDING_OVERFLOW,
                    NFC_MULTI_TRUNC_BITS, NFC_MULTI_TRUNC_EDGES, NFC_MULTI_TRUNC_PACKETS, NFC_MULTI_TRUNC_SYMBOLS, NFC_REC_ENVELOPE,
-                   NFC_REC_REAL_PART, PACKET_DTYPE)
+                   NFC_RAW_CRC_A_OK, NFC_RAW_CUT, NFC_RAW_PARITY_OK, NFC_REC_REAL_PART, PACKET_DTYPE, RAW_FRAME_DTYPE)
 
 __all__ = ['NfcContext', 'NfcError', 'DeviceBuffer', 'host_decode_lut', 'host_envelope', 'NFC_IN_IQ_F32', 'NFC_IN_ENV_F32',
            'NFC_IN_REAL_F32_SQ', 'NFC_IN_I16_SQ', 'NFC_IN_IQ_I16', 'NFC_IN_IQ_I8', 'NFC_IN_IQ_U8', 'NFC_FLAG_FORCE_SEQUENTIAL',
@@ -18,7 +18,8 @@ __all__ = ['NfcContext', 'NfcError', 'DeviceBuffer', 'host_decode_lut', 'host_en
            'NfcMultiContext', 'NfcMultiStream', 'NFC_MULTI_TRUNC_EDGES', 'NFC_MULTI_TRUNC_SYMBOLS', 'NFC_MULTI_TRUNC_PACKETS',
            'NFC_MULTI_TRUNC_BITS', 'NFC_MULTI_PENDING_OVERFLOW', 'NfcMultiFetch', 'NFC_MULTI_FETCH_EDGES', 'NFC_MULTI_FETCH_SYMBOLS',
            'NFC_MULTI_FETCH_PACKETS', 'NFC_MULTI_FETCH_ALL', 'NFC_MF_EDGES', 'NFC_MF_SYM0', 'NFC_MF_SYM1', 'NFC_MF_PK0', 'NFC_MF_PK1',
-           'NFC_MF_BITS0', 'NFC_MF_BITS1', 'NFC_MF_ARRAYS', 'COUNTS_DTYPE', 'COUNTS_FLAGS_DTYPE']
+           'NFC_MF_BITS0', 'NFC_MF_BITS1', 'NFC_MF_ARRAYS', 'COUNTS_DTYPE', 'COUNTS_FLAGS_DTYPE', 'NfcFrames', 'NfcMultiFrames', 'host_frames',
+           'RAW_FRAME_DTYPE', 'NFC_RAW_PARITY_OK', 'NFC_RAW_CRC_A_OK', 'NFC_RAW_CUT']
 
 _KIND_DTYPE = {NFC_IN_IQ_F32: (np.float32, 2), NFC_IN_ENV_F32: (np.float32, 1),
                NFC_IN_REAL_F32_SQ: (np.float32, 1), NFC_IN_I16_SQ: (np.int16, 1), NFC_IN_IQ_I16: (np.int16, 2),
@@ -206,6 +207,27 @@ class NfcContext(object):
         items.sort(key=lambda r: r[0])
         return [(t, b) for _, t, b in items]
 
+    def frame_counts(self):
+        """(n_frames[2], n_bytes[2]) of the last batch (nfc_get_frame_counts); the first frame call after a batch assembles them."""
+        nf, nb = np.zeros(2, np.uint64), np.zeros(2, np.uint64)
+        self._chk(self.L.nfc_get_frame_counts(self.h, nf.ctypes.data, nb.ctypes.data), 'nfc_get_frame_counts')
+        return nf, nb
+
+    def frames(self):
+        """The last batch's closed packets as frames assembled on the GPU -- repaired, nine bits to a byte, parity verdict, CRC_A
+        (nfc_read_frames / nfc_read_frame_bytes) -> NfcFrames.  fsm.process_frames takes it."""
+        nf, nb = self.frame_counts()
+        recs, data, par = [], [], []
+        got = C.c_size_t(0)
+        for t in (0, 1):
+            r, b, p = np.zeros(int(nf[t]), RAW_FRAME_DTYPE), np.zeros(int(nb[t]), np.uint8), np.zeros(int(nb[t]), np.uint8)
+            if r.size:
+                self._chk(self.L.nfc_read_frames(self.h, t, r.ctypes.data, r.size, C.byref(got)), 'nfc_read_frames')
+            if b.size:
+                self._chk(self.L.nfc_read_frame_bytes(self.h, t, 0, b.ctypes.data, p.ctypes.data, b.size, C.byref(got)), 'nfc_read_frame_bytes')
+            recs.append(r), data.append(b), par.append(p)
+        return NfcFrames(recs, data, par)
+
     def val(self):
         return self._read(self.L.nfc_read_val, self.counts().n_samples, np.int8, 0)
 
@@ -375,6 +397,15 @@ class NfcMultiContext(object):
         f = _lib.MultiFetched()
         self._chk(self.L.nfc_multi_fetch(self.h, int(what), C.byref(f)), 'nfc_multi_fetch')
         return NfcMultiFetch(self, f, copy, allow_truncated)
+
+    def fetch_frames(self, copy=True):
+        """Every stream's stored packets as frames assembled on the GPU -- bytes, parity bits, parity and CRC_A verdicts -- in ONE
+        packed buffer and one copy (nfc_multi_fetch_frames) -> NfcMultiFrames.  It has buffers of its own: a fetch() made before stays
+        readable, and the reverse.  copy=False: views of the context's pinned memory, valid until the next push, fetch_frames, reset,
+        set_state or close of this context."""
+        f = _lib.MultiFrames()
+        self._chk(self.L.nfc_multi_fetch_frames(self.h, C.byref(f)), 'nfc_multi_fetch_frames')
+        return NfcMultiFrames(f, copy)
 
     def counts_all(self):
         """Every stream's counts and flags of the last push from one call: a COUNTS_FLAGS_DTYPE array of n_streams records."""
@@ -624,6 +655,89 @@ class NfcMultiFetch(object):
         for s, t, i, j in zip(stream[order].tolist(), typ[order].tolist(), a[order].tolist(), b[order].tolist()):
             out[s].append((t, bits[t][i:j].tolist()))
         return out
+
+
+def _merge_frames(records):
+    """Both types' RAW_FRAME_DTYPE records in stream order: by idx, type 0 first on a tie (a tie cannot happen: one edge feeds one decoder)."""
+    t = np.concatenate(records) if len(records) else np.zeros(0, RAW_FRAME_DTYPE)
+    return t[np.lexsort((t['type'], t['idx']))] if len(t) else t
+
+
+class NfcFrames(object):
+    """Frames of one stream: `records[t]` the RAW_FRAME_DTYPE records per type in the packet table's order, `table` both types merged
+    by idx, `bytes[t]` / `par[t]` the data bytes and the ninth bits as received, indexed by a record's byte_off."""
+
+    def __init__(self, records, data, par):
+        self.records, self.bytes, self.par = list(records), list(data), list(par)
+        self.table = _merge_frames(self.records)
+
+    def data_of(self, rec):
+        """The bytes of one record, as a numpy view."""
+        o = int(rec['byte_off'])
+        return self.bytes[int(rec['type'])][o:o + int(rec['n_bytes'])]
+
+    def crc_ok_mask(self):
+        return (self.table['flags'] & NFC_RAW_CRC_A_OK) != 0
+
+
+class NfcMultiFrames(object):
+    """What nfc_multi_fetch_frames packs: frames[t] (RAW_FRAME_DTYPE; byte_off relative to the stream's own part of bytes[t] / par[t],
+    idx in the stream's own sample count), bytes[t], par[t]; frame_off[t] / byte_off[t]: n_streams + 1 offsets, stream k's frames of
+    type t are frames[t][frame_off[t][k]:frame_off[t][k + 1]] and its bytes bytes[t][byte_off[t][k]:byte_off[t][k + 1]].  A frame whose
+    bits the stream's slab cut carries NFC_RAW_CUT and no bytes."""
+
+    def __init__(self, f, copy=True):
+        K = int(f.n_streams)
+        self.n_streams, self.n_launches, self.bytes_copied, self.ms_kernels = K, int(f.n_launches), int(f.bytes_copied), float(f.ms_kernels)
+
+        def arr(ptr, n, dtype):
+            dtype = np.dtype(dtype)
+            if not ptr or not n:
+                return np.zeros(0, dtype)
+            a = np.frombuffer((C.c_char * (int(n) * dtype.itemsize)).from_address(ptr), dtype)
+            return a.copy() if copy else a
+
+        self.frame_off = [arr(f.frame_off[t], K + 1, '<u8') for t in (0, 1)]
+        self.byte_off = [arr(f.byte_off[t], K + 1, '<u8') for t in (0, 1)]
+        self.base = arr(f.base, K, '<u8')
+        self.frames = [arr(f.frames[t], self.frame_off[t][K], RAW_FRAME_DTYPE) for t in (0, 1)]
+        self.bytes = [arr(f.bytes[t], self.byte_off[t][K], np.uint8) for t in (0, 1)]
+        self.par = [arr(f.par[t], self.byte_off[t][K], np.uint8) for t in (0, 1)]
+
+    def frames_of(self, k):
+        """Stream k's part as an NfcFrames of numpy views (no copy)."""
+        recs, data, par = [], [], []
+        for t in (0, 1):
+            recs.append(self.frames[t][int(self.frame_off[t][k]):int(self.frame_off[t][k + 1])])
+            a, b = int(self.byte_off[t][k]), int(self.byte_off[t][k + 1])
+            data.append(self.bytes[t][a:b]), par.append(self.par[t][a:b])
+        return NfcFrames(recs, data, par)
+
+    def stream_of(self, ptype):
+        """The stream every frame of frames[ptype] belongs to."""
+        return np.repeat(np.arange(self.n_streams, dtype=np.int64), np.diff(self.frame_off[ptype]).astype(np.int64))
+
+    def crc_ok_mask(self):
+        """Per type, over ALL frames of frames[t]: parity held and the CRC_A matched."""
+        return [(self.frames[t]['flags'] & NFC_RAW_CRC_A_OK) != 0 for t in (0, 1)]
+
+
+def host_frames(table, bits, ptype):
+    """The frame kernels' twin on the CPU (nfc_host_frames): the packets `table` (PACKET_DTYPE rows of ONE type) over that type's bit
+    array, a byte per bit -> (records, bytes, par)."""
+    L = _lib.load()
+    t = np.ascontiguousarray(table, PACKET_DTYPE)
+    b = np.ascontiguousarray(bits, np.uint8)
+    if len(t) and int((t['bit_off'] + t['n_bits']).max()) > b.size:
+        raise NfcError('the packets reach behind the bit array')
+    cap = int(t['n_bits'].sum()) // 9 + len(t) + 1
+    recs, data, par = np.zeros(len(t), RAW_FRAME_DTYPE), np.zeros(cap, np.uint8), np.zeros(cap, np.uint8)
+    used = C.c_size_t(0)
+    rc = L.nfc_host_frames(t.ctypes.data if len(t) else None, len(t), b.ctypes.data if b.size else None, int(ptype), recs.ctypes.data,
+                           data.ctypes.data, par.ctypes.data, cap, C.byref(used))
+    if rc != 0:
+        raise NfcError('nfc_host_frames status %d' % rc)
+    return recs, data[:used.value], par[:used.value]
 
 
 class DeviceBuffer(object):

@@ -267,6 +267,12 @@ struct nfc_ctx {
     // lazily built packet lists
     std::vector<nfc_packet> pk[2];
     bool pk_ready[2] = {false, false};
+    // lazily assembled frames (frames.hip.h; nfc_read_frames ...): records, bytes and parity bits per type, the four totals
+    DevBuf d_fr_rec[2], d_fr_bytes[2], d_fr_par[2], d_fr_tot;
+    bool frames_ready = false;
+    uint64_t fr_frames[2] = {0, 0}, fr_bytes[2] = {0, 0};
+    hipEvent_t fr_ev[2] = {};   // around the two launches (nfc_set_timing >= 1)
+    float fr_ms = 0.f;
 };
 
 namespace {

@@ -575,7 +575,7 @@ int process_batch(nfc_ctx *c, const void *d_in, size_t n64) {
     if (c->sub_count && !c->in_wait) return fail(c, NFC_ERR_STATE, "batches submitted with nfc_submit_device are in flight: nfc_wait for them first");
     c->low_valid = false;
     c->have_outputs = false;
-    c->pk_ready[0] = c->pk_ready[1] = false;
+    c->pk_ready[0] = c->pk_ready[1] = c->frames_ready = false;
     c->n_edges = 0;
     for (int t = 0; t < 2; t++) c->n_sym[t] = c->n_close[t] = c->n_bits[t] = 0;
     memset(&c->stats, 0, sizeof c->stats);

@@ -98,7 +98,7 @@ int enqueue_stages_behind(nfc_ctx *c, nfc_ctx::Submitted &b) {
     HIPCHK(c, hipStreamWaitEvent(c->st, c->ev_a[b.slot], 0));
     if (b.planes >= 0) take_planes(c, b);
     c->have_outputs = false;
-    c->pk_ready[0] = c->pk_ready[1] = false;
+    c->pk_ready[0] = c->pk_ready[1] = c->frames_ready = false;
     c->n_edges = 0;
     for (int t = 0; t < 2; t++) c->n_sym[t] = c->n_close[t] = c->n_bits[t] = 0;
     memset(&c->stats, 0, sizeof c->stats);

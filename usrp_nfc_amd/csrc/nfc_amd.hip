@@ -54,6 +54,7 @@
 #include "iq8.h"    // (the complex 8-bit kinds' kernels: nfc_iq8.hip)
 #include "tx.hip.h"
 #include "record.hip.h"   // (the recording kernel: nfc_record.hip)
+#include "frames.hip.h"   // (the frame assembly kernels: nfc_frames.hip)
 #include "scale_arg.h"
 
 using namespace nfc;
@@ -501,8 +502,11 @@ void nfc_destroy(nfc_ctx *c) {
                      &c->d_touched[1], &c->d_info[0], &c->d_info[1], &c->d_ver, &c->d_cflags, &c->d_list, &c->d_ecode, &c->d_epos, &c->d_eidx, &c->d_states, &c->d_sym[0], &c->d_sym[1],
                      &c->d_bits[0], &c->d_bits[1], &c->d_pending[0][0], &c->d_pending[0][1],
                      &c->d_pending[1][0], &c->d_pending[1][1], &c->d_partials2, &c->d_close_end[0], &c->d_close_end[1], &c->d_close_idx[0], &c->d_close_idx[1],
-                     &c->d_partials, &c->d_aggs, &c->d_faggs, &c->d_spec, &c->d_stage_bits[0], &c->d_stage_bits[1], &c->d_stage_cb[0], &c->d_stage_cb[1], &c->d_stage_ci[0], &c->d_stage_ci[1], &c->d_stage_q[0], &c->d_stage_q[1], &c->d_stage_own, &c->d_gring, &c->d_pack, &c->d_gvtop, &c->d_seqout, &c->d_tail_st, &c->d_tail_ticket, &c->d_bits_alt[0], &c->d_bits_alt[1]};
+                     &c->d_partials, &c->d_aggs, &c->d_faggs, &c->d_spec, &c->d_stage_bits[0], &c->d_stage_bits[1], &c->d_stage_cb[0], &c->d_stage_cb[1], &c->d_stage_ci[0], &c->d_stage_ci[1], &c->d_stage_q[0], &c->d_stage_q[1], &c->d_stage_own, &c->d_gring, &c->d_pack, &c->d_gvtop, &c->d_seqout, &c->d_tail_st, &c->d_tail_ticket, &c->d_bits_alt[0], &c->d_bits_alt[1],
+                     &c->d_fr_rec[0], &c->d_fr_rec[1], &c->d_fr_bytes[0], &c->d_fr_bytes[1], &c->d_fr_par[0], &c->d_fr_par[1], &c->d_fr_tot};
     for (DevBuf *b : all) b->release();
+    for (auto &e : c->fr_ev)
+        if (e) (void)hipEventDestroy(e);
     if (c->hs) (void)hipHostFree(c->hs);
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     if (c->h_edge_stage) (void)hipHostFree(c->h_edge_stage);
@@ -575,7 +579,7 @@ int nfc_push_edges(nfc_ctx *c, const nfc_edge *host_edges, size_t n64) {
     if (hipSetDevice(c->P.device) != hipSuccess) return fail(c, NFC_ERR_DEVICE, "hipSetDevice failed");
     const uint32_t n = (uint32_t)n64;
     c->have_outputs = false;
-    c->pk_ready[0] = c->pk_ready[1] = false;
+    c->pk_ready[0] = c->pk_ready[1] = c->frames_ready = false;
     c->n_edges = 0;
     for (int t = 0; t < 2; t++) c->n_sym[t] = c->n_close[t] = c->n_bits[t] = 0;
     memset(&c->stats, 0, sizeof c->stats);
@@ -864,6 +868,125 @@ int nfc_read_packet_bits(nfc_ctx *c, int type, size_t first, uint8_t *out, size_
     return NFC_OK;
 }
 
+// ---- frames: assembled on the device on the first read after a batch (frames.hip.h, nfc_frames.hip) ----
+extern "C++" {
+namespace {
+int pk_stage(nfc_ctx *c, size_t need) {   // the pinned staging area the packet tables use, at least `need` bytes
+    if (c->h_pk_stage_cap >= need) return NFC_OK;
+    devbuf_allocs()++;
+    if (c->h_pk_stage) (void)hipHostFree(c->h_pk_stage);
+    c->h_pk_stage = nullptr;
+    c->h_pk_stage_cap = 0;
+    const size_t cap2 = need + need / 2 + 65536;
+    HIPCHK(c, hipHostMalloc((void **)&c->h_pk_stage, cap2, hipHostMallocDefault));
+    c->h_pk_stage_cap = cap2;
+    return NFC_OK;
+}
+int ensure_frames(nfc_ctx *c) {
+    if (!c->have_outputs) return fail(c, NFC_ERR_STATE, "no completed batch");
+    if (c->frames_ready) return NFC_OK;
+    if (hipSetDevice(c->P.device) != hipSuccess) return fail(c, NFC_ERR_DEVICE, "hipSetDevice failed");
+    c->fr_frames[0] = c->fr_frames[1] = c->fr_bytes[0] = c->fr_bytes[1] = 0;
+    c->fr_ms = 0.f;
+    if (c->n_close[0] || c->n_close[1]) {   // (a batch that closed no packet launches nothing)
+        frames::CtxArgs A;
+        memset(&A, 0, sizeof A);
+        HIPCHK(c, c->d_fr_tot.ensure(64));
+        for (int t = 0; t < 2; t++) {
+            // a frame has at most (n_bits + 1) / 9 bytes: the type's bits and one more per close bound the section
+            const size_t byte_cap = ((size_t)c->n_bits[t] + c->n_close[t]) / 9 + 16;
+            HIPCHK(c, c->d_fr_rec[t].ensure(((size_t)c->n_close[t] + 1) * sizeof(nfc_raw_frame)));
+            HIPCHK(c, c->d_fr_bytes[t].ensure(byte_cap));
+            HIPCHK(c, c->d_fr_par[t].ensure(byte_cap));
+            A.close_end[t] = c->d_close_end[t].as<uint32_t>();
+            A.close_idx[t] = c->d_close_idx[t].as<uint64_t>();
+            A.n_close[t] = c->n_close[t];
+            A.bits[t] = c->d_bits[t].p;
+            A.records[t] = c->d_fr_rec[t].as<nfc_raw_frame>();
+            A.bytes[t] = c->d_fr_bytes[t].as<uint8_t>();
+            A.par[t] = c->d_fr_par[t].as<uint8_t>();
+            A.byte_cap[t] = (uint32_t)std::min<size_t>(byte_cap, 0xFFFFFFFFu);
+        }
+        A.totals = c->d_fr_tot.as<uint64_t>();
+        const bool timed = c->timing >= 1;
+        if (timed)
+            for (auto &e : c->fr_ev)
+                if (!e) HIPCHK(c, hipEventCreate(&e));
+        frames::launch_ctx(A, c->bits_packed, c->st, timed ? c->fr_ev[0] : nullptr, timed ? c->fr_ev[1] : nullptr);
+        if (int rc = pk_stage(c, 64)) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->h_pk_stage, c->d_fr_tot.p, 32, hipMemcpyDeviceToHost, c->st));
+        HIPCHK(c, hipStreamSynchronize(c->st));
+        BATCHCHK(c, false);
+        const uint64_t *tot = (const uint64_t *)c->h_pk_stage;
+        for (int t = 0; t < 2; t++) {
+            c->fr_frames[t] = tot[2 * t];
+            c->fr_bytes[t] = tot[2 * t + 1];
+            if (c->fr_frames[t] > c->n_close[t] || c->fr_bytes[t] > A.byte_cap[t])
+                return fail(c, NFC_ERR_INTERNAL, "frame scan of type %d: %llu frames, %llu bytes from %u closes and %u bits", t,
+                            (unsigned long long)c->fr_frames[t], (unsigned long long)c->fr_bytes[t], c->n_close[t], c->n_bits[t]);
+        }
+        if (timed) HIPCHK(c, hipEventElapsedTime(&c->fr_ms, c->fr_ev[0], c->fr_ev[1]));
+    }
+    c->frames_ready = true;   // (only now: a launch or a wait that failed leaves nothing behind, and the next read tries again)
+    return NFC_OK;
+}
+// n entries of esz bytes from dev to out: straight into a pinned destination, else through the pinned staging area
+int read_pinned(nfc_ctx *c, const void *dev, void *out, size_t bytes) {
+    unsigned int f0 = 0;
+    if (hipHostGetFlags(&f0, out) == hipSuccess) {
+        HIPCHK(c, hipMemcpyAsync(out, dev, bytes, hipMemcpyDeviceToHost, c->st));
+        HIPCHK(c, hipStreamSynchronize(c->st));
+        return NFC_OK;
+    }
+    (void)hipGetLastError();   // (not pinned: hipHostGetFlags left its complaint behind)
+    if (int rc = pk_stage(c, bytes)) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->h_pk_stage, dev, bytes, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    memcpy(out, c->h_pk_stage, bytes);
+    return NFC_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int nfc_get_frame_counts(nfc_ctx *c, uint64_t n_frames[2], uint64_t n_bytes[2]) {
+    LaunchScope launch_scope_(c ? &c->launch_err : nullptr);
+    if (!c) return NFC_ERR_ARG;
+    if (int rc = ensure_frames(c)) return rc;
+    for (int t = 0; t < 2; t++) {
+        if (n_frames) n_frames[t] = c->fr_frames[t];
+        if (n_bytes) n_bytes[t] = c->fr_bytes[t];
+    }
+    return NFC_OK;
+}
+
+int nfc_read_frames(nfc_ctx *c, int type, nfc_raw_frame *out, size_t cap, size_t *n_out) {
+    LaunchScope launch_scope_(c ? &c->launch_err : nullptr);
+    if (!c || type < 0 || type > 1) return NFC_ERR_ARG;
+    if (int rc = ensure_frames(c)) return rc;
+    const size_t n = std::min<size_t>(cap, c->fr_frames[type]);
+    if (n && !out) return fail(c, NFC_ERR_ARG, "null output");
+    if (n)
+        if (int rc = read_pinned(c, c->d_fr_rec[type].p, out, n * sizeof(nfc_raw_frame))) return rc;
+    if (n_out) *n_out = n;
+    return NFC_OK;
+}
+
+int nfc_read_frame_bytes(nfc_ctx *c, int type, size_t first, uint8_t *bytes_out, uint8_t *par_out, size_t cap, size_t *n_out) {
+    LaunchScope launch_scope_(c ? &c->launch_err : nullptr);
+    if (!c || type < 0 || type > 1) return NFC_ERR_ARG;
+    if (int rc = ensure_frames(c)) return rc;
+    size_t n = 0;
+    if (first < c->fr_bytes[type]) n = std::min<size_t>(cap, c->fr_bytes[type] - first);
+    if (n && !bytes_out) return fail(c, NFC_ERR_ARG, "null output");
+    if (n) {
+        if (int rc = read_pinned(c, c->d_fr_bytes[type].as<uint8_t>() + first, bytes_out, n)) return rc;
+        if (par_out)
+            if (int rc = read_pinned(c, c->d_fr_par[type].as<uint8_t>() + first, par_out, n)) return rc;
+    }
+    if (n_out) *n_out = n;
+    return NFC_OK;
+}
+
 int nfc_read_val(nfc_ctx *c, size_t first, int8_t *out, size_t cap, size_t *n_out) {
     LaunchScope launch_scope_(c ? &c->launch_err : nullptr);
     if (!c) return NFC_ERR_ARG;
@@ -1110,6 +1233,24 @@ int nfc_fsm_process_packets(nfc_fsm *f, const nfc_packet *packets, size_t n_pack
         if (p.n_bits && !bits) return NFC_ERR_ARG;
         if (used + p.n_bits / 9 + 1 > bytes_cap) return NFC_ERR_ARG;
         fsm_process(*f, bits ? bits + p.bit_off : nullptr, p.n_bits, p.type, &frames_out[i], bytes_out + used, enc_out ? enc_out + used : nullptr);
+        frames_out[i].byte_off = (uint32_t)used;
+        used += std::max<size_t>(frames_out[i].n_bytes, frames_out[i].n_enc);
+    }
+    if (bytes_used) *bytes_used = used;
+    return NFC_OK;
+}
+int nfc_fsm_process_frames(nfc_fsm *f, const nfc_raw_frame *frames, size_t n, const uint8_t *bytes0, const uint8_t *par0, const uint8_t *bytes1,
+                           const uint8_t *par1, nfc_frame *frames_out, uint8_t *bytes_out, size_t bytes_cap, size_t *bytes_used, uint16_t *enc_out) {
+    if (!f || (n && (!frames || !frames_out || !bytes_out))) return NFC_ERR_ARG;
+    size_t used = 0;
+    for (size_t i = 0; i < n; i++) {
+        const nfc_raw_frame &r = frames[i];
+        if ((r.type != 0 && r.type != 1) || (r.flags & NFC_RAW_CUT)) return NFC_ERR_ARG;
+        const uint8_t *b = r.type ? bytes1 : bytes0, *p = r.type ? par1 : par0;
+        if (r.n_bytes && (!b || !p)) return NFC_ERR_ARG;
+        if (used + r.n_bits / 9 + 1 > bytes_cap) return NFC_ERR_ARG;
+        fsm_process_frame(*f, r, b ? b + r.byte_off : nullptr, p ? p + r.byte_off : nullptr, &frames_out[i], bytes_out + used,
+                          enc_out ? enc_out + used : nullptr);
         frames_out[i].byte_off = (uint32_t)used;
         used += std::max<size_t>(frames_out[i].n_bytes, frames_out[i].n_enc);
     }
@@ -1486,4 +1627,9 @@ extern "C" int nfc_debug_gen_prof(unsigned long long *out, int reset) {
     }
     return 0;
 }
+#endif
+#ifdef NFC_TEST_HOOKS
+// the frame assembly's two launches of the last batch by HIP events (nfc_set_timing >= 1 before the frames were first read; else 0):
+// what tests/frames_bench.py sets beside the batch's own time
+extern "C" float nfc_debug_frames_ms(const nfc_ctx *c) { return c && c->frames_ready ? c->fr_ms : -1.f; }
 #endif

@@ -23,6 +23,7 @@
 #include "decoder_tables.h"
 #include "multi.hip.h"
 #include "multi_fetch.hip.h"
+#include "frames.hip.h"   // (the frame assembly kernels: nfc_frames.hip)
 #include "scale_arg.h"
 
 using namespace nfc;
@@ -71,6 +72,12 @@ struct nfc_multi {
     FetchLayout flay;                                    // of the last fetch that copied anything
     bool fetch_guarded = false;                          // d_fetch holds guards at flay's places
     nfc_multi_fetched fout;
+    // the frames (frames.hip.h, nfc_multi_fetch_frames): a packed buffer and a pinned twin of their own -- a fetch and a frame fetch do
+    // not end each other's pointers; the pinned one is followed by base[K]
+    uint8_t *d_frames = nullptr, *h_frames = nullptr;
+    size_t d_frames_cap = 0, h_frames_cap = 0;
+    frames::MultiLayout frlay;
+    bool frames_guarded = false;
     nfc_multi_stats stats;
     std::string err;
     LaunchError launch_err;
@@ -282,6 +289,8 @@ void nfc_multi_destroy(nfc_multi *m) {
     if (m->d_stage) (void)hipFree(m->d_stage);
     if (m->d_fetch) (void)hipFree(m->d_fetch);
     if (m->d_ftable) (void)hipFree(m->d_ftable);
+    if (m->d_frames) (void)hipFree(m->d_frames);
+    if (m->h_frames) (void)hipHostFree(m->h_frames);
     for (uint8_t *p : {m->h_up, (uint8_t *)m->h_counts, m->h_blob, m->h_stage, m->h_read, m->h_fetch, (uint8_t *)m->h_ftable})
         if (p) (void)hipHostFree(p);
     for (hipEvent_t e : m->ev)
@@ -714,6 +723,141 @@ int nfc_multi_fetch(nfc_multi *m, uint32_t what, nfc_multi_fetched *out) {
     return NFC_OK;
 }
 
+// The frames of every stream's stored packets, assembled on the device into one packed buffer (frames.hip.h):
+//     totals (64 bytes) | table [4][K + 1] | records 0 | records 1 | bytes 0 | bytes 1 | par 0 | par 1
+// each section on 16 bytes with GUARD_BYTES of the guard word behind it.  The host knows every stream's frame count from its mirror of
+// the counts, not its byte count (that takes the close rows): the byte sections are laid out for the most the stored bits can give --
+// a frame has at most (n_bits + 1) / 9 bytes -- and the device's table, which travels in the buffer, says where a stream's bytes are.
+int nfc_multi_fetch_frames(nfc_multi *m, nfc_multi_frames *out) {
+    if (!m) return NFC_ERR_ARG;
+    LaunchScope scope(&m->launch_err);
+    if (!m->have_outputs) return mfail(m, NFC_ERR_STATE, "no completed push");
+    if (hipSetDevice(m->P.device) != hipSuccess) return mfail(m, NFC_ERR_DEVICE, "hipSetDevice failed");
+    const uint32_t K = m->K;
+    const size_t T = (size_t)K + 1;
+    uint64_t n_fr[2] = {0, 0}, room[2] = {0, 0};
+    for (uint32_t k = 0; k < K; k++) {
+        const uint32_t *c = m->h_counts + (size_t)k * CNT_WORDS;
+        for (int t = 0; t < 2; t++) {
+            const uint64_t npk = std::min(c[CNT_PK0 + t], m->C.packets), bits = std::min(c[CNT_BITS0 + t], m->C.bits);
+            n_fr[t] += npk;
+            room[t] += npk ? (bits + npk) / 9 : 0;
+        }
+    }
+    nfc_multi_frames f;
+    memset(&f, 0, sizeof f);
+    f.n_streams = K;
+    frames::MultiLayout F;
+    memset(&F, 0, sizeof F);
+    size_t at = up16(frames::MULTI_HEADER_BYTES + 4 * T * 8);
+    for (int t = 0; t < 2; t++) {
+        F.at_fr[t] = at;
+        F.end_fr[t] = at + n_fr[t] * sizeof(nfc_raw_frame);
+        at = up16(F.end_fr[t] + GUARD_BYTES);
+        F.total_frames[t] = n_fr[t];
+        F.total_bytes[t] = room[t];
+    }
+    for (int t = 0; t < 2; t++) {
+        F.at_bytes[t] = at;
+        F.end_bytes[t] = at + room[t];
+        at = up16(F.end_bytes[t] + GUARD_BYTES);
+    }
+    for (int t = 0; t < 2; t++) {
+        F.at_par[t] = at;
+        F.end_par[t] = at + room[t];
+        at = up16(F.end_par[t] + GUARD_BYTES);
+    }
+    const size_t bytes = at, host_bytes = bytes + (size_t)K * 8;
+    // (the pinned buffer always: the offset tables and base[] are handed out when nothing was stored, too)
+    if (m->h_frames_cap < host_bytes) {
+        if (m->h_frames) (void)hipHostFree(m->h_frames);
+        m->h_frames = nullptr;
+        m->h_frames_cap = 0;
+        const size_t cap = host_bytes + host_bytes / 2 + 4096;
+        if (hipHostMalloc((void **)&m->h_frames, cap, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            m->h_frames = nullptr;
+            return mfail(m, NFC_ERR_NOMEM, "nfc_multi_fetch_frames: no pinned host memory for %zu bytes", cap);
+        }
+        m->h_frames_cap = cap;
+    }
+    uint8_t *h = m->h_frames;
+    uint64_t *tab = (uint64_t *)(h + frames::MULTI_HEADER_BYTES), *base = (uint64_t *)(h + bytes);
+    bool based = false;
+    for (uint32_t k = 0; k < K; k++) {
+        base[k] = m->g0[k];
+        based = based || m->g0[k] != 0;
+    }
+    if (n_fr[0] + n_fr[1]) {
+        if (m->d_frames_cap < bytes) {
+            if (m->d_frames) (void)hipFree(m->d_frames);
+            m->d_frames = nullptr;
+            m->d_frames_cap = 0;
+            m->frames_guarded = false;
+            const size_t cap = bytes + bytes / 2 + 4096;
+            if (hipMalloc((void **)&m->d_frames, cap) != hipSuccess) {
+                (void)hipGetLastError();
+                m->d_frames = nullptr;
+                return mfail(m, NFC_ERR_NOMEM, "nfc_multi_fetch_frames: no device memory for %zu bytes", cap);
+            }
+            m->d_frames_cap = cap;
+        }
+        frames::MultiArgs A;
+        memset(&A, 0, sizeof A);
+        for (int t = 0; t < 2; t++) {
+            A.close[t] = m->A.O.close[t];
+            A.bits[t] = m->A.O.bits[t];
+        }
+        A.counts = m->A.O.counts;
+        A.cnt_words = CNT_WORDS, A.cnt_pk0 = CNT_PK0, A.cnt_bits0 = CNT_BITS0;
+        A.cap_packets = m->C.packets, A.cap_bits = m->C.bits, A.s_packets = m->C.s_packets, A.s_bits = m->C.s_bits;
+        A.K = K;
+        A.table = (uint64_t *)(m->d_frames + frames::MULTI_HEADER_BYTES);
+        A.packed = m->d_frames;
+        A.guard_word = GUARD_WORD, A.guard_bytes = GUARD_BYTES;
+        A.F = F;
+        frames::launch_multi(A, m->st, m->timing ? m->ev[0] : nullptr, m->timing ? m->ev[1] : nullptr);
+        m->frlay = F;
+        m->frames_guarded = true;
+        MCHK(m, hipMemcpyAsync(h, m->d_frames, bytes, hipMemcpyDeviceToHost, m->st));
+        MCHK(m, hipStreamSynchronize(m->st));
+        if (int rc = launch_ok(m)) return rc;
+        const uint64_t *dev_total = (const uint64_t *)h;
+        for (int t = 0; t < 2; t++)
+            if (dev_total[t] != n_fr[t] || dev_total[2 + t] > room[t])
+                return mfail(m, NFC_ERR_INTERNAL, "nfc_multi_fetch_frames: type %d: the device counts %llu frames and %llu bytes, the host %llu frames and room for %llu bytes",
+                             t, (unsigned long long)dev_total[t], (unsigned long long)dev_total[2 + t], (unsigned long long)n_fr[t], (unsigned long long)room[t]);
+        if (m->timing) {
+            float ms = 0.f;
+            MCHK(m, hipEventElapsedTime(&ms, m->ev[0], m->ev[1]));
+            f.ms_kernels = ms;
+        }
+        f.n_launches = 2;
+        f.bytes_copied = bytes;
+        for (int t = 0; t < 2; t++) {
+            f.frames[t] = (const nfc_raw_frame *)(h + F.at_fr[t]);
+            f.bytes[t] = h + F.at_bytes[t];
+            f.par[t] = h + F.at_par[t];
+        }
+        if (based)   // (the device left idx batch-local: the stream's base is added here, over the few frames there are)
+            for (int t = 0; t < 2; t++) {
+                nfc_raw_frame *fr = (nfc_raw_frame *)(h + F.at_fr[t]);
+                const uint64_t *off = tab + (size_t)t * T;
+                for (uint32_t k = 0; k < K; k++)
+                    for (uint64_t i = off[k]; i < off[k + 1]; i++) fr[i].idx += base[k];
+            }
+    } else {
+        memset(tab, 0, 4 * T * 8);
+    }
+    for (int t = 0; t < 2; t++) {
+        f.frame_off[t] = tab + (size_t)t * T;
+        f.byte_off[t] = tab + (size_t)(2 + t) * T;
+    }
+    f.base = base;
+    if (out) *out = f;
+    return NFC_OK;
+}
+
 int nfc_multi_read_edges(nfc_multi *m, uint32_t stream, size_t first, nfc_edge *out, size_t cap, size_t *n_out) {
     if (!m) return NFC_ERR_ARG;
     LaunchScope scope(&m->launch_err);
@@ -945,6 +1089,16 @@ extern "C" int nfc_debug_multi_guards(nfc_multi *m) {
             if (hipMemcpyAsync(g[s], m->d_fetch + ends[s], GUARD_BYTES, hipMemcpyDeviceToHost, m->st) != hipSuccess) return -1;
         if (hipStreamSynchronize(m->st) != hipSuccess) return -1;
         for (int s = 0; s < MF_SECTIONS; s++)
+            for (int b = 0; b < GUARD_BYTES; b++) h += g[s][b] != (uint8_t)(GUARD_WORD >> (8 * (b & 3)));
+    }
+    if (m->frames_guarded) {   // ... and behind the sections of the frames' packed buffer (nfc_multi_fetch_frames)
+        const frames::MultiLayout &F = m->frlay;
+        const uint64_t ends[6] = {F.end_fr[0], F.end_fr[1], F.end_bytes[0], F.end_bytes[1], F.end_par[0], F.end_par[1]};
+        uint8_t g[6][GUARD_BYTES];
+        for (int s = 0; s < 6; s++)
+            if (hipMemcpyAsync(g[s], m->d_frames + ends[s], GUARD_BYTES, hipMemcpyDeviceToHost, m->st) != hipSuccess) return -1;
+        if (hipStreamSynchronize(m->st) != hipSuccess) return -1;
+        for (int s = 0; s < 6; s++)
             for (int b = 0; b < GUARD_BYTES; b++) h += g[s][b] != (uint8_t)(GUARD_WORD >> (8 * (b & 3)));
     }
     return (int)h;

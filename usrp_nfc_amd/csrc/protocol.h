@@ -281,27 +281,10 @@ struct nfc_fsm {
 
 namespace nfc {
 
-// One packet (bits as PacketProcessor hands them over, packets.py:94-98).  Returns the frame record; bytes_out
-// receives the frame's bytes (capacity >= n_bits / 9 + 1).
-// enc_out (optional, same capacity): while a session is up, what was on the air -- one entry per nine bits, the byte in
-// the low half, bit 8 set when the parity bit equals the data parity (the '!' of fsm._print_enc, fsm.py:113-131).
-inline void fsm_process(nfc_fsm &F, const uint8_t *bits_in, size_t n_bits, int type, nfc_frame *out, uint8_t *bytes_out,
-                        uint16_t *enc_out = nullptr) {
-    memset(out, 0, sizeof *out);
-    out->type = type;
-    out->cmd = NFC_CMD_UNKNOWN;
-    // fsm.py:49-66: bring the bit count to a multiple of nine
-    const int start_bit = (type == 0) ? 1 : 0;   // packets.py:24-28
-    std::vector<uint8_t> bits(bits_in, bits_in + n_bits);
-    const size_t rem = n_bits % 9;
-    if (rem == 8) bits.push_back((uint8_t)start_bit);
-    else if (rem == 1) {
-        if (bits.back() != start_bit) out->flags |= NFC_FRAME_EXTRA_ERROR;
-        bits.pop_back();
-    } else if (rem != 0) {
-        out->flags |= NFC_FRAME_MANY_MORE_ERROR;
-        bits.resize(n_bits - rem);
-    }
+// The core is shared by the two entries: fsm_process (a packet's bits) and fsm_process_frame (a frame assembled on the GPU).
+//   fsm_strip   the repaired bits (a multiple of nine) -> decryption while a session is up -> parity strip: the frame's bytes
+//   fsm_finish  the bytes -> command, record, tag type / UID / session state
+inline int fsm_strip(nfc_fsm &F, std::vector<uint8_t> &bits, nfc_frame *out, uint8_t *bytes_out, uint16_t *enc_out) {
     if (F.encrypted) {   // fsm.py:133-154
         out->flags |= NFC_FRAME_ENCRYPTED;
         int ne = 0;
@@ -359,6 +342,10 @@ inline void fsm_process(nfc_fsm &F, const uint8_t *bits_in, size_t n_bits, int t
         if (!bad && k == 8) bytes_out[nb++] = (uint8_t)cur;
         if (bad) nb = 0;
     }
+    return nb;
+}
+
+inline void fsm_finish(nfc_fsm &F, int nb, int type, nfc_frame *out, uint8_t *bytes_out) {
     if (nb == 0) {   // `if not bytes` (fsm.py:225): a parity error, or nothing left
         out->cmd = NFC_CMD_PARITY_ERROR;
         return;
@@ -424,6 +411,56 @@ inline void fsm_process(nfc_fsm &F, const uint8_t *bits_in, size_t n_bits, int t
         break;
     default: break;
     }
+}
+
+// One packet (bits as PacketProcessor hands them over, packets.py:94-98).  Returns the frame record; bytes_out
+// receives the frame's bytes (capacity >= n_bits / 9 + 1).
+// enc_out (optional, same capacity): while a session is up, what was on the air -- one entry per nine bits, the byte in
+// the low half, bit 8 set when the parity bit equals the data parity (the '!' of fsm._print_enc, fsm.py:113-131).
+inline void fsm_process(nfc_fsm &F, const uint8_t *bits_in, size_t n_bits, int type, nfc_frame *out, uint8_t *bytes_out,
+                        uint16_t *enc_out = nullptr) {
+    memset(out, 0, sizeof *out);
+    out->type = type;
+    out->cmd = NFC_CMD_UNKNOWN;
+    // fsm.py:49-66: bring the bit count to a multiple of nine
+    const int start_bit = (type == 0) ? 1 : 0;   // packets.py:24-28
+    std::vector<uint8_t> bits(bits_in, bits_in + n_bits);
+    const size_t rem = n_bits % 9;
+    if (rem == 8) bits.push_back((uint8_t)start_bit);
+    else if (rem == 1) {
+        if (bits.back() != start_bit) out->flags |= NFC_FRAME_EXTRA_ERROR;
+        bits.pop_back();
+    } else if (rem != 0) {
+        out->flags |= NFC_FRAME_MANY_MORE_ERROR;
+        bits.resize(n_bits - rem);
+    }
+    const int nb = fsm_strip(F, bits, out, bytes_out, enc_out);
+    fsm_finish(F, nb, type, out, bytes_out);
+}
+
+// One frame as the GPU assembled it (nfc_raw_frame: csrc/frames.hip.h): the repair is done, `bytes` / `par` hold its n_bytes data bytes
+// and the ninth bits as received, its flags the repair's messages and the parity verdict.  Outside a session the bytes are taken as
+// they are and no bit is touched; inside one the on-air bits are rebuilt from bytes and par -- exactly the repaired bit list of
+// fsm_process -- and go the same way.  Same outputs, same state afterwards as fsm_process on the packet the frame came from.
+inline void fsm_process_frame(nfc_fsm &F, const nfc_raw_frame &r, const uint8_t *bytes, const uint8_t *par, nfc_frame *out,
+                              uint8_t *bytes_out, uint16_t *enc_out = nullptr) {
+    memset(out, 0, sizeof *out);
+    out->type = r.type;
+    out->cmd = NFC_CMD_UNKNOWN;
+    out->flags = r.flags & (uint32_t)(NFC_FRAME_EXTRA_ERROR | NFC_FRAME_MANY_MORE_ERROR);
+    int nb;
+    if (F.encrypted) {
+        std::vector<uint8_t> bits((size_t)r.n_bytes * 9);
+        for (size_t i = 0; i < r.n_bytes; i++) {
+            for (int k = 0; k < 8; k++) bits[9 * i + k] = (uint8_t)((bytes[i] >> k) & 1);
+            bits[9 * i + 8] = par[i] & 1;
+        }
+        nb = fsm_strip(F, bits, out, bytes_out, enc_out);
+    } else {
+        nb = (r.flags & NFC_RAW_PARITY_OK) ? (int)r.n_bytes : 0;
+        if (nb) memcpy(bytes_out, bytes, (size_t)nb);
+    }
+    fsm_finish(F, nb, r.type, out, bytes_out);
 }
 
 

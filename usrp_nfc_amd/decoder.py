@@ -80,7 +80,7 @@ _SCALED_KINDS = (api.NFC_IN_I16_SQ, api.NFC_IN_IQ_I16, api.NFC_IN_IQ_I8, api.NFC
 _RECORDED_KINDS = _IQ_KINDS + (api.NFC_IN_ENV_F32,)   # (the kinds `dst` records: the UHD branch's stand-ins and a ready envelope)
 
 
-def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None, keep=None, device=0, push_stats=None, **sink_kwargs):
+def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None, keep=None, device=0, push_stats=None, frames=False, **sink_kwargs):
     """Decode many recordings at once: every source is a stream of one api.NfcMultiContext, a GPU lane each, one kernel launch per
     round of pieces (include/nfc_amd.h: nfc_multi) -- what a loop of ``decoder(src=s).run()`` does capture by capture.
 
@@ -91,6 +91,9 @@ def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None,
     After every push the streams' outputs come to the host in ONE fetch (api.NfcMultiContext.fetch: the packets, and the symbols
     unless ``keep`` is 0) and are delivered from that host copy.  push_stats: a list that gets one ``(n_fetches, n_reads_device)``
     per push, read from the context's statistics after the push's delivery (one fetch and no read from the device are expected).
+    frames=True: after every push the streams' frames -- bytes, parity bits, parity and CRC_A verdicts, assembled on the GPU -- are
+    fetched once more (api.NfcMultiContext.fetch_frames) and every source's part is appended to its background's ``frames``, a list
+    with one api.NfcFrames per push that gave the source samples; the default leaves the backgrounds as they were.
     -> one ``background`` per source, in order: ``decode_many(srcs)[i].packets`` and its fsm's command trace are what
     ``decoder(src=srcs[i]).run()`` gives."""
     scales = {k: sink_kwargs.pop(k, 0.0) for k in ('wav_scale', 'iq16_scale', 'iq8_scale')}
@@ -104,6 +107,9 @@ def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None,
         raise ValueError('decode_many: the sources are of different input kinds %s: decode each kind in a call of its own' % kinds)
     backs = [background(reader, tag, None, fsm=fsm_factory() if fsm_factory else None, keep=keep, samp_rate=samp_rate,
                         max_len=sink.get('max_len', 50), device=device, attached=True) for _ in loaded]
+    if frames:
+        for b in backs:
+            b.frames = []
     if not loaded:
         return backs
     kind, scale = kinds[0], loaded[0][2]
@@ -129,6 +135,10 @@ def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None,
                     m.fetch(api.NFC_MULTI_FETCH_PACKETS | (api.NFC_MULTI_FETCH_SYMBOLS if keep != 0 else 0), copy=False)
                     for k in numpy.nonzero(n)[0]:
                         backs[g0 + int(k)].deliver(m.stream(int(k)))
+                    if frames:
+                        fr = m.fetch_frames()
+                        for k in numpy.nonzero(n)[0]:
+                            backs[g0 + int(k)].frames.append(fr.frames_of(int(k)))
                     if push_stats is not None:
                         st = m.stats()
                         push_stats.append((int(st.n_fetches), int(st.n_reads_device)))

@@ -128,6 +128,29 @@ class fsm(object):
             self._dispatch(f, data[o:o + int(f['n_bytes'])].tolist(), enc[o:o + int(f['n_enc'])])
         return frames, data[:used.value]
 
+    def process_frames(self, frames, data=None, par=None, dispatch=True):
+        """process_packets over frames assembled on the GPU (NfcContext.frames(), NfcMultiFrames.frames_of(k), api.host_frames):
+        `frames` an NfcFrames, or the merged RAW_FRAME_DTYPE table with data = (bytes0, bytes1) and par = (par0, par1).  Returns what
+        process_packets returns on the packets the frames came from, and leaves the machine in the same state."""
+        if data is None:
+            frames, data, par = frames.table, frames.bytes, frames.par
+        t = np.ascontiguousarray(frames, _lib.RAW_FRAME_DTYPE)
+        b = [np.ascontiguousarray(a, np.uint8) for a in data]
+        p = [np.ascontiguousarray(a, np.uint8) for a in par]
+        out = np.zeros(len(t), FRAME_DTYPE)
+        buf = np.zeros(int(t['n_bits'].sum()) // 9 + len(t) + 1, np.uint8)
+        enc = np.zeros(buf.size, np.uint16)
+        used = C.c_size_t(0)
+        ptr = lambda a: a.ctypes.data if a.size else None
+        rc = self.L.nfc_fsm_process_frames(self._h, ptr(t), len(t), ptr(b[0]), ptr(p[0]), ptr(b[1]), ptr(p[1]), out.ctypes.data,
+                                           buf.ctypes.data, buf.size, C.byref(used), enc.ctypes.data)
+        if rc != 0:
+            raise ValueError('nfc_fsm_process_frames status %d' % rc)
+        for f in (out if dispatch else ()):
+            o = int(f['byte_off'])
+            self._dispatch(f, buf[o:o + int(f['n_bytes'])].tolist(), enc[o:o + int(f['n_enc'])])
+        return out, buf[:used.value]
+
 
 def crc_a(data):
     """ISO 14443-3 type A CRC as [low, high] (utilities.CRC.calculate_crc, utilities.py:30-41)."""
