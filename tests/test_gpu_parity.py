@@ -1178,3 +1178,68 @@ def test_fused_tail_golden_fixture_in_long_batches(monkeypatch):
     c = Case('fx_ultralight_txn')
     check_case(c, run_gpu(c.x, c.params))
     check_case(c, run_gpu(c.x, c.params, pushes=[0, 2500, 9000, len(c.x)]))
+
+
+_EVERY_PARAMS = dict(hi_val=1.1, av_window=2560, max_len=50)
+_EVERY_RAW = {}      # kind -> the capture in the kind's raw format
+_EVERY_ORACLE = {}   # (kind, samples) -> (transitions, symbols 0, symbols 1, packets) of the C oracle
+
+
+def _every_kind_raw(kind):
+    """synth.workload('all', 600_000) carried into every input kind's raw format, once."""
+    if not _EVERY_RAW:
+        iq = synth.workload('all', 600_000)
+        root = np.sqrt(synth.envelope_f32(iq).astype(np.float64))
+        _EVERY_RAW.update({
+            api.NFC_IN_IQ_F32: iq, api.NFC_IN_ENV_F32: synth.envelope_f32(iq), api.NFC_IN_REAL_F32_SQ: root.astype(np.float32),
+            api.NFC_IN_I16_SQ: np.clip(np.round(root * 20000.0), -32768, 32767).astype(np.int16),
+            api.NFC_IN_IQ_I16: synth.quantise_sc16(iq), api.NFC_IN_IQ_I8: synth.quantise_sc8(iq), api.NFC_IN_IQ_U8: synth.quantise_cu8(iq)})
+    return _EVERY_RAW[kind]
+
+
+def _every_kind_oracle(kind, n):
+    if (kind, n) not in _EVERY_ORACLE:
+        o = co.COracle(trace=False, **_EVERY_PARAMS)
+        o.push_env(api.host_envelope(_every_kind_raw(kind)[:n * api._KIND_DTYPE[kind][1]], kind))
+        _EVERY_ORACLE[kind, n] = (o.transitions(), o.symbols(0).tolist(), o.symbols(1).tolist(), o.packets())
+    return _EVERY_ORACLE[kind, n]
+
+
+@pytest.mark.parametrize('kind', sorted(api._KIND_DTYPE))
+def test_every_kind_every_form(monkeypatch, kind):
+    # Every slot of an input kind's kernel table (csrc/kind_kernels.h) on one capture: the workgroup kernel with eight and four rows per
+    # step, the lean kernel, the general one with the ring in LDS and in global memory, the per-wave-counter form with four and eight
+    # rows, the sequential kernel; k_fill in all of them.  37 chunks of whole eight-row rounds in a batch of more than 2^18 samples (the
+    # multi-launch stages); the window holds an eight-row round and two steps of the global ring.  A kind without a slot (eight rows: the
+    # float32 real and int16 PCM kinds; the flag form: the complex integer kinds) ignores the switch and is as exact.  Expected: the C
+    # oracle on api.host_envelope of the same raw samples.
+    n = 600_000
+    per = api._KIND_DTYPE[kind][1]
+    raw = _every_kind_raw(kind)
+    want = _every_kind_oracle(kind, n)
+    assert len(want[3]) > 10 and len(want[0]) > 1000
+    # (the product library first -- the default and the sequential form --, then the switches, which bring the test build)
+    forms = [({}, 0), ({}, api.NFC_FLAG_FORCE_SEQUENTIAL), (dict(NFC_WG_NR='8'), 0), (dict(NFC_WG_NR='4'), 0), (dict(NFC_WG='0'), 0),
+             (dict(NFC_LEAN='0'), 0), (dict(NFC_RING='global'), 0), (dict(NFC_WG_FLAGS='1', NFC_WG_NR='4'), 0),
+             (dict(NFC_WG_FLAGS='1', NFC_WG_NR='8'), 0)]
+
+    def decode(x, flags):
+        with api.NfcContext(input_kind=kind, flags=flags, chunk_samples=16384, **_EVERY_PARAMS) as ctx:
+            ctx.push(x)
+            return (ctx.transitions(), ctx.symbols(0).tolist(), ctx.symbols(1).tolist(), ctx.packets()), ctx.stats()
+
+    for env, flags in forms:
+        for name, v in env.items():
+            monkeypatch.setenv(name, v)
+        got, st = decode(raw, flags)
+        for name in env:
+            monkeypatch.delenv(name)
+        d = first_diff(got[0], want[0])
+        assert d is None, 'transition %s (%s, flags %d)' % (d, env, flags)
+        assert got[1] == want[1] and got[2] == want[2] and got[3] == want[3], (env, flags)
+        assert st.used_sequential == (1 if flags else 0), (env, flags)
+    # ... and a batch of at most 2^18 samples into a fresh context: the single-launch stage behind the same table
+    short = _every_kind_oracle(kind, 200_000)
+    got, st = decode(raw[:200_000 * per], 0)
+    assert first_diff(got[0], short[0]) is None and got[1:] == short[1:]
+    assert st.used_sequential == 0

@@ -7,9 +7,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 SO = os.path.join(HERE, 'libnfc_amd.so')
 SO_HOOKS = os.path.join(HERE, 'libnfc_amd_hooks.so')   # the same sources with -DNFC_TEST_HOOKS: test hooks and diagnostics (README.md)
-SOURCES = ['nfc_amd.hip', 'nfc_iq16.hip', 'nfc_iq8.hip', 'nfc_record.hip', 'nfc_multi.hip', 'nfc_frames.hip']   # (the frame assembly kernels: frames.hip.h; the complex int16 and the complex 8-bit input kinds' kernels: csrc/iq16.h, iq8.h; the recording kernel: record.hip.h; the multi-stream context: multi.hip.h, multi_fetch.hip.h)
-DEPS = ['nfc_amd.hip', 'nfc_iq16.hip', 'iq16.h', 'nfc_iq8.hip', 'iq8.h', 'nfc_record.hip', 'record.hip.h', 'nfc_multi.hip', 'multi.hip.h', 'multi_fetch.hip.h', 'nfc_frames.hip', 'frames.hip.h', 'scale_arg.h', 'host_context.h', 'host_threshold.h', 'host_stages.h', 'host_submit.h', 'chunk_cut.h', 'launch_check.h', 'threshold.hip.h', 'threshold_lean.hip.h', 'threshold_wg.hip.h', 'edges.hip.h', 'decode.hip.h', 'scan.hip.h', 'small.hip.h', 'tail.hip.h', 'tx.hip.h', 'decoder_tables.h', 'protocol.h',
-        os.path.join('..', '..', 'include', 'nfc_amd.h')]
+SOURCES = ['nfc_amd.hip', 'nfc_iq16.hip', 'nfc_iq8.hip', 'nfc_record.hip', 'nfc_multi.hip', 'nfc_frames.hip']   # (the frame assembly kernels: frames.hip.h; the complex int16 and the complex 8-bit input kinds' kernels: csrc/kind_kernels.h; the recording kernel: record.hip.h; the multi-stream context: multi.hip.h, multi_fetch.hip.h)
+DEPS = sorted(f for f in os.listdir(CSRC) if f.endswith(('.h', '.hip'))) + [os.path.join('..', '..', 'include', 'nfc_amd.h')]
 
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared',
          '-ffp-contract=off', '-fno-fast-math',      # envelope and fp64 sums must round like the reference

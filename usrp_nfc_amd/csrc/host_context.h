@@ -100,6 +100,7 @@ constexpr int NSUB = 3;    // batches that may be submitted and not yet waited f
 
 struct nfc_ctx {
     nfc_params P;
+    const KindKernels *kk = nullptr;   // the threshold-stage kernels of P.input_kind (kind_kernels.h)
     int L, mx, C, Lpad, wpb, twords;
     double factor;
     double hi_plus, lo_a, lo_b, hi_a, hi_b;
@@ -378,43 +379,19 @@ int batch_ok(nfc_ctx *c, bool with_mirror) {
         if (int rc__ = batch_ok((c), (with_mirror))) return rc__;  \
     } while (0)
 
-// The threshold-stage kernels of an input kind.  The complex int16 kind's live in a translation unit of their own (nfc_iq16.hip),
-// and so do the complex 8-bit kinds' (nfc_iq8.hip): nfc_amd.hip reaches them by pointer (iq16.h, iq8.h) and instantiates none of them.
-constexpr bool is_iq8(int kind) { return kind == IN_IQ_I8 || kind == IN_IQ_U8; }
-template <int KIND, bool GRING>
-ThrKernel thr_kern() {
-    if constexpr (KIND == IN_IQ_I16) return iq16::threshold_kernel(GRING);
-    else if constexpr (is_iq8(KIND)) return iq8::threshold_kernel(KIND, GRING);
-    else return k_threshold<KIND, 4, GRING>;
-}
-template <int KIND, bool BLK16>
-ThrKernel lean_kern() {
-    if constexpr (KIND == IN_IQ_I16) return iq16::lean_kernel(BLK16);
-    else if constexpr (is_iq8(KIND)) return iq8::lean_kernel(KIND, BLK16);
-    else return k_threshold_lean<KIND, 4, BLK16>;
-}
-template <int KIND, int NR, bool EX = false>
-ThrKernel wg_kern() {
-    if constexpr (KIND == IN_IQ_I16) return EX ? iq16::wg_ex_kernel() : iq16::wg_kernel(NR);
-    else if constexpr (is_iq8(KIND)) return EX ? iq8::wg_ex_kernel(KIND) : iq8::wg_kernel(KIND, NR);
-    else return k_threshold_wg<KIND, NR, EX>;
-}
-
 // Timed launches (nfc_set_timing >= 1) hand the kernel its own start / stop events (hipExtLaunchKernelGGL): the
 // events take the kernel's begin and end, not the position of a marker in the stream, so they neither measure nor add
 // inter-launch gaps.
-template <int KIND>
 void launch_threshold(nfc_ctx *c, const ThrArgs &A, uint32_t nwork, hipEvent_t e0, hipEvent_t e1) {
     const uint32_t wpb = c->gring ? 4u : (uint32_t)c->wpb;
     const uint32_t blocks = (nwork + wpb - 1) / wpb;
     const size_t lds = c->gring ? 0 : (size_t)wpb * c->Lpad * c->lds_per_slot;
-    const ThrKernel kern = c->gring ? thr_kern<KIND, true>() : thr_kern<KIND, false>();
+    const ThrKernel kern = c->kk->thr[c->gring ? 1 : 0];
     if (e0) NFC_LAUNCH_EXT(kern, dim3(blocks), dim3(64 * wpb), lds, c->st, e0, e1, 0, A);
     else NFC_LAUNCH(kern, dim3(blocks), dim3(64 * wpb), lds, c->st, A);
 }
 // Pass 0 with the LDS ring: the lean optimistic kernel (threshold_lean.hip.h); chunks it gives up on are re-run by k_threshold.
 // ... or, where it applies, with a chunk per workgroup (threshold_wg.hip.h)
-template <int KIND>
 void launch_wg(nfc_ctx *c, const ThrArgs &A, uint32_t nwork, hipEvent_t e0, hipEvent_t e1) {
     // the staging of the plane words (threshold_wg.hip.h): the whole chunk's when this launch may and the LDS has room, else the ring
     ThrArgs B = A;
@@ -433,40 +410,23 @@ void launch_wg(nfc_ctx *c, const ThrArgs &A, uint32_t nwork, hipEvent_t e0, hipE
         lds = c->wg_ex_lds;
     }
     if (c->dbg_bad_launch) lds += (size_t)1 << 20;
-    auto go = [&](auto kern) {
-        if (e0) NFC_LAUNCH_EXT(kern, dim3(nwork), dim3(256), lds, c->st, e0, e1, 0, B);
-        else NFC_LAUNCH(kern, dim3(nwork), dim3(256), lds, c->st, B);
-    };
-    if (c->wg_ex_launch) return go(wg_kern<KIND, 4, true>());
-#ifdef NFC_TEST_HOOKS
-    if constexpr (KIND != IN_IQ_I16 && !is_iq8(KIND)) {   // (not instantiated for the complex integer kinds: nfc_create leaves wg_flags 0 for them)
-        if (c->wg_flags) {   // (NFC_WG_FLAGS=1: per-wave counters instead of a round's first barrier -- built and measured, threshold_wg.hip.h)
-            if constexpr (KIND == IN_IQ_F32 || KIND == IN_ENV_F32) {
-                if (c->wg_nr == 8) return go(k_threshold_wg<KIND, 8, false, true>);
-            }
-            return go(k_threshold_wg<KIND, 4, false, true>);
-        }
-    }
-#endif
-    if constexpr (KIND == IN_IQ_F32 || KIND == IN_ENV_F32 || KIND == IN_IQ_I16 || is_iq8(KIND)) {   // (the kinds eight rows per step are instantiated for: nfc_create chooses wg_nr)
-        if (c->wg_nr == 8) return go(wg_kern<KIND, 8>());
-    }
-    go(wg_kern<KIND, 4>());
+    // pass 0: eight rows per step where nfc_create chose them (a kind without that slot runs four)
+    ThrKernel kern = c->kk->wg[c->wg_nr == 8 && c->kk->wg[1] ? 1 : 0];
+    // (NFC_WG_FLAGS=1, test build: per-wave counters instead of a round's first barrier -- built and measured, threshold_wg.hip.h)
+    if (c->wg_flags) kern = c->kk->wg_flags[c->wg_nr == 8 && c->kk->wg_flags[1] ? 1 : 0];
+    if (c->wg_ex_launch) kern = c->kk->wg_ex;
+    if (e0) NFC_LAUNCH_EXT(kern, dim3(nwork), dim3(256), lds, c->st, e0, e1, 0, B);
+    else NFC_LAUNCH(kern, dim3(nwork), dim3(256), lds, c->st, B);
 }
-template <int KIND>
 void launch_lean(nfc_ctx *c, const ThrArgs &A, uint32_t nwork, hipEvent_t e0, hipEvent_t e1) {
-    if (c->wg_now) return launch_wg<KIND>(c, A, nwork, e0, e1);
+    if (c->wg_now) return launch_wg(c, A, nwork, e0, e1);
     const uint32_t wpb = (uint32_t)c->wpb;
     const uint32_t blocks = (nwork + wpb - 1) / wpb;
     // (NFC_DEBUG_BAD_LAUNCH: a dynamic-LDS request the runtime must reject -- the test of the launch checks)
     const size_t lds = (size_t)wpb * c->Lpad * c->lds_per_slot + (c->dbg_bad_launch ? (size_t)1 << 20 : 0);
-    auto go = [&](auto kern) {
-        if (e0) NFC_LAUNCH_EXT(kern, dim3(blocks), dim3(64 * wpb), lds, c->st, e0, e1, 0, A);
-        else NFC_LAUNCH(kern, dim3(blocks), dim3(64 * wpb), lds, c->st, A);
-    };
-    const bool b16 = (1 << c->nfold) == 16;
-    if (b16) go(lean_kern<KIND, true>());
-    else go(lean_kern<KIND, false>());
+    const ThrKernel kern = c->kk->lean[(1 << c->nfold) == 16 ? 1 : 0];
+    if (e0) NFC_LAUNCH_EXT(kern, dim3(blocks), dim3(64 * wpb), lds, c->st, e0, e1, 0, A);
+    else NFC_LAUNCH(kern, dim3(blocks), dim3(64 * wpb), lds, c->st, A);
 }
 void launch_threshold_kind(nfc_ctx *c, const ThrArgs &A, uint32_t nwork, bool lean = false, hipEvent_t *own_events = nullptr) {
     const bool timed = !own_events && c->timing >= 1 && c->n_kev < 6;
@@ -476,27 +436,8 @@ void launch_threshold_kind(nfc_ctx *c, const ThrArgs &A, uint32_t nwork, bool le
         e0 = own_events[0];
         e1 = own_events[1];
     }
-    if (lean) {
-        switch (c->P.input_kind) {
-        case NFC_IN_IQ_F32: launch_lean<IN_IQ_F32>(c, A, nwork, e0, e1); break;
-        case NFC_IN_ENV_F32: launch_lean<IN_ENV_F32>(c, A, nwork, e0, e1); break;
-        case NFC_IN_REAL_F32_SQ: launch_lean<IN_REAL_F32_SQ>(c, A, nwork, e0, e1); break;
-        case NFC_IN_IQ_I16: launch_lean<IN_IQ_I16>(c, A, nwork, e0, e1); break;
-        case NFC_IN_IQ_I8: launch_lean<IN_IQ_I8>(c, A, nwork, e0, e1); break;
-        case NFC_IN_IQ_U8: launch_lean<IN_IQ_U8>(c, A, nwork, e0, e1); break;
-        default: launch_lean<IN_I16_SQ>(c, A, nwork, e0, e1); break;
-        }
-        return;
-    }
-    switch (c->P.input_kind) {
-    case NFC_IN_IQ_F32: launch_threshold<IN_IQ_F32>(c, A, nwork, e0, e1); break;
-    case NFC_IN_ENV_F32: launch_threshold<IN_ENV_F32>(c, A, nwork, e0, e1); break;
-    case NFC_IN_REAL_F32_SQ: launch_threshold<IN_REAL_F32_SQ>(c, A, nwork, e0, e1); break;
-    case NFC_IN_IQ_I16: launch_threshold<IN_IQ_I16>(c, A, nwork, e0, e1); break;
-    case NFC_IN_IQ_I8: launch_threshold<IN_IQ_I8>(c, A, nwork, e0, e1); break;
-    case NFC_IN_IQ_U8: launch_threshold<IN_IQ_U8>(c, A, nwork, e0, e1); break;
-    default: launch_threshold<IN_I16_SQ>(c, A, nwork, e0, e1); break;
-    }
+    if (lean) launch_lean(c, A, nwork, e0, e1);
+    else launch_threshold(c, A, nwork, e0, e1);
 }
 void launch_fill_kind(nfc_ctx *c, const void *in, uint32_t n, int nchunks, int ring_idx = -1) {
     float *ring = c->d_ring[ring_idx < 0 ? c->ring_cur : ring_idx].as<float>();
@@ -524,51 +465,10 @@ void launch_fill_kind(nfc_ctx *c, const void *in, uint32_t n, int nchunks, int r
         // (a stream that starts here with a whole window in the batch: k_fill's short form)
         fresh = h.carry.stable == 0 && h.carry.filled == 0 && n >= (uint32_t)c->L && (void *)cr == c->d_state.p;
     }
-    switch (c->P.input_kind) {
-    case NFC_IN_IQ_F32: NFC_LAUNCH((k_fill<IN_IQ_F32>), dim3(1), dim3(FILL_BLOCK), (size_t)c->Lpad * 4, c->st, in, n, c->i16_scale, c->L, ring, cr, eci, ver, nchunks, sum, init, &((DevState *)c->d_state.p)->seq[0], c->batch_seq, fresh); break;
-    case NFC_IN_ENV_F32: NFC_LAUNCH((k_fill<IN_ENV_F32>), dim3(1), dim3(FILL_BLOCK), (size_t)c->Lpad * 4, c->st, in, n, c->i16_scale, c->L, ring, cr, eci, ver, nchunks, sum, init, &((DevState *)c->d_state.p)->seq[0], c->batch_seq, fresh); break;
-    case NFC_IN_REAL_F32_SQ: NFC_LAUNCH((k_fill<IN_REAL_F32_SQ>), dim3(1), dim3(FILL_BLOCK), (size_t)c->Lpad * 4, c->st, in, n, c->i16_scale, c->L, ring, cr, eci, ver, nchunks, sum, init, &((DevState *)c->d_state.p)->seq[0], c->batch_seq, fresh); break;
-    case NFC_IN_IQ_I16: {
-        const FillKernel kf = iq16::fill_kernel();
-        NFC_LAUNCH(kf, dim3(1), dim3(FILL_BLOCK), (size_t)c->Lpad * 4, c->st, in, n, c->i16_scale, c->L, ring, cr, eci, ver, nchunks, sum, init, &((DevState *)c->d_state.p)->seq[0], c->batch_seq, fresh);
-        break;
-    }
-    case NFC_IN_IQ_I8: {
-        const FillKernel kf = iq8::fill_kernel(IN_IQ_I8);
-        NFC_LAUNCH(kf, dim3(1), dim3(FILL_BLOCK), (size_t)c->Lpad * 4, c->st, in, n, c->i16_scale, c->L, ring, cr, eci, ver, nchunks, sum, init, &((DevState *)c->d_state.p)->seq[0], c->batch_seq, fresh);
-        break;
-    }
-    case NFC_IN_IQ_U8: {
-        const FillKernel kf = iq8::fill_kernel(IN_IQ_U8);
-        NFC_LAUNCH(kf, dim3(1), dim3(FILL_BLOCK), (size_t)c->Lpad * 4, c->st, in, n, c->i16_scale, c->L, ring, cr, eci, ver, nchunks, sum, init, &((DevState *)c->d_state.p)->seq[0], c->batch_seq, fresh);
-        break;
-    }
-    default: NFC_LAUNCH((k_fill<IN_I16_SQ>), dim3(1), dim3(FILL_BLOCK), (size_t)c->Lpad * 4, c->st, in, n, c->i16_scale, c->L, ring, cr, eci, ver, nchunks, sum, init, &((DevState *)c->d_state.p)->seq[0], c->batch_seq, fresh); break;
-    }
+    NFC_LAUNCH(c->kk->fill, dim3(1), dim3(FILL_BLOCK), (size_t)c->Lpad * 4, c->st, in, n, c->i16_scale, c->L, ring, cr, eci, ver, nchunks, sum, init,
+               &((DevState *)c->d_state.p)->seq[0], c->batch_seq, fresh);
 }
-void launch_seq_kind(nfc_ctx *c, const SeqArgs &A) {
-    switch (c->P.input_kind) {
-    case NFC_IN_IQ_F32: NFC_LAUNCH((k_threshold_seq<IN_IQ_F32>), dim3(1), dim3(64), 0, c->st, A); break;
-    case NFC_IN_ENV_F32: NFC_LAUNCH((k_threshold_seq<IN_ENV_F32>), dim3(1), dim3(64), 0, c->st, A); break;
-    case NFC_IN_REAL_F32_SQ: NFC_LAUNCH((k_threshold_seq<IN_REAL_F32_SQ>), dim3(1), dim3(64), 0, c->st, A); break;
-    case NFC_IN_IQ_I16: {
-        const SeqKernel ks = iq16::seq_kernel();
-        NFC_LAUNCH(ks, dim3(1), dim3(64), 0, c->st, A);
-        break;
-    }
-    case NFC_IN_IQ_I8: {
-        const SeqKernel ks = iq8::seq_kernel(IN_IQ_I8);
-        NFC_LAUNCH(ks, dim3(1), dim3(64), 0, c->st, A);
-        break;
-    }
-    case NFC_IN_IQ_U8: {
-        const SeqKernel ks = iq8::seq_kernel(IN_IQ_U8);
-        NFC_LAUNCH(ks, dim3(1), dim3(64), 0, c->st, A);
-        break;
-    }
-    default: NFC_LAUNCH((k_threshold_seq<IN_I16_SQ>), dim3(1), dim3(64), 0, c->st, A); break;
-    }
-}
+void launch_seq_kind(nfc_ctx *c, const SeqArgs &A) { NFC_LAUNCH(c->kk->seq, dim3(1), dim3(64), 0, c->st, A); }
 
 int ceil_log2(int v) {
     int b = 0;

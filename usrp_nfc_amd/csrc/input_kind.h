@@ -1,11 +1,43 @@
-// scale_arg.h -- the kernels' conversion argument for an input kind and the caller's i16_scale, on the host: shared by the
-// translation units that create contexts (nfc_amd.hip: nfc_create, nfc_record_pcm16_device; nfc_multi.hip: nfc_multi_create).
+// input_kind.h -- what is a property of an input kind and not of a kernel, on the host: how many kinds there are, a sample's bytes,
+// the kernels' conversion argument for the caller's i16_scale, and with_kind -- the one switch over the kinds in csrc/.  Shared by the
+// translation units that create contexts or pick a kind's kernel (nfc_amd.hip, nfc_multi.hip, nfc_record.hip; kind_kernels.h).
+// Included after threshold.hip.h, whose IN_* the kernels are instantiated with.
 #pragma once
 #include <cmath>
+#include <cstddef>
+#include <type_traits>
+#include <utility>
 
 #include "../../include/nfc_amd.h"
 
 namespace nfc {
+
+constexpr int N_KINDS = 7;
+static_assert(IN_IQ_F32 == NFC_IN_IQ_F32 && IN_ENV_F32 == NFC_IN_ENV_F32 && IN_REAL_F32_SQ == NFC_IN_REAL_F32_SQ && IN_I16_SQ == NFC_IN_I16_SQ &&
+                  IN_IQ_I16 == NFC_IN_IQ_I16 && IN_IQ_I8 == NFC_IN_IQ_I8 && IN_IQ_U8 == NFC_IN_IQ_U8 && IN_IQ_U8 == N_KINDS - 1,
+              "the kernels' kinds are the header's, 0 .. N_KINDS - 1");
+
+constexpr bool kind_valid(int kind) { return kind >= 0 && kind < N_KINDS; }
+constexpr bool is_iq8(int kind) { return kind == IN_IQ_I8 || kind == IN_IQ_U8; }
+// input bytes per sample (kind_valid(kind))
+inline size_t kind_bytes(int kind) {
+    static const size_t bps[N_KINDS] = {8, 4, 4, 2, 4, 2, 2};
+    return bps[kind];
+}
+
+// f(std::integral_constant<int, KIND>{}) for the kind: where a kind chosen at run time picks a template's instantiation.
+template <class F>
+decltype(auto) with_kind(int kind, F &&f) {
+    switch (kind) {
+    case IN_IQ_F32: return std::forward<F>(f)(std::integral_constant<int, IN_IQ_F32>{});
+    case IN_ENV_F32: return std::forward<F>(f)(std::integral_constant<int, IN_ENV_F32>{});
+    case IN_REAL_F32_SQ: return std::forward<F>(f)(std::integral_constant<int, IN_REAL_F32_SQ>{});
+    case IN_IQ_I16: return std::forward<F>(f)(std::integral_constant<int, IN_IQ_I16>{});
+    case IN_IQ_I8: return std::forward<F>(f)(std::integral_constant<int, IN_IQ_I8>{});
+    case IN_IQ_U8: return std::forward<F>(f)(std::integral_constant<int, IN_IQ_U8>{});
+    default: return std::forward<F>(f)(std::integral_constant<int, IN_I16_SQ>{});
+    }
+}
 
 // The complex 8-bit kinds' kernel argument (threshold.hip.h: iq8_env).  scale: i16_scale, 2^-7 where it is not positive.  A power of
 // two 2^k takes the integer route, -2^(2k), where every nonzero value of the definition is a normal float: the smallest nonzero square

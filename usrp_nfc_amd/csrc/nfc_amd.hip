@@ -50,12 +50,10 @@
 #endif
 #include "threshold_lean.hip.h"
 #include "threshold_wg.hip.h"
-#include "iq16.h"   // (the complex int16 kind's kernels: nfc_iq16.hip)
-#include "iq8.h"    // (the complex 8-bit kinds' kernels: nfc_iq8.hip)
+#include "kind_kernels.h"   // (every kind's threshold-stage kernels; the complex integer kinds': nfc_iq16.hip, nfc_iq8.hip)
 #include "tx.hip.h"
 #include "record.hip.h"   // (the recording kernel: nfc_record.hip)
 #include "frames.hip.h"   // (the frame assembly kernels: nfc_frames.hip)
-#include "scale_arg.h"
 
 using namespace nfc;
 
@@ -69,44 +67,19 @@ using namespace nfc;
 // C-ABI
 // ===========================================================================
 namespace {
-// the instantiation of k_threshold_wg a context launches (for the occupancy query and the LDS attribute)
-const void *wg_ex_kernel_of(int kind) {
-    switch (kind) {
-    case NFC_IN_IQ_F32: return (const void *)k_threshold_wg<IN_IQ_F32, 4, true>;
-    case NFC_IN_ENV_F32: return (const void *)k_threshold_wg<IN_ENV_F32, 4, true>;
-    case NFC_IN_REAL_F32_SQ: return (const void *)k_threshold_wg<IN_REAL_F32_SQ, 4, true>;
-    case NFC_IN_IQ_I16: return (const void *)iq16::wg_ex_kernel();
-    case NFC_IN_IQ_I8: return (const void *)iq8::wg_ex_kernel(IN_IQ_I8);
-    case NFC_IN_IQ_U8: return (const void *)iq8::wg_ex_kernel(IN_IQ_U8);
-    default: return (const void *)k_threshold_wg<IN_I16_SQ, 4, true>;
-    }
-}
-#ifdef NFC_TEST_HOOKS
-const void *wg_flags_kernel_of(int kind, int nr) {
-    switch (kind) {
-    case NFC_IN_IQ_F32: return nr == 8 ? (const void *)k_threshold_wg<IN_IQ_F32, 8, false, true> : (const void *)k_threshold_wg<IN_IQ_F32, 4, false, true>;
-    case NFC_IN_ENV_F32: return nr == 8 ? (const void *)k_threshold_wg<IN_ENV_F32, 8, false, true> : (const void *)k_threshold_wg<IN_ENV_F32, 4, false, true>;
-    case NFC_IN_REAL_F32_SQ: return (const void *)k_threshold_wg<IN_REAL_F32_SQ, 4, false, true>;
-    case NFC_IN_IQ_I16: return nullptr;   // (no such form of the complex int16 kind: nfc_create never asks for it, see wg_flags)
-    case NFC_IN_IQ_I8:
-    case NFC_IN_IQ_U8: return nullptr;    // (nor of the complex 8-bit kinds)
-    default: return (const void *)k_threshold_wg<IN_I16_SQ, 4, false, true>;
-    }
-}
-#endif
-const void *wg_kernel_of(int kind, int nr) {
-    // (six instantiations for pass 0: four rows per step for every input kind, eight for the two kinds a long-window capture arrives in;
-    // wg_ex_kernel_of above: the four that re-run chunks with failed rounds evaluated in place.  The complex int16 kind's three --
-    // four and eight rows, the re-run form -- are nfc_iq16.hip's, the complex 8-bit kinds' three each nfc_iq8.hip's)
-    switch (kind) {
-    case NFC_IN_IQ_F32: return nr == 8 ? (const void *)k_threshold_wg<IN_IQ_F32, 8> : (const void *)k_threshold_wg<IN_IQ_F32, 4>;
-    case NFC_IN_ENV_F32: return nr == 8 ? (const void *)k_threshold_wg<IN_ENV_F32, 8> : (const void *)k_threshold_wg<IN_ENV_F32, 4>;
-    case NFC_IN_REAL_F32_SQ: return (const void *)k_threshold_wg<IN_REAL_F32_SQ, 4>;
-    case NFC_IN_IQ_I16: return (const void *)iq16::wg_kernel(nr);
-    case NFC_IN_IQ_I8: return (const void *)iq8::wg_kernel(IN_IQ_I8, nr);
-    case NFC_IN_IQ_U8: return (const void *)iq8::wg_kernel(IN_IQ_U8, nr);
-    default: return (const void *)k_threshold_wg<IN_I16_SQ, 4>;
-    }
+// The kernel table of an input kind (kind_kernels.h): the one place that knows which translation unit a kind's instantiations live in.
+// This unit's: per kind, two each of k_threshold and k_threshold_lean, k_threshold_wg with four rows per step, with eight for the two
+// kinds a long-window capture arrives in, and its re-run form, k_fill, k_threshold_seq.
+const KindKernels &kind_kernels(int kind) {
+    return with_kind(kind, [](auto K) -> const KindKernels & {
+        constexpr int KIND = decltype(K)::value;
+        if constexpr (KIND == IN_IQ_I16) return iq16::kernels();
+        else if constexpr (is_iq8(KIND)) return iq8::kernels(KIND);
+        else {
+            static const KindKernels k = make_kind_kernels<KIND>();
+            return k;
+        }
+    });
 }
 }  // namespace
 
@@ -140,7 +113,7 @@ int nfc_create(const nfc_params *p, nfc_ctx **out) {
     if (!(p->samp_rate > 0)) return fail(nullptr, NFC_ERR_ARG, "samp_rate must be positive");
     if (p->av_window < 1 || p->av_window > 30000) return fail(nullptr, NFC_ERR_ARG, "av_window must be in [1, 30000]");
     if (p->max_len < 1 || p->max_len > 4000) return fail(nullptr, NFC_ERR_ARG, "max_len must be in [1, 4000]");
-    if (p->input_kind < 0 || p->input_kind > 6) return fail(nullptr, NFC_ERR_ARG, "unknown input_kind");
+    if (!kind_valid(p->input_kind)) return fail(nullptr, NFC_ERR_ARG, "unknown input_kind");
     float scale_arg = 0.f;
     if (const char *bad = kernel_scale_arg(p->input_kind, p->i16_scale, &scale_arg)) return fail(nullptr, NFC_ERR_ARG, "%s", bad);
     int ndev = 0;
@@ -151,6 +124,7 @@ int nfc_create(const nfc_params *p, nfc_ctx **out) {
 
     nfc_ctx *c = new nfc_ctx();
     c->P = *p;
+    c->kk = &kind_kernels(p->input_kind);
     c->L = p->av_window;
     c->mx = p->max_len;
     c->factor = 1e6 / p->samp_rate;
@@ -250,8 +224,7 @@ int nfc_create(const nfc_params *p, nfc_ctx **out) {
     c->eps = 0.01f;  // certification margin of the speculative pass, relative to the window sum
     if (const char *e = NFC_ENV("NFC_EPS")) c->eps = (float)atof(e);
     c->i16_scale = scale_arg;   // (kernel_scale_arg)
-    static const size_t bps[7] = {8, 4, 4, 2, 4, 2, 2};
-    c->in_bytes_per_sample = bps[p->input_kind];
+    c->in_bytes_per_sample = kind_bytes(p->input_kind);
     memset(&c->h_carry, 0, sizeof c->h_carry);
     c->h_carry.ss_emin = 255;
     c->h_ecarry = EdgeCarry{0, 0, 1, 0};  // transition_sink.py:22-23,30
@@ -296,9 +269,8 @@ int nfc_create(const nfc_params *p, nfc_ctx **out) {
         // rows per step: eight where that leaves a superstep of at least two rounds within 0.8 windows (measured: at av_window 10000
         // eight rows gain 2 % over four; at 2000 more rows with one-round supersteps lose to four rows with two), else four; a round
         // (four steps) must fit the window, max_len must lie within one step.  Eight rows are instantiated for fc32, sc16, sc8 and cu8 IQ
-        // and the float32 envelope -- what a capture at a rate that wants such a window arrives as.
-        const bool nr8_kind = p->input_kind == NFC_IN_IQ_F32 || p->input_kind == NFC_IN_ENV_F32 || p->input_kind == NFC_IN_IQ_I16 ||
-                              p->input_kind == NFC_IN_IQ_I8 || p->input_kind == NFC_IN_IQ_U8;
+        // and the float32 envelope -- what a capture at a rate that wants such a window arrives as (kind_kernels.h: has_nr8).
+        const bool nr8_kind = c->kk->wg[1] != nullptr;
         c->wg_nr = (nr8_kind && 0.8 * c->L / (double)wg_round_samples(8) >= 1.5) ? 8 : 4;
         if (const char *e = NFC_ENV("NFC_WG_NR")) {
             const int v = atoi(e);
@@ -308,11 +280,11 @@ int nfc_create(const nfc_params *p, nfc_ctx **out) {
         c->wg_lds = c->wg_lds_base + wg_stage_bytes(c->wg_nr, 2 * wg_flush_rounds(c->wg_nr));
         c->wg_ok = c->mx <= 64 * c->wg_nr - 2 && c->L >= wg_round_samples(c->wg_nr) && c->wg_lds <= 160 * 1024;
         if (c->wg_ok) {
-            const void *kern = wg_kernel_of(p->input_kind, c->wg_nr);
+            const void *kern = (const void *)c->kk->wg[c->wg_nr == 8 ? 1 : 0];
 #ifdef NFC_TEST_HOOKS
-            if (const char *e = getenv("NFC_WG_FLAGS"))   // (no such form of the complex integer kinds)
-                c->wg_flags = atoi(e) != 0 && p->input_kind != NFC_IN_IQ_I16 && p->input_kind != NFC_IN_IQ_I8 && p->input_kind != NFC_IN_IQ_U8;
-            if (c->wg_flags) kern = wg_flags_kernel_of(p->input_kind, c->wg_nr);
+            if (const char *e = getenv("NFC_WG_FLAGS"))   // (ignored for a kind without that form: the complex integer kinds)
+                c->wg_flags = atoi(e) != 0 && c->kk->wg_flags[0] != nullptr;
+            if (c->wg_flags) kern = (const void *)c->kk->wg_flags[c->wg_nr == 8 && c->kk->wg_flags[1] ? 1 : 0];
             if (!kern) {
                 nfc_destroy(c);
                 return fail(nullptr, NFC_ERR_INTERNAL, "no workgroup kernel for input kind %d", p->input_kind);
@@ -359,7 +331,7 @@ int nfc_create(const nfc_params *p, nfc_ctx **out) {
             c->wg_ex_lds = c->wg_lds_base + wg_stage_bytes(4, 2 * wg_flush_rounds(4));
             c->wg_ex_ok = c->wg_ok && c->mx <= 64 * 4 - 2 && c->L >= wg_round_samples(4) && c->wg_ex_lds <= 160 * 1024;
             if (c->wg_ex_ok) {
-                const void *kx = wg_ex_kernel_of(p->input_kind);
+                const void *kx = (const void *)c->kk->wg_ex;
                 if (c->wg_ex_lds > 64 * 1024) CRT(hipFuncSetAttribute(kx, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->wg_ex_lds));
                 int fit = 0;
                 CRT(hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, kx, 256, c->wg_ex_lds));
@@ -398,26 +370,9 @@ int nfc_create(const nfc_params *p, nfc_ctx **out) {
         return fail(nullptr, NFC_ERR_ARG, "av_window too large for one wave's LDS ring");
     }
     if (lds > 64 * 1024) {
-        CRT(hipFuncSetAttribute((const void *)k_threshold<IN_IQ_F32, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        CRT(hipFuncSetAttribute((const void *)k_threshold<IN_ENV_F32, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        CRT(hipFuncSetAttribute((const void *)k_threshold<IN_REAL_F32_SQ, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        CRT(hipFuncSetAttribute((const void *)k_threshold<IN_I16_SQ, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        CRT(hipFuncSetAttribute((const void *)k_threshold_lean<IN_IQ_F32, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        CRT(hipFuncSetAttribute((const void *)k_threshold_lean<IN_IQ_F32, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        CRT(hipFuncSetAttribute((const void *)k_threshold_lean<IN_ENV_F32, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        CRT(hipFuncSetAttribute((const void *)k_threshold_lean<IN_ENV_F32, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        CRT(hipFuncSetAttribute((const void *)k_threshold_lean<IN_REAL_F32_SQ, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        CRT(hipFuncSetAttribute((const void *)k_threshold_lean<IN_REAL_F32_SQ, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        CRT(hipFuncSetAttribute((const void *)k_threshold_lean<IN_I16_SQ, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        CRT(hipFuncSetAttribute((const void *)k_threshold_lean<IN_I16_SQ, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        CRT(hipFuncSetAttribute((const void *)iq16::threshold_kernel(false), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        CRT(hipFuncSetAttribute((const void *)iq16::lean_kernel(true), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        CRT(hipFuncSetAttribute((const void *)iq16::lean_kernel(false), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        for (int k : {IN_IQ_I8, IN_IQ_U8}) {
-            CRT(hipFuncSetAttribute((const void *)iq8::threshold_kernel(k, false), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            CRT(hipFuncSetAttribute((const void *)iq8::lean_kernel(k, true), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            CRT(hipFuncSetAttribute((const void *)iq8::lean_kernel(k, false), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        }
+        for (int kind = 0; kind < N_KINDS; kind++)   // (every kind's, not only this context's)
+            for (const ThrKernel kern : {kind_kernels(kind).thr[0], kind_kernels(kind).lean[0], kind_kernels(kind).lean[1]})
+                CRT(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     }
     // decoder LUTs
     DecoderTables t = build_tables(p->samp_rate, c->mx);
@@ -1475,7 +1430,7 @@ int nfc_record_pcm16_device(int device, int tap, int input_kind, float i16_scale
                             void *dev_pcm_out, void *stream, float *kernel_ms) {
     // (every argument check comes before anything touches the device)
     if (tap != NFC_REC_ENVELOPE && tap != NFC_REC_REAL_PART) return fail(nullptr, NFC_ERR_ARG, "nfc_record_pcm16_device: unknown tap %d", tap);
-    if (input_kind < 0 || input_kind > 6) return fail(nullptr, NFC_ERR_ARG, "nfc_record_pcm16_device: unknown input_kind");
+    if (!kind_valid(input_kind)) return fail(nullptr, NFC_ERR_ARG, "nfc_record_pcm16_device: unknown input_kind");
     if (tap == NFC_REC_REAL_PART && input_kind != NFC_IN_IQ_F32)
         return fail(nullptr, NFC_ERR_ARG, "nfc_record_pcm16_device: the real-part tap takes complex float32 input (NFC_IN_IQ_F32) only");
     if (!(gain > 0.f) || !std::isfinite(gain)) return fail(nullptr, NFC_ERR_ARG, "nfc_record_pcm16_device: gain must be finite and positive");

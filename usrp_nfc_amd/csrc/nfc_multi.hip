@@ -24,7 +24,7 @@
 #include "multi.hip.h"
 #include "multi_fetch.hip.h"
 #include "frames.hip.h"   // (the frame assembly kernels: nfc_frames.hip)
-#include "scale_arg.h"
+#include "input_kind.h"
 
 using namespace nfc;
 using namespace nfc::multi;
@@ -105,15 +105,7 @@ int mfail(nfc_multi *m, int code, const char *fmt, ...) {
 
 using MultiKernel = void (*)(Args);
 MultiKernel kernel_of(int kind) {
-    switch (kind) {
-    case NFC_IN_IQ_F32: return k_multi<IN_IQ_F32>;
-    case NFC_IN_ENV_F32: return k_multi<IN_ENV_F32>;
-    case NFC_IN_REAL_F32_SQ: return k_multi<IN_REAL_F32_SQ>;
-    case NFC_IN_IQ_I16: return k_multi<IN_IQ_I16>;
-    case NFC_IN_IQ_I8: return k_multi<IN_IQ_I8>;
-    case NFC_IN_IQ_U8: return k_multi<IN_IQ_U8>;
-    default: return k_multi<IN_I16_SQ>;
-    }
+    return with_kind(kind, [](auto K) -> MultiKernel { return k_multi<decltype(K)::value>; });
 }
 
 int launch_ok(nfc_multi *m) {
@@ -305,7 +297,7 @@ int nfc_multi_create(const nfc_params *p, const nfc_multi_config *c, nfc_multi *
     if (!(p->samp_rate > 0)) return mfail(nullptr, NFC_ERR_ARG, "samp_rate must be positive");
     if (p->av_window < 1 || p->av_window > 30000) return mfail(nullptr, NFC_ERR_ARG, "av_window must be in [1, 30000]");
     if (p->max_len < 1 || p->max_len > 4000) return mfail(nullptr, NFC_ERR_ARG, "max_len must be in [1, 4000]");
-    if (p->input_kind < 0 || p->input_kind > 6) return mfail(nullptr, NFC_ERR_ARG, "unknown input_kind");
+    if (!kind_valid(p->input_kind)) return mfail(nullptr, NFC_ERR_ARG, "unknown input_kind");
     if (p->flags != 0) return mfail(nullptr, NFC_ERR_ARG, "nfc_params.flags must be 0 for a multi-stream context");
     if (p->chunk_samples != 0) return mfail(nullptr, NFC_ERR_ARG, "nfc_params.chunk_samples must be 0 for a multi-stream context");
     if (c->n_streams < 1 || c->n_streams > 65536) return mfail(nullptr, NFC_ERR_ARG, "n_streams must be in [1, 65536]");
@@ -336,8 +328,7 @@ int nfc_multi_create(const nfc_params *p, const nfc_multi_config *c, nfc_multi *
     m->mx = p->max_len;
     m->nd = m->mx + 1;
     m->scale = scale_arg;
-    static const size_t bps[7] = {8, 4, 4, 2, 4, 2, 2};
-    m->bps = bps[p->input_kind];
+    m->bps = kind_bytes(p->input_kind);
     memset(&m->stats, 0, sizeof m->stats);
     memset(&m->fout, 0, sizeof m->fout);
     memset(&m->flay, 0, sizeof m->flay);

@@ -20,6 +20,7 @@
 #include "launch_check.h"
 #include "threshold.hip.h"
 #include "record.hip.h"
+#include "input_kind.h"
 
 namespace nfc {
 namespace rec {
@@ -67,15 +68,7 @@ using RecKernel = void (*)(const void *, uint64_t, float, float, int16_t *);
 template <bool NT>
 RecKernel kernel_of(int kind, int tap) {
     if (tap == TAP_REAL_PART) return k_record_pcm16<IN_IQ_F32, TAP_REAL_PART, NT>;
-    switch (kind) {
-    case IN_IQ_F32: return k_record_pcm16<IN_IQ_F32, TAP_ENVELOPE, NT>;
-    case IN_ENV_F32: return k_record_pcm16<IN_ENV_F32, TAP_ENVELOPE, NT>;
-    case IN_REAL_F32_SQ: return k_record_pcm16<IN_REAL_F32_SQ, TAP_ENVELOPE, NT>;
-    case IN_IQ_I16: return k_record_pcm16<IN_IQ_I16, TAP_ENVELOPE, NT>;
-    case IN_IQ_I8: return k_record_pcm16<IN_IQ_I8, TAP_ENVELOPE, NT>;
-    case IN_IQ_U8: return k_record_pcm16<IN_IQ_U8, TAP_ENVELOPE, NT>;
-    default: return k_record_pcm16<IN_I16_SQ, TAP_ENVELOPE, NT>;
-    }
+    return with_kind(kind, [](auto K) -> RecKernel { return k_record_pcm16<decltype(K)::value, TAP_ENVELOPE, NT>; });
 }
 
 void launch(int kind, int tap, const void *in, size_t n, float arg, float gain, void *out, int cus, bool nontemporal, hipStream_t stream,

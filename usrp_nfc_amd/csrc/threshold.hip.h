@@ -352,29 +352,8 @@ __device__ __forceinline__ void iq8_env_step(const float (&w)[N], float (&x)[N],
 }
 
 // Envelope of one sample (gnuradio complex_to_mag_squared; compiled with
-// -ffp-contract=off so the products and the sum round separately).
-template <int KIND>
-__device__ __forceinline__ float envelope_at(const void *in, size_t m, float i16_scale) {
-    if (KIND == IN_IQ_F32) {
-        const float2 v = ((const float2 *)in)[m];
-        const float a = v.x * v.x, b = v.y * v.y;
-        return a + b;
-    } else if (KIND == IN_ENV_F32) {
-        return ((const float *)in)[m];
-    } else if (KIND == IN_REAL_F32_SQ) {
-        const float s = ((const float *)in)[m];
-        return s * s;
-    } else if (KIND == IN_IQ_I16) {
-        return iq16_env(((const uint32_t *)in)[m], i16_scale);
-    } else if constexpr (KIND == IN_IQ_I8 || KIND == IN_IQ_U8) {
-        return iq8_env<KIND>(((const uint16_t *)in)[m], i16_scale);
-    } else {
-        const float s = i16_to_float((int)((const int16_t *)in)[m], i16_scale);
-        return s * s;
-    }
-}
-
-// The same in two halves, so that a load can stay in flight across loop iterations: the raw sample
+// -ffp-contract=off so the products and the sum round separately), in two halves, so that a load can stay in flight across loop
+// iterations: the raw sample
 // is fetched steps ahead and only turned into the envelope when its step begins.
 template <int KIND> struct RawOf { using T = float; };
 template <> struct RawOf<IN_IQ_F32> { using T = float2; };
@@ -402,6 +381,23 @@ __device__ __forceinline__ float env_of(typename RawOf<KIND>::T v, float i16_sca
     } else {
         const float s = i16_to_float((int)v, i16_scale);
         return s * s;
+    }
+}
+template <int KIND>
+__device__ __forceinline__ float envelope_at(const void *in, size_t m, float i16_scale) {
+    return env_of<KIND>(load_raw<KIND>(in, m), i16_scale);
+}
+// ... of a one-dword kind's sample as the lean and the workgroup kernel hold it, the load's register as a float: the int16 sign-extended
+// by global_load_sshort, sc16's pair one dword (I low, Q high), the float32 kinds' value itself
+template <int KIND>
+__device__ __forceinline__ float env_of_word(float w, float i16_scale) {
+    if constexpr (KIND == IN_I16_SQ) {
+        const float sv = i16_to_float(__float_as_int(w), i16_scale);
+        return sv * sv;
+    } else if constexpr (KIND == IN_IQ_I16) {
+        return iq16_env(__float_as_uint(w), i16_scale);
+    } else {
+        return env_of<KIND>(w, i16_scale);   // IN_ENV_F32 (what transition_sink.work receives, transition_sink.py:13-18), IN_REAL_F32_SQ
     }
 }
 template <int KIND>

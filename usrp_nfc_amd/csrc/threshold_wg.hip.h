@@ -177,18 +177,7 @@ __device__ __forceinline__ void wg_take(float (&x)[NR], float i16_scale) {
             return;
         }
 #pragma unroll
-        for (int j = 0; j < NR; j++) {
-            if constexpr (KIND == IN_I16_SQ) {
-                const float sv = i16_to_float(__float_as_int(w[j]), i16_scale);   // (global_load_sshort sign-extends into the register)
-                x[j] = sv * sv;
-            } else if constexpr (KIND == IN_IQ_I16) {
-                x[j] = iq16_env(__float_as_uint(w[j]), i16_scale);   // (one dword: I low, Q high -- the loads of the 4-byte kinds)
-            } else if constexpr (KIND == IN_ENV_F32) {
-                x[j] = w[j];          // the envelope itself (what transition_sink.work receives, transition_sink.py:13-18)
-            } else {
-                x[j] = w[j] * w[j];   // IN_REAL_F32_SQ
-            }
-        }
+        for (int j = 0; j < NR; j++) x[j] = env_of_word<KIND>(w[j], i16_scale);
     }
 }
 // the dwords of NR masks into lanes LANE0 .. LANE0 + 2 NR - 1 of pk
