@@ -38,6 +38,9 @@ extern "C" {
  *  of nfc_multi_stats are now n_fetches and n_reads_device, its size unchanged) */
 /* (still 4, only new names: nfc_raw_frame, NFC_RAW_*, nfc_get_frame_counts, nfc_read_frames, nfc_read_frame_bytes, nfc_multi_frames,
  *  nfc_multi_fetch_frames, nfc_host_frames, nfc_fsm_process_frames) */
+/* (still 4, only new names: nfc_fsm_state, NFC_FSM_*, NFC_CMD_CUT, nfc_fsm_state_init, nfc_fsm_get_state, nfc_fsm_set_state, nfc_host_commands,
+ *  nfc_multi_commands, nfc_multi_track_commands, nfc_multi_fetch_commands, nfc_multi_set_keys, nfc_multi_get_fsm_state,
+ *  nfc_multi_set_fsm_state) */
 #define NFC_AMD_ABI_VERSION 4
 
 typedef enum {
@@ -484,7 +487,8 @@ int nfc_multi_fetch(nfc_multi *m, uint32_t what, nfc_multi_fetched *out /* may b
  * bits to a byte plus the odd-parity check (fsm.py:28-47) and the ISO 14443-3 CRC_A (utilities.py:30-41).  Two kernel launches
  * (csrc/frames.hip.h, nfc_frames.hip): a scan over the packet closes gives every frame its place, then a lane per frame reads its
  * nine-bit fields from the bit array the decode stage left (packed 32 to a word, or a byte per bit) and writes the record, the bytes
- * and the parity bits.  What stays on the host is the sequential protocol machine: nfc_fsm_process_frames.
+ * and the parity bits.  What stays on the host is the sequential protocol machine: nfc_fsm_process_frames (for the many streams of an
+ * nfc_multi it runs on the GPU too, a lane per stream: nfc_multi_fetch_commands below).
  * REPAIR, with rem = n_bits % 9 and start_bit = (type == 0 ? 1 : 0):
  *   rem 0: nothing;  rem 8: the last byte's parity bit is start_bit;  rem 1: the last bit is dropped, NFC_FRAME_EXTRA_ERROR iff it
  *   differs from start_bit;  rem 2..7: rem bits are dropped, NFC_FRAME_MANY_MORE_ERROR.
@@ -546,6 +550,93 @@ typedef struct {
     uint64_t reserved[4];
 } nfc_multi_frames;
 int nfc_multi_fetch_frames(nfc_multi *m, nfc_multi_frames *out);
+
+/* ---- commands on the GPU: the protocol machine, CRYPTO1 included, a lane per stream -----------------------------------------------
+ * What nfc_fsm_process_frames does on the host -- command lookup by protocol stage and leading bytes, tag type and UID tracking, the
+ * CRYPTO1 sessions of MIFARE Classic with nested authentications -- is sequential in ONE stream and independent across streams.  With
+ * tracking on, every push of a multi-stream context assembles the frames (the two launches of nfc_multi_fetch_frames, into a buffer of
+ * the tracking's own) and runs k_multi_commands behind them (csrc/multi_commands.hip.h): a lane per stream merges the stream's two frame
+ * lists by idx (type 0 first on a tie), runs every frame through csrc/fsm.hip.h -- a restatement of csrc/protocol.h without vectors,
+ * pinned to it by the CPU suite -- and writes records, plaintext and enc entries.  The machines' state stays on the device from push to
+ * push, so a session that spans pushes stays in step whether or not anybody fetches.
+ * THE STATE is public and plain: nfc_fsm_state, 88 bytes.  A host machine hands itself over with nfc_fsm_get_state / nfc_fsm_set_state,
+ * a stream with nfc_multi_get_fsm_state / nfc_multi_set_fsm_state; nfc_host_commands is the kernel's twin on the CPU.
+ * UID CAPACITY.  The host machine's UID is an unbounded vector; here it holds 32 bytes (an Ultralight's is 7, the standard's longest
+ * 10).  An append that would pass 32 is not made and sets the sticky NFC_FSM_UID_OVERFLOW: from there on that stream's commands are no
+ * longer promised to equal the host machine's.  No other stream is affected; a reset clears the flag.
+ * CUT FRAMES.  A frame with NFC_RAW_CUT gives a record with cmd == NFC_CMD_CUT and no bytes, does not touch the machine and sets the
+ * sticky NFC_FSM_LOST: a session's keystream is out of step from here on.  A stream whose packet table or bit slab was truncated in a
+ * push carries NFC_FSM_LOST too.
+ * ONE FRAME OUT.  An nfc_frame record; the plaintext bytes (data) and, inside a session, the enc entries as nfc_fsm_process gives them
+ * (on-air byte | 0x100 where the parity bit equals the data parity; n_enc of them, none outside a session), both indexed by the
+ * record's byte_off.  Every frame owns a slot of its RAW n_bytes entries in both arrays (the nested-authentication route yields fewer
+ * plaintext bytes than raw ones; a parity error none); entries of the slot that are not written are 0. */
+enum { NFC_CMD_CUT = -3 };          /* beside NFC_CMD_UNKNOWN, NFC_CMD_PARITY_ERROR: the frame's bits were cut (NFC_RAW_CUT) */
+enum { NFC_FSM_LOST = 1, NFC_FSM_UID_OVERFLOW = 2 };   /* nfc_fsm_state.flags, sticky until a reset */
+typedef struct nfc_fsm_state {      /* 88 bytes */
+    int32_t cur_cmd;                /* the command in flight (index for nfc_command_info) */
+    int32_t tag_type;               /* -1 none, 0 Ultralight, 1 Classic 1K, 2 Classic 4K, 3 DESFire */
+    int32_t encrypted;              /* a CRYPTO1 session is up */
+    int32_t cur_key;                /* 0: key A, 1: key B */
+    uint64_t cipher;                /* the 48-bit register; bit i is the i-th oldest bit */
+    uint8_t ar[4], at[4];           /* the expected reader / tag answers */
+    uint8_t key_a[6], key_b[6];
+    uint32_t uid_len;               /* 0 .. 32 */
+    uint8_t uid[32];                /* zero behind uid_len */
+    uint32_t flags;                 /* NFC_FSM_* */
+    uint32_t reserved;              /* 0 */
+} nfc_fsm_state;
+/* the state nfc_fsm_reset leaves: REQA in flight, no tag, both keys FF FF FF FF FF FF */
+int nfc_fsm_state_init(nfc_fsm_state *st);
+/* a host machine's state out and in.  get: NFC_ERR_ARG when the host UID is longer than 32 bytes; set: NFC_ERR_ARG for a field out of range */
+int nfc_fsm_get_state(const nfc_fsm *f, nfc_fsm_state *st);
+int nfc_fsm_set_state(nfc_fsm *f, const nfc_fsm_state *st);
+/* The kernel's twin on the CPU (no GPU needed): nfc_fsm_process_frames' arguments, but on the plain state and with the slots described
+ * above -- frame i's byte_off is the sum of the raw n_bytes before it; data / enc hold cap entries each (NFC_ERR_ARG when the frames
+ * need more); *used: entries that belong to the frames.  A frame with NFC_RAW_CUT is accepted (NFC_CMD_CUT). */
+int nfc_host_commands(nfc_fsm_state *st, const nfc_raw_frame *merged, size_t n, const uint8_t *bytes0, const uint8_t *par0,
+                      const uint8_t *bytes1, const uint8_t *par1, nfc_frame *out, uint8_t *data, uint16_t *enc, size_t cap, size_t *used);
+/* nfc_multi_track_commands(m, on): off at create.  While it is on, every nfc_multi_push / _push_device enqueues three launches before it
+ * returns, after it has read the counts -- the frames scan, the frames assembly, k_multi_commands -- with no host wait: the machines
+ * advance exactly once per push and stream.  A push in which nothing is stored launches nothing.  nfc_multi_fetch and
+ * nfc_multi_fetch_frames keep their own buffers and lifetimes; a context that never switches tracking on launches what it always did.
+ * nfc_multi_fetch_commands: ONE copy of the tracking's buffer to pinned memory, then one wait.
+ *   raw            the frames of this push, exactly what nfc_multi_fetch_frames gives for it (its n_launches / bytes_copied / ms_kernels: 0)
+ *   cmd_off        n_streams + 1: stream k's commands are cmd / src [cmd_off[k] .. cmd_off[k + 1]), in stream order (both types merged)
+ *   cbyte_off      n_streams + 1: its slots are data / enc [cbyte_off[k] .. cbyte_off[k + 1]); a record's byte_off is relative to cbyte_off[k]
+ *   src            per command: type << 31 | index among the stream's raw frames of that type (raw.frames[type][raw.frame_off[type][k] + index])
+ *   stream_flags   n_streams: NFC_FSM_LOST, NFC_FSM_UID_OVERFLOW
+ *   ms_kernels     with nfc_multi_set_timing(on): the three launches by HIP events, ms_machine the machine kernel alone; else 0
+ * A second call before the next push returns the same data and touches no machine.  Tracking off at the last push, or no completed
+ * push: NFC_ERR_STATE.  Device totals that differ from the host's: NFC_ERR_INTERNAL.  Nothing stored in the push: n_launches == 0, the
+ * offsets all zero, NULL arrays but stream_flags.  The pointers live until the next nfc_multi_push / _push_device,
+ * nfc_multi_fetch_commands, nfc_multi_reset, nfc_multi_set_state, nfc_multi_set_fsm_state or nfc_multi_destroy.
+ * nfc_multi_set_keys: the sector keys of stream `stream` (-1: of every stream), as nfc_fsm_set_keys.  nfc_multi_get_fsm_state /
+ * nfc_multi_set_fsm_state complete the device first.  nfc_multi_reset(stream) also returns that stream's machine to
+ * nfc_fsm_state_init's state, keys included, as nfc_fsm_reset does; nfc_multi_set_state does not touch the machine.
+ * Argument errors (a stream out of range, a null key or state, a state field out of range) are NFC_ERR_ARG, raised before the device is
+ * touched, the argument's name in the message.
+ * COST, measured with K copies of a 24-frame Classic capture of 39 269 samples (README.md, profiles/commands_bench.json): the call and two
+ * vectorised masks cost 0.730 us per capture at 1 024 streams and 0.724 us at 16 384, against 93.27 / 94.07 us for nfc_multi_fetch_frames and
+ * a host call per stream; tracking adds 0.32 ms / 1.05 ms to a push of 15.7 / 16.2 ms, the machine kernel alone 0.28 - 0.29 ms. */
+typedef struct {
+    nfc_multi_frames raw;
+    const uint64_t *cmd_off, *cbyte_off;   /* n_streams + 1 entries each */
+    const nfc_frame *cmd;
+    const uint32_t *src;
+    const uint8_t *data;
+    const uint16_t *enc;
+    const uint32_t *stream_flags;          /* n_streams */
+    uint32_t n_streams, n_launches;        /* of the push: 3, or 0 when nothing was stored */
+    uint64_t bytes_copied;                 /* device -> host, of this call */
+    double ms_kernels, ms_machine;
+    uint64_t reserved[4];
+} nfc_multi_commands;
+int nfc_multi_track_commands(nfc_multi *m, int on);
+int nfc_multi_fetch_commands(nfc_multi *m, nfc_multi_commands *out);
+int nfc_multi_set_keys(nfc_multi *m, int64_t stream /* -1: every stream */, const uint8_t key_a[6], const uint8_t key_b[6]);
+int nfc_multi_get_fsm_state(nfc_multi *m, uint32_t stream, nfc_fsm_state *st);
+int nfc_multi_set_fsm_state(nfc_multi *m, uint32_t stream, const nfc_fsm_state *st);
 
 /* one stream's boundary state, in the form an nfc_ctx exports and imports it */
 int nfc_multi_get_state(nfc_multi *m, uint32_t stream, nfc_state_header *hdr, float *ring, size_t ring_cap, uint8_t *pending, size_t pending_cap);

@@ -66,6 +66,18 @@ class MultiFrames(C.Structure):   # nfc_multi_frames
                 ('bytes_copied', C.c_uint64), ('ms_kernels', C.c_double), ('reserved', C.c_uint64 * 4)]
 
 
+class FsmState(C.Structure):   # nfc_fsm_state
+    _fields_ = [('cur_cmd', C.c_int32), ('tag_type', C.c_int32), ('encrypted', C.c_int32), ('cur_key', C.c_int32), ('cipher', C.c_uint64),
+                ('ar', C.c_uint8 * 4), ('at', C.c_uint8 * 4), ('key_a', C.c_uint8 * 6), ('key_b', C.c_uint8 * 6), ('uid_len', C.c_uint32),
+                ('uid', C.c_uint8 * 32), ('flags', C.c_uint32), ('reserved', C.c_uint32)]
+
+
+class MultiCommands(C.Structure):   # nfc_multi_commands
+    _fields_ = [('raw', MultiFrames), ('cmd_off', C.c_void_p), ('cbyte_off', C.c_void_p), ('cmd', C.c_void_p), ('src', C.c_void_p),
+                ('data', C.c_void_p), ('enc', C.c_void_p), ('stream_flags', C.c_void_p), ('n_streams', C.c_uint32), ('n_launches', C.c_uint32),
+                ('bytes_copied', C.c_uint64), ('ms_kernels', C.c_double), ('ms_machine', C.c_double), ('reserved', C.c_uint64 * 4)]
+
+
 class Frame(C.Structure):   # nfc_frame
     _fields_ = [('cmd', C.c_int32), ('type', C.c_int32), ('byte_off', C.c_uint32), ('n_bytes', C.c_uint16),
                 ('n_header', C.c_uint16), ('n_extra', C.c_uint16), ('n_crc', C.c_uint16), ('flags', C.c_uint32),
@@ -93,6 +105,12 @@ PACKET_DTYPE = np.dtype([('idx', '<u8'), ('bit_off', '<u8'), ('n_bits', '<u4'), 
 RAW_FRAME_DTYPE = np.dtype([('idx', '<u8'), ('byte_off', '<u4'), ('n_bits', '<u4'), ('n_bytes', '<u4'), ('flags', '<u4'), ('type', '<i4'),
                             ('reserved', '<u4')])
 NFC_RAW_PARITY_OK, NFC_RAW_CRC_A_OK, NFC_RAW_CUT = 0x100, 0x200, 0x400
+# nfc_fsm_state as a record (FsmState is its ctypes form), its sticky flags, and the record of a frame whose bits were cut
+FSM_STATE_DTYPE = np.dtype([('cur_cmd', '<i4'), ('tag_type', '<i4'), ('encrypted', '<i4'), ('cur_key', '<i4'), ('cipher', '<u8'), ('ar', 'u1', (4,)),
+                            ('at', 'u1', (4,)), ('key_a', 'u1', (6,)), ('key_b', 'u1', (6,)), ('uid_len', '<u4'), ('uid', 'u1', (32,)), ('flags', '<u4'),
+                            ('reserved', '<u4')])
+NFC_FSM_LOST, NFC_FSM_UID_OVERFLOW = 1, 2
+NFC_CMD_CUT = -3
 COUNTS_DTYPE = np.dtype([('n_samples', '<u8'), ('n_edges', '<u8'), ('n_symbols', '<u8', (2,)), ('n_packets', '<u8', (2,)),
                          ('n_packet_bits', '<u8', (2,))])   # nfc_counts
 
@@ -108,7 +126,9 @@ SYMBOLS = ['nfc_abi_version', 'nfc_device_count', 'nfc_create', 'nfc_destroy', '
            'nfc_multi_create', 'nfc_multi_destroy', 'nfc_multi_last_error', 'nfc_multi_push_device', 'nfc_multi_push', 'nfc_multi_get_counts',
            'nfc_multi_read_edges', 'nfc_multi_read_symbols', 'nfc_multi_read_packets', 'nfc_multi_read_packet_bits', 'nfc_multi_get_state',
            'nfc_multi_set_state', 'nfc_multi_reset', 'nfc_multi_get_stats', 'nfc_multi_set_timing', 'nfc_multi_fetch', 'nfc_multi_get_counts_all',
-           'nfc_get_frame_counts', 'nfc_read_frames', 'nfc_read_frame_bytes', 'nfc_host_frames', 'nfc_fsm_process_frames', 'nfc_multi_fetch_frames']
+           'nfc_get_frame_counts', 'nfc_read_frames', 'nfc_read_frame_bytes', 'nfc_host_frames', 'nfc_fsm_process_frames', 'nfc_multi_fetch_frames',
+           'nfc_fsm_state_init', 'nfc_fsm_get_state', 'nfc_fsm_set_state', 'nfc_host_commands', 'nfc_multi_track_commands', 'nfc_multi_fetch_commands',
+           'nfc_multi_set_keys', 'nfc_multi_get_fsm_state', 'nfc_multi_set_fsm_state']
 
 _libs = {}
 
@@ -224,6 +244,15 @@ def load(path=None):
     L.nfc_host_frames.argtypes = [vp, sz, vp, C.c_int, vp, vp, vp, sz, psz]
     L.nfc_fsm_process_frames.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp, sz, psz, vp]
     L.nfc_multi_fetch_frames.argtypes = [vp, C.POINTER(MultiFrames)]
+    L.nfc_fsm_state_init.argtypes = [C.POINTER(FsmState)]
+    L.nfc_fsm_get_state.argtypes = [vp, C.POINTER(FsmState)]
+    L.nfc_fsm_set_state.argtypes = [vp, C.POINTER(FsmState)]
+    L.nfc_host_commands.argtypes = [C.POINTER(FsmState), vp, sz, vp, vp, vp, vp, vp, vp, vp, sz, psz]
+    L.nfc_multi_track_commands.argtypes = [vp, C.c_int]
+    L.nfc_multi_fetch_commands.argtypes = [vp, C.POINTER(MultiCommands)]
+    L.nfc_multi_set_keys.argtypes = [vp, C.c_int64, vp, vp]
+    L.nfc_multi_get_fsm_state.argtypes = [vp, u32, C.POINTER(FsmState)]
+    L.nfc_multi_set_fsm_state.argtypes = [vp, u32, C.POINTER(FsmState)]
     for name in SYMBOLS:
         getattr(L, name)
     _libs[path] = L

@@ -10,7 +10,8 @@ from ._lib import (COUNTS_DTYPE, EDGE_DTYPE, NFC_MF_ARRAYS, NFC_MF_BITS0, NFC_MF
                    NFC_FLAG_FORCE_SEQUENTIAL, NFC_FLAG_NO_EDGES, NFC_IN_ENV_F32, NFC_IN_I16_SQ,
                    NFC_IN_IQ_F32, NFC_IN_IQ_I8, NFC_IN_IQ_I16, NFC_IN_IQ_U8, NFC_IN_REAL_F32_SQ, NFC_MULTI_PENDING_OVERFLOW,
                    NFC_MULTI_TRUNC_BITS, NFC_MULTI_TRUNC_EDGES, NFC_MULTI_TRUNC_PACKETS, NFC_MULTI_TRUNC_SYMBOLS, NFC_REC_ENVELOPE,
-                   NFC_RAW_CRC_A_OK, NFC_RAW_CUT, NFC_RAW_PARITY_OK, NFC_REC_REAL_PART, PACKET_DTYPE, RAW_FRAME_DTYPE)
+                   NFC_RAW_CRC_A_OK, NFC_RAW_CUT, NFC_RAW_PARITY_OK, NFC_REC_REAL_PART, PACKET_DTYPE, RAW_FRAME_DTYPE, NFC_FSM_LOST,
+                   NFC_FSM_UID_OVERFLOW, NFC_CMD_CUT)
 
 __all__ = ['NfcContext', 'NfcError', 'DeviceBuffer', 'host_decode_lut', 'host_envelope', 'NFC_IN_IQ_F32', 'NFC_IN_ENV_F32',
            'NFC_IN_REAL_F32_SQ', 'NFC_IN_I16_SQ', 'NFC_IN_IQ_I16', 'NFC_IN_IQ_I8', 'NFC_IN_IQ_U8', 'NFC_FLAG_FORCE_SEQUENTIAL',
@@ -19,7 +20,8 @@ __all__ = ['NfcContext', 'NfcError', 'DeviceBuffer', 'host_decode_lut', 'host_en
            'NFC_MULTI_TRUNC_BITS', 'NFC_MULTI_PENDING_OVERFLOW', 'NfcMultiFetch', 'NFC_MULTI_FETCH_EDGES', 'NFC_MULTI_FETCH_SYMBOLS',
            'NFC_MULTI_FETCH_PACKETS', 'NFC_MULTI_FETCH_ALL', 'NFC_MF_EDGES', 'NFC_MF_SYM0', 'NFC_MF_SYM1', 'NFC_MF_PK0', 'NFC_MF_PK1',
            'NFC_MF_BITS0', 'NFC_MF_BITS1', 'NFC_MF_ARRAYS', 'COUNTS_DTYPE', 'COUNTS_FLAGS_DTYPE', 'NfcFrames', 'NfcMultiFrames', 'host_frames',
-           'RAW_FRAME_DTYPE', 'NFC_RAW_PARITY_OK', 'NFC_RAW_CRC_A_OK', 'NFC_RAW_CUT']
+           'RAW_FRAME_DTYPE', 'NFC_RAW_PARITY_OK', 'NFC_RAW_CRC_A_OK', 'NFC_RAW_CUT', 'NfcMultiCommands', 'NFC_FSM_LOST', 'NFC_FSM_UID_OVERFLOW',
+           'NFC_CMD_CUT']
 
 _KIND_DTYPE = {NFC_IN_IQ_F32: (np.float32, 2), NFC_IN_ENV_F32: (np.float32, 1),
                NFC_IN_REAL_F32_SQ: (np.float32, 1), NFC_IN_I16_SQ: (np.int16, 1), NFC_IN_IQ_I16: (np.int16, 2),
@@ -407,6 +409,41 @@ class NfcMultiContext(object):
         self._chk(self.L.nfc_multi_fetch_frames(self.h, C.byref(f)), 'nfc_multi_fetch_frames')
         return NfcMultiFrames(f, copy)
 
+    def track_commands(self, on=True):
+        """While on, every push also assembles the frames and runs the protocol machine, CRYPTO1 included, a GPU lane per stream
+        (nfc_multi_track_commands): three more launches behind the push's own, no host wait.  The machines' state stays on the device
+        from push to push; fetch_commands() brings the last push's commands to the host."""
+        self._chk(self.L.nfc_multi_track_commands(self.h, int(bool(on))), 'nfc_multi_track_commands')
+
+    def set_keys(self, key_a=(0xFF,) * 6, key_b=(0xFF,) * 6, stream=None):
+        """MIFARE Classic sector keys A / B of one stream's machine (default: of every stream's), six bytes each, as fsm.set_keys."""
+        a, b = np.ascontiguousarray(key_a, np.uint8), np.ascontiguousarray(key_b, np.uint8)
+        if a.size != 6 or b.size != 6:
+            raise NfcError('set_keys: key_a and key_b are six bytes each')
+        self._chk(self.L.nfc_multi_set_keys(self.h, -1 if stream is None else int(stream), a.ctypes.data, b.ctypes.data), 'nfc_multi_set_keys')
+
+    def fsm_state(self, k):
+        """Stream k's protocol machine as a plain nfc_fsm_state (an _lib.FsmState): what fsm.set_state takes."""
+        if not 0 <= int(k) < self.n_streams:
+            raise NfcError('fsm_state: stream %d out of range (n_streams %d)' % (k, self.n_streams))
+        st = _lib.FsmState()
+        self._chk(self.L.nfc_multi_get_fsm_state(self.h, int(k), C.byref(st)), 'nfc_multi_get_fsm_state')
+        return st
+
+    def set_fsm_state(self, k, st):
+        """Stream k's machine continues from `st` (fsm.get_state(), another stream's fsm_state())."""
+        if not 0 <= int(k) < self.n_streams:
+            raise NfcError('set_fsm_state: stream %d out of range (n_streams %d)' % (k, self.n_streams))
+        self._chk(self.L.nfc_multi_set_fsm_state(self.h, int(k), C.byref(st)), 'nfc_multi_set_fsm_state')
+
+    def fetch_commands(self, copy=True):
+        """The commands of the last push, tracked on the GPU (track_commands), in ONE copy (nfc_multi_fetch_commands) -> NfcMultiCommands.
+        copy=False: views of the context's pinned memory, valid until the next push, fetch_commands, reset, set_state, set_fsm_state or
+        close of this context."""
+        c = _lib.MultiCommands()
+        self._chk(self.L.nfc_multi_fetch_commands(self.h, C.byref(c)), 'nfc_multi_fetch_commands')
+        return NfcMultiCommands(c, copy)
+
     def counts_all(self):
         """Every stream's counts and flags of the last push from one call: a COUNTS_FLAGS_DTYPE array of n_streams records."""
         cnt, flags = np.zeros(self.n_streams, COUNTS_DTYPE), np.zeros(self.n_streams, np.uint32)
@@ -720,6 +757,59 @@ class NfcMultiFrames(object):
     def crc_ok_mask(self):
         """Per type, over ALL frames of frames[t]: parity held and the CRC_A matched."""
         return [(self.frames[t]['flags'] & NFC_RAW_CRC_A_OK) != 0 for t in (0, 1)]
+
+
+class NfcMultiCommands(object):
+    """What nfc_multi_fetch_commands brings: every stream's commands of one push, found by the protocol machine on the GPU.
+    cmd: fsm.FRAME_DTYPE records of ALL streams, stream k's are cmd[cmd_off[k]:cmd_off[k + 1]] in stream order (both directions merged);
+    data / enc: the plaintext bytes and, inside a CRYPTO1 session, the on-air entries (byte | 0x100 where the parity bit equals the data
+    parity), stream k's part data[cbyte_off[k]:cbyte_off[k + 1]], a record's byte_off relative to it; every frame owns a slot of its raw
+    n_bytes entries in both, zero where nothing was written.  src: type << 31 | index among the stream's raw frames of that type.
+    raw: the NfcMultiFrames of the same push.  stream_flags: NFC_FSM_LOST / NFC_FSM_UID_OVERFLOW per stream."""
+
+    def __init__(self, c, copy=True):
+        from .fsm import FRAME_DTYPE
+        K = int(c.n_streams)
+        self.n_streams, self.n_launches, self.bytes_copied = K, int(c.n_launches), int(c.bytes_copied)
+        self.ms_kernels, self.ms_machine = float(c.ms_kernels), float(c.ms_machine)
+
+        def arr(ptr, n, dtype):
+            dtype = np.dtype(dtype)
+            if not ptr or not n:
+                return np.zeros(0, dtype)
+            a = np.frombuffer((C.c_char * (int(n) * dtype.itemsize)).from_address(ptr), dtype)
+            return a.copy() if copy else a
+
+        self.raw = NfcMultiFrames(c.raw, copy)
+        self.cmd_off, self.cbyte_off = arr(c.cmd_off, K + 1, '<u8'), arr(c.cbyte_off, K + 1, '<u8')
+        self.cmd = arr(c.cmd, self.cmd_off[K], FRAME_DTYPE)
+        self.src = arr(c.src, self.cmd_off[K], '<u4')
+        self.data = arr(c.data, self.cbyte_off[K], np.uint8)
+        self.enc = arr(c.enc, self.cbyte_off[K], '<u2')
+        self.stream_flags = arr(c.stream_flags, K, '<u4')
+
+    def commands_of(self, k):
+        """Stream k's (table, data, enc) as numpy views: what fsm.dispatch takes."""
+        a, b = int(self.cbyte_off[k]), int(self.cbyte_off[k + 1])
+        return self.cmd[int(self.cmd_off[k]):int(self.cmd_off[k + 1])], self.data[a:b], self.enc[a:b]
+
+    def src_of(self, k):
+        """Per command of stream k: (type, index among the stream's raw frames of that type)."""
+        s = self.src[int(self.cmd_off[k]):int(self.cmd_off[k + 1])]
+        return (s >> 31).astype(np.int64), (s & 0x7FFFFFFF).astype(np.int64)
+
+    def stream_of(self):
+        """The stream every command of cmd belongs to."""
+        return np.repeat(np.arange(self.n_streams, dtype=np.int64), np.diff(self.cmd_off).astype(np.int64))
+
+    def cmd_mask(self, index):
+        """Over ALL commands: true where the command is `index` (an index of the command table, or NFC_CMD_*)."""
+        return self.cmd['cmd'] == int(index)
+
+    def plain_crc_ok_mask(self):
+        """Over ALL commands: true where the command's definition carries a CRC_A.  A command is only found when its CRC matches -- inside
+        a session: the CRC of the PLAINTEXT -- so no byte is touched."""
+        return (self.cmd['cmd'] >= 0) & (self.cmd['n_crc'] == 2)
 
 
 def host_frames(table, bits, ptype):

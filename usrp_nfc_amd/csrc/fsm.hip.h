@@ -1,0 +1,510 @@
+// fsm.hip.h -- the protocol machine of protocol.h (fsm_process_frame and everything it reaches: fsm_strip, fsm_finish, find_command /
+// compatible, Crypto1::{load_key, crypt, set_answers, set_tag}) restated without vectors and without allocation, for host and device:
+// one frame as the GPU assembled it (nfc_raw_frame, its bytes and ninth bits) in, one nfc_frame record, the plaintext and the `enc`
+// entries out, the state in a plain struct (nfc_fsm_state, include/nfc_amd.h).  k_multi_commands (multi_commands.hip.h) runs it a lane
+// per stream, nfc_host_commands on the CPU; protocol.h stays the oracle: tests/test_commands.py pins this file to it.
+//
+// Form.  The machine lives in named scalars (Machine): the 48-bit cipher register in a uint64, ar / at and the keys as integers (byte 0
+// lowest), the UID as eight words reached through select chains -- nothing is an array with a dynamic index, so a lane needs no
+// scratch.  Only a frame of at most 18 bytes can be a command (the longest total() of the table: READT / COMPW2), so the lookup sees
+// the frame through five words (Bytes); the CRC_A register runs two bytes behind the byte loop as in assemble_frame (frames.hip.h).
+// CRYPTO1 is bit-serial: per clock the filter reads 20 fixed register bits through truth-table words that a constexpr builds from fa /
+// fb / fc as protocol.h states them, and the feedback is the parity of popcount(st & TAPS), TAPS built from the eighteen tap positions.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include/nfc_amd.h"
+#include "frames.hip.h"
+
+namespace nfc {
+namespace fsmd {
+
+#define NFC_HD __host__ __device__ __forceinline__
+
+// ---- the command table (protocol.h: COMMANDS, in its order; nfc_host_commands checks the two against each other) ----
+enum {
+    C_REQA, C_WUPA, C_ATQAUL, C_ATQA1K, C_ATQA4K, C_ATQADS, C_ANTI1R, C_ANTI1U, C_ANTI1G, C_SEL1R, C_SEL1U,
+    C_SEL1K, C_ANTI2R, C_ANTI2T, C_AUTHA, C_AUTHB, C_RANDTA, C_RANDRB, C_RANDTB, C_SEL2R, C_SEL2T, C_READR,
+    C_READT, C_HALT, C_WRITE, C_COMPW1, C_COMPW2, C_COUNT
+};
+constexpr int MAX_COMMAND_BYTES = 18;
+// stage | n_header << 4 | type << 6 | crc << 7 | n_extra << 8 | has_xor << 13 | xor seed << 16 | header[0] << 24; header[1] apart
+constexpr uint32_t def_word(int stage, int n_header, int h0, int type, int crc, int n_extra, int xor_check) {
+    return (uint32_t)stage | (uint32_t)n_header << 4 | (uint32_t)type << 6 | (uint32_t)crc << 7 | (uint32_t)n_extra << 8 |
+           (xor_check >= 0 ? 1u << 13 | (uint32_t)xor_check << 16 : 0u) | (uint32_t)h0 << 24;
+}
+struct Def {
+    uint32_t w, h1;
+    NFC_HD int stage() const { return (int)(w & 15u); }
+    NFC_HD int n_header() const { return (int)((w >> 4) & 3u); }
+    NFC_HD int type() const { return (int)((w >> 6) & 1u); }
+    NFC_HD int crc() const { return (int)((w >> 7) & 1u); }
+    NFC_HD int n_extra() const { return (int)((w >> 8) & 31u); }
+    NFC_HD int xor_check() const { return (w >> 13) & 1u ? (int)((w >> 16) & 0xFFu) : -1; }
+    NFC_HD uint32_t h0() const { return w >> 24; }
+    NFC_HD int total() const { return n_header() + n_extra() + 2 * crc(); }
+};
+NFC_HD Def def_of(int cmd) {
+    switch (cmd) {
+    case C_REQA: return Def{def_word(0, 1, 0x26, 1, 0, 0, -1), 0};
+    case C_WUPA: return Def{def_word(0, 1, 0x52, 1, 0, 0, -1), 0};
+    case C_ATQAUL: return Def{def_word(0, 2, 0x44, 0, 0, 0, -1), 0x00};
+    case C_ATQA1K: return Def{def_word(0, 2, 0x04, 0, 0, 0, -1), 0x00};
+    case C_ATQA4K: return Def{def_word(0, 2, 0x02, 0, 0, 0, -1), 0x00};
+    case C_ATQADS: return Def{def_word(0, 2, 0x03, 0, 0, 0, -1), 0x44};
+    case C_ANTI1R: return Def{def_word(1, 2, 0x93, 1, 0, 0, -1), 0x20};
+    case C_ANTI1U: return Def{def_word(1, 1, 0x88, 0, 0, 4, 0x88), 0};
+    case C_ANTI1G: return Def{def_word(1, 0, 0, 0, 0, 5, 0), 0};
+    case C_SEL1R: return Def{def_word(2, 2, 0x93, 1, 1, 5, 0), 0x70};
+    case C_SEL1U: return Def{def_word(2, 1, 0x04, 0, 1, 0, -1), 0};
+    case C_SEL1K: return Def{def_word(2, 1, 0x08, 0, 1, 0, -1), 0};
+    case C_ANTI2R: return Def{def_word(3, 2, 0x95, 1, 0, 0, -1), 0x20};
+    case C_ANTI2T: return Def{def_word(3, 0, 0, 0, 0, 5, 0), 0};
+    case C_AUTHA: return Def{def_word(3, 1, 0x60, 1, 1, 1, -1), 0};
+    case C_AUTHB: return Def{def_word(3, 1, 0x61, 1, 1, 1, -1), 0};
+    case C_RANDTA: return Def{def_word(3, 0, 0, 0, 0, 4, -1), 0};
+    case C_RANDRB: return Def{def_word(4, 0, 0, 1, 0, 8, -1), 0};
+    case C_RANDTB: return Def{def_word(4, 0, 0, 0, 0, 4, -1), 0};
+    case C_SEL2R: return Def{def_word(4, 2, 0x95, 1, 1, 5, 0), 0x70};
+    case C_SEL2T: return Def{def_word(4, 1, 0x00, 0, 1, 0, -1), 0};
+    case C_READR: return Def{def_word(5, 1, 0x30, 1, 1, 1, -1), 0};
+    case C_READT: return Def{def_word(5, 0, 0, 0, 1, 16, -1), 0};
+    case C_HALT: return Def{def_word(10, 2, 0x50, 1, 1, 0, -1), 0x00};
+    case C_WRITE: return Def{def_word(6, 1, 0xA2, 1, 1, 5, -1), 0};
+    case C_COMPW1: return Def{def_word(6, 1, 0xA0, 1, 1, 1, -1), 0};
+    default: return Def{def_word(7, 0, 0, 1, 1, 16, -1), 0};   // C_COMPW2
+    }
+}
+// candidates per protocol stage and direction, in the reference's order (protocol.h: TAG_STAGE, READER_STAGE), four to a word, 0xFF: none
+constexpr uint32_t cand4(int a, int b = 0xFF, int c = 0xFF, int d = 0xFF) {
+    return (uint32_t)a | (uint32_t)b << 8 | (uint32_t)c << 16 | (uint32_t)d << 24;
+}
+NFC_HD uint32_t tag_stage(int v) {
+    switch (v) {
+    case 0: return cand4(C_ATQAUL, C_ATQA1K, C_ATQA4K, C_ATQADS);
+    case 1: return cand4(C_ANTI1U, C_ANTI1G);
+    case 2: return cand4(C_SEL1U, C_SEL1K);
+    case 3: return cand4(C_ANTI2T, C_RANDTA);
+    case 4: return cand4(C_SEL2T, C_RANDTB);
+    case 5: return cand4(C_READT);
+    default: return 0xFFFFFFFFu;   // (v >= 6: the reference has no entry)
+    }
+}
+NFC_HD uint32_t reader_stage(int v) {
+    switch (v) {
+    case 0: return cand4(C_REQA, C_WUPA);
+    case 1: return cand4(C_ANTI1R);
+    case 2: return cand4(C_SEL1R);
+    case 3: return cand4(C_ANTI2R, C_AUTHA, C_AUTHB);
+    case 4: return cand4(C_SEL2R, C_RANDRB);
+    case 5: return cand4(C_READR);
+    case 6: return cand4(C_WRITE, C_COMPW1);
+    case 7: return cand4(C_COMPW2);
+    default: return 0xFFFFFFFFu;   // (v >= 8)
+    }
+}
+
+// ---- CRYPTO1 (protocol.h: Crypto1; cipher.py) ----
+constexpr int fa(int a, int b, int c, int d) { return ((a | b) ^ (a & d)) ^ (c & ((a ^ b) | d)); }
+constexpr int fb(int a, int b, int c, int d) { return ((a & b) | c) ^ ((a ^ b) & (c | d)); }
+constexpr int fc(int a, int b, int c, int d, int e) { return (a | ((b | e) & (d ^ e))) ^ ((a ^ (b & d)) & ((c ^ d) | (b & e))); }
+// truth tables: bit (a | b << 1 | c << 2 | d << 3 [| e << 4]) of the word is the function's value
+constexpr uint32_t table_fa() {
+    uint32_t t = 0;
+    for (int i = 0; i < 16; i++) t |= (uint32_t)(fa(i & 1, (i >> 1) & 1, (i >> 2) & 1, (i >> 3) & 1) & 1) << i;
+    return t;
+}
+constexpr uint32_t table_fb() {
+    uint32_t t = 0;
+    for (int i = 0; i < 16; i++) t |= (uint32_t)(fb(i & 1, (i >> 1) & 1, (i >> 2) & 1, (i >> 3) & 1) & 1) << i;
+    return t;
+}
+constexpr uint32_t table_fc() {
+    uint32_t t = 0;
+    for (int i = 0; i < 32; i++) t |= (uint32_t)(fc(i & 1, (i >> 1) & 1, (i >> 2) & 1, (i >> 3) & 1, (i >> 4) & 1) & 1) << i;
+    return t;
+}
+constexpr uint64_t taps_mask() {
+    const int taps[18] = {0, 5, 9, 10, 12, 14, 15, 17, 19, 24, 25, 27, 29, 35, 39, 41, 42, 43};   // protocol.h: Crypto1::feedback
+    uint64_t m = 0;
+    for (int i = 0; i < 18; i++) m |= 1ull << taps[i];
+    return m;
+}
+constexpr uint32_t TT_FA = table_fa(), TT_FB = table_fb(), TT_FC = table_fc();
+constexpr uint64_t TAPS = taps_mask(), ST_MASK = (1ull << 48) - 1;
+
+// register bits p, p + 2, p + 4, p + 6 as a four-bit index
+NFC_HD uint32_t quad(uint64_t st, int p) {
+    const uint32_t x = (uint32_t)(st >> p);
+    return (x & 1u) | ((x >> 1) & 2u) | ((x >> 2) & 4u) | ((x >> 3) & 8u);
+}
+NFC_HD uint32_t filter(uint64_t st) {   // protocol.h: Crypto1::filter
+    const uint32_t a = (TT_FA >> quad(st, 9)) & 1u, b = (TT_FB >> quad(st, 17)) & 1u, c = (TT_FB >> quad(st, 25)) & 1u;
+    const uint32_t d = (TT_FA >> quad(st, 33)) & 1u, e = (TT_FB >> quad(st, 41)) & 1u;
+    return (TT_FC >> (a | b << 1 | c << 2 | d << 3 | e << 4)) & 1u;
+}
+NFC_HD uint32_t feedback(uint64_t st) { return (uint32_t)__builtin_popcountll(st & TAPS) & 1u; }
+NFC_HD uint64_t shift_in(uint64_t st, uint32_t in) { return (st >> 1) | ((uint64_t)((feedback(st) ^ in) & 1u) << 47); }
+// the nonce register 64 and 96 clocks on (protocol.h: set_answers): bit j of x is the j-th oldest of the 32 bits
+NFC_HD uint32_t nonce_advance(uint32_t x, int ticks) {
+    for (int t = 0; t < ticks; t++) x = (x >> 1) | ((((x >> 16) ^ (x >> 18) ^ (x >> 19) ^ (x >> 21)) & 1u) << 31);
+    return x;
+}
+
+// ---- the machine in scalars ----
+struct Machine {
+    int32_t cur_cmd, tag_type, encrypted, cur_key;
+    uint64_t st, key_a, key_b;   // 48 bits each; a key's byte 0 lowest: load_key's bit order makes the key the register
+    uint32_t ar, at;             // byte 0 lowest
+    uint32_t uid_len, flags;
+    uint32_t u0, u1, u2, u3, u4, u5, u6, u7;
+};
+constexpr uint32_t UID_CAP = 32;
+
+NFC_HD uint32_t uid_byte(const Machine &M, uint32_t i) {
+    const uint32_t j = i >> 2;
+    const uint32_t w = j == 0 ? M.u0 : j == 1 ? M.u1 : j == 2 ? M.u2 : j == 3 ? M.u3 : j == 4 ? M.u4 : j == 5 ? M.u5 : j == 6 ? M.u6 : M.u7;
+    return (w >> (8u * (i & 3u))) & 0xFFu;
+}
+NFC_HD void uid_put(Machine &M, uint32_t i, uint32_t b) {
+    const uint32_t j = i >> 2, sh = 8u * (i & 3u), keep = ~(0xFFu << sh), v = (b & 0xFFu) << sh;
+    M.u0 = j == 0 ? (M.u0 & keep) | v : M.u0;
+    M.u1 = j == 1 ? (M.u1 & keep) | v : M.u1;
+    M.u2 = j == 2 ? (M.u2 & keep) | v : M.u2;
+    M.u3 = j == 3 ? (M.u3 & keep) | v : M.u3;
+    M.u4 = j == 4 ? (M.u4 & keep) | v : M.u4;
+    M.u5 = j == 5 ? (M.u5 & keep) | v : M.u5;
+    M.u6 = j == 6 ? (M.u6 & keep) | v : M.u6;
+    M.u7 = j == 7 ? (M.u7 & keep) | v : M.u7;
+}
+NFC_HD void uid_clear(Machine &M) {
+    M.uid_len = 0;
+    M.u0 = M.u1 = M.u2 = M.u3 = M.u4 = M.u5 = M.u6 = M.u7 = 0;
+}
+NFC_HD void machine_init(Machine &M) {   // nfc_fsm_reset
+    M.cur_cmd = C_REQA;
+    M.tag_type = -1;
+    M.encrypted = 0;
+    M.cur_key = 0;
+    M.st = 0;
+    M.key_a = M.key_b = ST_MASK;
+    M.ar = M.at = 0;
+    M.flags = 0;
+    uid_clear(M);
+}
+
+// a frame's first 20 bytes in five words
+struct Bytes {
+    uint32_t w0, w1, w2, w3, w4;
+    NFC_HD uint32_t at(uint32_t i) const {
+        const uint32_t j = i >> 2;
+        const uint32_t w = j == 0 ? w0 : j == 1 ? w1 : j == 2 ? w2 : j == 3 ? w3 : w4;
+        return (w >> (8u * (i & 3u))) & 0xFFu;
+    }
+    NFC_HD void put(uint32_t i, uint32_t b) {   // (into a cleared word, i < 20)
+        const uint32_t j = i >> 2, v = (b & 0xFFu) << (8u * (i & 3u));
+        w0 |= j == 0 ? v : 0u;
+        w1 |= j == 1 ? v : 0u;
+        w2 |= j == 2 ? v : 0u;
+        w3 |= j == 3 ? v : 0u;
+        w4 |= j == 4 ? v : 0u;
+    }
+    NFC_HD uint32_t word_at(uint32_t i) const { return at(i) | at(i + 1) << 8 | at(i + 2) << 16 | at(i + 3) << 24; }   // i + 3 < 20
+};
+
+struct Rec {
+    int32_t cmd, type;
+    uint32_t flags, n_bytes, n_header, n_extra, n_crc, n_enc;
+};
+
+// protocol.h: compatible.  crc_ok: the last two of the n bytes are the CRC_A of those before them.
+NFC_HD bool compatible(const Def &c, const Bytes &B, int n, bool crc_ok) {
+    if (c.total() != n) return false;
+    if (c.n_header() >= 1 && c.h0() != B.at(0)) return false;
+    if (c.n_header() >= 2 && c.h1 != B.at(1)) return false;
+    int end = n;
+    if (c.crc()) {
+        end -= 2;
+        if (!crc_ok) return false;
+    }
+    if (c.xor_check() >= 0) {
+        uint32_t a = (uint32_t)c.xor_check();
+#pragma unroll
+        for (int i = 0; i < MAX_COMMAND_BYTES; i++)
+            if (i >= c.n_header() && i < end) a ^= B.at((uint32_t)i);
+        if (a != 0) return false;
+    }
+    return true;
+}
+NFC_HD int first_compatible(uint32_t cands, const Bytes &B, int n, bool crc_ok) {
+    for (int k = 0; k < 4; k++) {
+        const int c = (int)((cands >> (8 * k)) & 0xFFu);
+        if (c == 0xFF) break;
+        if (compatible(def_of(c), B, n, crc_ok)) return c;
+    }
+    return -1;
+}
+// protocol.h: find_command, for 1 <= n <= MAX_COMMAND_BYTES
+NFC_HD int find_command(const Bytes &B, int n, int type, int prev_cmd, bool crc_ok) {
+    const int ind = def_of(prev_cmd).stage();
+    for (int v = ind; v <= ind + 1; v++) {
+        const int c = first_compatible(type == 0 ? tag_stage(v) : reader_stage(v), B, n, crc_ok);
+        if (c >= 0) return c;
+    }
+    int o0 = -1, o1 = -1;   // by leading bytes: the first listed option, or the second when the second byte names it
+    switch (B.at(0)) {
+    case 0x00: o0 = C_SEL2T; break;
+    case 0x02: o0 = C_ATQA4K; break;
+    case 0x03: o0 = C_ATQADS; break;
+    case 0x04: o0 = C_SEL1U; o1 = C_ATQA1K; break;
+    case 0x08: o0 = C_SEL1K; break;
+    case 0x26: o0 = C_REQA; break;
+    case 0x30: o0 = C_READR; break;
+    case 0x44: o0 = C_ATQAUL; break;
+    case 0x50: o0 = C_HALT; break;
+    case 0x52: o0 = C_WUPA; break;
+    case 0x60: o0 = C_AUTHA; break;
+    case 0x61: o0 = C_AUTHB; break;
+    case 0x88: o0 = C_ANTI1U; break;
+    case 0x93: o0 = C_ANTI1R; o1 = C_SEL1R; break;
+    case 0x95: o0 = C_ANTI2R; o1 = C_SEL2R; break;
+    case 0xA0: o0 = C_COMPW1; break;
+    case 0xA2: o0 = C_WRITE; break;
+    default: return -1;
+    }
+    int option = o0;
+    if (o1 >= 0) {
+        if (n < 2) return -1;
+        bool named;
+        switch (B.at(1)) {
+        case 0x00: named = (o1 == C_ATQAUL || o1 == C_HALT || o1 == C_ATQA1K); break;
+        case 0x20: named = (o1 == C_ANTI1R || o1 == C_ANTI2R); break;
+        case 0x70: named = (o1 == C_SEL1R || o1 == C_SEL2R); break;
+        default: return -1;
+        }
+        if (named) option = o1;
+    }
+    return compatible(def_of(option), B, n, crc_ok) ? option : -1;
+}
+
+// the UID grows by the n bytes at B[from ..): not made when it would pass UID_CAP (the host machine's vector is unbounded)
+NFC_HD void uid_append(Machine &M, const Bytes &B, uint32_t from, uint32_t n) {
+    if (M.uid_len + n > UID_CAP) {
+        M.flags |= NFC_FSM_UID_OVERFLOW;
+        return;
+    }
+    for (uint32_t j = 0; j < n; j++) uid_put(M, M.uid_len + j, B.at(from + j));
+    M.uid_len += n;
+}
+// how many UID bytes Crypto1::set_tag takes: its bit buffer holds 64 entries and a byte must fit whole, with or without a parity place
+NFC_HD uint32_t set_tag_bytes(const Machine &M) { return M.uid_len < 7u ? M.uid_len : 7u; }
+
+// protocol.h: fsm_finish.  nb plaintext bytes (0: a parity error, or nothing left), the first 20 of them in B.
+NFC_HD void finish(Machine &M, uint32_t nb, int type, Rec &out, const Bytes &B, bool crc_ok) {
+    if (nb == 0) {
+        out.cmd = NFC_CMD_PARITY_ERROR;
+        return;
+    }
+    out.n_bytes = nb;
+    // (a frame longer than the longest command is UNKNOWN without inspection: every route of find_command ends in total() == n)
+    const int cmd = nb <= (uint32_t)MAX_COMMAND_BYTES ? find_command(B, (int)nb, type, M.cur_cmd, crc_ok) : -1;
+    if (cmd < 0) {
+        out.cmd = NFC_CMD_UNKNOWN;
+        out.n_extra = nb;
+        return;
+    }
+    M.cur_cmd = cmd;
+    out.cmd = cmd;
+    const Def c = def_of(cmd);
+    const uint32_t h = (uint32_t)c.n_header();
+    out.n_header = h;
+    out.n_crc = c.crc() ? 2u : 0u;
+    out.n_extra = nb - h - out.n_crc;
+    switch (cmd) {
+    case C_REQA: case C_WUPA: case C_HALT:
+        uid_clear(M);
+        M.tag_type = -1;
+        M.encrypted = 0;
+        break;
+    case C_ATQAUL: M.tag_type = 0; break;
+    case C_ATQA1K: M.tag_type = 1; break;
+    case C_ATQA4K: M.tag_type = 2; break;
+    case C_ATQADS: M.tag_type = 3; break;
+    case C_ANTI1U: uid_append(M, B, h, 3); break;
+    case C_ANTI1G: uid_append(M, B, h, 4); break;
+    case C_SEL1R: {
+        const uint32_t start = M.tag_type == 0 ? 1u : 0u, n = 4u - start;
+        bool same = M.uid_len == n;
+        for (uint32_t j = 0; j < n; j++) same = same && uid_byte(M, j) == B.at(h + start + j);
+        if (!same) {
+            out.flags |= NFC_FRAME_UID_MISMATCH;
+            uid_clear(M);
+            for (uint32_t j = 0; j < n; j++) uid_put(M, j, B.at(h + start + j));
+            M.uid_len = n;
+        }
+        break;
+    }
+    case C_ANTI2T: uid_append(M, B, h, 4); break;
+    case C_SEL2R: {
+        bool same = M.uid_len >= 4u;
+        for (uint32_t j = 0; j < 4u; j++) same = same && uid_byte(M, (M.uid_len - 4u + j) & (UID_CAP - 1u)) == B.at(h + j);
+        if (!same) {
+            out.flags |= NFC_FRAME_UID_MISMATCH;
+            uid_append(M, B, h, 4);
+        }
+        break;
+    }
+    case C_AUTHA: M.cur_key = 0; break;
+    case C_AUTHB: M.cur_key = 1; break;
+    case C_RANDTA:
+        if (!M.encrypted) {   // first authentication: the tag nonce came in the clear; uid ^ nonce goes into a fresh register
+            M.st = M.cur_key ? M.key_b : M.key_a;
+            M.ar = M.at = 0;
+            const uint32_t nonce = B.word_at(h), nu = set_tag_bytes(M);
+            if (nu >= 1u && nu <= 4u) {   // (set_tag: nothing at all with no UID or with more UID bits than the nonce has)
+                for (uint32_t i = 0; i < nu; i++) {
+                    const uint32_t x = uid_byte(M, i) ^ ((nonce >> (8u * i)) & 0xFFu);
+                    for (int k = 0; k < 8; k++) M.st = shift_in(M.st, (x >> k) & 1u);
+                }
+                if (nu == 4u) {
+                    M.ar = nonce_advance(nonce, 64);
+                    M.at = nonce_advance(M.ar, 32);
+                    M.encrypted = 1;
+                }
+            }
+        }
+        break;
+    case C_RANDRB: out.flags |= (M.encrypted && B.word_at(h + 4u) == M.ar) ? NFC_FRAME_AR_OK : NFC_FRAME_AR_ERROR; break;
+    case C_RANDTB: out.flags |= (M.encrypted && B.word_at(h) == M.at) ? NFC_FRAME_AT_OK : NFC_FRAME_AT_ERROR; break;
+    default: break;
+    }
+}
+
+// One frame (protocol.h: fsm_process_frame): raw_flags / n its nfc_raw_frame's flags and n_bytes, bytes / par its data bytes and ninth
+// bits as received.  data / enc: the frame's slot, n entries each, ALL written: the plaintext bytes and the enc entries first, 0 behind.
+NFC_HD Rec process_frame(Machine &M, int type, uint32_t raw_flags, uint32_t n, const uint8_t *__restrict__ bytes, const uint8_t *__restrict__ par,
+                         uint8_t *__restrict__ data, uint16_t *__restrict__ enc) {
+    Rec out = {NFC_CMD_UNKNOWN, type, 0u, 0u, 0u, 0u, 0u, 0u};
+    if (raw_flags & NFC_RAW_CUT) {   // its bits are not there: the machine is not touched, the keystream of a session is out of step from here
+        out.cmd = NFC_CMD_CUT;
+        M.flags |= NFC_FSM_LOST;
+        return out;
+    }
+    out.flags = raw_flags & (uint32_t)(NFC_FRAME_EXTRA_ERROR | NFC_FRAME_MANY_MORE_ERROR);
+    Bytes B = {0u, 0u, 0u, 0u, 0u};
+    uint32_t nb;
+    bool crc_ok;
+    if (!M.encrypted) {
+        nb = (raw_flags & NFC_RAW_PARITY_OK) ? n : 0u;
+        crc_ok = (raw_flags & NFC_RAW_CRC_A_OK) != 0;
+        for (uint32_t i = 0; i < n; i++) {
+            const uint32_t b = nb ? bytes[i] : 0u;
+            data[i] = (uint8_t)b;
+            enc[i] = 0;
+            if (i < 20u) B.put(i, b);
+        }
+    } else {   // protocol.h: fsm_strip inside a session
+        out.flags |= NFC_FRAME_ENCRYPTED;
+        out.n_enc = n;
+        // {nr}{ar}: the reader nonce (the first half) is fed back into the register while it is decrypted
+        const bool nr_ar = M.cur_cmd == C_RANDTA && n == 8u;
+        // nested authentication: a fresh register keyed for the new sector swallows the encrypted tag nonce, uid ^ nonce fed in
+        const bool nested = !nr_ar && (M.cur_cmd == C_AUTHA || M.cur_cmd == C_AUTHB);
+        uint32_t todo = n;   // bytes that are decrypted
+        if (nested) {
+            M.st = M.cur_key ? M.key_b : M.key_a;
+            M.ar = M.at = 0;
+            const uint32_t nu = set_tag_bytes(M);
+            todo = (nu >= 1u && nu <= n) ? nu : 0u;   // (set_tag: nothing at all with no UID or a frame shorter than the UID)
+        }
+        bool bad = false;
+        uint32_t crc = 0x6363u, p1 = 0, p2 = 0, nonce = 0;
+        for (uint32_t i = 0; i < n; i++) {
+            const uint32_t b = bytes[i], p = par[i] & 1u;
+            enc[i] = (uint16_t)(b | (((frames::popc8(b) & 1u) == p) ? 0x100u : 0u));
+            uint32_t pt = 0;
+            if (i < todo) {
+                const uint32_t ub = nested ? uid_byte(M, i) : 0u;
+                const bool feed = nested || (nr_ar && i < 4u);
+                for (int k = 0; k < 8; k++) {
+                    const uint32_t f = filter(M.st), ct = (b >> k) & 1u;
+                    pt |= (ct ^ f) << k;
+                    M.st = shift_in(M.st, feed ? (ct ^ ((ub >> k) & 1u) ^ f) : 0u);
+                }
+                // the ninth bit reuses the keystream bit of the next data bit: the register does not move for it
+                if ((frames::popc8(pt) & 1u) == (p ^ filter(M.st))) bad = true;
+                if (i < 20u) B.put(i, pt);
+                if (i < 4u) nonce |= pt << (8u * i);
+                if (i >= 2u) crc = frames::crc_a_step(crc, p2);
+                p2 = p1;
+                p1 = pt;
+            }
+            data[i] = (uint8_t)pt;
+        }
+        nb = todo;
+        if (nested && todo) {
+            if (todo >= 4u) {   // 32 nonce bits were there: the answers are set even when the frame then fails its parity
+                M.ar = nonce_advance(nonce, 64);
+                M.at = nonce_advance(M.ar, 32);
+            } else {
+                nb = 0;
+            }
+            if (M.uid_len > todo) nb = 0;   // (a UID longer than set_tag takes: the host machine pads the plaintext with zero groups, which fail parity)
+        }
+        if (bad) nb = 0;
+        crc_ok = nb >= 2u && p2 == (crc & 0xFFu) && p1 == (crc >> 8);
+        if (nb == 0)
+            for (uint32_t i = 0; i < n; i++) data[i] = 0;
+    }
+    finish(M, nb, type, out, B, crc_ok);
+    return out;
+}
+
+// ---- Machine <-> nfc_fsm_state ----
+NFC_HD uint64_t key_of(const uint8_t k[6]) {
+    uint64_t v = 0;
+    for (int i = 0; i < 6; i++) v |= (uint64_t)k[i] << (8 * i);
+    return v;
+}
+NFC_HD void machine_from_state(Machine &M, const nfc_fsm_state &s) {
+    M.cur_cmd = s.cur_cmd, M.tag_type = s.tag_type, M.encrypted = s.encrypted, M.cur_key = s.cur_key;
+    M.st = s.cipher & ST_MASK;
+    M.key_a = key_of(s.key_a), M.key_b = key_of(s.key_b);
+    M.ar = (uint32_t)s.ar[0] | (uint32_t)s.ar[1] << 8 | (uint32_t)s.ar[2] << 16 | (uint32_t)s.ar[3] << 24;
+    M.at = (uint32_t)s.at[0] | (uint32_t)s.at[1] << 8 | (uint32_t)s.at[2] << 16 | (uint32_t)s.at[3] << 24;
+    M.flags = s.flags;
+    uid_clear(M);
+    M.uid_len = s.uid_len < UID_CAP ? s.uid_len : UID_CAP;
+    for (uint32_t i = 0; i < M.uid_len; i++) uid_put(M, i, s.uid[i]);
+}
+NFC_HD void machine_to_state(const Machine &M, nfc_fsm_state &s) {
+    s.cur_cmd = M.cur_cmd, s.tag_type = M.tag_type, s.encrypted = M.encrypted, s.cur_key = M.cur_key;
+    s.cipher = M.st;
+    for (int i = 0; i < 4; i++) s.ar[i] = (uint8_t)(M.ar >> (8 * i)), s.at[i] = (uint8_t)(M.at >> (8 * i));
+    for (int i = 0; i < 6; i++) s.key_a[i] = (uint8_t)(M.key_a >> (8 * i)), s.key_b[i] = (uint8_t)(M.key_b >> (8 * i));
+    s.uid_len = M.uid_len;
+    for (uint32_t i = 0; i < UID_CAP; i++) s.uid[i] = i < M.uid_len ? (uint8_t)uid_byte(M, i) : (uint8_t)0;
+    s.flags = M.flags;
+    s.reserved = 0;
+}
+// what is wrong with a caller's state, or null
+inline const char *state_fault(const nfc_fsm_state &s) {
+    if (s.cur_cmd < 0 || s.cur_cmd >= C_COUNT) return "cur_cmd out of range";
+    if (s.tag_type < -1 || s.tag_type > 3) return "tag_type out of range";
+    if (s.encrypted != 0 && s.encrypted != 1) return "encrypted must be 0 or 1";
+    if (s.cur_key != 0 && s.cur_key != 1) return "cur_key must be 0 or 1";
+    if (s.cipher >> 48) return "cipher holds more than 48 bits";
+    if (s.uid_len > UID_CAP) return "uid_len exceeds 32";
+    if (s.flags & ~(uint32_t)(NFC_FSM_LOST | NFC_FSM_UID_OVERFLOW)) return "unknown flags";
+    if (s.reserved != 0) return "reserved must be 0";
+    return nullptr;
+}
+
+// the machine as words, the layout of the device's [word][stream] arrays (multi_commands.hip.h) and of nothing else
+enum { W_CUR_CMD, W_TAG_TYPE, W_ENCRYPTED, W_CUR_KEY, W_ST_LO, W_ST_HI, W_AR, W_AT, W_KA_LO, W_KA_HI, W_KB_LO, W_KB_HI, W_UID_LEN, W_FLAGS,
+       W_UID0, W_WORDS = W_UID0 + 8 };
+
+}  // namespace fsmd
+}  // namespace nfc

@@ -1,0 +1,197 @@
+// multi_commands.hip.h -- k_multi_commands: the protocol machine of fsm.hip.h, a lane per stream, over the frames the assembly kernels
+// (nfc_frames.hip: launch_multi) left in the packed buffer; and what nfc_multi.hip reaches of nfc_commands.hip.
+//
+// 64 streams per workgroup, one wave, as k_multi (multi.hip.h).  The lane loads its stream's machine from the [word][stream] arrays,
+// walks the stream's two raw-frame lists with two pointers -- by idx, type 0 first on a tie: the order of api._merge_frames -- runs
+// every frame through fsmd::process_frame and stores the machine back.  No scan of its own: in the merged order stream k's commands
+// start at frame_off[0][k] + frame_off[1][k] and its byte slots at byte_off[0][k] + byte_off[1][k], both in the table
+// k_multi_frames_scan wrote; a frame's slot inside the stream is a running sum in the lane.  Lanes of one wave sit in different
+// branches of the lookup and in or out of a session: accepted, as k_multi accepts it in its decoders.
+//
+// The buffer: the frames' part as frames::MultiLayout lays it out, then the sections of Layout, each on 16 bytes and followed by
+// guard_bytes of the guard word.  Every range is cut to what the HOST laid out: the device's counts cannot write past a section.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/nfc_amd.h"
+#include "frames.hip.h"
+#include "fsm.hip.h"
+
+namespace nfc {
+namespace commands {
+
+enum { SEC_CMD_OFF, SEC_CBYTE_OFF, SEC_FLAGS, SEC_CMD, SEC_SRC, SEC_DATA, SEC_ENC, SEC_COUNT };
+struct Layout {
+    uint64_t at[SEC_COUNT], end[SEC_COUNT];   // section starts; where each section's guard starts
+    uint64_t total_cmds, total_bytes;         // the HOST's totals (total_bytes: the room of both byte sections of the frames)
+};
+struct Args {
+    frames::MultiArgs R;   // the frames' part: what launch_multi was given
+    uint32_t *state;       // [fsmd::W_WORDS][K]
+    Layout L;
+};
+constexpr int THREADS = 64;
+
+void launch(const Args &A, hipStream_t stream, hipEvent_t e0, hipEvent_t e1);
+// streams [k0, k1): the state of nfc_fsm_state_init / the two keys (48 bits, byte 0 lowest)
+void launch_init(uint32_t *state, uint32_t K, uint32_t k0, uint32_t k1, hipStream_t stream);
+void launch_set_keys(uint32_t *state, uint32_t K, uint32_t k0, uint32_t k1, uint64_t key_a, uint64_t key_b, hipStream_t stream);
+// one stream's machine to (set == 0) or from blob[0 .. W_WORDS)
+void launch_io(uint32_t *state, uint32_t K, uint32_t k, int set, uint32_t *blob, hipStream_t stream);
+
+#ifdef NFC_COMMANDS_KERNELS
+__device__ __forceinline__ void load_machine(fsmd::Machine &M, const uint32_t *__restrict__ s, size_t K, size_t k) {
+    using namespace fsmd;
+    M.cur_cmd = (int32_t)s[W_CUR_CMD * K + k];
+    M.tag_type = (int32_t)s[W_TAG_TYPE * K + k];
+    M.encrypted = (int32_t)s[W_ENCRYPTED * K + k];
+    M.cur_key = (int32_t)s[W_CUR_KEY * K + k];
+    M.st = (uint64_t)s[W_ST_LO * K + k] | (uint64_t)s[W_ST_HI * K + k] << 32;
+    M.ar = s[W_AR * K + k];
+    M.at = s[W_AT * K + k];
+    M.key_a = (uint64_t)s[W_KA_LO * K + k] | (uint64_t)s[W_KA_HI * K + k] << 32;
+    M.key_b = (uint64_t)s[W_KB_LO * K + k] | (uint64_t)s[W_KB_HI * K + k] << 32;
+    M.uid_len = s[W_UID_LEN * K + k];
+    M.flags = s[W_FLAGS * K + k];
+    M.u0 = s[(W_UID0 + 0) * K + k], M.u1 = s[(W_UID0 + 1) * K + k], M.u2 = s[(W_UID0 + 2) * K + k], M.u3 = s[(W_UID0 + 3) * K + k];
+    M.u4 = s[(W_UID0 + 4) * K + k], M.u5 = s[(W_UID0 + 5) * K + k], M.u6 = s[(W_UID0 + 6) * K + k], M.u7 = s[(W_UID0 + 7) * K + k];
+    // (a machine is only ever written by store_machine, launch_init and a checked nfc_fsm_state; still, nothing below may index by these)
+    if ((uint32_t)M.cur_cmd >= (uint32_t)C_COUNT) M.cur_cmd = C_REQA;
+    if (M.uid_len > UID_CAP) M.uid_len = UID_CAP;
+    M.st &= ST_MASK;
+}
+__device__ __forceinline__ void store_machine(const fsmd::Machine &M, uint32_t *__restrict__ s, size_t K, size_t k) {
+    using namespace fsmd;
+    s[W_CUR_CMD * K + k] = (uint32_t)M.cur_cmd;
+    s[W_TAG_TYPE * K + k] = (uint32_t)M.tag_type;
+    s[W_ENCRYPTED * K + k] = (uint32_t)M.encrypted;
+    s[W_CUR_KEY * K + k] = (uint32_t)M.cur_key;
+    s[W_ST_LO * K + k] = (uint32_t)M.st;
+    s[W_ST_HI * K + k] = (uint32_t)(M.st >> 32);
+    s[W_AR * K + k] = M.ar;
+    s[W_AT * K + k] = M.at;
+    s[W_KA_LO * K + k] = (uint32_t)M.key_a;
+    s[W_KA_HI * K + k] = (uint32_t)(M.key_a >> 32);
+    s[W_KB_LO * K + k] = (uint32_t)M.key_b;
+    s[W_KB_HI * K + k] = (uint32_t)(M.key_b >> 32);
+    s[W_UID_LEN * K + k] = M.uid_len;
+    s[W_FLAGS * K + k] = M.flags;
+    s[(W_UID0 + 0) * K + k] = M.u0, s[(W_UID0 + 1) * K + k] = M.u1, s[(W_UID0 + 2) * K + k] = M.u2, s[(W_UID0 + 3) * K + k] = M.u3;
+    s[(W_UID0 + 4) * K + k] = M.u4, s[(W_UID0 + 5) * K + k] = M.u5, s[(W_UID0 + 6) * K + k] = M.u6, s[(W_UID0 + 7) * K + k] = M.u7;
+}
+
+__global__ __launch_bounds__(THREADS) void k_multi_commands(Args A) {
+    const frames::MultiArgs &R = A.R;
+    const Layout &L = A.L;
+    uint8_t *__restrict__ buf = R.packed;
+    if (blockIdx.x == 0)
+        for (uint32_t i = threadIdx.x; i < (uint32_t)SEC_COUNT * R.guard_bytes; i += THREADS) {
+            const uint32_t s = i / R.guard_bytes, b = i % R.guard_bytes;
+            buf[L.end[s] + b] = (uint8_t)(R.guard_word >> (8 * (b & 3u)));
+        }
+    const uint32_t K = R.K, k = blockIdx.x * THREADS + threadIdx.x;
+    if (k >= K) return;
+    const size_t T = (size_t)K + 1;
+    const uint64_t *__restrict__ tab = R.table;
+    // the stream's raw frames per type, cut to the sections as the assembly cut them (named per type: no array a lane would index)
+    uint32_t nfr0, nfr1;
+    const nfc_raw_frame *rec0, *rec1;
+    const uint8_t *rb0, *rb1, *rp0, *rp1;
+    uint64_t room0, room1;   // bytes of the type's section from the stream's first on
+#define NFC_STREAM_PART(t, nfr, rec, rb, rp, room)                                     \
+    {                                                                                  \
+        uint64_t fe = tab[(size_t)t * T + k + 1], fb = tab[(size_t)t * T + k];         \
+        fe = fe < R.F.total_frames[t] ? fe : R.F.total_frames[t];                      \
+        fb = fb < fe ? fb : fe;                                                        \
+        uint64_t bb = tab[(size_t)(2 + t) * T + k];                                    \
+        bb = bb < R.F.total_bytes[t] ? bb : R.F.total_bytes[t];                        \
+        nfr = (uint32_t)(fe - fb);                                                     \
+        rec = (const nfc_raw_frame *)(buf + R.F.at_fr[t]) + fb;                        \
+        rb = buf + R.F.at_bytes[t] + bb;                                               \
+        rp = buf + R.F.at_par[t] + bb;                                                 \
+        room = R.F.total_bytes[t] - bb;                                                \
+    }
+    NFC_STREAM_PART(0, nfr0, rec0, rb0, rp0, room0)
+    NFC_STREAM_PART(1, nfr1, rec1, rb1, rp1, room1)
+#undef NFC_STREAM_PART
+    const uint64_t c0 = tab[0 * T + k] + tab[1 * T + k], b0 = tab[2 * T + k] + tab[3 * T + k];
+    uint64_t *cmd_off = (uint64_t *)(buf + L.at[SEC_CMD_OFF]), *cbyte_off = (uint64_t *)(buf + L.at[SEC_CBYTE_OFF]);
+    cmd_off[k] = c0;
+    cbyte_off[k] = b0;
+    if (k == K - 1u) {
+        cmd_off[K] = tab[0 * T + K] + tab[1 * T + K];
+        cbyte_off[K] = tab[2 * T + K] + tab[3 * T + K];
+    }
+    fsmd::Machine M;
+    load_machine(M, A.state, K, k);
+    {   // what the slabs did not store is lost to the machine
+        const uint32_t *c = R.counts + (size_t)k * R.cnt_words;
+        if (c[R.cnt_pk0] > R.cap_packets || c[R.cnt_pk0 + 1] > R.cap_packets || c[R.cnt_bits0] > R.cap_bits || c[R.cnt_bits0 + 1] > R.cap_bits)
+            M.flags |= NFC_FSM_LOST;
+    }
+    uint32_t *__restrict__ out_cmd = (uint32_t *)(buf + L.at[SEC_CMD]);
+    uint32_t *__restrict__ out_src = (uint32_t *)(buf + L.at[SEC_SRC]);
+    uint8_t *__restrict__ out_data = buf + L.at[SEC_DATA];
+    uint16_t *__restrict__ out_enc = (uint16_t *)(buf + L.at[SEC_ENC]);
+    uint32_t i0 = 0, i1 = 0, run = 0;
+    while (i0 < nfr0 || i1 < nfr1) {
+        int t;
+        if (i1 >= nfr1) t = 0;
+        else if (i0 >= nfr0) t = 1;
+        else t = rec0[i0].idx <= rec1[i1].idx ? 0 : 1;
+        const uint32_t i = t ? i1 : i0;
+        const uint4 *q = (const uint4 *)(t ? rec1 + i1 : rec0 + i0);
+        const uint4 q0 = q[0], q1 = q[1];
+        uint32_t byte_off = q0.z, n = q1.x, flags = q1.y;
+        const uint8_t *rbt = t ? rb1 : rb0, *rpt = t ? rp1 : rp0;
+        const uint64_t roomt = t ? room1 : room0;
+        const uint64_t c = c0 + i0 + i1;
+        if (c >= L.total_cmds) break;   // (never: the host's total is the sum of the streams' frames)
+        // (never: a frame's bytes lie inside its type's section, its slot inside the host's room)
+        if ((uint64_t)byte_off + n > roomt || b0 + run + n > L.total_bytes) flags = NFC_RAW_CUT;
+        if (flags & NFC_RAW_CUT) n = 0;
+        const fsmd::Rec r = fsmd::process_frame(M, t, flags, n, rbt + byte_off, rpt + byte_off, out_data + b0 + run, out_enc + b0 + run);
+        uint32_t *w = out_cmd + c * (sizeof(nfc_frame) / 4);
+        w[0] = (uint32_t)r.cmd;
+        w[1] = (uint32_t)r.type;
+        w[2] = run;
+        w[3] = r.n_bytes | r.n_header << 16;
+        w[4] = r.n_extra | r.n_crc << 16;
+        w[5] = r.flags;
+        w[6] = r.n_enc;
+        out_src[c] = (uint32_t)t << 31 | i;
+        run += n;
+        if (t) i1++;
+        else i0++;
+    }
+    ((uint32_t *)(buf + L.at[SEC_FLAGS]))[k] = M.flags;
+    store_machine(M, A.state, K, k);
+}
+
+__global__ __launch_bounds__(256) void k_commands_init(uint32_t *state, uint32_t K, uint32_t k0, uint32_t k1) {
+    const uint32_t k = k0 + blockIdx.x * 256 + threadIdx.x;
+    if (k >= k1 || k >= K) return;
+    fsmd::Machine M;
+    fsmd::machine_init(M);
+    store_machine(M, state, K, k);
+}
+__global__ __launch_bounds__(256) void k_commands_set_keys(uint32_t *state, uint32_t K, uint32_t k0, uint32_t k1, uint64_t key_a, uint64_t key_b) {
+    using namespace fsmd;
+    const size_t k = (size_t)k0 + blockIdx.x * 256 + threadIdx.x;
+    if (k >= k1 || k >= K) return;
+    state[W_KA_LO * (size_t)K + k] = (uint32_t)key_a;
+    state[W_KA_HI * (size_t)K + k] = (uint32_t)(key_a >> 32);
+    state[W_KB_LO * (size_t)K + k] = (uint32_t)key_b;
+    state[W_KB_HI * (size_t)K + k] = (uint32_t)(key_b >> 32);
+}
+__global__ __launch_bounds__(64) void k_commands_io(uint32_t *state, uint32_t K, uint32_t k, int set, uint32_t *blob) {
+    const uint32_t w = threadIdx.x;
+    if (w >= (uint32_t)fsmd::W_WORDS || k >= K) return;
+    if (set) state[(size_t)w * K + k] = blob[w];
+    else blob[w] = state[(size_t)w * K + k];
+}
+#endif   // NFC_COMMANDS_KERNELS
+
+}  // namespace commands
+}  // namespace nfc

@@ -24,6 +24,7 @@
 #include "multi.hip.h"
 #include "multi_fetch.hip.h"
 #include "frames.hip.h"   // (the frame assembly kernels: nfc_frames.hip)
+#include "multi_commands.hip.h"   // (the protocol machine a lane per stream: nfc_commands.hip)
 #include "input_kind.h"
 
 using namespace nfc;
@@ -36,6 +37,7 @@ static_assert(F_EDGES == NFC_MULTI_TRUNC_EDGES && F_SYMBOLS == NFC_MULTI_TRUNC_S
 static_assert(MF_EDGES == NFC_MULTI_FETCH_EDGES && MF_SYMBOLS == NFC_MULTI_FETCH_SYMBOLS && MF_PACKETS == NFC_MULTI_FETCH_PACKETS &&
                   MF_ARRAYS == NFC_MF_ARRAYS && sizeof(nfc_packet) == 24 && sizeof(nfc_multi_stats) == 64,
               "the fetch kernels' arrays and records are the header's");
+static_assert(sizeof(nfc_multi_frames) == 144 && sizeof(nfc_multi_commands) == 264 && sizeof(nfc_frame) == 28, "the commands' structures are the header's");
 
 struct nfc_multi {
     nfc_params P;
@@ -78,6 +80,20 @@ struct nfc_multi {
     size_t d_frames_cap = 0, h_frames_cap = 0;
     frames::MultiLayout frlay;
     bool frames_guarded = false;
+    // command tracking (multi_commands.hip.h): the machines' words on the device, allocated when tracking is first asked for; the
+    // buffer every tracked push fills -- the frames' part, then the commands' sections -- and its pinned twin, followed by base[K]
+    enum CmdState { CMD_NONE, CMD_EMPTY, CMD_LAUNCHED };   // of the last push: not tracked (or reset since) / nothing stored / three launches
+    bool track = false;
+    uint32_t *d_fsm = nullptr, *d_fsm_blob = nullptr, *h_fsm_blob = nullptr;
+    uint8_t *d_cmd = nullptr, *h_cmd = nullptr;
+    size_t d_cmd_cap = 0, h_cmd_cap = 0, cmd_bytes = 0;
+    CmdState cmd_state = CMD_NONE;
+    bool cmd_fetched = false, cmd_guarded = false, cmd_timed = false;
+    frames::MultiLayout cmd_frlay;
+    commands::Layout cmd_lay;
+    uint64_t cmd_nfr[2] = {0, 0}, cmd_room[2] = {0, 0};
+    hipEvent_t evc[4] = {nullptr, nullptr, nullptr, nullptr};
+    nfc_multi_commands cout;
     nfc_multi_stats stats;
     std::string err;
     LaunchError launch_err;
@@ -263,6 +279,168 @@ int read_fetched(nfc_multi *m, int a, const uint8_t *section, uint32_t stream, s
     return NFC_OK;
 }
 
+// ---- the frames' packed buffer: totals (64 bytes) | table [4][K + 1] | records 0 | records 1 | bytes 0 | bytes 1 | par 0 | par 1 ----
+// The host knows every stream's frame count from its mirror of the counts, not its byte count (that takes the close rows): the byte
+// sections are laid out for the most the stored bits can give -- a frame has at most (n_bits + 1) / 9 bytes.  Returns the bytes used.
+size_t frames_layout(const nfc_multi *m, frames::MultiLayout &F, uint64_t n_fr[2], uint64_t room[2]) {
+    const size_t T = (size_t)m->K + 1;
+    n_fr[0] = n_fr[1] = room[0] = room[1] = 0;
+    for (uint32_t k = 0; k < m->K; k++) {
+        const uint32_t *c = m->h_counts + (size_t)k * CNT_WORDS;
+        for (int t = 0; t < 2; t++) {
+            const uint64_t npk = std::min(c[CNT_PK0 + t], m->C.packets), bits = std::min(c[CNT_BITS0 + t], m->C.bits);
+            n_fr[t] += npk;
+            room[t] += npk ? (bits + npk) / 9 : 0;
+        }
+    }
+    memset(&F, 0, sizeof F);
+    size_t at = up16(frames::MULTI_HEADER_BYTES + 4 * T * 8);
+    for (int t = 0; t < 2; t++) {
+        F.at_fr[t] = at;
+        F.end_fr[t] = at + n_fr[t] * sizeof(nfc_raw_frame);
+        at = up16(F.end_fr[t] + GUARD_BYTES);
+        F.total_frames[t] = n_fr[t];
+        F.total_bytes[t] = room[t];
+    }
+    for (int t = 0; t < 2; t++) {
+        F.at_bytes[t] = at;
+        F.end_bytes[t] = at + room[t];
+        at = up16(F.end_bytes[t] + GUARD_BYTES);
+    }
+    for (int t = 0; t < 2; t++) {
+        F.at_par[t] = at;
+        F.end_par[t] = at + room[t];
+        at = up16(F.end_par[t] + GUARD_BYTES);
+    }
+    return at;
+}
+frames::MultiArgs frames_args(const nfc_multi *m, uint8_t *packed, const frames::MultiLayout &F) {
+    frames::MultiArgs A;
+    memset(&A, 0, sizeof A);
+    for (int t = 0; t < 2; t++) {
+        A.close[t] = m->A.O.close[t];
+        A.bits[t] = m->A.O.bits[t];
+    }
+    A.counts = m->A.O.counts;
+    A.cnt_words = CNT_WORDS, A.cnt_pk0 = CNT_PK0, A.cnt_bits0 = CNT_BITS0;
+    A.cap_packets = m->C.packets, A.cap_bits = m->C.bits, A.s_packets = m->C.s_packets, A.s_bits = m->C.s_bits;
+    A.K = m->K;
+    A.table = (uint64_t *)(packed + frames::MULTI_HEADER_BYTES);
+    A.packed = packed;
+    A.guard_word = GUARD_WORD, A.guard_bytes = GUARD_BYTES;
+    A.F = F;
+    return A;
+}
+// what the caller gets of the frames' part of a host copy `h` (fetch_frames, fetch_commands): pointers, and idx in the stream's own count
+void frames_view(const nfc_multi *m, uint8_t *h, const frames::MultiLayout &F, const uint64_t *base, bool stored, nfc_multi_frames &f) {
+    const uint32_t K = m->K;
+    const size_t T = (size_t)K + 1;
+    uint64_t *tab = (uint64_t *)(h + frames::MULTI_HEADER_BYTES);
+    if (stored) {
+        bool based = false;
+        for (uint32_t k = 0; k < K; k++) based = based || base[k] != 0;
+        for (int t = 0; t < 2; t++) {
+            f.frames[t] = (const nfc_raw_frame *)(h + F.at_fr[t]);
+            f.bytes[t] = h + F.at_bytes[t];
+            f.par[t] = h + F.at_par[t];
+        }
+        if (based)   // (the device left idx batch-local: the stream's base is added here, over the few frames there are)
+            for (int t = 0; t < 2; t++) {
+                nfc_raw_frame *fr = (nfc_raw_frame *)(h + F.at_fr[t]);
+                const uint64_t *off = tab + (size_t)t * T;
+                for (uint32_t k = 0; k < K; k++)
+                    for (uint64_t i = off[k]; i < off[k + 1]; i++) fr[i].idx += base[k];
+            }
+    } else {
+        memset(tab, 0, 4 * T * 8);
+    }
+    for (int t = 0; t < 2; t++) {
+        f.frame_off[t] = tab + (size_t)t * T;
+        f.byte_off[t] = tab + (size_t)(2 + t) * T;
+    }
+    f.base = base;
+}
+
+// ---- command tracking ----
+// the machines' words, the blob of one machine and the events, when tracking, keys or a machine's state are first asked for: a context that
+// never does allocates and launches what it always did
+int ensure_fsm(nfc_multi *m) {
+    if (m->d_fsm) return NFC_OK;
+    uint32_t *d = nullptr, *db = nullptr, *hb = nullptr;
+    if (hipMalloc((void **)&d, (size_t)fsmd::W_WORDS * m->K * 4) != hipSuccess || hipMalloc((void **)&db, 256) != hipSuccess ||
+        hipHostMalloc((void **)&hb, 256, hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        if (d) (void)hipFree(d);
+        if (db) (void)hipFree(db);
+        return mfail(m, NFC_ERR_NOMEM, "no memory for the protocol machines of %u streams", m->K);
+    }
+    for (hipEvent_t &e : m->evc)
+        if (hipEventCreate(&e) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipFree(d), (void)hipFree(db), (void)hipHostFree(hb);
+            return mfail(m, NFC_ERR_DEVICE, "hipEventCreate failed");
+        }
+    m->d_fsm = d, m->d_fsm_blob = db, m->h_fsm_blob = hb;
+    commands::launch_init(m->d_fsm, m->K, 0, m->K, m->st);
+    return launch_ok(m);
+}
+
+// the three launches of a tracked push, behind the push's own kernel and its counts; no host wait
+int enqueue_commands(nfc_multi *m) {
+    m->cmd_state = nfc_multi::CMD_NONE;
+    m->cmd_fetched = false;
+    if (int rc = ensure_fsm(m)) return rc;
+    frames::MultiLayout F;
+    const size_t fr_bytes = frames_layout(m, F, m->cmd_nfr, m->cmd_room);
+    if (m->cmd_nfr[0] + m->cmd_nfr[1] == 0) {   // (the buffer, its layouts and its guards stay those of the last push that stored anything)
+        m->cmd_state = nfc_multi::CMD_EMPTY;
+        return NFC_OK;
+    }
+    m->cmd_frlay = F;
+    const uint32_t K = m->K;
+    const size_t T = (size_t)K + 1;
+    commands::Layout &L = m->cmd_lay;
+    memset(&L, 0, sizeof L);
+    L.total_cmds = m->cmd_nfr[0] + m->cmd_nfr[1];
+    L.total_bytes = m->cmd_room[0] + m->cmd_room[1];
+    const size_t sizes[commands::SEC_COUNT] = {T * 8, T * 8, (size_t)K * 4, (size_t)L.total_cmds * sizeof(nfc_frame), (size_t)L.total_cmds * 4,
+                                               (size_t)L.total_bytes, (size_t)L.total_bytes * 2};
+    size_t at = fr_bytes;
+    for (int s = 0; s < commands::SEC_COUNT; s++) {
+        L.at[s] = at;
+        L.end[s] = at + sizes[s];
+        at = up16(L.end[s] + GUARD_BYTES);
+    }
+    const size_t bytes = at;
+    if (m->d_cmd_cap < bytes) {
+        if (m->d_cmd) (void)hipFree(m->d_cmd);
+        m->d_cmd = nullptr;
+        m->d_cmd_cap = 0;
+        m->cmd_guarded = false;
+        const size_t cap = bytes + bytes / 2 + 4096;
+        if (hipMalloc((void **)&m->d_cmd, cap) != hipSuccess) {
+            (void)hipGetLastError();
+            m->d_cmd = nullptr;
+            return mfail(m, NFC_ERR_NOMEM, "command tracking: no device memory for %zu bytes", cap);
+        }
+        m->d_cmd_cap = cap;
+    }
+    commands::Args A;
+    A.R = frames_args(m, m->d_cmd, F);
+    A.state = m->d_fsm;
+    A.L = L;
+    const bool timed = m->timing != 0;
+    frames::launch_multi(A.R, m->st, timed ? m->evc[0] : nullptr, timed ? m->evc[1] : nullptr);
+    commands::launch(A, m->st, timed ? m->evc[2] : nullptr, timed ? m->evc[3] : nullptr);
+    m->cmd_timed = timed;
+    m->cmd_bytes = bytes;
+    m->cmd_guarded = true;
+    if (int rc = launch_ok(m)) return rc;
+    m->cmd_state = nfc_multi::CMD_LAUNCHED;
+    m->stats.n_launches += 3;
+    return NFC_OK;
+}
+
 int state_io(nfc_multi *m, uint32_t k, int set) {
     NFC_LAUNCH(k_multi_state_io, dim3(1), dim3(256), 0, m->st, m->A.S, m->C, m->K, k, m->L, set, m->d_blob);
     return launch_ok(m);
@@ -283,6 +461,12 @@ void nfc_multi_destroy(nfc_multi *m) {
     if (m->d_ftable) (void)hipFree(m->d_ftable);
     if (m->d_frames) (void)hipFree(m->d_frames);
     if (m->h_frames) (void)hipHostFree(m->h_frames);
+    for (void *p : {(void *)m->d_fsm, (void *)m->d_fsm_blob, (void *)m->d_cmd})
+        if (p) (void)hipFree(p);
+    for (void *p : {(void *)m->h_fsm_blob, (void *)m->h_cmd})
+        if (p) (void)hipHostFree(p);
+    for (hipEvent_t e : m->evc)
+        if (e) (void)hipEventDestroy(e);
     for (uint8_t *p : {m->h_up, (uint8_t *)m->h_counts, m->h_blob, m->h_stage, m->h_read, m->h_fetch, (uint8_t *)m->h_ftable})
         if (p) (void)hipHostFree(p);
     for (hipEvent_t e : m->ev)
@@ -332,6 +516,7 @@ int nfc_multi_create(const nfc_params *p, const nfc_multi_config *c, nfc_multi *
     memset(&m->stats, 0, sizeof m->stats);
     memset(&m->fout, 0, sizeof m->fout);
     memset(&m->flay, 0, sizeof m->flay);
+    memset(&m->cout, 0, sizeof m->cout);
     const uint32_t K = m->K;
     // Capacities per stream and push.  Entries are 6-13 % of the samples on every capture of this tree's generators (the densest:
     // 0.133 edges and 0.10 symbols of one type per sample): a quarter of the samples is room to spare.  A non-empty packet takes a
@@ -523,6 +708,9 @@ int nfc_multi_push_device(nfc_multi *m, const void *dev_base, const uint64_t *fi
     m->stats.n_launches = 1;
     m->stats.n_streams_truncated = cut;
     m->stats.n_fetches = m->stats.n_reads_device = 0;
+    m->cmd_state = nfc_multi::CMD_NONE;
+    m->cmd_fetched = false;
+    if (m->track) return enqueue_commands(m);
     return NFC_OK;
 }
 
@@ -714,51 +902,21 @@ int nfc_multi_fetch(nfc_multi *m, uint32_t what, nfc_multi_fetched *out) {
     return NFC_OK;
 }
 
-// The frames of every stream's stored packets, assembled on the device into one packed buffer (frames.hip.h):
-//     totals (64 bytes) | table [4][K + 1] | records 0 | records 1 | bytes 0 | bytes 1 | par 0 | par 1
-// each section on 16 bytes with GUARD_BYTES of the guard word behind it.  The host knows every stream's frame count from its mirror of
-// the counts, not its byte count (that takes the close rows): the byte sections are laid out for the most the stored bits can give --
-// a frame has at most (n_bits + 1) / 9 bytes -- and the device's table, which travels in the buffer, says where a stream's bytes are.
+// The frames of every stream's stored packets, assembled on the device into one packed buffer (frames.hip.h; frames_layout above: each
+// section on 16 bytes with GUARD_BYTES of the guard word behind it); the device's table, which travels in the buffer, says where a
+// stream's bytes are.
 int nfc_multi_fetch_frames(nfc_multi *m, nfc_multi_frames *out) {
     if (!m) return NFC_ERR_ARG;
     LaunchScope scope(&m->launch_err);
     if (!m->have_outputs) return mfail(m, NFC_ERR_STATE, "no completed push");
     if (hipSetDevice(m->P.device) != hipSuccess) return mfail(m, NFC_ERR_DEVICE, "hipSetDevice failed");
     const uint32_t K = m->K;
-    const size_t T = (size_t)K + 1;
-    uint64_t n_fr[2] = {0, 0}, room[2] = {0, 0};
-    for (uint32_t k = 0; k < K; k++) {
-        const uint32_t *c = m->h_counts + (size_t)k * CNT_WORDS;
-        for (int t = 0; t < 2; t++) {
-            const uint64_t npk = std::min(c[CNT_PK0 + t], m->C.packets), bits = std::min(c[CNT_BITS0 + t], m->C.bits);
-            n_fr[t] += npk;
-            room[t] += npk ? (bits + npk) / 9 : 0;
-        }
-    }
+    uint64_t n_fr[2], room[2];
     nfc_multi_frames f;
     memset(&f, 0, sizeof f);
     f.n_streams = K;
     frames::MultiLayout F;
-    memset(&F, 0, sizeof F);
-    size_t at = up16(frames::MULTI_HEADER_BYTES + 4 * T * 8);
-    for (int t = 0; t < 2; t++) {
-        F.at_fr[t] = at;
-        F.end_fr[t] = at + n_fr[t] * sizeof(nfc_raw_frame);
-        at = up16(F.end_fr[t] + GUARD_BYTES);
-        F.total_frames[t] = n_fr[t];
-        F.total_bytes[t] = room[t];
-    }
-    for (int t = 0; t < 2; t++) {
-        F.at_bytes[t] = at;
-        F.end_bytes[t] = at + room[t];
-        at = up16(F.end_bytes[t] + GUARD_BYTES);
-    }
-    for (int t = 0; t < 2; t++) {
-        F.at_par[t] = at;
-        F.end_par[t] = at + room[t];
-        at = up16(F.end_par[t] + GUARD_BYTES);
-    }
-    const size_t bytes = at, host_bytes = bytes + (size_t)K * 8;
+    const size_t bytes = frames_layout(m, F, n_fr, room), host_bytes = bytes + (size_t)K * 8;
     // (the pinned buffer always: the offset tables and base[] are handed out when nothing was stored, too)
     if (m->h_frames_cap < host_bytes) {
         if (m->h_frames) (void)hipHostFree(m->h_frames);
@@ -773,12 +931,8 @@ int nfc_multi_fetch_frames(nfc_multi *m, nfc_multi_frames *out) {
         m->h_frames_cap = cap;
     }
     uint8_t *h = m->h_frames;
-    uint64_t *tab = (uint64_t *)(h + frames::MULTI_HEADER_BYTES), *base = (uint64_t *)(h + bytes);
-    bool based = false;
-    for (uint32_t k = 0; k < K; k++) {
-        base[k] = m->g0[k];
-        based = based || m->g0[k] != 0;
-    }
+    uint64_t *base = (uint64_t *)(h + bytes);
+    for (uint32_t k = 0; k < K; k++) base[k] = m->g0[k];
     if (n_fr[0] + n_fr[1]) {
         if (m->d_frames_cap < bytes) {
             if (m->d_frames) (void)hipFree(m->d_frames);
@@ -793,20 +947,7 @@ int nfc_multi_fetch_frames(nfc_multi *m, nfc_multi_frames *out) {
             }
             m->d_frames_cap = cap;
         }
-        frames::MultiArgs A;
-        memset(&A, 0, sizeof A);
-        for (int t = 0; t < 2; t++) {
-            A.close[t] = m->A.O.close[t];
-            A.bits[t] = m->A.O.bits[t];
-        }
-        A.counts = m->A.O.counts;
-        A.cnt_words = CNT_WORDS, A.cnt_pk0 = CNT_PK0, A.cnt_bits0 = CNT_BITS0;
-        A.cap_packets = m->C.packets, A.cap_bits = m->C.bits, A.s_packets = m->C.s_packets, A.s_bits = m->C.s_bits;
-        A.K = K;
-        A.table = (uint64_t *)(m->d_frames + frames::MULTI_HEADER_BYTES);
-        A.packed = m->d_frames;
-        A.guard_word = GUARD_WORD, A.guard_bytes = GUARD_BYTES;
-        A.F = F;
+        const frames::MultiArgs A = frames_args(m, m->d_frames, F);
         frames::launch_multi(A, m->st, m->timing ? m->ev[0] : nullptr, m->timing ? m->ev[1] : nullptr);
         m->frlay = F;
         m->frames_guarded = true;
@@ -825,26 +966,8 @@ int nfc_multi_fetch_frames(nfc_multi *m, nfc_multi_frames *out) {
         }
         f.n_launches = 2;
         f.bytes_copied = bytes;
-        for (int t = 0; t < 2; t++) {
-            f.frames[t] = (const nfc_raw_frame *)(h + F.at_fr[t]);
-            f.bytes[t] = h + F.at_bytes[t];
-            f.par[t] = h + F.at_par[t];
-        }
-        if (based)   // (the device left idx batch-local: the stream's base is added here, over the few frames there are)
-            for (int t = 0; t < 2; t++) {
-                nfc_raw_frame *fr = (nfc_raw_frame *)(h + F.at_fr[t]);
-                const uint64_t *off = tab + (size_t)t * T;
-                for (uint32_t k = 0; k < K; k++)
-                    for (uint64_t i = off[k]; i < off[k + 1]; i++) fr[i].idx += base[k];
-            }
-    } else {
-        memset(tab, 0, 4 * T * 8);
     }
-    for (int t = 0; t < 2; t++) {
-        f.frame_off[t] = tab + (size_t)t * T;
-        f.byte_off[t] = tab + (size_t)(2 + t) * T;
-    }
-    f.base = base;
+    frames_view(m, h, F, base, n_fr[0] + n_fr[1] != 0, f);
     if (out) *out = f;
     return NFC_OK;
 }
@@ -1012,6 +1135,8 @@ int nfc_multi_set_state(nfc_multi *m, uint32_t stream, const nfc_state_header *h
     if (int rc = state_io(m, stream, 1)) return rc;
     // the stream's outputs of the last push are void: its counts go to 0 on the device as in the mirror (a later fetch scans them)
     m->fetched = 0;
+    m->cmd_state = nfc_multi::CMD_NONE;   // (the commands of the last push go with its outputs; the machine itself is not touched)
+    m->cmd_fetched = false;
     MCHK(m, hipMemsetAsync(m->A.O.counts + (size_t)stream * CNT_WORDS, 0, CNT_WORDS * 4, m->st));
     MCHK(m, hipStreamSynchronize(m->st));
     m->nseen[stream] = h->n_seen;
@@ -1030,6 +1155,9 @@ int nfc_multi_reset(nfc_multi *m, int64_t stream) {
     const uint32_t k0 = stream < 0 ? 0u : (uint32_t)stream, k1 = stream < 0 ? m->K : (uint32_t)stream + 1u;
     const size_t work = (size_t)(k1 - k0) * (size_t)m->L;
     NFC_LAUNCH(k_multi_reset, dim3((unsigned)std::min<size_t>(1024, (work + 255) / 256)), dim3(256), 0, m->st, m->A.S, m->K, k0, k1, m->L, m->A.O.counts);
+    if (m->d_fsm) commands::launch_init(m->d_fsm, m->K, k0, k1, m->st);   // the machines too, keys included, as nfc_fsm_reset
+    m->cmd_state = nfc_multi::CMD_NONE;
+    m->cmd_fetched = false;
     if (int rc = launch_ok(m)) return rc;
     MCHK(m, hipStreamSynchronize(m->st));
     for (uint32_t k = k0; k < k1; k++) {
@@ -1038,6 +1166,170 @@ int nfc_multi_reset(nfc_multi *m, int64_t stream) {
         memset(m->h_counts + (size_t)k * CNT_WORDS, 0, CNT_WORDS * 4);
     }
     if (stream < 0) m->have_outputs = false;
+    return NFC_OK;
+}
+
+// ---- commands (multi_commands.hip.h) ----
+int nfc_multi_track_commands(nfc_multi *m, int on) {
+    if (!m) return NFC_ERR_ARG;
+    LaunchScope scope(&m->launch_err);
+    if (on) {
+        if (hipSetDevice(m->P.device) != hipSuccess) return mfail(m, NFC_ERR_DEVICE, "hipSetDevice failed");
+        if (int rc = ensure_fsm(m)) return rc;
+    }
+    m->track = on != 0;
+    return NFC_OK;
+}
+
+int nfc_multi_set_keys(nfc_multi *m, int64_t stream, const uint8_t key_a[6], const uint8_t key_b[6]) {
+    if (!m) return NFC_ERR_ARG;
+    LaunchScope scope(&m->launch_err);
+    if (stream < -1 || stream >= (int64_t)m->K) return mfail(m, NFC_ERR_ARG, "stream %lld out of range (n_streams %u)", (long long)stream, m->K);
+    if (!key_a) return mfail(m, NFC_ERR_ARG, "key_a is null");
+    if (!key_b) return mfail(m, NFC_ERR_ARG, "key_b is null");
+    if (hipSetDevice(m->P.device) != hipSuccess) return mfail(m, NFC_ERR_DEVICE, "hipSetDevice failed");
+    if (int rc = ensure_fsm(m)) return rc;
+    const uint32_t k0 = stream < 0 ? 0u : (uint32_t)stream, k1 = stream < 0 ? m->K : (uint32_t)stream + 1u;
+    commands::launch_set_keys(m->d_fsm, m->K, k0, k1, fsmd::key_of(key_a), fsmd::key_of(key_b), m->st);
+    return launch_ok(m);
+}
+
+int nfc_multi_get_fsm_state(nfc_multi *m, uint32_t stream, nfc_fsm_state *st) {
+    if (!m) return NFC_ERR_ARG;
+    LaunchScope scope(&m->launch_err);
+    if (stream >= m->K) return mfail(m, NFC_ERR_ARG, "stream %u out of range (n_streams %u)", stream, m->K);
+    if (!st) return mfail(m, NFC_ERR_ARG, "st is null");
+    if (hipSetDevice(m->P.device) != hipSuccess) return mfail(m, NFC_ERR_DEVICE, "hipSetDevice failed");
+    if (int rc = ensure_fsm(m)) return rc;
+    commands::launch_io(m->d_fsm, m->K, stream, 0, m->d_fsm_blob, m->st);
+    if (int rc = launch_ok(m)) return rc;
+    MCHK(m, hipMemcpyAsync(m->h_fsm_blob, m->d_fsm_blob, fsmd::W_WORDS * 4, hipMemcpyDeviceToHost, m->st));
+    MCHK(m, hipStreamSynchronize(m->st));
+    const uint32_t *w = m->h_fsm_blob;
+    fsmd::Machine M;
+    M.cur_cmd = (int32_t)w[fsmd::W_CUR_CMD], M.tag_type = (int32_t)w[fsmd::W_TAG_TYPE], M.encrypted = (int32_t)w[fsmd::W_ENCRYPTED];
+    M.cur_key = (int32_t)w[fsmd::W_CUR_KEY];
+    M.st = (uint64_t)w[fsmd::W_ST_LO] | (uint64_t)w[fsmd::W_ST_HI] << 32;
+    M.ar = w[fsmd::W_AR], M.at = w[fsmd::W_AT];
+    M.key_a = (uint64_t)w[fsmd::W_KA_LO] | (uint64_t)w[fsmd::W_KA_HI] << 32;
+    M.key_b = (uint64_t)w[fsmd::W_KB_LO] | (uint64_t)w[fsmd::W_KB_HI] << 32;
+    M.uid_len = std::min<uint32_t>(w[fsmd::W_UID_LEN], fsmd::UID_CAP), M.flags = w[fsmd::W_FLAGS];
+    M.u0 = w[fsmd::W_UID0 + 0], M.u1 = w[fsmd::W_UID0 + 1], M.u2 = w[fsmd::W_UID0 + 2], M.u3 = w[fsmd::W_UID0 + 3];
+    M.u4 = w[fsmd::W_UID0 + 4], M.u5 = w[fsmd::W_UID0 + 5], M.u6 = w[fsmd::W_UID0 + 6], M.u7 = w[fsmd::W_UID0 + 7];
+    memset(st, 0, sizeof *st);
+    fsmd::machine_to_state(M, *st);
+    return NFC_OK;
+}
+
+int nfc_multi_set_fsm_state(nfc_multi *m, uint32_t stream, const nfc_fsm_state *st) {
+    if (!m) return NFC_ERR_ARG;
+    LaunchScope scope(&m->launch_err);
+    if (stream >= m->K) return mfail(m, NFC_ERR_ARG, "stream %u out of range (n_streams %u)", stream, m->K);
+    if (!st) return mfail(m, NFC_ERR_ARG, "st is null");
+    if (const char *bad = fsmd::state_fault(*st)) return mfail(m, NFC_ERR_ARG, "st: %s", bad);
+    if (hipSetDevice(m->P.device) != hipSuccess) return mfail(m, NFC_ERR_DEVICE, "hipSetDevice failed");
+    if (int rc = ensure_fsm(m)) return rc;
+    MCHK(m, hipStreamSynchronize(m->st));   // (the blob may still be on its way from an earlier call)
+    fsmd::Machine M;
+    fsmd::machine_from_state(M, *st);
+    uint32_t *w = m->h_fsm_blob;
+    w[fsmd::W_CUR_CMD] = (uint32_t)M.cur_cmd, w[fsmd::W_TAG_TYPE] = (uint32_t)M.tag_type, w[fsmd::W_ENCRYPTED] = (uint32_t)M.encrypted;
+    w[fsmd::W_CUR_KEY] = (uint32_t)M.cur_key;
+    w[fsmd::W_ST_LO] = (uint32_t)M.st, w[fsmd::W_ST_HI] = (uint32_t)(M.st >> 32);
+    w[fsmd::W_AR] = M.ar, w[fsmd::W_AT] = M.at;
+    w[fsmd::W_KA_LO] = (uint32_t)M.key_a, w[fsmd::W_KA_HI] = (uint32_t)(M.key_a >> 32);
+    w[fsmd::W_KB_LO] = (uint32_t)M.key_b, w[fsmd::W_KB_HI] = (uint32_t)(M.key_b >> 32);
+    w[fsmd::W_UID_LEN] = M.uid_len, w[fsmd::W_FLAGS] = M.flags;
+    w[fsmd::W_UID0 + 0] = M.u0, w[fsmd::W_UID0 + 1] = M.u1, w[fsmd::W_UID0 + 2] = M.u2, w[fsmd::W_UID0 + 3] = M.u3;
+    w[fsmd::W_UID0 + 4] = M.u4, w[fsmd::W_UID0 + 5] = M.u5, w[fsmd::W_UID0 + 6] = M.u6, w[fsmd::W_UID0 + 7] = M.u7;
+    MCHK(m, hipMemcpyAsync(m->d_fsm_blob, m->h_fsm_blob, fsmd::W_WORDS * 4, hipMemcpyHostToDevice, m->st));
+    commands::launch_io(m->d_fsm, m->K, stream, 1, m->d_fsm_blob, m->st);
+    if (int rc = launch_ok(m)) return rc;
+    MCHK(m, hipStreamSynchronize(m->st));
+    m->cmd_fetched = false;   // (the pointers of a fetch end here; the last push's commands stay fetchable)
+    return NFC_OK;
+}
+
+// One copy of the tracked push's buffer -- the frames' part and the commands' sections -- to pinned memory, one wait.  The pinned copy is
+// followed by base[K].  With nothing stored there is no buffer: the tables are zeroed on the host and the machines' flags come from their words.
+int nfc_multi_fetch_commands(nfc_multi *m, nfc_multi_commands *out) {
+    if (!m) return NFC_ERR_ARG;
+    LaunchScope scope(&m->launch_err);
+    if (!m->have_outputs) return mfail(m, NFC_ERR_STATE, "no completed push");
+    if (m->cmd_state == nfc_multi::CMD_NONE)
+        return mfail(m, NFC_ERR_STATE, "command tracking was off at the last push (nfc_multi_track_commands), or a stream was reset or set since");
+    if (m->cmd_fetched) {   // the same data: nothing is copied again and no machine is touched
+        if (out) *out = m->cout;
+        return NFC_OK;
+    }
+    if (hipSetDevice(m->P.device) != hipSuccess) return mfail(m, NFC_ERR_DEVICE, "hipSetDevice failed");
+    const uint32_t K = m->K;
+    const size_t T = (size_t)K + 1;
+    const bool stored = m->cmd_state == nfc_multi::CMD_LAUNCHED;
+    // nothing stored: [64 bytes | table [4][T] | cmd_off [T] | cbyte_off [T] | flags [K]] on the host alone
+    const size_t empty_tabs = up16(frames::MULTI_HEADER_BYTES + 4 * T * 8), empty_bytes = up16(empty_tabs + 2 * T * 8 + (size_t)K * 4);
+    const size_t bytes = stored ? m->cmd_bytes : empty_bytes, host_bytes = bytes + (size_t)K * 8;
+    if (m->h_cmd_cap < host_bytes) {
+        if (m->h_cmd) (void)hipHostFree(m->h_cmd);
+        m->h_cmd = nullptr;
+        m->h_cmd_cap = 0;
+        const size_t cap = host_bytes + host_bytes / 2 + 4096;
+        if (hipHostMalloc((void **)&m->h_cmd, cap, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            m->h_cmd = nullptr;
+            return mfail(m, NFC_ERR_NOMEM, "nfc_multi_fetch_commands: no pinned host memory for %zu bytes", cap);
+        }
+        m->h_cmd_cap = cap;
+    }
+    uint8_t *h = m->h_cmd;
+    uint64_t *base = (uint64_t *)(h + bytes);
+    for (uint32_t k = 0; k < K; k++) base[k] = m->g0[k];
+    nfc_multi_commands &c = m->cout;
+    memset(&c, 0, sizeof c);
+    c.n_streams = c.raw.n_streams = K;
+    if (stored) {
+        const commands::Layout &L = m->cmd_lay;
+        MCHK(m, hipMemcpyAsync(h, m->d_cmd, bytes, hipMemcpyDeviceToHost, m->st));
+        MCHK(m, hipStreamSynchronize(m->st));
+        if (int rc = launch_ok(m)) return rc;
+        const uint64_t *dev_total = (const uint64_t *)h;
+        const uint64_t *cmd_off = (const uint64_t *)(h + L.at[commands::SEC_CMD_OFF]), *cbyte_off = (const uint64_t *)(h + L.at[commands::SEC_CBYTE_OFF]);
+        for (int t = 0; t < 2; t++)
+            if (dev_total[t] != m->cmd_nfr[t] || dev_total[2 + t] > m->cmd_room[t])
+                return mfail(m, NFC_ERR_INTERNAL, "nfc_multi_fetch_commands: type %d: the device counts %llu frames and %llu bytes, the host %llu frames and room for %llu bytes",
+                             t, (unsigned long long)dev_total[t], (unsigned long long)dev_total[2 + t], (unsigned long long)m->cmd_nfr[t], (unsigned long long)m->cmd_room[t]);
+        if (cmd_off[K] != L.total_cmds || cbyte_off[K] != dev_total[2] + dev_total[3])
+            return mfail(m, NFC_ERR_INTERNAL, "nfc_multi_fetch_commands: the device counts %llu commands over %llu bytes, the host %llu commands, the frames %llu bytes",
+                         (unsigned long long)cmd_off[K], (unsigned long long)cbyte_off[K], (unsigned long long)L.total_cmds, (unsigned long long)(dev_total[2] + dev_total[3]));
+        if (m->cmd_timed) {
+            float ms = 0.f;
+            MCHK(m, hipEventElapsedTime(&ms, m->evc[0], m->evc[3]));
+            c.ms_kernels = ms;
+            MCHK(m, hipEventElapsedTime(&ms, m->evc[2], m->evc[3]));
+            c.ms_machine = ms;
+        }
+        c.n_launches = 3;
+        c.bytes_copied = bytes;
+        c.cmd_off = cmd_off;
+        c.cbyte_off = cbyte_off;
+        c.stream_flags = (const uint32_t *)(h + L.at[commands::SEC_FLAGS]);
+        c.cmd = (const nfc_frame *)(h + L.at[commands::SEC_CMD]);
+        c.src = (const uint32_t *)(h + L.at[commands::SEC_SRC]);
+        c.data = h + L.at[commands::SEC_DATA];
+        c.enc = (const uint16_t *)(h + L.at[commands::SEC_ENC]);
+    } else {
+        memset(h, 0, empty_bytes);
+        uint32_t *flags = (uint32_t *)(h + empty_tabs + 2 * T * 8);
+        MCHK(m, hipMemcpyAsync(flags, m->d_fsm + (size_t)fsmd::W_FLAGS * K, (size_t)K * 4, hipMemcpyDeviceToHost, m->st));
+        MCHK(m, hipStreamSynchronize(m->st));
+        c.bytes_copied = (size_t)K * 4;
+        c.cmd_off = (const uint64_t *)(h + empty_tabs);
+        c.cbyte_off = c.cmd_off + T;
+        c.stream_flags = flags;
+    }
+    frames_view(m, h, m->cmd_frlay, base, stored, c.raw);
+    m->cmd_fetched = true;
+    if (out) *out = c;
     return NFC_OK;
 }
 
@@ -1090,6 +1382,18 @@ extern "C" int nfc_debug_multi_guards(nfc_multi *m) {
             if (hipMemcpyAsync(g[s], m->d_frames + ends[s], GUARD_BYTES, hipMemcpyDeviceToHost, m->st) != hipSuccess) return -1;
         if (hipStreamSynchronize(m->st) != hipSuccess) return -1;
         for (int s = 0; s < 6; s++)
+            for (int b = 0; b < GUARD_BYTES; b++) h += g[s][b] != (uint8_t)(GUARD_WORD >> (8 * (b & 3)));
+    }
+    if (m->cmd_guarded) {   // ... and behind the sections of the tracked push's buffer: the frames' six and the commands' seven
+        const frames::MultiLayout &F = m->cmd_frlay;
+        const commands::Layout &L = m->cmd_lay;
+        uint64_t ends[6 + commands::SEC_COUNT] = {F.end_fr[0], F.end_fr[1], F.end_bytes[0], F.end_bytes[1], F.end_par[0], F.end_par[1]};
+        for (int s = 0; s < commands::SEC_COUNT; s++) ends[6 + s] = L.end[s];
+        uint8_t g[6 + commands::SEC_COUNT][GUARD_BYTES];
+        for (int s = 0; s < 6 + commands::SEC_COUNT; s++)
+            if (hipMemcpyAsync(g[s], m->d_cmd + ends[s], GUARD_BYTES, hipMemcpyDeviceToHost, m->st) != hipSuccess) return -1;
+        if (hipStreamSynchronize(m->st) != hipSuccess) return -1;
+        for (int s = 0; s < 6 + commands::SEC_COUNT; s++)
             for (int b = 0; b < GUARD_BYTES; b++) h += g[s][b] != (uint8_t)(GUARD_WORD >> (8 * (b & 3)));
     }
     return (int)h;

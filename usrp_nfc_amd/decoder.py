@@ -80,7 +80,8 @@ _SCALED_KINDS = (api.NFC_IN_I16_SQ, api.NFC_IN_IQ_I16, api.NFC_IN_IQ_I8, api.NFC
 _RECORDED_KINDS = _IQ_KINDS + (api.NFC_IN_ENV_F32,)   # (the kinds `dst` records: the UHD branch's stand-ins and a ready envelope)
 
 
-def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None, keep=None, device=0, push_stats=None, frames=False, **sink_kwargs):
+def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None, keep=None, device=0, push_stats=None, frames=False, commands=False,
+                keys=None, **sink_kwargs):
     """Decode many recordings at once: every source is a stream of one api.NfcMultiContext, a GPU lane each, one kernel launch per
     round of pieces (include/nfc_amd.h: nfc_multi) -- what a loop of ``decoder(src=s).run()`` does capture by capture.
 
@@ -94,6 +95,10 @@ def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None,
     frames=True: after every push the streams' frames -- bytes, parity bits, parity and CRC_A verdicts, assembled on the GPU -- are
     fetched once more (api.NfcMultiContext.fetch_frames) and every source's part is appended to its background's ``frames``, a list
     with one api.NfcFrames per push that gave the source samples; the default leaves the backgrounds as they were.
+    commands=True: the context tracks the commands on the GPU (api.NfcMultiContext.track_commands: the protocol machine, CRYPTO1
+    included, a lane per source); after every push they are fetched once (fetch_commands) and every source's ``(table, data, enc)``
+    -- what fsm.dispatch prints -- is appended to its background's ``commands``.  keys: ``(key_a, key_b)`` for all sources, or a list
+    with one such pair per source (default: FF..FF).  Without the argument nothing changes.
     -> one ``background`` per source, in order: ``decode_many(srcs)[i].packets`` and its fsm's command trace are what
     ``decoder(src=srcs[i]).run()`` gives."""
     scales = {k: sink_kwargs.pop(k, 0.0) for k in ('wav_scale', 'iq16_scale', 'iq8_scale')}
@@ -110,6 +115,19 @@ def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None,
     if frames:
         for b in backs:
             b.frames = []
+    if commands:
+        for b in backs:
+            b.commands = []
+    per_source_keys = None
+    if keys is not None:
+        if not commands:
+            raise ValueError('decode_many: keys are for commands=True')
+        if len(keys) == 2 and numpy.ndim(keys[0]) == 1 and numpy.size(keys[0]) == 6:
+            per_source_keys = [tuple(keys)] * len(loaded)
+        elif len(keys) == len(loaded):
+            per_source_keys = [tuple(k) for k in keys]
+        else:
+            raise ValueError('decode_many: keys is one (key_a, key_b) pair or one pair per source')
     if not loaded:
         return backs
     kind, scale = kinds[0], loaded[0][2]
@@ -125,6 +143,15 @@ def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None,
         try:
             with api.NfcMultiContext(len(group), piece, samp_rate=samp_rate, hi_val=_hi_val(kind), reader=reader, tag=tag, input_kind=kind,
                                      device=device, i16_scale=scale if kind in _SCALED_KINDS else 0.0, **sink) as m:
+                if commands:
+                    m.track_commands(True)
+                    if per_source_keys is not None:
+                        same = all(numpy.array_equal(k, per_source_keys[g0]) for k in per_source_keys[g0:g0 + len(group)])
+                        if same:
+                            m.set_keys(*per_source_keys[g0])
+                        else:
+                            for k in range(len(group)):
+                                m.set_keys(*per_source_keys[g0 + k], stream=k)
                 done = numpy.zeros(len(group), numpy.int64)
                 while True:
                     n = numpy.minimum(lens - done, piece)
@@ -139,6 +166,10 @@ def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None,
                         fr = m.fetch_frames()
                         for k in numpy.nonzero(n)[0]:
                             backs[g0 + int(k)].frames.append(fr.frames_of(int(k)))
+                    if commands:
+                        cm = m.fetch_commands()
+                        for k in numpy.nonzero(n)[0]:
+                            backs[g0 + int(k)].commands.append(cm.commands_of(int(k)))
                     if push_stats is not None:
                         st = m.stats()
                         push_stats.append((int(st.n_fetches), int(st.n_reads_device)))

@@ -35,6 +35,68 @@ def _structure(cmd_index, n_header, n_extra, data):
     return cmd, CommandStructure(cmd.name(), data[:n_header], data[n_header:n_header + n_extra], data[n_header + n_extra:])
 
 
+def dispatch(table, data, enc, out=None, callback=None):
+    """Print or forward the records of a frame table exactly as the machine does while it processes them: `table` FRAME_DTYPE records,
+    `data` / `enc` the byte and ciphertext arrays their byte_off indexes (fsm.process_frames' outputs, host_commands', or one
+    stream's part of an NfcMultiCommands: ``dispatch(*cmds.commands_of(k))``).  out: where the messages go (default sys.stdout);
+    callback(cmd, struct): default struct.display(out).  It uses no machine state.  -> the CommandStructures (None: a parity error)."""
+    out = out or sys.stdout
+    callback = callback or (lambda cmd, struct: struct.display(out))
+    res = []
+    for f in table:
+        o = int(f['byte_off'])
+        res.append(_dispatch_one(f, data[o:o + int(f['n_bytes'])].tolist(), enc[o:o + int(f['n_enc'])], out, callback))
+    return res
+
+
+def _dispatch_one(f, data, enc, out, callback):
+    flags = int(f['flags'])
+    _messages(flags, out)
+    if flags & FRAME_ENCRYPTED:   # fsm._print_enc (fsm.py:113-131): what was on the air, '!' where the parity bit equals the data parity
+        out.write(''.join('0x%02X%s ' % (int(e) & 0xFF, '!' if int(e) & 0x100 else '') for e in enc) + '\n')
+    if int(f['cmd']) == NFC_CMD_PARITY_ERROR:
+        out.write('PARITY ERROR\n')
+        return None
+    if int(f['cmd']) == _lib.NFC_CMD_CUT:   # (only the GPU machine of a multi-stream context makes these: the frame's bits were not stored)
+        out.write('CUT\n')
+        return None
+    if flags & FRAME_UID_MISMATCH:
+        out.write('MISMATCH BETWEEN READER-TAG UID\n')
+    for bit, msg in ((FRAME_AR_OK, 'AR OK'), (FRAME_AR_ERROR, 'ERROR WITH AR'), (FRAME_AT_OK, 'AT OK'), (FRAME_AT_ERROR, 'ERROR WITH AT')):
+        if flags & bit:
+            out.write(msg + '\n')
+    cmd, st = _structure(int(f['cmd']), int(f['n_header']), int(f['n_extra']), data)
+    callback(cmd, st)
+    return st
+
+
+def state_init():
+    """The nfc_fsm_state a reset leaves (nfc_fsm_state_init): REQA in flight, no tag, both keys FF..FF."""
+    st = _lib.FsmState()
+    if _lib.load().nfc_fsm_state_init(C.byref(st)) != 0:
+        raise RuntimeError('nfc_fsm_state_init failed')
+    return st
+
+
+def host_commands(state, frames, data=None, par=None):
+    """The GPU machine's twin on the CPU (nfc_host_commands): `frames` as process_frames takes them, `state` an _lib.FsmState that is
+    advanced in place.  -> (table, data, enc): every frame owns a slot of its raw n_bytes entries in data and enc."""
+    if data is None:
+        frames, data, par = frames.table, frames.bytes, frames.par
+    t = np.ascontiguousarray(frames, _lib.RAW_FRAME_DTYPE)
+    b = [np.ascontiguousarray(a, np.uint8) for a in data]
+    p = [np.ascontiguousarray(a, np.uint8) for a in par]
+    cap = int(t['n_bytes'].sum()) + 1
+    out, buf, enc = np.zeros(len(t), FRAME_DTYPE), np.zeros(cap, np.uint8), np.zeros(cap, np.uint16)
+    used = C.c_size_t(0)
+    ptr = lambda a: a.ctypes.data if a.size else None
+    rc = _lib.load().nfc_host_commands(C.byref(state), ptr(t), len(t), ptr(b[0]), ptr(p[0]), ptr(b[1]), ptr(p[1]), out.ctypes.data,
+                                       buf.ctypes.data, enc.ctypes.data, cap, C.byref(used))
+    if rc != 0:
+        raise ValueError('nfc_host_commands status %d' % rc)
+    return out, buf[:used.value], enc[:used.value]
+
+
 class fsm(object):
     def __init__(self, callback=None, out=None):
         self.L = _lib.load()
@@ -62,22 +124,21 @@ class fsm(object):
         if a.size != 6 or b.size != 6 or self.L.nfc_fsm_set_keys(self._h, a.ctypes.data, b.ctypes.data) != 0:
             raise ValueError('keys are six bytes each')
 
-    def _dispatch(self, f, data, enc=()):
-        flags = int(f['flags'])
-        _messages(flags, self._out)
-        if flags & FRAME_ENCRYPTED:   # fsm._print_enc (fsm.py:113-131): what was on the air, '!' where the parity bit equals the data parity
-            self._out.write(''.join('0x%02X%s ' % (int(e) & 0xFF, '!' if int(e) & 0x100 else '') for e in enc) + '\n')
-        if int(f['cmd']) == NFC_CMD_PARITY_ERROR:
-            self._out.write('PARITY ERROR\n')
-            return None
-        if flags & FRAME_UID_MISMATCH:
-            self._out.write('MISMATCH BETWEEN READER-TAG UID\n')
-        for bit, msg in ((FRAME_AR_OK, 'AR OK'), (FRAME_AR_ERROR, 'ERROR WITH AR'), (FRAME_AT_OK, 'AT OK'), (FRAME_AT_ERROR, 'ERROR WITH AT')):
-            if flags & bit:
-                self._out.write(msg + '\n')
-        cmd, st = _structure(int(f['cmd']), int(f['n_header']), int(f['n_extra']), data)
-        self._callback(cmd, st)
+    def get_state(self):
+        """The machine as a plain nfc_fsm_state (nfc_fsm_get_state) -- what NfcMultiContext.set_fsm_state takes.  ValueError when the
+        UID is longer than the 32 bytes the plain state holds."""
+        st = _lib.FsmState()
+        if self.L.nfc_fsm_get_state(self._h, C.byref(st)) != 0:
+            raise ValueError('nfc_fsm_get_state: the UID is longer than 32 bytes')
         return st
+
+    def set_state(self, st):
+        """Continue from a plain nfc_fsm_state (NfcMultiContext.fsm_state(k), another machine's get_state())."""
+        if self.L.nfc_fsm_set_state(self._h, C.byref(st)) != 0:
+            raise ValueError('nfc_fsm_set_state: a field of the state is out of range')
+
+    def _dispatch(self, f, data, enc=()):
+        return _dispatch_one(f, data, enc, self._out, self._callback)
 
     def process_bits(self, bits, packet_type):
         """One closed packet (fsm.py:218).  Returns the CommandStructure, or None on a parity error."""
