@@ -41,6 +41,8 @@ extern "C" {
 /* (still 4, only new names: nfc_fsm_state, NFC_FSM_*, NFC_CMD_CUT, nfc_fsm_state_init, nfc_fsm_get_state, nfc_fsm_set_state, nfc_host_commands,
  *  nfc_multi_commands, nfc_multi_track_commands, nfc_multi_fetch_commands, nfc_multi_set_keys, nfc_multi_get_fsm_state,
  *  nfc_multi_set_fsm_state) */
+/* (still 4, only new names: nfc_auth_trace, nfc_key_result, nfc_key_config, nfc_key_stats, NFC_KEY_*, nfc_find_auths, nfc_host_recover_keys,
+ *  nfc_recover_keys_device) */
 #define NFC_AMD_ABI_VERSION 4
 
 typedef enum {
@@ -637,6 +639,73 @@ int nfc_multi_fetch_commands(nfc_multi *m, nfc_multi_commands *out);
 int nfc_multi_set_keys(nfc_multi *m, int64_t stream /* -1: every stream */, const uint8_t key_a[6], const uint8_t key_b[6]);
 int nfc_multi_get_fsm_state(nfc_multi *m, uint32_t stream, nfc_fsm_state *st);
 int nfc_multi_set_fsm_state(nfc_multi *m, uint32_t stream, const nfc_fsm_state *st);
+
+/* ---- key recovery: a MIFARE Classic sector key from one sniffed first authentication --------------------------------------------------
+ * An eavesdropper who has no keys still sees everything the recovery needs: the UID (SEL1R), the tag nonce nt in the clear (RANDTA),
+ * {nr}{ar} (RANDRB) and {at} (RANDTB).  ks2 = {ar} ^ suc64(nt) and ks3 = {at} ^ suc96(nt) are 64 known keystream bits of a free-running
+ * 48-bit register; they determine it, and rolling it back over {nr} and uid ^ nt gives the key (csrc/keys.hip.h states the method,
+ * DESIGN.md 8h the layout).  Independent across authentications: nfc_recover_keys_device runs a batch of traces per launch.
+ * A 32-bit word of a frame has bit i = bit (i & 7) of byte (i >> 3) -- byte 0 lowest.  par: bit i the ninth bit, as received, of byte i of
+ * {nr}{ar} (i = 0 .. 7) and of byte i - 8 of {at} (i = 8 .. 11).  40 bytes: five words, the parity bits, key type and block, stream and
+ * frame as 32-bit counts and the 64-bit sample index at their natural widths.
+ * NOT PROMISED: nested authentications (their nt is encrypted; nfc_find_auths does not return them), recovery without {at}, 7-byte UIDs. */
+typedef struct nfc_auth_trace {
+    uint32_t uid, nt, nr_enc, ar_enc, at_enc;
+    uint16_t par;
+    uint8_t key_type;              /* 0x60: key A, 0x61: key B */
+    uint8_t block;
+    uint32_t stream;               /* nfc_find_auths writes 0: the caller's to fill */
+    uint32_t frame;                /* index of the AUTH frame in the merged order */
+    uint64_t idx;                  /* nfc_raw_frame.idx of the AUTH frame */
+} nfc_auth_trace;
+enum { NFC_KEY_OK = 0,             /* exactly one verified candidate */
+       NFC_KEY_NONE = 1,           /* no candidate passed the verification */
+       NFC_KEY_AMBIGUOUS = 2,      /* more than one: the lowest key as a 48-bit integer (byte 0 lowest) is reported */
+       NFC_KEY_OVERFLOW = 3 };     /* the trace's table does not fit max_capacity: nothing was searched, n_odd / n_even are exact */
+typedef struct nfc_key_result {    /* 24 bytes */
+    uint8_t key[6];
+    uint8_t status;                /* NFC_KEY_* */
+    uint8_t reserved;
+    uint32_t n_candidates;         /* verified candidates, saturating */
+    uint32_t n_odd, n_even;        /* the exact sizes of the two lists */
+    uint32_t nr;                   /* the decrypted reader nonce under `key` (0 without a key) */
+} nfc_key_result;
+/* CAPACITY is counted in table slots (16 bytes each in device memory).  A trace needs a table of the smallest power of two that is at least
+ * twice its odd list; the traces of a batch are searched in groups, in order, whose tables together fit max_capacity.  The scratch
+ * starts at initial_capacity and grows to fit a group that needs more (nfc_key_stats.n_grown counts that), never beyond max_capacity; a
+ * trace whose table alone exceeds max_capacity gets NFC_KEY_OVERFLOW -- nothing is truncated and nothing written past a table.
+ * Defaults (a 0): initial_capacity 2^26 (1 GiB: sixteen tables of 2^22, DESIGN.md 8h says where that comes from), max_capacity 2^28,
+ * max_batch 16.  initial_capacity above max_capacity, max_capacity above 2^32, max_batch above 4096, unknown flags or non-zero
+ * reserved words are NFC_ERR_ARG. */
+enum { NFC_KEY_TIMING = 1 };       /* nfc_key_config.flags: HIP events around every launch -> nfc_key_stats.ms_* (device call only) */
+typedef struct nfc_key_config {    /* 32 bytes */
+    uint64_t initial_capacity, max_capacity;
+    uint32_t max_batch;            /* traces per count launch */
+    uint32_t flags;
+    uint32_t reserved[2];
+} nfc_key_config;
+typedef struct nfc_key_stats {     /* 56 bytes */
+    double ms_kernels;             /* ms_count + ms_fill + ms_probe; 0 without NFC_KEY_TIMING and from the host twin */
+    double ms_count, ms_fill, ms_probe;
+    uint64_t scratch_bytes;        /* the tables' scratch at the end of the call (the host twin: what the device call would hold) */
+    uint32_t n_batches, n_grown;
+    uint32_t n_launches, reserved;
+} nfc_key_stats;
+/* Host only.  `frames`: both types merged by idx, as nfc_fsm_process_frames takes them (type 0: tag, bytes0 / par0; type 1: reader).  A
+ * first authentication is: the most recent reader frame 93 70 u0 u1 u2 u3 bcc crc with NFC_RAW_CRC_A_OK (4-byte UIDs only, as the
+ * machine's set_tag); then, consecutive in the merged order and none NFC_RAW_CUT: a reader frame 60|61 blk crc with NFC_RAW_CRC_A_OK, a tag
+ * frame of 4 bytes with NFC_RAW_PARITY_OK (nt), a reader frame of 8 bytes ({nr}{ar}), a tag frame of 4 bytes ({at}).  out: the first
+ * `cap` of them; *n_out: how many there are. */
+int nfc_find_auths(const nfc_raw_frame *frames, size_t n, const uint8_t *bytes0, const uint8_t *par0, const uint8_t *bytes1,
+                   const uint8_t *par1, nfc_auth_trace *out, size_t cap, size_t *n_out);
+/* The CPU twin (no GPU needed): the same header, the same capacity rules and statuses; the join is a sort of the odd list and a binary
+ * search per even sequence.  cfg and stats may be NULL. */
+int nfc_host_recover_keys(const nfc_auth_trace *traces, size_t n, const nfc_key_config *cfg, nfc_key_result *out, nfc_key_stats *stats);
+/* No context, like nfc_record_pcm16_device: per batch one count launch and one read of the counts, then per group a fill and a probe
+ * launch (csrc/keys.hip.h).  The results are complete when the call returns.  n == 0 launches nothing and touches no device.  Every
+ * argument is checked before the device is touched.  There is no CPU fallback: without a usable device the call fails. */
+int nfc_recover_keys_device(int device, const nfc_auth_trace *traces, size_t n, const nfc_key_config *cfg, nfc_key_result *out,
+                            nfc_key_stats *stats);
 
 /* one stream's boundary state, in the form an nfc_ctx exports and imports it */
 int nfc_multi_get_state(nfc_multi *m, uint32_t stream, nfc_state_header *hdr, float *ring, size_t ring_cap, uint8_t *pending, size_t pending_cap);

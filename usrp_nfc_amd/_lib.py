@@ -78,6 +78,17 @@ class MultiCommands(C.Structure):   # nfc_multi_commands
                 ('bytes_copied', C.c_uint64), ('ms_kernels', C.c_double), ('ms_machine', C.c_double), ('reserved', C.c_uint64 * 4)]
 
 
+class KeyConfig(C.Structure):   # nfc_key_config
+    _fields_ = [('initial_capacity', C.c_uint64), ('max_capacity', C.c_uint64), ('max_batch', C.c_uint32), ('flags', C.c_uint32),
+                ('reserved', C.c_uint32 * 2)]
+
+
+class KeyStats(C.Structure):   # nfc_key_stats
+    _fields_ = [('ms_kernels', C.c_double), ('ms_count', C.c_double), ('ms_fill', C.c_double), ('ms_probe', C.c_double),
+                ('scratch_bytes', C.c_uint64), ('n_batches', C.c_uint32), ('n_grown', C.c_uint32), ('n_launches', C.c_uint32),
+                ('reserved', C.c_uint32)]
+
+
 class Frame(C.Structure):   # nfc_frame
     _fields_ = [('cmd', C.c_int32), ('type', C.c_int32), ('byte_off', C.c_uint32), ('n_bytes', C.c_uint16),
                 ('n_header', C.c_uint16), ('n_extra', C.c_uint16), ('n_crc', C.c_uint16), ('flags', C.c_uint32),
@@ -111,6 +122,13 @@ FSM_STATE_DTYPE = np.dtype([('cur_cmd', '<i4'), ('tag_type', '<i4'), ('encrypted
                             ('reserved', '<u4')])
 NFC_FSM_LOST, NFC_FSM_UID_OVERFLOW = 1, 2
 NFC_CMD_CUT = -3
+# nfc_auth_trace: one sniffed first authentication (words: byte 0 lowest), and nfc_key_result with its statuses
+AUTH_DTYPE = np.dtype([('uid', '<u4'), ('nt', '<u4'), ('nr_enc', '<u4'), ('ar_enc', '<u4'), ('at_enc', '<u4'), ('par', '<u2'), ('key_type', 'u1'),
+                       ('block', 'u1'), ('stream', '<u4'), ('frame', '<u4'), ('idx', '<u8')])
+KEY_RESULT_DTYPE = np.dtype([('key', 'u1', (6,)), ('status', 'u1'), ('reserved', 'u1'), ('n_candidates', '<u4'), ('n_odd', '<u4'), ('n_even', '<u4'),
+                             ('nr', '<u4')])
+NFC_KEY_OK, NFC_KEY_NONE, NFC_KEY_AMBIGUOUS, NFC_KEY_OVERFLOW = 0, 1, 2, 3
+NFC_KEY_TIMING = 1
 COUNTS_DTYPE = np.dtype([('n_samples', '<u8'), ('n_edges', '<u8'), ('n_symbols', '<u8', (2,)), ('n_packets', '<u8', (2,)),
                          ('n_packet_bits', '<u8', (2,))])   # nfc_counts
 
@@ -128,7 +146,8 @@ SYMBOLS = ['nfc_abi_version', 'nfc_device_count', 'nfc_create', 'nfc_destroy', '
            'nfc_multi_set_state', 'nfc_multi_reset', 'nfc_multi_get_stats', 'nfc_multi_set_timing', 'nfc_multi_fetch', 'nfc_multi_get_counts_all',
            'nfc_get_frame_counts', 'nfc_read_frames', 'nfc_read_frame_bytes', 'nfc_host_frames', 'nfc_fsm_process_frames', 'nfc_multi_fetch_frames',
            'nfc_fsm_state_init', 'nfc_fsm_get_state', 'nfc_fsm_set_state', 'nfc_host_commands', 'nfc_multi_track_commands', 'nfc_multi_fetch_commands',
-           'nfc_multi_set_keys', 'nfc_multi_get_fsm_state', 'nfc_multi_set_fsm_state']
+           'nfc_multi_set_keys', 'nfc_multi_get_fsm_state', 'nfc_multi_set_fsm_state',
+           'nfc_find_auths', 'nfc_host_recover_keys', 'nfc_recover_keys_device']
 
 _libs = {}
 
@@ -253,6 +272,9 @@ def load(path=None):
     L.nfc_multi_set_keys.argtypes = [vp, C.c_int64, vp, vp]
     L.nfc_multi_get_fsm_state.argtypes = [vp, u32, C.POINTER(FsmState)]
     L.nfc_multi_set_fsm_state.argtypes = [vp, u32, C.POINTER(FsmState)]
+    L.nfc_find_auths.argtypes = [vp, sz, vp, vp, vp, vp, vp, sz, psz]
+    L.nfc_host_recover_keys.argtypes = [vp, sz, C.POINTER(KeyConfig), vp, C.POINTER(KeyStats)]
+    L.nfc_recover_keys_device.argtypes = [C.c_int, vp, sz, C.POINTER(KeyConfig), vp, C.POINTER(KeyStats)]
     for name in SYMBOLS:
         getattr(L, name)
     _libs[path] = L

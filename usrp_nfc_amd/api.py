@@ -422,6 +422,14 @@ class NfcMultiContext(object):
             raise NfcError('set_keys: key_a and key_b are six bytes each')
         self._chk(self.L.nfc_multi_set_keys(self.h, -1 if stream is None else int(stream), a.ctypes.data, b.ctypes.data), 'nfc_multi_set_keys')
 
+    def recover_keys(self, **cfg):
+        """The sector keys of the last push's first authentications: fetch_frames() + NfcMultiFrames.auths() + ONE keys.recover call on
+        this context's device (cfg: keys.recover's).  -> per stream a dict (key_type, block) -> six key bytes (keys.keys_by_stream)."""
+        from . import keys
+        traces = self.fetch_frames().auths()
+        results, _ = keys.recover(traces, device=self.device, **cfg)
+        return keys.keys_by_stream(traces, results, self.n_streams)
+
     def fsm_state(self, k):
         """Stream k's protocol machine as a plain nfc_fsm_state (an _lib.FsmState): what fsm.set_state takes."""
         if not 0 <= int(k) < self.n_streams:
@@ -749,6 +757,17 @@ class NfcMultiFrames(object):
             a, b = int(self.byte_off[t][k]), int(self.byte_off[t][k + 1])
             data.append(self.bytes[t][a:b]), par.append(self.par[t][a:b])
         return NfcFrames(recs, data, par)
+
+    def auths(self):
+        """Every stream's first authentications (keys.find_auths per stream, in stream order) as ONE AUTH_DTYPE array, `stream` filled
+        in and `idx` in the stream's own sample count: what keys.recover takes.  A loop over the streams that have frames of both types."""
+        from . import keys
+        parts = []
+        for k in np.nonzero((np.diff(self.frame_off[0]) > 0) & (np.diff(self.frame_off[1]) > 0))[0]:
+            a = keys.find_auths(self.frames_of(int(k)))
+            a['stream'] = int(k)
+            parts.append(a)
+        return np.concatenate(parts) if parts else np.zeros(0, _lib.AUTH_DTYPE)
 
     def stream_of(self, ptype):
         """The stream every frame of frames[ptype] belongs to."""

@@ -26,6 +26,7 @@ import wave
 import numpy
 
 from . import api
+from . import keys as _keys
 from .background import background
 from .transition_sink import transition_sink
 
@@ -99,6 +100,10 @@ def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None,
     included, a lane per source); after every push they are fetched once (fetch_commands) and every source's ``(table, data, enc)``
     -- what fsm.dispatch prints -- is appended to its background's ``commands``.  keys: ``(key_a, key_b)`` for all sources, or a list
     with one such pair per source (default: FF..FF).  Without the argument nothing changes.
+    keys='recover': per group of sources one UNTRACKED pass first collects every source's frames across its pushes, ONE key recovery
+    (usrp_nfc_amd.keys.recover) searches the keys of all their first authentications, the context is reset, every stream gets the first
+    key found for type A and for type B (the default where none was found), and the tracked pass follows as above.  Every background
+    gets ``recovered_keys``: (key_type, block) -> six key bytes.  The cost is the doubled push.
     -> one ``background`` per source, in order: ``decode_many(srcs)[i].packets`` and its fsm's command trace are what
     ``decoder(src=srcs[i]).run()`` gives."""
     scales = {k: sink_kwargs.pop(k, 0.0) for k in ('wav_scale', 'iq16_scale', 'iq8_scale')}
@@ -119,7 +124,13 @@ def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None,
         for b in backs:
             b.commands = []
     per_source_keys = None
-    if keys is not None:
+    recover = isinstance(keys, str) and keys == 'recover'
+    if recover:
+        if not commands:
+            raise ValueError('decode_many: keys are for commands=True')
+        for b in backs:
+            b.recovered_keys = {}
+    elif keys is not None:
         if not commands:
             raise ValueError('decode_many: keys are for commands=True')
         if len(keys) == 2 and numpy.ndim(keys[0]) == 1 and numpy.size(keys[0]) == 6:
@@ -143,8 +154,14 @@ def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None,
         try:
             with api.NfcMultiContext(len(group), piece, samp_rate=samp_rate, hi_val=_hi_val(kind), reader=reader, tag=tag, input_kind=kind,
                                      device=device, i16_scale=scale if kind in _SCALED_KINDS else 0.0, **sink) as m:
+                if recover:
+                    _recover_group_keys(m, buf, starts, lens, piece, backs[g0:g0 + len(group)], device)
                 if commands:
                     m.track_commands(True)
+                    if recover:
+                        for k, b in enumerate(backs[g0:g0 + len(group)]):
+                            if b.recovered_keys:
+                                m.set_keys(*_keys.first_keys(b.recovered_keys), stream=k)
                     if per_source_keys is not None:
                         same = all(numpy.array_equal(k, per_source_keys[g0]) for k in per_source_keys[g0:g0 + len(group)])
                         if same:
@@ -176,6 +193,49 @@ def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None,
         finally:
             buf.free()
     return backs
+
+
+def _joined_frames(parts):
+    """[(NfcFrames, base), ...] of one stream's consecutive pushes as one NfcFrames: byte_offs moved behind each other, idx in the stream's
+    whole sample count."""
+    recs, data, par = [[], []], [[], []], [[], []]
+    at = [0, 0]
+    for fr, base in parts:
+        for t in (0, 1):
+            r = fr.records[t].copy()
+            r['byte_off'] += at[t]
+            r['idx'] += base
+            at[t] += len(fr.bytes[t])
+            recs[t].append(r), data[t].append(fr.bytes[t]), par[t].append(fr.par[t])
+    cat = lambda xs, dt: numpy.concatenate(xs) if xs else numpy.zeros(0, dt)
+    return api.NfcFrames([cat(recs[t], api.RAW_FRAME_DTYPE) for t in (0, 1)], [cat(data[t], numpy.uint8) for t in (0, 1)],
+                         [cat(par[t], numpy.uint8) for t in (0, 1)])
+
+
+def _recover_group_keys(m, buf, starts, lens, piece, backs, device):
+    """The untracked pass of decode_many(keys='recover') over one group: every source's frames across its pushes, one recovery call for
+    all of them, the context reset afterwards.  Fills every background's ``recovered_keys``."""
+    parts = [[] for _ in backs]
+    done = numpy.zeros(len(backs), numpy.int64)
+    while True:
+        n = numpy.minimum(lens - done, piece)
+        if not n.any():
+            break
+        m.push_device(buf, starts + done, n)
+        done += n
+        fr = m.fetch_frames()
+        for k in numpy.nonzero(n)[0]:
+            parts[int(k)].append((fr.frames_of(int(k)), int(fr.base[k]) if len(fr.base) else 0))
+    traces = []
+    for k, ps in enumerate(parts):
+        a = _keys.find_auths(_joined_frames(ps))
+        a['stream'] = k
+        traces.append(a)
+    traces = numpy.concatenate(traces) if traces else numpy.zeros(0, _keys.AUTH_DTYPE)
+    results, _ = _keys.recover(traces, device=device)
+    for b, found in zip(backs, _keys.keys_by_stream(traces, results, len(backs))):
+        b.recovered_keys = found
+    m.reset()
 
 
 if _gr is not None:
