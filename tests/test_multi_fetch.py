@@ -391,6 +391,70 @@ def test_truncated_streams_contribute_their_stored_prefix():
         assert int(m.stats().n_reads_device) == reads and guards(m.h) == 0   # nothing was read from the device after the fetch
 
 
+def packed_arrays(f, fr, cm):
+    """Every array a fetch(), a fetch_frames() and a fetch_commands() hand out, in a fixed order."""
+    out = list(f.off) + [f.base, f.edge_pos, f.edge_code] + f.symbols + f.packet_table + f.packet_bits
+    for r in (fr, cm.raw):
+        out += r.frame_off + r.byte_off + [r.base] + r.frames + r.bytes + r.par
+    return out + [cm.cmd_off, cm.cbyte_off, cm.cmd, cm.src, cm.data, cm.enc, cm.stream_flags]
+
+
+@pytest.mark.gpu
+def test_packed_buffers_grow_between_two_pushes():
+    """The three packed buffers -- the fetch's, the frames', the tracked push's -- are allocated for a small first push and must be
+    replaced for the second, in the same context: every call of push 2 copies more than 1.5 x its push-1 bytes + 4096, the most a buffer
+    sized for push 1 can hold.  Nothing of it may show: the guards hold after every call and push 2 reads byte for byte as in a context
+    whose buffers were allocated once, at their final size.
+
+    The streams: the Classic capture of tests/test_commands.py, TWICE in a row in each of the three (the third with the wrong key A).  One
+    copy is not enough for the condition: the frames of all three whole captures pack into 3 424 bytes, fewer than the 4 096 alone.
+    Push 1 is the first 4 000 samples of stream 0 (REQA and ATQA: a packet of each type), the first 2 500 of stream 1 (edges, no
+    packet), nothing of stream 2; push 2 the remainder.  With these cuts the C oracle's counts give, push 1 -> push 2: the fetch 880 ->
+    114 688 bytes, the frames 416 -> 6 944, the commands 720 -> 14 848."""
+    from tests import test_commands as tc
+    one = tc.classic_iq()
+    x = np.concatenate([one, one])
+    cuts = (4000, 2500, 0)
+    first, second = [x[:2 * c] for c in cuts], [x[2 * c:] for c in cuts]
+    hooks = _lib.hooks_path()
+
+    def calls(m):
+        guards = m.L.nfc_debug_multi_guards
+        guards.argtypes = [C.c_void_p]
+        got = []
+        for call in (m.fetch, m.fetch_frames, m.fetch_commands):
+            got.append(call())
+            assert guards(m.h) == 0, call.__name__
+        return got
+
+    with tc.tracked(3, len(x) // 2, lib_path=hooks) as m, tc.tracked(3, len(x) // 2, lib_path=hooks) as twin:
+        m.push(first)
+        small = calls(m)
+        cnt = m.counts_all()
+        assert cnt['n_packets'][0].tolist() == [1, 1] and int(cnt['n_edges'][1]) > 0 and not cnt['n_packets'][1].any() and int(cnt['n_edges'][2]) == 0
+        assert len(small[1].frames[0]) == len(small[1].frames[1]) == 1 and len(small[2].cmd) == 2
+        m.push(second)
+        large = calls(m)
+        for a, b in zip(small, large):
+            print('%s: %d -> %d bytes copied' % (type(a).__name__, a.bytes_copied, b.bytes_copied))
+            assert a.bytes_copied > 0 and b.bytes_copied > 1.5 * a.bytes_copied + 4096, type(a).__name__
+        assert large[0].base.tolist() == list(cuts) == large[1].base.tolist() == large[2].raw.base.tolist()
+        twin.push(first)
+        twin.push(second)
+        want = calls(twin)
+        assert len(want[2].cmd) == 3 * 48 - 2 and [w.n_launches for w in want] == [2, 2, 3] == [g.n_launches for g in large]
+        for i, (g, w) in enumerate(zip(packed_arrays(*large), packed_arrays(*want))):
+            assert len(g) and g.dtype == w.dtype and g.tobytes() == w.tobytes(), i
+        m.reset(-1)
+        m.push([x[:0]] * 3)
+        f, fr, cm = calls(m)
+        assert f.n_launches == fr.n_launches == cm.n_launches == 0
+        assert all(not o.any() for o in f.off + fr.frame_off + fr.byte_off + cm.raw.frame_off + cm.raw.byte_off + [cm.cmd_off, cm.cbyte_off])
+        assert all(not len(a) for a in [f.edge_pos, f.edge_code] + f.symbols + f.packet_table + f.packet_bits + fr.frames + fr.bytes + cm.raw.frames
+                   + [cm.cmd, cm.src, cm.data, cm.enc])
+        assert not f.base.any() and not fr.base.any() and cm.stream_flags.tolist() == [0, 0, 0]
+
+
 def edge_codes(e, nd):
     """EDGE_DTYPE records -> the 16-bit codes the device keeps (edges.hip.h: edge_code)."""
     return (((e['v'].astype(np.int64) + 1) * nd + e['d']) | ((e['t'].astype(np.int64) + 1) << 14)).astype(np.uint16)

@@ -502,9 +502,48 @@ inline const char *state_fault(const nfc_fsm_state &s) {
     return nullptr;
 }
 
-// the machine as words, the layout of the device's [word][stream] arrays (multi_commands.hip.h) and of nothing else
+// the machine as words, the layout of the device's [word][stream] arrays (multi_commands.hip.h), of one machine's blob (nfc_multi.hip:
+// the same with one stream) and of nothing else
 enum { W_CUR_CMD, W_TAG_TYPE, W_ENCRYPTED, W_CUR_KEY, W_ST_LO, W_ST_HI, W_AR, W_AT, W_KA_LO, W_KA_HI, W_KB_LO, W_KB_HI, W_UID_LEN, W_FLAGS,
        W_UID0, W_WORDS = W_UID0 + 8 };
+// stream k of K: (words, K, k); one machine alone: (words, 1, 0)
+NFC_HD void load_machine(Machine &M, const uint32_t *__restrict__ s, size_t K, size_t k) {
+    M.cur_cmd = (int32_t)s[W_CUR_CMD * K + k];
+    M.tag_type = (int32_t)s[W_TAG_TYPE * K + k];
+    M.encrypted = (int32_t)s[W_ENCRYPTED * K + k];
+    M.cur_key = (int32_t)s[W_CUR_KEY * K + k];
+    M.st = (uint64_t)s[W_ST_LO * K + k] | (uint64_t)s[W_ST_HI * K + k] << 32;
+    M.ar = s[W_AR * K + k];
+    M.at = s[W_AT * K + k];
+    M.key_a = (uint64_t)s[W_KA_LO * K + k] | (uint64_t)s[W_KA_HI * K + k] << 32;
+    M.key_b = (uint64_t)s[W_KB_LO * K + k] | (uint64_t)s[W_KB_HI * K + k] << 32;
+    M.uid_len = s[W_UID_LEN * K + k];
+    M.flags = s[W_FLAGS * K + k];
+    M.u0 = s[(W_UID0 + 0) * K + k], M.u1 = s[(W_UID0 + 1) * K + k], M.u2 = s[(W_UID0 + 2) * K + k], M.u3 = s[(W_UID0 + 3) * K + k];
+    M.u4 = s[(W_UID0 + 4) * K + k], M.u5 = s[(W_UID0 + 5) * K + k], M.u6 = s[(W_UID0 + 6) * K + k], M.u7 = s[(W_UID0 + 7) * K + k];
+    // (a machine is only ever written by store_machine, launch_init and a checked nfc_fsm_state; still, nothing may index by these)
+    if ((uint32_t)M.cur_cmd >= (uint32_t)C_COUNT) M.cur_cmd = C_REQA;
+    if (M.uid_len > UID_CAP) M.uid_len = UID_CAP;
+    M.st &= ST_MASK;
+}
+NFC_HD void store_machine(const Machine &M, uint32_t *__restrict__ s, size_t K, size_t k) {
+    s[W_CUR_CMD * K + k] = (uint32_t)M.cur_cmd;
+    s[W_TAG_TYPE * K + k] = (uint32_t)M.tag_type;
+    s[W_ENCRYPTED * K + k] = (uint32_t)M.encrypted;
+    s[W_CUR_KEY * K + k] = (uint32_t)M.cur_key;
+    s[W_ST_LO * K + k] = (uint32_t)M.st;
+    s[W_ST_HI * K + k] = (uint32_t)(M.st >> 32);
+    s[W_AR * K + k] = M.ar;
+    s[W_AT * K + k] = M.at;
+    s[W_KA_LO * K + k] = (uint32_t)M.key_a;
+    s[W_KA_HI * K + k] = (uint32_t)(M.key_a >> 32);
+    s[W_KB_LO * K + k] = (uint32_t)M.key_b;
+    s[W_KB_HI * K + k] = (uint32_t)(M.key_b >> 32);
+    s[W_UID_LEN * K + k] = M.uid_len;
+    s[W_FLAGS * K + k] = M.flags;
+    s[(W_UID0 + 0) * K + k] = M.u0, s[(W_UID0 + 1) * K + k] = M.u1, s[(W_UID0 + 2) * K + k] = M.u2, s[(W_UID0 + 3) * K + k] = M.u3;
+    s[(W_UID0 + 4) * K + k] = M.u4, s[(W_UID0 + 5) * K + k] = M.u5, s[(W_UID0 + 6) * K + k] = M.u6, s[(W_UID0 + 7) * K + k] = M.u7;
+}
 
 }  // namespace fsmd
 }  // namespace nfc

@@ -41,46 +41,6 @@ void launch_set_keys(uint32_t *state, uint32_t K, uint32_t k0, uint32_t k1, uint
 void launch_io(uint32_t *state, uint32_t K, uint32_t k, int set, uint32_t *blob, hipStream_t stream);
 
 #ifdef NFC_COMMANDS_KERNELS
-__device__ __forceinline__ void load_machine(fsmd::Machine &M, const uint32_t *__restrict__ s, size_t K, size_t k) {
-    using namespace fsmd;
-    M.cur_cmd = (int32_t)s[W_CUR_CMD * K + k];
-    M.tag_type = (int32_t)s[W_TAG_TYPE * K + k];
-    M.encrypted = (int32_t)s[W_ENCRYPTED * K + k];
-    M.cur_key = (int32_t)s[W_CUR_KEY * K + k];
-    M.st = (uint64_t)s[W_ST_LO * K + k] | (uint64_t)s[W_ST_HI * K + k] << 32;
-    M.ar = s[W_AR * K + k];
-    M.at = s[W_AT * K + k];
-    M.key_a = (uint64_t)s[W_KA_LO * K + k] | (uint64_t)s[W_KA_HI * K + k] << 32;
-    M.key_b = (uint64_t)s[W_KB_LO * K + k] | (uint64_t)s[W_KB_HI * K + k] << 32;
-    M.uid_len = s[W_UID_LEN * K + k];
-    M.flags = s[W_FLAGS * K + k];
-    M.u0 = s[(W_UID0 + 0) * K + k], M.u1 = s[(W_UID0 + 1) * K + k], M.u2 = s[(W_UID0 + 2) * K + k], M.u3 = s[(W_UID0 + 3) * K + k];
-    M.u4 = s[(W_UID0 + 4) * K + k], M.u5 = s[(W_UID0 + 5) * K + k], M.u6 = s[(W_UID0 + 6) * K + k], M.u7 = s[(W_UID0 + 7) * K + k];
-    // (a machine is only ever written by store_machine, launch_init and a checked nfc_fsm_state; still, nothing below may index by these)
-    if ((uint32_t)M.cur_cmd >= (uint32_t)C_COUNT) M.cur_cmd = C_REQA;
-    if (M.uid_len > UID_CAP) M.uid_len = UID_CAP;
-    M.st &= ST_MASK;
-}
-__device__ __forceinline__ void store_machine(const fsmd::Machine &M, uint32_t *__restrict__ s, size_t K, size_t k) {
-    using namespace fsmd;
-    s[W_CUR_CMD * K + k] = (uint32_t)M.cur_cmd;
-    s[W_TAG_TYPE * K + k] = (uint32_t)M.tag_type;
-    s[W_ENCRYPTED * K + k] = (uint32_t)M.encrypted;
-    s[W_CUR_KEY * K + k] = (uint32_t)M.cur_key;
-    s[W_ST_LO * K + k] = (uint32_t)M.st;
-    s[W_ST_HI * K + k] = (uint32_t)(M.st >> 32);
-    s[W_AR * K + k] = M.ar;
-    s[W_AT * K + k] = M.at;
-    s[W_KA_LO * K + k] = (uint32_t)M.key_a;
-    s[W_KA_HI * K + k] = (uint32_t)(M.key_a >> 32);
-    s[W_KB_LO * K + k] = (uint32_t)M.key_b;
-    s[W_KB_HI * K + k] = (uint32_t)(M.key_b >> 32);
-    s[W_UID_LEN * K + k] = M.uid_len;
-    s[W_FLAGS * K + k] = M.flags;
-    s[(W_UID0 + 0) * K + k] = M.u0, s[(W_UID0 + 1) * K + k] = M.u1, s[(W_UID0 + 2) * K + k] = M.u2, s[(W_UID0 + 3) * K + k] = M.u3;
-    s[(W_UID0 + 4) * K + k] = M.u4, s[(W_UID0 + 5) * K + k] = M.u5, s[(W_UID0 + 6) * K + k] = M.u6, s[(W_UID0 + 7) * K + k] = M.u7;
-}
-
 __global__ __launch_bounds__(THREADS) void k_multi_commands(Args A) {
     const frames::MultiArgs &R = A.R;
     const Layout &L = A.L;
@@ -124,7 +84,7 @@ __global__ __launch_bounds__(THREADS) void k_multi_commands(Args A) {
         cbyte_off[K] = tab[2 * T + K] + tab[3 * T + K];
     }
     fsmd::Machine M;
-    load_machine(M, A.state, K, k);
+    fsmd::load_machine(M, A.state, K, k);
     {   // what the slabs did not store is lost to the machine
         const uint32_t *c = R.counts + (size_t)k * R.cnt_words;
         if (c[R.cnt_pk0] > R.cap_packets || c[R.cnt_pk0 + 1] > R.cap_packets || c[R.cnt_bits0] > R.cap_bits || c[R.cnt_bits0 + 1] > R.cap_bits)
@@ -166,7 +126,7 @@ __global__ __launch_bounds__(THREADS) void k_multi_commands(Args A) {
         else i0++;
     }
     ((uint32_t *)(buf + L.at[SEC_FLAGS]))[k] = M.flags;
-    store_machine(M, A.state, K, k);
+    fsmd::store_machine(M, A.state, K, k);
 }
 
 __global__ __launch_bounds__(256) void k_commands_init(uint32_t *state, uint32_t K, uint32_t k0, uint32_t k1) {
@@ -174,7 +134,7 @@ __global__ __launch_bounds__(256) void k_commands_init(uint32_t *state, uint32_t
     if (k >= k1 || k >= K) return;
     fsmd::Machine M;
     fsmd::machine_init(M);
-    store_machine(M, state, K, k);
+    fsmd::store_machine(M, state, K, k);
 }
 __global__ __launch_bounds__(256) void k_commands_set_keys(uint32_t *state, uint32_t K, uint32_t k0, uint32_t k1, uint64_t key_a, uint64_t key_b) {
     using namespace fsmd;

@@ -58,6 +58,7 @@
 using namespace nfc;
 
 #include "chunk_cut.h"
+#include "dev_buf.h"
 #include "host_context.h"
 #include "host_threshold.h"
 #include "host_stages.h"

@@ -4,7 +4,12 @@
 //
 // A push: the streams' (first_sample, n) and the lane order go up in one copy, ONE launch walks every stream, one copy brings
 // all counts and flags back to pinned memory, one wait.  Everything else stays in the per-stream slabs until it is read -- stream by
-// stream from the slabs, or after an nfc_multi_fetch (multi_fetch.hip.h: two launches, one copy) from the packed host copy.
+// stream from the slabs, or packed on the device and brought over in one copy: the decoder's arrays by nfc_multi_fetch
+// (multi_fetch.hip.h), the frames by nfc_multi_fetch_frames (frames.hip.h), and with command tracking on the frames and the commands of
+// every push (multi_commands.hip.h: three launches behind the push's own, nfc_multi_fetch_commands copies).
+//
+// The host side below, in the file's order: the context; its growable buffers (dev_buf.h; grow) and the layout of the three packed
+// ones (Sections: one rule, and the guard offsets the test build checks); the readers; the fetch; the frames; command tracking; the C-ABI.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -20,6 +25,7 @@
 #define NFC_HDR_KERNEL_LINKAGE static
 #include "../../include/nfc_amd.h"
 #include "launch_check.h"
+#include "dev_buf.h"
 #include "decoder_tables.h"
 #include "multi.hip.h"
 #include "multi_fetch.hip.h"
@@ -39,6 +45,24 @@ static_assert(MF_EDGES == NFC_MULTI_FETCH_EDGES && MF_SYMBOLS == NFC_MULTI_FETCH
               "the fetch kernels' arrays and records are the header's");
 static_assert(sizeof(nfc_multi_frames) == 144 && sizeof(nfc_multi_commands) == 264 && sizeof(nfc_frame) == 28, "the commands' structures are the header's");
 
+namespace {
+// a growable buffer as a member of the context: released with it
+template <class Buf>
+struct Owned : Buf {
+    Owned() = default;
+    Owned(const Owned &) = delete;
+    Owned &operator=(const Owned &) = delete;
+    ~Owned() { Buf::release(); }
+};
+// a packed buffer: on the device, its pinned twin, and where the launches that last filled the device's left GUARD_BYTES of the guard
+// word -- behind every section (Sections); empty: nowhere yet, or the buffer was replaced since
+struct Packed {
+    Owned<DevBuf> d;
+    Owned<PinBuf> h;
+    std::vector<uint64_t> guards;
+};
+}  // namespace
+
 struct nfc_multi {
     nfc_params P;
     uint32_t K = 0, max_push = 0;
@@ -50,46 +74,45 @@ struct nfc_multi {
     hipStream_t st = nullptr;
     hipEvent_t ev[2] = {nullptr, nullptr};
     int timing = 0;
+    // allocated once, by nfc_multi_create
     std::vector<void *> dev;   // every device allocation
     uint8_t *h_up = nullptr;   // pinned: first_sample (u64) | n (u32) | order (u32), K each
     uint8_t *d_up = nullptr;
     uint32_t *h_counts = nullptr;   // pinned mirror of the counts
     uint8_t *d_blob = nullptr, *h_blob = nullptr;   // one stream's state (k_multi_state_io)
     size_t blob_bytes = 0;
-    uint8_t *h_stage = nullptr, *d_stage = nullptr;   // nfc_multi_push: the host arrays packed, and their place on the device
-    size_t stage_cap = 0;
-    uint8_t *h_read = nullptr;   // pinned staging of the readers
-    size_t read_cap = 0;
-    std::vector<uint64_t> nseen, g0;   // samples consumed so far / before the last push, per stream
-    std::vector<uint32_t> last_n;
     std::vector<std::pair<void *, size_t>> guards;   // (slab, row stride in bytes) -- rows end in GUARD_BYTES of the guard word
     std::vector<size_t> guard_row;                   // payload bytes per row
+    // the streams
+    std::vector<uint64_t> nseen, g0;   // samples consumed so far / before the last push, per stream
+    std::vector<uint32_t> last_n;
     uint8_t canon[16];
     bool have_outputs = false;
-    // the fetch (multi_fetch.hip.h): the packed buffer on the device and its pinned twin, the prefix tables, what the host copy holds
-    uint8_t *d_fetch = nullptr, *h_fetch = nullptr;
-    size_t d_fetch_cap = 0, h_fetch_cap = 0;
-    uint64_t *d_ftable = nullptr, *h_ftable = nullptr;   // [MF_ARRAYS][K + 1]; the host's is followed by base[K]
-    uint32_t fetched = 0;                                // NFC_MULTI_FETCH_* bits the host copy serves; 0: none (a push, a reset)
-    FetchLayout flay;                                    // of the last fetch that copied anything
-    bool fetch_guarded = false;                          // d_fetch holds guards at flay's places
+    // grown when a call needs more (grow), released with the context
+    Owned<PinBuf> h_stage;   // nfc_multi_push: the host arrays packed ...
+    Owned<DevBuf> d_stage;   // ... and their place on the device
+    Owned<PinBuf> h_read;    // staging of the per-stream readers
+    // the fetch (multi_fetch.hip.h): the packed buffer, the prefix tables, what the host copy holds
+    Packed fetch;
+    Owned<DevBuf> d_ftable;   // [MF_ARRAYS][K + 1]
+    Owned<PinBuf> h_ftable;   // the same, followed by base[K]
+    uint32_t fetched = 0;     // NFC_MULTI_FETCH_* bits the host copy serves; 0: none (a push, a reset)
     nfc_multi_fetched fout;
-    // the frames (frames.hip.h, nfc_multi_fetch_frames): a packed buffer and a pinned twin of their own -- a fetch and a frame fetch do
-    // not end each other's pointers; the pinned one is followed by base[K]
-    uint8_t *d_frames = nullptr, *h_frames = nullptr;
-    size_t d_frames_cap = 0, h_frames_cap = 0;
-    frames::MultiLayout frlay;
-    bool frames_guarded = false;
-    // command tracking (multi_commands.hip.h): the machines' words on the device, allocated when tracking is first asked for; the
-    // buffer every tracked push fills -- the frames' part, then the commands' sections -- and its pinned twin, followed by base[K]
+    // the frames (frames.hip.h, nfc_multi_fetch_frames): a packed buffer of their own -- a fetch and a frame fetch do not end each
+    // other's pointers; the pinned one is followed by base[K]
+    Packed frames;
+    // command tracking (multi_commands.hip.h): the machines' words on the device and one machine's blob, allocated when tracking is
+    // first asked for; the buffer every tracked push fills -- the frames' part, then the commands' sections -- and its pinned twin,
+    // followed by base[K]
     enum CmdState { CMD_NONE, CMD_EMPTY, CMD_LAUNCHED };   // of the last push: not tracked (or reset since) / nothing stored / three launches
     bool track = false;
-    uint32_t *d_fsm = nullptr, *d_fsm_blob = nullptr, *h_fsm_blob = nullptr;
-    uint8_t *d_cmd = nullptr, *h_cmd = nullptr;
-    size_t d_cmd_cap = 0, h_cmd_cap = 0, cmd_bytes = 0;
+    Owned<DevBuf> d_fsm, d_fsm_blob;
+    Owned<PinBuf> h_fsm_blob;
+    Packed cmd;
+    size_t cmd_bytes = 0;
     CmdState cmd_state = CMD_NONE;
-    bool cmd_fetched = false, cmd_guarded = false, cmd_timed = false;
-    frames::MultiLayout cmd_frlay;
+    bool cmd_fetched = false, cmd_timed = false;
+    frames::MultiLayout cmd_frlay;   // of the last push that stored anything, as cmd_lay, cmd_nfr and cmd_room
     commands::Layout cmd_lay;
     uint64_t cmd_nfr[2] = {0, 0}, cmd_room[2] = {0, 0};
     hipEvent_t evc[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -178,29 +201,71 @@ __global__ __launch_bounds__(256) void k_multi_guard_check(const uint8_t *slab, 
     if (mine) atomicAdd(bad, mine);
 }
 
-int ensure_read(nfc_multi *m, size_t bytes) {
-    if (m->read_cap >= bytes) return NFC_OK;
-    if (m->h_read) (void)hipHostFree(m->h_read);
-    m->h_read = nullptr;
-    m->read_cap = 0;
-    const size_t cap = bytes + bytes / 2 + 4096;
-    MCHK(m, hipHostMalloc((void **)&m->h_read, cap, hipHostMallocDefault));
-    m->read_cap = cap;
+size_t up16(size_t v) { return (v + 15u) & ~(size_t)15u; }
+
+// A buffer for `bytes` of the call `fn`: as it is when it holds them, otherwise released and allocated anew with half as much again (or,
+// for what never changes its size, exactly).  Returns 0: as it was; 1: another buffer -- nothing of the old one's contents is there;
+// NFC_ERR_NOMEM: the too-small buffer is gone and the context is otherwise as it was.
+const char *memory_of(const DevBuf &) { return "device"; }
+const char *memory_of(const PinBuf &) { return "pinned host"; }
+template <class Buf>
+int grow(nfc_multi *m, Buf &b, size_t bytes, const char *fn, bool headroom = true) {
+    if (b.cap >= bytes) return 0;
+    b.release();
+    const size_t cap = headroom ? bytes + bytes / 2 + 4096 : bytes;
+    if (b.ensure(cap) == hipSuccess) return 1;
+    (void)hipGetLastError();
+    return mfail(m, NFC_ERR_NOMEM, "%s: no %s memory for %zu bytes", fn, memory_of(b), cap);
+}
+// ... of a packed buffer's device side, for the launches that fill it: another buffer holds no guards
+int grow_packed(nfc_multi *m, Packed &p, size_t bytes, const char *fn) {
+    const int g = grow(m, p.d, bytes, fn);
+    if (g) p.guards.clear();
+    return g < 0 ? g : NFC_OK;
+}
+
+// The sections of a packed buffer, one after the other: each starts on 16 bytes and has GUARD_BYTES of the guard word behind its end.
+// `at` is where the next one starts -- in the end the bytes used -- and `guards` every end so far.
+struct Sections {
+    size_t at;
+    std::vector<uint64_t> guards;
+    void place(uint64_t &sec_at, uint64_t &sec_end, size_t bytes) {
+        sec_at = at;
+        sec_end = at + bytes;
+        guards.push_back(sec_end);
+        at = up16(sec_end + GUARD_BYTES);
+    }
+};
+
+// [k0, k1) of the calls that take one stream or, with -1, all of them
+int stream_range(nfc_multi *m, int64_t stream, uint32_t &k0, uint32_t &k1) {
+    if (stream < -1 || stream >= (int64_t)m->K) return mfail(m, NFC_ERR_ARG, "stream %lld out of range (n_streams %u)", (long long)stream, m->K);
+    k0 = stream < 0 ? 0u : (uint32_t)stream;
+    k1 = stream < 0 ? m->K : (uint32_t)stream + 1u;
     return NFC_OK;
 }
 
+// the records a packing kernel left with idx batch-local, `off` [K + 1] their offset table: the stream's base is added here, over the few
+// records there are
+template <class Rec>
+void add_base(Rec *rec, const uint64_t *off, const uint64_t *base, uint32_t K) {
+    for (uint32_t k = 0; k < K; k++)
+        if (base[k])
+            for (uint64_t i = off[k]; i < off[k + 1]; i++) rec[i].idx += base[k];
+}
+
 // [first, first + n) of a stream's row, n cut to what the slab stores and the caller's room
-int read_row(nfc_multi *m, const void *slab, size_t stride_entries, size_t esz, uint32_t stream, size_t stored, size_t first, void *out,
+int read_row(nfc_multi *m, const char *fn, const void *slab, size_t stride_entries, size_t esz, uint32_t stream, size_t stored, size_t first, void *out,
              size_t cap, size_t *n_out) {
     size_t n = 0;
     if (first < stored) n = std::min(cap, stored - first);
     if (n && !out) return mfail(m, NFC_ERR_ARG, "null output");
     if (n) {
-        if (int rc = ensure_read(m, n * esz)) return rc;
+        if (grow(m, m->h_read, n * esz, fn) < 0) return NFC_ERR_NOMEM;
         m->stats.n_reads_device++;
-        MCHK(m, hipMemcpyAsync(m->h_read, (const char *)slab + ((size_t)stream * stride_entries + first) * esz, n * esz, hipMemcpyDeviceToHost, m->st));
+        MCHK(m, hipMemcpyAsync(m->h_read.p, (const char *)slab + ((size_t)stream * stride_entries + first) * esz, n * esz, hipMemcpyDeviceToHost, m->st));
         MCHK(m, hipStreamSynchronize(m->st));
-        memcpy(out, m->h_read, n * esz);
+        memcpy(out, m->h_read.p, n * esz);
     }
     if (n_out) *n_out = n;
     return NFC_OK;
@@ -214,58 +279,10 @@ int check_stream(nfc_multi *m, uint32_t stream, bool outputs) {
 }
 
 // ---- the fetch ----
-const uint64_t *foff(const nfc_multi *m, int a) { return m->h_ftable + (size_t)a * ((size_t)m->K + 1); }
+const uint64_t *foff(const nfc_multi *m, int a) { return m->h_ftable.as<uint64_t>() + (size_t)a * ((size_t)m->K + 1); }
 
 // whether the host copy of the last fetch serves the arrays `bit` stands for
 bool served(const nfc_multi *m, uint32_t bit) { return (m->fetched & bit) != 0; }
-
-size_t up16(size_t v) { return (v + 15u) & ~(size_t)15u; }
-
-// the pinned and the device buffer for `bytes`, grown geometrically (ensure_read); a failure leaves the context as it was, less the
-// buffer that was too small
-int ensure_fetch(nfc_multi *m, size_t bytes) {
-    if (m->h_fetch_cap < bytes) {
-        if (m->h_fetch) (void)hipHostFree(m->h_fetch);
-        m->h_fetch = nullptr;
-        m->h_fetch_cap = 0;
-        const size_t cap = bytes + bytes / 2 + 4096;
-        if (hipHostMalloc((void **)&m->h_fetch, cap, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            m->h_fetch = nullptr;
-            return mfail(m, NFC_ERR_NOMEM, "nfc_multi_fetch: no pinned host memory for %zu bytes", cap);
-        }
-        m->h_fetch_cap = cap;
-    }
-    if (m->d_fetch_cap < bytes) {
-        if (m->d_fetch) (void)hipFree(m->d_fetch);
-        m->d_fetch = nullptr;
-        m->d_fetch_cap = 0;
-        m->fetch_guarded = false;
-        const size_t cap = bytes + bytes / 2 + 4096;
-        if (hipMalloc((void **)&m->d_fetch, cap) != hipSuccess) {
-            (void)hipGetLastError();
-            m->d_fetch = nullptr;
-            return mfail(m, NFC_ERR_NOMEM, "nfc_multi_fetch: no device memory for %zu bytes", cap);
-        }
-        m->d_fetch_cap = cap;
-    }
-    return NFC_OK;
-}
-
-int ensure_ftable(nfc_multi *m) {
-    const size_t T = (size_t)m->K + 1;
-    if (!m->h_ftable && hipHostMalloc((void **)&m->h_ftable, (MF_ARRAYS * T + m->K) * 8, hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        m->h_ftable = nullptr;
-        return mfail(m, NFC_ERR_NOMEM, "nfc_multi_fetch: no pinned host memory for the offset tables (n_streams %u)", m->K);
-    }
-    if (!m->d_ftable && hipMalloc((void **)&m->d_ftable, MF_ARRAYS * T * 8) != hipSuccess) {
-        (void)hipGetLastError();
-        m->d_ftable = nullptr;
-        return mfail(m, NFC_ERR_NOMEM, "nfc_multi_fetch: no device memory for the offset tables (n_streams %u)", m->K);
-    }
-    return NFC_OK;
-}
 
 // rows [first, first + n) of stream k's part of a packed byte array, n cut as read_row cuts it
 int read_fetched(nfc_multi *m, int a, const uint8_t *section, uint32_t stream, size_t first, uint8_t *out, size_t cap, size_t *n_out) {
@@ -281,8 +298,8 @@ int read_fetched(nfc_multi *m, int a, const uint8_t *section, uint32_t stream, s
 
 // ---- the frames' packed buffer: totals (64 bytes) | table [4][K + 1] | records 0 | records 1 | bytes 0 | bytes 1 | par 0 | par 1 ----
 // The host knows every stream's frame count from its mirror of the counts, not its byte count (that takes the close rows): the byte
-// sections are laid out for the most the stored bits can give -- a frame has at most (n_bits + 1) / 9 bytes.  Returns the bytes used.
-size_t frames_layout(const nfc_multi *m, frames::MultiLayout &F, uint64_t n_fr[2], uint64_t room[2]) {
+// sections are laid out for the most the stored bits can give -- a frame has at most (n_bits + 1) / 9 bytes.  Returns the sections so far.
+Sections frames_layout(const nfc_multi *m, frames::MultiLayout &F, uint64_t n_fr[2], uint64_t room[2]) {
     const size_t T = (size_t)m->K + 1;
     n_fr[0] = n_fr[1] = room[0] = room[1] = 0;
     for (uint32_t k = 0; k < m->K; k++) {
@@ -294,25 +311,15 @@ size_t frames_layout(const nfc_multi *m, frames::MultiLayout &F, uint64_t n_fr[2
         }
     }
     memset(&F, 0, sizeof F);
-    size_t at = up16(frames::MULTI_HEADER_BYTES + 4 * T * 8);
+    Sections S{up16(frames::MULTI_HEADER_BYTES + 4 * T * 8), {}};
     for (int t = 0; t < 2; t++) {
-        F.at_fr[t] = at;
-        F.end_fr[t] = at + n_fr[t] * sizeof(nfc_raw_frame);
-        at = up16(F.end_fr[t] + GUARD_BYTES);
+        S.place(F.at_fr[t], F.end_fr[t], n_fr[t] * sizeof(nfc_raw_frame));
         F.total_frames[t] = n_fr[t];
         F.total_bytes[t] = room[t];
     }
-    for (int t = 0; t < 2; t++) {
-        F.at_bytes[t] = at;
-        F.end_bytes[t] = at + room[t];
-        at = up16(F.end_bytes[t] + GUARD_BYTES);
-    }
-    for (int t = 0; t < 2; t++) {
-        F.at_par[t] = at;
-        F.end_par[t] = at + room[t];
-        at = up16(F.end_par[t] + GUARD_BYTES);
-    }
-    return at;
+    for (int t = 0; t < 2; t++) S.place(F.at_bytes[t], F.end_bytes[t], room[t]);
+    for (int t = 0; t < 2; t++) S.place(F.at_par[t], F.end_par[t], room[t]);
+    return S;
 }
 frames::MultiArgs frames_args(const nfc_multi *m, uint8_t *packed, const frames::MultiLayout &F) {
     frames::MultiArgs A;
@@ -337,20 +344,12 @@ void frames_view(const nfc_multi *m, uint8_t *h, const frames::MultiLayout &F, c
     const size_t T = (size_t)K + 1;
     uint64_t *tab = (uint64_t *)(h + frames::MULTI_HEADER_BYTES);
     if (stored) {
-        bool based = false;
-        for (uint32_t k = 0; k < K; k++) based = based || base[k] != 0;
         for (int t = 0; t < 2; t++) {
             f.frames[t] = (const nfc_raw_frame *)(h + F.at_fr[t]);
             f.bytes[t] = h + F.at_bytes[t];
             f.par[t] = h + F.at_par[t];
+            add_base((nfc_raw_frame *)(h + F.at_fr[t]), tab + (size_t)t * T, base, K);
         }
-        if (based)   // (the device left idx batch-local: the stream's base is added here, over the few frames there are)
-            for (int t = 0; t < 2; t++) {
-                nfc_raw_frame *fr = (nfc_raw_frame *)(h + F.at_fr[t]);
-                const uint64_t *off = tab + (size_t)t * T;
-                for (uint32_t k = 0; k < K; k++)
-                    for (uint64_t i = off[k]; i < off[k + 1]; i++) fr[i].idx += base[k];
-            }
     } else {
         memset(tab, 0, 4 * T * 8);
     }
@@ -361,27 +360,29 @@ void frames_view(const nfc_multi *m, uint8_t *h, const frames::MultiLayout &F, c
     f.base = base;
 }
 
+// the header of a host copy `h` of the frames' part against what the host laid out
+int check_frame_totals(nfc_multi *m, const char *fn, const uint8_t *h, const uint64_t n_fr[2], const uint64_t room[2]) {
+    const uint64_t *dev_total = (const uint64_t *)h;
+    for (int t = 0; t < 2; t++)
+        if (dev_total[t] != n_fr[t] || dev_total[2 + t] > room[t])
+            return mfail(m, NFC_ERR_INTERNAL, "%s: type %d: the device counts %llu frames and %llu bytes, the host %llu frames and room for %llu bytes", fn, t,
+                         (unsigned long long)dev_total[t], (unsigned long long)dev_total[2 + t], (unsigned long long)n_fr[t], (unsigned long long)room[t]);
+    return NFC_OK;
+}
+
 // ---- command tracking ----
 // the machines' words, the blob of one machine and the events, when tracking, keys or a machine's state are first asked for: a context that
 // never does allocates and launches what it always did
-int ensure_fsm(nfc_multi *m) {
-    if (m->d_fsm) return NFC_OK;
-    uint32_t *d = nullptr, *db = nullptr, *hb = nullptr;
-    if (hipMalloc((void **)&d, (size_t)fsmd::W_WORDS * m->K * 4) != hipSuccess || hipMalloc((void **)&db, 256) != hipSuccess ||
-        hipHostMalloc((void **)&hb, 256, hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        if (d) (void)hipFree(d);
-        if (db) (void)hipFree(db);
-        return mfail(m, NFC_ERR_NOMEM, "no memory for the protocol machines of %u streams", m->K);
-    }
+int ensure_fsm(nfc_multi *m, const char *fn) {
+    if (m->d_fsm.p) return NFC_OK;
+    if (grow(m, m->d_fsm_blob, 256, fn, false) < 0 || grow(m, m->h_fsm_blob, 256, fn, false) < 0) return NFC_ERR_NOMEM;
     for (hipEvent_t &e : m->evc)
-        if (hipEventCreate(&e) != hipSuccess) {
+        if (!e && hipEventCreate(&e) != hipSuccess) {
             (void)hipGetLastError();
-            (void)hipFree(d), (void)hipFree(db), (void)hipHostFree(hb);
             return mfail(m, NFC_ERR_DEVICE, "hipEventCreate failed");
         }
-    m->d_fsm = d, m->d_fsm_blob = db, m->h_fsm_blob = hb;
-    commands::launch_init(m->d_fsm, m->K, 0, m->K, m->st);
+    if (grow(m, m->d_fsm, (size_t)fsmd::W_WORDS * m->K * 4, fn, false) < 0) return NFC_ERR_NOMEM;   // (the last: with it everything is there)
+    commands::launch_init(m->d_fsm.as<uint32_t>(), m->K, 0, m->K, m->st);
     return launch_ok(m);
 }
 
@@ -389,9 +390,9 @@ int ensure_fsm(nfc_multi *m) {
 int enqueue_commands(nfc_multi *m) {
     m->cmd_state = nfc_multi::CMD_NONE;
     m->cmd_fetched = false;
-    if (int rc = ensure_fsm(m)) return rc;
+    if (int rc = ensure_fsm(m, "nfc_multi_push")) return rc;
     frames::MultiLayout F;
-    const size_t fr_bytes = frames_layout(m, F, m->cmd_nfr, m->cmd_room);
+    Sections S = frames_layout(m, F, m->cmd_nfr, m->cmd_room);
     if (m->cmd_nfr[0] + m->cmd_nfr[1] == 0) {   // (the buffer, its layouts and its guards stay those of the last push that stored anything)
         m->cmd_state = nfc_multi::CMD_EMPTY;
         return NFC_OK;
@@ -405,40 +406,37 @@ int enqueue_commands(nfc_multi *m) {
     L.total_bytes = m->cmd_room[0] + m->cmd_room[1];
     const size_t sizes[commands::SEC_COUNT] = {T * 8, T * 8, (size_t)K * 4, (size_t)L.total_cmds * sizeof(nfc_frame), (size_t)L.total_cmds * 4,
                                                (size_t)L.total_bytes, (size_t)L.total_bytes * 2};
-    size_t at = fr_bytes;
-    for (int s = 0; s < commands::SEC_COUNT; s++) {
-        L.at[s] = at;
-        L.end[s] = at + sizes[s];
-        at = up16(L.end[s] + GUARD_BYTES);
-    }
-    const size_t bytes = at;
-    if (m->d_cmd_cap < bytes) {
-        if (m->d_cmd) (void)hipFree(m->d_cmd);
-        m->d_cmd = nullptr;
-        m->d_cmd_cap = 0;
-        m->cmd_guarded = false;
-        const size_t cap = bytes + bytes / 2 + 4096;
-        if (hipMalloc((void **)&m->d_cmd, cap) != hipSuccess) {
-            (void)hipGetLastError();
-            m->d_cmd = nullptr;
-            return mfail(m, NFC_ERR_NOMEM, "command tracking: no device memory for %zu bytes", cap);
-        }
-        m->d_cmd_cap = cap;
-    }
+    for (int s = 0; s < commands::SEC_COUNT; s++) S.place(L.at[s], L.end[s], sizes[s]);
+    const size_t bytes = S.at;
+    if (int rc = grow_packed(m, m->cmd, bytes, "nfc_multi_push")) return rc;
     commands::Args A;
-    A.R = frames_args(m, m->d_cmd, F);
-    A.state = m->d_fsm;
+    A.R = frames_args(m, m->cmd.d.as<uint8_t>(), F);
+    A.state = m->d_fsm.as<uint32_t>();
     A.L = L;
     const bool timed = m->timing != 0;
     frames::launch_multi(A.R, m->st, timed ? m->evc[0] : nullptr, timed ? m->evc[1] : nullptr);
     commands::launch(A, m->st, timed ? m->evc[2] : nullptr, timed ? m->evc[3] : nullptr);
+    m->cmd.guards = std::move(S.guards);
     m->cmd_timed = timed;
     m->cmd_bytes = bytes;
-    m->cmd_guarded = true;
     if (int rc = launch_ok(m)) return rc;
     m->cmd_state = nfc_multi::CMD_LAUNCHED;
     m->stats.n_launches += 3;
     return NFC_OK;
+}
+
+// stream k's counts and flags of the last push, from the pinned mirror
+void counts_of(const nfc_multi *m, uint32_t k, nfc_counts &o, uint32_t *flags) {
+    const uint32_t *c = m->h_counts + (size_t)k * CNT_WORDS;
+    o.n_samples = m->last_n[k];
+    o.n_edges = c[CNT_EDGES];
+    o.n_symbols[0] = c[CNT_SYM0];
+    o.n_symbols[1] = c[CNT_SYM1];
+    o.n_packets[0] = c[CNT_PK0];
+    o.n_packets[1] = c[CNT_PK1];
+    o.n_packet_bits[0] = c[CNT_PKBITS0];
+    o.n_packet_bits[1] = c[CNT_PKBITS1];
+    if (flags) *flags = c[CNT_FLAGS];
 }
 
 int state_io(nfc_multi *m, uint32_t k, int set) {
@@ -456,23 +454,14 @@ void nfc_multi_destroy(nfc_multi *m) {
     (void)hipSetDevice(m->P.device);
     if (m->st) (void)hipStreamSynchronize(m->st);
     for (void *p : m->dev) (void)hipFree(p);
-    if (m->d_stage) (void)hipFree(m->d_stage);
-    if (m->d_fetch) (void)hipFree(m->d_fetch);
-    if (m->d_ftable) (void)hipFree(m->d_ftable);
-    if (m->d_frames) (void)hipFree(m->d_frames);
-    if (m->h_frames) (void)hipHostFree(m->h_frames);
-    for (void *p : {(void *)m->d_fsm, (void *)m->d_fsm_blob, (void *)m->d_cmd})
-        if (p) (void)hipFree(p);
-    for (void *p : {(void *)m->h_fsm_blob, (void *)m->h_cmd})
-        if (p) (void)hipHostFree(p);
     for (hipEvent_t e : m->evc)
         if (e) (void)hipEventDestroy(e);
-    for (uint8_t *p : {m->h_up, (uint8_t *)m->h_counts, m->h_blob, m->h_stage, m->h_read, m->h_fetch, (uint8_t *)m->h_ftable})
+    for (uint8_t *p : {m->h_up, (uint8_t *)m->h_counts, m->h_blob})
         if (p) (void)hipHostFree(p);
     for (hipEvent_t e : m->ev)
         if (e) (void)hipEventDestroy(e);
     if (m->st) (void)hipStreamDestroy(m->st);
-    delete m;
+    delete m;   // (and with it the buffers that grew)
 }
 
 int nfc_multi_create(const nfc_params *p, const nfc_multi_config *c, nfc_multi **out) {
@@ -515,7 +504,6 @@ int nfc_multi_create(const nfc_params *p, const nfc_multi_config *c, nfc_multi *
     m->bps = kind_bytes(p->input_kind);
     memset(&m->stats, 0, sizeof m->stats);
     memset(&m->fout, 0, sizeof m->fout);
-    memset(&m->flay, 0, sizeof m->flay);
     memset(&m->cout, 0, sizeof m->cout);
     const uint32_t K = m->K;
     // Capacities per stream and push.  Entries are 6-13 % of the samples on every capture of this tree's generators (the densest:
@@ -726,28 +714,16 @@ int nfc_multi_push(nfc_multi *m, const void *const *host_ptrs, const uint32_t *n
     }
     if (hipSetDevice(m->P.device) != hipSuccess) return mfail(m, NFC_ERR_DEVICE, "hipSetDevice failed");
     const size_t bytes = (size_t)total * m->bps;
-    if (m->stage_cap < bytes) {
-        if (m->h_stage) (void)hipHostFree(m->h_stage);
-        if (m->d_stage) (void)hipFree(m->d_stage);
-        m->h_stage = m->d_stage = nullptr;
-        m->stage_cap = 0;
-        const size_t cap = bytes + bytes / 4 + 4096;
-        MCHK(m, hipHostMalloc((void **)&m->h_stage, cap, hipHostMallocDefault));
-        if (hipMalloc((void **)&m->d_stage, cap) != hipSuccess) {
-            (void)hipGetLastError();
-            return mfail(m, NFC_ERR_NOMEM, "no device memory to stage %zu input bytes", cap);
-        }
-        m->stage_cap = cap;
-    }
+    if (grow(m, m->h_stage, bytes, "nfc_multi_push") < 0 || grow(m, m->d_stage, bytes, "nfc_multi_push") < 0) return NFC_ERR_NOMEM;
     std::vector<uint64_t> first(K);
     uint64_t at = 0;
     for (uint32_t k = 0; k < K; k++) {
         first[k] = at;
-        if (n[k]) memcpy(m->h_stage + at * m->bps, host_ptrs[k], (size_t)n[k] * m->bps);
+        if (n[k]) memcpy(m->h_stage.as<uint8_t>() + at * m->bps, host_ptrs[k], (size_t)n[k] * m->bps);
         at += n[k];
     }
-    if (bytes) MCHK(m, hipMemcpyAsync(m->d_stage, m->h_stage, bytes, hipMemcpyHostToDevice, m->st));
-    return nfc_multi_push_device(m, bytes ? m->d_stage : nullptr, first.data(), n);
+    if (bytes) MCHK(m, hipMemcpyAsync(m->d_stage.p, m->h_stage.p, bytes, hipMemcpyHostToDevice, m->st));
+    return nfc_multi_push_device(m, bytes ? m->d_stage.p : nullptr, first.data(), n);
 }
 
 int nfc_multi_get_counts(nfc_multi *m, uint32_t stream, nfc_counts *out, uint32_t *flags_out) {
@@ -755,17 +731,7 @@ int nfc_multi_get_counts(nfc_multi *m, uint32_t stream, nfc_counts *out, uint32_
     if (!out) return mfail(m, NFC_ERR_ARG, "null output");
     if (stream >= m->K) return mfail(m, NFC_ERR_ARG, "stream %u out of range (n_streams %u)", stream, m->K);
     if (!m->have_outputs) return mfail(m, NFC_ERR_STATE, "no completed push");
-    const uint32_t *c = m->h_counts + (size_t)stream * CNT_WORDS;
-    memset(out, 0, sizeof *out);
-    out->n_samples = m->last_n[stream];
-    out->n_edges = c[CNT_EDGES];
-    out->n_symbols[0] = c[CNT_SYM0];
-    out->n_symbols[1] = c[CNT_SYM1];
-    out->n_packets[0] = c[CNT_PK0];
-    out->n_packets[1] = c[CNT_PK1];
-    out->n_packet_bits[0] = c[CNT_PKBITS0];
-    out->n_packet_bits[1] = c[CNT_PKBITS1];
-    if (flags_out) *flags_out = c[CNT_FLAGS];
+    counts_of(m, stream, *out, flags_out);
     return NFC_OK;
 }
 
@@ -773,19 +739,7 @@ int nfc_multi_get_counts_all(nfc_multi *m, nfc_counts *out, uint32_t *flags_out)
     if (!m) return NFC_ERR_ARG;
     if (!out) return mfail(m, NFC_ERR_ARG, "null output");
     if (!m->have_outputs) return mfail(m, NFC_ERR_STATE, "no completed push");
-    for (uint32_t k = 0; k < m->K; k++) {
-        const uint32_t *c = m->h_counts + (size_t)k * CNT_WORDS;
-        nfc_counts &o = out[k];
-        o.n_samples = m->last_n[k];
-        o.n_edges = c[CNT_EDGES];
-        o.n_symbols[0] = c[CNT_SYM0];
-        o.n_symbols[1] = c[CNT_SYM1];
-        o.n_packets[0] = c[CNT_PK0];
-        o.n_packets[1] = c[CNT_PK1];
-        o.n_packet_bits[0] = c[CNT_PKBITS0];
-        o.n_packet_bits[1] = c[CNT_PKBITS1];
-        if (flags_out) flags_out[k] = c[CNT_FLAGS];
-    }
+    for (uint32_t k = 0; k < m->K; k++) counts_of(m, k, out[k], flags_out ? flags_out + k : nullptr);
     return NFC_OK;
 }
 
@@ -796,13 +750,13 @@ int nfc_multi_fetch(nfc_multi *m, uint32_t what, nfc_multi_fetched *out) {
     if (!m->have_outputs) return mfail(m, NFC_ERR_STATE, "no completed push");
     if (hipSetDevice(m->P.device) != hipSuccess) return mfail(m, NFC_ERR_DEVICE, "hipSetDevice failed");
     m->fetched = 0;
-    if (int rc = ensure_ftable(m)) return rc;
     const uint32_t K = m->K;
     const size_t T = (size_t)K + 1;
+    if (grow(m, m->h_ftable, (MF_ARRAYS * T + K) * 8, "nfc_multi_fetch", false) < 0 || grow(m, m->d_ftable, MF_ARRAYS * T * 8, "nfc_multi_fetch", false) < 0)
+        return NFC_ERR_NOMEM;
     // the same table the scan kernel forms, from the pinned mirror of the counts: it sizes the buffers and is the caller's off[]
-    uint64_t *tab = m->h_ftable, *base = m->h_ftable + MF_ARRAYS * T;
+    uint64_t *tab = m->h_ftable.as<uint64_t>(), *base = tab + MF_ARRAYS * T;
     Amounts run = {0, 0, 0, 0, 0, 0, 0};
-    bool based = false;
     for (uint32_t k = 0; k < K; k++) {
         const Amounts s = stored_amounts(m->h_counts + (size_t)k * CNT_WORDS, m->C, what);
         tab[0 * T + k] = run.a0;
@@ -816,7 +770,6 @@ int nfc_multi_fetch(nfc_multi *m, uint32_t what, nfc_multi_fetched *out) {
         MF_EACH(X)
 #undef X
         base[k] = m->g0[k];
-        based = based || m->g0[k] != 0;
     }
     const uint64_t total[MF_ARRAYS] = {run.a0, run.a1, run.a2, run.a3, run.a4, run.a5, run.a6};
     for (int a = 0; a < MF_ARRAYS; a++) tab[a * T + K] = total[a];
@@ -830,43 +783,38 @@ int nfc_multi_fetch(nfc_multi *m, uint32_t what, nfc_multi_fetched *out) {
     uint64_t any = 0;
     for (int a = 0; a < MF_ARRAYS; a++) any |= total[a];
     if (any) {
-        // sections: each starts on 16 bytes and is followed by GUARD_BYTES of the guard word
         FetchLayout F;
-        size_t at = MF_HEADER_BYTES;
-#define SECTION(name, entries, esz)            \
-    F.at_##name = at;                          \
-    F.end_##name = at + (size_t)(entries) * (esz); \
-    at = up16(F.end_##name + GUARD_BYTES);
-        SECTION(epos, total[0], 4)
-        SECTION(ecode, total[0], 2)
-        SECTION(sym0, total[1], 1)
-        SECTION(sym1, total[2], 1)
-        SECTION(pk0, total[3], sizeof(nfc_packet))
-        SECTION(pk1, total[4], sizeof(nfc_packet))
-        SECTION(bits0, total[5], 1)
-        SECTION(bits1, total[6], 1)
-#undef SECTION
+        Sections S{MF_HEADER_BYTES, {}};
+        S.place(F.at_epos, F.end_epos, (size_t)total[0] * 4);
+        S.place(F.at_ecode, F.end_ecode, (size_t)total[0] * 2);
+        S.place(F.at_sym0, F.end_sym0, (size_t)total[1]);
+        S.place(F.at_sym1, F.end_sym1, (size_t)total[2]);
+        S.place(F.at_pk0, F.end_pk0, (size_t)total[3] * sizeof(nfc_packet));
+        S.place(F.at_pk1, F.end_pk1, (size_t)total[4] * sizeof(nfc_packet));
+        S.place(F.at_bits0, F.end_bits0, (size_t)total[5]);
+        S.place(F.at_bits1, F.end_bits1, (size_t)total[6]);
         F.total = run;
-        const size_t bytes = at;
-        if (int rc = ensure_fetch(m, bytes)) return rc;
+        const size_t bytes = S.at;
+        if (grow(m, m->fetch.h, bytes, "nfc_multi_fetch") < 0) return NFC_ERR_NOMEM;
+        if (int rc = grow_packed(m, m->fetch, bytes, "nfc_multi_fetch")) return rc;
+        uint8_t *h = m->fetch.h.as<uint8_t>(), *d = m->fetch.d.as<uint8_t>();
         GatherArgs G;
         G.O = m->A.O;
         G.C = m->C;
         G.K = K;
-        G.table = m->d_ftable;
-        G.packed = m->d_fetch;
+        G.table = m->d_ftable.as<uint64_t>();
+        G.packed = d;
         G.F = F;
         const unsigned wgs = std::min<unsigned>(MF_GATHER_MAX_WG, (K + MF_GATHER_THREADS / 64 - 1) / (MF_GATHER_THREADS / 64));
         if (m->timing) MCHK(m, hipEventRecord(m->ev[0], m->st));
-        NFC_LAUNCH(k_multi_fetch_scan, dim3(1), dim3(MF_SCAN_THREADS), 0, m->st, (const uint32_t *)m->A.O.counts, m->C, K, what, m->d_ftable, m->d_fetch, F);
+        NFC_LAUNCH(k_multi_fetch_scan, dim3(1), dim3(MF_SCAN_THREADS), 0, m->st, (const uint32_t *)m->A.O.counts, m->C, K, what, m->d_ftable.as<uint64_t>(), d, F);
         NFC_LAUNCH(k_multi_fetch_gather, dim3(wgs), dim3(MF_GATHER_THREADS), 0, m->st, G);
         if (m->timing) MCHK(m, hipEventRecord(m->ev[1], m->st));
-        m->flay = F;
-        m->fetch_guarded = true;
-        MCHK(m, hipMemcpyAsync(m->h_fetch, m->d_fetch, bytes, hipMemcpyDeviceToHost, m->st));
+        m->fetch.guards = std::move(S.guards);
+        MCHK(m, hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, m->st));
         MCHK(m, hipStreamSynchronize(m->st));
         if (int rc = launch_ok(m)) return rc;
-        const uint64_t *dev_total = (const uint64_t *)m->h_fetch;
+        const uint64_t *dev_total = (const uint64_t *)h;
         for (int a = 0; a < MF_ARRAYS; a++)
             if (dev_total[a] != total[a])
                 return mfail(m, NFC_ERR_INTERNAL, "nfc_multi_fetch: the device's total of array %d is %llu, the host's %llu", a, (unsigned long long)dev_total[a],
@@ -878,7 +826,6 @@ int nfc_multi_fetch(nfc_multi *m, uint32_t what, nfc_multi_fetched *out) {
         }
         f.n_launches = 2;
         f.bytes_copied = bytes;
-        uint8_t *h = m->h_fetch;
         f.edge_pos = (const uint32_t *)(h + F.at_epos);
         f.edge_code = (const uint16_t *)(h + F.at_ecode);
         f.symbols[0] = h + F.at_sym0;
@@ -887,14 +834,8 @@ int nfc_multi_fetch(nfc_multi *m, uint32_t what, nfc_multi_fetched *out) {
         f.packets[1] = (const nfc_packet *)(h + F.at_pk1);
         f.packet_bits[0] = h + F.at_bits0;
         f.packet_bits[1] = h + F.at_bits1;
-        // the gather left the packets' idx batch-local: the stream's base is added here, over the few packets there are
-        if (based)
-            for (int t = 0; t < 2; t++) {
-                nfc_packet *pk = (nfc_packet *)(h + (t ? F.at_pk1 : F.at_pk0));
-                const uint64_t *off = foff(m, NFC_MF_PK0 + t);
-                for (uint32_t k = 0; k < K; k++)
-                    for (uint64_t i = off[k]; i < off[k + 1]; i++) pk[i].idx += base[k];
-            }
+        add_base((nfc_packet *)(h + F.at_pk0), foff(m, NFC_MF_PK0), base, K);   // (the gather left the packets' idx batch-local)
+        add_base((nfc_packet *)(h + F.at_pk1), foff(m, NFC_MF_PK1), base, K);
     }
     m->fetched = what;
     m->stats.n_fetches++;
@@ -916,49 +857,22 @@ int nfc_multi_fetch_frames(nfc_multi *m, nfc_multi_frames *out) {
     memset(&f, 0, sizeof f);
     f.n_streams = K;
     frames::MultiLayout F;
-    const size_t bytes = frames_layout(m, F, n_fr, room), host_bytes = bytes + (size_t)K * 8;
+    Sections S = frames_layout(m, F, n_fr, room);
+    const size_t bytes = S.at;
     // (the pinned buffer always: the offset tables and base[] are handed out when nothing was stored, too)
-    if (m->h_frames_cap < host_bytes) {
-        if (m->h_frames) (void)hipHostFree(m->h_frames);
-        m->h_frames = nullptr;
-        m->h_frames_cap = 0;
-        const size_t cap = host_bytes + host_bytes / 2 + 4096;
-        if (hipHostMalloc((void **)&m->h_frames, cap, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            m->h_frames = nullptr;
-            return mfail(m, NFC_ERR_NOMEM, "nfc_multi_fetch_frames: no pinned host memory for %zu bytes", cap);
-        }
-        m->h_frames_cap = cap;
-    }
-    uint8_t *h = m->h_frames;
+    if (grow(m, m->frames.h, bytes + (size_t)K * 8, "nfc_multi_fetch_frames") < 0) return NFC_ERR_NOMEM;
+    uint8_t *h = m->frames.h.as<uint8_t>();
     uint64_t *base = (uint64_t *)(h + bytes);
     for (uint32_t k = 0; k < K; k++) base[k] = m->g0[k];
     if (n_fr[0] + n_fr[1]) {
-        if (m->d_frames_cap < bytes) {
-            if (m->d_frames) (void)hipFree(m->d_frames);
-            m->d_frames = nullptr;
-            m->d_frames_cap = 0;
-            m->frames_guarded = false;
-            const size_t cap = bytes + bytes / 2 + 4096;
-            if (hipMalloc((void **)&m->d_frames, cap) != hipSuccess) {
-                (void)hipGetLastError();
-                m->d_frames = nullptr;
-                return mfail(m, NFC_ERR_NOMEM, "nfc_multi_fetch_frames: no device memory for %zu bytes", cap);
-            }
-            m->d_frames_cap = cap;
-        }
-        const frames::MultiArgs A = frames_args(m, m->d_frames, F);
+        if (int rc = grow_packed(m, m->frames, bytes, "nfc_multi_fetch_frames")) return rc;
+        const frames::MultiArgs A = frames_args(m, m->frames.d.as<uint8_t>(), F);
         frames::launch_multi(A, m->st, m->timing ? m->ev[0] : nullptr, m->timing ? m->ev[1] : nullptr);
-        m->frlay = F;
-        m->frames_guarded = true;
-        MCHK(m, hipMemcpyAsync(h, m->d_frames, bytes, hipMemcpyDeviceToHost, m->st));
+        m->frames.guards = std::move(S.guards);
+        MCHK(m, hipMemcpyAsync(h, m->frames.d.p, bytes, hipMemcpyDeviceToHost, m->st));
         MCHK(m, hipStreamSynchronize(m->st));
         if (int rc = launch_ok(m)) return rc;
-        const uint64_t *dev_total = (const uint64_t *)h;
-        for (int t = 0; t < 2; t++)
-            if (dev_total[t] != n_fr[t] || dev_total[2 + t] > room[t])
-                return mfail(m, NFC_ERR_INTERNAL, "nfc_multi_fetch_frames: type %d: the device counts %llu frames and %llu bytes, the host %llu frames and room for %llu bytes",
-                             t, (unsigned long long)dev_total[t], (unsigned long long)dev_total[2 + t], (unsigned long long)n_fr[t], (unsigned long long)room[t]);
+        if (int rc = check_frame_totals(m, "nfc_multi_fetch_frames", h, n_fr, room)) return rc;
         if (m->timing) {
             float ms = 0.f;
             MCHK(m, hipEventElapsedTime(&ms, m->ev[0], m->ev[1]));
@@ -989,9 +903,9 @@ int nfc_multi_read_edges(nfc_multi *m, uint32_t stream, size_t first, nfc_edge *
         pos = m->fout.edge_pos + at;
         code = m->fout.edge_code + at;
     } else {
-        if (int rc = ensure_read(m, n * 6 + 16)) return rc;
-        uint32_t *dpos = (uint32_t *)m->h_read;
-        uint16_t *dcode = (uint16_t *)(m->h_read + n * 4);
+        if (grow(m, m->h_read, n * 6 + 16, "nfc_multi_read_edges") < 0) return NFC_ERR_NOMEM;
+        uint32_t *dpos = m->h_read.as<uint32_t>();
+        uint16_t *dcode = (uint16_t *)(dpos + n);
         m->stats.n_reads_device++;
         MCHK(m, hipMemcpyAsync(dpos, m->A.O.epos + (size_t)stream * m->C.s_epos + first, n * 4, hipMemcpyDeviceToHost, m->st));
         MCHK(m, hipMemcpyAsync(dcode, m->A.O.ecode + (size_t)stream * m->C.s_ecode + first, n * 2, hipMemcpyDeviceToHost, m->st));
@@ -1019,7 +933,7 @@ int nfc_multi_read_symbols(nfc_multi *m, uint32_t stream, int type, size_t first
     if (int rc = check_stream(m, stream, true)) return rc;
     if (served(m, NFC_MULTI_FETCH_SYMBOLS)) return read_fetched(m, NFC_MF_SYM0 + type, m->fout.symbols[type], stream, first, out, cap, n_out);
     const size_t stored = std::min<size_t>(m->h_counts[(size_t)stream * CNT_WORDS + CNT_SYM0 + type], m->C.symbols);
-    return read_row(m, m->A.O.sym[type], m->C.s_symbols, 1, stream, stored, first, out, cap, n_out);
+    return read_row(m, "nfc_multi_read_symbols", m->A.O.sym[type], m->C.s_symbols, 1, stream, stored, first, out, cap, n_out);
 }
 
 int nfc_multi_read_packets(nfc_multi *m, uint32_t stream, int type, nfc_packet *out, size_t cap, size_t *n_out) {
@@ -1035,11 +949,11 @@ int nfc_multi_read_packets(nfc_multi *m, uint32_t stream, int type, nfc_packet *
         memcpy(out, m->fout.packets[type] + foff(m, NFC_MF_PK0 + type)[stream], n * sizeof(nfc_packet));
         return NFC_OK;
     }
-    if (int rc = ensure_read(m, n * 8)) return rc;
+    if (grow(m, m->h_read, n * 8, "nfc_multi_read_packets") < 0) return NFC_ERR_NOMEM;
     m->stats.n_reads_device++;
-    MCHK(m, hipMemcpyAsync(m->h_read, m->A.O.close[type] + (size_t)stream * m->C.s_packets, n * 8, hipMemcpyDeviceToHost, m->st));
+    MCHK(m, hipMemcpyAsync(m->h_read.p, m->A.O.close[type] + (size_t)stream * m->C.s_packets, n * 8, hipMemcpyDeviceToHost, m->st));
     MCHK(m, hipStreamSynchronize(m->st));
-    const uint32_t *cl = (const uint32_t *)m->h_read;
+    const uint32_t *cl = m->h_read.as<uint32_t>();
     uint32_t prev = 0;
     for (size_t i = 0; i < n; i++) {
         nfc_packet p;
@@ -1059,7 +973,7 @@ int nfc_multi_read_packet_bits(nfc_multi *m, uint32_t stream, int type, size_t f
     if (int rc = check_stream(m, stream, true)) return rc;
     if (served(m, NFC_MULTI_FETCH_PACKETS)) return read_fetched(m, NFC_MF_BITS0 + type, m->fout.packet_bits[type], stream, first, out, cap, n_out);
     const size_t stored = std::min<size_t>(m->h_counts[(size_t)stream * CNT_WORDS + CNT_BITS0 + type], m->C.bits);
-    return read_row(m, m->A.O.bits[type], m->C.s_bits, 1, stream, stored, first, out, cap, n_out);
+    return read_row(m, "nfc_multi_read_packet_bits", m->A.O.bits[type], m->C.s_bits, 1, stream, stored, first, out, cap, n_out);
 }
 
 int nfc_multi_get_state(nfc_multi *m, uint32_t stream, nfc_state_header *h, float *ring, size_t ring_cap, uint8_t *pending, size_t pending_cap) {
@@ -1149,13 +1063,13 @@ int nfc_multi_set_state(nfc_multi *m, uint32_t stream, const nfc_state_header *h
 int nfc_multi_reset(nfc_multi *m, int64_t stream) {
     if (!m) return NFC_ERR_ARG;
     LaunchScope scope(&m->launch_err);
-    if (stream < -1 || stream >= (int64_t)m->K) return mfail(m, NFC_ERR_ARG, "stream %lld out of range (n_streams %u)", (long long)stream, m->K);
+    uint32_t k0, k1;
+    if (int rc = stream_range(m, stream, k0, k1)) return rc;
     if (hipSetDevice(m->P.device) != hipSuccess) return mfail(m, NFC_ERR_DEVICE, "hipSetDevice failed");
     m->fetched = 0;
-    const uint32_t k0 = stream < 0 ? 0u : (uint32_t)stream, k1 = stream < 0 ? m->K : (uint32_t)stream + 1u;
     const size_t work = (size_t)(k1 - k0) * (size_t)m->L;
     NFC_LAUNCH(k_multi_reset, dim3((unsigned)std::min<size_t>(1024, (work + 255) / 256)), dim3(256), 0, m->st, m->A.S, m->K, k0, k1, m->L, m->A.O.counts);
-    if (m->d_fsm) commands::launch_init(m->d_fsm, m->K, k0, k1, m->st);   // the machines too, keys included, as nfc_fsm_reset
+    if (m->d_fsm.p) commands::launch_init(m->d_fsm.as<uint32_t>(), m->K, k0, k1, m->st);   // the machines too, keys included, as nfc_fsm_reset
     m->cmd_state = nfc_multi::CMD_NONE;
     m->cmd_fetched = false;
     if (int rc = launch_ok(m)) return rc;
@@ -1175,7 +1089,7 @@ int nfc_multi_track_commands(nfc_multi *m, int on) {
     LaunchScope scope(&m->launch_err);
     if (on) {
         if (hipSetDevice(m->P.device) != hipSuccess) return mfail(m, NFC_ERR_DEVICE, "hipSetDevice failed");
-        if (int rc = ensure_fsm(m)) return rc;
+        if (int rc = ensure_fsm(m, "nfc_multi_track_commands")) return rc;
     }
     m->track = on != 0;
     return NFC_OK;
@@ -1184,13 +1098,13 @@ int nfc_multi_track_commands(nfc_multi *m, int on) {
 int nfc_multi_set_keys(nfc_multi *m, int64_t stream, const uint8_t key_a[6], const uint8_t key_b[6]) {
     if (!m) return NFC_ERR_ARG;
     LaunchScope scope(&m->launch_err);
-    if (stream < -1 || stream >= (int64_t)m->K) return mfail(m, NFC_ERR_ARG, "stream %lld out of range (n_streams %u)", (long long)stream, m->K);
+    uint32_t k0, k1;
+    if (int rc = stream_range(m, stream, k0, k1)) return rc;
     if (!key_a) return mfail(m, NFC_ERR_ARG, "key_a is null");
     if (!key_b) return mfail(m, NFC_ERR_ARG, "key_b is null");
     if (hipSetDevice(m->P.device) != hipSuccess) return mfail(m, NFC_ERR_DEVICE, "hipSetDevice failed");
-    if (int rc = ensure_fsm(m)) return rc;
-    const uint32_t k0 = stream < 0 ? 0u : (uint32_t)stream, k1 = stream < 0 ? m->K : (uint32_t)stream + 1u;
-    commands::launch_set_keys(m->d_fsm, m->K, k0, k1, fsmd::key_of(key_a), fsmd::key_of(key_b), m->st);
+    if (int rc = ensure_fsm(m, "nfc_multi_set_keys")) return rc;
+    commands::launch_set_keys(m->d_fsm.as<uint32_t>(), m->K, k0, k1, fsmd::key_of(key_a), fsmd::key_of(key_b), m->st);
     return launch_ok(m);
 }
 
@@ -1200,22 +1114,13 @@ int nfc_multi_get_fsm_state(nfc_multi *m, uint32_t stream, nfc_fsm_state *st) {
     if (stream >= m->K) return mfail(m, NFC_ERR_ARG, "stream %u out of range (n_streams %u)", stream, m->K);
     if (!st) return mfail(m, NFC_ERR_ARG, "st is null");
     if (hipSetDevice(m->P.device) != hipSuccess) return mfail(m, NFC_ERR_DEVICE, "hipSetDevice failed");
-    if (int rc = ensure_fsm(m)) return rc;
-    commands::launch_io(m->d_fsm, m->K, stream, 0, m->d_fsm_blob, m->st);
+    if (int rc = ensure_fsm(m, "nfc_multi_get_fsm_state")) return rc;
+    commands::launch_io(m->d_fsm.as<uint32_t>(), m->K, stream, 0, m->d_fsm_blob.as<uint32_t>(), m->st);
     if (int rc = launch_ok(m)) return rc;
-    MCHK(m, hipMemcpyAsync(m->h_fsm_blob, m->d_fsm_blob, fsmd::W_WORDS * 4, hipMemcpyDeviceToHost, m->st));
+    MCHK(m, hipMemcpyAsync(m->h_fsm_blob.p, m->d_fsm_blob.p, fsmd::W_WORDS * 4, hipMemcpyDeviceToHost, m->st));
     MCHK(m, hipStreamSynchronize(m->st));
-    const uint32_t *w = m->h_fsm_blob;
     fsmd::Machine M;
-    M.cur_cmd = (int32_t)w[fsmd::W_CUR_CMD], M.tag_type = (int32_t)w[fsmd::W_TAG_TYPE], M.encrypted = (int32_t)w[fsmd::W_ENCRYPTED];
-    M.cur_key = (int32_t)w[fsmd::W_CUR_KEY];
-    M.st = (uint64_t)w[fsmd::W_ST_LO] | (uint64_t)w[fsmd::W_ST_HI] << 32;
-    M.ar = w[fsmd::W_AR], M.at = w[fsmd::W_AT];
-    M.key_a = (uint64_t)w[fsmd::W_KA_LO] | (uint64_t)w[fsmd::W_KA_HI] << 32;
-    M.key_b = (uint64_t)w[fsmd::W_KB_LO] | (uint64_t)w[fsmd::W_KB_HI] << 32;
-    M.uid_len = std::min<uint32_t>(w[fsmd::W_UID_LEN], fsmd::UID_CAP), M.flags = w[fsmd::W_FLAGS];
-    M.u0 = w[fsmd::W_UID0 + 0], M.u1 = w[fsmd::W_UID0 + 1], M.u2 = w[fsmd::W_UID0 + 2], M.u3 = w[fsmd::W_UID0 + 3];
-    M.u4 = w[fsmd::W_UID0 + 4], M.u5 = w[fsmd::W_UID0 + 5], M.u6 = w[fsmd::W_UID0 + 6], M.u7 = w[fsmd::W_UID0 + 7];
+    fsmd::load_machine(M, m->h_fsm_blob.as<uint32_t>(), 1, 0);
     memset(st, 0, sizeof *st);
     fsmd::machine_to_state(M, *st);
     return NFC_OK;
@@ -1228,22 +1133,13 @@ int nfc_multi_set_fsm_state(nfc_multi *m, uint32_t stream, const nfc_fsm_state *
     if (!st) return mfail(m, NFC_ERR_ARG, "st is null");
     if (const char *bad = fsmd::state_fault(*st)) return mfail(m, NFC_ERR_ARG, "st: %s", bad);
     if (hipSetDevice(m->P.device) != hipSuccess) return mfail(m, NFC_ERR_DEVICE, "hipSetDevice failed");
-    if (int rc = ensure_fsm(m)) return rc;
+    if (int rc = ensure_fsm(m, "nfc_multi_set_fsm_state")) return rc;
     MCHK(m, hipStreamSynchronize(m->st));   // (the blob may still be on its way from an earlier call)
     fsmd::Machine M;
     fsmd::machine_from_state(M, *st);
-    uint32_t *w = m->h_fsm_blob;
-    w[fsmd::W_CUR_CMD] = (uint32_t)M.cur_cmd, w[fsmd::W_TAG_TYPE] = (uint32_t)M.tag_type, w[fsmd::W_ENCRYPTED] = (uint32_t)M.encrypted;
-    w[fsmd::W_CUR_KEY] = (uint32_t)M.cur_key;
-    w[fsmd::W_ST_LO] = (uint32_t)M.st, w[fsmd::W_ST_HI] = (uint32_t)(M.st >> 32);
-    w[fsmd::W_AR] = M.ar, w[fsmd::W_AT] = M.at;
-    w[fsmd::W_KA_LO] = (uint32_t)M.key_a, w[fsmd::W_KA_HI] = (uint32_t)(M.key_a >> 32);
-    w[fsmd::W_KB_LO] = (uint32_t)M.key_b, w[fsmd::W_KB_HI] = (uint32_t)(M.key_b >> 32);
-    w[fsmd::W_UID_LEN] = M.uid_len, w[fsmd::W_FLAGS] = M.flags;
-    w[fsmd::W_UID0 + 0] = M.u0, w[fsmd::W_UID0 + 1] = M.u1, w[fsmd::W_UID0 + 2] = M.u2, w[fsmd::W_UID0 + 3] = M.u3;
-    w[fsmd::W_UID0 + 4] = M.u4, w[fsmd::W_UID0 + 5] = M.u5, w[fsmd::W_UID0 + 6] = M.u6, w[fsmd::W_UID0 + 7] = M.u7;
-    MCHK(m, hipMemcpyAsync(m->d_fsm_blob, m->h_fsm_blob, fsmd::W_WORDS * 4, hipMemcpyHostToDevice, m->st));
-    commands::launch_io(m->d_fsm, m->K, stream, 1, m->d_fsm_blob, m->st);
+    fsmd::store_machine(M, m->h_fsm_blob.as<uint32_t>(), 1, 0);
+    MCHK(m, hipMemcpyAsync(m->d_fsm_blob.p, m->h_fsm_blob.p, fsmd::W_WORDS * 4, hipMemcpyHostToDevice, m->st));
+    commands::launch_io(m->d_fsm.as<uint32_t>(), m->K, stream, 1, m->d_fsm_blob.as<uint32_t>(), m->st);
     if (int rc = launch_ok(m)) return rc;
     MCHK(m, hipStreamSynchronize(m->st));
     m->cmd_fetched = false;   // (the pointers of a fetch end here; the last push's commands stay fetchable)
@@ -1269,19 +1165,8 @@ int nfc_multi_fetch_commands(nfc_multi *m, nfc_multi_commands *out) {
     // nothing stored: [64 bytes | table [4][T] | cmd_off [T] | cbyte_off [T] | flags [K]] on the host alone
     const size_t empty_tabs = up16(frames::MULTI_HEADER_BYTES + 4 * T * 8), empty_bytes = up16(empty_tabs + 2 * T * 8 + (size_t)K * 4);
     const size_t bytes = stored ? m->cmd_bytes : empty_bytes, host_bytes = bytes + (size_t)K * 8;
-    if (m->h_cmd_cap < host_bytes) {
-        if (m->h_cmd) (void)hipHostFree(m->h_cmd);
-        m->h_cmd = nullptr;
-        m->h_cmd_cap = 0;
-        const size_t cap = host_bytes + host_bytes / 2 + 4096;
-        if (hipHostMalloc((void **)&m->h_cmd, cap, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            m->h_cmd = nullptr;
-            return mfail(m, NFC_ERR_NOMEM, "nfc_multi_fetch_commands: no pinned host memory for %zu bytes", cap);
-        }
-        m->h_cmd_cap = cap;
-    }
-    uint8_t *h = m->h_cmd;
+    if (grow(m, m->cmd.h, host_bytes, "nfc_multi_fetch_commands") < 0) return NFC_ERR_NOMEM;
+    uint8_t *h = m->cmd.h.as<uint8_t>();
     uint64_t *base = (uint64_t *)(h + bytes);
     for (uint32_t k = 0; k < K; k++) base[k] = m->g0[k];
     nfc_multi_commands &c = m->cout;
@@ -1289,15 +1174,12 @@ int nfc_multi_fetch_commands(nfc_multi *m, nfc_multi_commands *out) {
     c.n_streams = c.raw.n_streams = K;
     if (stored) {
         const commands::Layout &L = m->cmd_lay;
-        MCHK(m, hipMemcpyAsync(h, m->d_cmd, bytes, hipMemcpyDeviceToHost, m->st));
+        MCHK(m, hipMemcpyAsync(h, m->cmd.d.p, bytes, hipMemcpyDeviceToHost, m->st));
         MCHK(m, hipStreamSynchronize(m->st));
         if (int rc = launch_ok(m)) return rc;
         const uint64_t *dev_total = (const uint64_t *)h;
         const uint64_t *cmd_off = (const uint64_t *)(h + L.at[commands::SEC_CMD_OFF]), *cbyte_off = (const uint64_t *)(h + L.at[commands::SEC_CBYTE_OFF]);
-        for (int t = 0; t < 2; t++)
-            if (dev_total[t] != m->cmd_nfr[t] || dev_total[2 + t] > m->cmd_room[t])
-                return mfail(m, NFC_ERR_INTERNAL, "nfc_multi_fetch_commands: type %d: the device counts %llu frames and %llu bytes, the host %llu frames and room for %llu bytes",
-                             t, (unsigned long long)dev_total[t], (unsigned long long)dev_total[2 + t], (unsigned long long)m->cmd_nfr[t], (unsigned long long)m->cmd_room[t]);
+        if (int rc = check_frame_totals(m, "nfc_multi_fetch_commands", h, m->cmd_nfr, m->cmd_room)) return rc;
         if (cmd_off[K] != L.total_cmds || cbyte_off[K] != dev_total[2] + dev_total[3])
             return mfail(m, NFC_ERR_INTERNAL, "nfc_multi_fetch_commands: the device counts %llu commands over %llu bytes, the host %llu commands, the frames %llu bytes",
                          (unsigned long long)cmd_off[K], (unsigned long long)cbyte_off[K], (unsigned long long)L.total_cmds, (unsigned long long)(dev_total[2] + dev_total[3]));
@@ -1320,7 +1202,7 @@ int nfc_multi_fetch_commands(nfc_multi *m, nfc_multi_commands *out) {
     } else {
         memset(h, 0, empty_bytes);
         uint32_t *flags = (uint32_t *)(h + empty_tabs + 2 * T * 8);
-        MCHK(m, hipMemcpyAsync(flags, m->d_fsm + (size_t)fsmd::W_FLAGS * K, (size_t)K * 4, hipMemcpyDeviceToHost, m->st));
+        MCHK(m, hipMemcpyAsync(flags, m->d_fsm.as<uint32_t>() + (size_t)fsmd::W_FLAGS * K, (size_t)K * 4, hipMemcpyDeviceToHost, m->st));
         MCHK(m, hipStreamSynchronize(m->st));
         c.bytes_copied = (size_t)K * 4;
         c.cmd_off = (const uint64_t *)(h + empty_tabs);
@@ -1351,6 +1233,16 @@ int nfc_multi_set_timing(nfc_multi *m, int on) {
 #ifdef NFC_TEST_HOOKS
 // Test support, in the test build only and not part of the C-ABI: the damaged bytes among the guards behind every stream's row of
 // every slab (0: intact).
+// the damaged bytes among the guards of a packed buffer's device side; -1: a copy failed
+static int packed_guards_damaged(nfc_multi *m, const Packed &p) {
+    std::vector<uint8_t> g(p.guards.size() * GUARD_BYTES);
+    for (size_t s = 0; s < p.guards.size(); s++)
+        if (hipMemcpyAsync(g.data() + s * GUARD_BYTES, p.d.as<uint8_t>() + p.guards[s], GUARD_BYTES, hipMemcpyDeviceToHost, m->st) != hipSuccess) return -1;
+    if (hipStreamSynchronize(m->st) != hipSuccess) return -1;
+    int bad = 0;
+    for (size_t i = 0; i < g.size(); i++) bad += g[i] != (uint8_t)(GUARD_WORD >> (8 * ((i % GUARD_BYTES) & 3)));
+    return bad;
+}
 extern "C" int nfc_debug_multi_guards(nfc_multi *m) {
     if (!m || hipSetDevice(m->P.device) != hipSuccess) return -1;
     LaunchScope scope(&m->launch_err);
@@ -1364,37 +1256,11 @@ extern "C" int nfc_debug_multi_guards(nfc_multi *m) {
     uint32_t h = 0;
     if (launch_ok(m) || hipMemcpyAsync(m->h_blob, bad, 4, hipMemcpyDeviceToHost, m->st) != hipSuccess || hipStreamSynchronize(m->st) != hipSuccess) return -1;
     memcpy(&h, m->h_blob, 4);
-    if (m->fetch_guarded) {   // and the guard bytes behind the sections of the fetch's packed buffer, where the last fetch put them
-        const FetchLayout &F = m->flay;
-        const uint64_t ends[MF_SECTIONS] = {F.end_epos, F.end_ecode, F.end_sym0, F.end_sym1, F.end_pk0, F.end_pk1, F.end_bits0, F.end_bits1};
-        uint8_t g[MF_SECTIONS][GUARD_BYTES];
-        for (int s = 0; s < MF_SECTIONS; s++)
-            if (hipMemcpyAsync(g[s], m->d_fetch + ends[s], GUARD_BYTES, hipMemcpyDeviceToHost, m->st) != hipSuccess) return -1;
-        if (hipStreamSynchronize(m->st) != hipSuccess) return -1;
-        for (int s = 0; s < MF_SECTIONS; s++)
-            for (int b = 0; b < GUARD_BYTES; b++) h += g[s][b] != (uint8_t)(GUARD_WORD >> (8 * (b & 3)));
-    }
-    if (m->frames_guarded) {   // ... and behind the sections of the frames' packed buffer (nfc_multi_fetch_frames)
-        const frames::MultiLayout &F = m->frlay;
-        const uint64_t ends[6] = {F.end_fr[0], F.end_fr[1], F.end_bytes[0], F.end_bytes[1], F.end_par[0], F.end_par[1]};
-        uint8_t g[6][GUARD_BYTES];
-        for (int s = 0; s < 6; s++)
-            if (hipMemcpyAsync(g[s], m->d_frames + ends[s], GUARD_BYTES, hipMemcpyDeviceToHost, m->st) != hipSuccess) return -1;
-        if (hipStreamSynchronize(m->st) != hipSuccess) return -1;
-        for (int s = 0; s < 6; s++)
-            for (int b = 0; b < GUARD_BYTES; b++) h += g[s][b] != (uint8_t)(GUARD_WORD >> (8 * (b & 3)));
-    }
-    if (m->cmd_guarded) {   // ... and behind the sections of the tracked push's buffer: the frames' six and the commands' seven
-        const frames::MultiLayout &F = m->cmd_frlay;
-        const commands::Layout &L = m->cmd_lay;
-        uint64_t ends[6 + commands::SEC_COUNT] = {F.end_fr[0], F.end_fr[1], F.end_bytes[0], F.end_bytes[1], F.end_par[0], F.end_par[1]};
-        for (int s = 0; s < commands::SEC_COUNT; s++) ends[6 + s] = L.end[s];
-        uint8_t g[6 + commands::SEC_COUNT][GUARD_BYTES];
-        for (int s = 0; s < 6 + commands::SEC_COUNT; s++)
-            if (hipMemcpyAsync(g[s], m->d_cmd + ends[s], GUARD_BYTES, hipMemcpyDeviceToHost, m->st) != hipSuccess) return -1;
-        if (hipStreamSynchronize(m->st) != hipSuccess) return -1;
-        for (int s = 0; s < 6 + commands::SEC_COUNT; s++)
-            for (int b = 0; b < GUARD_BYTES; b++) h += g[s][b] != (uint8_t)(GUARD_WORD >> (8 * (b & 3)));
+    // ... and the guards behind the sections of the three packed buffers, where the launches that last filled each left them
+    for (const Packed *p : {&m->fetch, &m->frames, &m->cmd}) {
+        const int bad_bytes = packed_guards_damaged(m, *p);
+        if (bad_bytes < 0) return -1;
+        h += (uint32_t)bad_bytes;
     }
     return (int)h;
 }
