@@ -43,6 +43,8 @@ extern "C" {
  *  nfc_multi_set_fsm_state) */
 /* (still 4, only new names: nfc_auth_trace, nfc_key_result, nfc_key_config, nfc_key_stats, NFC_KEY_*, nfc_find_auths, nfc_host_recover_keys,
  *  nfc_recover_keys_device) */
+/* (still 4, only new names: nfc_nested_trace, nfc_nested_result, nfc_nested_config, nfc_find_nested_auths, nfc_host_nested_candidates,
+ *  nfc_nested_candidates_device, nfc_host_recover_nested_keys, nfc_recover_nested_keys_device) */
 #define NFC_AMD_ABI_VERSION 4
 
 typedef enum {
@@ -648,7 +650,8 @@ int nfc_multi_set_fsm_state(nfc_multi *m, uint32_t stream, const nfc_fsm_state *
  * A 32-bit word of a frame has bit i = bit (i & 7) of byte (i >> 3) -- byte 0 lowest.  par: bit i the ninth bit, as received, of byte i of
  * {nr}{ar} (i = 0 .. 7) and of byte i - 8 of {at} (i = 8 .. 11).  40 bytes: five words, the parity bits, key type and block, stream and
  * frame as 32-bit counts and the 64-bit sample index at their natural widths.
- * NOT PROMISED: nested authentications (their nt is encrypted; nfc_find_auths does not return them), recovery without {at}, 7-byte UIDs. */
+ * NOT PROMISED: recovery without {at}, 7-byte UIDs.  (Nested authentications, whose nt is encrypted, are not nfc_find_auths' but
+ * nfc_find_nested_auths': the section below.) */
 typedef struct nfc_auth_trace {
     uint32_t uid, nt, nr_enc, ar_enc, at_enc;
     uint16_t par;
@@ -685,7 +688,7 @@ typedef struct nfc_key_config {    /* 32 bytes */
     uint32_t reserved[2];
 } nfc_key_config;
 typedef struct nfc_key_stats {     /* 56 bytes */
-    double ms_kernels;             /* ms_count + ms_fill + ms_probe; 0 without NFC_KEY_TIMING and from the host twin */
+    double ms_kernels;             /* ms_count + ms_fill + ms_probe (the nested call: + its candidate launch); 0 without NFC_KEY_TIMING and from the host twin */
     double ms_count, ms_fill, ms_probe;
     uint64_t scratch_bytes;        /* the tables' scratch at the end of the call (the host twin: what the device call would hold) */
     uint32_t n_batches, n_grown;
@@ -706,6 +709,71 @@ int nfc_host_recover_keys(const nfc_auth_trace *traces, size_t n, const nfc_key_
  * argument is checked before the device is touched.  There is no CPU fallback: without a usable device the call fails. */
 int nfc_recover_keys_device(int device, const nfc_auth_trace *traces, size_t n, const nfc_key_config *cfg, nfc_key_result *out,
                             nfc_key_stats *stats);
+
+/* ---- key recovery from NESTED authentications ---------------------------------------------------------------------------------------
+ * Every authentication after a session's first one is nested: the AUTH command and the tag nonce arrive encrypted.  A genuine card draws
+ * nt from a 16-bit LFSR, so there are 65 536 candidates; ten of the ninth bits of {nt}, {ar} and {at} are encrypted with keystream bits
+ * that follow from the candidate alone, and 64 candidates pass them -- or none, when the nonce is off the sequence (a hardened card) or
+ * a bit was misheard.  For ONE candidate a nested authentication is a first one with another nt: the search above runs once per
+ * candidate (a VIRTUAL trace), and a key must besides reproduce the 32 keystream bits over {nt} and its four ninth bits (csrc/keys.hip.h,
+ * DESIGN.md 8i).
+ * nfc_nested_trace, 40 bytes in nfc_auth_trace's layout with nt_enc for nt.  par: bits 0 .. 11 as in nfc_auth_trace, bits 12 .. 15 the
+ * ninth bits, as received, of {nt} bytes 0 .. 3.  key_type / block: 0 / 0xFF while the AUTH command is not known in plaintext (the
+ * search reads neither).
+ * NOT PROMISED: cards whose nested nonces are not on the 16-bit sequence (no candidates: NFC_KEY_NONE with n_nt 0), recovery without
+ * {at}, 7-byte UIDs, a search that uses ks1 alone. */
+typedef struct nfc_nested_trace {
+    uint32_t uid, nt_enc, nr_enc, ar_enc, at_enc;
+    uint16_t par;
+    uint8_t key_type;              /* 0x60 / 0x61 once labelled, else 0 */
+    uint8_t block;                 /* 0xFF until labelled */
+    uint32_t stream;               /* nfc_find_nested_auths writes 0: the caller's to fill */
+    uint32_t frame;                /* index of the encrypted AUTH frame in the merged order */
+    uint64_t idx;                  /* nfc_raw_frame.idx of that frame */
+} nfc_nested_trace;
+/* status: NFC_KEY_OK / NONE / AMBIGUOUS over the verified (candidate, key) pairs of the searched candidates; AMBIGUOUS reports the
+ * lowest key and the nt that goes with it.  NFC_KEY_OVERFLOW: the table of at least one searched candidate alone exceeds max_capacity
+ * and that candidate was not searched; the OTHER candidates still were, and a key verified among them is reported -- status OVERFLOW
+ * with key, nt, nr and n_verified set (n_verified 0 and a zero key: none was). */
+typedef struct nfc_nested_result { /* 48 bytes */
+    uint8_t key[6];
+    uint8_t status;                /* NFC_KEY_* */
+    uint8_t reserved;
+    uint32_t n_verified;           /* verified (candidate, key) pairs, saturating */
+    uint32_t n_nt;                 /* candidates the trace has: 0 or 64 */
+    uint32_t n_searched;           /* how many of them the window held */
+    uint32_t nt;                   /* the recovered plaintext tag nonce (0 without a key) */
+    uint32_t nr;                   /* the decrypted reader nonce under `key` (0 without a key) */
+    uint32_t reserved2;
+    uint64_t n_odd, n_even;        /* the exact list sizes, summed over the searched candidates */
+} nfc_nested_result;
+/* search: as for first authentications, its limits and defaults; capacity and max_batch count VIRTUAL traces.  Per trace only the
+ * candidates [cand_first, cand_first + cand_count) of its ascending list are searched (cand_count 0: all from cand_first): how several
+ * devices share a card.  cand_first above 64 or a non-zero reserved word is NFC_ERR_ARG. */
+typedef struct nfc_nested_config { /* 48 bytes */
+    nfc_key_config search;
+    uint32_t cand_first, cand_count;
+    uint32_t reserved[2];
+} nfc_nested_config;
+/* Host only, nfc_find_auths' arguments.  A nested authentication comes after a first authentication (nfc_find_auths' rule) of the current
+ * UID with no reader SELECT frame (93 70 .., NFC_RAW_CRC_A_OK) in between, and is four consecutive frames of the merged order, none
+ * NFC_RAW_CUT: a reader frame of 4 bytes that is not itself a plain 60|61 blk crc with NFC_RAW_CRC_A_OK, a tag frame of 4 bytes ({nt}), a
+ * reader frame of 8 bytes, a tag frame of 4 bytes.  No keys are needed: inside a session no other exchange has this shape. */
+int nfc_find_nested_auths(const nfc_raw_frame *frames, size_t n, const uint8_t *bytes0, const uint8_t *par0, const uint8_t *bytes1,
+                          const uint8_t *par1, nfc_nested_trace *out, size_t cap, size_t *n_out);
+/* The candidate plaintext nonces of one trace in ascending seed order (the seed: bits 0 .. 15 of the nonce): *n_out is 0 or 64, the first
+ * `cap` are written.  nfc_nested_candidates_device: the kernel's answer for n traces, out_nt [n][64] (unused entries 0) and out_n [n]. */
+int nfc_host_nested_candidates(const nfc_nested_trace *trace, uint32_t *out_nt, size_t cap, size_t *n_out);
+int nfc_nested_candidates_device(int device, const nfc_nested_trace *traces, size_t n, uint32_t *out_nt, uint32_t *out_n);
+/* The CPU twin and the device call, as nfc_host_recover_keys / nfc_recover_keys_device: one candidate launch for all traces, then the
+ * virtual traces (trace, candidate), in order, in batches of max_batch through the same capacity rules.  stats: n_launches counts the
+ * candidate launch too, and with NFC_KEY_TIMING ms_kernels includes its time (ms_count + ms_fill + ms_probe is then less than
+ * ms_kernels).  n == 0 launches nothing and touches no device; every argument is checked before the device is touched; no CPU
+ * fallback.  cfg and stats may be NULL. */
+int nfc_host_recover_nested_keys(const nfc_nested_trace *traces, size_t n, const nfc_nested_config *cfg, nfc_nested_result *out,
+                                 nfc_key_stats *stats);
+int nfc_recover_nested_keys_device(int device, const nfc_nested_trace *traces, size_t n, const nfc_nested_config *cfg,
+                                   nfc_nested_result *out, nfc_key_stats *stats);
 
 /* one stream's boundary state, in the form an nfc_ctx exports and imports it */
 int nfc_multi_get_state(nfc_multi *m, uint32_t stream, nfc_state_header *hdr, float *ring, size_t ring_cap, uint8_t *pending, size_t pending_cap);

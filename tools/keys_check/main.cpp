@@ -1,8 +1,11 @@
 // keys_check -- nfc_find_auths and nfc_host_recover_keys on the reference vector (the first authentication of
-// tests/golden/1k_with_enc.out), as a stand-alone host program: the way to run the key recovery's host code under a sanitizer.
+// tests/golden/1k_with_enc.out), then the nested authentication that follows it in that trace: nfc_find_nested_auths, the candidate list
+// (nfc_host_nested_candidates) and nfc_host_recover_nested_keys on the one-candidate window of the printed nonce -- the nested verify
+// and the host's reduction.  A stand-alone host program: the way to run the key recovery's host code under a sanitizer.
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined tools/keys_check/main.cpp \
 //         usrp_nfc_amd/csrc/nfc_keys.hip -o keys_check && ./keys_check
-// It touches no GPU.  Exit status 0: the frames give the quoted trace and the trace gives key FF FF FF FF FF FF, one candidate.
+// It touches no GPU.  Exit status 0: the frames give the quoted traces, the first one gives key FF FF FF FF FF FF, one candidate, and
+// the nested one 64 candidate nonces, 8F 82 69 9E among them, and from that one key FF FF FF FF FF FF with nr 01 3A 6B BA.
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -58,5 +61,57 @@ int main() {
     printf("status %d key %02X %02X %02X %02X %02X %02X candidates %u n_odd %u n_even %u nr %08X par %03X\n", r.status, r.key[0], r.key[1], r.key[2], r.key[3],
            r.key[4], r.key[5], r.n_candidates, r.n_odd, r.n_even, r.nr, t[0].par);
     const uint8_t ff[6] = {0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF};
-    return (r.status == NFC_KEY_OK && r.n_candidates == 1 && memcmp(r.key, ff, 6) == 0) ? 0 : 1;
+    if (!(r.status == NFC_KEY_OK && r.n_candidates == 1 && memcmp(r.key, ff, 6) == 0)) return 1;
+
+    // the nested authentication behind it: {AUTHA 0x38}, {nt}, {nr}{ar}, {at} as the trace prints them
+    const uint8_t auth2[4] = {0xC6, 0xDC, 0xBA, 0x11}, nt2[4] = {0x70, 0xBD, 0xED, 0x81};
+    const uint8_t nrar2[8] = {0xFC, 0x1A, 0x1A, 0x1D, 0x7D, 0x90, 0x7E, 0x24}, at2[4] = {0x87, 0x4D, 0xFF, 0x8A};
+    const int auth2_bang[4] = {0, 0, 1, 1}, nt2_bang[4] = {1, 0, 1, 0}, nrar2_bang[8] = {1, 0, 1, 1, 1, 0, 1, 1}, at2_bang[4] = {0, 0, 1, 0};
+    add(1, auth2, 4, auth2_bang, 0);
+    add(0, nt2, 4, nt2_bang, 0);
+    add(1, nrar2, 8, nrar2_bang, 0);
+    add(0, at2, 4, at2_bang, 0);
+    nfc_nested_trace nest[2];
+    if (nfc_find_nested_auths(fr.data(), fr.size(), b[0].data(), p[0].data(), b[1].data(), p[1].data(), nest, 2, &n) != NFC_OK || n != 1) {
+        printf("nfc_find_nested_auths: %zu traces\n", n);
+        return 1;
+    }
+    if (nfc_find_auths(fr.data(), fr.size(), b[0].data(), p[0].data(), b[1].data(), p[1].data(), t, 2, &n) != NFC_OK || n != 1) return 1;
+    if (nest[0].uid != 0x749276CDu || nest[0].nt_enc != 0x81EDBD70u || nest[0].nr_enc != 0x1D1A1AFCu || nest[0].ar_enc != 0x247E907Du ||
+        nest[0].at_enc != 0x8AFF4D87u || nest[0].key_type != 0 || nest[0].block != 0xFF || nest[0].frame != 5 || nest[0].idx != 6000) {
+        printf("nfc_find_nested_auths: another trace than the quoted one\n");
+        return 1;
+    }
+    uint32_t cand[64];
+    size_t nc = 0, at_i = 64;
+    if (nfc_host_nested_candidates(&nest[0], cand, 64, &nc) != NFC_OK || nc != 64) {
+        printf("nfc_host_nested_candidates: %zu candidates\n", nc);
+        return 1;
+    }
+    for (size_t i = 0; i < nc; i++) {
+        if (i && (cand[i] & 0xFFFFu) <= (cand[i - 1] & 0xFFFFu)) return 1;   // ascending in seed
+        if (cand[i] == 0x9E69828Fu) at_i = i;
+    }
+    if (at_i == 64) {
+        printf("the printed nonce is not among the candidates\n");
+        return 1;
+    }
+    nfc_nested_config cfg;
+    memset(&cfg, 0, sizeof cfg);
+    cfg.cand_first = (uint32_t)at_i, cfg.cand_count = 1;
+    nfc_nested_result nres;
+    if (nfc_host_recover_nested_keys(nest, 1, &cfg, &nres, &s) != NFC_OK) return 1;
+    printf("nested: status %d key %02X %02X %02X %02X %02X %02X verified %u n_nt %u searched %u nt %08X nr %08X n_odd %llu n_even %llu par %04X\n", nres.status,
+           nres.key[0], nres.key[1], nres.key[2], nres.key[3], nres.key[4], nres.key[5], nres.n_verified, nres.n_nt, nres.n_searched, nres.nt, nres.nr,
+           (unsigned long long)nres.n_odd, (unsigned long long)nres.n_even, nest[0].par);
+    if (!(nres.status == NFC_KEY_OK && nres.n_verified == 1 && nres.n_nt == 64 && nres.n_searched == 1 && memcmp(nres.key, ff, 6) == 0 &&
+          nres.nt == 0x9E69828Fu && nres.nr == 0xBA6B3A01u))
+        return 1;
+    // the window beside it holds no key, and one behind the list nothing to search
+    cfg.cand_first = (uint32_t)((at_i + 1) % 64);
+    if (nfc_host_recover_nested_keys(nest, 1, &cfg, &nres, &s) != NFC_OK || nres.status != NFC_KEY_NONE || nres.n_searched != 1) return 1;
+    cfg.cand_first = 64;
+    if (nfc_host_recover_nested_keys(nest, 1, &cfg, &nres, &s) != NFC_OK || nres.status != NFC_KEY_NONE || nres.n_searched != 0 || nres.n_nt != 64) return 1;
+    cfg.cand_first = 65;
+    return nfc_host_recover_nested_keys(nest, 1, &cfg, &nres, &s) == NFC_ERR_ARG ? 0 : 1;
 }

@@ -89,6 +89,10 @@ class KeyStats(C.Structure):   # nfc_key_stats
                 ('reserved', C.c_uint32)]
 
 
+class NestedConfig(C.Structure):   # nfc_nested_config
+    _fields_ = [('search', KeyConfig), ('cand_first', C.c_uint32), ('cand_count', C.c_uint32), ('reserved', C.c_uint32 * 2)]
+
+
 class Frame(C.Structure):   # nfc_frame
     _fields_ = [('cmd', C.c_int32), ('type', C.c_int32), ('byte_off', C.c_uint32), ('n_bytes', C.c_uint16),
                 ('n_header', C.c_uint16), ('n_extra', C.c_uint16), ('n_crc', C.c_uint16), ('flags', C.c_uint32),
@@ -127,6 +131,12 @@ AUTH_DTYPE = np.dtype([('uid', '<u4'), ('nt', '<u4'), ('nr_enc', '<u4'), ('ar_en
                        ('block', 'u1'), ('stream', '<u4'), ('frame', '<u4'), ('idx', '<u8')])
 KEY_RESULT_DTYPE = np.dtype([('key', 'u1', (6,)), ('status', 'u1'), ('reserved', 'u1'), ('n_candidates', '<u4'), ('n_odd', '<u4'), ('n_even', '<u4'),
                              ('nr', '<u4')])
+# nfc_nested_trace: one sniffed nested authentication (nt_enc for nt; par bits 12 .. 15: the ninth bits of {nt}), and nfc_nested_result
+NESTED_DTYPE = np.dtype([('uid', '<u4'), ('nt_enc', '<u4'), ('nr_enc', '<u4'), ('ar_enc', '<u4'), ('at_enc', '<u4'), ('par', '<u2'), ('key_type', 'u1'),
+                         ('block', 'u1'), ('stream', '<u4'), ('frame', '<u4'), ('idx', '<u8')])
+NESTED_RESULT_DTYPE = np.dtype([('key', 'u1', (6,)), ('status', 'u1'), ('reserved', 'u1'), ('n_verified', '<u4'), ('n_nt', '<u4'), ('n_searched', '<u4'),
+                                ('nt', '<u4'), ('nr', '<u4'), ('reserved2', '<u4'), ('n_odd', '<u8'), ('n_even', '<u8')])
+NESTED_CANDS = 64
 NFC_KEY_OK, NFC_KEY_NONE, NFC_KEY_AMBIGUOUS, NFC_KEY_OVERFLOW = 0, 1, 2, 3
 NFC_KEY_TIMING = 1
 COUNTS_DTYPE = np.dtype([('n_samples', '<u8'), ('n_edges', '<u8'), ('n_symbols', '<u8', (2,)), ('n_packets', '<u8', (2,)),
@@ -147,7 +157,9 @@ SYMBOLS = ['nfc_abi_version', 'nfc_device_count', 'nfc_create', 'nfc_destroy', '
            'nfc_get_frame_counts', 'nfc_read_frames', 'nfc_read_frame_bytes', 'nfc_host_frames', 'nfc_fsm_process_frames', 'nfc_multi_fetch_frames',
            'nfc_fsm_state_init', 'nfc_fsm_get_state', 'nfc_fsm_set_state', 'nfc_host_commands', 'nfc_multi_track_commands', 'nfc_multi_fetch_commands',
            'nfc_multi_set_keys', 'nfc_multi_get_fsm_state', 'nfc_multi_set_fsm_state',
-           'nfc_find_auths', 'nfc_host_recover_keys', 'nfc_recover_keys_device']
+           'nfc_find_auths', 'nfc_host_recover_keys', 'nfc_recover_keys_device',
+           'nfc_find_nested_auths', 'nfc_host_nested_candidates', 'nfc_nested_candidates_device', 'nfc_host_recover_nested_keys',
+           'nfc_recover_nested_keys_device']
 
 _libs = {}
 
@@ -275,6 +287,11 @@ def load(path=None):
     L.nfc_find_auths.argtypes = [vp, sz, vp, vp, vp, vp, vp, sz, psz]
     L.nfc_host_recover_keys.argtypes = [vp, sz, C.POINTER(KeyConfig), vp, C.POINTER(KeyStats)]
     L.nfc_recover_keys_device.argtypes = [C.c_int, vp, sz, C.POINTER(KeyConfig), vp, C.POINTER(KeyStats)]
+    L.nfc_find_nested_auths.argtypes = [vp, sz, vp, vp, vp, vp, vp, sz, psz]
+    L.nfc_host_nested_candidates.argtypes = [vp, vp, sz, psz]
+    L.nfc_nested_candidates_device.argtypes = [C.c_int, vp, sz, vp, vp]
+    L.nfc_host_recover_nested_keys.argtypes = [vp, sz, C.POINTER(NestedConfig), vp, C.POINTER(KeyStats)]
+    L.nfc_recover_nested_keys_device.argtypes = [C.c_int, vp, sz, C.POINTER(NestedConfig), vp, C.POINTER(KeyStats)]
     for name in SYMBOLS:
         getattr(L, name)
     _libs[path] = L

@@ -422,10 +422,16 @@ class NfcMultiContext(object):
             raise NfcError('set_keys: key_a and key_b are six bytes each')
         self._chk(self.L.nfc_multi_set_keys(self.h, -1 if stream is None else int(stream), a.ctypes.data, b.ctypes.data), 'nfc_multi_set_keys')
 
-    def recover_keys(self, **cfg):
+    def recover_keys(self, nested=False, **cfg):
         """The sector keys of the last push's first authentications: fetch_frames() + NfcMultiFrames.auths() + ONE keys.recover call on
-        this context's device (cfg: keys.recover's).  -> per stream a dict (key_type, block) -> six key bytes (keys.keys_by_stream)."""
+        this context's device (cfg: keys.recover's).  -> per stream a dict (key_type, block) -> six key bytes (keys.keys_by_stream).
+        nested=True: the nested authentications too (keys.recover_streams: one more call, keys.recover_nested, and keys.label_auths per
+        stream), so the dicts also hold every later sector's key whose AUTH command could be decrypted."""
         from . import keys
+        if nested:
+            fr = self.fetch_frames()
+            have = (np.diff(fr.frame_off[0]) > 0) & (np.diff(fr.frame_off[1]) > 0)
+            return keys.recover_streams([fr.frames_of(k) if have[k] else None for k in range(self.n_streams)], device=self.device, **cfg)
         traces = self.fetch_frames().auths()
         results, _ = keys.recover(traces, device=self.device, **cfg)
         return keys.keys_by_stream(traces, results, self.n_streams)
@@ -768,6 +774,17 @@ class NfcMultiFrames(object):
             a['stream'] = int(k)
             parts.append(a)
         return np.concatenate(parts) if parts else np.zeros(0, _lib.AUTH_DTYPE)
+
+    def nested_auths(self):
+        """Every stream's nested authentications (keys.find_nested_auths per stream, in stream order) as ONE NESTED_DTYPE array, `stream`
+        filled in: what keys.recover_nested takes."""
+        from . import keys
+        parts = []
+        for k in np.nonzero((np.diff(self.frame_off[0]) > 0) & (np.diff(self.frame_off[1]) > 0))[0]:
+            a = keys.find_nested_auths(self.frames_of(int(k)))
+            a['stream'] = int(k)
+            parts.append(a)
+        return np.concatenate(parts) if parts else np.zeros(0, _lib.NESTED_DTYPE)
 
     def stream_of(self, ptype):
         """The stream every frame of frames[ptype] belongs to."""

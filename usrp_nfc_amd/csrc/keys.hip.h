@@ -17,6 +17,13 @@
 // ROLL BACK.  The pair is the register at clock 73; 73 steps back (rollback) give the register at clock 0: the key, in load_key's order.
 // VERIFY.  The candidate key runs forward through fsmd's CRYPTO1 over the trace (verify): it must reproduce ar and at and decrypt {nr} to
 // bytes whose four parity bits are right.
+//
+// NESTED.  Inside a session the tag nonce arrives encrypted, {nt}; the new sector's register is loaded with the key and
+// clocked with uid ^ nt in PLAINTEXT (fsm.hip.h, the nested branch), so for ONE candidate nt a nested authentication is a first one with
+// another nt.  A genuine card draws nt from a 16-bit LFSR: 65 536 candidates, a seed each (nonce_extend).  Ten ninth bits of {nt}, {ar},
+// {at} are encrypted with keystream bits that follow from the candidate alone (nested_candidate): 64 seeds pass, or none.
+// k_nested_candidates writes the survivors as Prepared records in ascending seed order; the three search kernels run over (nested
+// trace, candidate) pairs -- virtual traces -- through an index (`map`), and verify additionally asks for ks1 and the {nt} ninth bits.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -97,9 +104,11 @@ struct Prepared {
     uint32_t uid_nt;            // uid ^ nt
     uint32_t nr_enc, ar_enc, at_enc;
     uint32_t ar, at;            // suc64(nt), suc96(nt)
-    uint32_t par;               // the twelve parity bits as received
-    uint32_t pad;
+    uint32_t par;               // the twelve parity bits as received; nested: bits 12 .. 15 those of {nt}, and PREP_NESTED
+    uint32_t parent;            // nested: the index of the nested trace (0 for a first authentication)
+    uint32_t nt_enc, nt;        // nested: {nt} and the candidate plaintext nonce (0 for a first authentication)
 };
+constexpr uint32_t PREP_NESTED = 1u << 31;
 NFC_HD uint32_t even_bits(uint64_t x) {   // bits 0, 2, 4 .. 62 of x
     uint32_t r = 0;
     for (int i = 0; i < 32; i++) r |= (uint32_t)((x >> (2 * i)) & 1ull) << i;
@@ -115,8 +124,43 @@ NFC_HD Prepared prepare(const nfc_auth_trace &t) {
     P.uid_nt = t.uid ^ t.nt;
     P.nr_enc = t.nr_enc, P.ar_enc = t.ar_enc, P.at_enc = t.at_enc;
     P.par = t.par;
-    P.pad = 0;
+    P.parent = 0, P.nt_enc = 0, P.nt = 0;
     return P;
+}
+
+// ---- nested authentications: the candidate nonces ----
+constexpr uint32_t NESTED_SEEDS = 1u << 16, NESTED_CANDS = 64;
+// the 32 nonce bits from the first 16: b[k + 16] = b[k] ^ b[k + 2] ^ b[k + 3] ^ b[k + 5] (fsmd::nonce_advance's recurrence)
+NFC_HD uint32_t nonce_extend(uint32_t seed) {
+    uint32_t x = seed & 0xFFFFu;
+    for (int k = 0; k < 16; k++) x |= (((x >> k) ^ (x >> (k + 2)) ^ (x >> (k + 3)) ^ (x >> (k + 5))) & 1u) << (k + 16);
+    return x;
+}
+// a ninth bit `p` over the plaintext byte `pt`, encrypted with keystream bit `ks`: right when p ^ ks is the odd parity of pt
+NFC_HD bool ninth_fits(uint32_t p, uint32_t ks, uint32_t pt) { return ((p ^ ks) & 1u) == (1u ^ (frames::popc8(pt & 0xFFu) & 1u)); }
+// The record of (trace, seed), and whether the seed passes the ten tests: the ninth bit of a byte is encrypted with the keystream bit
+// of the NEXT data bit, and ks1 = {nt} ^ nt, ks2 = {ar} ^ suc64(nt), ks3 = {at} ^ suc96(nt) follow from the candidate.  {nt} bytes
+// 0 .. 2 with ks1 bits 8, 16, 24; {ar} bytes 0 .. 2 with ks2 bits 8, 16, 24 and byte 3 with ks3 bit 0; {at} bytes 0 .. 2 with ks3 bits
+// 8, 16, 24.  (The ninth bits of {nr}, of {nt} byte 3 and of {at} byte 3 need the register or a later frame: verify's.)
+NFC_HD bool nested_candidate(const nfc_nested_trace &t, uint32_t parent, uint32_t seed, Prepared &P) {
+    const uint32_t nt = nonce_extend(seed);
+    P.ar = fsmd::nonce_advance(nt, 64);
+    P.at = fsmd::nonce_advance(P.ar, 32);
+    const uint32_t ks1 = t.nt_enc ^ nt, ks2 = t.ar_enc ^ P.ar, ks3 = t.at_enc ^ P.at, par = t.par;
+    bool ok = ninth_fits(par >> 7, ks3, P.ar >> 24);
+    for (int b = 0; b < 3; b++) {
+        ok = ok && ninth_fits(par >> (12 + b), ks1 >> (8 * b + 8), nt >> (8 * b));
+        ok = ok && ninth_fits(par >> (4 + b), ks2 >> (8 * b + 8), P.ar >> (8 * b));
+        ok = ok && ninth_fits(par >> (8 + b), ks3 >> (8 * b + 8), P.at >> (8 * b));
+    }
+    const uint64_t ks = (uint64_t)ks2 | (uint64_t)ks3 << 32;
+    P.ks_odd = even_bits(ks);
+    P.ks_even = even_bits(ks >> 1);
+    P.uid_nt = t.uid ^ nt;
+    P.nr_enc = t.nr_enc, P.ar_enc = t.ar_enc, P.at_enc = t.at_enc;
+    P.par = (uint32_t)par | PREP_NESTED;
+    P.parent = parent, P.nt_enc = t.nt_enc, P.nt = nt;
+    return ok;
 }
 
 // the register at clock 73 from the pair: bit i = b_{73 + i}
@@ -135,11 +179,23 @@ NFC_HD uint64_t rollback(uint64_t s, const Prepared &P) {
     return s;
 }
 // the candidate key forward over the trace, as fsmd's machine runs a first authentication.  nr_out: the decrypted reader nonce.
+// A nested record (PREP_NESTED) must also give ks1: over clocks 0 .. 31 the filter output xor {nt} is the candidate nt, and the four
+// ninth bits of {nt} fit, each under the keystream bit of the next data bit (the fourth: clock 32, the first of {nr}).
 NFC_HD bool verify(uint64_t key, const Prepared &P, uint32_t *nr_out) {
     uint64_t st = key & fsmd::ST_MASK;
-    for (int i = 0; i < 32; i++) st = fsmd::shift_in(st, (P.uid_nt >> i) & 1u);
-    uint32_t nr = 0;
     bool bad = false;
+    if (P.par & PREP_NESTED) {
+        uint32_t ks1 = 0;
+        for (int i = 0; i < 32; i++) {
+            ks1 |= fsmd::filter(st) << i;
+            st = fsmd::shift_in(st, (P.uid_nt >> i) & 1u);
+            if ((i & 7) == 7 && !ninth_fits(P.par >> (12 + (i >> 3)), fsmd::filter(st), P.nt >> (i - 7))) bad = true;
+        }
+        if ((P.nt_enc ^ ks1) != P.nt) bad = true;
+    } else {
+        for (int i = 0; i < 32; i++) st = fsmd::shift_in(st, (P.uid_nt >> i) & 1u);
+    }
+    uint32_t nr = 0;
     for (int b = 0; b < 4; b++) {
         uint32_t pt = 0;
         for (int k = 0; k < 8; k++) {
@@ -168,8 +224,48 @@ NFC_HD uint64_t slot_of(uint64_t sig, uint32_t log2) { return (sig * 0x9E3779B97
 
 #if defined(__HIPCC__)
 // ---- the kernels.  A workgroup is 256 consecutive starting windows of one half of one trace; blockIdx.z + t0 is the trace. ----
+// The trace is a place in the BATCH: counts, place, n_found and min_key are indexed by it and hold a batch's worth.  Its record is
+// prep[trace], or prep[map[trace]] with a map: the virtual traces of a nested search lie where k_nested_candidates wrote them, 64
+// slots per nested trace, and the host lists the batch's ones.  A record is only read, so a map entry decides what is searched and
+// never where anything is written: the memory-safety argument does not depend on how many records there are.
 constexpr int KEYS_BLOCK = 256;
-enum { KEYS_ERR_TABLE_FULL = 1 };
+enum { KEYS_ERR_TABLE_FULL = 1, KEYS_ERR_CANDIDATES = 2 };
+__device__ __forceinline__ const Prepared &record_of(const Prepared *__restrict__ prep, const uint32_t *__restrict__ map, uint32_t tr) {
+    return prep[map ? map[tr] : tr];
+}
+
+// A workgroup per nested trace: NESTED_SEEDS / NESTED_BLOCK rounds of one seed per lane.  The rank of a survivor is the survivors of
+// earlier rounds + those of lower waves in this round + those of lower lanes in its wave (ballot), so the order is the seeds' own and
+// no atomic decides it.  Slot rank of the trace's NESTED_CANDS holds it; a rank that is not below NESTED_CANDS (it cannot be: the
+// ten tests have rank 10) is not written and raises KEYS_ERR_CANDIDATES.  n_out[trace]: the survivors, at most NESTED_CANDS.
+constexpr int NESTED_BLOCK = 1024, NESTED_WAVES = NESTED_BLOCK / 64;
+__global__ __launch_bounds__(NESTED_BLOCK) void k_nested_candidates(const nfc_nested_trace *__restrict__ traces, Prepared *__restrict__ prep /* [trace][64] */,
+                                                                    uint32_t *__restrict__ n_out, uint32_t *__restrict__ err) {
+    __shared__ uint32_t wave_n[2][NESTED_WAVES];
+    const uint32_t tr = blockIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const nfc_nested_trace t = traces[tr];
+    uint32_t base = 0;
+    for (uint32_t round = 0; round < NESTED_SEEDS / NESTED_BLOCK; round++) {
+        Prepared P;
+        const bool ok = nested_candidate(t, tr, round * NESTED_BLOCK + threadIdx.x, P);
+        const uint64_t votes = __ballot(ok);
+        if (lane == 0) wave_n[round & 1u][wave] = (uint32_t)__popcll(votes);
+        __syncthreads();   // (two buffers: a wave that runs ahead writes the other one, and meets the next barrier before this one again)
+        uint32_t before = 0, total = 0;
+        for (uint32_t w = 0; w < NESTED_WAVES; w++) {
+            const uint32_t c = wave_n[round & 1u][w];
+            before += w < wave ? c : 0u;
+            total += c;
+        }
+        if (ok) {
+            const uint32_t rank = base + before + (uint32_t)__popcll(votes & ((1ull << lane) - 1ull));
+            if (rank < NESTED_CANDS) prep[(size_t)tr * NESTED_CANDS + rank] = P;
+            else atomicOr(err, (uint32_t)KEYS_ERR_CANDIDATES);
+        }
+        base += total;
+    }
+    if (threadIdx.x == 0) n_out[tr] = base < NESTED_CANDS ? base : NESTED_CANDS;
+}
 
 // per trace of the batch: where its table lies in the scratch (slots), and its size (0: the trace takes no part in this launch)
 struct Place {
@@ -177,9 +273,10 @@ struct Place {
     uint32_t log2, pad;
 };
 
-__global__ __launch_bounds__(KEYS_BLOCK) void k_keys_count(const Prepared *__restrict__ prep, uint32_t *__restrict__ counts /* [trace][half] */) {
+__global__ __launch_bounds__(KEYS_BLOCK) void k_keys_count(const Prepared *__restrict__ prep, const uint32_t *__restrict__ map,
+                                                           uint32_t *__restrict__ counts /* [trace][half] */) {
     const uint32_t tr = blockIdx.z, half = blockIdx.y, w = blockIdx.x * KEYS_BLOCK + threadIdx.x;
-    const uint32_t ks = half ? prep[tr].ks_even : prep[tr].ks_odd;
+    const uint32_t ks = half ? record_of(prep, map, tr).ks_even : record_of(prep, map, tr).ks_odd;
     uint32_t n = walk(w, ks, [](uint64_t) {});
     __shared__ uint32_t total;
     if (threadIdx.x == 0) total = 0;
@@ -192,13 +289,13 @@ __global__ __launch_bounds__(KEYS_BLOCK) void k_keys_count(const Prepared *__res
 
 // Every slot index is masked to the trace's table, so nothing is written outside its section whatever the counts were; a table that
 // turns out full (it cannot, the host sized it from the exact count) raises KEYS_ERR_TABLE_FULL and the sequence is dropped.
-__global__ __launch_bounds__(KEYS_BLOCK) void k_keys_fill_odd(const Prepared *__restrict__ prep, const Place *__restrict__ place, uint32_t t0,
-                                                              uint64_t *__restrict__ sig_tab, uint64_t *__restrict__ seq_tab, uint32_t *__restrict__ err) {
+__global__ __launch_bounds__(KEYS_BLOCK) void k_keys_fill_odd(const Prepared *__restrict__ prep, const uint32_t *__restrict__ map,
+                                                              const Place *__restrict__ place, uint32_t t0, uint64_t *__restrict__ sig_tab, uint64_t *__restrict__ seq_tab, uint32_t *__restrict__ err) {
     const uint32_t tr = t0 + blockIdx.z, w = blockIdx.x * KEYS_BLOCK + threadIdx.x;
     const Place pl = place[tr];
     if (pl.log2 == 0) return;
     const uint64_t mask = (1ull << pl.log2) - 1ull;
-    walk(w, prep[tr].ks_odd, [&](uint64_t seq) {
+    walk(w, record_of(prep, map, tr).ks_odd, [&](uint64_t seq) {
         const uint64_t sig = signature<0>(seq);
         uint64_t slot = slot_of(sig, pl.log2);
         for (uint64_t tries = 0; tries <= mask; tries++) {
@@ -213,14 +310,14 @@ __global__ __launch_bounds__(KEYS_BLOCK) void k_keys_fill_odd(const Prepared *__
     });
 }
 
-__global__ __launch_bounds__(KEYS_BLOCK) void k_keys_probe_even(const Prepared *__restrict__ prep, const Place *__restrict__ place, uint32_t t0,
-                                                                const uint64_t *__restrict__ sig_tab, const uint64_t *__restrict__ seq_tab,
+__global__ __launch_bounds__(KEYS_BLOCK) void k_keys_probe_even(const Prepared *__restrict__ prep, const uint32_t *__restrict__ map,
+                                                                const Place *__restrict__ place, uint32_t t0, const uint64_t *__restrict__ sig_tab, const uint64_t *__restrict__ seq_tab,
                                                                 uint32_t *__restrict__ n_found, unsigned long long *__restrict__ min_key) {
     const uint32_t tr = t0 + blockIdx.z, w = blockIdx.x * KEYS_BLOCK + threadIdx.x;
     const Place pl = place[tr];
     if (pl.log2 == 0) return;
     const uint64_t mask = (1ull << pl.log2) - 1ull;
-    const Prepared P = prep[tr];
+    const Prepared P = record_of(prep, map, tr);
     walk(w, P.ks_even, [&](uint64_t seq) {
         const uint64_t sig = signature<1>(seq);
         uint64_t slot = slot_of(sig, pl.log2);

@@ -2,6 +2,9 @@
 // nfc_find_auths picks the first authentications out of a stream's frames, nfc_host_recover_keys is the CPU twin (sort and search for the
 // join), nfc_recover_keys_device batches the traces, reads the exact counts, places every trace's table in the scratch and launches.
 // The capacity rules live in ONE place (plan_batch) that both use, so their statuses and statistics agree by construction.
+// Both searches are stated once over a list of RECORDS (keys::Prepared): host_search and device_search.  A first authentication is one
+// record; a nested one is up to 64, one per candidate nonce -- virtual traces -- which k_nested_candidates writes on the
+// device and nested_records lists on the host, and reduce_nested folds a nested trace's verdicts into its one result.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -16,6 +19,9 @@
 
 static_assert(sizeof(nfc_auth_trace) == 40 && sizeof(nfc_key_result) == 24 && sizeof(nfc_key_config) == 32 && sizeof(nfc_key_stats) == 56,
               "the key recovery's public structures");
+static_assert(sizeof(nfc_nested_trace) == 40 && sizeof(nfc_nested_result) == 48 && sizeof(nfc_nested_config) == 48,
+              "the nested key recovery's public structures");
+static_assert(sizeof(nfc::keys::Prepared) == 48, "a record is twelve words");
 
 namespace {
 using namespace nfc;
@@ -83,20 +89,295 @@ void account(const Plan &p, uint64_t &capacity, nfc_key_stats &S) {
         if (g.slots > capacity) capacity = g.slots, S.n_grown++;
 }
 
-void result_of(nfc_key_result &r, bool overflow, uint32_t n_found, uint64_t min_key, uint32_t n_odd, uint32_t n_even, const Prepared &P) {
+// what the search says of one record
+struct Verdict {
+    bool overflow;
+    uint32_t n_found, n_odd, n_even;
+    uint64_t min_key;
+};
+
+void result_of(nfc_key_result &r, const Verdict &v, const Prepared &P) {
     memset(&r, 0, sizeof r);
-    r.n_odd = n_odd, r.n_even = n_even;
-    if (overflow) {
+    r.n_odd = v.n_odd, r.n_even = v.n_even;
+    if (v.overflow) {
         r.status = NFC_KEY_OVERFLOW;
         return;
     }
-    r.n_candidates = n_found;
-    r.status = n_found == 0 ? NFC_KEY_NONE : n_found == 1 ? NFC_KEY_OK : NFC_KEY_AMBIGUOUS;
-    if (n_found) {
-        for (int i = 0; i < 6; i++) r.key[i] = (uint8_t)(min_key >> (8 * i));
-        (void)verify(min_key, P, &r.nr);
+    r.n_candidates = v.n_found;
+    r.status = v.n_found == 0 ? NFC_KEY_NONE : v.n_found == 1 ? NFC_KEY_OK : NFC_KEY_AMBIGUOUS;
+    if (v.n_found) {
+        for (int i = 0; i < 6; i++) r.key[i] = (uint8_t)(v.min_key >> (8 * i));
+        (void)verify(v.min_key, P, &r.nr);
     }
 }
+
+// ---- the CPU twin over records: record_of(v) -> Prepared, sink(v, verdict, record) ----
+template <class RecordOf, class Sink>
+void host_search(const Limits &L, nfc_key_stats &S, size_t nv, RecordOf &&record_of, Sink &&sink) {
+    uint64_t capacity = L.initial;
+    std::vector<std::pair<uint64_t, uint64_t>> odd;   // (signature, sequence)
+    std::vector<uint32_t> n_odd;
+    for (size_t b0 = 0; b0 < nv; b0 += L.max_batch) {
+        const uint32_t nb = (uint32_t)std::min<size_t>(L.max_batch, nv - b0);
+        n_odd.assign(nb, 0);
+        for (uint32_t i = 0; i < nb; i++) {
+            const Prepared P = record_of(b0 + i);
+            odd.clear();
+            for (uint32_t w = 0; w < WINDOWS; w++) walk(w, P.ks_odd, [&](uint64_t seq) { odd.emplace_back(signature<0>(seq), seq); });
+            n_odd[i] = (uint32_t)odd.size();
+            Verdict V{(1ull << table_log2(odd.size())) > L.max, 0u, n_odd[i], 0u, ~0ull};
+            if (!V.overflow) std::sort(odd.begin(), odd.end());
+            for (uint32_t w = 0; w < WINDOWS; w++)
+                V.n_even += walk(w, P.ks_even, [&](uint64_t seq) {
+                    if (V.overflow) return;
+                    const uint64_t sig = signature<1>(seq);
+                    for (auto it = std::lower_bound(odd.begin(), odd.end(), std::make_pair(sig, (uint64_t)0)); it != odd.end() && it->first == sig; ++it) {
+                        const uint64_t key = rollback(join_state(it->second, seq), P);
+                        if (verify(key, P, nullptr)) {
+                            if (V.n_found != 0xFFFFFFFFu) V.n_found++;
+                            V.min_key = std::min(V.min_key, key);
+                        }
+                    }
+                });
+            sink(b0 + i, V, P);
+        }
+        account(plan_batch(n_odd.data(), nb, L.max), capacity, S);
+        S.n_batches++;
+    }
+    S.scratch_bytes = nv ? capacity * 16 : 0;
+}
+
+// ---- the device search over records ----
+// prelude(D) runs once the device is set and the events exist: it may allocate and launch (D.timed), and leaves D.nv, the number of
+// records, and -- where they already lie on the device -- D.d_records with D.map, the place of record v in it.  Without d_records the
+// batch's records, record_of(v), are uploaded.  sink(v, verdict, record) sees every record in order.
+struct DeviceSearch {
+    const Limits &L;
+    nfc_key_stats &S;
+    int rc = NFC_OK;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    size_t nv = 0;
+    const Prepared *d_records = nullptr;
+    const uint32_t *map = nullptr;   // [nv], the host's
+    double ms_prelude = 0;
+    std::vector<void *> owned;   // device memory of the prelude's, freed at the end
+
+    bool bad(hipError_t e, int status = NFC_ERR_DEVICE) {
+        if (e == hipSuccess) return false;
+        rc = (e == hipErrorOutOfMemory) ? NFC_ERR_NOMEM : status;
+        return true;
+    }
+    template <class T>
+    bool alloc(T *&p, size_t bytes) {
+        void *q = nullptr;
+        if (bad(hipMalloc(&q, bytes ? bytes : 1))) return false;
+        owned.push_back(q);
+        p = (T *)q;
+        return true;
+    }
+    // one launch, timed by HIP events when asked
+    template <class Launch>
+    bool timed(double &ms, Launch &&launch) {
+        if (L.timing && bad(hipEventRecord(e0, 0))) return false;
+        launch_error() = LaunchError{};
+        launch();
+        S.n_launches++;
+        if (bad(launch_error().err)) return false;
+        if (L.timing) {
+            float t = 0.f;
+            if (bad(hipEventRecord(e1, 0)) || bad(hipEventSynchronize(e1)) || bad(hipEventElapsedTime(&t, e0, e1))) return false;
+            ms += t;
+        }
+        return true;
+    }
+};
+
+template <class Prelude, class RecordOf, class Sink>
+int device_search(int device, const Limits &L, nfc_key_stats &S, Prelude &&prelude, RecordOf &&record_of, Sink &&sink) {
+    if (hipSetDevice(device) != hipSuccess) return NFC_ERR_DEVICE;
+    DeviceSearch D{L, S};
+    uint8_t *small = nullptr;
+    uint64_t *scratch = nullptr;
+    uint64_t capacity = L.initial;
+    bool searched = false;
+    auto bad = [&](hipError_t e) { return D.bad(e); };
+    do {
+        if (L.timing && (bad(hipEventCreate(&D.e0)) || bad(hipEventCreate(&D.e1)))) break;
+        if (!prelude(D) || D.nv == 0) break;
+        searched = true;
+        const size_t nv = D.nv;
+        const uint32_t mb = (uint32_t)std::min<size_t>(L.max_batch, nv);
+        // the small per-batch arrays in one allocation: prep | place | counts [2 mb] | n_found [mb] | err [1] (padded) | min_key [mb] | map [mb]
+        const size_t o_place = sizeof(Prepared) * mb, o_counts = o_place + sizeof(Place) * mb, o_found = o_counts + 8 * (size_t)mb,
+                     o_err = o_found + 4 * (size_t)mb, o_min = (o_err + 4 + 7) & ~(size_t)7, o_map = o_min + 8 * (size_t)mb,
+                     small_bytes = o_map + 4 * (size_t)mb;
+        if (bad(hipMalloc((void **)&small, small_bytes)) || bad(hipMalloc((void **)&scratch, capacity * 16))) break;
+        Prepared *d_prep = (Prepared *)small;
+        Place *d_place = (Place *)(small + o_place);
+        uint32_t *d_counts = (uint32_t *)(small + o_counts), *d_found = (uint32_t *)(small + o_found), *d_err = (uint32_t *)(small + o_err);
+        unsigned long long *d_min = (unsigned long long *)(small + o_min);
+        uint32_t *d_map_buf = (uint32_t *)(small + o_map);
+        const Prepared *k_prep = D.d_records ? D.d_records : d_prep;
+        const uint32_t *k_map = D.d_records ? d_map_buf : nullptr;
+        const dim3 block(KEYS_BLOCK);
+        std::vector<Prepared> prep(mb);
+        std::vector<Place> place(mb);
+        std::vector<uint32_t> counts(2 * (size_t)mb), n_odd(mb), found(mb);
+        std::vector<uint64_t> min_key(mb);
+        for (size_t b0 = 0; b0 < nv && D.rc == NFC_OK; b0 += mb) {
+            const uint32_t nb = (uint32_t)std::min<size_t>(mb, nv - b0);
+            for (uint32_t i = 0; i < nb; i++) prep[i] = record_of(b0 + i);
+            // the batch's records, or where they lie; counts, found and err to 0, min_key to all ones
+            if (D.d_records ? bad(hipMemcpy(d_map_buf, D.map + b0, 4 * (size_t)nb, hipMemcpyHostToDevice))
+                            : bad(hipMemcpy(d_prep, prep.data(), sizeof(Prepared) * nb, hipMemcpyHostToDevice)))
+                break;
+            if (bad(hipMemsetAsync(d_counts, 0, o_min - o_counts, 0)) || bad(hipMemsetAsync(d_min, 0xFF, 8 * (size_t)mb, 0))) break;
+            if (!D.timed(S.ms_count, [&] { NFC_LAUNCH(k_keys_count, dim3(WINDOWS / KEYS_BLOCK, 2, nb), block, 0, 0, k_prep, k_map, d_counts); })) break;
+            if (bad(hipMemcpy(counts.data(), d_counts, 8 * (size_t)nb, hipMemcpyDeviceToHost))) break;   // (waits for the launch)
+            for (uint32_t i = 0; i < nb; i++) n_odd[i] = counts[2 * i];
+            const Plan plan = plan_batch(n_odd.data(), nb, L.max);
+            for (const Group &g : plan.groups) {
+                if (g.slots > capacity) {   // grow to fit: the old tables are not needed
+                    (void)hipFree(scratch);
+                    scratch = nullptr;
+                    capacity = g.slots;
+                    S.n_grown++;
+                    if (bad(hipMalloc((void **)&scratch, capacity * 16))) break;
+                }
+                for (uint32_t i = 0; i < nb; i++) {
+                    const bool in = i >= g.t0 && i < g.t1 && plan.log2[i];
+                    place[i] = Place{in ? plan.off[i] : 0, in ? plan.log2[i] : 0u, 0u};
+                }
+                uint64_t *sig_tab = scratch, *seq_tab = scratch + capacity;
+                if (bad(hipMemcpy(d_place, place.data(), sizeof(Place) * nb, hipMemcpyHostToDevice)) ||
+                    bad(hipMemsetAsync(sig_tab, 0xFF, g.slots * 8, 0)))
+                    break;
+                const dim3 grid(WINDOWS / KEYS_BLOCK, 1, g.t1 - g.t0);
+                if (!D.timed(S.ms_fill, [&] { NFC_LAUNCH(k_keys_fill_odd, grid, block, 0, 0, k_prep, k_map, d_place, g.t0, sig_tab, seq_tab, d_err); }))
+                    break;
+                if (!D.timed(S.ms_probe,
+                             [&] { NFC_LAUNCH(k_keys_probe_even, grid, block, 0, 0, k_prep, k_map, d_place, g.t0, sig_tab, seq_tab, d_found, d_min); }))
+                    break;
+                if (bad(hipStreamSynchronize(0))) break;   // (the next group rewrites d_place and the tables)
+            }
+            if (D.rc != NFC_OK) break;
+            uint32_t err = 0;
+            if (bad(hipMemcpy(found.data(), d_found, 4 * (size_t)nb, hipMemcpyDeviceToHost)) ||
+                bad(hipMemcpy(min_key.data(), d_min, 8 * (size_t)nb, hipMemcpyDeviceToHost)) || bad(hipMemcpy(&err, d_err, 4, hipMemcpyDeviceToHost)))
+                break;
+            if (err) {
+                D.rc = NFC_ERR_INTERNAL;
+                break;
+            }
+            for (uint32_t i = 0; i < nb; i++) sink(b0 + i, Verdict{plan.log2[i] == 0, found[i], counts[2 * i], counts[2 * i + 1], min_key[i]}, prep[i]);
+            S.n_batches++;
+        }
+    } while (0);
+    if (D.e0) (void)hipEventDestroy(D.e0);
+    if (D.e1) (void)hipEventDestroy(D.e1);
+    if (scratch) (void)hipFree(scratch);
+    if (small) (void)hipFree(small);
+    for (void *p : D.owned) (void)hipFree(p);
+    S.ms_kernels = S.ms_count + S.ms_fill + S.ms_probe + D.ms_prelude;
+    S.scratch_bytes = searched ? capacity * 16 : 0;
+    return D.rc;
+}
+
+// ---- nested authentications ----
+struct NestedLimits {
+    Limits search;
+    uint32_t first, count;   // count 0: all from first
+};
+bool nested_limits_of(const nfc_nested_config *c, NestedLimits &N) {
+    N.first = N.count = 0;
+    if (!c) return limits_of(nullptr, N.search);
+    if (!limits_of(&c->search, N.search) || c->cand_first > NESTED_CANDS || c->reserved[0] || c->reserved[1]) return false;
+    N.first = c->cand_first, N.count = c->cand_count;
+    return true;
+}
+// the window of a trace with n_nt candidates: [first, end)
+uint32_t window_end(const NestedLimits &N, uint32_t n_nt) {
+    if (N.first >= n_nt) return N.first;
+    return N.count ? (uint32_t)std::min<uint64_t>((uint64_t)N.first + N.count, n_nt) : n_nt;
+}
+// the records of one trace in ascending seed order, at most NESTED_CANDS (the kernel's rule) -> how many
+uint32_t nested_records(const nfc_nested_trace &t, uint32_t parent, Prepared *out) {
+    uint32_t n = 0;
+    for (uint32_t seed = 0; seed < NESTED_SEEDS; seed++) {
+        Prepared P;
+        if (nested_candidate(t, parent, seed, P) && n < NESTED_CANDS) out[n++] = P;
+    }
+    return n;
+}
+// One nested trace's result from the verdicts of its searched candidates, in candidate order: the sums, the lowest key and its nt.
+struct NestedFold {
+    nfc_nested_result r;
+    uint64_t min_key = ~0ull;
+    bool overflow = false;
+    Prepared best;
+    explicit NestedFold(uint32_t n_nt) {
+        memset(&r, 0, sizeof r);
+        r.n_nt = n_nt;
+    }
+    void add(const Verdict &v, const Prepared &P) {
+        r.n_searched++;
+        r.n_odd += v.n_odd, r.n_even += v.n_even;
+        if (v.overflow) {
+            overflow = true;
+            return;
+        }
+        r.n_verified = (uint32_t)std::min<uint64_t>((uint64_t)r.n_verified + v.n_found, 0xFFFFFFFFull);
+        if (v.n_found && v.min_key < min_key) min_key = v.min_key, best = P;
+    }
+    nfc_nested_result done() {
+        r.status = overflow ? NFC_KEY_OVERFLOW : r.n_verified == 0 ? NFC_KEY_NONE : r.n_verified == 1 ? NFC_KEY_OK : NFC_KEY_AMBIGUOUS;
+        if (r.n_verified) {
+            for (int i = 0; i < 6; i++) r.key[i] = (uint8_t)(min_key >> (8 * i));
+            r.nt = best.nt;
+            (void)verify(min_key, best, &r.nr);
+        }
+        return r;
+    }
+};
+// `records` [n][NESTED_CANDS] and n_nt [n] -> the virtual traces of the windows, in order: their places in `records`
+std::vector<uint32_t> virtual_traces(const NestedLimits &N, const uint32_t *n_nt, size_t n) {
+    std::vector<uint32_t> map;
+    for (size_t p = 0; p < n; p++)
+        for (uint32_t c = N.first; c < window_end(N, n_nt[p]); c++) map.push_back((uint32_t)(p * NESTED_CANDS + c));
+    return map;
+}
+// the folds of all traces, fed by either search's sink in virtual-trace order
+struct NestedFolds {
+    std::vector<NestedFold> f;
+    NestedFolds(const uint32_t *n_nt, size_t n) {
+        f.reserve(n);
+        for (size_t p = 0; p < n; p++) f.emplace_back(n_nt[p]);
+    }
+    void add(uint32_t place, const Verdict &v, const Prepared &P) { f[place / NESTED_CANDS].add(v, P); }
+    void done(nfc_nested_result *out) {
+        for (size_t p = 0; p < f.size(); p++) out[p] = f[p].done();
+    }
+};
+// the candidate launch for all traces; the records stay on the device (d_rec) and come down once, with the counts, for the host's side
+bool launch_candidates(DeviceSearch &D, const nfc_nested_trace *traces, size_t n, Prepared *&d_rec, std::vector<Prepared> &rec, uint32_t *n_nt) {
+    nfc_nested_trace *d_traces = nullptr;
+    uint32_t *d_n = nullptr;   // [n] counts, then the error word
+    rec.resize(n * NESTED_CANDS);
+    if (!D.alloc(d_traces, sizeof(nfc_nested_trace) * n) || !D.alloc(d_rec, sizeof(Prepared) * rec.size()) || !D.alloc(d_n, 4 * (n + 1))) return false;
+    if (D.bad(hipMemcpy(d_traces, traces, sizeof(nfc_nested_trace) * n, hipMemcpyHostToDevice)) ||
+        D.bad(hipMemsetAsync(d_rec, 0, sizeof(Prepared) * rec.size(), 0)) || D.bad(hipMemsetAsync(d_n, 0, 4 * (n + 1), 0)))
+        return false;
+    if (!D.timed(D.ms_prelude, [&] { NFC_LAUNCH(k_nested_candidates, dim3((uint32_t)n), dim3(NESTED_BLOCK), 0, 0, d_traces, d_rec, d_n, d_n + n); }))
+        return false;
+    uint32_t err = 0;
+    if (D.bad(hipMemcpy(n_nt, d_n, 4 * n, hipMemcpyDeviceToHost)) || D.bad(hipMemcpy(&err, d_n + n, 4, hipMemcpyDeviceToHost)) ||
+        D.bad(hipMemcpy(rec.data(), d_rec, sizeof(Prepared) * rec.size(), hipMemcpyDeviceToHost)))
+        return false;
+    if (err) D.rc = NFC_ERR_INTERNAL;
+    for (size_t p = 0; p < n; p++) n_nt[p] = std::min<uint32_t>(n_nt[p], NESTED_CANDS);
+    return !err;
+}
+constexpr size_t NESTED_MAX_TRACES = (1ull << 32) / NESTED_CANDS;   // a record's place is 32 bits
 
 bool key_type_ok(const nfc_auth_trace &t) { return t.key_type == 0x60 || t.key_type == 0x61; }
 
@@ -160,39 +441,7 @@ int nfc_host_recover_keys(const nfc_auth_trace *traces, size_t n, const nfc_key_
         if (!key_type_ok(traces[i])) return NFC_ERR_ARG;
     nfc_key_stats S;
     memset(&S, 0, sizeof S);
-    uint64_t capacity = L.initial;
-    std::vector<std::pair<uint64_t, uint64_t>> odd;   // (signature, sequence)
-    std::vector<uint32_t> n_odd;
-    for (size_t b0 = 0; b0 < n; b0 += L.max_batch) {
-        const uint32_t nb = (uint32_t)std::min<size_t>(L.max_batch, n - b0);
-        n_odd.assign(nb, 0);
-        for (uint32_t i = 0; i < nb; i++) {
-            const Prepared P = prepare(traces[b0 + i]);
-            odd.clear();
-            for (uint32_t w = 0; w < WINDOWS; w++) walk(w, P.ks_odd, [&](uint64_t seq) { odd.emplace_back(signature<0>(seq), seq); });
-            n_odd[i] = (uint32_t)odd.size();
-            const bool overflow = (1ull << table_log2(odd.size())) > L.max;
-            if (!overflow) std::sort(odd.begin(), odd.end());
-            uint32_t n_even = 0, n_found = 0;
-            uint64_t min_key = ~0ull;
-            for (uint32_t w = 0; w < WINDOWS; w++)
-                n_even += walk(w, P.ks_even, [&](uint64_t seq) {
-                    if (overflow) return;
-                    const uint64_t sig = signature<1>(seq);
-                    for (auto it = std::lower_bound(odd.begin(), odd.end(), std::make_pair(sig, (uint64_t)0)); it != odd.end() && it->first == sig; ++it) {
-                        const uint64_t key = rollback(join_state(it->second, seq), P);
-                        if (verify(key, P, nullptr)) {
-                            if (n_found != 0xFFFFFFFFu) n_found++;
-                            min_key = std::min(min_key, key);
-                        }
-                    }
-                });
-            result_of(out[b0 + i], overflow, n_found, min_key, n_odd[i], n_even, P);
-        }
-        account(plan_batch(n_odd.data(), nb, L.max), capacity, S);
-        S.n_batches++;
-    }
-    S.scratch_bytes = n ? capacity * 16 : 0;
+    host_search(L, S, n, [&](size_t v) { return prepare(traces[v]); }, [&](size_t v, const Verdict &V, const Prepared &P) { result_of(out[v], V, P); });
     if (stats) *stats = S;
     return NFC_OK;
 }
@@ -207,100 +456,139 @@ int nfc_recover_keys_device(int device, const nfc_auth_trace *traces, size_t n, 
     memset(&S, 0, sizeof S);
     if (stats) *stats = S;
     if (n == 0) return NFC_OK;
-    if (hipSetDevice(device) != hipSuccess) return NFC_ERR_DEVICE;
+    const int rc = device_search(
+        device, L, S,
+        [&](DeviceSearch &D) {
+            D.nv = n;
+            return true;
+        },
+        [&](size_t v) { return prepare(traces[v]); }, [&](size_t v, const Verdict &V, const Prepared &P) { result_of(out[v], V, P); });
+    if (stats) *stats = S;
+    return rc;
+}
 
-    const uint32_t mb = (uint32_t)std::min<size_t>(L.max_batch, n);
-    // the small per-batch arrays in one allocation: prep | place | counts [2 mb] | n_found [mb] | err [1] (padded) | min_key [mb]
-    const size_t o_place = sizeof(Prepared) * mb, o_counts = o_place + sizeof(Place) * mb, o_found = o_counts + 8 * (size_t)mb,
-                 o_err = o_found + 4 * (size_t)mb, o_min = (o_err + 4 + 7) & ~(size_t)7, small_bytes = o_min + 8 * (size_t)mb;
-    uint8_t *small = nullptr;
-    uint64_t *scratch = nullptr;
-    uint64_t capacity = L.initial;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int rc = NFC_OK;
-    auto bad = [&](hipError_t e, int status = NFC_ERR_DEVICE) {
-        if (e == hipSuccess) return false;
-        rc = (e == hipErrorOutOfMemory) ? NFC_ERR_NOMEM : status;
-        return true;
+int nfc_find_nested_auths(const nfc_raw_frame *frames, size_t n, const uint8_t *bytes0, const uint8_t *par0, const uint8_t *bytes1,
+                          const uint8_t *par1, nfc_nested_trace *out, size_t cap, size_t *n_out) {
+    if (!n_out || (n && !frames) || (cap && !out)) return NFC_ERR_ARG;
+    *n_out = 0;
+    for (size_t i = 0; i < n; i++)
+        if (frames[i].type != 0 && frames[i].type != 1) return NFC_ERR_ARG;
+    auto bytes_of = [&](const nfc_raw_frame &r) { return (r.type ? bytes1 : bytes0) + r.byte_off; };
+    auto par_of = [&](const nfc_raw_frame &r) { return (r.type ? par1 : par0) + r.byte_off; };
+    auto is = [&](size_t i, int type, uint32_t n_bytes, uint32_t need) {
+        const nfc_raw_frame &r = frames[i];
+        if (r.type != type || (r.flags & NFC_RAW_CUT) || r.n_bytes != n_bytes || (r.flags & need) != need) return false;
+        return (r.type ? bytes1 && par1 : bytes0 && par0);
     };
-    // one launch, timed by HIP events when asked
-    auto timed = [&](double &ms, auto &&launch) {
-        if (L.timing && bad(hipEventRecord(e0, 0))) return false;
-        launch_error() = LaunchError{};
-        launch();
-        S.n_launches++;
-        if (bad(launch_error().err)) return false;
-        if (L.timing) {
-            float t = 0.f;
-            if (bad(hipEventRecord(e1, 0)) || bad(hipEventSynchronize(e1)) || bad(hipEventElapsedTime(&t, e0, e1))) return false;
-            ms += t;
+    auto word = [](const uint8_t *b) { return (uint32_t)b[0] | (uint32_t)b[1] << 8 | (uint32_t)b[2] << 16 | (uint32_t)b[3] << 24; };
+    bool have_uid = false, session = false;   // session: a first authentication of this UID was seen
+    uint32_t uid = 0;
+    size_t found = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (is(i, 1, 9, NFC_RAW_CRC_A_OK)) {
+            const uint8_t *b = bytes_of(frames[i]);
+            if (b[0] == 0x93 && b[1] == 0x70) have_uid = true, session = false, uid = word(b + 2);
+            continue;
         }
-        return true;
-    };
-    std::vector<Prepared> prep(mb);
-    std::vector<Place> place(mb);
-    std::vector<uint32_t> counts(2 * (size_t)mb), n_odd(mb), found(mb);
-    std::vector<uint64_t> min_key(mb);
-    do {
-        if (bad(hipMalloc((void **)&small, small_bytes)) || bad(hipMalloc((void **)&scratch, capacity * 16))) break;
-        if (L.timing && (bad(hipEventCreate(&e0)) || bad(hipEventCreate(&e1)))) break;
-        Prepared *d_prep = (Prepared *)small;
-        Place *d_place = (Place *)(small + o_place);
-        uint32_t *d_counts = (uint32_t *)(small + o_counts), *d_found = (uint32_t *)(small + o_found), *d_err = (uint32_t *)(small + o_err);
-        unsigned long long *d_min = (unsigned long long *)(small + o_min);
-        const dim3 block(KEYS_BLOCK);
-        for (size_t b0 = 0; b0 < n && rc == NFC_OK; b0 += mb) {
-            const uint32_t nb = (uint32_t)std::min<size_t>(mb, n - b0);
-            for (uint32_t i = 0; i < nb; i++) prep[i] = prepare(traces[b0 + i]);
-            // counts, found and err to 0, min_key to all ones
-            if (bad(hipMemcpy(d_prep, prep.data(), sizeof(Prepared) * nb, hipMemcpyHostToDevice)) ||
-                bad(hipMemsetAsync(d_counts, 0, o_min - o_counts, 0)) || bad(hipMemsetAsync(d_min, 0xFF, 8 * (size_t)mb, 0)))
-                break;
-            if (!timed(S.ms_count, [&] { NFC_LAUNCH(k_keys_count, dim3(WINDOWS / KEYS_BLOCK, 2, nb), block, 0, 0, d_prep, d_counts); })) break;
-            if (bad(hipMemcpy(counts.data(), d_counts, 8 * (size_t)nb, hipMemcpyDeviceToHost))) break;   // (waits for the launch)
-            for (uint32_t i = 0; i < nb; i++) n_odd[i] = counts[2 * i];
-            const Plan plan = plan_batch(n_odd.data(), nb, L.max);
-            for (const Group &g : plan.groups) {
-                if (g.slots > capacity) {   // grow to fit: the old tables are not needed
-                    (void)hipFree(scratch);
-                    scratch = nullptr;
-                    capacity = g.slots;
-                    S.n_grown++;
-                    if (bad(hipMalloc((void **)&scratch, capacity * 16))) break;
-                }
-                for (uint32_t i = 0; i < nb; i++) {
-                    const bool in = i >= g.t0 && i < g.t1 && plan.log2[i];
-                    place[i] = Place{in ? plan.off[i] : 0, in ? plan.log2[i] : 0u, 0u};
-                }
-                uint64_t *sig_tab = scratch, *seq_tab = scratch + capacity;
-                if (bad(hipMemcpy(d_place, place.data(), sizeof(Place) * nb, hipMemcpyHostToDevice)) ||
-                    bad(hipMemsetAsync(sig_tab, 0xFF, g.slots * 8, 0)))
-                    break;
-                const dim3 grid(WINDOWS / KEYS_BLOCK, 1, g.t1 - g.t0);
-                if (!timed(S.ms_fill, [&] { NFC_LAUNCH(k_keys_fill_odd, grid, block, 0, 0, d_prep, d_place, g.t0, sig_tab, seq_tab, d_err); })) break;
-                if (!timed(S.ms_probe, [&] { NFC_LAUNCH(k_keys_probe_even, grid, block, 0, 0, d_prep, d_place, g.t0, sig_tab, seq_tab, d_found, d_min); }))
-                    break;
-                if (bad(hipStreamSynchronize(0))) break;   // (the next group rewrites d_place and the tables)
-            }
-            if (rc != NFC_OK) break;
-            uint32_t err = 0;
-            if (bad(hipMemcpy(found.data(), d_found, 4 * (size_t)nb, hipMemcpyDeviceToHost)) ||
-                bad(hipMemcpy(min_key.data(), d_min, 8 * (size_t)nb, hipMemcpyDeviceToHost)) || bad(hipMemcpy(&err, d_err, 4, hipMemcpyDeviceToHost)))
-                break;
-            if (err) {
-                rc = NFC_ERR_INTERNAL;
-                break;
-            }
-            for (uint32_t i = 0; i < nb; i++) result_of(out[b0 + i], plan.log2[i] == 0, found[i], min_key[i], counts[2 * i], counts[2 * i + 1], prep[i]);
-            S.n_batches++;
+        if (!have_uid || i + 3 >= n || !is(i, 1, 4, 0)) continue;
+        const uint8_t *a = bytes_of(frames[i]);
+        const bool plain = (frames[i].flags & NFC_RAW_CRC_A_OK) && (a[0] == 0x60 || a[0] == 0x61);
+        if (plain) {   // nfc_find_auths' rule
+            if (is(i + 1, 0, 4, NFC_RAW_PARITY_OK) && is(i + 2, 1, 8, 0) && is(i + 3, 0, 4, 0)) session = true;
+            continue;
         }
-    } while (0);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (scratch) (void)hipFree(scratch);
-    if (small) (void)hipFree(small);
-    S.ms_kernels = S.ms_count + S.ms_fill + S.ms_probe;
-    S.scratch_bytes = capacity * 16;
+        if (!session || !is(i + 1, 0, 4, 0) || !is(i + 2, 1, 8, 0) || !is(i + 3, 0, 4, 0)) continue;
+        if (found < cap) {
+            nfc_nested_trace &t = out[found];
+            memset(&t, 0, sizeof t);
+            const uint8_t *rb = bytes_of(frames[i + 2]), *rp = par_of(frames[i + 2]), *tp = par_of(frames[i + 3]), *np = par_of(frames[i + 1]);
+            t.uid = uid;
+            t.nt_enc = word(bytes_of(frames[i + 1]));
+            t.nr_enc = word(rb);
+            t.ar_enc = word(rb + 4);
+            t.at_enc = word(bytes_of(frames[i + 3]));
+            for (int k = 0; k < 8; k++) t.par |= (uint16_t)((rp[k] & 1u) << k);
+            for (int k = 0; k < 4; k++) t.par |= (uint16_t)((tp[k] & 1u) << (8 + k));
+            for (int k = 0; k < 4; k++) t.par |= (uint16_t)((np[k] & 1u) << (12 + k));
+            t.key_type = 0;
+            t.block = 0xFF;
+            t.frame = (uint32_t)i;
+            t.idx = frames[i].idx;
+        }
+        found++;
+    }
+    *n_out = found;
+    return NFC_OK;
+}
+
+int nfc_host_nested_candidates(const nfc_nested_trace *trace, uint32_t *out_nt, size_t cap, size_t *n_out) {
+    if (!trace || !n_out || (cap && !out_nt)) return NFC_ERR_ARG;
+    Prepared rec[NESTED_CANDS];
+    const uint32_t n = nested_records(*trace, 0, rec);
+    for (uint32_t i = 0; i < n && i < cap; i++) out_nt[i] = rec[i].nt;
+    *n_out = n;
+    return NFC_OK;
+}
+
+int nfc_nested_candidates_device(int device, const nfc_nested_trace *traces, size_t n, uint32_t *out_nt, uint32_t *out_n) {
+    if ((n && (!traces || !out_nt || !out_n)) || device < 0 || n > NESTED_MAX_TRACES) return NFC_ERR_ARG;
+    if (n == 0) return NFC_OK;
+    Limits L;
+    (void)limits_of(nullptr, L);
+    nfc_key_stats S;
+    memset(&S, 0, sizeof S);
+    std::vector<Prepared> rec;
+    return device_search(
+        device, L, S,
+        [&](DeviceSearch &D) {   // the prelude alone: no record is searched
+            Prepared *d_rec = nullptr;
+            if (!launch_candidates(D, traces, n, d_rec, rec, out_n)) return false;
+            for (size_t i = 0; i < rec.size(); i++) out_nt[i] = rec[i].nt;
+            return true;
+        },
+        [&](size_t) { return Prepared{}; }, [&](size_t, const Verdict &, const Prepared &) {});
+}
+
+int nfc_host_recover_nested_keys(const nfc_nested_trace *traces, size_t n, const nfc_nested_config *cfg, nfc_nested_result *out,
+                                 nfc_key_stats *stats) {
+    NestedLimits N;
+    if (!nested_limits_of(cfg, N) || (n && (!traces || !out)) || n > NESTED_MAX_TRACES) return NFC_ERR_ARG;
+    nfc_key_stats S;
+    memset(&S, 0, sizeof S);
+    std::vector<Prepared> rec(n * NESTED_CANDS);
+    std::vector<uint32_t> n_nt(n);
+    for (size_t p = 0; p < n; p++) n_nt[p] = nested_records(traces[p], (uint32_t)p, rec.data() + p * NESTED_CANDS);
+    const std::vector<uint32_t> map = virtual_traces(N, n_nt.data(), n);
+    NestedFolds folds(n_nt.data(), n);
+    host_search(N.search, S, map.size(), [&](size_t v) { return rec[map[v]]; }, [&](size_t v, const Verdict &V, const Prepared &P) { folds.add(map[v], V, P); });
+    folds.done(out);
+    if (stats) *stats = S;
+    return NFC_OK;
+}
+
+int nfc_recover_nested_keys_device(int device, const nfc_nested_trace *traces, size_t n, const nfc_nested_config *cfg, nfc_nested_result *out,
+                                   nfc_key_stats *stats) {
+    NestedLimits N;
+    if (!nested_limits_of(cfg, N) || (n && (!traces || !out)) || device < 0 || n > NESTED_MAX_TRACES) return NFC_ERR_ARG;
+    nfc_key_stats S;
+    memset(&S, 0, sizeof S);
+    if (stats) *stats = S;
+    if (n == 0) return NFC_OK;
+    std::vector<Prepared> rec;   // the device's records, read back for the fold (key -> nt, nr); never sent up
+    std::vector<uint32_t> n_nt(n), map;
+    std::vector<NestedFolds> folds;   // (made once n_nt is known)
+    const int rc = device_search(
+        device, N.search, S,
+        [&](DeviceSearch &D) {
+            Prepared *d_rec = nullptr;
+            if (!launch_candidates(D, traces, n, d_rec, rec, n_nt.data())) return false;
+            map = virtual_traces(N, n_nt.data(), n);
+            D.map = map.data(), D.nv = map.size(), D.d_records = d_rec;
+            folds.emplace_back(n_nt.data(), n);
+            return true;
+        },
+        [&](size_t v) { return rec[map[v]]; }, [&](size_t v, const Verdict &V, const Prepared &P) { folds[0].add(map[v], V, P); });
+    if (rc == NFC_OK && !folds.empty()) folds[0].done(out);
     if (stats) *stats = S;
     return rc;
 }

@@ -82,7 +82,7 @@ _RECORDED_KINDS = _IQ_KINDS + (api.NFC_IN_ENV_F32,)   # (the kinds `dst` records
 
 
 def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None, keep=None, device=0, push_stats=None, frames=False, commands=False,
-                keys=None, **sink_kwargs):
+                keys=None, nested=False, **sink_kwargs):
     """Decode many recordings at once: every source is a stream of one api.NfcMultiContext, a GPU lane each, one kernel launch per
     round of pieces (include/nfc_amd.h: nfc_multi) -- what a loop of ``decoder(src=s).run()`` does capture by capture.
 
@@ -104,6 +104,10 @@ def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None,
     (usrp_nfc_amd.keys.recover) searches the keys of all their first authentications, the context is reset, every stream gets the first
     key found for type A and for type B (the default where none was found), and the tracked pass follows as above.  Every background
     gets ``recovered_keys``: (key_type, block) -> six key bytes.  The cost is the doubled push.
+    nested=True (with keys='recover'): the nested authentications are searched too (usrp_nfc_amd.keys.recover_streams), and
+    ``recovered_keys`` holds every sector key whose AUTH command could be decrypted and labelled.  The streams still get
+    ``first_keys(...)``: the machine holds ONE key A and ONE key B, so a card with more than one key per type decrypts only as far as
+    those two reach (a per-sector key table in the machine is not built: DESIGN.md 8i).
     -> one ``background`` per source, in order: ``decode_many(srcs)[i].packets`` and its fsm's command trace are what
     ``decoder(src=srcs[i]).run()`` gives."""
     scales = {k: sink_kwargs.pop(k, 0.0) for k in ('wav_scale', 'iq16_scale', 'iq8_scale')}
@@ -130,6 +134,8 @@ def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None,
             raise ValueError('decode_many: keys are for commands=True')
         for b in backs:
             b.recovered_keys = {}
+    elif nested:
+        raise ValueError("decode_many: nested is for keys='recover'")
     elif keys is not None:
         if not commands:
             raise ValueError('decode_many: keys are for commands=True')
@@ -155,7 +161,7 @@ def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None,
             with api.NfcMultiContext(len(group), piece, samp_rate=samp_rate, hi_val=_hi_val(kind), reader=reader, tag=tag, input_kind=kind,
                                      device=device, i16_scale=scale if kind in _SCALED_KINDS else 0.0, **sink) as m:
                 if recover:
-                    _recover_group_keys(m, buf, starts, lens, piece, backs[g0:g0 + len(group)], device)
+                    _recover_group_keys(m, buf, starts, lens, piece, backs[g0:g0 + len(group)], device, nested)
                 if commands:
                     m.track_commands(True)
                     if recover:
@@ -212,7 +218,7 @@ def _joined_frames(parts):
                          [cat(par[t], numpy.uint8) for t in (0, 1)])
 
 
-def _recover_group_keys(m, buf, starts, lens, piece, backs, device):
+def _recover_group_keys(m, buf, starts, lens, piece, backs, device, nested=False):
     """The untracked pass of decode_many(keys='recover') over one group: every source's frames across its pushes, one recovery call for
     all of them, the context reset afterwards.  Fills every background's ``recovered_keys``."""
     parts = [[] for _ in backs]
@@ -226,6 +232,11 @@ def _recover_group_keys(m, buf, starts, lens, piece, backs, device):
         fr = m.fetch_frames()
         for k in numpy.nonzero(n)[0]:
             parts[int(k)].append((fr.frames_of(int(k)), int(fr.base[k]) if len(fr.base) else 0))
+    if nested:
+        for b, found in zip(backs, _keys.recover_streams([_joined_frames(ps) if ps else None for ps in parts], device=device)):
+            b.recovered_keys = found
+        m.reset()
+        return
     traces = []
     for k, ps in enumerate(parts):
         a = _keys.find_auths(_joined_frames(ps))

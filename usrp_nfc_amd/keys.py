@@ -1,36 +1,51 @@
-"""MIFARE Classic key recovery from sniffed first authentications (include/nfc_amd.h: nfc_find_auths, nfc_recover_keys_device,
-nfc_host_recover_keys; csrc/keys.hip.h states the method, DESIGN.md 8h the layout).
+"""MIFARE Classic key recovery from sniffed authentications (include/nfc_amd.h: nfc_find_auths, nfc_recover_keys_device,
+nfc_host_recover_keys and their nested counterparts; csrc/keys.hip.h states the method, DESIGN.md 8h and 8i the layout).
 
 ``find_auths(frames)`` picks the first authentications out of one stream's frames, ``recover(traces)`` searches their keys on the GPU,
 ``host_recover(traces)`` is the same search on one CPU core.  Both return ``(results, stats)``: a KEY_RESULT_DTYPE record per trace and
-the call's _lib.KeyStats.  There is no fall-back from one to the other."""
+the call's _lib.KeyStats.  There is no fall-back from one to the other.
+
+Every later authentication of a session is NESTED, its tag nonce encrypted: ``find_nested_auths(frames)`` finds them by shape,
+``nested_candidates(traces)`` lists the 64 (or 0) plaintext nonces each can have, ``recover_nested(traces)`` / ``host_recover_nested``
+search one key per candidate and report a NESTED_RESULT_DTYPE record per trace, and ``label_auths`` decrypts the AUTH commands with the
+recovered keys to say which sector each key belongs to."""
 import ctypes as C
 
 import numpy as np
 
 from . import _lib
-from ._lib import (AUTH_DTYPE, KEY_RESULT_DTYPE, NFC_KEY_AMBIGUOUS, NFC_KEY_NONE, NFC_KEY_OK, NFC_KEY_OVERFLOW,  # noqa: F401
-                   NFC_KEY_TIMING)
+from ._lib import (AUTH_DTYPE, KEY_RESULT_DTYPE, NESTED_CANDS, NESTED_DTYPE, NESTED_RESULT_DTYPE, NFC_KEY_AMBIGUOUS,  # noqa: F401
+                   NFC_KEY_NONE, NFC_KEY_OK, NFC_KEY_OVERFLOW, NFC_KEY_TIMING)
 
 
 class KeyRecoveryError(RuntimeError):
     pass
 
 
-def find_auths(frames):
-    """The first authentications of one stream: `frames` an api.NfcFrames (NfcContext.frames(), NfcMultiFrames.frames_of(k),
-    api.host_frames) -> AUTH_DTYPE records in stream order, `stream` 0."""
+def _find(name, dtype, frames):
     L = _lib.load()
     t = np.ascontiguousarray(frames.table, _lib.RAW_FRAME_DTYPE)
     b = [np.ascontiguousarray(a, np.uint8) for a in frames.bytes]
     p = [np.ascontiguousarray(a, np.uint8) for a in frames.par]
-    out = np.zeros(len(t) // 4 + 1, AUTH_DTYPE)   # (an authentication is four frames)
+    out = np.zeros(len(t) // 4 + 1, dtype)   # (an authentication is four frames)
     n = C.c_size_t(0)
     ptr = lambda a: a.ctypes.data if a.size else None
-    rc = L.nfc_find_auths(ptr(t), len(t), ptr(b[0]), ptr(p[0]), ptr(b[1]), ptr(p[1]), out.ctypes.data, len(out), C.byref(n))
+    rc = getattr(L, name)(ptr(t), len(t), ptr(b[0]), ptr(p[0]), ptr(b[1]), ptr(p[1]), out.ctypes.data, len(out), C.byref(n))
     if rc != 0:
-        raise KeyRecoveryError('nfc_find_auths status %d' % rc)
+        raise KeyRecoveryError('%s status %d' % (name, rc))
     return out[:n.value]
+
+
+def find_auths(frames):
+    """The first authentications of one stream: `frames` an api.NfcFrames (NfcContext.frames(), NfcMultiFrames.frames_of(k),
+    api.host_frames) -> AUTH_DTYPE records in stream order, `stream` 0."""
+    return _find('nfc_find_auths', AUTH_DTYPE, frames)
+
+
+def find_nested_auths(frames):
+    """The nested authentications of one stream, found by shape with no keys (nfc_find_nested_auths) -> NESTED_DTYPE records in stream
+    order, `stream` 0, key_type 0 and block 0xFF (label_auths fills them in)."""
+    return _find('nfc_find_nested_auths', NESTED_DTYPE, frames)
 
 
 def _config(initial_capacity=0, max_capacity=0, max_batch=0, timing=False):
@@ -75,3 +90,110 @@ def first_keys(found):
         ks = [v for (t, _), v in found.items() if t == kt]
         pair.append(list(bytearray(ks[0])) if ks else [0xFF] * 6)
     return tuple(pair)
+
+
+def nested_candidates(traces, device=None):
+    """The candidate plaintext nonces of every nested trace, ascending in seed -> (nt [n][64] uint32, n [n] uint32; unused entries 0).
+    device None: the host twin (nfc_host_nested_candidates), else the kernel's answer on that device (nfc_nested_candidates_device)."""
+    L = _lib.load()
+    t = np.ascontiguousarray(traces, NESTED_DTYPE).reshape(-1)
+    nt, cnt = np.zeros((len(t), NESTED_CANDS), np.uint32), np.zeros(len(t), np.uint32)
+    if device is None:
+        for i in range(len(t)):
+            n = C.c_size_t(0)
+            rc = L.nfc_host_nested_candidates(t[i:i + 1].ctypes.data, nt[i].ctypes.data, NESTED_CANDS, C.byref(n))
+            if rc != 0:
+                raise KeyRecoveryError('nfc_host_nested_candidates status %d' % rc)
+            cnt[i] = n.value
+    else:
+        ptr = lambda a: a.ctypes.data if a.size else None
+        rc = L.nfc_nested_candidates_device(int(device), ptr(t), len(t), ptr(nt), ptr(cnt))
+        if rc != 0:
+            raise KeyRecoveryError('nfc_nested_candidates_device status %d' % rc)
+    return nt, cnt
+
+
+def _run_nested(call, traces, cand_first, cand_count, cfg):
+    t = np.ascontiguousarray(traces, NESTED_DTYPE).reshape(-1)
+    out, stats = np.zeros(len(t), NESTED_RESULT_DTYPE), _lib.KeyStats()
+    c = _lib.NestedConfig(_config(**cfg), int(cand_first), int(cand_count))
+    rc = call(t.ctypes.data if len(t) else None, len(t), C.byref(c), out.ctypes.data if len(t) else None, C.byref(stats))
+    if rc != 0:
+        raise KeyRecoveryError('nested key recovery failed with status %d' % rc)
+    return out, stats
+
+
+def recover_nested(traces, device=0, cand_first=0, cand_count=0, **cfg):
+    """Every nested trace's key on the GPU (nfc_recover_nested_keys_device): one search per candidate nonce of the window
+    [cand_first, cand_first + cand_count) of each trace's ascending list (cand_count 0: all from cand_first).  cfg: recover's; capacity
+    and max_batch count (trace, candidate) pairs.  -> (NESTED_RESULT_DTYPE records, _lib.KeyStats)."""
+    L = _lib.load()
+    return _run_nested(lambda *a: L.nfc_recover_nested_keys_device(int(device), *a), traces, cand_first, cand_count, cfg)
+
+
+def host_recover_nested(traces, cand_first=0, cand_count=0, **cfg):
+    """The CPU twin (nfc_host_recover_nested_keys): a quarter of a second per candidate on one core, so give it a window."""
+    return _run_nested(_lib.load().nfc_host_recover_nested_keys, traces, cand_first, cand_count, cfg)
+
+
+def label_auths(frames, firsts, first_results, nested, nested_results):
+    """Which sector every recovered key of ONE stream belongs to.  Host only.  The project's protocol machine runs once over `frames` (an
+    api.NfcFrames), in slices: before the AUTH frame of every authentication whose key was recovered (status NFC_KEY_OK) both of its keys
+    are set to that key.  A nested trace's AUTH command then decrypts under its PREDECESSOR's key, and where its CRC holds the trace's
+    key_type and block are filled in (`nested` is written in place); one whose predecessor's key was not recovered stays unlabelled.
+    -> dict (key_type, block) -> six key bytes over the firsts and the labelled nesteds with status OK; the first of a kind wins."""
+    from . import fsm as _fsm
+    import io
+    auths = sorted([(int(t['frame']), False, i) for i, t in enumerate(firsts)] + [(int(t['frame']), True, i) for i, t in enumerate(nested)])
+    m = _fsm.fsm(out=io.StringIO())
+    table, found, at = frames.table, {}, 0
+    key_bytes = lambda r: bytes(bytearray(r['key'].tolist()))
+
+    def run(upto):   # the frames [at, upto) -> the record of the last one and its plaintext bytes
+        out, buf = m.process_frames(table[at:upto], frames.bytes, frames.par, dispatch=False)
+        if not len(out):
+            return None, []
+        o = int(out[-1]['byte_off'])
+        return out[-1], buf[o:o + int(out[-1]['n_bytes'])].tolist()
+
+    prev_ok = False   # the session's keystream is right up to here: the previous authentication's key is known
+    for frame, is_nested, i in auths:
+        run(frame)
+        at = frame
+        r = (nested_results if is_nested else first_results)[i]
+        ok = int(r['status']) == NFC_KEY_OK
+        if ok:
+            m.set_keys(r['key'].tolist(), r['key'].tolist())
+        rec, data = run(frame + 1)   # the AUTH frame itself; the nonce that follows takes the key that is set now
+        at = frame + 1
+        # (the machine names a frame AUTHA / AUTHB only where 60|61 blk crc decrypts with its CRC right)
+        if is_nested and prev_ok and rec is not None and len(data) == 4 and data[0] in (0x60, 0x61) and int(rec['n_crc']) == 2:
+            nested[i]['key_type'], nested[i]['block'] = data[0], data[1]
+        t = (nested if is_nested else firsts)[i]
+        if ok and int(t['key_type']) in (0x60, 0x61):
+            found.setdefault((int(t['key_type']), int(t['block'])), key_bytes(r))
+        prev_ok = ok
+    return found
+
+
+def recover_streams(frames_by_stream, device=0, **cfg):
+    """First AND nested authentications of several streams: `frames_by_stream` one api.NfcFrames (or None) per stream -> per stream the
+    dict of label_auths.  ONE keys.recover call over all first authentications, ONE keys.recover_nested call over all nested ones (cfg:
+    recover's), then label_auths per stream on the host."""
+    firsts, nested = [], []
+    for k, fr in enumerate(frames_by_stream):
+        if fr is None:
+            continue
+        for find, parts in ((find_auths, firsts), (find_nested_auths, nested)):
+            a = find(fr)
+            a['stream'] = k
+            parts.append(a)
+    firsts = np.concatenate(firsts) if firsts else np.zeros(0, AUTH_DTYPE)
+    nested = np.concatenate(nested) if nested else np.zeros(0, NESTED_DTYPE)
+    first_results, _ = recover(firsts, device=device, **cfg)
+    nested_results, _ = recover_nested(nested, device=device, **cfg)
+    out = []
+    for k, fr in enumerate(frames_by_stream):
+        a, b = firsts['stream'] == k, nested['stream'] == k
+        out.append(label_auths(fr, firsts[a], first_results[a], nested[b].copy(), nested_results[b]) if fr is not None and a.any() else {})
+    return out
