@@ -48,11 +48,29 @@ constexpr int DEC_ITEMS = 16;                       // edges per group: one 16-b
 #define NFC_DEC_GROUPS 2
 #endif
 constexpr int DEC_GROUPS = NFC_DEC_GROUPS;          // groups per thread in the multi-launch stage: a tile's block scans (the
-                                                    // larger part of k_dec_reduce's instructions) are paid per 32 edges, not 16
+                                                    // larger part of k_dec_reduce's instructions) are paid per 32 edges, not 16.
+                                                    // One (tiles of 4 096 edges) was measured again with every workgroup of the bench
+                                                    // resident at once (68 VGPRs, 7 KB of LDS): k_dec_spec 20.3 us against 20.1, and
+                                                    // k_concat 10.3 against 7.0 -- twice the tiles to fold (profiles/decode_tiles_ab.txt)
 constexpr int DEC_PER_THREAD = DEC_ITEMS * DEC_GROUPS;
 constexpr int DEC_TILE = SCAN_BLOCK * DEC_PER_THREAD;
-constexpr int DEC_LDS_ROWS = 512;                   // LUT rows staged in LDS: 4 (max_len + 1) <= 512 (cur = -1 .. 2)
+constexpr int DEC_LDS_ROWS = 512;                   // LUT rows staged in LDS at most: 4 (max_len + 1) <= 512 (cur = -1 .. 2)
 inline size_t dec_num_tiles(size_t n) { return (n + DEC_TILE - 1) / DEC_TILE; }
+
+// The tables a decode kernel stages are DYNAMIC shared memory, sized to the stream: 4 nd rows (the two map tables of k_dec_spec one
+// more, the identity), and nothing for a decoder the stream does not run.  Bytes per row and decoder: k_dec_spec 16 (walk) + 8 (map),
+// k_dec_reduce 16 / 8 (the 16-state Miller map, the Manchester map), k_dec_apply 32 / 16 (the walks).  The host works the byte counts
+// out once per context (dec_table_bytes) and passes them at launch; the kernels lay the tables out in the same order.
+enum DecLdsUser { DEC_LDS_SPEC = 0, DEC_LDS_REDUCE = 1, DEC_LDS_APPLY = 2 };
+inline size_t dec_table_bytes(DecLdsUser k, const DecTables &T) {
+    const size_t rows = 4 * (size_t)T.nd, nr = T.reader ? 1 : 0, nt = T.tag ? 1 : 0;
+    if (rows > (size_t)DEC_LDS_ROWS) return 0;   // (the tables stay in global memory)
+    switch (k) {
+    case DEC_LDS_SPEC: return (nr + nt) * (rows * 16 + (rows + 1) * 8);
+    case DEC_LDS_REDUCE: return nr * rows * 16 + nt * rows * 8;
+    default: return nr * rows * 32 + nt * rows * 16;
+    }
+}
 
 // Edges arrive as 16-bit codes (edges.hip.h: edge_code): LUT row | route << 14.  A thread's sixteen, two per word.
 __device__ __forceinline__ void load_codes(const uint16_t *ecode, size_t base, size_t n, uint32_t (&c)[8]) {
@@ -164,7 +182,6 @@ __device__ __forceinline__ uint32_t pm_apply(uint32_t fl, uint32_t started) { re
 __device__ __forceinline__ uint32_t fa_bits(const FrameAgg &a, int t, uint32_t started) { return a.nb[t] - (started ? 0u : (a.fl[t] >> 2) & 1u); }
 __device__ __forceinline__ uint32_t fa_closes(const FrameAgg &a, int t, uint32_t started) { return a.nc[t] - (started ? 0u : (a.fl[t] >> 3) & 1u); }
 __device__ __forceinline__ uint32_t start_bit_of(int type) { return type == 0 ? 1u : 0u; }   // packets.py:24-28
-
 // PacketProcessor.append_bit per symbol (packets.py:67-79): an error symbol (> 1) closes a started packet and leaves the
 // state "not started"; a bit is appended unless it is the start-bit value arriving while not started (it starts the
 // packet and is dropped); the start-bit value leaves the state "started".
@@ -184,6 +201,9 @@ __device__ __forceinline__ uint32_t transpose_pairs(uint32_t m0, uint32_t m1, ui
 struct SlotMasks {
     uint32_t V[2], ST[2], SA[2];   // per type: slots that hold a symbol / an error symbol / a start-bit value
 };
+// (DECS: bit 0 the Miller / reader decoder runs, bit 1 the Manchester / tag decoder.  Out-bytes hold no symbol of a decoder that
+// does not run, so its masks are zero whatever the bytes say: a kernel that knows the set at compile time loses their instructions.)
+template <int DECS = 3>
 __device__ __forceinline__ SlotMasks slot_masks(const uint32_t (&ow)[4]) {
     constexpr uint32_t M = 0x01010101u;
     uint32_t V1[4], ST1[4], SA1[4], V0[4], ST0[4], SA0[4];
@@ -205,9 +225,18 @@ __device__ __forceinline__ SlotMasks slot_masks(const uint32_t (&ow)[4]) {
         ST0[i] = hi0 & v0;
         SA0[i] = o0 & v0;
     }
-    return SlotMasks{{transpose_pairs(V0[0], V0[1], V0[2], V0[3]), transpose_pairs(V1[0], V1[1], V1[2], V1[3])},
-                     {transpose_pairs(ST0[0], ST0[1], ST0[2], ST0[3]), transpose_pairs(ST1[0], ST1[1], ST1[2], ST1[3])},
-                     {transpose_pairs(SA0[0], SA0[1], SA0[2], SA0[3]), transpose_pairs(SA1[0], SA1[1], SA1[2], SA1[3])}};
+    SlotMasks m{{0u, 0u}, {0u, 0u}, {0u, 0u}};
+    if (DECS & 2) {
+        m.V[0] = transpose_pairs(V0[0], V0[1], V0[2], V0[3]);
+        m.ST[0] = transpose_pairs(ST0[0], ST0[1], ST0[2], ST0[3]);
+        m.SA[0] = transpose_pairs(SA0[0], SA0[1], SA0[2], SA0[3]);
+    }
+    if (DECS & 1) {
+        m.V[1] = transpose_pairs(V1[0], V1[1], V1[2], V1[3]);
+        m.ST[1] = transpose_pairs(ST1[0], ST1[1], ST1[2], ST1[3]);
+        m.SA[1] = transpose_pairs(SA1[0], SA1[1], SA1[2], SA1[3]);
+    }
+    return m;
 }
 // started / not started before every slot, entered in state `started`: the carry into the slot of (SA | keep) + SA + started,
 // keep = slots that are neither a start nor an error (a start generates a carry, an error kills it, the rest propagate)
@@ -215,8 +244,9 @@ __device__ __forceinline__ uint32_t started_before(const SlotMasks &m, int t, ui
     const uint32_t x = m.SA[t] | ~(m.ST[t] | m.SA[t]), y = m.SA[t];
     return (x + y + started) ^ x ^ y;
 }
+template <int DECS = 3>
 __device__ __forceinline__ FrameAgg frame_agg_of(const uint32_t (&ow)[4]) {
-    const SlotMasks m = slot_masks(ow);
+    const SlotMasks m = slot_masks<DECS>(ow);
     FrameAgg a;
 #pragma unroll
     for (int t = 0; t < 2; t++) {
@@ -290,8 +320,9 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_dec_reduce(const uint16_t *ecode
     if (n_dev) n = min(n, (size_t)*n_dev);
     if ((size_t)blockIdx.x * DEC_TILE >= n) return;
     TP_DECL();
-    __shared__ uint4 s_mil[LDS ? DEC_LDS_ROWS : 1];
-    __shared__ uint2 s_man[LDS ? DEC_LDS_ROWS : 1];
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_dec_tab[];   // dec_table_bytes(DEC_LDS_REDUCE)
+    uint4 *const s_mil = (uint4 *)s_dec_tab;
+    uint2 *const s_man = (uint2 *)(s_mil + (LDS && T.reader ? 4 * T.nd : 0));
     __shared__ DecMaps lds[SCAN_WAVES];
     if (LDS) {
         const int rows = 4 * T.nd;
@@ -344,8 +375,9 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_dec_apply(const uint16_t *ecode,
     if (own_prefix && n == 0 && blockIdx.x == 0 && threadIdx.x == 0) *total_out = ComposeDec::identity();
     if ((size_t)blockIdx.x * DEC_TILE >= n) return;
     TP_DECL();
-    __shared__ __attribute__((aligned(16))) uint16_t s_mil[LDS ? DEC_LDS_ROWS * 16 : 8];
-    __shared__ __attribute__((aligned(16))) uint16_t s_man[LDS ? DEC_LDS_ROWS * 8 : 8];
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_dec_tab[];   // dec_table_bytes(DEC_LDS_APPLY)
+    uint16_t *const s_mil = (uint16_t *)s_dec_tab;
+    uint16_t *const s_man = s_mil + (LDS && T.reader ? 4 * T.nd * 16 : 0);
     __shared__ DecMaps lds[SCAN_WAVES];
     __shared__ FramePk lds2[SCAN_WAVES];
     // own_prefix: `partials` still holds the tiles' maps (scan.hip.h: tile_prefix; first, while few registers are live)
@@ -425,7 +457,7 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_dec_apply(const uint16_t *ecode,
 // FA_DB / FA_DC.  k_concat knows the state every tile is really entered in (the scan of the tiles' FrameAgg) and moves the bits to
 // their place in the stream.
 constexpr int FW_WORDS = DEC_TILE * 2 / 32 + 4;   // bit words of a tile: two symbols per edge at most (+ the tile's phase in the stream, k_frame_write)
-constexpr uint32_t ST_CLOSES = 1024;              // packet ends staged per tile and type (125 on the bench captures); a tile with more fails the check
+constexpr uint32_t ST_CLOSES = 512 * DEC_GROUPS;  // packet ends staged per tile and type (125 on the bench captures); a tile with more fails the check
 struct TileStage {
     uint32_t *bits[2];        // [tile][FW_WORDS], NULL: packet type not decoded
     uint32_t *close_bit[2];   // [tile][ST_CLOSES]: bits of the tile appended before the packet end
@@ -484,17 +516,19 @@ constexpr int DEC_RUNIN_MAX = 8;   // run-in edges per thread at most (runin = 2
 // must lie inside the tile before: both break silently with more groups per thread)
 static_assert(DEC_GROUPS >= 1 && DEC_GROUPS <= 2, "NFC_DEC_GROUPS: a thread's packed bits are accumulated in 64 bits (32 slots per group)");
 static_assert(DEC_RUNIN_MAX * SCAN_BLOCK <= DEC_TILE, "the longest run-in fits inside the tile before");
-template <bool LDS>
+template <bool LDS, int DECS>
 __global__ __launch_bounds__(SCAN_BLOCK) void k_dec_spec(const uint16_t *ecode, size_t n, const uint32_t *n_dev, DecTables T, uint32_t state0, int runin_per_thread,
                                                         uint8_t *outw, FrameAgg *frame_aggs, DecSpec *spec, ZeroJob Z, TileStage S) {
+    constexpr bool RD = (DECS & 1) != 0, TG = (DECS & 2) != 0;   // the decoders of the stream (the host picks the instance by T.reader, T.tag: dec_spec_kernel)
     zero_words(Z);
     if (n_dev) n = min(n, (size_t)*n_dev);
     if ((size_t)blockIdx.x * DEC_TILE >= n) return;
     TP_DECL();
-    __shared__ uint2 s_milmap[LDS ? DEC_LDS_ROWS + 1 : 1];
-    __shared__ uint2 s_manmap[LDS ? DEC_LDS_ROWS + 1 : 1];
-    __shared__ __attribute__((aligned(16))) uint16_t s_mil[LDS ? DEC_LDS_ROWS * 8 : 8];
-    __shared__ __attribute__((aligned(16))) uint16_t s_man[LDS ? DEC_LDS_ROWS * 8 : 8];
+    // the stream's tables (dec_table_bytes(DEC_LDS_SPEC)): the walks first (16-byte rows), then the maps with their identity rows
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_dec_tab[];
+    const int trows = LDS ? 4 * T.nd : 0;
+    uint16_t *const s_mil = (uint16_t *)s_dec_tab, *const s_man = s_mil + (RD ? trows * 8 : 0);
+    uint2 *const s_milmap = (uint2 *)(s_man + (TG ? trows * 8 : 0)), *const s_manmap = s_milmap + (LDS && RD ? trows + 1 : 0);
     __shared__ QMaps lds[SCAN_WAVES];
     __shared__ FramePk lds2[SCAN_WAVES];
     __shared__ uint32_t s_needs;
@@ -506,12 +540,12 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_dec_spec(const uint16_t *ecode, 
     if (LDS) {
         const int rows = 4 * T.nd;
         for (int i = threadIdx.x; i <= rows; i += SCAN_BLOCK) {
-            if (T.reader) s_milmap[i] = T.qmil_map[i];
-            if (T.tag) s_manmap[i] = T.man_map[i];
+            if (RD) s_milmap[i] = T.qmil_map[i];
+            if (TG) s_manmap[i] = T.man_map[i];
         }
         for (int i = threadIdx.x; i < rows; i += SCAN_BLOCK) {
-            if (T.reader) ((uint4 *)s_mil)[i] = ((const uint4 *)T.qmil_step)[i];
-            if (T.tag) ((uint4 *)s_man)[i] = ((const uint4 *)T.man_step)[i];
+            if (RD) ((uint4 *)s_mil)[i] = ((const uint4 *)T.qmil_step)[i];
+            if (TG) ((uint4 *)s_man)[i] = ((const uint4 *)T.man_step)[i];
         }
     }
     if (threadIdx.x == 0) s_needs = 0u;
@@ -550,8 +584,8 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_dec_spec(const uint16_t *ecode, 
     };
     auto compose4 = [&](uint2 &am, uint2 &an, uint32_t w0, uint32_t w1) __attribute__((always_inline)) {   // four edges (two words of codes)
         const uint32_t c0 = w0 & 0xFFFFu, c1 = w0 >> 16, c2 = w1 & 0xFFFFu, c3 = w1 >> 16;
-        if (T.reader) am = then(am, then(then(mil_row(c0), mil_row(c1)), then(mil_row(c2), mil_row(c3))));
-        if (T.tag) an = then(an, then(then(man_row(c0), man_row(c1)), then(man_row(c2), man_row(c3))));
+        if (RD) am = then(am, then(then(mil_row(c0), mil_row(c1)), then(mil_row(c2), mil_row(c3))));
+        if (TG) an = then(an, then(then(man_row(c0), man_row(c1)), then(man_row(c2), man_row(c3))));
     };
     const QMaps idm = ComposeQ::identity();
     QMaps runin = idm;
@@ -587,8 +621,8 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_dec_spec(const uint16_t *ecode, 
             seen |= routes_of(c[g][k]) | routes_of(c[g][k + 1]);
         }
     }
-    if (!T.reader) seen &= ~1u;
-    if (!T.tag) seen &= ~2u;
+    if (!RD) seen &= ~1u;
+    if (!TG) seen &= ~2u;
     const QMaps agg{{am.x, am.y}, {an.x, an.y}};
     TP_MARK();   // 2: the compositions
     QMaps total;
@@ -597,8 +631,8 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_dec_spec(const uint16_t *ecode, 
     const QMaps upto = ComposeQ::op(runin, excl);
     const uint32_t dep = ((seen & 1u) && !map8_constant(upto.mil) ? 1u : 0u) | ((seen & 2u) && !map8_constant(upto.man) ? 2u : 0u);
     if (blockIdx.x > 0 && dep) atomicOr(&s_needs, dep);   // (rare; tile 0 starts from the carried state itself)
-    // The walk: one table look-up per edge from the state before it -- a chain of dependent LDS reads.  A thread's 32 edges are
-    // FOUR chains of eight, each started from the state the maps composed above give it, and walked side by side.
+    // The walk: one table look-up per edge from the state before it -- a chain of dependent LDS reads.  A thread's edges are
+    // chains of eight (two per group of 16), each started from the state the maps composed above give it, and walked side by side.
     uint32_t st[NCH];
 #pragma unroll
     for (int j = 0; j < NCH; j++) st[j] = ComposeQ::step(ComposeQ::op(upto, QMaps{{pm[j].x, pm[j].y}, {pn[j].x, pn[j].y}}), state0);
@@ -616,11 +650,11 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_dec_spec(const uint16_t *ecode, 
             const uint32_t code = (c[g][k >> 1] >> (16 * (k & 1))) & 0xFFFFu;
             const uint32_t li = code & 0x3FFFu, route = code >> 14;
             uint32_t w = 0;
-            if (route == 2u && T.reader) {
+            if (route == 2u && RD) {
                 const uint32_t en = mil[li * 8u + (st[j] & 7u)];
                 w = en >> 8;
                 st[j] = (st[j] & ~15u) | (en & 15u);
-            } else if (route == 1u && T.tag) {
+            } else if (route == 1u && TG) {
                 const uint32_t en = man[li * 8u + ((st[j] >> 4) & 7u)];
                 const uint32_t m = en >> 8;
                 w = (m & 3u) ? ((m & 0xFCu) | 3u) : 0u;
@@ -634,7 +668,7 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_dec_spec(const uint16_t *ecode, 
     for (int g = 0; g < DEC_GROUPS; g++) {
         const size_t gb = base + (size_t)DEC_ITEMS * g;
         if (gb < n) *(uint4 *)(outw + gb) = make_uint4(ow[g][0], ow[g][1], ow[g][2], ow[g][3]);   // outw has 16 bytes of slack
-        mine = FramePkOp::op(mine, FramePkOp::pack(frame_agg_of(ow[g])));
+        mine = FramePkOp::op(mine, FramePkOp::pack(frame_agg_of<DECS>(ow[g])));
     }
     TP_MARK();   // 4: the walk
     FramePk total_fa;
@@ -649,11 +683,11 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_dec_spec(const uint16_t *ecode, 
 #pragma unroll
         for (int g = 0; g < DEC_GROUPS; g++) {
             if (ow[g][0] | ow[g][1] | ow[g][2] | ow[g][3]) {
-                const SlotMasks m = slot_masks(ow[g]);
+                const SlotMasks m = slot_masks<DECS>(ow[g]);
                 const uint32_t low = symbol_low_bits(ow[g]);
 #pragma unroll
                 for (int t = 0; t < 2; t++) {
-                    if (!m.V[t] || !S.bits[t]) continue;
+                    if (!(t ? RD : TG) || !m.V[t]) continue;
                     const uint32_t started = pm_apply(before.fl[t], 1u);
                     const uint32_t bef = started_before(m, t, started);
                     const uint32_t appended = m.V[t] & ~m.ST[t] & (bef | ~m.SA[t]);
@@ -683,7 +717,7 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_dec_spec(const uint16_t *ecode, 
                         }
                     }
                 }
-                if (g + 1 < DEC_GROUPS) before = FrameAggOp::op(before, frame_agg_of(ow[g]));
+                if (g + 1 < DEC_GROUPS) before = FrameAggOp::op(before, frame_agg_of<DECS>(ow[g]));
             }
         }
 #pragma unroll
@@ -703,20 +737,29 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_dec_spec(const uint16_t *ecode, 
     const FrameAgg tile_fa = FramePkOp::unpack(total_fa);
 #pragma unroll
     for (int t = 0; t < 2; t++) {
-        if (!S.bits[t]) continue;
+        if (!(t ? RD : TG)) continue;
         const uint32_t nw = min((uint32_t)FW_WORDS, (tile_fa.nb[t] + 31u) / 32u + 1u);   // (one word more: k_concat reads pairs)
         for (uint32_t j = threadIdx.x; j < nw; j += SCAN_BLOCK) S.bits[t][(size_t)blockIdx.x * FW_WORDS + j] = s_bits[t][j];
     }
     if (threadIdx.x == 0) {
         frame_aggs[blockIdx.x] = tile_fa;
         S.own[blockIdx.x] = tile_fa;
-        if (S.bits[0]) S.drop_bit[0][blockIdx.x] = s_drop[0];
-        if (S.bits[1]) S.drop_bit[1][blockIdx.x] = s_drop[1];
+        if (TG) S.drop_bit[0][blockIdx.x] = s_drop[0];
+        if (RD) S.drop_bit[1][blockIdx.x] = s_drop[1];
         const uint32_t s_in = ComposeQ::step(runin, state0);
         ((uint4 *)(spec + blockIdx.x))[0] = make_uint4(total.mil[0], total.mil[1], total.man[0], total.man[1]);
         ((uint4 *)(spec + blockIdx.x))[1] = make_uint4(s_in, s_needs, 0u, 0u);
     }
     TP_DONE(1);   // 5: block scan
+}
+
+// k_dec_spec by table form and decoder set (bit 0 reader, bit 1 tag): a stream that runs one decoder takes the instance that holds
+// no register and issues no instruction for the other
+using DecSpecKernel = void (*)(const uint16_t *, size_t, const uint32_t *, DecTables, uint32_t, int, uint8_t *, FrameAgg *, DecSpec *, ZeroJob, TileStage);
+inline DecSpecKernel dec_spec_kernel(bool lds, const DecTables &T) {
+    static const DecSpecKernel k[2][4] = {{k_dec_spec<false, 0>, k_dec_spec<false, 1>, k_dec_spec<false, 2>, k_dec_spec<false, 3>},
+                                          {k_dec_spec<true, 0>, k_dec_spec<true, 1>, k_dec_spec<true, 2>, k_dec_spec<true, 3>}};
+    return k[lds ? 1 : 0][(T.reader ? 1 : 0) | (T.tag ? 2 : 0)];
 }
 
 // The check of k_dec_spec's assumptions: ONE workgroup scans the tiles' maps from the carried state, compares the state every tile

@@ -69,6 +69,7 @@ struct nfc_ctx {
     // after a batch whose check failed the next batches take the three-launch form (spec_off_left counts them down)
     bool dec_spec = true, dec_spec_now = false;
     int dec_runin = 2, spec_off_left = 0, spec_fail_streak = 0;   // (streak: speculative attempts that failed in a row: the back-off doubles)
+    size_t dec_lds[3] = {0, 0, 0};   // dynamic LDS of k_dec_spec / k_dec_reduce / k_dec_apply: the stream's tables (decode.hip.h: dec_table_bytes), set with T
     // what the decode stage left for the readers: packet bits packed 32 to a word (the multi-launch stage) or a byte each (short
     // batches); symbol arrays not written yet (materialize_symbols: on the first nfc_read_symbols)
     bool bits_packed = false, sym_lazy = false, sym_own = false;

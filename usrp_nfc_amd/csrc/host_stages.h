@@ -202,24 +202,20 @@ int run_decode(nfc_ctx *c, bool force_classic = false) {
             S.drop_bit[t] = c->d_stage_q[t].as<uint32_t>();
         }
         if (tiles) {
-            if (lds_tables)
-                NFC_LAUNCH(k_dec_spec<true>, dim3((unsigned)tiles), dim3(SCAN_BLOCK), 0, c->st, ecode, (size_t)ce, ne_dev, c->T, spec_state_in, c->dec_runin, outw,
-                           fparts, c->d_spec.as<DecSpec>(), Z, S);
-            else
-                NFC_LAUNCH(k_dec_spec<false>, dim3((unsigned)tiles), dim3(SCAN_BLOCK), 0, c->st, ecode, (size_t)ce, ne_dev, c->T, spec_state_in, c->dec_runin, outw,
-                           fparts, c->d_spec.as<DecSpec>(), Z, S);
+            NFC_LAUNCH(dec_spec_kernel(lds_tables, c->T), dim3((unsigned)tiles), dim3(SCAN_BLOCK), c->dec_lds[DEC_LDS_SPEC], c->st, ecode, (size_t)ce, ne_dev, c->T,
+                       spec_state_in, c->dec_runin, outw, fparts, c->d_spec.as<DecSpec>(), Z, S);
         }
     } else {
         if (tiles) {
             if (lds_tables)
-                NFC_LAUNCH(k_dec_reduce<true>, dim3((unsigned)tiles), dim3(SCAN_BLOCK), 0, c->st, ecode, (size_t)ce, ne_dev, c->T, dparts, daggs, Z);
+                NFC_LAUNCH(k_dec_reduce<true>, dim3((unsigned)tiles), dim3(SCAN_BLOCK), c->dec_lds[DEC_LDS_REDUCE], c->st, ecode, (size_t)ce, ne_dev, c->T, dparts, daggs, Z);
             else
                 NFC_LAUNCH(k_dec_reduce<false>, dim3((unsigned)tiles), dim3(SCAN_BLOCK), 0, c->st, ecode, (size_t)ce, ne_dev, c->T, dparts, daggs, Z);
         }
         if (!own) scan_partials<ComposeDec>(c->st, tiles, ne_dev, DEC_TILE, dparts, ComposeDec::identity_host(), map_total);
         if (tiles) {
             if (lds_tables)
-                NFC_LAUNCH(k_dec_apply<true>, dim3((unsigned)tiles), dim3(SCAN_BLOCK), 0, c->st, ecode, (size_t)ce, ne_dev, c->T, dparts, daggs,
+                NFC_LAUNCH(k_dec_apply<true>, dim3((unsigned)tiles), dim3(SCAN_BLOCK), c->dec_lds[DEC_LDS_APPLY], c->st, ecode, (size_t)ce, ne_dev, c->T, dparts, daggs,
                                    dec_state_in, outw, fparts, c->d_faggs.as<FramePk>(), own, map_total);
             else
                 NFC_LAUNCH(k_dec_apply<false>, dim3((unsigned)tiles), dim3(SCAN_BLOCK), 0, c->st, ecode, (size_t)ce, ne_dev, c->T, dparts, daggs,

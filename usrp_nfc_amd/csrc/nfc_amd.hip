@@ -426,6 +426,7 @@ int nfc_create(const nfc_params *p, nfc_ctx **out) {
     c->T.nd = c->mx + 1;
     c->T.reader = p->enable_reader ? 1 : 0;
     c->T.tag = p->enable_tag ? 1 : 0;
+    for (int k = 0; k < 3; k++) c->dec_lds[k] = dec_table_bytes((DecLdsUser)k, c->T);   // what the decode kernels stage of these tables
     // carried state
     CRT(c->d_state.ensure(sizeof(DevState)));
     // (mapped AND coherent, explicitly: the host watches the stamp word while the stream runs -- host_threshold.h: wait_for_stamp)
@@ -1588,4 +1589,29 @@ extern "C" int nfc_debug_gen_prof(unsigned long long *out, int reset) {
 // the frame assembly's two launches of the last batch by HIP events (nfc_set_timing >= 1 before the frames were first read; else 0):
 // what tests/frames_bench.py sets beside the batch's own time
 extern "C" float nfc_debug_frames_ms(const nfc_ctx *c) { return c && c->frames_ready ? c->fr_ms : -1.f; }
+// the decode kernels' dynamic LDS as this context launches them (which: 0 k_dec_spec, 1 k_dec_reduce, 2 k_dec_apply), and the
+// workgroups per CU the occupancy query gives the kernel with it
+extern "C" int nfc_debug_dec_lds(const nfc_ctx *c, int which, uint32_t *dyn_bytes, int *wgs_per_cu) {
+    if (!c || which < 0 || which > 2 || !dyn_bytes || !wgs_per_cu) return NFC_ERR_ARG;
+    const bool lds = 4 * c->T.nd <= nfc::DEC_LDS_ROWS;
+    const void *k = which == 0   ? (const void *)nfc::dec_spec_kernel(lds, c->T)
+                    : which == 1 ? (lds ? (const void *)nfc::k_dec_reduce<true> : (const void *)nfc::k_dec_reduce<false>)
+                                 : (lds ? (const void *)nfc::k_dec_apply<true> : (const void *)nfc::k_dec_apply<false>);
+    *dyn_bytes = (uint32_t)c->dec_lds[which];
+    if (hipSetDevice(c->P.device) != hipSuccess) return NFC_ERR_DEVICE;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(wgs_per_cu, k, nfc::SCAN_BLOCK, c->dec_lds[which]) == hipSuccess ? NFC_OK : NFC_ERR_DEVICE;
+}
+// the decode stage's shapes: edges per tile, the tile count up to which a tile's workgroup folds its predecessors itself (this
+// context's), packet ends staged per tile, LUT rows staged in LDS at most, the longest run-in in edges; and whether the last batch's
+// tiles folded their predecessors themselves (1) or the single-workgroup prefix launch ran (0)
+extern "C" int nfc_debug_dec_shapes(const nfc_ctx *c, uint32_t *out6) {
+    if (!c || !out6) return NFC_ERR_ARG;
+    out6[0] = (uint32_t)nfc::DEC_TILE;
+    out6[1] = c->own_prefix_max;
+    out6[2] = nfc::ST_CLOSES;
+    out6[3] = (uint32_t)nfc::DEC_LDS_ROWS;
+    out6[4] = (uint32_t)(nfc::DEC_RUNIN_MAX * nfc::SCAN_BLOCK);
+    out6[5] = c->sym_own ? 1u : 0u;
+    return NFC_OK;
+}
 #endif
