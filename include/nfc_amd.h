@@ -45,6 +45,9 @@ extern "C" {
  *  nfc_recover_keys_device) */
 /* (still 4, only new names: nfc_nested_trace, nfc_nested_result, nfc_nested_config, nfc_find_nested_auths, nfc_host_nested_candidates,
  *  nfc_nested_candidates_device, nfc_host_recover_nested_keys, nfc_recover_nested_keys_device) */
+/* (still 4, only new names: nfc_fsm_key_table, NFC_KEY_SECTORS, nfc_sector_of_block, nfc_fsm_key_table_init, nfc_fsm_set_sector_key,
+ *  nfc_fsm_get_key_table, nfc_fsm_set_key_table, nfc_host_commands_keyed, nfc_multi_set_sector_keys, nfc_multi_get_sector_keys;
+ *  nfc_fsm_state.cur_key also takes 2 + slot of such a table, its layout unchanged) */
 #define NFC_AMD_ABI_VERSION 4
 
 typedef enum {
@@ -581,7 +584,7 @@ typedef struct nfc_fsm_state {      /* 88 bytes */
     int32_t cur_cmd;                /* the command in flight (index for nfc_command_info) */
     int32_t tag_type;               /* -1 none, 0 Ultralight, 1 Classic 1K, 2 Classic 4K, 3 DESFire */
     int32_t encrypted;              /* a CRYPTO1 session is up */
-    int32_t cur_key;                /* 0: key A, 1: key B */
+    int32_t cur_key;                /* 0: key A, 1: key B, 2 + slot: that slot of the sector key table (below) */
     uint64_t cipher;                /* the 48-bit register; bit i is the i-th oldest bit */
     uint8_t ar[4], at[4];           /* the expected reader / tag answers */
     uint8_t key_a[6], key_b[6];
@@ -641,6 +644,47 @@ int nfc_multi_fetch_commands(nfc_multi *m, nfc_multi_commands *out);
 int nfc_multi_set_keys(nfc_multi *m, int64_t stream /* -1: every stream */, const uint8_t key_a[6], const uint8_t key_b[6]);
 int nfc_multi_get_fsm_state(nfc_multi *m, uint32_t stream, nfc_fsm_state *st);
 int nfc_multi_set_fsm_state(nfc_multi *m, uint32_t stream, const nfc_fsm_state *st);
+
+/* ---- a key per sector: the key table of the protocol machines ----------------------------------------------------------------------
+ * A MIFARE Classic card has one key A and one key B PER SECTOR, 40 sectors at most: blocks 0 .. 127 lie four to a sector, blocks
+ * 128 .. 255 sixteen (nfc_sector_of_block).  Beside its two keys every machine -- the host machine, nfc_host_commands_keyed, every
+ * stream of a multi-stream context -- can hold a TABLE of 80 slots, slot = (key_type & 1) * 40 + sector, each empty or six key bytes.
+ * When a machine recognises AUTHA / AUTHB it takes the block from the command's plaintext byte 1 (already decrypted under the running
+ * session for a nested one) and chooses: the table's slot when it is present, else key A / key B exactly as without a table.  The
+ * choice is nfc_fsm_state.cur_key (0 / 1: the machine's key A / B; 2 + slot: the table's slot), so it survives until the nonce frame
+ * that loads the register, in a later call or push if need be; a slot emptied in between falls back to the key A / B of its type.
+ * nfc_fsm_process_outgoing chooses the same way at an outgoing AUTHA / AUTHB (with no slot present it leaves cur_key to its caller, as
+ * before).  AN EMPTY TABLE IS THE BEHAVIOUR WITHOUT ONE, bit for bit, state included.  The table is no part of nfc_fsm_state:
+ * nfc_fsm_get_state / _set_state and nfc_multi_get_fsm_state / _set_fsm_state / nfc_multi_set_state leave it alone; nfc_fsm_reset and
+ * nfc_multi_reset(stream) empty it (that stream's); nfc_fsm_set_keys / nfc_multi_set_keys do not touch it.
+ * A `present` other than 0 or 1, a sector >= 40, a key_type other than 0x60 / 0x61 are NFC_ERR_ARG (nfc_multi_*: raised before the
+ * device is touched, the argument's name in the message).
+ * nfc_multi_set_sector_keys broadcasts ONE table to stream `stream` or to every stream; nfc_multi_get_sector_keys reads one stream's;
+ * both complete the device first.  The device holds the tables in a buffer of 640 bytes per stream (40 MiB at 65 536 streams) that is
+ * allocated, zeroed, by a context's FIRST nfc_multi_set_sector_keys: a context that never sets a sector key allocates nothing for it,
+ * launches what it always did, and its nfc_multi_get_sector_keys gives an empty table.  No device memory: NFC_ERR_NOMEM, the context
+ * as it was.
+ * nfc_host_commands_keyed: nfc_host_commands with a table (NULL: an empty one -- then it IS nfc_host_commands); the CPU twin of
+ * k_multi_commands for this path.
+ * COST, measured with K copies of a 26-frame card of three keys in four authentications (41 164 samples; README.md,
+ * profiles/sector_keys_bench.json): the machine kernel 0.275 ms with the two keys alone and 0.327 ms with a table per stream at 1 024
+ * streams, 0.284 / 0.336 ms at 16 384 -- mostly the two sectors more that the lanes then decrypt; a push of 16.8 / 18.1 ms grows by
+ * 0.05 - 0.07 ms.  With no table set the machine kernel is 1.3 % slower than it was before the table existed. */
+#define NFC_KEY_SECTORS 40
+typedef struct nfc_fsm_key_table {  /* 560 bytes */
+    uint8_t key[2][NFC_KEY_SECTORS][6];     /* [key_type & 1][sector] */
+    uint8_t present[2][NFC_KEY_SECTORS];    /* 0: empty, 1: key[..] holds the slot's key */
+} nfc_fsm_key_table;
+int nfc_sector_of_block(int block);         /* 0 .. 39 for block 0 .. 255; -1 outside */
+int nfc_fsm_key_table_init(nfc_fsm_key_table *t);   /* every slot empty, every byte 0 */
+int nfc_fsm_set_sector_key(nfc_fsm *f, int key_type /* 0x60, 0x61 */, int sector, const uint8_t key[6] /* NULL: clear the slot */);
+int nfc_fsm_get_key_table(const nfc_fsm *f, nfc_fsm_key_table *t);
+int nfc_fsm_set_key_table(nfc_fsm *f, const nfc_fsm_key_table *t);
+int nfc_host_commands_keyed(nfc_fsm_state *st, const nfc_fsm_key_table *table, const nfc_raw_frame *merged, size_t n, const uint8_t *bytes0,
+                            const uint8_t *par0, const uint8_t *bytes1, const uint8_t *par1, nfc_frame *out, uint8_t *data, uint16_t *enc,
+                            size_t cap, size_t *used);
+int nfc_multi_set_sector_keys(nfc_multi *m, int64_t stream /* -1: every stream */, const nfc_fsm_key_table *table);
+int nfc_multi_get_sector_keys(nfc_multi *m, uint32_t stream, nfc_fsm_key_table *table);
 
 /* ---- key recovery: a MIFARE Classic sector key from one sniffed first authentication --------------------------------------------------
  * An eavesdropper who has no keys still sees everything the recovery needs: the UID (SEL1R), the tag nonce nt in the clear (RANDTA),

@@ -72,6 +72,13 @@ class FsmState(C.Structure):   # nfc_fsm_state
                 ('uid', C.c_uint8 * 32), ('flags', C.c_uint32), ('reserved', C.c_uint32)]
 
 
+NFC_KEY_SECTORS = 40
+
+
+class FsmKeyTable(C.Structure):   # nfc_fsm_key_table: key[key_type & 1][sector][6], present[key_type & 1][sector]
+    _fields_ = [('key', C.c_uint8 * 6 * NFC_KEY_SECTORS * 2), ('present', C.c_uint8 * NFC_KEY_SECTORS * 2)]
+
+
 class MultiCommands(C.Structure):   # nfc_multi_commands
     _fields_ = [('raw', MultiFrames), ('cmd_off', C.c_void_p), ('cbyte_off', C.c_void_p), ('cmd', C.c_void_p), ('src', C.c_void_p),
                 ('data', C.c_void_p), ('enc', C.c_void_p), ('stream_flags', C.c_void_p), ('n_streams', C.c_uint32), ('n_launches', C.c_uint32),
@@ -125,6 +132,7 @@ FSM_STATE_DTYPE = np.dtype([('cur_cmd', '<i4'), ('tag_type', '<i4'), ('encrypted
                             ('at', 'u1', (4,)), ('key_a', 'u1', (6,)), ('key_b', 'u1', (6,)), ('uid_len', '<u4'), ('uid', 'u1', (32,)), ('flags', '<u4'),
                             ('reserved', '<u4')])
 NFC_FSM_LOST, NFC_FSM_UID_OVERFLOW = 1, 2
+KEY_TABLE_DTYPE = np.dtype([('key', 'u1', (2, NFC_KEY_SECTORS, 6)), ('present', 'u1', (2, NFC_KEY_SECTORS))])   # nfc_fsm_key_table as a record
 NFC_CMD_CUT = -3
 # nfc_auth_trace: one sniffed first authentication (words: byte 0 lowest), and nfc_key_result with its statuses
 AUTH_DTYPE = np.dtype([('uid', '<u4'), ('nt', '<u4'), ('nr_enc', '<u4'), ('ar_enc', '<u4'), ('at_enc', '<u4'), ('par', '<u2'), ('key_type', 'u1'),
@@ -157,6 +165,8 @@ SYMBOLS = ['nfc_abi_version', 'nfc_device_count', 'nfc_create', 'nfc_destroy', '
            'nfc_get_frame_counts', 'nfc_read_frames', 'nfc_read_frame_bytes', 'nfc_host_frames', 'nfc_fsm_process_frames', 'nfc_multi_fetch_frames',
            'nfc_fsm_state_init', 'nfc_fsm_get_state', 'nfc_fsm_set_state', 'nfc_host_commands', 'nfc_multi_track_commands', 'nfc_multi_fetch_commands',
            'nfc_multi_set_keys', 'nfc_multi_get_fsm_state', 'nfc_multi_set_fsm_state',
+           'nfc_sector_of_block', 'nfc_fsm_key_table_init', 'nfc_fsm_set_sector_key', 'nfc_fsm_get_key_table', 'nfc_fsm_set_key_table',
+           'nfc_host_commands_keyed', 'nfc_multi_set_sector_keys', 'nfc_multi_get_sector_keys',
            'nfc_find_auths', 'nfc_host_recover_keys', 'nfc_recover_keys_device',
            'nfc_find_nested_auths', 'nfc_host_nested_candidates', 'nfc_nested_candidates_device', 'nfc_host_recover_nested_keys',
            'nfc_recover_nested_keys_device']
@@ -284,6 +294,14 @@ def load(path=None):
     L.nfc_multi_set_keys.argtypes = [vp, C.c_int64, vp, vp]
     L.nfc_multi_get_fsm_state.argtypes = [vp, u32, C.POINTER(FsmState)]
     L.nfc_multi_set_fsm_state.argtypes = [vp, u32, C.POINTER(FsmState)]
+    L.nfc_sector_of_block.argtypes = [C.c_int]
+    L.nfc_fsm_key_table_init.argtypes = [C.POINTER(FsmKeyTable)]
+    L.nfc_fsm_set_sector_key.argtypes = [vp, C.c_int, C.c_int, vp]
+    L.nfc_fsm_get_key_table.argtypes = [vp, C.POINTER(FsmKeyTable)]
+    L.nfc_fsm_set_key_table.argtypes = [vp, C.POINTER(FsmKeyTable)]
+    L.nfc_host_commands_keyed.argtypes = [C.POINTER(FsmState), C.POINTER(FsmKeyTable), vp, sz, vp, vp, vp, vp, vp, vp, vp, sz, psz]
+    L.nfc_multi_set_sector_keys.argtypes = [vp, C.c_int64, C.POINTER(FsmKeyTable)]
+    L.nfc_multi_get_sector_keys.argtypes = [vp, u32, C.POINTER(FsmKeyTable)]
     L.nfc_find_auths.argtypes = [vp, sz, vp, vp, vp, vp, vp, sz, psz]
     L.nfc_host_recover_keys.argtypes = [vp, sz, C.POINTER(KeyConfig), vp, C.POINTER(KeyStats)]
     L.nfc_recover_keys_device.argtypes = [C.c_int, vp, sz, C.POINTER(KeyConfig), vp, C.POINTER(KeyStats)]

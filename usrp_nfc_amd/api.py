@@ -422,6 +422,26 @@ class NfcMultiContext(object):
             raise NfcError('set_keys: key_a and key_b are six bytes each')
         self._chk(self.L.nfc_multi_set_keys(self.h, -1 if stream is None else int(stream), a.ctypes.data, b.ctypes.data), 'nfc_multi_set_keys')
 
+    def set_sector_keys(self, table, stream=None):
+        """The per-sector key table of one stream's machine (default: of every stream's), as fsm.set_sector_keys: a dict
+        (key_type, sector) -> six key bytes or an _lib.FsmKeyTable; None or {} empties it (nfc_multi_set_sector_keys).  The first call
+        allocates the tables' device buffer, 640 bytes per stream; reset(k) empties stream k's table."""
+        from . import keys
+        try:
+            t = keys.key_table(table)
+        except ValueError as e:
+            raise NfcError('set_sector_keys: %s' % e)
+        self._chk(self.L.nfc_multi_set_sector_keys(self.h, -1 if stream is None else int(stream), C.byref(t)), 'nfc_multi_set_sector_keys')
+
+    def sector_keys(self, k):
+        """Stream k's key table as the dict (key_type, sector) -> six key bytes of its present slots (nfc_multi_get_sector_keys)."""
+        from . import keys
+        if not 0 <= int(k) < self.n_streams:
+            raise NfcError('sector_keys: stream %d out of range (n_streams %d)' % (k, self.n_streams))
+        t = _lib.FsmKeyTable()
+        self._chk(self.L.nfc_multi_get_sector_keys(self.h, int(k), C.byref(t)), 'nfc_multi_get_sector_keys')
+        return keys.table_dict(t)
+
     def recover_keys(self, nested=False, **cfg):
         """The sector keys of the last push's first authentications: fetch_frames() + NfcMultiFrames.auths() + ONE keys.recover call on
         this context's device (cfg: keys.recover's).  -> per stream a dict (key_type, block) -> six key bytes (keys.keys_by_stream).

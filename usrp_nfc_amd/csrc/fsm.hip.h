@@ -17,6 +17,7 @@
 
 #include "../../include/nfc_amd.h"
 #include "frames.hip.h"
+#include "sector_keys.h"
 
 namespace nfc {
 namespace fsmd {
@@ -155,7 +156,7 @@ NFC_HD uint32_t nonce_advance(uint32_t x, int ticks) {
 
 // ---- the machine in scalars ----
 struct Machine {
-    int32_t cur_cmd, tag_type, encrypted, cur_key;
+    int32_t cur_cmd, tag_type, encrypted, cur_key;   // cur_key: 0 / 1 key A / B, 2 + slot of the sector key table (sector_keys.h)
     uint64_t st, key_a, key_b;   // 48 bits each; a key's byte 0 lowest: load_key's bit order makes the key the register
     uint32_t ar, at;             // byte 0 lowest
     uint32_t uid_len, flags;
@@ -301,8 +302,10 @@ NFC_HD void uid_append(Machine &M, const Bytes &B, uint32_t from, uint32_t n) {
 // how many UID bytes Crypto1::set_tag takes: its bit buffer holds 64 entries and a byte must fit whole, with or without a parity place
 NFC_HD uint32_t set_tag_bytes(const Machine &M) { return M.uid_len < 7u ? M.uid_len : 7u; }
 
-// protocol.h: fsm_finish.  nb plaintext bytes (0: a parity error, or nothing left), the first 20 of them in B.
-NFC_HD void finish(Machine &M, uint32_t nb, int type, Rec &out, const Bytes &B, bool crc_ok) {
+// protocol.h: fsm_finish.  nb plaintext bytes (0: a parity error, or nothing left), the first 20 of them in B.  tab: the stream's sector
+// key table (sector_keys.h), read only where an AUTH command is recognised and where a nonce loads the register.
+template <class Table>
+NFC_HD void finish(Machine &M, uint32_t nb, int type, Rec &out, const Bytes &B, bool crc_ok, const Table &tab) {
     if (nb == 0) {
         out.cmd = NFC_CMD_PARITY_ERROR;
         return;
@@ -356,11 +359,11 @@ NFC_HD void finish(Machine &M, uint32_t nb, int type, Rec &out, const Bytes &B, 
         }
         break;
     }
-    case C_AUTHA: M.cur_key = 0; break;
-    case C_AUTHB: M.cur_key = 1; break;
+    case C_AUTHA: M.cur_key = skeys::choose(tab, 0u, B.at(h)); break;
+    case C_AUTHB: M.cur_key = skeys::choose(tab, 1u, B.at(h)); break;
     case C_RANDTA:
         if (!M.encrypted) {   // first authentication: the tag nonce came in the clear; uid ^ nonce goes into a fresh register
-            M.st = M.cur_key ? M.key_b : M.key_a;
+            M.st = skeys::resolve(tab, M.cur_key, M.key_a, M.key_b);
             M.ar = M.at = 0;
             const uint32_t nonce = B.word_at(h), nu = set_tag_bytes(M);
             if (nu >= 1u && nu <= 4u) {   // (set_tag: nothing at all with no UID or with more UID bits than the nonce has)
@@ -384,8 +387,9 @@ NFC_HD void finish(Machine &M, uint32_t nb, int type, Rec &out, const Bytes &B, 
 
 // One frame (protocol.h: fsm_process_frame): raw_flags / n its nfc_raw_frame's flags and n_bytes, bytes / par its data bytes and ninth
 // bits as received.  data / enc: the frame's slot, n entries each, ALL written: the plaintext bytes and the enc entries first, 0 behind.
+template <class Table>
 NFC_HD Rec process_frame(Machine &M, int type, uint32_t raw_flags, uint32_t n, const uint8_t *__restrict__ bytes, const uint8_t *__restrict__ par,
-                         uint8_t *__restrict__ data, uint16_t *__restrict__ enc) {
+                         uint8_t *__restrict__ data, uint16_t *__restrict__ enc, const Table &tab) {
     Rec out = {NFC_CMD_UNKNOWN, type, 0u, 0u, 0u, 0u, 0u, 0u};
     if (raw_flags & NFC_RAW_CUT) {   // its bits are not there: the machine is not touched, the keystream of a session is out of step from here
         out.cmd = NFC_CMD_CUT;
@@ -414,7 +418,7 @@ NFC_HD Rec process_frame(Machine &M, int type, uint32_t raw_flags, uint32_t n, c
         const bool nested = !nr_ar && (M.cur_cmd == C_AUTHA || M.cur_cmd == C_AUTHB);
         uint32_t todo = n;   // bytes that are decrypted
         if (nested) {
-            M.st = M.cur_key ? M.key_b : M.key_a;
+            M.st = skeys::resolve(tab, M.cur_key, M.key_a, M.key_b);
             M.ar = M.at = 0;
             const uint32_t nu = set_tag_bytes(M);
             todo = (nu >= 1u && nu <= n) ? nu : 0u;   // (set_tag: nothing at all with no UID or a frame shorter than the UID)
@@ -458,7 +462,7 @@ NFC_HD Rec process_frame(Machine &M, int type, uint32_t raw_flags, uint32_t n, c
         if (nb == 0)
             for (uint32_t i = 0; i < n; i++) data[i] = 0;
     }
-    finish(M, nb, type, out, B, crc_ok);
+    finish(M, nb, type, out, B, crc_ok, tab);
     return out;
 }
 
@@ -494,7 +498,7 @@ inline const char *state_fault(const nfc_fsm_state &s) {
     if (s.cur_cmd < 0 || s.cur_cmd >= C_COUNT) return "cur_cmd out of range";
     if (s.tag_type < -1 || s.tag_type > 3) return "tag_type out of range";
     if (s.encrypted != 0 && s.encrypted != 1) return "encrypted must be 0 or 1";
-    if (s.cur_key != 0 && s.cur_key != 1) return "cur_key must be 0 or 1";
+    if (s.cur_key < 0 || s.cur_key > skeys::CUR_KEY_MAX) return "cur_key must be 0, 1 or 2 + a slot below 80";
     if (s.cipher >> 48) return "cipher holds more than 48 bits";
     if (s.uid_len > UID_CAP) return "uid_len exceeds 32";
     if (s.flags & ~(uint32_t)(NFC_FSM_LOST | NFC_FSM_UID_OVERFLOW)) return "unknown flags";
@@ -523,6 +527,7 @@ NFC_HD void load_machine(Machine &M, const uint32_t *__restrict__ s, size_t K, s
     M.u4 = s[(W_UID0 + 4) * K + k], M.u5 = s[(W_UID0 + 5) * K + k], M.u6 = s[(W_UID0 + 6) * K + k], M.u7 = s[(W_UID0 + 7) * K + k];
     // (a machine is only ever written by store_machine, launch_init and a checked nfc_fsm_state; still, nothing may index by these)
     if ((uint32_t)M.cur_cmd >= (uint32_t)C_COUNT) M.cur_cmd = C_REQA;
+    if ((uint32_t)M.cur_key > (uint32_t)skeys::CUR_KEY_MAX) M.cur_key = 0;
     if (M.uid_len > UID_CAP) M.uid_len = UID_CAP;
     M.st &= ST_MASK;
 }

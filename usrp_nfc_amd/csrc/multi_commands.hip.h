@@ -30,6 +30,7 @@ struct Args {
     frames::MultiArgs R;   // the frames' part: what launch_multi was given
     uint32_t *state;       // [fsmd::W_WORDS][K]
     Layout L;
+    const uint32_t *sector_keys;   // [skeys::SLOTS][2][K] (sector_keys.h), or null: no stream of the context was ever given a sector key
 };
 constexpr int THREADS = 64;
 
@@ -39,9 +40,14 @@ void launch_init(uint32_t *state, uint32_t K, uint32_t k0, uint32_t k1, hipStrea
 void launch_set_keys(uint32_t *state, uint32_t K, uint32_t k0, uint32_t k1, uint64_t key_a, uint64_t key_b, hipStream_t stream);
 // one stream's machine to (set == 0) or from blob[0 .. W_WORDS)
 void launch_io(uint32_t *state, uint32_t K, uint32_t k, int set, uint32_t *blob, hipStream_t stream);
+// the sector key tables, [skeys::SLOTS][2][K]: streams [k0, k1) all get the skeys::WORDS words of `blob` (null: emptied); one stream's
+// table to (set == 0) or from blob[0 .. skeys::WORDS).  Their only writers; k_multi_commands only reads them.
+void launch_set_table(uint32_t *tables, uint32_t K, uint32_t k0, uint32_t k1, const uint32_t *blob, hipStream_t stream);
+void launch_table_io(uint32_t *tables, uint32_t K, uint32_t k, int set, uint32_t *blob, hipStream_t stream);
 
 #ifdef NFC_COMMANDS_KERNELS
-__global__ __launch_bounds__(THREADS) void k_multi_commands(Args A) {
+// (three waves per SIMD, as before the sector key look-up: left alone the allocator takes 169 registers with it, one past the step)
+__global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(3))) void k_multi_commands(Args A) {
     const frames::MultiArgs &R = A.R;
     const Layout &L = A.L;
     uint8_t *__restrict__ buf = R.packed;
@@ -85,6 +91,7 @@ __global__ __launch_bounds__(THREADS) void k_multi_commands(Args A) {
     }
     fsmd::Machine M;
     fsmd::load_machine(M, A.state, K, k);
+    const skeys::DeviceTable keys = {A.sector_keys, K, k};   // (two words of it are read at an AUTH command and at the nonce that follows)
     {   // what the slabs did not store is lost to the machine
         const uint32_t *c = R.counts + (size_t)k * R.cnt_words;
         if (c[R.cnt_pk0] > R.cap_packets || c[R.cnt_pk0 + 1] > R.cap_packets || c[R.cnt_bits0] > R.cap_bits || c[R.cnt_bits0 + 1] > R.cap_bits)
@@ -111,7 +118,7 @@ __global__ __launch_bounds__(THREADS) void k_multi_commands(Args A) {
         // (never: a frame's bytes lie inside its type's section, its slot inside the host's room)
         if ((uint64_t)byte_off + n > roomt || b0 + run + n > L.total_bytes) flags = NFC_RAW_CUT;
         if (flags & NFC_RAW_CUT) n = 0;
-        const fsmd::Rec r = fsmd::process_frame(M, t, flags, n, rbt + byte_off, rpt + byte_off, out_data + b0 + run, out_enc + b0 + run);
+        const fsmd::Rec r = fsmd::process_frame(M, t, flags, n, rbt + byte_off, rpt + byte_off, out_data + b0 + run, out_enc + b0 + run, keys);
         uint32_t *w = out_cmd + c * (sizeof(nfc_frame) / 4);
         w[0] = (uint32_t)r.cmd;
         w[1] = (uint32_t)r.type;
@@ -150,6 +157,19 @@ __global__ __launch_bounds__(64) void k_commands_io(uint32_t *state, uint32_t K,
     if (w >= (uint32_t)fsmd::W_WORDS || k >= K) return;
     if (set) state[(size_t)w * K + k] = blob[w];
     else blob[w] = state[(size_t)w * K + k];
+}
+// a thread per (stream of [k0, k1) ∩ [0, K), word): neighbouring threads write neighbouring streams of one word
+__global__ __launch_bounds__(256) void k_commands_set_table(uint32_t *tables, uint32_t K, uint32_t k0, uint32_t k1, const uint32_t *blob) {
+    const size_t k = (size_t)k0 + blockIdx.x * 256 + threadIdx.x;
+    const uint32_t w = blockIdx.y;
+    if (k >= k1 || k >= K || w >= skeys::WORDS) return;
+    tables[(size_t)w * K + k] = blob ? blob[w] : 0u;
+}
+__global__ __launch_bounds__(256) void k_commands_table_io(uint32_t *tables, uint32_t K, uint32_t k, int set, uint32_t *blob) {
+    const uint32_t w = threadIdx.x;
+    if (w >= skeys::WORDS || k >= K) return;
+    if (set) tables[(size_t)w * K + k] = blob[w];
+    else blob[w] = tables[(size_t)w * K + k];
 }
 #endif   // NFC_COMMANDS_KERNELS
 

@@ -15,6 +15,7 @@
 
 static_assert(sizeof(nfc_fsm_state) == 88 && sizeof(nfc_fsm_state) % 8 == 0, "nfc_fsm_state is 88 bytes");
 static_assert(sizeof(nfc_frame) == 28, "nfc_frame is seven words");
+static_assert(sizeof(nfc_fsm_key_table) == 560, "nfc_fsm_key_table is 560 bytes");
 static_assert((int)nfc::fsmd::C_COUNT == (int)nfc::CMD_COUNT && (int)nfc::fsmd::C_COMPW2 == (int)nfc::CMD_COMPW2, "one command order");
 
 namespace nfc {
@@ -35,6 +36,14 @@ void launch_set_keys(uint32_t *state, uint32_t K, uint32_t k0, uint32_t k1, uint
 }
 void launch_io(uint32_t *state, uint32_t K, uint32_t k, int set, uint32_t *blob, hipStream_t stream) {
     NFC_LAUNCH(k_commands_io, dim3(1), dim3(64), 0, stream, state, K, k, set, blob);
+}
+void launch_set_table(uint32_t *tables, uint32_t K, uint32_t k0, uint32_t k1, const uint32_t *blob, hipStream_t stream) {
+    if (k1 <= k0) return;
+    NFC_LAUNCH(k_commands_set_table, dim3((k1 - k0 + 255) / 256, skeys::WORDS), dim3(256), 0, stream, tables, K, k0, k1, blob);
+}
+void launch_table_io(uint32_t *tables, uint32_t K, uint32_t k, int set, uint32_t *blob, hipStream_t stream) {
+    static_assert(skeys::WORDS <= 256, "one block copies a table");
+    NFC_LAUNCH(k_commands_table_io, dim3(1), dim3(256), 0, stream, tables, K, k, set, blob);
 }
 
 }  // namespace commands
@@ -82,7 +91,7 @@ int nfc_fsm_get_state(const nfc_fsm *f, nfc_fsm_state *st) {
     st->cur_cmd = f->cur_cmd;
     st->tag_type = f->tag_type;
     st->encrypted = f->encrypted;
-    st->cur_key = f->cur_key == f->key_b ? 1 : 0;
+    st->cur_key = f->cur_key;
     st->cipher = f->cipher.st;
     memcpy(st->ar, f->cipher.ar, 4);
     memcpy(st->at, f->cipher.at, 4);
@@ -103,17 +112,54 @@ int nfc_fsm_set_state(nfc_fsm *f, const nfc_fsm_state *st) {
     memcpy(f->cipher.at, st->at, 4);
     memcpy(f->key_a, st->key_a, 6);
     memcpy(f->key_b, st->key_b, 6);
-    f->cur_key = st->cur_key ? f->key_b : f->key_a;
+    f->cur_key = st->cur_key;
     f->uid.assign(st->uid, st->uid + st->uid_len);
+    return NFC_OK;
+}
+
+int nfc_sector_of_block(int block) { return block < 0 || block > 255 ? -1 : (int)nfc::skeys::sector_of((uint32_t)block); }
+
+int nfc_fsm_key_table_init(nfc_fsm_key_table *t) {
+    if (!t) return NFC_ERR_ARG;
+    memset(t, 0, sizeof *t);
+    return NFC_OK;
+}
+
+int nfc_fsm_set_sector_key(nfc_fsm *f, int key_type, int sector, const uint8_t key[6]) {
+    if (!f || (key_type != 0x60 && key_type != 0x61) || sector < 0 || sector >= (int)nfc::skeys::SECTORS) return NFC_ERR_ARG;
+    const int t = key_type & 1;
+    f->table.present[t][sector] = key ? 1 : 0;
+    if (key) memcpy(f->table.key[t][sector], key, 6);
+    else memset(f->table.key[t][sector], 0, 6);
+    return NFC_OK;
+}
+
+int nfc_fsm_get_key_table(const nfc_fsm *f, nfc_fsm_key_table *t) {
+    if (!f || !t) return NFC_ERR_ARG;
+    *t = f->table;
+    return NFC_OK;
+}
+
+int nfc_fsm_set_key_table(nfc_fsm *f, const nfc_fsm_key_table *t) {
+    if (!f || !t || nfc::skeys::table_fault(*t)) return NFC_ERR_ARG;
+    f->table = *t;
     return NFC_OK;
 }
 
 int nfc_host_commands(nfc_fsm_state *st, const nfc_raw_frame *merged, size_t n, const uint8_t *bytes0, const uint8_t *par0, const uint8_t *bytes1,
                       const uint8_t *par1, nfc_frame *out, uint8_t *data, uint16_t *enc, size_t cap, size_t *used) {
+    return nfc_host_commands_keyed(st, nullptr, merged, n, bytes0, par0, bytes1, par1, out, data, enc, cap, used);
+}
+
+int nfc_host_commands_keyed(nfc_fsm_state *st, const nfc_fsm_key_table *table, const nfc_raw_frame *merged, size_t n, const uint8_t *bytes0,
+                            const uint8_t *par0, const uint8_t *bytes1, const uint8_t *par1, nfc_frame *out, uint8_t *data, uint16_t *enc,
+                            size_t cap, size_t *used) {
     using namespace nfc;
     static const bool agree = tables_agree();
     if (!agree) return NFC_ERR_INTERNAL;
     if (!st || fsmd::state_fault(*st) || (n && (!merged || !out))) return NFC_ERR_ARG;
+    if (table && skeys::table_fault(*table)) return NFC_ERR_ARG;
+    const skeys::HostTable keys = {table};
     fsmd::Machine M;
     fsmd::machine_from_state(M, *st);
     size_t at = 0;
@@ -126,7 +172,7 @@ int nfc_host_commands(nfc_fsm_state *st, const nfc_raw_frame *merged, size_t n, 
         if (nb && (!b || !p || !data || !enc)) return NFC_ERR_ARG;
         if (at + nb > cap || at + nb > 0xFFFFFFFFull) return NFC_ERR_ARG;
         const fsmd::Rec rec = fsmd::process_frame(M, r.type, r.flags, (uint32_t)nb, b ? b + r.byte_off : nullptr, p ? p + r.byte_off : nullptr,
-                                                  data ? data + at : nullptr, enc ? enc + at : nullptr);
+                                                  data ? data + at : nullptr, enc ? enc + at : nullptr, keys);
         nfc_frame &o = out[i];
         memset(&o, 0, sizeof o);
         o.cmd = rec.cmd;

@@ -108,6 +108,10 @@ struct nfc_multi {
     bool track = false;
     Owned<DevBuf> d_fsm, d_fsm_blob;
     Owned<PinBuf> h_fsm_blob;
+    // the sector key tables (sector_keys.h), [skeys::SLOTS][2][K] words, and one table's blob: there from the first
+    // nfc_multi_set_sector_keys on, never before -- a null d_keys is "every table empty" to the kernel and to the calls
+    Owned<DevBuf> d_keys, d_keys_blob;
+    Owned<PinBuf> h_keys_blob;
     Packed cmd;
     size_t cmd_bytes = 0;
     CmdState cmd_state = CMD_NONE;
@@ -413,6 +417,7 @@ int enqueue_commands(nfc_multi *m) {
     A.R = frames_args(m, m->cmd.d.as<uint8_t>(), F);
     A.state = m->d_fsm.as<uint32_t>();
     A.L = L;
+    A.sector_keys = m->d_keys.as<uint32_t>();
     const bool timed = m->timing != 0;
     frames::launch_multi(A.R, m->st, timed ? m->evc[0] : nullptr, timed ? m->evc[1] : nullptr);
     commands::launch(A, m->st, timed ? m->evc[2] : nullptr, timed ? m->evc[3] : nullptr);
@@ -1070,6 +1075,7 @@ int nfc_multi_reset(nfc_multi *m, int64_t stream) {
     const size_t work = (size_t)(k1 - k0) * (size_t)m->L;
     NFC_LAUNCH(k_multi_reset, dim3((unsigned)std::min<size_t>(1024, (work + 255) / 256)), dim3(256), 0, m->st, m->A.S, m->K, k0, k1, m->L, m->A.O.counts);
     if (m->d_fsm.p) commands::launch_init(m->d_fsm.as<uint32_t>(), m->K, k0, k1, m->st);   // the machines too, keys included, as nfc_fsm_reset
+    if (m->d_keys.p) commands::launch_set_table(m->d_keys.as<uint32_t>(), m->K, k0, k1, nullptr, m->st);   // ... and their sector keys
     m->cmd_state = nfc_multi::CMD_NONE;
     m->cmd_fetched = false;
     if (int rc = launch_ok(m)) return rc;
@@ -1106,6 +1112,73 @@ int nfc_multi_set_keys(nfc_multi *m, int64_t stream, const uint8_t key_a[6], con
     if (int rc = ensure_fsm(m, "nfc_multi_set_keys")) return rc;
     commands::launch_set_keys(m->d_fsm.as<uint32_t>(), m->K, k0, k1, fsmd::key_of(key_a), fsmd::key_of(key_b), m->st);
     return launch_ok(m);
+}
+
+// the tables' buffer, zeroed, and the blobs, at the first nfc_multi_set_sector_keys of a context
+static int ensure_keys(nfc_multi *m, const char *fn) {
+    if (m->d_keys.p) return NFC_OK;
+    const size_t blob = (size_t)skeys::WORDS * 4, bytes = blob * m->K;
+    if (grow(m, m->d_keys_blob, blob, fn, false) < 0 || grow(m, m->h_keys_blob, blob, fn, false) < 0) return NFC_ERR_NOMEM;
+    Owned<DevBuf> fresh;
+    if (fresh.ensure(bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return mfail(m, NFC_ERR_NOMEM, "%s: no device memory for %zu bytes", fn, bytes);
+    }
+    MCHK(m, hipMemsetAsync(fresh.p, 0, fresh.cap, m->st));
+    std::swap(m->d_keys.p, fresh.p);   // (only a zeroed buffer is ever the context's)
+    std::swap(m->d_keys.cap, fresh.cap);
+    return NFC_OK;
+}
+
+int nfc_multi_set_sector_keys(nfc_multi *m, int64_t stream, const nfc_fsm_key_table *table) {
+    if (!m) return NFC_ERR_ARG;
+    LaunchScope scope(&m->launch_err);
+    uint32_t k0, k1;
+    if (int rc = stream_range(m, stream, k0, k1)) return rc;
+    if (!table) return mfail(m, NFC_ERR_ARG, "table is null");
+    if (const char *bad = skeys::table_fault(*table)) return mfail(m, NFC_ERR_ARG, "table: %s", bad);
+    if (hipSetDevice(m->P.device) != hipSuccess) return mfail(m, NFC_ERR_DEVICE, "hipSetDevice failed");
+    if (int rc = ensure_keys(m, "nfc_multi_set_sector_keys")) return rc;
+    MCHK(m, hipStreamSynchronize(m->st));   // (the blob may still be on its way from an earlier call)
+    uint32_t *w = m->h_keys_blob.as<uint32_t>();
+    const skeys::HostTable T = {table};
+    for (uint32_t slot = 0; slot < skeys::SLOTS; slot++) {
+        uint64_t key = 0;
+        const bool have = T.get(slot, key);
+        w[2 * slot] = have ? skeys::word_lo(key) : 0u;
+        w[2 * slot + 1] = skeys::word_hi(key, have);
+    }
+    MCHK(m, hipMemcpyAsync(m->d_keys_blob.p, m->h_keys_blob.p, skeys::WORDS * 4, hipMemcpyHostToDevice, m->st));
+    commands::launch_set_table(m->d_keys.as<uint32_t>(), m->K, k0, k1, m->d_keys_blob.as<uint32_t>(), m->st);
+    if (int rc = launch_ok(m)) return rc;
+    MCHK(m, hipStreamSynchronize(m->st));
+    return NFC_OK;
+}
+
+int nfc_multi_get_sector_keys(nfc_multi *m, uint32_t stream, nfc_fsm_key_table *table) {
+    if (!m) return NFC_ERR_ARG;
+    LaunchScope scope(&m->launch_err);
+    if (stream >= m->K) return mfail(m, NFC_ERR_ARG, "stream %u out of range (n_streams %u)", stream, m->K);
+    if (!table) return mfail(m, NFC_ERR_ARG, "table is null");
+    memset(table, 0, sizeof *table);
+    if (hipSetDevice(m->P.device) != hipSuccess) return mfail(m, NFC_ERR_DEVICE, "hipSetDevice failed");
+    if (!m->d_keys.p) {   // no sector key was ever set: every table is empty and nothing is allocated for the question
+        MCHK(m, hipStreamSynchronize(m->st));
+        return NFC_OK;
+    }
+    commands::launch_table_io(m->d_keys.as<uint32_t>(), m->K, stream, 0, m->d_keys_blob.as<uint32_t>(), m->st);
+    if (int rc = launch_ok(m)) return rc;
+    MCHK(m, hipMemcpyAsync(m->h_keys_blob.p, m->d_keys_blob.p, skeys::WORDS * 4, hipMemcpyDeviceToHost, m->st));
+    MCHK(m, hipStreamSynchronize(m->st));
+    const uint32_t *w = m->h_keys_blob.as<uint32_t>();
+    for (uint32_t slot = 0; slot < skeys::SLOTS; slot++) {
+        if (!(w[2 * slot + 1] & skeys::PRESENT)) continue;
+        const uint32_t type = slot / skeys::SECTORS, sec = slot % skeys::SECTORS;
+        const uint64_t key = (uint64_t)w[2 * slot] | (uint64_t)(w[2 * slot + 1] & 0xFFFFu) << 32;
+        table->present[type][sec] = 1;
+        for (int i = 0; i < 6; i++) table->key[type][sec][i] = (uint8_t)(key >> (8 * i));
+    }
+    return NFC_OK;
 }
 
 int nfc_multi_get_fsm_state(nfc_multi *m, uint32_t stream, nfc_fsm_state *st) {

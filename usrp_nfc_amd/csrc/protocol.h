@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/nfc_amd.h"
+#include "sector_keys.h"
 
 namespace nfc {
 
@@ -262,7 +263,7 @@ struct nfc_fsm {
     nfc_fsm &operator=(const nfc_fsm &o) {
         cur_cmd = o.cur_cmd; tag_type = o.tag_type; encrypted = o.encrypted; cipher = o.cipher; uid = o.uid;
         memcpy(key_a, o.key_a, 6); memcpy(key_b, o.key_b, 6);
-        cur_key = (o.cur_key == o.key_b) ? key_b : key_a;
+        cur_key = o.cur_key; table = o.table;
         return *this;
     }
     int cur_cmd = nfc::CMD_REQA;
@@ -270,8 +271,17 @@ struct nfc_fsm {
     int encrypted = 0;          // a CRYPTO1 session is up (fsm._encryption)
     nfc::Crypto1 cipher;
     uint8_t key_a[6] = {0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF}, key_b[6] = {0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF};   // fsm.py:157-160
-    const uint8_t *cur_key = key_a;
+    int cur_key = 0;            // 0: key_a, 1: key_b, 2 + slot: that slot of `table` (sector_keys.h)
+    nfc_fsm_key_table table = {};   // the per-sector keys; empty: the two keys above serve every sector
     std::vector<uint8_t> uid;
+    // the choice at an AUTHA (type 0) / AUTHB (1) on `block`; the key a choice stands for, at the nonce frame that loads the register
+    int choose_key(int type, uint8_t block) const { return nfc::skeys::choose(nfc::skeys::HostTable{&table}, (uint32_t)type, block); }
+    void load_cur_key(nfc::Crypto1 &c) const {
+        const uint64_t k = nfc::skeys::resolve(nfc::skeys::HostTable{&table}, cur_key, nfc::skeys::key48(key_a), nfc::skeys::key48(key_b));
+        uint8_t b[6];
+        for (int i = 0; i < 6; i++) b[i] = (uint8_t)(k >> (8 * i));
+        c.load_key(b);
+    }
     void reset_tag() {   // fsm.py:20-24
         uid.clear();
         tag_type = -1;
@@ -313,7 +323,7 @@ inline int fsm_strip(nfc_fsm &F, std::vector<uint8_t> &bits, nfc_frame *out, uin
         } else if (F.cur_cmd == CMD_AUTHA || F.cur_cmd == CMD_AUTHB) {
             // nested authentication: a fresh register keyed for the new sector swallows the encrypted tag nonce
             F.cipher = Crypto1();
-            F.cipher.load_key(F.cur_key);
+            F.load_cur_key(F.cipher);
             plain.assign(bits.size(), 0);
             size_t ll = F.uid.size() * 9;
             if (!F.cipher.set_tag(F.uid, bits.data(), bits.size(), true, plain.data())) ll = 0;
@@ -392,12 +402,12 @@ inline void fsm_finish(nfc_fsm &F, int nb, int type, nfc_frame *out, uint8_t *by
             F.uid.insert(F.uid.end(), extra, extra + 4);
         }
         break;
-    case CMD_AUTHA: F.cur_key = F.key_a; break;
-    case CMD_AUTHB: F.cur_key = F.key_b; break;
+    case CMD_AUTHA: F.cur_key = F.choose_key(0, extra[0]); break;   // (total() == 4: the block is there)
+    case CMD_AUTHB: F.cur_key = F.choose_key(1, extra[0]); break;
     case CMD_RANDTA:
         if (!F.encrypted) {   // first authentication: the tag nonce came in the clear (fsm.py:197-202)
             F.cipher = Crypto1();
-            F.cipher.load_key(F.cur_key);
+            F.load_cur_key(F.cipher);
             uint8_t nb[32];
             for (int i = 0; i < 32; i++) nb[i] = (uint8_t)((extra[i >> 3] >> (i & 7)) & 1);
             if (out->n_extra >= 4 && F.cipher.set_tag(F.uid, nb, 32, false, nullptr)) F.encrypted = 1;
@@ -473,6 +483,13 @@ inline int fsm_process_outgoing(nfc_fsm &F, const uint8_t *bits, size_t n, int c
     for (size_t i = 0; i < n; i++) out[i] = bits[i] & 1;
     if (F.tag_type == 1) {   // CLASSIC1K (fsm.py:73-99)
         F.cur_cmd = cmd;
+        if ((cmd == CMD_AUTHA || cmd == CMD_AUTHB) && n >= 17) {
+            // the sector's key from the table, as a heard AUTH chooses it; with no slot present the choice stays the caller's, as ever
+            uint8_t block = 0;
+            for (int k = 0; k < 8; k++) block |= (uint8_t)((bits[9 + k] & 1) << k);
+            const int c = F.choose_key(cmd == CMD_AUTHB, block);
+            if (c >= 2) F.cur_key = c;
+        }
         if (F.encrypted && cmd != CMD_RANDTA) {
             if (cmd == CMD_RANDRB) {   // {nr}{ar}: the reader's own nonce feeds the register as it is encrypted
                 const size_t ll = n / 2;
@@ -491,7 +508,7 @@ inline int fsm_process_outgoing(nfc_fsm &F, const uint8_t *bits, size_t n, int c
             for (size_t i = 0; i < n && m < 32; i++)
                 if (i % 9 != 8) nb[m++] = bits[i] & 1;
             F.cipher = Crypto1();
-            F.cipher.load_key(F.cur_key);
+            F.load_cur_key(F.cipher);
             if (m == 32 && F.cipher.set_tag(F.uid, nb, 32, false, nullptr)) F.encrypted = 1;
             if (was) old.crypt(bits, n, out, 0, 0, 1);
         }

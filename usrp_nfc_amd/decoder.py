@@ -81,6 +81,23 @@ _SCALED_KINDS = (api.NFC_IN_I16_SQ, api.NFC_IN_IQ_I16, api.NFC_IN_IQ_I8, api.NFC
 _RECORDED_KINDS = _IQ_KINDS + (api.NFC_IN_ENV_F32,)   # (the kinds `dst` records: the UHD branch's stand-ins and a ready envelope)
 
 
+def _is_key(k):
+    try:
+        return len(k) == 6 and all(isinstance(v, (int, numpy.integer)) for v in k)
+    except TypeError:
+        return False
+
+
+def _per_source_keys(keys, n):
+    """decode_many's ``keys`` as one (key_a, key_b) or (key_a, key_b, table) per source."""
+    one = lambda k: len(k) in (2, 3) and _is_key(k[0]) and _is_key(k[1])
+    if one(keys):
+        return [tuple(keys)] * n
+    if len(keys) == n and all(one(k) for k in keys):
+        return [tuple(k) for k in keys]
+    raise ValueError('decode_many: keys is one (key_a, key_b) pair or (key_a, key_b, table) triple, or one of them per source')
+
+
 def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None, keep=None, device=0, push_stats=None, frames=False, commands=False,
                 keys=None, nested=False, **sink_kwargs):
     """Decode many recordings at once: every source is a stream of one api.NfcMultiContext, a GPU lane each, one kernel launch per
@@ -99,15 +116,18 @@ def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None,
     commands=True: the context tracks the commands on the GPU (api.NfcMultiContext.track_commands: the protocol machine, CRYPTO1
     included, a lane per source); after every push they are fetched once (fetch_commands) and every source's ``(table, data, enc)``
     -- what fsm.dispatch prints -- is appended to its background's ``commands``.  keys: ``(key_a, key_b)`` for all sources, or a list
-    with one such pair per source (default: FF..FF).  Without the argument nothing changes.
+    with one such pair per source (default: FF..FF); in place of a pair also a triple ``(key_a, key_b, table)``, `table` the sector keys
+    as NfcMultiContext.set_sector_keys takes them ((key_type, sector) -> key).  Without the argument nothing changes.
     keys='recover': per group of sources one UNTRACKED pass first collects every source's frames across its pushes, ONE key recovery
     (usrp_nfc_amd.keys.recover) searches the keys of all their first authentications, the context is reset, every stream gets the first
     key found for type A and for type B (the default where none was found), and the tracked pass follows as above.  Every background
     gets ``recovered_keys``: (key_type, block) -> six key bytes.  The cost is the doubled push.
     nested=True (with keys='recover'): the nested authentications are searched too (usrp_nfc_amd.keys.recover_streams), and
-    ``recovered_keys`` holds every sector key whose AUTH command could be decrypted and labelled.  The streams still get
-    ``first_keys(...)``: the machine holds ONE key A and ONE key B, so a card with more than one key per type decrypts only as far as
-    those two reach (a per-sector key table in the machine is not built: DESIGN.md 8i).
+    ``recovered_keys`` holds every sector key whose AUTH command could be decrypted and labelled.
+    With keys='recover' every stream gets ``first_keys(...)`` as its two keys AND ``keys.sector_table(recovered_keys)`` as its table
+    (DESIGN.md 8j), so a card whose sectors have different keys is decrypted through every authentication whose key was found.  Two
+    blocks of one sector with different keys: the lower block's is used and the others are the background's ``key_conflicts``, a dict
+    (key_type, block) -> key (empty where there were none).
     -> one ``background`` per source, in order: ``decode_many(srcs)[i].packets`` and its fsm's command trace are what
     ``decoder(src=srcs[i]).run()`` gives."""
     scales = {k: sink_kwargs.pop(k, 0.0) for k in ('wav_scale', 'iq16_scale', 'iq8_scale')}
@@ -134,17 +154,13 @@ def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None,
             raise ValueError('decode_many: keys are for commands=True')
         for b in backs:
             b.recovered_keys = {}
+            b.key_conflicts = {}
     elif nested:
         raise ValueError("decode_many: nested is for keys='recover'")
     elif keys is not None:
         if not commands:
             raise ValueError('decode_many: keys are for commands=True')
-        if len(keys) == 2 and numpy.ndim(keys[0]) == 1 and numpy.size(keys[0]) == 6:
-            per_source_keys = [tuple(keys)] * len(loaded)
-        elif len(keys) == len(loaded):
-            per_source_keys = [tuple(k) for k in keys]
-        else:
-            raise ValueError('decode_many: keys is one (key_a, key_b) pair or one pair per source')
+        per_source_keys = _per_source_keys(keys, len(loaded))
     if not loaded:
         return backs
     kind, scale = kinds[0], loaded[0][2]
@@ -168,13 +184,23 @@ def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None,
                         for k, b in enumerate(backs[g0:g0 + len(group)]):
                             if b.recovered_keys:
                                 m.set_keys(*_keys.first_keys(b.recovered_keys), stream=k)
+                                table, b.key_conflicts = _keys.sector_table(b.recovered_keys)
+                                m.set_sector_keys(table, stream=k)
                     if per_source_keys is not None:
-                        same = all(numpy.array_equal(k, per_source_keys[g0]) for k in per_source_keys[g0:g0 + len(group)])
-                        if same:
-                            m.set_keys(*per_source_keys[g0])
+                        mine = per_source_keys[g0:g0 + len(group)]
+                        pairs, tables = [k[:2] for k in mine], [k[2] if len(k) == 3 else None for k in mine]
+                        if all(numpy.array_equal(k, pairs[0]) for k in pairs):
+                            m.set_keys(*pairs[0])
                         else:
                             for k in range(len(group)):
-                                m.set_keys(*per_source_keys[g0 + k], stream=k)
+                                m.set_keys(*pairs[k], stream=k)
+                        if all(t is tables[0] for t in tables):   # (no table anywhere: nothing is set and nothing allocated)
+                            if tables[0] is not None:
+                                m.set_sector_keys(tables[0])
+                        else:
+                            for k in range(len(group)):
+                                if tables[k] is not None:
+                                    m.set_sector_keys(tables[k], stream=k)
                 done = numpy.zeros(len(group), numpy.int64)
                 while True:
                     n = numpy.minimum(lens - done, piece)

@@ -5,13 +5,16 @@
 and UID tracking run in the shared library (csrc/protocol.h).  `process_packets` is the batch form for the
 packet tables a GPU batch produces.  MIFARE Classic sessions are decrypted (CRYPTO1: cipher.py, lfsr.py) with the
 keys of set_keys (default FF..FF), nested authentications included; as in the reference, the ciphertext of every
-frame of a session is printed before its decoded command."""
+frame of a session is printed before its decoded command.  A card whose sectors have different keys takes a table
+(set_sector_keys: (key_type, sector) -> key; include/nfc_amd.h): every AUTHA / AUTHB looks its block's
+sector up there and falls back to the two keys of set_keys where the table has no entry."""
 import ctypes as C
 import sys
 
 import numpy as np
 
 from . import _lib
+from . import keys as _keys
 from .command import CommandStructure, CommandType
 
 NFC_CMD_UNKNOWN, NFC_CMD_PARITY_ERROR = -1, -2
@@ -78,9 +81,10 @@ def state_init():
     return st
 
 
-def host_commands(state, frames, data=None, par=None):
-    """The GPU machine's twin on the CPU (nfc_host_commands): `frames` as process_frames takes them, `state` an _lib.FsmState that is
-    advanced in place.  -> (table, data, enc): every frame owns a slot of its raw n_bytes entries in data and enc."""
+def host_commands(state, frames, data=None, par=None, sector_keys=None):
+    """The GPU machine's twin on the CPU (nfc_host_commands_keyed): `frames` as process_frames takes them, `state` an _lib.FsmState that
+    is advanced in place, sector_keys the stream's key table (keys.key_table's argument; None: none -- nfc_host_commands).
+    -> (table, data, enc): every frame owns a slot of its raw n_bytes entries in data and enc."""
     if data is None:
         frames, data, par = frames.table, frames.bytes, frames.par
     t = np.ascontiguousarray(frames, _lib.RAW_FRAME_DTYPE)
@@ -90,10 +94,11 @@ def host_commands(state, frames, data=None, par=None):
     out, buf, enc = np.zeros(len(t), FRAME_DTYPE), np.zeros(cap, np.uint8), np.zeros(cap, np.uint16)
     used = C.c_size_t(0)
     ptr = lambda a: a.ctypes.data if a.size else None
-    rc = _lib.load().nfc_host_commands(C.byref(state), ptr(t), len(t), ptr(b[0]), ptr(p[0]), ptr(b[1]), ptr(p[1]), out.ctypes.data,
-                                       buf.ctypes.data, enc.ctypes.data, cap, C.byref(used))
+    keyed = None if sector_keys is None else C.byref(_keys.key_table(sector_keys))
+    rc = _lib.load().nfc_host_commands_keyed(C.byref(state), keyed, ptr(t), len(t), ptr(b[0]), ptr(p[0]), ptr(b[1]), ptr(p[1]), out.ctypes.data,
+                                             buf.ctypes.data, enc.ctypes.data, cap, C.byref(used))
     if rc != 0:
-        raise ValueError('nfc_host_commands status %d' % rc)
+        raise ValueError('nfc_host_commands_keyed status %d' % rc)
     return out, buf[:used.value], enc[:used.value]
 
 
@@ -123,6 +128,27 @@ class fsm(object):
         b = np.ascontiguousarray(key_b, np.uint8)
         if a.size != 6 or b.size != 6 or self.L.nfc_fsm_set_keys(self._h, a.ctypes.data, b.ctypes.data) != 0:
             raise ValueError('keys are six bytes each')
+
+    def set_sector_keys(self, table=None):
+        """The per-sector key table (nfc_fsm_set_key_table): a dict (key_type, sector) -> six key bytes, key_type 0x60 / 0x61, or an
+        _lib.FsmKeyTable; None or {} empties it.  An AUTHA / AUTHB on a block whose sector has an entry is keyed with it, every other
+        one with set_keys' two keys.  reset() empties the table; set_keys and set_state leave it alone."""
+        if self.L.nfc_fsm_set_key_table(self._h, C.byref(_keys.key_table(table))) != 0:
+            raise ValueError('nfc_fsm_set_key_table failed')
+
+    def set_sector_key(self, key_type, sector, key):
+        """One slot of the table (nfc_fsm_set_sector_key): key None clears it."""
+        _keys.key_table({(key_type, sector): key})   # (names what is wrong)
+        k = None if key is None else np.ascontiguousarray(list(bytearray(key)), np.uint8)
+        if self.L.nfc_fsm_set_sector_key(self._h, int(key_type), int(sector), None if k is None else k.ctypes.data) != 0:
+            raise ValueError('nfc_fsm_set_sector_key failed')
+
+    def sector_keys(self):
+        """The table as the dict (key_type, sector) -> six key bytes of its present slots (nfc_fsm_get_key_table)."""
+        t = _lib.FsmKeyTable()
+        if self.L.nfc_fsm_get_key_table(self._h, C.byref(t)) != 0:
+            raise ValueError('nfc_fsm_get_key_table failed')
+        return _keys.table_dict(t)
 
     def get_state(self):
         """The machine as a plain nfc_fsm_state (nfc_fsm_get_state) -- what NfcMultiContext.set_fsm_state takes.  ValueError when the

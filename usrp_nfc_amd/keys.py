@@ -8,7 +8,12 @@ the call's _lib.KeyStats.  There is no fall-back from one to the other.
 Every later authentication of a session is NESTED, its tag nonce encrypted: ``find_nested_auths(frames)`` finds them by shape,
 ``nested_candidates(traces)`` lists the 64 (or 0) plaintext nonces each can have, ``recover_nested(traces)`` / ``host_recover_nested``
 search one key per candidate and report a NESTED_RESULT_DTYPE record per trace, and ``label_auths`` decrypts the AUTH commands with the
-recovered keys to say which sector each key belongs to."""
+recovered keys to say which sector each key belongs to.
+
+A card has a key A and a key B PER SECTOR: ``sector_of(block)`` is the mapping, ``sector_table(found)`` turns the recovered
+``(key_type, block) -> key`` into the ``(key_type, sector) -> key`` table that the protocol machines take (fsm.set_sector_keys,
+NfcMultiContext.set_sector_keys, fsm.host_commands(..., sector_keys=)), ``key_table`` / ``table_dict`` go between that dict and the C
+structure (_lib.FsmKeyTable: nfc_fsm_key_table)."""
 import ctypes as C
 
 import numpy as np
@@ -90,6 +95,58 @@ def first_keys(found):
         ks = [v for (t, _), v in found.items() if t == kt]
         pair.append(list(bytearray(ks[0])) if ks else [0xFF] * 6)
     return tuple(pair)
+
+
+def sector_of(block):
+    """The sector of a block (nfc_sector_of_block): blocks 0 .. 127 four to a sector, 128 .. 255 sixteen -> 0 .. 39."""
+    s = _lib.load().nfc_sector_of_block(int(block))
+    if s < 0:
+        raise ValueError('block %r is outside 0 .. 255' % (block,))
+    return s
+
+
+def key_table(table=None):
+    """An _lib.FsmKeyTable (nfc_fsm_key_table) from None (empty), another FsmKeyTable (a checked copy) or a dict
+    (key_type, sector) -> six key bytes (None: that slot stays empty), key_type 0x60 / 0x61, sector 0 .. 39.  ValueError names what is wrong."""
+    t = _lib.FsmKeyTable()
+    if table is None:
+        return t
+    if isinstance(table, _lib.FsmKeyTable):
+        C.memmove(C.byref(t), C.byref(table), C.sizeof(t))
+        if any(p > 1 for row in t.present for p in row):
+            raise ValueError('present: a byte of the table is neither 0 nor 1')
+        return t
+    for (key_type, sector), key in dict(table).items():
+        if key_type not in (0x60, 0x61):
+            raise ValueError('key_type %r is neither 0x60 nor 0x61' % (key_type,))
+        if not 0 <= int(sector) < _lib.NFC_KEY_SECTORS:
+            raise ValueError('sector %r is outside 0 .. %d' % (sector, _lib.NFC_KEY_SECTORS - 1))
+        if key is None:
+            continue
+        k = list(bytearray(key))
+        if len(k) != 6:
+            raise ValueError('key: the key of (0x%02X, %d) is not six bytes' % (key_type, sector))
+        t.present[key_type & 1][int(sector)] = 1
+        for i in range(6):
+            t.key[key_type & 1][int(sector)][i] = k[i]
+    return t
+
+
+def table_dict(table):
+    """An _lib.FsmKeyTable as the dict (key_type, sector) -> six key bytes of its present slots."""
+    return {(0x60 + t, s): bytes(bytearray(table.key[t][s])) for t in (0, 1) for s in range(_lib.NFC_KEY_SECTORS) if table.present[t][s]}
+
+
+def sector_table(found):
+    """A dict of recovered keys (key_type, block) -> key (keys_by_stream, label_auths, a background's ``recovered_keys``) as the machines'
+    table: -> (table, conflicts), `table` the dict (key_type, sector) -> six key bytes.  Two blocks of one sector whose keys differ cannot
+    both be right: the LOWER block's key is kept and the other entry comes back in `conflicts`, a dict (key_type, block) -> key."""
+    table, conflicts = {}, {}
+    for (key_type, block), key in sorted(found.items()):
+        slot, key = (int(key_type), sector_of(block)), bytes(bytearray(key))
+        if table.setdefault(slot, key) != key:
+            conflicts[(int(key_type), int(block))] = key
+    return table, conflicts
 
 
 def nested_candidates(traces, device=None):
