@@ -362,7 +362,9 @@ constexpr int ES_ITEMS = EW_WORDS / 64;            // words per thread here: a w
 static_assert(ES_ITEMS % 2 == 0 && ES_ITEMS * 64 == EW_WORDS, "a wave of the reduce pass covers one writer tile");
 inline size_t edge_num_supers(size_t nwords) { return (edge_num_tiles(nwords) + EW_SUPER - 1) / EW_SUPER; }
 // (round 4: WPT waves per tile -- 512 threads a workgroup at WPT = 2, four words per lane; 4 and 1 measured the same within 1 us: the pass is the first read of the 25 MB of planes the threshold kernel just wrote, not its arithmetic.  With one wave per tile
-// a lane folded eight words one after the other behind one round of loads, at three waves per SIMD: 12 us for 25 MB.)
+// a lane folded eight words one after the other behind one round of loads, at three waves per SIMD: 12 us for 25 MB.
+// With the writer threads' records (EdgeRec, below) a lane of WPT = 2 covers two writer threads and derives the second one's record from its own
+// words; WPT = 4, a lane per writer thread and three waves to join through LDS, measured 1.5 us more in this pass and in the step.)
 #ifndef NFC_ER_WPT
 #define NFC_ER_WPT 2
 #endif
@@ -370,21 +372,48 @@ constexpr int ER_WPT = NFC_ER_WPT;                    // waves per tile
 constexpr int ER_ITEMS = ES_ITEMS / ER_WPT;           // words per lane
 constexpr int ER_BLOCK = 64 * ER_WPT * EW_SUPER;      // threads per workgroup: EW_SUPER tiles
 static_assert(ER_ITEMS >= 2 && ER_ITEMS % 2 == 0 && ER_ITEMS * ER_WPT == ES_ITEMS, "pairs of words per lane");
-__device__ __forceinline__ void edge_reduce_super(const EdgeArgs &A, size_t nwords, uint32_t super, EdgeAgg *partials, EdgeAgg *supers) {
-    __shared__ EdgeAgg lds[EW_SUPER * ER_WPT];
+// What the pass leaves per WRITER thread (EW_ITEMS consecutive words of a tile), so that the writer need not scan its tile again: the exclusive
+// EdgeAggOp fold of the threads before it IN THE TILE -- the last two changes (POS_NONE: none) and the entries the tile is sure of before the
+// thread.  The run that enters the tile is not in it: the writer adds its time-outs from the tile's prefix (write_edges_tile).
+// Eight bytes: the positions are tile-local in 16 bits -- a tile is at most 65 536 samples and no exclusive prefix reaches its last word, so
+// 0xFFFF is free for "none".  (Twelve bytes with the positions as they are measured 2 us more in the writer and 0.8 in this pass, the
+// step 0.5 us more: profiles/edge_prefix_ab.txt.)
+struct EdgeRec {
+    uint32_t l16;   // s1 | s2 << 16
+    uint32_t sum;
+};
+__device__ __forceinline__ EdgeRec edge_rec_pack(Last2 l, uint32_t sum, int32_t tile_p0) {
+    const uint32_t a = l.s1 != POS_NONE ? (uint32_t)(l.s1 - tile_p0) : 0xFFFFu, b = l.s2 != POS_NONE ? (uint32_t)(l.s2 - tile_p0) : 0xFFFFu;
+    return EdgeRec{a | (b << 16), sum};
+}
+__device__ __forceinline__ Last2 edge_rec_last2(const EdgeRec &r, int32_t tile_p0) {
+    const uint32_t a = r.l16 & 0xFFFFu, b = r.l16 >> 16;
+    return Last2{a != 0xFFFFu ? tile_p0 + (int32_t)a : POS_NONE, b != 0xFFFFu ? tile_p0 + (int32_t)b : POS_NONE};
+}
+constexpr int ER_RECS = ER_ITEMS / EW_ITEMS;          // writer threads per lane
+static_assert(ER_RECS * EW_ITEMS == ER_ITEMS && (ER_RECS == 1 || ER_RECS == 2), "a lane covers one or two writer threads");
+__device__ __forceinline__ void edge_reduce_super(const EdgeArgs &A, size_t nwords, uint32_t super, EdgeAgg *partials, EdgeAgg *supers, EdgeRec *recs) {
+    __shared__ EdgeAgg lds[EW_SUPER * ER_WPT], lds_t[EW_SUPER];   // per wave; per tile
     const EdgeAggOp op{A.mx, A.mx_magic};
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;   // wave: ER_WPT consecutive ones per tile
     const size_t tile = (size_t)super * EW_SUPER + wave / ER_WPT;
     const size_t w = tile * EW_WORDS + ((size_t)(wave % ER_WPT) * 64 + lane) * ER_ITEMS;
     uint64_t ng[ER_ITEMS], ps[ER_ITEMS], m[ER_ITEMS];
     load_words<ER_ITEMS>(A, w, nwords, ng, ps, m);
-    EdgeAgg agg = op.identity();
     bool may = false;
 #pragma unroll
     for (int i = 0; i < ER_ITEMS; i++) may = may || word_may_time_out(A, m[i]);
     const bool inner = __any(may);
+    EdgeAgg sub[ER_RECS];   // a writer thread's words each; the lane's aggregate from those (the operator is associative, exactly)
 #pragma unroll
-    for (int i = 0; i < ER_ITEMS; i++) agg = op(agg, word_agg(A, (int32_t)((w + i) * 64), m[i], inner));
+    for (int r = 0; r < ER_RECS; r++) {
+        sub[r] = word_agg(A, (int32_t)((w + r * EW_ITEMS) * 64), m[r * EW_ITEMS], inner);
+#pragma unroll
+        for (int i = 1; i < EW_ITEMS; i++) sub[r] = op(sub[r], word_agg(A, (int32_t)((w + r * EW_ITEMS + i) * 64), m[r * EW_ITEMS + i], inner));
+    }
+    EdgeAgg agg = sub[0];
+#pragma unroll
+    for (int r = 1; r < ER_RECS; r++) agg = op(agg, sub[r]);
     // The wave's aggregate without scanning the whole aggregate (round 5; the operator's division by max_len is then paid once per lane
     // instead of once per lane and scan step): the last two changes by a scan of selects, the first change by a minimum, and the entries
     // by a sum -- a lane adds the time-outs of the run that ENDS at its first change, which it knows from the changes before it in the wave
@@ -396,24 +425,56 @@ __device__ __forceinline__ void edge_reduce_super(const EdgeArgs &A, size_t nwor
     const int32_t first_inc = wave_inclusive<MinI32>(agg.first != POS_NONE ? agg.first : INT32_MAX);
     if (lane == 63) lds[wave] = EdgeAgg{first_inc != INT32_MAX ? first_inc : POS_NONE, l_inc, sum_inc};
     __syncthreads();
+    if (recs && tile * EW_WORDS < nwords) {
+        // The writer threads' records: what the scans above already hold is the fold of the lanes before this one in the WAVE; the waves of
+        // the tile before this one come on top (P), with the time-outs of the run that crosses from them to the wave's first change (join:
+        // one division per wave, every lane behind that change counts it).
+        EdgeAgg P = op.identity();
+#pragma unroll
+        for (int k = 0; k + 1 < ER_WPT; k++)
+            if (k < wave % ER_WPT) P = op(P, lds[wave / ER_WPT * ER_WPT + k]);
+        const int32_t wave_first = __builtin_amdgcn_readlane(first_inc, 63);
+        const uint32_t join = (P.l.s1 != POS_NONE && wave_first != INT32_MAX) ? A.timeouts_between(P.l.s1, wave_first) : 0u;
+        struct { Last2 l; uint32_t sum; } e[ER_RECS];
+        e[0].l = Last2Op::op(P.l, l_exc);
+        e[0].sum = P.sum + (sum_inc - (agg.sum + cross)) + (l_exc.s1 != POS_NONE ? join : 0u);
+        if (ER_RECS == 2) {
+            // ... and the lane's first writer thread before its second: the run that ends at that thread's first change (the lane's first) is
+            // the one `cross` counted, or the one that crosses from the earlier waves, or the one that enters the tile (not counted here)
+            const uint32_t x = sub[0].first == POS_NONE ? 0u : (l_exc.s1 != POS_NONE ? cross : join);
+            e[ER_RECS - 1].l = Last2Op::op(e[0].l, sub[0].l);
+            e[ER_RECS - 1].sum = e[0].sum + sub[0].sum + x;
+        }
+        EdgeRec *o = recs + tile * SCAN_BLOCK + (size_t)((wave % ER_WPT) * 64 + lane) * ER_RECS;
+        const int32_t tile_p0 = (int32_t)(tile * EW_WORDS * 64);
+        uint32_t o32[ER_RECS * 2];
+#pragma unroll
+        for (int r = 0; r < ER_RECS; r++) {
+            const EdgeRec x = edge_rec_pack(e[r].l, e[r].sum, tile_p0);
+            o32[2 * r] = x.l16;
+            o32[2 * r + 1] = x.sum;
+        }
+        if constexpr (ER_RECS == 2) *(uint4 *)o = make_uint4(o32[0], o32[1], o32[2], o32[3]);   // (a lane's two records in one 16-byte store)
+        else *(uint2 *)o = make_uint2(o32[0], o32[1]);
+    }
     if (threadIdx.x < EW_SUPER) {   // a lane per tile folds its waves; lane 0 the tiles
         EdgeAgg t = lds[threadIdx.x * ER_WPT];
 #pragma unroll
         for (int k = 1; k < ER_WPT; k++) t = op(t, lds[threadIdx.x * ER_WPT + k]);
         const size_t tl = (size_t)super * EW_SUPER + threadIdx.x;
         if (tl * EW_WORDS < nwords) partials[tl] = t;
-        lds[threadIdx.x * ER_WPT] = t;
+        lds_t[threadIdx.x] = t;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        EdgeAgg t = lds[0];
+        EdgeAgg t = lds_t[0];
 #pragma unroll
-        for (int k = 1; k < EW_SUPER; k++) t = op(t, lds[k * ER_WPT]);
+        for (int k = 1; k < EW_SUPER; k++) t = op(t, lds_t[k]);
         supers[super] = t;
     }
 }
-NFC_HDR_KERNEL_LINKAGE __global__ __launch_bounds__(ER_BLOCK) void k_edge_reduce(EdgeArgs A, size_t nwords, EdgeAgg *partials, EdgeAgg *supers) {
-    edge_reduce_super(A, nwords, blockIdx.x, partials, supers);
+NFC_HDR_KERNEL_LINKAGE __global__ __launch_bounds__(ER_BLOCK) void k_edge_reduce(EdgeArgs A, size_t nwords, EdgeAgg *partials, EdgeAgg *supers, EdgeRec *recs) {
+    edge_reduce_super(A, nwords, blockIdx.x, partials, supers, recs);
 }
 
 // per edge, for the decoders: LUT row (v + 1) * nd + d in the low 14 bits, route in the top two
@@ -479,7 +540,8 @@ inline size_t edge_num_tiles_of(size_t nwords, uint32_t sw, uint32_t tps) { retu
 //   left    _current_state the previous run left (a val-0 run that has not timed out keeps it)
 // and needs no division per entry.  Where a thread starts comes from ONE block scan of EdgeAgg on top of the tile's
 // prefix: the two changes before its first word AND, by entries_before(), the offset of its first entry.  Entries go to
-// LDS at their offsets and leave the workgroup as whole rows of positions and codes.
+// LDS at their offsets and leave the workgroup as whole rows of positions and codes.  (As launched the scan is not the writer's: the reduce
+// pass leaves every thread the fold of the threads before it in the tile -- EdgeRec -- and the writer only puts the tile's prefix in front.)
 constexpr int EW_CAP = NFC_EW_CAP;   // entries staged per round (a tile of 512 words holds 2150 on the bench workloads, 32768 at most).
 // 3072 entries of 2 + 2 bytes: 12 KB per workgroup -- six of them fit in the 96 KB of LDS a CU has left while the threshold
 // kernel of the next batch runs on it (batches submitted ahead), which is when this kernel's occupancy matters most.
@@ -494,7 +556,8 @@ struct EdgeWalk {
     int32_t cskip;   // A.skip while the run carried into the batch is still in progress (POS_NONE otherwise)
 };
 // (bid of ntiles: the writer may share a launch with another stage's workgroups -- host_context.h: k_certify_and_write)
-__device__ __forceinline__ void write_edges_tile(const EdgeArgs &A, size_t nwords, const EdgeAgg *partials, const EdgeAgg *supers, uint32_t *epos,
+// (recs: the reduce pass's records, one per thread of every tile (EdgeRec) -- null: the workgroup scans its tile itself)
+__device__ __forceinline__ void write_edges_tile(const EdgeArgs &A, size_t nwords, const EdgeAgg *partials, const EdgeAgg *supers, const EdgeRec *recs, uint32_t *epos,
                                                  uint16_t *ecode, uint32_t cap, bool own_prefix, uint32_t *total_out,
                                                  Last2 *last2_total, EdgeCarry *carry_out, const uint32_t bid, const uint32_t ntiles) {
     __shared__ uint32_t s_ent[EW_CAP + 1];   // tile-local sample position (a tile is EW_WORDS * 64 <= 65536 samples) | code << 16; slot EW_CAP: entries of another round
@@ -509,6 +572,13 @@ __device__ __forceinline__ void write_edges_tile(const EdgeArgs &A, size_t nword
     const EdgeAggOp op{A.mx, A.mx_magic};
     uint64_t ng[EW_ITEMS], ps[EW_ITEMS], m[EW_ITEMS];
     const int val_before = load_words<EW_ITEMS>(A, w_first, wend, ng, ps, m);
+    // (the thread's record and the tile's own aggregate with them)
+    EdgeRec rec = edge_rec_pack(Last2Op::identity(), 0u, 0);
+    EdgeAgg tile = op.identity();
+    if (recs) {
+        rec = recs[(size_t)bid * SCAN_BLOCK + threadIdx.x];
+        tile = partials[bid];
+    }
     EdgeAgg pre;
     const uint32_t g = ts.g, q = ts.q;
     if (own_prefix) {
@@ -549,28 +619,42 @@ __device__ __forceinline__ void write_edges_tile(const EdgeArgs &A, size_t nword
     const int32_t tile_p0 = (int32_t)min(wt * 64, (size_t)A.n);   // (an empty tile beyond the batch: nothing of it may be counted)
     const uint32_t gbase = entries_before(A, pre, tile_p0);
     TP_MARK();   // 1: words + tile prefix
-    EdgeAgg agg = op.identity();
-    bool may = false;
-#pragma unroll
-    for (int i = 0; i < EW_ITEMS; i++) may = may || word_may_time_out(A, m[i]);
-    const bool inner = __any(may);
-#pragma unroll
-    for (int i = 0; i < EW_ITEMS; i++) agg = op(agg, word_agg(A, (int32_t)((w_first + i) * 64), m[i], inner));
-    // Where a thread's entries go, in TWO cheap block scans instead of one of the whole aggregate (round 5: the aggregate's operator is
-    // 25 vector instructions, two of them quarter-rate multiplies for the division by max_len, and a block scan applies it 16 times per
-    // thread -- 420 of the writer's 1 390 vector instructions per wave).  Entries before a position are its val changes, plus per change
-    // the time-outs of the run that ENDS there, plus those of the run in progress (entries_before); the time-outs of the run that ends at
-    // a thread's first change need the change before it, which is all the first scan carries (Last2: selects only); the second scan adds
-    // counts.  Same numbers as entries_before(op(pre, exclusive aggregate), T): the gap between two spans is counted where it ends.
+    // Where a thread's entries go: the two changes before its first word and the entries before it.  Entries before a position are its val
+    // changes, plus per change the time-outs of the run that ENDS there, plus those of the run in progress (entries_before).  Same numbers as
+    // entries_before(op(pre, exclusive aggregate), T): the gap between two spans is counted where it ends.
     const int32_t s0 = (int32_t)A.skip - A.dur_in;   // where the run carried into the batch "starts"
-    __shared__ Last2 s_l2[SCAN_WAVES];
-    __shared__ uint32_t s_cnt[SCAN_WAVES];
-    Last2 tile_l;
-    const Last2 before_l = Last2Op::op(pre.l, block_exclusive<Last2Op>(agg.l, s_l2, tile_l));
-    const Last2 all_l = Last2Op::op(pre.l, tile_l);
-    const uint32_t cross = (agg.first != POS_NONE) ? A.timeouts_between(before_l.s1 != POS_NONE ? before_l.s1 : s0, agg.first) : 0u;
-    uint32_t tile_cnt;
-    const uint32_t excl_cnt = block_exclusive<AddU32>(agg.sum + cross, s_cnt, tile_cnt);
+    Last2 before_l, all_l;
+    uint32_t excl_cnt, tile_cnt;
+    if (recs) {
+        // The reduce pass scanned the tile already and left every thread the fold of the threads before it (EdgeRec).  What the record cannot
+        // hold is the run that ENTERS the tile and ends at the tile's first change: its time-outs depend on the tile's prefix, are the same for
+        // the whole tile, and only the threads behind that change count them.
+        const uint32_t enter = tile.first != POS_NONE ? A.timeouts_between(pre.l.s1 != POS_NONE ? pre.l.s1 : s0, tile.first) : 0u;
+        const Last2 rec_l = edge_rec_last2(rec, tile_p0);
+        before_l = Last2Op::op(pre.l, rec_l);
+        excl_cnt = rec.sum + (rec_l.s1 != POS_NONE ? enter : 0u);
+        all_l = Last2Op::op(pre.l, tile.l);
+        tile_cnt = tile.sum + enter;
+    } else {
+        // ... or the workgroup scans its tile itself, in TWO cheap block scans instead of one of the whole aggregate (round 5: the aggregate's
+        // operator is 25 vector instructions, two of them quarter-rate multiplies for the division by max_len, and a block scan applies it 16
+        // times per thread -- 420 of the writer's 1 390 vector instructions per wave).  The time-outs of the run that ends at a thread's first
+        // change need the change before it, which is all the first scan carries (Last2: selects only); the second scan adds counts.
+        EdgeAgg agg = op.identity();
+        bool may = false;
+#pragma unroll
+        for (int i = 0; i < EW_ITEMS; i++) may = may || word_may_time_out(A, m[i]);
+        const bool inner = __any(may);
+#pragma unroll
+        for (int i = 0; i < EW_ITEMS; i++) agg = op(agg, word_agg(A, (int32_t)((w_first + i) * 64), m[i], inner));
+        __shared__ Last2 s_l2[SCAN_WAVES];
+        __shared__ uint32_t s_cnt[SCAN_WAVES];
+        Last2 tile_l;
+        before_l = Last2Op::op(pre.l, block_exclusive<Last2Op>(agg.l, s_l2, tile_l));
+        all_l = Last2Op::op(pre.l, tile_l);
+        const uint32_t cross = (agg.first != POS_NONE) ? A.timeouts_between(before_l.s1 != POS_NONE ? before_l.s1 : s0, agg.first) : 0u;
+        excl_cnt = block_exclusive<AddU32>(agg.sum + cross, s_cnt, tile_cnt);
+    }
     const int32_t tile_end = (int32_t)min(wend * 64, (size_t)A.n), T = (int32_t)min(w_first * 64, (size_t)tile_end);
     // (entries before the tile that do not depend on where the tile begins: pre.sum and the carried run's time-outs up to the batch's first change)
     const uint32_t run_k = A.timeouts_between(before_l.s1 != POS_NONE ? before_l.s1 : s0, T);   // time-outs so far of the run in progress at T
@@ -667,10 +751,10 @@ __device__ __forceinline__ void write_edges_tile(const EdgeArgs &A, size_t nword
     }
     TP_DONE(0);   // 5: the stores
 }
-NFC_HDR_KERNEL_LINKAGE __global__ __launch_bounds__(SCAN_BLOCK) void k_write_edges(EdgeArgs A, size_t nwords, const EdgeAgg *partials, const EdgeAgg *supers, uint32_t *epos,
+NFC_HDR_KERNEL_LINKAGE __global__ __launch_bounds__(SCAN_BLOCK) void k_write_edges(EdgeArgs A, size_t nwords, const EdgeAgg *partials, const EdgeAgg *supers, const EdgeRec *recs, uint32_t *epos,
                                                            uint16_t *ecode, uint32_t cap, bool own_prefix, uint32_t *total_out,
                                                            Last2 *last2_total, EdgeCarry *carry_out) {
-    write_edges_tile(A, nwords, partials, supers, epos, ecode, cap, own_prefix, total_out, last2_total, carry_out, blockIdx.x, gridDim.x);
+    write_edges_tile(A, nwords, partials, supers, recs, epos, ecode, cap, own_prefix, total_out, last2_total, carry_out, blockIdx.x, gridDim.x);
 }
 
 }  // namespace nfc

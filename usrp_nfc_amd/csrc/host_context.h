@@ -9,7 +9,7 @@ std::string g_create_error;
 
 // (the round-5 form of the tail: the certification shares the edge writer's launch -- kept beside k_tail for the A/B)
 __global__ __launch_bounds__(256) void k_certify_and_write(CertLaunch C, EdgeArgs E, size_t nwords, const EdgeAgg *partials, const EdgeAgg *supers,
-                                                          uint32_t *epos, uint16_t *ecode, uint32_t cap, bool own_prefix, uint32_t *total_out,
+                                                          const EdgeRec *recs, uint32_t *epos, uint16_t *ecode, uint32_t cap, bool own_prefix, uint32_t *total_out,
                                                           Last2 *last2_total, EdgeCarry *carry_out) {
     const uint32_t tiles = gridDim.x - C.blocks;
     if (blockIdx.x == 0) {
@@ -20,7 +20,7 @@ __global__ __launch_bounds__(256) void k_certify_and_write(CertLaunch C, EdgeArg
         certify_block(C.A, C.cert, nullptr, C.ring_next, C.carry, C.sum, blockIdx.x - tiles - 1, C.blocks);
         return;
     }
-    write_edges_tile(E, nwords, partials, supers, epos, ecode, cap, own_prefix, total_out, last2_total, carry_out, tiles - blockIdx.x, tiles);
+    write_edges_tile(E, nwords, partials, supers, recs, epos, ecode, cap, own_prefix, total_out, last2_total, carry_out, tiles - blockIdx.x, tiles);
 }
 
 }  // namespace
@@ -188,6 +188,13 @@ struct nfc_ctx {
     DevBuf d_states, d_sym[2], d_bits[2], d_pending[2][2], d_close_end[2],
         d_close_idx[2];
     DevBuf d_partials, d_partials2, d_aggs, d_faggs;  // scan scratch
+    DevBuf d_edge_rec;   // the edge stage's reduce pass to its writer: a record per writer thread (edges.hip.h: EdgeRec).  One buffer serves batches
+                         // submitted ahead too: the edge stages of consecutive batches run one after the other on the main stream
+    // the writer reads those records instead of scanning its tile where the tail is what the step waits for: one batch at a time.  The edge
+    // stage of a batch that ran ahead runs beside the next batch's threshold kernel, which is bound by its bytes and sets the step: there the
+    // records' 12.5 MB of traffic cost more than the writer's instructions (measured: profiles/edge_prefix_ab.txt) and the writer scans.
+    // -1: that rule; the test build's NFC_EDGE_PREFIX=0 / 1: never / always
+    int edge_prefix = -1;
     // the fused tail (tail.hip.h: k_tail): status words of its look-backs, the ticket counter, the launch epoch; the packed bit arrays
     // alternate between two buffers -- a batch's launch clears the one the NEXT batch's tiles will or into
     DevBuf d_tail_st, d_tail_ticket, d_bits_alt[2];

@@ -11,7 +11,8 @@ namespace {
 // counts with head-room), the true counts stay on the device, and the caller checks them after the batch's
 // final sync -- on overflow the two stages are simply repeated with larger estimates (they are idempotent:
 // carried values come in by value and go out to write-only slots).
-int run_edges(nfc_ctx *c, uint32_t n, uint32_t skip, uint64_t g0) {
+// (beside_threshold: the stage is enqueued behind a threshold stage that ran ahead, and the next batch's may run beside it)
+int run_edges(nfc_ctx *c, uint32_t n, uint32_t skip, uint64_t g0, bool beside_threshold = false) {
     uint8_t *tot = dT(c);
     const size_t nwords = ((size_t)n + 63) / 64;
     EdgeArgs E;
@@ -35,6 +36,10 @@ int run_edges(nfc_ctx *c, uint32_t n, uint32_t skip, uint64_t g0) {
     HIPCHK(c, c->d_partials.ensure((tiles + supers + 2) * sizeof(EdgeAgg)));
     EdgeAgg *parts = c->d_partials.as<EdgeAgg>();
     EdgeAgg *sups = parts + tiles + 1;
+    // (a record per writer thread, from the reduce pass to the writer: edges.hip.h: EdgeRec -- host_context.h says when)
+    const bool use_recs = c->edge_prefix < 0 ? !beside_threshold : c->edge_prefix != 0;
+    if (use_recs) HIPCHK(c, c->d_edge_rec.ensure(std::max<size_t>(tiles, 1) * SCAN_BLOCK * sizeof(EdgeRec)));
+    EdgeRec *recs = use_recs ? c->d_edge_rec.as<EdgeRec>() : nullptr;
     // launch 1: one aggregate per tile (first change, last two changes, entries it is sure of).  While the tiles are few,
     // each tile's workgroup of the writer folds its predecessors' aggregates itself (scan.hip.h: tile_prefix) and the
     // single-workgroup prefix launch is not needed.
@@ -43,7 +48,7 @@ int run_edges(nfc_ctx *c, uint32_t n, uint32_t skip, uint64_t g0) {
     uint32_t *edges_total = (uint32_t *)(tot + TOT_EDGES);
     const EdgeAggOp op{E.mx, E.mx_magic};
     // (the first certification of the batch, when it is still to be launched, rides with the WRITER below: host_context.h)
-    if (tiles) NFC_LAUNCH(k_edge_reduce, dim3((unsigned)supers), dim3(ER_BLOCK), 0, c->st, E, nwords, parts, sups);
+    if (tiles) NFC_LAUNCH(k_edge_reduce, dim3((unsigned)supers), dim3(ER_BLOCK), 0, c->st, E, nwords, parts, sups, recs);
     if (!own || !tiles)   // (long batches: the prefix launch over the SUPER-aggregates; the totals and the carry in its epilogue)
         scan_partials_with(c->st, op, supers, nullptr, (uint32_t)(EW_WORDS * EW_SUPER), sups, op.identity(), (EdgeAgg *)nullptr,
                            EdgeTotalEpilogue{E, edges_total, last2_total, dE(c)});
@@ -53,10 +58,10 @@ int run_edges(nfc_ctx *c, uint32_t n, uint32_t skip, uint64_t g0) {
     HIPCHK(c, c->d_ecode.ensure((cap_al + 8) * 2));
     if (c->cert_pending && tiles) {
         c->cert_pending = false;
-        NFC_LAUNCH(k_certify_and_write, dim3((unsigned)(c->cert.blocks + tiles)), dim3(SCAN_BLOCK), 0, c->st, c->cert, E, nwords, parts, sups,
+        NFC_LAUNCH(k_certify_and_write, dim3((unsigned)(c->cert.blocks + tiles)), dim3(SCAN_BLOCK), 0, c->st, c->cert, E, nwords, parts, sups, recs,
                    c->d_epos.as<uint32_t>(), c->d_ecode.as<uint16_t>(), cap, own, edges_total, last2_total, dE(c));
     } else if (tiles) {
-        NFC_LAUNCH(k_write_edges, dim3((unsigned)tiles), dim3(SCAN_BLOCK), 0, c->st, E, nwords, parts, sups, c->d_epos.as<uint32_t>(),
+        NFC_LAUNCH(k_write_edges, dim3((unsigned)tiles), dim3(SCAN_BLOCK), 0, c->st, E, nwords, parts, sups, recs, c->d_epos.as<uint32_t>(),
                    c->d_ecode.as<uint16_t>(), cap, own, edges_total, last2_total, dE(c));
     }
     c->edges_from_host = false;

@@ -120,7 +120,7 @@ int enqueue_stages_behind(nfc_ctx *c, nfc_ctx::Submitted &b) {
         rc = run_tail(c, b.n, 0u, b.g0);
         if (!rc && !fused) rc = run_decode(c, true);
     } else {
-        rc = run_edges(c, b.n, 0u, b.g0);
+        rc = run_edges(c, b.n, 0u, b.g0, true);
         if (!rc) rc = run_decode(c);   // (its last launch mirrors the state block and stamps it)
     }
     if (rc) return rc;

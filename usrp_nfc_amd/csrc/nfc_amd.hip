@@ -173,6 +173,7 @@ int nfc_create(const nfc_params *p, nfc_ctx **out) {
     if (const char *e = NFC_ENV("NFC_LEAN_GFAC")) c->lean_gfac = (float)atof(e);
     if (const char *e = NFC_ENV("NFC_LEAN_GMIN")) c->lean_gmin = (float)atof(e);
     if (const char *e = NFC_ENV("NFC_OWN_PREFIX_MAX")) c->own_prefix_max = (uint32_t)strtoul(e, nullptr, 10);
+    if (const char *e = NFC_ENV("NFC_EDGE_PREFIX")) c->edge_prefix = atoi(e) != 0;   // 0 / 1: the edge writer always scans its tile itself / never does (edges.hip.h: EdgeRec)
     if (const char *e = NFC_ENV("NFC_DEC_SPEC")) c->dec_spec = atoi(e) != 0;
     if (const char *e = NFC_ENV("NFC_SPIN_WAIT")) c->spin_wait = atoi(e) != 0;
     if (const char *e = NFC_ENV("NFC_WG_ROWBAL")) {   // 0: chunks of equal length (host_threshold.h: the cut by dispatch row); a,b,c: the rows' factors
@@ -459,7 +460,7 @@ void nfc_destroy(nfc_ctx *c) {
                      &c->d_touched[1], &c->d_info[0], &c->d_info[1], &c->d_ver, &c->d_cflags, &c->d_list, &c->d_ecode, &c->d_epos, &c->d_eidx, &c->d_states, &c->d_sym[0], &c->d_sym[1],
                      &c->d_bits[0], &c->d_bits[1], &c->d_pending[0][0], &c->d_pending[0][1],
                      &c->d_pending[1][0], &c->d_pending[1][1], &c->d_partials2, &c->d_close_end[0], &c->d_close_end[1], &c->d_close_idx[0], &c->d_close_idx[1],
-                     &c->d_partials, &c->d_aggs, &c->d_faggs, &c->d_spec, &c->d_stage_bits[0], &c->d_stage_bits[1], &c->d_stage_cb[0], &c->d_stage_cb[1], &c->d_stage_ci[0], &c->d_stage_ci[1], &c->d_stage_q[0], &c->d_stage_q[1], &c->d_stage_own, &c->d_gring, &c->d_pack, &c->d_gvtop, &c->d_seqout, &c->d_tail_st, &c->d_tail_ticket, &c->d_bits_alt[0], &c->d_bits_alt[1],
+                     &c->d_partials, &c->d_edge_rec, &c->d_aggs, &c->d_faggs, &c->d_spec, &c->d_stage_bits[0], &c->d_stage_bits[1], &c->d_stage_cb[0], &c->d_stage_cb[1], &c->d_stage_ci[0], &c->d_stage_ci[1], &c->d_stage_q[0], &c->d_stage_q[1], &c->d_stage_own, &c->d_gring, &c->d_pack, &c->d_gvtop, &c->d_seqout, &c->d_tail_st, &c->d_tail_ticket, &c->d_bits_alt[0], &c->d_bits_alt[1],
                      &c->d_fr_rec[0], &c->d_fr_rec[1], &c->d_fr_bytes[0], &c->d_fr_bytes[1], &c->d_fr_par[0], &c->d_fr_par[1], &c->d_fr_tot};
     for (DevBuf *b : all) b->release();
     for (auto &e : c->fr_ev)
