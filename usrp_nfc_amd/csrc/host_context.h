@@ -1,5 +1,8 @@
-// host_context.h -- the context (nfc_ctx), the mirrored state block, launch helpers
+// host_context.h -- the test build's switches (Switches, read_switches), the context (nfc_ctx), the mirrored state block, launch helpers
 // (part of nfc_amd.hip: included there, in this order, into one translation unit)
+// Who owns what: every HIP resource of a context -- device and pinned buffers, events, its two streams -- is a member of nfc_ctx of one of
+// dev_buf.h's owning types, so `delete c` is the whole release (nfc_destroy waits for the streams first) and a context that nfc_create could
+// not finish releases what it had got.  A buffer added to the struct needs no second mention anywhere.
 #pragma once
 
 
@@ -57,6 +60,60 @@ constexpr size_t AHEAD_LDS_MAX = 96 * 1024;
 constexpr int NRING = 4;   // window buffers: the carried one + one per batch that may be in flight (they rotate)
 constexpr int NSUB = 3;    // batches that may be submitted and not yet waited for
 
+namespace {
+// The PRODUCT build reads no environment variable: which kernels a deployed process runs does not depend on what it inherited.
+// Every switch below -- the ones that make a context misbehave on purpose or talk, and the ones that select between kernel
+// forms that are all exact (the A/Bs of DESIGN.md, the tests that keep the less travelled forms exact) -- exists in the TEST
+// build only (-DNFC_TEST_HOOKS: usrp_nfc_amd/libnfc_amd_hooks.so, build.py), and is read here, once per nfc_create (NFC_REC_NT: per call of
+// nfc_record_pcm16_device).  README.md lists them.  A value is unset or what the variable parsed to; nfc_create clamps and applies it.
+struct Switches {
+    std::optional<std::string> debug_clk;
+    std::optional<int> no_small, debug_bad_launch, debug_redo_submitted, debug, trace, trace_alloc, no_submit_ahead, tail, wg, wg_rounds, wg_bulk, wg_rerun, wg_rowbal, wg_nr, wg_flags, wg_per_cu, wg_per_cu_ahead, wg_ex, lean, lean_rounds,
+        lean_waves, edge_prefix, dec_spec, dec_runin, spin_wait, chunk_adapt, chunk_mult;
+    std::optional<double> lean_gfac, lean_gmin, eps;
+    std::optional<unsigned long> own_prefix_max;
+    std::optional<std::pair<int, int>> wg_lone;        // max,div
+    std::optional<std::array<double, 3>> rowbal_f;     // NFC_WG_ROWBAL=a,b,c: the rows' factors (anything else: wg_rowbal, 0 / 1)
+    std::optional<bool> ring_global;                   // NFC_RING=global / lds
+};
+inline Switches read_switches() {
+    Switches s;
+#ifdef NFC_TEST_HOOKS
+    const struct { const char *name; std::optional<int> Switches::*at; } ints[] = {
+        {"NFC_NO_SMALL", &Switches::no_small}, {"NFC_DEBUG_BAD_LAUNCH", &Switches::debug_bad_launch}, {"NFC_DEBUG_REDO_SUBMITTED", &Switches::debug_redo_submitted},
+        {"NFC_DEBUG", &Switches::debug}, {"NFC_TRACE", &Switches::trace}, {"NFC_TRACE_ALLOC", &Switches::trace_alloc}, {"NFC_NO_SUBMIT_AHEAD", &Switches::no_submit_ahead},
+        {"NFC_TAIL", &Switches::tail}, {"NFC_WG", &Switches::wg}, {"NFC_WG_ROUNDS", &Switches::wg_rounds}, {"NFC_WG_BULK", &Switches::wg_bulk},
+        {"NFC_WG_RERUN", &Switches::wg_rerun}, {"NFC_WG_NR", &Switches::wg_nr}, {"NFC_WG_FLAGS", &Switches::wg_flags}, {"NFC_WG_PER_CU", &Switches::wg_per_cu},
+        {"NFC_WG_PER_CU_AHEAD", &Switches::wg_per_cu_ahead}, {"NFC_WG_EX", &Switches::wg_ex}, {"NFC_LEAN", &Switches::lean}, {"NFC_LEAN_ROUNDS", &Switches::lean_rounds},
+        {"NFC_LEAN_WAVES", &Switches::lean_waves}, {"NFC_EDGE_PREFIX", &Switches::edge_prefix}, {"NFC_DEC_SPEC", &Switches::dec_spec}, {"NFC_DEC_RUNIN", &Switches::dec_runin},
+        {"NFC_SPIN_WAIT", &Switches::spin_wait}, {"NFC_CHUNK_ADAPT", &Switches::chunk_adapt}, {"NFC_CHUNK_MULT", &Switches::chunk_mult}};
+    const struct { const char *name; std::optional<double> Switches::*at; } reals[] = {
+        {"NFC_LEAN_GFAC", &Switches::lean_gfac}, {"NFC_LEAN_GMIN", &Switches::lean_gmin}, {"NFC_EPS", &Switches::eps}};
+    for (const auto &v : ints)
+        if (const char *e = getenv(v.name)) s.*v.at = atoi(e);
+    for (const auto &v : reals)
+        if (const char *e = getenv(v.name)) s.*v.at = atof(e);
+    if (const char *e = getenv("NFC_DEBUG_CLK")) s.debug_clk = e;
+    if (const char *e = getenv("NFC_OWN_PREFIX_MAX")) s.own_prefix_max = strtoul(e, nullptr, 10);
+    if (const char *e = getenv("NFC_WG_LONE")) {
+        int a = 4, b = 64;
+        if (sscanf(e, "%d,%d", &a, &b) >= 1) s.wg_lone = std::make_pair(a, b);
+    }
+    if (const char *e = getenv("NFC_WG_ROWBAL")) {   // 0: chunks of equal length (host_threshold.h: the cut by dispatch row); a,b,c: the rows' factors
+        std::array<double, 3> f{0.0, 1.0, 1.0};
+        if (sscanf(e, "%lf,%lf,%lf", &f[0], &f[1], &f[2]) >= 2 && f[0] > 0.5 && f[0] < 1.5 && f[1] > 0.5 && f[1] < 1.5 && f[2] > 0.5 && f[2] < 1.5)
+            s.rowbal_f = f;
+        else s.wg_rowbal = atoi(e);
+    }
+    if (const char *e = getenv("NFC_RING")) {
+        if (strcmp(e, "global") == 0) s.ring_global = true;
+        else if (strcmp(e, "lds") == 0) s.ring_global = false;
+    }
+#endif
+    return s;
+}
+}  // namespace
+
 struct nfc_ctx {
     nfc_params P;
     const KindKernels *kk = nullptr;   // the threshold-stage kernels of P.input_kind (kind_kernels.h)
@@ -98,7 +155,6 @@ struct nfc_ctx {
     float lean_gfac = 1.3f, lean_gmin = 9.765625e-4f;   // drift allowance of the next superstep: max(gfac * B, gmin * ss)
     int gring = 0;   // this batch: the ring of a chunk in global memory instead of LDS
     int gring_ok = 0, gring_force = 0, wave_slots_g = 0;   // long windows qualify (NFC_RING=lds|global overrides the choice)
-    DevBuf d_gring;
     uint32_t own_prefix_max = OWN_PREFIX_MAX_TILES;   // tile counts up to this need no prefix launches (NFC_OWN_PREFIX_MAX overrides)
     int use_small = 1;   // short batches take the one-launch edge / decode / framing kernel (NFC_NO_SMALL=1 turns it off)
     double expect_ms = 0.3;   // how long the stamp of a batch has taken to appear lately (wait_for_stamp)
@@ -108,9 +164,12 @@ struct nfc_ctx {
     float i16_scale;         // the kernels' conversion argument: the int16 kinds' scale, -1 for sample / 32767 (i16_to_float); the complex 8-bit
                              // kinds' route and scale (iq8_kernel_arg, threshold.hip.h: iq8_env)
     size_t in_bytes_per_sample;
-    hipStream_t st = nullptr;
-    hipStream_t own_st = nullptr;   // the stream the context created (st may be the caller's: nfc_set_stream)
-    hipEvent_t ev[8] = {};
+    // (the streams come before every buffer and event of the context: members go in reverse order, so a stream outlives what was enqueued on it)
+    hipStream_t st = nullptr;   // the stream in use: own_st, st_a for a batch submitted ahead, or the caller's (nfc_set_stream) -- not owned
+    Stream own_st;              // the stream the context created
+    Stream st_a;                // a submitted batch's threshold stage runs here (host_submit.h)
+    Event ev[8];
+    DevBuf d_gring;
     bool state_dirty = false, dirty_fill_ring = false;   // host-side carried values not yet on the device (push_state)
     float dirty_fill = 0.f;
     Carry dirty_carry;
@@ -118,12 +177,12 @@ struct nfc_ctx {
     DecCarry dirty_dcarry;
     bool cert_pending = false;   // the first certification waits to share a launch with the edge stage (k_certify_and_count)
     CertLaunch cert;
-    // debugging switches, read ONCE in nfc_create (an inherited environment must not reach the per-launch path)
+    // debugging switches, read ONCE for nfc_create (read_switches: an inherited environment must not reach the per-launch path)
     bool dbg_bad_launch = false, dbg_redo_submitted = false, dbg_no_submit_ahead = false, dbg_any = false, dbg_clk = false, dbg_trace = false;
     std::string dbg_clk_path;
     uint32_t batch_seq = 0;   // stamped into the state block by every batch's first kernel, checked in the mirror
     int timing = 0;   // 0: no events, 1: the threshold kernels' own start / stop events, 2: + batch total and stages as stream markers (nfc_set_timing)
-    hipEvent_t kev[2 * 6] = {};  // start/stop pairs around the first k_threshold launches of a batch
+    Event kev[2 * 6];  // start/stop pairs around the first k_threshold launches of a batch
     int n_kev = 0;
     std::string err;
     LaunchError launch_err;   // the first launch of the batch in work that the runtime rejected (launch_check.h)
@@ -136,27 +195,25 @@ struct nfc_ctx {
     // carried state
     DevBuf d_state, d_ring[NRING];   // the window: the carried one, the one the batch in work writes, and -- with batches submitted
                                      // ahead (nfc_submit_device) -- the ones THOSE write; they rotate
-    DevState *hs = nullptr;        // pinned host mirror of d_state
+    // pinned host mirror of d_state (mapped AND coherent, explicitly: the host watches the stamp word while the stream runs -- host_threshold.h:
+    // wait_for_stamp); hs is the block of hs_pin as what it holds
+    PinBuf hs_pin{hipHostMallocMapped | hipHostMallocCoherent};
+    DevState *hs = nullptr;
     void *hs_dev = nullptr;        // the same memory as the device addresses it (kernels may fill the mirror themselves)
-    uint8_t *h_stage = nullptr;    // pinned staging for nfc_get_state
-    size_t h_stage_cap = 0;
-    uint8_t *h_pk_stage = nullptr;     // pinned staging for the packet tables (build_packets)
-    size_t h_pk_stage_cap = 0;
-    uint8_t *h_edge_stage = nullptr;   // pinned staging for nfc_read_edges / nfc_read_edges_compact (two pieces)
-    size_t h_edge_stage_cap = 0;
+    PinBuf h_stage;                // pinned staging for nfc_get_state
+    PinBuf h_pk_stage;             // pinned staging for the packet tables (pk_stage)
+    PinBuf h_edge_stage;           // pinned staging for nfc_read_edges / nfc_read_edges_compact (two pieces)
     std::vector<uint64_t> edge_lut;    // per LUT row: the (d, v) half of an nfc_edge record
-    uint8_t *h_cflags = nullptr;   // pinned mirror of the per-chunk flag sections
-    size_t h_cflags_cap = 0;
+    PinBuf h_cflags;               // pinned mirror of the per-chunk flag sections
     int ring_cur = 0;
     // ---- a batch submitted ahead (nfc_submit_device / nfc_wait): its threshold stage runs on st_a beside the edge and
     // decode stages of the batch before it on st
-    hipStream_t st_a = nullptr;
     DevBuf d_neg_alt[NSUB - 1], d_pos_alt[NSUB - 1];   // planes of the batches whose edge stage is not enqueued yet (a set becomes
                                                        // d_neg / d_pos then, and the retired set takes its place in the pool)
     uint32_t alt_free = (1u << (NSUB - 1)) - 1u;       // which of them are free
-    DevState *hs_a[NSUB] = {};                 // pinned snapshots of the state block taken right after a submitted batch's certification
-    hipEvent_t ev_a[NSUB] = {}, ev_b[NSUB] = {};   // its threshold stage / its last stage done
-    hipEvent_t kev_sub[NSUB][2] = {};          // start / stop of its threshold kernel (nfc_set_timing >= 1)
+    PinBuf hs_a[NSUB];                         // pinned snapshots of the state block taken right after a submitted batch's certification
+    Event ev_a[NSUB], ev_b[NSUB];              // its threshold stage / its last stage done
+    Event kev_sub[NSUB][2];                    // start / stop of its threshold kernel (nfc_set_timing >= 1)
     struct Submitted {
         const void *d_in = nullptr;
         uint32_t n = 0, seq = 0, nch = 0, chunk = 0;
@@ -239,7 +296,7 @@ struct nfc_ctx {
     DevBuf d_fr_rec[2], d_fr_bytes[2], d_fr_par[2], d_fr_tot;
     bool frames_ready = false;
     uint64_t fr_frames[2] = {0, 0}, fr_bytes[2] = {0, 0};
-    hipEvent_t fr_ev[2] = {};   // around the two launches (nfc_set_timing >= 1)
+    Event fr_ev[2];   // around the two launches (nfc_set_timing >= 1)
     float fr_ms = 0.f;
 };
 
@@ -395,9 +452,9 @@ void launch_lean(nfc_ctx *c, const ThrArgs &A, uint32_t nwork, hipEvent_t e0, hi
     if (e0) NFC_LAUNCH_EXT(kern, dim3(blocks), dim3(64 * wpb), lds, c->st, e0, e1, 0, A);
     else NFC_LAUNCH(kern, dim3(blocks), dim3(64 * wpb), lds, c->st, A);
 }
-void launch_threshold_kind(nfc_ctx *c, const ThrArgs &A, uint32_t nwork, bool lean = false, hipEvent_t *own_events = nullptr) {
+void launch_threshold_kind(nfc_ctx *c, const ThrArgs &A, uint32_t nwork, bool lean = false, const Event *own_events = nullptr) {
     const bool timed = !own_events && c->timing >= 1 && c->n_kev < 6;
-    hipEvent_t e0 = timed ? c->kev[2 * c->n_kev] : nullptr, e1 = timed ? c->kev[2 * c->n_kev + 1] : nullptr;
+    hipEvent_t e0 = timed ? (hipEvent_t)c->kev[2 * c->n_kev] : nullptr, e1 = timed ? (hipEvent_t)c->kev[2 * c->n_kev + 1] : nullptr;
     if (timed) c->n_kev++;
     if (own_events) {
         e0 = own_events[0];

@@ -73,7 +73,7 @@ int enqueue_threshold_ahead(nfc_ctx *c, nfc_ctx::Submitted &b) {
     A.ver_zero = 1;   // (pass 0 only: every summary is in buffer 0)
     NFC_LAUNCH(k_certify, dim3(cert_grid(np)), dim3(256), 0, c->st, A, P.d_cert, (CertInfo *)nullptr,
                c->d_ring[(b.ring_in + 1) % NRING].as<float>(), dC(c), A.sum);
-    hipError_t e = hipMemcpyAsync(c->hs_a[b.slot], c->d_state.p, sizeof(DevState), hipMemcpyDeviceToHost, c->st);
+    hipError_t e = hipMemcpyAsync(c->hs_a[b.slot].p, c->d_state.p, sizeof(DevState), hipMemcpyDeviceToHost, c->st);
     if (e == hipSuccess) e = hipEventRecord(c->ev_a[b.slot], c->st);
     c->st = keep;
     if (e != hipSuccess) return fail(c, NFC_ERR_DEVICE, "submitting the threshold stage failed: %s", hipGetErrorString(e));
@@ -247,7 +247,7 @@ int wait_batch(nfc_ctx *c) {
             return fail(c, NFC_ERR_DEVICE, "kernel launch failed: %s (%s:%d)", hipGetErrorString(e.err), e.file, e.line);
         }
     }
-    const DevState *sa = c->hs_a[b.slot];
+    const DevState *sa = c->hs_a[b.slot].as<DevState>();
     if (sa->seq[0] != b.seq || c->hs->seq[1] != b.seq) {
         abandon();
         return fail(c, NFC_ERR_DEVICE, "state mirror is stale (batch %u, mirrors %u / %u): a kernel of this batch did not run", b.seq, sa->seq[0], c->hs->seq[1]);
@@ -350,6 +350,14 @@ int wait_batch(nfc_ctx *c) {
     return restart_submitted(c);
 }
 
+// the pinned staging area the packet tables, the packed bits and the frames go through, at least `need` bytes
+int pk_stage(nfc_ctx *c, size_t need) {
+    if (c->h_pk_stage.cap >= need) return NFC_OK;
+    devbuf_allocs()++;   // (a pinned regrow costs what a device one does: nfc_stats.device_allocs counts both)
+    HIPCHK(c, c->h_pk_stage.ensure(need + need / 2 + 65536));
+    return NFC_OK;
+}
+
 int build_packets(nfc_ctx *c, int t) {
     if (c->pk_ready[t]) return NFC_OK;
     c->pk[t].clear();
@@ -358,18 +366,9 @@ int build_packets(nfc_ctx *c, int t) {
     if (nc) {
         // (through pinned staging: two copies of a few tens of KB into pageable vectors took 1.4 ms per batch -- the runtime stages
         // those itself, synchronously -- and were most of what `end_to_end` spent per piece: round 5)
-        const size_t need = (size_t)nc * 12 + 64;
-        if (c->h_pk_stage_cap < need) {
-            devbuf_allocs()++;   // (a pinned regrow costs what a device one does: nfc_stats.device_allocs counts both)
-            if (c->h_pk_stage) (void)hipHostFree(c->h_pk_stage);
-            c->h_pk_stage = nullptr;
-            c->h_pk_stage_cap = 0;
-            const size_t cap = need + need / 2 + 65536;
-            HIPCHK(c, hipHostMalloc((void **)&c->h_pk_stage, cap, hipHostMallocDefault));
-            c->h_pk_stage_cap = cap;
-        }
-        uint64_t *idx = (uint64_t *)c->h_pk_stage;
-        uint32_t *ends = (uint32_t *)(c->h_pk_stage + (size_t)nc * 8);
+        if (int rc = pk_stage(c, (size_t)nc * 12 + 64)) return rc;
+        uint64_t *idx = c->h_pk_stage.as<uint64_t>();
+        uint32_t *ends = (uint32_t *)(c->h_pk_stage.as<uint8_t>() + (size_t)nc * 8);
         HIPCHK(c, hipMemcpyAsync(idx, c->d_close_idx[t].p, (size_t)nc * 8, hipMemcpyDeviceToHost, c->st));
         HIPCHK(c, hipMemcpyAsync(ends, c->d_close_end[t].p, (size_t)nc * 4, hipMemcpyDeviceToHost, c->st));
         HIPCHK(c, hipStreamSynchronize(c->st));

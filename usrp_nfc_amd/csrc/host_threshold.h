@@ -179,18 +179,16 @@ static int thr_prepare(nfc_ctx *c, const void *d_in, uint32_t n, uint32_t n_all,
     HIPCHK(c, c->d_meta.ensure(nal * sizeof(RunMeta)));
     HIPCHK(c, c->d_ver.ensure(nal));
     HIPCHK(c, c->d_cflags.ensure((size_t)4 * nal));   // sections: cert | gflags | gmin | gmax
-    if (c->h_cflags_cap < (size_t)20 * nal + 64) {
+    if (c->h_cflags.cap < (size_t)20 * nal + 64) {
         devbuf_allocs()++;
-        if (c->h_cflags) (void)hipHostFree(c->h_cflags);
-        c->h_cflags_cap = (size_t)20 * nal + 4096;
-        HIPCHK(c, hipHostMalloc((void **)&c->h_cflags, c->h_cflags_cap, hipHostMallocDefault));
+        HIPCHK(c, c->h_cflags.ensure((size_t)20 * nal + 4096));
     }
+    uint8_t *const h_flags = c->h_cflags.as<uint8_t>();
     uint8_t *d_cert = c->d_cflags.as<uint8_t>(), *d_gflags = d_cert + nch, *d_gmin = d_cert + 2 * (size_t)nch,
             *d_gmax = d_cert + 3 * (size_t)nch;
-    const uint8_t *h_cert = c->h_cflags, *h_gflags = c->h_cflags + nch, *h_gmin = c->h_cflags + 2 * (size_t)nch,
-                  *h_gmax = c->h_cflags + 3 * (size_t)nch;
+    const uint8_t *h_cert = h_flags, *h_gflags = h_flags + nch, *h_gmin = h_flags + 2 * (size_t)nch, *h_gmax = h_flags + 3 * (size_t)nch;
     {
-        uint8_t *q = c->h_cflags + (((size_t)4 * nch + 15) & ~(size_t)15);
+        uint8_t *q = h_flags + (((size_t)4 * nch + 15) & ~(size_t)15);
         P.h_gvtop = (uint32_t *)q;
         P.h_list_a = (uint32_t *)(q + (size_t)4 * nch);
         P.h_list_b = (uint32_t *)(q + (size_t)8 * nch);
@@ -432,7 +430,7 @@ static int threshold_span(nfc_ctx *c, const void *d_in_all, uint32_t n_all, uint
                 // (a stream whose batches have needed re-runs: the first round's flags travel with its verdict too -- one host turn less)
                 flags_with_verdict = first_round && c->fine_left > 0;
                 if (!first_round || flags_with_verdict) {   // (the flags, and the chunks' sum bounds for the exactness guard: all in the round's one host turn)
-                    HIPCHK(c, hipMemcpyAsync(c->h_cflags, c->d_cflags.p, (size_t)4 * nch, hipMemcpyDeviceToHost, c->st));
+                    HIPCHK(c, hipMemcpyAsync(c->h_cflags.p, c->d_cflags.p, (size_t)4 * nch, hipMemcpyDeviceToHost, c->st));
                     HIPCHK(c, hipMemcpyAsync(P.h_gvtop, c->d_gvtop.p, (size_t)nch * 4, hipMemcpyDeviceToHost, c->st));
                 }
                 HIPCHK(c, mirror_async(c));
@@ -462,7 +460,7 @@ static int threshold_span(nfc_ctx *c, const void *d_in_all, uint32_t n_all, uint
                     A.ver_zero = 0;
                     return NFC_OK;
                 }
-                if (!flags_with_verdict) HIPCHK(c, hipMemcpy(c->h_cflags, c->d_cflags.p, (size_t)4 * nch, hipMemcpyDeviceToHost));
+                if (!flags_with_verdict) HIPCHK(c, hipMemcpy(c->h_cflags.p, c->d_cflags.p, (size_t)4 * nch, hipMemcpyDeviceToHost));
             }
             if (first_round && lean && !h_cert[0]) failing.push_back(0);   // chunk 0 gave up: re-run from the carried state
             for (uint32_t k : c->h_list)
@@ -617,7 +615,7 @@ static int threshold_span(nfc_ctx *c, const void *d_in_all, uint32_t n_all, uint
             vtop = summary.vtop;
         } else {
             if (first_round) {   // (no round of re-runs has fetched them: the debugging path)
-                HIPCHK(c, hipMemcpyAsync(c->h_cflags, c->d_cflags.p, (size_t)4 * nch, hipMemcpyDeviceToHost, c->st));
+                HIPCHK(c, hipMemcpyAsync(c->h_cflags.p, c->d_cflags.p, (size_t)4 * nch, hipMemcpyDeviceToHost, c->st));
                 HIPCHK(c, hipMemcpyAsync(P.h_gvtop, c->d_gvtop.p, (size_t)nch * 4, hipMemcpyDeviceToHost, c->st));
                 HIPCHK(c, mirror_async(c));
                 HIPCHK(c, hipStreamSynchronize(c->st));

@@ -15,7 +15,7 @@
 // encoders of tx.hip.h; its renderer (row f4) is a kernel of its own outside the batch.
 //
 // The host side in parts, included below into this one translation unit:
-//   host_context.h    nfc_ctx, the mirrored state block, launch helpers
+//   host_context.h    the test build's switches, nfc_ctx (every HIP resource a member that releases itself: dev_buf.h), the mirrored state block, launch helpers
 //   host_threshold.h  the threshold stage: plan, pass 0, certification rounds, re-runs, sequential fallback
 //   host_stages.h     edge stage, decode + framing stage, short batches in one launch, process_batch
 //   host_submit.h     batches submitted ahead (nfc_submit_device / nfc_wait)
@@ -33,7 +33,10 @@
 #include <cstring>
 #include <string>
 #include <thread>
+#include <array>
 #include <functional>
+#include <memory>
+#include <optional>
 #include <vector>
 
 #include "../../include/nfc_amd.h"
@@ -82,48 +85,30 @@ const KindKernels &kind_kernels(int kind) {
         }
     });
 }
-}  // namespace
 
-extern "C" {
+// ---- nfc_create in steps.  One that fails leaves its message (fail) and returns the status; the half-built context releases itself ----
+#define CRT(call)                                                                                                  \
+    do {                                                                                                           \
+        hipError_t e__ = (call);                                                                                   \
+        if (e__ != hipSuccess) return fail(nullptr, NFC_ERR_DEVICE, "%s failed: %s", #call, hipGetErrorString(e__)); \
+    } while (0)
 
-int nfc_abi_version(void) { return NFC_AMD_ABI_VERSION; }
-
-int nfc_plan_row_cut(uint32_t n, uint32_t C, uint32_t rs, uint32_t cus, uint32_t rows, const double *factors, uint32_t max_len, uint32_t out[10]) {
-    if (!out || !rs || !C || !cus || (rows >= 2 && !factors)) return NFC_ERR_ARG;
-    const RowCut t = (rows >= 2 && rows <= 4) ? plan_row_cut(n, C, rs, cus, rows, factors, max_len) : equal_cut(n, C, cus);
-    for (int r = 0; r < 4; r++) {
-        out[r] = t.row_len[r];
-        out[4 + r] = t.row_start[r];
-    }
-    out[8] = t.row_div;
-    out[9] = t.nch;
-    return t.by_row ? 1 : 0;
-}
-
-int nfc_device_count(void) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
-}
-
-const char *nfc_last_error(const nfc_ctx *ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
-
-int nfc_create(const nfc_params *p, nfc_ctx **out) {
-    if (!p || !out) return fail(nullptr, NFC_ERR_ARG, "null argument");
-    *out = nullptr;
+int create_check_args(const nfc_params *p, float *scale_arg) {
     if (!(p->samp_rate > 0)) return fail(nullptr, NFC_ERR_ARG, "samp_rate must be positive");
     if (p->av_window < 1 || p->av_window > 30000) return fail(nullptr, NFC_ERR_ARG, "av_window must be in [1, 30000]");
     if (p->max_len < 1 || p->max_len > 4000) return fail(nullptr, NFC_ERR_ARG, "max_len must be in [1, 4000]");
     if (!kind_valid(p->input_kind)) return fail(nullptr, NFC_ERR_ARG, "unknown input_kind");
-    float scale_arg = 0.f;
-    if (const char *bad = kernel_scale_arg(p->input_kind, p->i16_scale, &scale_arg)) return fail(nullptr, NFC_ERR_ARG, "%s", bad);
+    if (const char *bad = kernel_scale_arg(p->input_kind, p->i16_scale, scale_arg)) return fail(nullptr, NFC_ERR_ARG, "%s", bad);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(nullptr, NFC_ERR_DEVICE, "no HIP device: this library has no CPU fallback");
     if (p->device < 0 || p->device >= ndev) return fail(nullptr, NFC_ERR_ARG, "device %d out of range (%d devices)", p->device, ndev);
     if (hipSetDevice(p->device) != hipSuccess) return fail(nullptr, NFC_ERR_DEVICE, "hipSetDevice failed");
+    return NFC_OK;
+}
 
-    nfc_ctx *c = new nfc_ctx();
+// what follows from the parameters and the switches alone
+int create_plan_params(nfc_ctx *c, const nfc_params *p, const Switches &sw, float scale_arg) {
     c->P = *p;
     c->kk = &kind_kernels(p->input_kind);
     c->L = p->av_window;
@@ -135,58 +120,36 @@ int nfc_create(const nfc_params *p, nfc_ctx **out) {
     C = std::max(C, 2 * c->L);
     C = std::max(C, c->mx + 2);
     c->rows_per_step = 4;
-    // The PRODUCT build reads no environment variable: which kernels a deployed process runs does not depend on what it inherited.
-    // Every switch below -- the ones that make a context misbehave on purpose or talk, and the ones that select between kernel
-    // forms that are all exact (the A/Bs of DESIGN.md, the tests that keep the less travelled forms exact) -- exists in the TEST
-    // build only (-DNFC_TEST_HOOKS: usrp_nfc_amd/libnfc_amd_hooks.so, build.py), and is read here, once.  README.md lists them.
-#ifdef NFC_TEST_HOOKS
-#define NFC_ENV(name) getenv(name)
-#else
-#define NFC_ENV(name) ((const char *)nullptr)
-#endif
-    c->use_small = NFC_ENV("NFC_NO_SMALL") ? 0 : 1;
-#ifdef NFC_TEST_HOOKS
-    if (const char *e = getenv("NFC_TAIL")) c->tail_on = atoi(e) != 0;   // 1: the fused tail (tail.hip.h) instead of the five launches
-    c->dbg_bad_launch = getenv("NFC_DEBUG_BAD_LAUNCH") != nullptr;
-    c->dbg_redo_submitted = getenv("NFC_DEBUG_REDO_SUBMITTED") != nullptr;
-    c->dbg_any = getenv("NFC_DEBUG") != nullptr;
-    c->dbg_trace = getenv("NFC_TRACE") != nullptr;
-    devbuf_trace() = getenv("NFC_TRACE_ALLOC") != nullptr;
-    if (const char *e = getenv("NFC_DEBUG_CLK")) {
+    c->use_small = sw.no_small ? 0 : 1;   // (the first seven: set by being there, whatever the value)
+    if (sw.tail) c->tail_on = *sw.tail != 0;
+    c->dbg_bad_launch = sw.debug_bad_launch.has_value();
+    c->dbg_redo_submitted = sw.debug_redo_submitted.has_value();
+    c->dbg_any = sw.debug.has_value();
+    c->dbg_trace = sw.trace.has_value();
+    devbuf_trace() = sw.trace_alloc.has_value();
+    if (sw.debug_clk) {
         c->dbg_clk = true;
-        c->dbg_clk_path = e;
+        c->dbg_clk_path = *sw.debug_clk;
     }
-#endif
-    c->dbg_no_submit_ahead = NFC_ENV("NFC_NO_SUBMIT_AHEAD") != nullptr;
-    if (const char *e = NFC_ENV("NFC_WG")) c->wg = atoi(e) != 0;
-    if (const char *e = NFC_ENV("NFC_WG_ROUNDS")) c->wg_rounds = std::max(1, atoi(e));
-    if (const char *e = NFC_ENV("NFC_WG_BULK")) c->wg_bulk = atoi(e) != 0;
-    if (const char *e = NFC_ENV("NFC_WG_RERUN")) c->wg_rerun_lone = atoi(e) != 0;   // 0: lone failures are k_threshold's too (with NFC_WG_EX=0: it re-runs everything)
-    if (const char *e = NFC_ENV("NFC_WG_LONE")) {   // max,div
-        int a = 4, b = 64;
-        if (sscanf(e, "%d,%d", &a, &b) >= 1) c->wg_lone_max = std::max(0, a), c->wg_lone_div = std::max(1, b);
-    }
-    if (const char *e = NFC_ENV("NFC_LEAN")) c->lean = atoi(e) != 0;
-    c->lean_k = 0;        // chosen below from the occupancy the LDS ring allows, unless set here
+    c->dbg_no_submit_ahead = sw.no_submit_ahead.has_value();
+    if (sw.wg) c->wg = *sw.wg != 0;
+    if (sw.wg_rounds) c->wg_rounds = std::max(1, *sw.wg_rounds);
+    if (sw.wg_bulk) c->wg_bulk = *sw.wg_bulk != 0;
+    if (sw.wg_rerun) c->wg_rerun_lone = *sw.wg_rerun != 0;
+    if (sw.wg_lone) c->wg_lone_max = std::max(0, sw.wg_lone->first), c->wg_lone_div = std::max(1, sw.wg_lone->second);
+    if (sw.lean) c->lean = *sw.lean != 0;
+    c->lean_k = 0;        // chosen in create_plan_device from the occupancy the LDS ring allows
     c->lean_rounds = 0;
-    if (const char *e = NFC_ENV("NFC_LEAN_ROUNDS")) c->lean_rounds = std::max(1, atoi(e));
-    if (const char *e = NFC_ENV("NFC_LEAN_GFAC")) c->lean_gfac = (float)atof(e);
-    if (const char *e = NFC_ENV("NFC_LEAN_GMIN")) c->lean_gmin = (float)atof(e);
-    if (const char *e = NFC_ENV("NFC_OWN_PREFIX_MAX")) c->own_prefix_max = (uint32_t)strtoul(e, nullptr, 10);
-    if (const char *e = NFC_ENV("NFC_EDGE_PREFIX")) c->edge_prefix = atoi(e) != 0;   // 0 / 1: the edge writer always scans its tile itself / never does (edges.hip.h: EdgeRec)
-    if (const char *e = NFC_ENV("NFC_DEC_SPEC")) c->dec_spec = atoi(e) != 0;
-    if (const char *e = NFC_ENV("NFC_SPIN_WAIT")) c->spin_wait = atoi(e) != 0;
-    if (const char *e = NFC_ENV("NFC_WG_ROWBAL")) {   // 0: chunks of equal length (host_threshold.h: the cut by dispatch row); a,b,c: the rows' factors
-        double f[3];
-        f[1] = f[2] = 1.0;
-        if (sscanf(e, "%lf,%lf,%lf", &f[0], &f[1], &f[2]) >= 2 && f[0] > 0.5 && f[0] < 1.5 && f[1] > 0.5 && f[1] < 1.5 && f[2] > 0.5 && f[2] < 1.5)
-            memcpy(c->rowbal_f[0], f, sizeof f), c->rowbal_set = true;
-        else c->wg_rowbal = atoi(e) != 0;
-    }
-    if (const char *e = NFC_ENV("NFC_DEC_RUNIN")) {   // run-in edges per decode tile: 512, 1024 or 2048
-        const int v = atoi(e);
-        c->dec_runin = v >= 2048 ? 8 : (v >= 1024 ? 4 : 2);
-    }
+    if (sw.lean_rounds) c->lean_rounds = std::max(1, *sw.lean_rounds);
+    if (sw.lean_gfac) c->lean_gfac = (float)*sw.lean_gfac;
+    if (sw.lean_gmin) c->lean_gmin = (float)*sw.lean_gmin;
+    if (sw.own_prefix_max) c->own_prefix_max = (uint32_t)*sw.own_prefix_max;
+    if (sw.edge_prefix) c->edge_prefix = *sw.edge_prefix != 0;
+    if (sw.dec_spec) c->dec_spec = *sw.dec_spec != 0;
+    if (sw.spin_wait) c->spin_wait = *sw.spin_wait != 0;
+    if (sw.rowbal_f) memcpy(c->rowbal_f[0], sw.rowbal_f->data(), sizeof c->rowbal_f[0]), c->rowbal_set = true;
+    if (sw.wg_rowbal) c->wg_rowbal = *sw.wg_rowbal != 0;
+    if (sw.dec_runin) c->dec_runin = *sw.dec_runin >= 2048 ? 8 : (*sw.dec_runin >= 1024 ? 4 : 2);
     {
         c->rows_per_step = 4;   // (8-row steps measured slower: 126 VGPRs, four waves per SIMD)
         const int stp = 64 * c->rows_per_step;
@@ -199,9 +162,9 @@ int nfc_create(const nfc_params *p, nfc_ctx **out) {
     // An LDS ring beyond 12 KB leaves a SIMD with fewer than four waves: such windows keep the ring in global memory
     // (a delay line read one step ahead), and the registers set the occupancy again.
     c->gring_ok = (size_t)c->Lpad * c->lds_per_slot > 12 * 1024 && c->L >= 2 * STEP;
-    if (const char *e = NFC_ENV("NFC_RING")) {
-        if (strcmp(e, "global") == 0 && c->L >= 2 * STEP) c->gring_ok = c->gring_force = 1;
-        else if (strcmp(e, "lds") == 0) c->gring_ok = 0;
+    if (sw.ring_global) {
+        if (*sw.ring_global && c->L >= 2 * STEP) c->gring_ok = c->gring_force = 1;
+        else if (!*sw.ring_global) c->gring_ok = 0;
     }
     c->hi_plus = p->hi_val + 0.1;  // transition_sink.py:63
     const double eps = std::ldexp(1.0, -48);
@@ -224,7 +187,7 @@ int nfc_create(const nfc_params *p, nfc_ctx **out) {
         for (int k = 0; k < 64; k += b) c->selmask |= 1ull << k;
     }
     c->eps = 0.01f;  // certification margin of the speculative pass, relative to the window sum
-    if (const char *e = NFC_ENV("NFC_EPS")) c->eps = (float)atof(e);
+    if (sw.eps) c->eps = (float)*sw.eps;
     c->i16_scale = scale_arg;   // (kernel_scale_arg)
     c->in_bytes_per_sample = kind_bytes(p->input_kind);
     memset(&c->h_carry, 0, sizeof c->h_carry);
@@ -234,149 +197,136 @@ int nfc_create(const nfc_params *p, nfc_ctx **out) {
     c->h_dcarry.mil_state = 0;             // stage BEGINNING, not started, prev 0 (miller.py:22,29)
     c->h_dcarry.man_state = (0 + 1) << 1;  // prev_set False, prev 0 (manchester.py:22-25)
     memset(&c->stats, 0, sizeof c->stats);
+    return NFC_OK;
+}
 
-#define CRT(call)                                                                                      \
-    do {                                                                                               \
-        hipError_t e__ = (call);                                                                       \
-        if (e__ != hipSuccess) {                                                                       \
-            int rc__ = fail(nullptr, NFC_ERR_DEVICE, "%s failed: %s", #call, hipGetErrorString(e__));   \
-            nfc_destroy(c);                                                                            \
-            return rc__;                                                                               \
-        }                                                                                              \
-    } while (0)
-    {
-        hipDeviceProp_t prop;
-        CRT(hipGetDeviceProperties(&prop, p->device));
-        const size_t lds_wave = (size_t)c->Lpad * c->lds_per_slot;
-        int per_cu = (int)std::min<size_t>(20, (size_t)(160 * 1024) / (lds_wave * c->wpb) * c->wpb);   // LDS- and VGPR-bound
-        c->n_cus = std::max(1, prop.multiProcessorCount);
-        c->wave_slots = std::max(1, prop.multiProcessorCount * std::max(1, per_cu));
-        // lean kernel: four steps ahead (104 registers: at most four waves per SIMD); a superstep long enough that its fixed cost
-        // fades -- the drift allowance grows with its length relative to the window (about half the window at most: beyond, the
-        // widened bands reach the loaded half bits of tag frames)
-        // Measured (configs[1] / [2], 1e8 samples): two waves per SIMD with four steps ahead beat five waves with three --
-        // 0.206 / 0.196 ms against 0.237 / 0.230 on the same box: a chunk's fixed cost (the window before it read and
-        // summarised, its summary written) is paid half as often, and two waves already keep a SIMD's issue slots busy.
-        if (!c->lean_k) c->lean_k = 4;
-        c->lean_slots = std::min(c->wave_slots, prop.multiProcessorCount * 8);
-        if (const char *e = NFC_ENV("NFC_LEAN_WAVES")) c->lean_slots = std::min(c->wave_slots, prop.multiProcessorCount * 4 * std::max(1, atoi(e)));
-        if (!c->lean_rounds) c->lean_rounds = std::max(1, (int)(0.4 * c->L / (256.0 * c->lean_k)));
-        c->wave_slots_g = prop.multiProcessorCount * 20;   // VGPR-bound: five waves per SIMD
-        // LDS the lean kernel's resident waves hold per CU: a batch is only run ahead of its predecessor's edge / decode stages
-        // (nfc_submit_device) while those stages' workgroups (25 KB each) still fit beside it
-        c->lean_lds_per_cu = (size_t)((c->lean_slots + prop.multiProcessorCount - 1) / prop.multiProcessorCount) * lds_wave;
-        c->ahead_lds_per_cu = c->lean_lds_per_cu;
-        // the workgroup kernel: one chunk per 256-thread workgroup, as many resident per CU as LDS and registers admit
-        c->wg_lds_base = (size_t)c->Lpad * 4 + WG_SHARED_BYTES;
-        // rows per step: eight where that leaves a superstep of at least two rounds within 0.8 windows (measured: at av_window 10000
-        // eight rows gain 2 % over four; at 2000 more rows with one-round supersteps lose to four rows with two), else four; a round
-        // (four steps) must fit the window, max_len must lie within one step.  Eight rows are instantiated for fc32, sc16, sc8 and cu8 IQ
-        // and the float32 envelope -- what a capture at a rate that wants such a window arrives as (kind_kernels.h: has_nr8).
-        const bool nr8_kind = c->kk->wg[1] != nullptr;
-        c->wg_nr = (nr8_kind && 0.8 * c->L / (double)wg_round_samples(8) >= 1.5) ? 8 : 4;
-        if (const char *e = NFC_ENV("NFC_WG_NR")) {
-            const int v = atoi(e);
-            if ((v == 4 || (v == 8 && nr8_kind)) && c->L >= wg_round_samples(v)) c->wg_nr = v;
-        }
-        // (+ the staging of the plane words: a ring of 2 FR rounds; a whole chunk's where the LDS has room, launch_wg)
-        c->wg_lds = c->wg_lds_base + wg_stage_bytes(c->wg_nr, 2 * wg_flush_rounds(c->wg_nr));
-        c->wg_ok = c->mx <= 64 * c->wg_nr - 2 && c->L >= wg_round_samples(c->wg_nr) && c->wg_lds <= 160 * 1024;
-        if (c->wg_ok) {
-            const void *kern = (const void *)c->kk->wg[c->wg_nr == 8 ? 1 : 0];
-#ifdef NFC_TEST_HOOKS
-            if (const char *e = getenv("NFC_WG_FLAGS"))   // (ignored for a kind without that form: the complex integer kinds)
-                c->wg_flags = atoi(e) != 0 && c->kk->wg_flags[0] != nullptr;
-            if (c->wg_flags) kern = (const void *)c->kk->wg_flags[c->wg_nr == 8 && c->kk->wg_flags[1] ? 1 : 0];
-            if (!kern) {
-                nfc_destroy(c);
-                return fail(nullptr, NFC_ERR_INTERNAL, "no workgroup kernel for input kind %d", p->input_kind);
-            }
-#endif
-            if (c->wg_lds > 64 * 1024) CRT(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->wg_lds));
-            int per_cu_wg = 0;
-            CRT(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_wg, kern, 256, c->wg_lds));
-            const int per_cu_max = per_cu_wg;
-            if (per_cu_wg < 1) c->wg_ok = 0;   // (the kernel does not fit a CU with this ring: the one-wave kernels)
-            per_cu_wg = std::max(1, std::min(4, per_cu_wg));   // (measured: four resident workgroups per CU -- four waves per SIMD -- beat five and three)
-            if (const char *e = NFC_ENV("NFC_WG_PER_CU")) per_cu_wg = std::max(1, std::min(per_cu_max, atoi(e)));
-            c->wg_slots = prop.multiProcessorCount * per_cu_wg;
-            // the most dynamic LDS a workgroup may ask for with per_cu_wg of them still resident per CU: what a chunk's planes may
-            // take when they are kept until the chunk is done (one batch at a time only: launch_wg)
-            c->wg_lds_bulk_max = 0;
-            if (c->wg_bulk) {
-                size_t cand = ((size_t)160 * 1024 / (size_t)per_cu_wg) & ~(size_t)1023;
-                while (cand > c->wg_lds) {
-                    int fit = 0;
-                    if (cand > 64 * 1024) CRT(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cand));
-                    CRT(hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, kern, 256, cand));
-                    if (fit >= per_cu_wg) break;
-                    cand -= 1024;
-                }
-                if (cand > c->wg_lds) c->wg_lds_bulk_max = cand;
-            }
-            // Batches submitted ahead run beside the edge and decode stages of the batch before them, and those need registers to
-            // be resident at all: four workgroups of this kernel per CU hold 4 x 96 of a SIMD's 512 registers and leave the stages
-            // ONE wave per SIMD (measured: k_dec_apply 19 -> 102 us beside it, the stages' chain -- not this kernel -- then sets the
-            // period).  Three per CU leave them two or three: 0.263 -> 0.241 ms per batch (two: 0.254).
-            int per_cu_ahead = std::min(per_cu_wg, 3);
-            // (... and LDS: the later stages' workgroups want 12-29 KB each beside it.  A long window's ring -- av_window 10 000: 40 KB, 52 KB
-            // with the rest -- fills the CU at three per CU, so such streams take the synchronous path: host_submit.h, submit_fast_ok.
-            // Measured in round 5, configs[3], with TWO per CU for batches submitted ahead (56 KB left; the kernel alone loses 3 % to it,
-            // 1.589 -> 1.637 ms per launch; one per CU: 2.31): 1.87-2.02 ms per batch against 1.92 one batch at a time -- the kernel
-            // stretches to 1.69-2.0 ms beside the other stages, which are 0.35 ms of a 1.95 ms step to begin with.  Not taken.)
-            if (const char *e = NFC_ENV("NFC_WG_PER_CU_AHEAD")) per_cu_ahead = std::max(1, std::min(per_cu_max, atoi(e)));
-            c->wg_slots_ahead = prop.multiProcessorCount * per_cu_ahead;
-            // (what a batch submitted ahead holds of a CU's LDS is this kernel's, not the lean kernel's: host_submit.h, submit_fast_ok)
-            if (c->wg_ok && c->wg && c->lean) c->ahead_lds_per_cu = c->wg_lds * (size_t)per_cu_ahead;
-            // re-runs with failed rounds evaluated in place (k_threshold_wg<KIND, 4, true>): max_len within one four-row step, a round of
-            // four of them within the window; up to a machine-full of failing chunks per round
-            c->wg_ex_lds = c->wg_lds_base + wg_stage_bytes(4, 2 * wg_flush_rounds(4));
-            c->wg_ex_ok = c->wg_ok && c->mx <= 64 * 4 - 2 && c->L >= wg_round_samples(4) && c->wg_ex_lds <= 160 * 1024;
-            if (c->wg_ex_ok) {
-                const void *kx = (const void *)c->kk->wg_ex;
-                if (c->wg_ex_lds > 64 * 1024) CRT(hipFuncSetAttribute(kx, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->wg_ex_lds));
-                int fit = 0;
-                CRT(hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, kx, 256, c->wg_ex_lds));
-                if (fit < 1) c->wg_ex_ok = 0;
-                c->wg_ex_max = prop.multiProcessorCount * std::max(1, std::min(4, fit));
-            }
-            if (const char *e = NFC_ENV("NFC_WG_EX")) {   // 0: never; N: up to N failing chunks per round
-                const int v = atoi(e);
-                if (v <= 0) c->wg_ex_ok = 0;
-                else c->wg_ex_max = v;
-            }
-            // the longest superstep (rounds): the kernel lengthens and shortens its supersteps by the head-room it sees between the
-            // samples and the thresholds; this caps them
-            if (!c->wg_rounds) c->wg_rounds = 8;
-            if (const char *e = NFC_ENV("NFC_CHUNK_ADAPT")) c->fine_adapt = atoi(e) != 0;
-            if (const char *e = NFC_ENV("NFC_CHUNK_MULT")) c->fine_mult = std::max(1, std::min(16, atoi(e)));
-        }
+// what the device's size and the occupancy queries decide: slots, LDS budgets, which workgroup kernel
+int create_plan_device(nfc_ctx *c, const Switches &sw) {
+    hipDeviceProp_t prop;
+    CRT(hipGetDeviceProperties(&prop, c->P.device));
+    const size_t lds_wave = (size_t)c->Lpad * c->lds_per_slot;
+    int per_cu = (int)std::min<size_t>(20, (size_t)(160 * 1024) / (lds_wave * c->wpb) * c->wpb);   // LDS- and VGPR-bound
+    c->n_cus = std::max(1, prop.multiProcessorCount);
+    c->wave_slots = std::max(1, prop.multiProcessorCount * std::max(1, per_cu));
+    // lean kernel: four steps ahead (104 registers: at most four waves per SIMD); a superstep long enough that its fixed cost
+    // fades -- the drift allowance grows with its length relative to the window (about half the window at most: beyond, the
+    // widened bands reach the loaded half bits of tag frames)
+    // Measured (configs[1] / [2], 1e8 samples): two waves per SIMD with four steps ahead beat five waves with three --
+    // 0.206 / 0.196 ms against 0.237 / 0.230 on the same box: a chunk's fixed cost (the window before it read and
+    // summarised, its summary written) is paid half as often, and two waves already keep a SIMD's issue slots busy.
+    if (!c->lean_k) c->lean_k = 4;
+    c->lean_slots = std::min(c->wave_slots, prop.multiProcessorCount * 8);
+    if (sw.lean_waves) c->lean_slots = std::min(c->wave_slots, prop.multiProcessorCount * 4 * std::max(1, *sw.lean_waves));
+    if (!c->lean_rounds) c->lean_rounds = std::max(1, (int)(0.4 * c->L / (256.0 * c->lean_k)));
+    c->wave_slots_g = prop.multiProcessorCount * 20;   // VGPR-bound: five waves per SIMD
+    // LDS the lean kernel's resident waves hold per CU: a batch is only run ahead of its predecessor's edge / decode stages
+    // (nfc_submit_device) while those stages' workgroups (25 KB each) still fit beside it
+    c->lean_lds_per_cu = (size_t)((c->lean_slots + prop.multiProcessorCount - 1) / prop.multiProcessorCount) * lds_wave;
+    c->ahead_lds_per_cu = c->lean_lds_per_cu;
+    // the workgroup kernel: one chunk per 256-thread workgroup, as many resident per CU as LDS and registers admit
+    c->wg_lds_base = (size_t)c->Lpad * 4 + WG_SHARED_BYTES;
+    // rows per step: eight where that leaves a superstep of at least two rounds within 0.8 windows (measured: at av_window 10000
+    // eight rows gain 2 % over four; at 2000 more rows with one-round supersteps lose to four rows with two), else four; a round
+    // (four steps) must fit the window, max_len must lie within one step.  Eight rows are instantiated for fc32, sc16, sc8 and cu8 IQ
+    // and the float32 envelope -- what a capture at a rate that wants such a window arrives as (kind_kernels.h: has_nr8).
+    const bool nr8_kind = c->kk->wg[1] != nullptr;
+    c->wg_nr = (nr8_kind && 0.8 * c->L / (double)wg_round_samples(8) >= 1.5) ? 8 : 4;
+    if (sw.wg_nr) {
+        const int v = *sw.wg_nr;
+        if ((v == 4 || (v == 8 && nr8_kind)) && c->L >= wg_round_samples(v)) c->wg_nr = v;
     }
-    CRT(hipStreamCreateWithFlags(&c->own_st, hipStreamNonBlocking));
+    // (+ the staging of the plane words: a ring of 2 FR rounds; a whole chunk's where the LDS has room, launch_wg)
+    c->wg_lds = c->wg_lds_base + wg_stage_bytes(c->wg_nr, 2 * wg_flush_rounds(c->wg_nr));
+    c->wg_ok = c->mx <= 64 * c->wg_nr - 2 && c->L >= wg_round_samples(c->wg_nr) && c->wg_lds <= 160 * 1024;
+    if (!c->wg_ok) return NFC_OK;
+    const void *kern = (const void *)c->kk->wg[c->wg_nr == 8 ? 1 : 0];
+    if (sw.wg_flags) c->wg_flags = *sw.wg_flags != 0 && c->kk->wg_flags[0] != nullptr;   // (ignored for a kind without that form: the complex integer kinds)
+    if (c->wg_flags) kern = (const void *)c->kk->wg_flags[c->wg_nr == 8 && c->kk->wg_flags[1] ? 1 : 0];
+    if (!kern) return fail(nullptr, NFC_ERR_INTERNAL, "no workgroup kernel for input kind %d", c->P.input_kind);
+    if (c->wg_lds > 64 * 1024) CRT(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->wg_lds));
+    int per_cu_wg = 0;
+    CRT(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_wg, kern, 256, c->wg_lds));
+    const int per_cu_max = per_cu_wg;
+    if (per_cu_wg < 1) c->wg_ok = 0;   // (the kernel does not fit a CU with this ring: the one-wave kernels)
+    per_cu_wg = std::max(1, std::min(4, per_cu_wg));   // (measured: four resident workgroups per CU -- four waves per SIMD -- beat five and three)
+    if (sw.wg_per_cu) per_cu_wg = std::max(1, std::min(per_cu_max, *sw.wg_per_cu));
+    c->wg_slots = prop.multiProcessorCount * per_cu_wg;
+    // the most dynamic LDS a workgroup may ask for with per_cu_wg of them still resident per CU: what a chunk's planes may
+    // take when they are kept until the chunk is done (one batch at a time only: launch_wg)
+    c->wg_lds_bulk_max = 0;
+    if (c->wg_bulk) {
+        size_t cand = ((size_t)160 * 1024 / (size_t)per_cu_wg) & ~(size_t)1023;
+        while (cand > c->wg_lds) {
+            int fit = 0;
+            if (cand > 64 * 1024) CRT(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cand));
+            CRT(hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, kern, 256, cand));
+            if (fit >= per_cu_wg) break;
+            cand -= 1024;
+        }
+        if (cand > c->wg_lds) c->wg_lds_bulk_max = cand;
+    }
+    // Batches submitted ahead run beside the edge and decode stages of the batch before them, and those need registers to
+    // be resident at all: four workgroups of this kernel per CU hold 4 x 96 of a SIMD's 512 registers and leave the stages
+    // ONE wave per SIMD (measured: k_dec_apply 19 -> 102 us beside it, the stages' chain -- not this kernel -- then sets the
+    // period).  Three per CU leave them two or three: 0.263 -> 0.241 ms per batch (two: 0.254).
+    int per_cu_ahead = std::min(per_cu_wg, 3);
+    // (... and LDS: the later stages' workgroups want 12-29 KB each beside it.  A long window's ring -- av_window 10 000: 40 KB, 52 KB
+    // with the rest -- fills the CU at three per CU, so such streams take the synchronous path: host_submit.h, submit_fast_ok.
+    // Measured in round 5, configs[3], with TWO per CU for batches submitted ahead (56 KB left; the kernel alone loses 3 % to it,
+    // 1.589 -> 1.637 ms per launch; one per CU: 2.31): 1.87-2.02 ms per batch against 1.92 one batch at a time -- the kernel
+    // stretches to 1.69-2.0 ms beside the other stages, which are 0.35 ms of a 1.95 ms step to begin with.  Not taken.)
+    if (sw.wg_per_cu_ahead) per_cu_ahead = std::max(1, std::min(per_cu_max, *sw.wg_per_cu_ahead));
+    c->wg_slots_ahead = prop.multiProcessorCount * per_cu_ahead;
+    // (what a batch submitted ahead holds of a CU's LDS is this kernel's, not the lean kernel's: host_submit.h, submit_fast_ok)
+    if (c->wg_ok && c->wg && c->lean) c->ahead_lds_per_cu = c->wg_lds * (size_t)per_cu_ahead;
+    // re-runs with failed rounds evaluated in place (k_threshold_wg<KIND, 4, true>): max_len within one four-row step, a round of
+    // four of them within the window; up to a machine-full of failing chunks per round
+    c->wg_ex_lds = c->wg_lds_base + wg_stage_bytes(4, 2 * wg_flush_rounds(4));
+    c->wg_ex_ok = c->wg_ok && c->mx <= 64 * 4 - 2 && c->L >= wg_round_samples(4) && c->wg_ex_lds <= 160 * 1024;
+    if (c->wg_ex_ok) {
+        const void *kx = (const void *)c->kk->wg_ex;
+        if (c->wg_ex_lds > 64 * 1024) CRT(hipFuncSetAttribute(kx, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->wg_ex_lds));
+        int fit = 0;
+        CRT(hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, kx, 256, c->wg_ex_lds));
+        if (fit < 1) c->wg_ex_ok = 0;
+        c->wg_ex_max = prop.multiProcessorCount * std::max(1, std::min(4, fit));
+    }
+    if (sw.wg_ex) {
+        if (*sw.wg_ex <= 0) c->wg_ex_ok = 0;
+        else c->wg_ex_max = *sw.wg_ex;
+    }
+    // the longest superstep (rounds): the kernel lengthens and shortens its supersteps by the head-room it sees between the
+    // samples and the thresholds; this caps them
+    if (!c->wg_rounds) c->wg_rounds = 8;
+    if (sw.chunk_adapt) c->fine_adapt = *sw.chunk_adapt != 0;
+    if (sw.chunk_mult) c->fine_mult = std::max(1, std::min(16, *sw.chunk_mult));
+    return NFC_OK;
+}
+
+// the streams, the events and the pinned snapshots of batches submitted ahead; the one-wave kernels' LDS ring admitted; the decoder LUTs on
+// the device, the carried state and its mirror, the window buffers
+int create_resources(nfc_ctx *c) {
+    CRT(c->own_st.create());
     c->st = c->own_st;
-    for (auto &e : c->ev) CRT(hipEventCreate(&e));
-    for (auto &e : c->kev) CRT(hipEventCreate(&e));
-    CRT(hipStreamCreateWithFlags(&c->st_a, hipStreamNonBlocking));
-    static_assert(NRING == 4 && NSUB == 3, "the buffer list of nfc_destroy names them");
+    for (auto &e : c->ev) CRT(e.create());
+    for (auto &e : c->kev) CRT(e.create());
+    CRT(c->st_a.create());
     for (int b = 0; b < NSUB; b++) {
-        CRT(hipEventCreateWithFlags(&c->ev_a[b], hipEventDisableTiming));
-        CRT(hipEventCreateWithFlags(&c->ev_b[b], hipEventDisableTiming));
-        CRT(hipEventCreate(&c->kev_sub[b][0]));
-        CRT(hipEventCreate(&c->kev_sub[b][1]));
-        CRT(hipHostMalloc((void **)&c->hs_a[b], sizeof(DevState), hipHostMallocDefault));
-        memset(c->hs_a[b], 0, sizeof(DevState));
+        CRT(c->ev_a[b].create(hipEventDisableTiming));
+        CRT(c->ev_b[b].create(hipEventDisableTiming));
+        CRT(c->kev_sub[b][0].create());
+        CRT(c->kev_sub[b][1].create());
+        CRT(c->hs_a[b].ensure(sizeof(DevState)));
+        memset(c->hs_a[b].p, 0, sizeof(DevState));
     }
     const size_t lds = (size_t)c->wpb * c->Lpad * c->lds_per_slot;
-    if (lds > 160 * 1024) {
-        nfc_destroy(c);
-        return fail(nullptr, NFC_ERR_ARG, "av_window too large for one wave's LDS ring");
-    }
+    if (lds > 160 * 1024) return fail(nullptr, NFC_ERR_ARG, "av_window too large for one wave's LDS ring");
     if (lds > 64 * 1024) {
         for (int kind = 0; kind < N_KINDS; kind++)   // (every kind's, not only this context's)
             for (const ThrKernel kern : {kind_kernels(kind).thr[0], kind_kernels(kind).lean[0], kind_kernels(kind).lean[1]})
                 CRT(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     }
-    // decoder LUTs
+    const nfc_params *p = &c->P;
     DecoderTables t = build_tables(p->samp_rate, c->mx);
     std::vector<uint8_t> milb(t.miller_map.size() * 16), manb(t.manch_map.size() * 8);
     for (size_t i = 0; i < t.miller_map.size(); i++)
@@ -430,8 +380,8 @@ int nfc_create(const nfc_params *p, nfc_ctx **out) {
     for (int k = 0; k < 3; k++) c->dec_lds[k] = dec_table_bytes((DecLdsUser)k, c->T);   // what the decode kernels stage of these tables
     // carried state
     CRT(c->d_state.ensure(sizeof(DevState)));
-    // (mapped AND coherent, explicitly: the host watches the stamp word while the stream runs -- host_threshold.h: wait_for_stamp)
-    CRT(hipHostMalloc((void **)&c->hs, sizeof(DevState), hipHostMallocMapped | hipHostMallocCoherent));
+    CRT(c->hs_pin.ensure(sizeof(DevState)));
+    c->hs = c->hs_pin.as<DevState>();
     memset(c->hs, 0, sizeof(DevState));
     CRT(hipHostGetDevicePointer(&c->hs_dev, c->hs, 0));
     for (int b = 0; b < NRING; b++) {
@@ -444,8 +394,46 @@ int nfc_create(const nfc_params *p, nfc_ctx **out) {
     }
     push_state(c, 1);
     CRT(hipStreamSynchronize(c->st));
+    return NFC_OK;
+}
 #undef CRT
-    *out = c;
+}  // namespace
+
+extern "C" {
+
+int nfc_abi_version(void) { return NFC_AMD_ABI_VERSION; }
+
+int nfc_plan_row_cut(uint32_t n, uint32_t C, uint32_t rs, uint32_t cus, uint32_t rows, const double *factors, uint32_t max_len, uint32_t out[10]) {
+    if (!out || !rs || !C || !cus || (rows >= 2 && !factors)) return NFC_ERR_ARG;
+    const RowCut t = (rows >= 2 && rows <= 4) ? plan_row_cut(n, C, rs, cus, rows, factors, max_len) : equal_cut(n, C, cus);
+    for (int r = 0; r < 4; r++) {
+        out[r] = t.row_len[r];
+        out[4 + r] = t.row_start[r];
+    }
+    out[8] = t.row_div;
+    out[9] = t.nch;
+    return t.by_row ? 1 : 0;
+}
+
+int nfc_device_count(void) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
+    return n;
+}
+
+const char *nfc_last_error(const nfc_ctx *ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
+
+int nfc_create(const nfc_params *p, nfc_ctx **out) {
+    if (!p || !out) return fail(nullptr, NFC_ERR_ARG, "null argument");
+    *out = nullptr;
+    float scale_arg = 0.f;
+    if (int rc = create_check_args(p, &scale_arg)) return rc;
+    const Switches sw = read_switches();
+    std::unique_ptr<nfc_ctx, void (*)(nfc_ctx *)> c(new nfc_ctx(), nfc_destroy);   // (a step that fails: what there is waits, then goes)
+    if (int rc = create_plan_params(c.get(), p, sw, scale_arg)) return rc;
+    if (int rc = create_plan_device(c.get(), sw)) return rc;
+    if (int rc = create_resources(c.get())) return rc;
+    *out = c.release();
     return NFC_OK;
 }
 
@@ -455,35 +443,7 @@ void nfc_destroy(nfc_ctx *c) {
     if (c->st_a) (void)hipStreamSynchronize(c->st_a);
     if (c->st && c->st == c->own_st) (void)hipStreamSynchronize(c->st);
     else (void)hipDeviceSynchronize();   // on a caller's stream (nfc_set_stream): the handle may be gone by now
-    DevBuf *all[] = {&c->d_mil_map, &c->d_man_map, &c->d_mil_out, &c->d_man_out, &c->d_qmil_map, &c->d_qmil_step, &c->d_state,
-                     &c->d_ring[0], &c->d_ring[1], &c->d_ring[2], &c->d_ring[3], &c->d_neg_alt[0], &c->d_pos_alt[0], &c->d_neg_alt[1], &c->d_pos_alt[1], &c->d_certinfo, &c->d_in, &c->d_neg, &c->d_pos, &c->d_ringin, &c->d_meta, &c->d_ringout[0], &c->d_ringout[1], &c->d_touched[0],
-                     &c->d_touched[1], &c->d_info[0], &c->d_info[1], &c->d_ver, &c->d_cflags, &c->d_list, &c->d_ecode, &c->d_epos, &c->d_eidx, &c->d_states, &c->d_sym[0], &c->d_sym[1],
-                     &c->d_bits[0], &c->d_bits[1], &c->d_pending[0][0], &c->d_pending[0][1],
-                     &c->d_pending[1][0], &c->d_pending[1][1], &c->d_partials2, &c->d_close_end[0], &c->d_close_end[1], &c->d_close_idx[0], &c->d_close_idx[1],
-                     &c->d_partials, &c->d_edge_rec, &c->d_aggs, &c->d_faggs, &c->d_spec, &c->d_stage_bits[0], &c->d_stage_bits[1], &c->d_stage_cb[0], &c->d_stage_cb[1], &c->d_stage_ci[0], &c->d_stage_ci[1], &c->d_stage_q[0], &c->d_stage_q[1], &c->d_stage_own, &c->d_gring, &c->d_pack, &c->d_gvtop, &c->d_seqout, &c->d_tail_st, &c->d_tail_ticket, &c->d_bits_alt[0], &c->d_bits_alt[1],
-                     &c->d_fr_rec[0], &c->d_fr_rec[1], &c->d_fr_bytes[0], &c->d_fr_bytes[1], &c->d_fr_par[0], &c->d_fr_par[1], &c->d_fr_tot};
-    for (DevBuf *b : all) b->release();
-    for (auto &e : c->fr_ev)
-        if (e) (void)hipEventDestroy(e);
-    if (c->hs) (void)hipHostFree(c->hs);
-    if (c->h_stage) (void)hipHostFree(c->h_stage);
-    if (c->h_edge_stage) (void)hipHostFree(c->h_edge_stage);
-    if (c->h_pk_stage) (void)hipHostFree(c->h_pk_stage);
-    if (c->h_cflags) (void)hipHostFree(c->h_cflags);
-    for (auto &e : c->ev)
-        if (e) (void)hipEventDestroy(e);
-    for (auto &e : c->kev)
-        if (e) (void)hipEventDestroy(e);
-    for (int b = 0; b < NSUB; b++) {
-        if (c->ev_a[b]) (void)hipEventDestroy(c->ev_a[b]);
-        if (c->ev_b[b]) (void)hipEventDestroy(c->ev_b[b]);
-        if (c->kev_sub[b][0]) (void)hipEventDestroy(c->kev_sub[b][0]);
-        if (c->kev_sub[b][1]) (void)hipEventDestroy(c->kev_sub[b][1]);
-        if (c->hs_a[b]) (void)hipHostFree(c->hs_a[b]);
-    }
-    if (c->st_a) (void)hipStreamDestroy(c->st_a);
-    if (c->own_st) (void)hipStreamDestroy(c->own_st);
-    delete c;
+    delete c;   // (every buffer, event and stream is a member that releases itself: host_context.h)
 }
 
 int nfc_push_device(nfc_ctx *c, const void *dev_samples, size_t n) {
@@ -653,16 +613,13 @@ constexpr size_t EDGE_PIECE = 1u << 20;   // entries per piece
 template <class Consume>
 int fetch_entries(nfc_ctx *c, size_t first, size_t n, Consume consume) {   // consume(pos, code, count, offset)
     const size_t need = 2 * EDGE_PIECE * 6 + 64;
-    if (c->h_edge_stage_cap < need) {
+    if (c->h_edge_stage.cap < need) {
         devbuf_allocs()++;
-        if (c->h_edge_stage) (void)hipHostFree(c->h_edge_stage);
-        c->h_edge_stage = nullptr;
-        c->h_edge_stage_cap = 0;
-        HIPCHK(c, hipHostMalloc((void **)&c->h_edge_stage, need, hipHostMallocDefault));
-        c->h_edge_stage_cap = need;
+        HIPCHK(c, c->h_edge_stage.ensure(need));
     }
-    auto pos_of = [&](int b) { return (uint32_t *)(c->h_edge_stage + (size_t)b * EDGE_PIECE * 6); };
-    auto code_of = [&](int b) { return (uint16_t *)(c->h_edge_stage + (size_t)b * EDGE_PIECE * 6 + EDGE_PIECE * 4); };
+    uint8_t *const stage = c->h_edge_stage.as<uint8_t>();
+    auto pos_of = [&](int b) { return (uint32_t *)(stage + (size_t)b * EDGE_PIECE * 6); };
+    auto code_of = [&](int b) { return (uint16_t *)(stage + (size_t)b * EDGE_PIECE * 6 + EDGE_PIECE * 4); };
     auto request = [&](size_t off, int b) -> hipError_t {
         const size_t cnt = std::min(EDGE_PIECE, n - off);
         hipError_t e = hipMemcpyAsync(pos_of(b), c->d_epos.as<uint32_t>() + first + off, cnt * 4, hipMemcpyDeviceToHost, c->st);
@@ -789,18 +746,9 @@ int nfc_read_packet_bits(nfc_ctx *c, int type, size_t first, uint8_t *out, size_
     if (n) {
         const size_t w0 = first >> 5, w1 = (first + n + 31) >> 5;
         // (the words through pinned staging: a pageable destination makes the runtime stage the copy itself, synchronously)
-        const size_t need = (w1 - w0) * 4 + 64;
-        if (c->h_pk_stage_cap < need) {
-            devbuf_allocs()++;
-            if (c->h_pk_stage) (void)hipHostFree(c->h_pk_stage);
-            c->h_pk_stage = nullptr;
-            c->h_pk_stage_cap = 0;
-            const size_t cap2 = need + need / 2 + 65536;
-            HIPCHK(c, hipHostMalloc((void **)&c->h_pk_stage, cap2, hipHostMallocDefault));
-            c->h_pk_stage_cap = cap2;
-        }
-        const uint32_t *w = (const uint32_t *)c->h_pk_stage;
-        HIPCHK(c, hipMemcpyAsync(c->h_pk_stage, c->d_bits[type].as<uint32_t>() + w0, (w1 - w0) * 4, hipMemcpyDeviceToHost, c->st));
+        if (int rc = pk_stage(c, (w1 - w0) * 4 + 64)) return rc;
+        const uint32_t *w = c->h_pk_stage.as<uint32_t>();
+        HIPCHK(c, hipMemcpyAsync(c->h_pk_stage.p, c->d_bits[type].as<uint32_t>() + w0, (w1 - w0) * 4, hipMemcpyDeviceToHost, c->st));
         HIPCHK(c, hipStreamSynchronize(c->st));
         // a byte per bit, eight at a time: byte j of (b * 0x0101.. & 0x8040..01) is nonzero exactly when bit j of b is set
         auto spread8 = [](uint32_t b) -> uint64_t {
@@ -829,17 +777,6 @@ int nfc_read_packet_bits(nfc_ctx *c, int type, size_t first, uint8_t *out, size_
 // ---- frames: assembled on the device on the first read after a batch (frames.hip.h, nfc_frames.hip) ----
 extern "C++" {
 namespace {
-int pk_stage(nfc_ctx *c, size_t need) {   // the pinned staging area the packet tables use, at least `need` bytes
-    if (c->h_pk_stage_cap >= need) return NFC_OK;
-    devbuf_allocs()++;
-    if (c->h_pk_stage) (void)hipHostFree(c->h_pk_stage);
-    c->h_pk_stage = nullptr;
-    c->h_pk_stage_cap = 0;
-    const size_t cap2 = need + need / 2 + 65536;
-    HIPCHK(c, hipHostMalloc((void **)&c->h_pk_stage, cap2, hipHostMallocDefault));
-    c->h_pk_stage_cap = cap2;
-    return NFC_OK;
-}
 int ensure_frames(nfc_ctx *c) {
     if (!c->have_outputs) return fail(c, NFC_ERR_STATE, "no completed batch");
     if (c->frames_ready) return NFC_OK;
@@ -868,14 +805,13 @@ int ensure_frames(nfc_ctx *c) {
         A.totals = c->d_fr_tot.as<uint64_t>();
         const bool timed = c->timing >= 1;
         if (timed)
-            for (auto &e : c->fr_ev)
-                if (!e) HIPCHK(c, hipEventCreate(&e));
-        frames::launch_ctx(A, c->bits_packed, c->st, timed ? c->fr_ev[0] : nullptr, timed ? c->fr_ev[1] : nullptr);
+            for (auto &e : c->fr_ev) HIPCHK(c, e.create());
+        frames::launch_ctx(A, c->bits_packed, c->st, timed ? (hipEvent_t)c->fr_ev[0] : nullptr, timed ? (hipEvent_t)c->fr_ev[1] : nullptr);
         if (int rc = pk_stage(c, 64)) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->h_pk_stage, c->d_fr_tot.p, 32, hipMemcpyDeviceToHost, c->st));
+        HIPCHK(c, hipMemcpyAsync(c->h_pk_stage.p, c->d_fr_tot.p, 32, hipMemcpyDeviceToHost, c->st));
         HIPCHK(c, hipStreamSynchronize(c->st));
         BATCHCHK(c, false);
-        const uint64_t *tot = (const uint64_t *)c->h_pk_stage;
+        const uint64_t *tot = c->h_pk_stage.as<uint64_t>();
         for (int t = 0; t < 2; t++) {
             c->fr_frames[t] = tot[2 * t];
             c->fr_bytes[t] = tot[2 * t + 1];
@@ -898,9 +834,9 @@ int read_pinned(nfc_ctx *c, const void *dev, void *out, size_t bytes) {
     }
     (void)hipGetLastError();   // (not pinned: hipHostGetFlags left its complaint behind)
     if (int rc = pk_stage(c, bytes)) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->h_pk_stage, dev, bytes, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipMemcpyAsync(c->h_pk_stage.p, dev, bytes, hipMemcpyDeviceToHost, c->st));
     HIPCHK(c, hipStreamSynchronize(c->st));
-    memcpy(out, c->h_pk_stage, bytes);
+    memcpy(out, c->h_pk_stage.p, bytes);
     return NFC_OK;
 }
 }  // namespace
@@ -1082,13 +1018,8 @@ int nfc_get_state(nfc_ctx *c, nfc_state_header *h, float *ring, size_t ring_cap,
     if (pending && pending_cap < p0 + p1) return fail(c, NFC_ERR_ARG, "pending-bit buffer too small");
     // through a pinned staging buffer: asynchronous copies and a single wait
     const size_t need = (size_t)c->L * 4 + p0 + p1;
-    if (c->h_stage_cap < need) {
-        if (c->h_stage) (void)hipHostFree(c->h_stage);
-        c->h_stage = nullptr;
-        c->h_stage_cap = need + 4096;
-        HIPCHK(c, hipHostMalloc((void **)&c->h_stage, c->h_stage_cap, hipHostMallocDefault));
-    }
-    uint8_t *st = c->h_stage;
+    if (c->h_stage.cap < need) HIPCHK(c, c->h_stage.ensure(need + 4096));
+    uint8_t *st = c->h_stage.as<uint8_t>();
     if (ring || (pending && p0 + p1)) {
         // gathered on the device (ring | pending bits of type 0 | of type 1), then one copy and one wait
         HIPCHK(c, c->d_pack.ensure(need + 16));
@@ -1309,8 +1240,8 @@ int nfc_tx_render_device(int device, const nfc_tx_run *runs, size_t n_runs, doub
     if (tot == 0) return NFC_OK;
     TxArgs A;
     memset(&A, 0, sizeof A);
-    void *d_ends = nullptr, *d_levels = nullptr, *d_first = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    DevBuf d_ends, d_levels, d_first;
+    Event e0, e1;
     // per tile of the output, the run its first sample falls in (one walk over the runs; the last entry closes the last tile)
     const size_t n_tiles = (size_t)((tot + TX_TILE - 1) / TX_TILE);
     std::vector<uint32_t> first(n_tiles + 1);
@@ -1324,47 +1255,37 @@ int nfc_tx_render_device(int device, const nfc_tx_run *runs, size_t n_runs, doub
         while (ends[r] <= tot - 1) r++;
         first[n_tiles] = (uint32_t)r;
     }
-    int rc = NFC_OK;
-    auto bad = [&](hipError_t e, const char *what) {
-        if (e == hipSuccess) return false;
-        rc = fail(nullptr, NFC_ERR_DEVICE, "nfc_tx_render_device: %s: %s", what, hipGetErrorString(e));
-        return true;
+    auto bad = [](hipError_t e, const char *what) {
+        return e == hipSuccess ? NFC_OK : fail(nullptr, NFC_ERR_DEVICE, "nfc_tx_render_device: %s: %s", what, hipGetErrorString(e));
     };
-    do {
-        if (bad(hipMalloc(&d_ends, n_runs * 8), "hipMalloc")) break;
-        if (bad(hipMalloc(&d_levels, n_runs), "hipMalloc")) break;
-        if (bad(hipMemcpy(d_ends, ends.data(), n_runs * 8, hipMemcpyHostToDevice), "upload")) break;
-        if (bad(hipMemcpy(d_levels, levels.data(), n_runs, hipMemcpyHostToDevice), "upload")) break;
-        if (bad(hipMalloc(&d_first, first.size() * 4), "hipMalloc")) break;
-        if (bad(hipMemcpy(d_first, first.data(), first.size() * 4, hipMemcpyHostToDevice), "upload")) break;
-        A.tile_first = (const uint32_t *)d_first;
-        A.ends = (const uint64_t *)d_ends;
-        A.levels = (const int8_t *)d_levels;
-        A.n_runs = (uint32_t)n_runs;
-        A.n_samples = tot;
-        A.first_index = first_index;
-        A.carrier = carrier ? 1 : 0;
-        const double turns = freq / samp_rate, fr = turns - std::floor(turns);
-        A.phase_inc = (uint64_t)(fr * 18446744073709551616.0);   // floor(frac(f / fs) * 2^64)
-        A.amp = amp;
-        A.out = (float2 *)dev_out;
-        const unsigned blocks = (unsigned)n_tiles;
-        if (kernel_ms) {
-            if (bad(hipEventCreate(&e0), "event") || bad(hipEventCreate(&e1), "event")) break;
-            NFC_LAUNCH_EXT(k_tx_render, dim3(blocks), dim3(TX_BLOCK), 0, nullptr, e0, e1, 0, A);
-        } else {
-            NFC_LAUNCH(k_tx_render, dim3(blocks), dim3(TX_BLOCK), 0, nullptr, A);
-        }
-        if (bad(hipGetLastError(), "launch")) break;
-        if (bad(hipDeviceSynchronize(), "kernel")) break;
-        if (kernel_ms && bad(hipEventElapsedTime(kernel_ms, e0, e1), "event")) break;
-    } while (0);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (d_ends) (void)hipFree(d_ends);
-    if (d_levels) (void)hipFree(d_levels);
-    if (d_first) (void)hipFree(d_first);
-    return rc;
+    if (int rc = bad(d_ends.ensure(n_runs * 8), "hipMalloc")) return rc;
+    if (int rc = bad(d_levels.ensure(n_runs), "hipMalloc")) return rc;
+    if (int rc = bad(hipMemcpy(d_ends.p, ends.data(), n_runs * 8, hipMemcpyHostToDevice), "upload")) return rc;
+    if (int rc = bad(hipMemcpy(d_levels.p, levels.data(), n_runs, hipMemcpyHostToDevice), "upload")) return rc;
+    if (int rc = bad(d_first.ensure(first.size() * 4), "hipMalloc")) return rc;
+    if (int rc = bad(hipMemcpy(d_first.p, first.data(), first.size() * 4, hipMemcpyHostToDevice), "upload")) return rc;
+    A.tile_first = d_first.as<const uint32_t>();
+    A.ends = d_ends.as<const uint64_t>();
+    A.levels = d_levels.as<const int8_t>();
+    A.n_runs = (uint32_t)n_runs;
+    A.n_samples = tot;
+    A.first_index = first_index;
+    A.carrier = carrier ? 1 : 0;
+    const double turns = freq / samp_rate, fr = turns - std::floor(turns);
+    A.phase_inc = (uint64_t)(fr * 18446744073709551616.0);   // floor(frac(f / fs) * 2^64)
+    A.amp = amp;
+    A.out = (float2 *)dev_out;
+    const unsigned blocks = (unsigned)n_tiles;
+    if (kernel_ms) {
+        if (int rc = bad(e0.create(), "event")) return rc;
+        if (int rc = bad(e1.create(), "event")) return rc;
+        NFC_LAUNCH_EXT(k_tx_render, dim3(blocks), dim3(TX_BLOCK), 0, nullptr, e0, e1, 0, A);
+    } else {
+        NFC_LAUNCH(k_tx_render, dim3(blocks), dim3(TX_BLOCK), 0, nullptr, A);
+    }
+    if (int rc = bad(hipGetLastError(), "launch")) return rc;
+    if (int rc = bad(hipDeviceSynchronize(), "kernel")) return rc;
+    return kernel_ms ? bad(hipEventElapsedTime(kernel_ms, e0, e1), "event") : NFC_OK;
 }
 
 int nfc_device_alloc(int device, size_t bytes, void **out) {
@@ -1454,25 +1375,21 @@ int nfc_record_pcm16_device(int device, int tap, int input_kind, float i16_scale
     if (const char *e = getenv("NFC_REC_NT")) nontemporal = atoi(e) != 0;   // (the load-policy A/B of tests/record_bench.py: the test build only)
 #endif
     hipStream_t st = (hipStream_t)stream;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int rc = NFC_OK;
-    auto bad = [&](hipError_t e, const char *what) {
-        if (e == hipSuccess) return false;
-        rc = fail(nullptr, NFC_ERR_DEVICE, "nfc_record_pcm16_device: %s: %s", what, hipGetErrorString(e));
-        return true;
+    Event e0, e1;
+    auto bad = [](hipError_t e, const char *what) {
+        return e == hipSuccess ? NFC_OK : fail(nullptr, NFC_ERR_DEVICE, "nfc_record_pcm16_device: %s: %s", what, hipGetErrorString(e));
     };
-    do {
-        if (kernel_ms && (bad(hipEventCreate(&e0), "event") || bad(hipEventCreate(&e1), "event"))) break;
-        launch_error() = LaunchError{};
-        rec::launch(input_kind, tap, dev_samples, n, scale_arg, gain, dev_pcm_out, cus, nontemporal, st, e0, e1);
-        if (bad(launch_error().err, "launch")) break;
-        // (the caller's stream: only enqueued there, nfc_stream_sync completes it -- unless the duration is asked for)
-        if ((!st || kernel_ms) && bad(hipStreamSynchronize(st), "kernel")) break;
-        if (kernel_ms && bad(hipEventElapsedTime(kernel_ms, e0, e1), "event")) break;
-    } while (0);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    return rc;
+    if (kernel_ms) {
+        if (int rc = bad(e0.create(), "event")) return rc;
+        if (int rc = bad(e1.create(), "event")) return rc;
+    }
+    launch_error() = LaunchError{};
+    rec::launch(input_kind, tap, dev_samples, n, scale_arg, gain, dev_pcm_out, cus, nontemporal, st, e0, e1);
+    if (int rc = bad(launch_error().err, "launch")) return rc;
+    // (the caller's stream: only enqueued there, nfc_stream_sync completes it -- unless the duration is asked for)
+    if (!st || kernel_ms)
+        if (int rc = bad(hipStreamSynchronize(st), "kernel")) return rc;
+    return kernel_ms ? bad(hipEventElapsedTime(kernel_ms, e0, e1), "event") : NFC_OK;
 }
 
 int16_t nfc_host_record_pcm16(float x, float gain) { return pcm16_of(x, gain); }
@@ -1590,6 +1507,11 @@ extern "C" int nfc_debug_gen_prof(unsigned long long *out, int reset) {
 // the frame assembly's two launches of the last batch by HIP events (nfc_set_timing >= 1 before the frames were first read; else 0):
 // what tests/frames_bench.py sets beside the batch's own time
 extern "C" float nfc_debug_frames_ms(const nfc_ctx *c) { return c && c->frames_ready ? c->fr_ms : -1.f; }
+// the HIP resources the library's owning handles (dev_buf.h) hold right now, every context and call of the process together: device blocks,
+// pinned blocks, events, streams -- equal before and after a lifecycle when nothing leaked
+extern "C" void nfc_debug_live_resources(uint64_t out[4]) {
+    for (int k = 0; k < 4; k++) out[k] = nfc::live::count(k).load();
+}
 // the decode kernels' dynamic LDS as this context launches them (which: 0 k_dec_spec, 1 k_dec_reduce, 2 k_dec_apply), and the
 // workgroups per CU the occupancy query gives the kernel with it
 extern "C" int nfc_debug_dec_lds(const nfc_ctx *c, int which, uint32_t *dyn_bytes, int *wgs_per_cu) {

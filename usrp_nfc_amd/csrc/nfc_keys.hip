@@ -15,6 +15,7 @@
 
 #include "../../include/nfc_amd.h"
 #include "launch_check.h"
+#include "dev_buf.h"
 #include "keys.hip.h"
 
 static_assert(sizeof(nfc_auth_trace) == 40 && sizeof(nfc_key_result) == 24 && sizeof(nfc_key_config) == 32 && sizeof(nfc_key_stats) == 56,
@@ -155,12 +156,12 @@ struct DeviceSearch {
     const Limits &L;
     nfc_key_stats &S;
     int rc = NFC_OK;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    Event e0, e1;
     size_t nv = 0;
     const Prepared *d_records = nullptr;
     const uint32_t *map = nullptr;   // [nv], the host's
     double ms_prelude = 0;
-    std::vector<void *> owned;   // device memory of the prelude's, freed at the end
+    std::vector<DevBuf> owned;   // device memory of the prelude's, released with the search
 
     bool bad(hipError_t e, int status = NFC_ERR_DEVICE) {
         if (e == hipSuccess) return false;
@@ -169,10 +170,10 @@ struct DeviceSearch {
     }
     template <class T>
     bool alloc(T *&p, size_t bytes) {
-        void *q = nullptr;
-        if (bad(hipMalloc(&q, bytes ? bytes : 1))) return false;
-        owned.push_back(q);
-        p = (T *)q;
+        DevBuf b;
+        if (bad(b.ensure(bytes ? bytes : 1))) return false;
+        p = b.as<T>();
+        owned.push_back(std::move(b));
         return true;
     }
     // one launch, timed by HIP events when asked
@@ -196,22 +197,20 @@ template <class Prelude, class RecordOf, class Sink>
 int device_search(int device, const Limits &L, nfc_key_stats &S, Prelude &&prelude, RecordOf &&record_of, Sink &&sink) {
     if (hipSetDevice(device) != hipSuccess) return NFC_ERR_DEVICE;
     DeviceSearch D{L, S};
-    uint8_t *small = nullptr;
-    uint64_t *scratch = nullptr;
+    DevBuf small_buf, scratch;
     uint64_t capacity = L.initial;
-    bool searched = false;
     auto bad = [&](hipError_t e) { return D.bad(e); };
-    do {
-        if (L.timing && (bad(hipEventCreate(&D.e0)) || bad(hipEventCreate(&D.e1)))) break;
-        if (!prelude(D) || D.nv == 0) break;
-        searched = true;
+    const bool searched = [&] {   // (false: it ended before there was anything to search; D.rc holds the status)
+        if (L.timing && (bad(D.e0.create()) || bad(D.e1.create()))) return false;
+        if (!prelude(D) || D.nv == 0) return false;
         const size_t nv = D.nv;
         const uint32_t mb = (uint32_t)std::min<size_t>(L.max_batch, nv);
         // the small per-batch arrays in one allocation: prep | place | counts [2 mb] | n_found [mb] | err [1] (padded) | min_key [mb] | map [mb]
         const size_t o_place = sizeof(Prepared) * mb, o_counts = o_place + sizeof(Place) * mb, o_found = o_counts + 8 * (size_t)mb,
                      o_err = o_found + 4 * (size_t)mb, o_min = (o_err + 4 + 7) & ~(size_t)7, o_map = o_min + 8 * (size_t)mb,
                      small_bytes = o_map + 4 * (size_t)mb;
-        if (bad(hipMalloc((void **)&small, small_bytes)) || bad(hipMalloc((void **)&scratch, capacity * 16))) break;
+        if (bad(small_buf.ensure(small_bytes)) || bad(scratch.ensure(capacity * 16))) return true;
+        uint8_t *const small = small_buf.as<uint8_t>();
         Prepared *d_prep = (Prepared *)small;
         Place *d_place = (Place *)(small + o_place);
         uint32_t *d_counts = (uint32_t *)(small + o_counts), *d_found = (uint32_t *)(small + o_found), *d_err = (uint32_t *)(small + o_err);
@@ -230,54 +229,48 @@ int device_search(int device, const Limits &L, nfc_key_stats &S, Prelude &&prelu
             // the batch's records, or where they lie; counts, found and err to 0, min_key to all ones
             if (D.d_records ? bad(hipMemcpy(d_map_buf, D.map + b0, 4 * (size_t)nb, hipMemcpyHostToDevice))
                             : bad(hipMemcpy(d_prep, prep.data(), sizeof(Prepared) * nb, hipMemcpyHostToDevice)))
-                break;
-            if (bad(hipMemsetAsync(d_counts, 0, o_min - o_counts, 0)) || bad(hipMemsetAsync(d_min, 0xFF, 8 * (size_t)mb, 0))) break;
-            if (!D.timed(S.ms_count, [&] { NFC_LAUNCH(k_keys_count, dim3(WINDOWS / KEYS_BLOCK, 2, nb), block, 0, 0, k_prep, k_map, d_counts); })) break;
-            if (bad(hipMemcpy(counts.data(), d_counts, 8 * (size_t)nb, hipMemcpyDeviceToHost))) break;   // (waits for the launch)
+                return true;
+            if (bad(hipMemsetAsync(d_counts, 0, o_min - o_counts, 0)) || bad(hipMemsetAsync(d_min, 0xFF, 8 * (size_t)mb, 0))) return true;
+            if (!D.timed(S.ms_count, [&] { NFC_LAUNCH(k_keys_count, dim3(WINDOWS / KEYS_BLOCK, 2, nb), block, 0, 0, k_prep, k_map, d_counts); })) return true;
+            if (bad(hipMemcpy(counts.data(), d_counts, 8 * (size_t)nb, hipMemcpyDeviceToHost))) return true;   // (waits for the launch)
             for (uint32_t i = 0; i < nb; i++) n_odd[i] = counts[2 * i];
             const Plan plan = plan_batch(n_odd.data(), nb, L.max);
             for (const Group &g : plan.groups) {
                 if (g.slots > capacity) {   // grow to fit: the old tables are not needed
-                    (void)hipFree(scratch);
-                    scratch = nullptr;
+                    scratch.release();
                     capacity = g.slots;
                     S.n_grown++;
-                    if (bad(hipMalloc((void **)&scratch, capacity * 16))) break;
+                    if (bad(scratch.ensure(capacity * 16))) return true;
                 }
                 for (uint32_t i = 0; i < nb; i++) {
                     const bool in = i >= g.t0 && i < g.t1 && plan.log2[i];
                     place[i] = Place{in ? plan.off[i] : 0, in ? plan.log2[i] : 0u, 0u};
                 }
-                uint64_t *sig_tab = scratch, *seq_tab = scratch + capacity;
+                uint64_t *sig_tab = scratch.as<uint64_t>(), *seq_tab = sig_tab + capacity;
                 if (bad(hipMemcpy(d_place, place.data(), sizeof(Place) * nb, hipMemcpyHostToDevice)) ||
                     bad(hipMemsetAsync(sig_tab, 0xFF, g.slots * 8, 0)))
-                    break;
+                    return true;
                 const dim3 grid(WINDOWS / KEYS_BLOCK, 1, g.t1 - g.t0);
                 if (!D.timed(S.ms_fill, [&] { NFC_LAUNCH(k_keys_fill_odd, grid, block, 0, 0, k_prep, k_map, d_place, g.t0, sig_tab, seq_tab, d_err); }))
-                    break;
+                    return true;
                 if (!D.timed(S.ms_probe,
                              [&] { NFC_LAUNCH(k_keys_probe_even, grid, block, 0, 0, k_prep, k_map, d_place, g.t0, sig_tab, seq_tab, d_found, d_min); }))
-                    break;
-                if (bad(hipStreamSynchronize(0))) break;   // (the next group rewrites d_place and the tables)
+                    return true;
+                if (bad(hipStreamSynchronize(0))) return true;   // (the next group rewrites d_place and the tables)
             }
-            if (D.rc != NFC_OK) break;
             uint32_t err = 0;
             if (bad(hipMemcpy(found.data(), d_found, 4 * (size_t)nb, hipMemcpyDeviceToHost)) ||
                 bad(hipMemcpy(min_key.data(), d_min, 8 * (size_t)nb, hipMemcpyDeviceToHost)) || bad(hipMemcpy(&err, d_err, 4, hipMemcpyDeviceToHost)))
-                break;
+                return true;
             if (err) {
                 D.rc = NFC_ERR_INTERNAL;
-                break;
+                return true;
             }
             for (uint32_t i = 0; i < nb; i++) sink(b0 + i, Verdict{plan.log2[i] == 0, found[i], counts[2 * i], counts[2 * i + 1], min_key[i]}, prep[i]);
             S.n_batches++;
         }
-    } while (0);
-    if (D.e0) (void)hipEventDestroy(D.e0);
-    if (D.e1) (void)hipEventDestroy(D.e1);
-    if (scratch) (void)hipFree(scratch);
-    if (small) (void)hipFree(small);
-    for (void *p : D.owned) (void)hipFree(p);
+        return true;
+    }();
     S.ms_kernels = S.ms_count + S.ms_fill + S.ms_probe + D.ms_prelude;
     S.scratch_bytes = searched ? capacity * 16 : 0;
     return D.rc;

@@ -8,6 +8,10 @@
 // (multi_fetch.hip.h), the frames by nfc_multi_fetch_frames (frames.hip.h), and with command tracking on the frames and the commands of
 // every push (multi_commands.hip.h: three launches behind the push's own, nfc_multi_fetch_commands copies).
 //
+// Who owns what: the stream, the events and every block of device or pinned memory are members of nfc_multi of dev_buf.h's owning types --
+// the blocks allocated once by nfc_multi_create in one vector (dev), the ones that grow by name -- so `delete m` releases the context,
+// nfc_multi_destroy only waits for the stream first, and a create that fails half way leaves nothing behind.
+//
 // The host side below, in the file's order: the context; its growable buffers (dev_buf.h; grow) and the layout of the three packed
 // ones (Sections: one rule, and the guard offsets the test build checks); the readers; the fetch; the frames; command tracking; the C-ABI.
 #include <hip/hip_runtime.h>
@@ -19,6 +23,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -46,19 +51,11 @@ static_assert(MF_EDGES == NFC_MULTI_FETCH_EDGES && MF_SYMBOLS == NFC_MULTI_FETCH
 static_assert(sizeof(nfc_multi_frames) == 144 && sizeof(nfc_multi_commands) == 264 && sizeof(nfc_frame) == 28, "the commands' structures are the header's");
 
 namespace {
-// a growable buffer as a member of the context: released with it
-template <class Buf>
-struct Owned : Buf {
-    Owned() = default;
-    Owned(const Owned &) = delete;
-    Owned &operator=(const Owned &) = delete;
-    ~Owned() { Buf::release(); }
-};
 // a packed buffer: on the device, its pinned twin, and where the launches that last filled the device's left GUARD_BYTES of the guard
 // word -- behind every section (Sections); empty: nowhere yet, or the buffer was replaced since
 struct Packed {
-    Owned<DevBuf> d;
-    Owned<PinBuf> h;
+    DevBuf d;
+    PinBuf h;
     std::vector<uint64_t> guards;
 };
 }  // namespace
@@ -71,15 +68,16 @@ struct nfc_multi {
     size_t bps = 0;   // input bytes per sample
     Caps C;
     Args A;           // everything of the launch that does not change from push to push
-    hipStream_t st = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    Stream st;   // (before every buffer and event: members go in reverse order, the stream last)
+    Event ev[2];
     int timing = 0;
     // allocated once, by nfc_multi_create
-    std::vector<void *> dev;   // every device allocation
-    uint8_t *h_up = nullptr;   // pinned: first_sample (u64) | n (u32) | order (u32), K each
+    std::vector<DevBuf> dev;   // every device block (alloc_plain, alloc_slab): the launch arguments and d_up, d_blob point into them
+    PinBuf h_up;               // pinned: first_sample (u64) | n (u32) | order (u32), K each
     uint8_t *d_up = nullptr;
-    uint32_t *h_counts = nullptr;   // pinned mirror of the counts
-    uint8_t *d_blob = nullptr, *h_blob = nullptr;   // one stream's state (k_multi_state_io)
+    PinBuf h_counts;           // pinned mirror of the counts
+    uint8_t *d_blob = nullptr;   // one stream's state (k_multi_state_io) ...
+    PinBuf h_blob;               // ... and its pinned twin
     size_t blob_bytes = 0;
     std::vector<std::pair<void *, size_t>> guards;   // (slab, row stride in bytes) -- rows end in GUARD_BYTES of the guard word
     std::vector<size_t> guard_row;                   // payload bytes per row
@@ -89,13 +87,13 @@ struct nfc_multi {
     uint8_t canon[16];
     bool have_outputs = false;
     // grown when a call needs more (grow), released with the context
-    Owned<PinBuf> h_stage;   // nfc_multi_push: the host arrays packed ...
-    Owned<DevBuf> d_stage;   // ... and their place on the device
-    Owned<PinBuf> h_read;    // staging of the per-stream readers
+    PinBuf h_stage;   // nfc_multi_push: the host arrays packed ...
+    DevBuf d_stage;   // ... and their place on the device
+    PinBuf h_read;    // staging of the per-stream readers
     // the fetch (multi_fetch.hip.h): the packed buffer, the prefix tables, what the host copy holds
     Packed fetch;
-    Owned<DevBuf> d_ftable;   // [MF_ARRAYS][K + 1]
-    Owned<PinBuf> h_ftable;   // the same, followed by base[K]
+    DevBuf d_ftable;   // [MF_ARRAYS][K + 1]
+    PinBuf h_ftable;   // the same, followed by base[K]
     uint32_t fetched = 0;     // NFC_MULTI_FETCH_* bits the host copy serves; 0: none (a push, a reset)
     nfc_multi_fetched fout;
     // the frames (frames.hip.h, nfc_multi_fetch_frames): a packed buffer of their own -- a fetch and a frame fetch do not end each
@@ -106,12 +104,12 @@ struct nfc_multi {
     // followed by base[K]
     enum CmdState { CMD_NONE, CMD_EMPTY, CMD_LAUNCHED };   // of the last push: not tracked (or reset since) / nothing stored / three launches
     bool track = false;
-    Owned<DevBuf> d_fsm, d_fsm_blob;
-    Owned<PinBuf> h_fsm_blob;
+    DevBuf d_fsm, d_fsm_blob;
+    PinBuf h_fsm_blob;
     // the sector key tables (sector_keys.h), [skeys::SLOTS][2][K] words, and one table's blob: there from the first
     // nfc_multi_set_sector_keys on, never before -- a null d_keys is "every table empty" to the kernel and to the calls
-    Owned<DevBuf> d_keys, d_keys_blob;
-    Owned<PinBuf> h_keys_blob;
+    DevBuf d_keys, d_keys_blob;
+    PinBuf h_keys_blob;
     Packed cmd;
     size_t cmd_bytes = 0;
     CmdState cmd_state = CMD_NONE;
@@ -119,7 +117,7 @@ struct nfc_multi {
     frames::MultiLayout cmd_frlay;   // of the last push that stored anything, as cmd_lay, cmd_nfr and cmd_room
     commands::Layout cmd_lay;
     uint64_t cmd_nfr[2] = {0, 0}, cmd_room[2] = {0, 0};
-    hipEvent_t evc[4] = {nullptr, nullptr, nullptr, nullptr};
+    Event evc[4];
     nfc_multi_commands cout;
     nfc_multi_stats stats;
     std::string err;
@@ -159,30 +157,27 @@ int launch_ok(nfc_multi *m) {
     return mfail(m, NFC_ERR_DEVICE, "kernel launch failed: %s (%s:%d)", hipGetErrorString(e.err), e.file, e.line);
 }
 
+// a block the context keeps for good (m->dev); null: the device has none of that size
+void *alloc_once(nfc_multi *m, size_t bytes) {
+    DevBuf b;
+    if (b.ensure(bytes) != hipSuccess) return (void)hipGetLastError(), nullptr;
+    m->dev.push_back(std::move(b));
+    return m->dev.back().p;
+}
 // a slab of K rows, each `row` payload bytes and GUARD_BYTES of the guard word behind them
 template <class T>
 int alloc_slab(nfc_multi *m, T **out, size_t row_bytes) {
     const size_t stride = row_bytes + GUARD_BYTES, total = stride * m->K;
-    void *p = nullptr;
-    if (hipMalloc(&p, total) != hipSuccess) {
-        (void)hipGetLastError();
+    if (!(*out = (T *)alloc_once(m, total)))
         return mfail(nullptr, NFC_ERR_NOMEM, "nfc_multi_create: no device memory for a slab of %zu bytes (n_streams %u)", total, m->K);
-    }
-    m->dev.push_back(p);
-    m->guards.emplace_back(p, stride);
+    m->guards.emplace_back(*out, stride);
     m->guard_row.push_back(row_bytes);
-    *out = (T *)p;
     return NFC_OK;
 }
 template <class T>
 int alloc_plain(nfc_multi *m, T **out, size_t bytes) {
-    void *p = nullptr;
-    if (hipMalloc(&p, std::max<size_t>(bytes, 16)) != hipSuccess) {
-        (void)hipGetLastError();
+    if (!(*out = (T *)alloc_once(m, std::max<size_t>(bytes, 16))))
         return mfail(nullptr, NFC_ERR_NOMEM, "nfc_multi_create: no device memory for %zu bytes (n_streams %u)", bytes, m->K);
-    }
-    m->dev.push_back(p);
-    *out = (T *)p;
     return NFC_OK;
 }
 
@@ -307,7 +302,7 @@ Sections frames_layout(const nfc_multi *m, frames::MultiLayout &F, uint64_t n_fr
     const size_t T = (size_t)m->K + 1;
     n_fr[0] = n_fr[1] = room[0] = room[1] = 0;
     for (uint32_t k = 0; k < m->K; k++) {
-        const uint32_t *c = m->h_counts + (size_t)k * CNT_WORDS;
+        const uint32_t *c = m->h_counts.as<uint32_t>() + (size_t)k * CNT_WORDS;
         for (int t = 0; t < 2; t++) {
             const uint64_t npk = std::min(c[CNT_PK0 + t], m->C.packets), bits = std::min(c[CNT_BITS0 + t], m->C.bits);
             n_fr[t] += npk;
@@ -380,8 +375,8 @@ int check_frame_totals(nfc_multi *m, const char *fn, const uint8_t *h, const uin
 int ensure_fsm(nfc_multi *m, const char *fn) {
     if (m->d_fsm.p) return NFC_OK;
     if (grow(m, m->d_fsm_blob, 256, fn, false) < 0 || grow(m, m->h_fsm_blob, 256, fn, false) < 0) return NFC_ERR_NOMEM;
-    for (hipEvent_t &e : m->evc)
-        if (!e && hipEventCreate(&e) != hipSuccess) {
+    for (Event &e : m->evc)
+        if (e.create() != hipSuccess) {
             (void)hipGetLastError();
             return mfail(m, NFC_ERR_DEVICE, "hipEventCreate failed");
         }
@@ -432,7 +427,7 @@ int enqueue_commands(nfc_multi *m) {
 
 // stream k's counts and flags of the last push, from the pinned mirror
 void counts_of(const nfc_multi *m, uint32_t k, nfc_counts &o, uint32_t *flags) {
-    const uint32_t *c = m->h_counts + (size_t)k * CNT_WORDS;
+    const uint32_t *c = m->h_counts.as<uint32_t>() + (size_t)k * CNT_WORDS;
     o.n_samples = m->last_n[k];
     o.n_edges = c[CNT_EDGES];
     o.n_symbols[0] = c[CNT_SYM0];
@@ -458,15 +453,7 @@ void nfc_multi_destroy(nfc_multi *m) {
     if (!m) return;
     (void)hipSetDevice(m->P.device);
     if (m->st) (void)hipStreamSynchronize(m->st);
-    for (void *p : m->dev) (void)hipFree(p);
-    for (hipEvent_t e : m->evc)
-        if (e) (void)hipEventDestroy(e);
-    for (uint8_t *p : {m->h_up, (uint8_t *)m->h_counts, m->h_blob})
-        if (p) (void)hipHostFree(p);
-    for (hipEvent_t e : m->ev)
-        if (e) (void)hipEventDestroy(e);
-    if (m->st) (void)hipStreamDestroy(m->st);
-    delete m;   // (and with it the buffers that grew)
+    delete m;   // (every buffer, the events and the stream are members that release themselves)
 }
 
 int nfc_multi_create(const nfc_params *p, const nfc_multi_config *c, nfc_multi **out) {
@@ -498,7 +485,8 @@ int nfc_multi_create(const nfc_params *p, const nfc_multi_config *c, nfc_multi *
     if (p->device < 0 || p->device >= ndev) return mfail(nullptr, NFC_ERR_ARG, "device %d out of range (%d devices)", p->device, ndev);
     if (hipSetDevice(p->device) != hipSuccess) return mfail(nullptr, NFC_ERR_DEVICE, "hipSetDevice failed");
 
-    nfc_multi *m = new nfc_multi();
+    std::unique_ptr<nfc_multi, void (*)(nfc_multi *)> owner(new nfc_multi(), nfc_multi_destroy);   // (a failure below: what there is waits, then goes)
+    nfc_multi *const m = owner.get();
     m->P = *p;
     m->K = c->n_streams;
     m->max_push = c->max_push_samples;
@@ -535,22 +523,18 @@ int nfc_multi_create(const nfc_params *p, const nfc_multi_config *c, nfc_multi *
         if (e__ != hipSuccess) {                                                                               \
             const int rc__ = mfail(nullptr, e__ == hipErrorOutOfMemory ? NFC_ERR_NOMEM : NFC_ERR_DEVICE, "nfc_multi_create: %s failed: %s", #call, hipGetErrorString(e__)); \
             (void)hipGetLastError();                                                                           \
-            nfc_multi_destroy(m);                                                                              \
             return rc__;                                                                                       \
         }                                                                                                      \
     } while (0)
 #define CRC(call)                      \
     do {                               \
         const int rc__ = (call);       \
-        if (rc__) {                    \
-            nfc_multi_destroy(m);      \
-            return rc__;               \
-        }                              \
+        if (rc__) return rc__;         \
     } while (0)
 
-    CRT(hipStreamCreateWithFlags(&m->st, hipStreamNonBlocking));
-    CRT(hipEventCreate(&m->ev[0]));
-    CRT(hipEventCreate(&m->ev[1]));
+    CRT(m->st.create());
+    CRT(m->ev[0].create());
+    CRT(m->ev[1].create());
     Args &A = m->A;
     memset(&A, 0, sizeof A);
     State &S = A.S;
@@ -576,10 +560,10 @@ int nfc_multi_create(const nfc_params *p, const nfc_multi_config *c, nfc_multi *
     }
     CRC(alloc_slab(m, &O.epos, (size_t)C.edges * 4));
     CRC(alloc_slab(m, &O.ecode, (size_t)C.edges * 2));
-    CRT(hipHostMalloc((void **)&m->h_up, (size_t)K * 16, hipHostMallocDefault));
-    CRT(hipHostMalloc((void **)&m->h_counts, (size_t)K * CNT_WORDS * 4, hipHostMallocDefault));
-    CRT(hipHostMalloc((void **)&m->h_blob, m->blob_bytes, hipHostMallocDefault));
-    memset(m->h_counts, 0, (size_t)K * CNT_WORDS * 4);
+    CRT(m->h_up.ensure((size_t)K * 16));
+    CRT(m->h_counts.ensure((size_t)K * CNT_WORDS * 4));
+    CRT(m->h_blob.ensure(m->blob_bytes));
+    memset(m->h_counts.p, 0, (size_t)K * CNT_WORDS * 4);
 
     // decoder LUTs in the walking form: next state | out byte << 8 per (LUT row, state)
     {
@@ -636,7 +620,7 @@ int nfc_multi_create(const nfc_params *p, const nfc_multi_config *c, nfc_multi *
     CRT(hipStreamSynchronize(m->st));
 #undef CRT
 #undef CRC
-    *out = m;
+    *out = owner.release();
     return NFC_OK;
 }
 
@@ -657,8 +641,8 @@ int nfc_multi_push_device(nfc_multi *m, const void *dev_base, const uint64_t *fi
     if ((uintptr_t)dev_base & 15u) return mfail(m, NFC_ERR_ARG, "dev_base must be 16-byte aligned");
     if (hipSetDevice(m->P.device) != hipSuccess) return mfail(m, NFC_ERR_DEVICE, "hipSetDevice failed");
     m->fetched = 0;   // the host copy is the last push's
-    uint64_t *hf = (uint64_t *)m->h_up;
-    uint32_t *hn = (uint32_t *)(m->h_up + (size_t)K * 8), *ho = (uint32_t *)(m->h_up + (size_t)K * 12);
+    uint64_t *hf = m->h_up.as<uint64_t>();
+    uint32_t *hn = (uint32_t *)(m->h_up.as<uint8_t>() + (size_t)K * 8), *ho = (uint32_t *)(m->h_up.as<uint8_t>() + (size_t)K * 12);
     memcpy(hf, first_sample, (size_t)K * 8);
     memcpy(hn, n, (size_t)K * 4);
     // Lanes of a wave walk until the longest of their streams ends: streams go to lanes by length, longest first, in classes of
@@ -673,13 +657,13 @@ int nfc_multi_push_device(nfc_multi *m, const void *dev_base, const uint64_t *fi
         for (uint32_t i = 0; i < classes; i++) at[i + 1] += at[i];
         for (uint32_t k = 0; k < K; k++) ho[at[classes - 1 - (n[k] + 511) / 512]++] = k;
     }
-    MCHK(m, hipMemcpyAsync(m->d_up, m->h_up, (size_t)K * 16, hipMemcpyHostToDevice, m->st));
+    MCHK(m, hipMemcpyAsync(m->d_up, m->h_up.p, (size_t)K * 16, hipMemcpyHostToDevice, m->st));
     Args A = m->A;
     A.in = dev_base;
     const dim3 grid((K + MB - 1) / MB), block(MB);
     if (m->timing) NFC_LAUNCH_EXT(kernel_of(m->P.input_kind), grid, block, 0, m->st, m->ev[0], m->ev[1], 0, A);
     else NFC_LAUNCH(kernel_of(m->P.input_kind), grid, block, 0, m->st, A);
-    MCHK(m, hipMemcpyAsync(m->h_counts, A.O.counts, (size_t)K * CNT_WORDS * 4, hipMemcpyDeviceToHost, m->st));
+    MCHK(m, hipMemcpyAsync(m->h_counts.p, A.O.counts, (size_t)K * CNT_WORDS * 4, hipMemcpyDeviceToHost, m->st));
     MCHK(m, hipStreamSynchronize(m->st));
     if (int rc = launch_ok(m)) return rc;
     uint32_t cut = 0;
@@ -687,7 +671,7 @@ int nfc_multi_push_device(nfc_multi *m, const void *dev_base, const uint64_t *fi
         m->g0[k] = m->nseen[k];
         m->nseen[k] += n[k];
         m->last_n[k] = n[k];
-        cut += (m->h_counts[(size_t)k * CNT_WORDS + CNT_FLAGS] & 15u) != 0;
+        cut += (m->h_counts.as<uint32_t>()[(size_t)k * CNT_WORDS + CNT_FLAGS] & 15u) != 0;
     }
     m->have_outputs = true;
     m->stats.ms_kernels = 0;
@@ -763,7 +747,7 @@ int nfc_multi_fetch(nfc_multi *m, uint32_t what, nfc_multi_fetched *out) {
     uint64_t *tab = m->h_ftable.as<uint64_t>(), *base = tab + MF_ARRAYS * T;
     Amounts run = {0, 0, 0, 0, 0, 0, 0};
     for (uint32_t k = 0; k < K; k++) {
-        const Amounts s = stored_amounts(m->h_counts + (size_t)k * CNT_WORDS, m->C, what);
+        const Amounts s = stored_amounts(m->h_counts.as<uint32_t>() + (size_t)k * CNT_WORDS, m->C, what);
         tab[0 * T + k] = run.a0;
         tab[1 * T + k] = run.a1;
         tab[2 * T + k] = run.a2;
@@ -895,7 +879,7 @@ int nfc_multi_read_edges(nfc_multi *m, uint32_t stream, size_t first, nfc_edge *
     if (!m) return NFC_ERR_ARG;
     LaunchScope scope(&m->launch_err);
     if (int rc = check_stream(m, stream, true)) return rc;
-    const size_t stored = std::min<size_t>(m->h_counts[(size_t)stream * CNT_WORDS + CNT_EDGES], m->C.edges);
+    const size_t stored = std::min<size_t>(m->h_counts.as<uint32_t>()[(size_t)stream * CNT_WORDS + CNT_EDGES], m->C.edges);
     size_t n = 0;
     if (first < stored) n = std::min(cap, stored - first);
     if (n && !out) return mfail(m, NFC_ERR_ARG, "null output");
@@ -937,7 +921,7 @@ int nfc_multi_read_symbols(nfc_multi *m, uint32_t stream, int type, size_t first
     if (type < 0 || type > 1) return mfail(m, NFC_ERR_ARG, "type must be 0 or 1");
     if (int rc = check_stream(m, stream, true)) return rc;
     if (served(m, NFC_MULTI_FETCH_SYMBOLS)) return read_fetched(m, NFC_MF_SYM0 + type, m->fout.symbols[type], stream, first, out, cap, n_out);
-    const size_t stored = std::min<size_t>(m->h_counts[(size_t)stream * CNT_WORDS + CNT_SYM0 + type], m->C.symbols);
+    const size_t stored = std::min<size_t>(m->h_counts.as<uint32_t>()[(size_t)stream * CNT_WORDS + CNT_SYM0 + type], m->C.symbols);
     return read_row(m, "nfc_multi_read_symbols", m->A.O.sym[type], m->C.s_symbols, 1, stream, stored, first, out, cap, n_out);
 }
 
@@ -945,7 +929,7 @@ int nfc_multi_read_packets(nfc_multi *m, uint32_t stream, int type, nfc_packet *
     if (!m) return NFC_ERR_ARG;
     if (type < 0 || type > 1) return mfail(m, NFC_ERR_ARG, "type must be 0 or 1");
     if (int rc = check_stream(m, stream, true)) return rc;
-    const size_t stored = std::min<size_t>(m->h_counts[(size_t)stream * CNT_WORDS + CNT_PK0 + type], m->C.packets);
+    const size_t stored = std::min<size_t>(m->h_counts.as<uint32_t>()[(size_t)stream * CNT_WORDS + CNT_PK0 + type], m->C.packets);
     const size_t n = std::min(cap, stored);
     if (n && !out) return mfail(m, NFC_ERR_ARG, "null output");
     if (n_out) *n_out = n;
@@ -977,7 +961,7 @@ int nfc_multi_read_packet_bits(nfc_multi *m, uint32_t stream, int type, size_t f
     if (type < 0 || type > 1) return mfail(m, NFC_ERR_ARG, "type must be 0 or 1");
     if (int rc = check_stream(m, stream, true)) return rc;
     if (served(m, NFC_MULTI_FETCH_PACKETS)) return read_fetched(m, NFC_MF_BITS0 + type, m->fout.packet_bits[type], stream, first, out, cap, n_out);
-    const size_t stored = std::min<size_t>(m->h_counts[(size_t)stream * CNT_WORDS + CNT_BITS0 + type], m->C.bits);
+    const size_t stored = std::min<size_t>(m->h_counts.as<uint32_t>()[(size_t)stream * CNT_WORDS + CNT_BITS0 + type], m->C.bits);
     return read_row(m, "nfc_multi_read_packet_bits", m->A.O.bits[type], m->C.s_bits, 1, stream, stored, first, out, cap, n_out);
 }
 
@@ -987,9 +971,9 @@ int nfc_multi_get_state(nfc_multi *m, uint32_t stream, nfc_state_header *h, floa
     if (!h) return mfail(m, NFC_ERR_ARG, "null header");
     if (int rc = check_stream(m, stream, false)) return rc;
     if (int rc = state_io(m, stream, 0)) return rc;
-    MCHK(m, hipMemcpyAsync(m->h_blob, m->d_blob, m->blob_bytes, hipMemcpyDeviceToHost, m->st));
+    MCHK(m, hipMemcpyAsync(m->h_blob.p, m->d_blob, m->blob_bytes, hipMemcpyDeviceToHost, m->st));
     MCHK(m, hipStreamSynchronize(m->st));
-    const IoHeader *io = (const IoHeader *)m->h_blob;
+    const IoHeader *io = m->h_blob.as<const IoHeader>();
     memset(h, 0, sizeof *h);
     h->n_seen = m->nseen[stream];
     h->ss = io->ss;
@@ -1011,7 +995,7 @@ int nfc_multi_get_state(nfc_multi *m, uint32_t stream, nfc_state_header *h, floa
     if (pending && pending_cap < p0 + p1) return mfail(m, NFC_ERR_ARG, "pending-bit buffer too small");
     if (pending && (p0 > m->C.pending || p1 > m->C.pending))
         return mfail(m, NFC_ERR_STATE, "stream %u: an open packet outgrew cap_pending_bits (NFC_MULTI_PENDING_OVERFLOW): reset the stream", stream);
-    const uint8_t *b = m->h_blob + sizeof(IoHeader);
+    const uint8_t *b = m->h_blob.as<uint8_t>() + sizeof(IoHeader);
     if (ring) memcpy(ring, b, (size_t)m->L * 4);
     b += (size_t)m->L * 4;
     if (pending && p0) memcpy(pending, b, p0);
@@ -1034,8 +1018,8 @@ int nfc_multi_set_state(nfc_multi *m, uint32_t stream, const nfc_state_header *h
     if (p0 + p1 != pending_len || ((p0 + p1) && !pending)) return mfail(m, NFC_ERR_ARG, "pending bits do not match the header");
     if (p0 > m->C.pending || p1 > m->C.pending) return mfail(m, NFC_ERR_ARG, "pending bits exceed cap_pending_bits = %u", m->C.pending);
     MCHK(m, hipStreamSynchronize(m->st));
-    memset(m->h_blob, 0, m->blob_bytes);
-    IoHeader *io = (IoHeader *)m->h_blob;
+    memset(m->h_blob.p, 0, m->blob_bytes);
+    IoHeader *io = m->h_blob.as<IoHeader>();
     io->ss = h->ss;
     io->filled = h->filled;
     // (the slot of the first stable sample while the window fills; of the next sample afterwards)
@@ -1045,12 +1029,12 @@ int nfc_multi_set_state(nfc_multi *m, uint32_t stream, const nfc_state_header *h
     io->npend[0] = (uint32_t)p0;
     io->npend[1] = (uint32_t)p1;
     io->flags = 0;
-    uint8_t *b = m->h_blob + sizeof(IoHeader);
+    uint8_t *b = m->h_blob.as<uint8_t>() + sizeof(IoHeader);
     memcpy(b, ring, (size_t)m->L * 4);
     b += (size_t)m->L * 4;
     if (p0) memcpy(b, pending, p0);
     if (p1) memcpy(b + m->C.pending, pending + p0, p1);
-    MCHK(m, hipMemcpyAsync(m->d_blob, m->h_blob, m->blob_bytes, hipMemcpyHostToDevice, m->st));
+    MCHK(m, hipMemcpyAsync(m->d_blob, m->h_blob.p, m->blob_bytes, hipMemcpyHostToDevice, m->st));
     if (int rc = state_io(m, stream, 1)) return rc;
     // the stream's outputs of the last push are void: its counts go to 0 on the device as in the mirror (a later fetch scans them)
     m->fetched = 0;
@@ -1061,7 +1045,7 @@ int nfc_multi_set_state(nfc_multi *m, uint32_t stream, const nfc_state_header *h
     m->nseen[stream] = h->n_seen;
     m->g0[stream] = h->n_seen;
     m->last_n[stream] = 0;
-    memset(m->h_counts + (size_t)stream * CNT_WORDS, 0, CNT_WORDS * 4);
+    memset(m->h_counts.as<uint32_t>() + (size_t)stream * CNT_WORDS, 0, CNT_WORDS * 4);
     return NFC_OK;
 }
 
@@ -1083,7 +1067,7 @@ int nfc_multi_reset(nfc_multi *m, int64_t stream) {
     for (uint32_t k = k0; k < k1; k++) {
         m->nseen[k] = m->g0[k] = 0;
         m->last_n[k] = 0;
-        memset(m->h_counts + (size_t)k * CNT_WORDS, 0, CNT_WORDS * 4);
+        memset(m->h_counts.as<uint32_t>() + (size_t)k * CNT_WORDS, 0, CNT_WORDS * 4);
     }
     if (stream < 0) m->have_outputs = false;
     return NFC_OK;
@@ -1119,14 +1103,13 @@ static int ensure_keys(nfc_multi *m, const char *fn) {
     if (m->d_keys.p) return NFC_OK;
     const size_t blob = (size_t)skeys::WORDS * 4, bytes = blob * m->K;
     if (grow(m, m->d_keys_blob, blob, fn, false) < 0 || grow(m, m->h_keys_blob, blob, fn, false) < 0) return NFC_ERR_NOMEM;
-    Owned<DevBuf> fresh;
+    DevBuf fresh;
     if (fresh.ensure(bytes) != hipSuccess) {
         (void)hipGetLastError();
         return mfail(m, NFC_ERR_NOMEM, "%s: no device memory for %zu bytes", fn, bytes);
     }
     MCHK(m, hipMemsetAsync(fresh.p, 0, fresh.cap, m->st));
-    std::swap(m->d_keys.p, fresh.p);   // (only a zeroed buffer is ever the context's)
-    std::swap(m->d_keys.cap, fresh.cap);
+    std::swap(m->d_keys, fresh);   // (only a zeroed buffer is ever the context's)
     return NFC_OK;
 }
 
@@ -1319,16 +1302,16 @@ static int packed_guards_damaged(nfc_multi *m, const Packed &p) {
 extern "C" int nfc_debug_multi_guards(nfc_multi *m) {
     if (!m || hipSetDevice(m->P.device) != hipSuccess) return -1;
     LaunchScope scope(&m->launch_err);
-    uint32_t *bad = nullptr;   // (a word of its own: the state blob stays the state calls')
-    if (hipMalloc((void **)&bad, 16) != hipSuccess) return -1;
-    struct Free { void *p; ~Free() { (void)hipFree(p); } } free_bad{bad};
+    DevBuf bad_word;   // (a word of its own: the state blob stays the state calls')
+    if (bad_word.ensure(16) != hipSuccess) return -1;
+    uint32_t *const bad = bad_word.as<uint32_t>();
     if (hipMemsetAsync(bad, 0, 4, m->st) != hipSuccess) return -1;
     for (size_t i = 0; i < m->guards.size(); i++)
         NFC_LAUNCH(k_multi_guard_check, dim3(std::min<uint32_t>(1024, (m->K * 4 + 255) / 256)), dim3(256), 0, m->st, (const uint8_t *)m->guards[i].first,
                    m->guards[i].second, m->guard_row[i], m->K, bad);
     uint32_t h = 0;
-    if (launch_ok(m) || hipMemcpyAsync(m->h_blob, bad, 4, hipMemcpyDeviceToHost, m->st) != hipSuccess || hipStreamSynchronize(m->st) != hipSuccess) return -1;
-    memcpy(&h, m->h_blob, 4);
+    if (launch_ok(m) || hipMemcpyAsync(m->h_blob.p, bad, 4, hipMemcpyDeviceToHost, m->st) != hipSuccess || hipStreamSynchronize(m->st) != hipSuccess) return -1;
+    memcpy(&h, m->h_blob.p, 4);
     // ... and the guards behind the sections of the three packed buffers, where the launches that last filled each left them
     for (const Packed *p : {&m->fetch, &m->frames, &m->cmd}) {
         const int bad_bytes = packed_guards_damaged(m, *p);
