@@ -284,7 +284,7 @@ enum {
 enum {
     NFC_FRAME_EXTRA_ERROR = 1,      /* "EXTRA ERROR" (fsm.py:61) */
     NFC_FRAME_MANY_MORE_ERROR = 2,  /* "MANY MORE ERROR" (fsm.py:65) */
-    NFC_FRAME_UID_MISMATCH = 4,     /* "MISMATCH BETWEEN READER-TAG UID" (fsm.py:186,195) */
+    NFC_FRAME_UID_MISMATCH = 4,     /* "MISMATCH BETWEEN READER-TAG UID" / "... READER_TAG UID#2" at a SEL2R (fsm.py:184,192) */
     NFC_FRAME_ENCRYPTED = 8,        /* a CRYPTO1 session was up: the frame was decrypted first (fsm.py:133-154) */
     NFC_FRAME_AR_OK = 16, NFC_FRAME_AR_ERROR = 32,   /* reader answer vs suc64(nt): "AR OK" / "ERROR WITH AR" (fsm.py:203-208) */
     NFC_FRAME_AT_OK = 64, NFC_FRAME_AT_ERROR = 128   /* tag answer vs suc96(nt) (fsm.py:209-214) */
@@ -583,7 +583,8 @@ enum { NFC_FSM_LOST = 1, NFC_FSM_UID_OVERFLOW = 2 };   /* nfc_fsm_state.flags, s
 typedef struct nfc_fsm_state {      /* 88 bytes */
     int32_t cur_cmd;                /* the command in flight (index for nfc_command_info) */
     int32_t tag_type;               /* -1 none, 0 Ultralight, 1 Classic 1K, 2 Classic 4K, 3 DESFire */
-    int32_t encrypted;              /* a CRYPTO1 session is up */
+    int32_t encrypted;              /* a CRYPTO1 session is up: 1; 2: up, but its nonce register was not 32 bits (a UID that is not four
+                                     * bytes under a nested tag nonce), so that no {ar} / {at} is ever reported as right */
     int32_t cur_key;                /* 0: key A, 1: key B, 2 + slot: that slot of the sector key table (below) */
     uint64_t cipher;                /* the 48-bit register; bit i is the i-th oldest bit */
     uint8_t ar[4], at[4];           /* the expected reader / tag answers */

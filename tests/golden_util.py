@@ -8,7 +8,7 @@ import numpy as np
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 
 PATH_CASES = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN, 'fx_*.npz'))
-                    if os.path.basename(p) not in ('fx_decoder_vectors.npz', 'fx_ultralight_iq.npz', 'fx_nonfinite_iq.npz'))
+                    if os.path.basename(p) not in ('fx_decoder_vectors.npz', 'fx_ultralight_iq.npz', 'fx_nonfinite_iq.npz', 'fx_fsm_fuzz.npz'))
 
 
 class Case(object):

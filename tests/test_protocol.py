@@ -194,6 +194,81 @@ def test_process_outgoing_before_a_tag_type_and_with_an_ultralight():
     assert out == sel and len(seen) == 1   # (through process_bits: the callback saw the frame)
 
 
+def _tag_emulator_up_to_the_nonce(hear_sel2r):
+    """A tag emulator through the anticollision of the Classic trace up to the AUTHA it hears.  It learns its UID from the SEL1R it
+    hears (process_outgoing runs no process_command): with that frame's parity broken the UID stays EMPTY; a SEL2R heard behind it
+    appends four more bytes (a mismatch), eight in all.  -> (emulator, a monitor that heard every frame, the plain tag nonce's bits)"""
+    from usrp_nfc_amd import synth
+    packets, _ = packets_from_trace(GOLD_1K)
+    ct = command.CommandType
+    emu = fsm.fsm(callback=lambda cmd, st: None, out=io.StringIO())
+    mon = fsm.fsm(callback=lambda cmd, st: None, out=io.StringIO())
+    sel1r = list(packets[4][1])
+    if not hear_sel2r:
+        sel1r[8] ^= 1
+    sel2r = synth.frame_bits([0x95, 0x70, 0x22, 0x09, 0x29, 0x80, 0x82, 0xD8, 0xBA])
+    for t, bits, cmd in ((1, packets[0][1], None), (0, packets[1][1], ct.ATQA1K), (1, packets[2][1], None), (0, packets[3][1], ct.ANTI1G), (1, sel1r, None),
+                         (0, packets[5][1], ct.SEL1K)) + (((1, sel2r, None),) if hear_sel2r else ()) + ((1, packets[6][1], None),):
+        if t == 1:
+            emu.process_bits(bits, t)
+        else:
+            assert emu.process_outgoing(list(bits), cmd) == list(bits)
+        if cmd is not ct.ANTI1G:   # (the monitor does not see the tag's UID either: it knows what the emulator knows, from the SELs)
+            mon.process_bits(bits, t)
+    return emu, mon, list(packets[7][1])
+
+
+def test_process_outgoing_starts_a_session_with_an_empty_uid():
+    # fsm.py:86-97: the reference installs the new cipher whatever the UID is -- no UID bits to mix, the whole nonce loaded (ADVICE, round 6)
+    from usrp_nfc_amd import synth
+    emu, mon, nonce = _tag_emulator_up_to_the_nonce(hear_sel2r=False)
+    assert emu.get_state().uid_len == 0 and emu.get_state().encrypted == 0
+    assert emu.process_outgoing(nonce, command.CommandType.RANDTA) == nonce        # the first nonce goes out in the clear
+    assert mon.process_bits(nonce, 0).name() == 'RANDTA'
+    se, sm = emu.get_state(), mon.get_state()
+    assert se.encrypted == 1 and sm.encrypted == 1 and se.cipher == sm.cipher and bytes(se.ar) == bytes(sm.ar) and bytes(se.at) == bytes(sm.at)
+    at = synth.frame_bits(list(bytearray(se.at)))
+    mon.process_bits(synth.frame_bits([0] * 8), 1)                                   # (some {nr}{ar}: four bytes are fed back, the emulator hears the same)
+    emu.process_bits(synth.frame_bits([0] * 8), 1)
+    air = emu.process_outgoing(at, command.CommandType.RANDTB)
+    assert air != at                                                                 # the session is up: the answer is encrypted ...
+    st = mon.process_bits(air, 0)
+    assert st is not None and st.all_bytes() == list(bytearray(se.at))               # ... and the monitor's session decrypts it
+
+
+def test_process_outgoing_where_the_reference_raises_leaves_the_session_as_it_was():
+    # a UID longer than the nonce (eight bytes), and a nonce frame shorter than the UID under a session that is up: the reference raises
+    # before it installs anything (fsm.py:96-97).  The project installs nothing either: no session starts, a session that is up keeps
+    # its register (ADVICE, round 6: it used to continue with a freshly keyed one)
+    emu, _, nonce = _tag_emulator_up_to_the_nonce(hear_sel2r=True)
+    assert emu.get_state().uid_len == 8
+    assert emu.process_outgoing(nonce, command.CommandType.RANDTA) == nonce
+    st = emu.get_state()
+    assert st.encrypted == 0 and st.cipher == 0 and bytes(st.ar) == bytes(st.at) == bytes(4)
+    at = [1, 0] * 18
+    assert emu.process_outgoing(at, command.CommandType.RANDTB) == at               # nothing is encrypted
+    # under a session: the first authentication of the trace as a tag emulator, then a nested nonce cut to three bytes
+    packets, _ = packets_from_trace(GOLD_1K)
+    seen = []
+    mon = fsm.fsm(callback=lambda cmd, st: seen.append((cmd, st)), out=io.StringIO())
+    emu = fsm.fsm(callback=lambda cmd, st: None, out=io.StringIO())
+    from usrp_nfc_amd import synth
+    for t, air in packets[:19]:
+        mon.process_bits(air, t)
+        cmd, s = seen[-1]
+        if t == 1:
+            emu.process_bits(air, t)
+        else:
+            emu.process_outgoing(synth.frame_bits(s.all_bytes()), cmd)
+    before = emu.get_state()
+    assert before.encrypted == 1 and before.uid_len == 4
+    cut = synth.frame_bits([0x01, 0x02, 0x03])
+    out = emu.process_outgoing(cut, command.CommandType.RANDTA)
+    after = emu.get_state()
+    assert out != cut and len(out) == len(cut)
+    assert (after.encrypted, after.cipher, bytes(after.ar), bytes(after.at)) == (1, before.cipher, bytes(before.ar), bytes(before.at))
+
+
 @pytest.mark.gpu
 def test_classic_1k_capture_to_trace_on_gpu():
     # BASELINE.json configs[3] in miniature: the MIFARE Classic 1K transaction of outputs/1k_with_enc.out, synthesised

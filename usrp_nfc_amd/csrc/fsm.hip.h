@@ -156,7 +156,7 @@ NFC_HD uint32_t nonce_advance(uint32_t x, int ticks) {
 
 // ---- the machine in scalars ----
 struct Machine {
-    int32_t cur_cmd, tag_type, encrypted, cur_key;   // cur_key: 0 / 1 key A / B, 2 + slot of the sector key table (sector_keys.h)
+    int32_t cur_cmd, tag_type, encrypted, cur_key;   // encrypted: 0, 1 a session, 2 a session whose ar / at nothing equals; cur_key: 0 / 1 key A / B, 2 + slot of the sector key table (sector_keys.h)
     uint64_t st, key_a, key_b;   // 48 bits each; a key's byte 0 lowest: load_key's bit order makes the key the register
     uint32_t ar, at;             // byte 0 lowest
     uint32_t uid_len, flags;
@@ -299,8 +299,6 @@ NFC_HD void uid_append(Machine &M, const Bytes &B, uint32_t from, uint32_t n) {
     for (uint32_t j = 0; j < n; j++) uid_put(M, M.uid_len + j, B.at(from + j));
     M.uid_len += n;
 }
-// how many UID bytes Crypto1::set_tag takes: its bit buffer holds 64 entries and a byte must fit whole, with or without a parity place
-NFC_HD uint32_t set_tag_bytes(const Machine &M) { return M.uid_len < 7u ? M.uid_len : 7u; }
 
 // protocol.h: fsm_finish.  nb plaintext bytes (0: a parity error, or nothing left), the first 20 of them in B.  tab: the stream's sector
 // key table (sector_keys.h), read only where an AUTH command is recognised and where a nonce loads the register.
@@ -365,22 +363,20 @@ NFC_HD void finish(Machine &M, uint32_t nb, int type, Rec &out, const Bytes &B, 
         if (!M.encrypted) {   // first authentication: the tag nonce came in the clear; uid ^ nonce goes into a fresh register
             M.st = skeys::resolve(tab, M.cur_key, M.key_a, M.key_b);
             M.ar = M.at = 0;
-            const uint32_t nonce = B.word_at(h), nu = set_tag_bytes(M);
-            if (nu >= 1u && nu <= 4u) {   // (set_tag: nothing at all with no UID or with more UID bits than the nonce has)
+            const uint32_t nonce = B.word_at(h), nu = M.uid_len;
+            if (nu <= 4u) {   // the UID bytes there are go in, none included (set_tag: nothing at all with more UID bits than the nonce has)
                 for (uint32_t i = 0; i < nu; i++) {
                     const uint32_t x = uid_byte(M, i) ^ ((nonce >> (8u * i)) & 0xFFu);
                     for (int k = 0; k < 8; k++) M.st = shift_in(M.st, (x >> k) & 1u);
                 }
-                if (nu == 4u) {
-                    M.ar = nonce_advance(nonce, 64);
-                    M.at = nonce_advance(M.ar, 32);
-                    M.encrypted = 1;
-                }
+                M.ar = nonce_advance(nonce, 64);
+                M.at = nonce_advance(M.ar, 32);
+                M.encrypted = 1;
             }
         }
         break;
-    case C_RANDRB: out.flags |= (M.encrypted && B.word_at(h + 4u) == M.ar) ? NFC_FRAME_AR_OK : NFC_FRAME_AR_ERROR; break;
-    case C_RANDTB: out.flags |= (M.encrypted && B.word_at(h) == M.at) ? NFC_FRAME_AT_OK : NFC_FRAME_AT_ERROR; break;
+    case C_RANDRB: out.flags |= (M.encrypted == 1 && B.word_at(h + 4u) == M.ar) ? NFC_FRAME_AR_OK : NFC_FRAME_AR_ERROR; break;
+    case C_RANDTB: out.flags |= (M.encrypted == 1 && B.word_at(h) == M.at) ? NFC_FRAME_AT_OK : NFC_FRAME_AT_ERROR; break;
     default: break;
     }
 }
@@ -420,7 +416,7 @@ NFC_HD Rec process_frame(Machine &M, int type, uint32_t raw_flags, uint32_t n, c
         if (nested) {
             M.st = skeys::resolve(tab, M.cur_key, M.key_a, M.key_b);
             M.ar = M.at = 0;
-            const uint32_t nu = set_tag_bytes(M);
+            const uint32_t nu = M.uid_len;
             todo = (nu >= 1u && nu <= n) ? nu : 0u;   // (set_tag: nothing at all with no UID or a frame shorter than the UID)
         }
         bool bad = false;
@@ -449,13 +445,13 @@ NFC_HD Rec process_frame(Machine &M, int type, uint32_t raw_flags, uint32_t n, c
         }
         nb = todo;
         if (nested && todo) {
-            if (todo >= 4u) {   // 32 nonce bits were there: the answers are set even when the frame then fails its parity
+            if (todo == 4u) {   // a nonce register of 32 bits: the answers are set even when the frame then fails its parity
                 M.ar = nonce_advance(nonce, 64);
                 M.at = nonce_advance(M.ar, 32);
+                M.encrypted = 1;
             } else {
-                nb = 0;
+                M.encrypted = 2;   // (as many nonce bits as UID bits: answers of another length, which nothing equals)
             }
-            if (M.uid_len > todo) nb = 0;   // (a UID longer than set_tag takes: the host machine pads the plaintext with zero groups, which fail parity)
         }
         if (bad) nb = 0;
         crc_ok = nb >= 2u && p2 == (crc & 0xFFu) && p1 == (crc >> 8);
@@ -497,7 +493,7 @@ NFC_HD void machine_to_state(const Machine &M, nfc_fsm_state &s) {
 inline const char *state_fault(const nfc_fsm_state &s) {
     if (s.cur_cmd < 0 || s.cur_cmd >= C_COUNT) return "cur_cmd out of range";
     if (s.tag_type < -1 || s.tag_type > 3) return "tag_type out of range";
-    if (s.encrypted != 0 && s.encrypted != 1) return "encrypted must be 0 or 1";
+    if (s.encrypted < 0 || s.encrypted > 2) return "encrypted must be 0, 1 or 2";
     if (s.cur_key < 0 || s.cur_key > skeys::CUR_KEY_MAX) return "cur_key must be 0, 1 or 2 + a slot below 80";
     if (s.cipher >> 48) return "cipher holds more than 48 bits";
     if (s.uid_len > UID_CAP) return "uid_len exceeds 32";

@@ -229,28 +229,35 @@ struct Crypto1 {
         advance(32);
         bytes(at);
     }
-    // cipher.py:62-72: mix uid ^ tag nonce into the register.  Plain nonce (first authentication): 32 bits in,
-    // nothing returned.  Encrypted nonce (nested authentication): 36 bits with parity in, the decrypted 36 out.
-    bool set_tag(const std::vector<uint8_t> &uid, const uint8_t *nonce, size_t n_nonce, bool encrypted, uint8_t *plain_out) {
-        uint8_t ub[64], xb[64], kb[64];
-        size_t ll = 0;
-        for (size_t k = 0; k < uid.size() && ll + 9 <= sizeof ub; k++) {
-            for (int i = 0; i < 8; i++) ub[ll++] = (uint8_t)((uid[k] >> i) & 1);
-            if (encrypted) ub[ll++] = 0;   // cipher.py:54-60: a zero where the parity bit sits
+    // cipher.py:62-72: mix uid ^ tag nonce into the register.  Plain nonce (first authentication): nothing returned.  Encrypted nonce
+    // (nested authentication): the frame's bits with parity in, the decrypted nine bits per UID byte out.  The UID bits THERE ARE go in --
+    // none, three bytes' -- and the nonce register (lfsr.py) is loaded with the whole plain nonce, or with the decrypted bits under the UID.
+    // -> the nonce register's bit count: 32 and ar / at are set; another count and the reference's answers have that many bits, so that
+    // no {ar} / {at} ever equals them (the caller keeps that as encrypted == 2); -1 where the reference raises -- more UID bits than
+    // nonce bits (IndexError), a nonce register of no bits (ZeroDivisionError in lfsr.py) -- with the register left at the key.
+    int set_tag(const std::vector<uint8_t> &uid, const uint8_t *nonce, size_t n_nonce, bool encrypted, uint8_t *plain_out) {
+        std::vector<uint8_t> ub;
+        for (size_t k = 0; k < uid.size(); k++) {
+            for (int i = 0; i < 8; i++) ub.push_back((uint8_t)((uid[k] >> i) & 1));
+            if (encrypted) ub.push_back(0);   // cipher.py:54-60: a zero where the parity bit sits
         }
-        if (n_nonce < ll || ll == 0) return false;   // (IndexError in the reference)
+        const size_t ll = ub.size();
+        if (n_nonce < ll || (encrypted ? ll : n_nonce) == 0) return -1;
+        std::vector<uint8_t> xb(ll + 1), kb(ll + 1);
         for (size_t i = 0; i < ll; i++) xb[i] = ub[i] ^ (nonce[i] & 1);
-        crypt(xb, ll, kb, 1, encrypted ? 1 : 0, encrypted ? 1 : 0);
+        crypt(xb.data(), ll, kb.data(), 1, encrypted ? 1 : 0, encrypted ? 1 : 0);
         uint8_t nb[32];
         size_t m = 0;
-        for (size_t i = 0; i < ll; i++) {
+        for (size_t i = 0; i < (encrypted ? ll : n_nonce); i++) {
             const uint8_t pb = encrypted ? (uint8_t)(ub[i] ^ kb[i]) : (uint8_t)(nonce[i] & 1);
-            if (plain_out) plain_out[i] = pb;
-            if ((!encrypted || i % 9 != 8) && m < 32) nb[m++] = pb;
+            if (plain_out && encrypted) plain_out[i] = pb;
+            if (!encrypted || i % 9 != 8) {
+                if (m < 32) nb[m] = pb;
+                m++;
+            }
         }
-        if (m != 32) return false;
-        set_answers(nb);
-        return true;
+        if (m == 32) set_answers(nb);
+        return (int)m;
     }
 };
 
@@ -268,7 +275,7 @@ struct nfc_fsm {
     }
     int cur_cmd = nfc::CMD_REQA;
     int tag_type = -1;          // -1 none, 0 Ultralight, 1 Classic 1K, 2 Classic 4K, 3 DESFire (command.py:70-74)
-    int encrypted = 0;          // a CRYPTO1 session is up (fsm._encryption)
+    int encrypted = 0;          // a CRYPTO1 session is up (fsm._encryption): 1, or 2 when its nonce register was not 32 bits (no answer matches)
     nfc::Crypto1 cipher;
     uint8_t key_a[6] = {0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF}, key_b[6] = {0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF};   // fsm.py:157-160
     int cur_key = 0;            // 0: key_a, 1: key_b, 2 + slot: that slot of `table` (sector_keys.h)
@@ -325,9 +332,9 @@ inline int fsm_strip(nfc_fsm &F, std::vector<uint8_t> &bits, nfc_frame *out, uin
             F.cipher = Crypto1();
             F.load_cur_key(F.cipher);
             plain.assign(bits.size(), 0);
-            size_t ll = F.uid.size() * 9;
-            if (!F.cipher.set_tag(F.uid, bits.data(), bits.size(), true, plain.data())) ll = 0;
-            plain.resize(ll);
+            const int m = F.cipher.set_tag(F.uid, bits.data(), bits.size(), true, plain.data());
+            if (m > 0) F.encrypted = m == 32 ? 1 : 2;
+            plain.resize(m > 0 ? F.uid.size() * 9 : 0);   // (-1, where the reference raises: nothing is left, a parity error)
         } else {
             F.cipher.crypt(bits.data(), bits.size(), plain.data(), 0, 0, 1);
         }
@@ -410,14 +417,15 @@ inline void fsm_finish(nfc_fsm &F, int nb, int type, nfc_frame *out, uint8_t *by
             F.load_cur_key(F.cipher);
             uint8_t nb[32];
             for (int i = 0; i < 32; i++) nb[i] = (uint8_t)((extra[i >> 3] >> (i & 7)) & 1);
-            if (out->n_extra >= 4 && F.cipher.set_tag(F.uid, nb, 32, false, nullptr)) F.encrypted = 1;
+            // a UID of up to four bytes starts the session, whatever its length; a longer one (the reference raises) leaves none
+            if (out->n_extra >= 4 && F.cipher.set_tag(F.uid, nb, 32, false, nullptr) > 0) F.encrypted = 1;
         }
         break;
     case CMD_RANDRB:   // fsm.py:203-208
-        out->flags |= (F.encrypted && memcmp(extra + 4, F.cipher.ar, 4) == 0) ? NFC_FRAME_AR_OK : NFC_FRAME_AR_ERROR;
+        out->flags |= (F.encrypted == 1 && memcmp(extra + 4, F.cipher.ar, 4) == 0) ? NFC_FRAME_AR_OK : NFC_FRAME_AR_ERROR;
         break;
     case CMD_RANDTB:   // fsm.py:209-214
-        out->flags |= (F.encrypted && memcmp(extra, F.cipher.at, 4) == 0) ? NFC_FRAME_AT_OK : NFC_FRAME_AT_ERROR;
+        out->flags |= (F.encrypted == 1 && memcmp(extra, F.cipher.at, 4) == 0) ? NFC_FRAME_AT_OK : NFC_FRAME_AT_ERROR;
         break;
     default: break;
     }
@@ -499,17 +507,21 @@ inline int fsm_process_outgoing(nfc_fsm &F, const uint8_t *bits, size_t n, int c
                 F.cipher.crypt(bits, n, out, 0, 0, 1);
             }
         } else if (cmd == CMD_RANDTA) {
-            // the tag's nonce: a fresh register keyed for the sector takes uid ^ nonce; under a session that is already up
-            // (nested authentication) the OLD register encrypts what goes on the air
+            // the tag's nonce: a fresh register keyed for the sector takes uid ^ nonce -- the UID bits there are, the nonce bits there are
+            // (fsm.py:86-97) -- and becomes the session; under a session that is already up (nested authentication) the OLD register
+            // encrypts what goes on the air.  Where the reference raises (set_tag: -1) it has installed nothing: the session stays as it was.
             Crypto1 old = F.cipher;
             const bool was = F.encrypted != 0;
-            uint8_t nb[32];
-            size_t m = 0;
-            for (size_t i = 0; i < n && m < 32; i++)
-                if (i % 9 != 8) nb[m++] = bits[i] & 1;
-            F.cipher = Crypto1();
-            F.load_cur_key(F.cipher);
-            if (m == 32 && F.cipher.set_tag(F.uid, nb, 32, false, nullptr)) F.encrypted = 1;
+            std::vector<uint8_t> nb;
+            for (size_t i = 0; i < n; i++)
+                if (i % 9 != 8) nb.push_back(bits[i] & 1);
+            Crypto1 fresh;
+            F.load_cur_key(fresh);
+            const int m = fresh.set_tag(F.uid, nb.data(), nb.size(), false, nullptr);
+            if (m > 0) {
+                F.cipher = fresh;
+                F.encrypted = m == 32 ? 1 : 2;
+            }
             if (was) old.crypt(bits, n, out, 0, 0, 1);
         }
         return 0;

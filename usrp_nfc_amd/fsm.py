@@ -20,6 +20,7 @@ from .command import CommandStructure, CommandType
 NFC_CMD_UNKNOWN, NFC_CMD_PARITY_ERROR = -1, -2
 FRAME_EXTRA_ERROR, FRAME_MANY_MORE_ERROR, FRAME_UID_MISMATCH, FRAME_ENCRYPTED = 1, 2, 4, 8
 FRAME_AR_OK, FRAME_AR_ERROR, FRAME_AT_OK, FRAME_AT_ERROR = 16, 32, 64, 128
+_SEL2R = 19   # csrc/protocol.h: CMD_SEL2R
 FRAME_DTYPE = np.dtype([('cmd', '<i4'), ('type', '<i4'), ('byte_off', '<u4'), ('n_bytes', '<u2'), ('n_header', '<u2'),
                         ('n_extra', '<u2'), ('n_crc', '<u2'), ('flags', '<u4'), ('n_enc', '<u2'), ('pad', '<u2')])
 
@@ -63,8 +64,8 @@ def _dispatch_one(f, data, enc, out, callback):
     if int(f['cmd']) == _lib.NFC_CMD_CUT:   # (only the GPU machine of a multi-stream context makes these: the frame's bits were not stored)
         out.write('CUT\n')
         return None
-    if flags & FRAME_UID_MISMATCH:
-        out.write('MISMATCH BETWEEN READER-TAG UID\n')
+    if flags & FRAME_UID_MISMATCH:   # fsm.py:184,192: the two lines, without the lists the reference prints behind them
+        out.write('MISMATCH BETWEEN READER_TAG UID#2\n' if int(f['cmd']) == _SEL2R else 'MISMATCH BETWEEN READER-TAG UID\n')
     for bit, msg in ((FRAME_AR_OK, 'AR OK'), (FRAME_AR_ERROR, 'ERROR WITH AR'), (FRAME_AT_OK, 'AT OK'), (FRAME_AT_ERROR, 'ERROR WITH AT')):
         if flags & bit:
             out.write(msg + '\n')
