@@ -276,7 +276,11 @@ int nfc_set_timing(nfc_ctx *ctx, int level);
  * fsm.process_bits (fsm.py:218-238): frame-end repair (fsm.py:49-66), decryption while a session is up, odd-parity strip and
  * check (fsm.py:28-47), command lookup by protocol stage and leading bytes with CRC_A / BCC checks
  * (command.py:44-67,166-199; utilities.py:26-46), header / extra / CRC split (command.py:245-253), tag type and
- * UID tracking (fsm.py:165-216).  No device work. */
+ * UID tracking (fsm.py:165-216).  No device work here -- but the machine is ONE text, csrc/fsm.hip.h, for this host machine (a shell over
+ * it with an unbounded UID: csrc/protocol.h), for nfc_host_commands and for k_multi_commands, a GPU lane per stream (below).  A packet is
+ * assembled into a frame by the text the frame kernels run (csrc/frames.hip.h) and then goes the frame's way: nfc_fsm_process_packets and
+ * nfc_fsm_process_frames give the same records, bytes and enc entries.  Behind a record's n_bytes / n_enc the rest of the frame's room
+ * in bytes_out / enc_out is written too (with zeros): the capacities asked for below cover it. */
 enum {
     NFC_CMD_UNKNOWN = -1,       /* bytes that match no command: CommandStructure("UNKNOWN", [], bytes) */
     NFC_CMD_PARITY_ERROR = -2   /* "PARITY ERROR" (fsm.py:225-227): no bytes, nothing dispatched */
@@ -309,7 +313,8 @@ typedef struct nfc_fsm nfc_fsm; /* protocol state across packets: previous comma
 int nfc_fsm_create(nfc_fsm **out);
 void nfc_fsm_destroy(nfc_fsm *f);
 int nfc_fsm_reset(nfc_fsm *f);
-/* one packet's bits (as nfc_read_packet_bits returns them); bytes_out needs n_bits / 9 + 1 bytes */
+/* one packet's bits (as nfc_read_packet_bits returns them); bytes_out needs n_bits / 9 + 1 bytes.  NFC_ERR_ARG also for a packet of
+   2^32 bits or more (an nfc_packet counts its bits in 32) */
 int nfc_fsm_process(nfc_fsm *f, const uint8_t *bits, size_t n_bits, int packet_type, nfc_frame *out, uint8_t *bytes_out,
                     size_t bytes_cap, uint16_t *enc_out /* NULL, or the same capacity: on-air byte | 0x100 if marked '!' */);
 /* fsm.process_outgoing (fsm.py:68-112, wired at packets.py:88-90 as the emulator's encoder hook): a frame an emulator is about to
@@ -527,9 +532,10 @@ int nfc_host_frames(const nfc_packet *packets, size_t n, const uint8_t *bits, in
                     size_t cap, size_t *used);
 /* nfc_fsm_process_packets over frames: `frames` holds both types merged by idx, as the rows of nfc_fsm_process_packets are; its outputs
  * and the machine's state afterwards are IDENTICAL to nfc_fsm_process_packets on the packets the frames came from, through CRYPTO1
- * sessions and nested authentications.  Outside a session it uses the assembled bytes and the parity verdict and touches no bits;
- * inside one it rebuilds the on-air bits from bytes and par and takes the route of nfc_fsm_process.  A frame with NFC_RAW_CUT is
- * NFC_ERR_ARG (its bits are not there). */
+ * sessions and nested authentications.  Outside a session it uses the assembled bytes and the parity and CRC verdicts; inside one
+ * it decrypts bytes and par -- the route nfc_fsm_process takes once it has assembled its packet.  A frame with NFC_RAW_CUT is
+ * NFC_ERR_ARG (its bits are not there), and so is one whose n_bytes exceeds n_bits / 9 + 1: all n_bytes entries of the frame's
+ * room in bytes_out / enc_out are written, and that is the room the capacity check reserves. */
 int nfc_fsm_process_frames(nfc_fsm *f, const nfc_raw_frame *frames, size_t n, const uint8_t *bytes0, const uint8_t *par0,
                            const uint8_t *bytes1, const uint8_t *par1, nfc_frame *frames_out, uint8_t *bytes_out, size_t bytes_cap,
                            size_t *bytes_used, uint16_t *enc_out);
@@ -563,8 +569,8 @@ int nfc_multi_fetch_frames(nfc_multi *m, nfc_multi_frames *out);
  * CRYPTO1 sessions of MIFARE Classic with nested authentications -- is sequential in ONE stream and independent across streams.  With
  * tracking on, every push of a multi-stream context assembles the frames (the two launches of nfc_multi_fetch_frames, into a buffer of
  * the tracking's own) and runs k_multi_commands behind them (csrc/multi_commands.hip.h): a lane per stream merges the stream's two frame
- * lists by idx (type 0 first on a tie), runs every frame through csrc/fsm.hip.h -- a restatement of csrc/protocol.h without vectors,
- * pinned to it by the CPU suite -- and writes records, plaintext and enc entries.  The machines' state stays on the device from push to
+ * lists by idx (type 0 first on a tie), runs every frame through csrc/fsm.hip.h -- the one protocol machine, the text the host machine
+ * behind nfc_fsm_* runs too -- and writes records, plaintext and enc entries.  The machines' state stays on the device from push to
  * push, so a session that spans pushes stays in step whether or not anybody fetches.
  * THE STATE is public and plain: nfc_fsm_state, 88 bytes.  A host machine hands itself over with nfc_fsm_get_state / nfc_fsm_set_state,
  * a stream with nfc_multi_get_fsm_state / nfc_multi_set_fsm_state; nfc_host_commands is the kernel's twin on the CPU.

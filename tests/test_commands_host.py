@@ -1,5 +1,7 @@
-"""The protocol machine restated for host and device (csrc/fsm.hip.h) against the host machine it restates (csrc/protocol.h), on the CPU:
-nfc_host_commands -- the twin of k_multi_commands -- against nfc_fsm_process_frames, the hand-over of a machine through nfc_fsm_state,
+"""The protocol machine (csrc/fsm.hip.h, one text for host and device) in two of its holders on the CPU: nfc_host_commands -- the twin of
+k_multi_commands, the UID in eight words, a slot per frame -- against the host machine (csrc/protocol.h: an unbounded UID, packed outputs)
+through nfc_fsm_process_frames.  Both run the same text, so what these comparisons pin is what a holder adds; what the text computes is
+pinned by tests/test_fsm_fuzz.py and tests/test_fsm_parent.py.  Also here: the hand-over of a machine through nfc_fsm_state,
 the UID capacity, cut frames and fsm.dispatch.  Every comparison is for equality.  tests/test_commands.py holds the GPU half and uses
 the helpers and the fixture below.
 

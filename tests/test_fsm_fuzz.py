@@ -1,5 +1,5 @@
-"""The three protocol machines -- csrc/protocol.h behind fsm.fsm, its restatement csrc/fsm.hip.h behind fsm.host_commands, and k_multi_commands,
-the restatement a GPU lane per stream -- on MALFORMED traffic, against the reference's own fsm.process_bits / process_outgoing.
+"""The protocol machine (csrc/fsm.hip.h) in its three holders -- the host machine behind fsm.fsm (csrc/protocol.h), the twin behind
+fsm.host_commands, and k_multi_commands, a GPU lane per stream -- on MALFORMED traffic, against the reference's own fsm.process_bits / process_outgoing.
 
 THE FIXTURE, tests/golden/fx_fsm_fuzz.npz, is written by tests/golden/make_fsm_golden.py, which runs the reference's machine itself (translated
 to Python 3 in memory, gated on printing both golden traces): 2 000 seeded sequences -- the 24-frame Classic prefix, the Ultralight
@@ -13,7 +13,7 @@ IQ at 2 Msps and decoded by the C oracle: their frames are the oracle's packets,
 
 WHERE THE REFERENCE RAISES (a UID longer than the nonce, RANDRB / RANDTB with no session, an empty UID or a frame shorter than the UID in a
 nested authentication) it has no behaviour: the comparison with its text stops at that frame, and what the project does from there on
- is pinned by the twin and kernel legs, which cover the whole sequence.  Every comparison is for equality."""
+ is pinned by tests/test_fsm_parent.py, whose recorded digests cover the whole sequence; the twin and kernel legs here compare holders.  Every comparison is for equality."""
 import ctypes
 import io
 import os

@@ -36,7 +36,7 @@ def word(b):
 
 
 def crafted_trace(key, key_type, uid, nt, nr, block=0x04):
-    """One first authentication made by the project's own machine and CRYPTO1 (fsm.process_bits / process_outgoing; csrc/protocol.h):
+    """One first authentication made by the project's own machine and CRYPTO1 (fsm.process_bits / process_outgoing; csrc/protocol.h over csrc/fsm.hip.h):
     the tag type and the UID go in as heard frames, the AUTH too (it selects the key), then the machine ENCRYPTS what a tag and a reader
     would send -- nt, nr | suc64(nt), suc96(nt); the two answers are the machine's own (its state after nt)."""
     m = fsm.fsm(out=io.StringIO())

@@ -1,5 +1,5 @@
 """The per-sector key table of the protocol machines on the CPU (include/nfc_amd.h: nfc_fsm_key_table; csrc/sector_keys.h):
-the host machine (csrc/protocol.h), its restatement's twin nfc_host_commands_keyed (csrc/fsm.hip.h) and the Python layers, on cards
+the host machine (csrc/protocol.h over csrc/fsm.hip.h), the kernel's twin nfc_host_commands_keyed (the same text, the capped UID) and the Python layers, on cards
 whose sectors have DIFFERENT keys.  No GPU.  tests/test_sector_keys.py holds the GPU half and uses the cards and helpers below.  Every
 comparison is for equality.
 

@@ -1,5 +1,5 @@
 """Command table of the reference's protocol layer (command.py:11-118, 201-265) over the host C++ of
-csrc/protocol.h -- "next" row f1 of SURVEY.md section 8: the names, accessors and the printed form are the
+csrc/fsm.hip.h -- "next" row f1 of SURVEY.md section 8: the names, accessors and the printed form are the
 reference's (a `Command` per table row, `CommandType.REQA` ..., `CommandStructure.display()`), the table and
 the lookup themselves live in the shared library (nfc_command_get, nfc_fsm_process)."""
 import ctypes as C
@@ -70,7 +70,7 @@ class _CommandTypeMeta(type):
     _table = None
     _attr = ['REQA', 'WUPA', 'ATQAUL', 'ATQA1K', 'ATQA4K', 'ATQADS', 'ANTI1R', 'ANTI1U', 'ANTI1G', 'SEL1R', 'SEL1U', 'SEL1K',
              'ANTI2R', 'ANTI2T', 'AUTHA', 'AUTHB', 'RANDTA', 'RANDRB', 'RANDTB', 'SEL2R', 'SEL2T', 'READR', 'READT', 'HALT',
-             'WRITE', 'COMPW1', 'COMPW2']   # table order of csrc/protocol.h (attribute names: command.py:78-118)
+             'WRITE', 'COMPW1', 'COMPW2']   # table order of csrc/fsm.hip.h (attribute names: command.py:78-118)
 
     def table(cls):
         if _CommandTypeMeta._table is None:

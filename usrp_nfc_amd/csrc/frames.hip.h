@@ -21,7 +21,7 @@ namespace frames {
 __host__ __device__ __forceinline__ uint32_t frame_bytes_of(uint32_t n_bits) {
     return n_bits % 9u == 8u ? (n_bits + 1u) / 9u : n_bits / 9u;
 }
-// one byte into the CRC_A register (protocol.h: crc_a -- reflected 0x8408, the caller starts from 0x6363)
+// one byte into the CRC_A register (fsm.hip.h: crc_a -- reflected 0x8408, the caller starts from 0x6363)
 __host__ __device__ __forceinline__ uint32_t crc_a_step(uint32_t w, uint32_t byte) {
     uint32_t b = (byte ^ w) & 0xFFu;
     b ^= (b << 4) & 0xFFu;
@@ -74,7 +74,7 @@ __host__ __device__ __forceinline__ uint32_t assemble_frame(const Src &S, uint64
         flags |= NFC_FRAME_MANY_MORE_ERROR;
     }
     bool par_ok = n_bytes > 0;
-    // the CRC register runs two bytes behind: after the loop it covers bytes[0 .. n - 2) and p2, p1 are the last two (protocol.h: crc_a_ok)
+    // the CRC register runs two bytes behind: after the loop it covers bytes[0 .. n - 2) and p2, p1 are the last two (the check of a frame's CRC_A)
     uint32_t crc = 0x6363u, p1 = 0, p2 = 0;
     for (uint32_t i = 0; i < n_bytes; i++) {
         uint32_t f = S.field(bit_off + 9ull * i, end);

@@ -1,15 +1,23 @@
-// fsm.hip.h -- the protocol machine of protocol.h (fsm_process_frame and everything it reaches: fsm_strip, fsm_finish, find_command /
-// compatible, Crypto1::{load_key, crypt, set_answers, set_tag}) restated without vectors and without allocation, for host and device:
-// one frame as the GPU assembled it (nfc_raw_frame, its bytes and ninth bits) in, one nfc_frame record, the plaintext and the `enc`
-// entries out, the state in a plain struct (nfc_fsm_state, include/nfc_amd.h).  k_multi_commands (multi_commands.hip.h) runs it a lane
-// per stream, nfc_host_commands on the CPU; protocol.h stays the oracle: tests/test_commands.py pins this file to it.
+// fsm.hip.h -- THE protocol machine (fsm.py, command.py, cipher.py, lfsr.py of the reference; "next" rows f1 and f3 of SURVEY.md 8f), one
+// text for host and device, without vectors and without allocation: one frame as the GPU assembled it (nfc_raw_frame, its bytes and
+// ninth bits) in, one nfc_frame record, the plaintext and the `enc` entries out.  What the reference does per packet in fsm.process_bits
+// (fsm.py:218-238): find the command by the protocol stage of the previous command and the leading bytes (command.py:166-199, with the
+// CRC_A of utilities.py:26-46 and the BCC xor check of command.py:44-67), split it into header / extra / CRC (command.py:245-253), track
+// tag type and UID (fsm.py:165-216), and decrypt the frames of a MIFARE Classic session before the parity check, nested authentications
+// included (fsm.py:133-154,197-213).  Three holders instantiate it: k_multi_commands (multi_commands.hip.h) a lane per stream,
+// nfc_host_commands, its twin on the CPU, and the host machine nfc_fsm (protocol.h), whose UID is unbounded.  What pins it:
+// the reference's own text on malformed traffic and what the project's first, separate host machine made of the same rows
+// (tests/test_fsm_fuzz.py, tests/test_fsm_parent.py).
 //
 // Form.  The machine lives in named scalars (Machine): the 48-bit cipher register in a uint64, ar / at and the keys as integers (byte 0
-// lowest), the UID as eight words reached through select chains -- nothing is an array with a dynamic index, so a lane needs no
-// scratch.  Only a frame of at most 18 bytes can be a command (the longest total() of the table: READT / COMPW2), so the lookup sees
+// lowest).  The UID is reached through an accessor -- uid_len(M), uid_byte(M, i), uid_clear(M), uid_append(M, B, from, n),
+// overloaded on the machine's type -- as the key table is through Table (sector_keys.h).  A Machine's own,
+// the kernel's and the twin's, is eight words reached through select chains -- nothing is an array with a dynamic index, so a lane
+// needs no scratch -- and holds 32 bytes; the host machine derives from Machine and keeps a vector (protocol.h).
+// Only a frame of at most 18 bytes can be a command (the longest total() of the table: READT / COMPW2), so the lookup sees
 // the frame through five words (Bytes); the CRC_A register runs two bytes behind the byte loop as in assemble_frame (frames.hip.h).
 // CRYPTO1 is bit-serial: per clock the filter reads 20 fixed register bits through truth-table words that a constexpr builds from fa /
-// fb / fc as protocol.h states them, and the feedback is the parity of popcount(st & TAPS), TAPS built from the eighteen tap positions.
+// fb / fc as cipher.py:97-107 states them, and the feedback is the parity of popcount(st & TAPS), TAPS built from the eighteen taps.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -20,11 +28,21 @@
 #include "sector_keys.h"
 
 namespace nfc {
+
+// ---- ISO 14443-3 type A CRC (utilities.py:30-41): reflected 0x8408, initial 0x6363, low byte first ----
+inline uint16_t crc_a(const uint8_t *data, size_t n) {
+    uint32_t w = 0x6363u;
+    for (size_t i = 0; i < n; i++) w = frames::crc_a_step(w, data[i]);
+    return (uint16_t)w;
+}
+
 namespace fsmd {
 
 #define NFC_HD __host__ __device__ __forceinline__
 
-// ---- the command table (protocol.h: COMMANDS, in its order; nfc_host_commands checks the two against each other) ----
+// ---- the command table (command.py:78-118, in its order: a command's number is its index; nfc_command_get names them) ----
+// type: 0 tag -> reader, 1 reader -> tag (packets.py:18-20); crc: the frame ends with CRC_A; xor_check: -1 none, else the xor of the extra
+// bytes, seeded with it, must be 0.  (ATQA4K carries the 1K name in the reference, command.py:84.)
 enum {
     C_REQA, C_WUPA, C_ATQAUL, C_ATQA1K, C_ATQA4K, C_ATQADS, C_ANTI1R, C_ANTI1U, C_ANTI1G, C_SEL1R, C_SEL1U,
     C_SEL1K, C_ANTI2R, C_ANTI2T, C_AUTHA, C_AUTHB, C_RANDTA, C_RANDRB, C_RANDTB, C_SEL2R, C_SEL2T, C_READR,
@@ -38,16 +56,16 @@ constexpr uint32_t def_word(int stage, int n_header, int h0, int type, int crc, 
 }
 struct Def {
     uint32_t w, h1;
-    NFC_HD int stage() const { return (int)(w & 15u); }
-    NFC_HD int n_header() const { return (int)((w >> 4) & 3u); }
-    NFC_HD int type() const { return (int)((w >> 6) & 1u); }
-    NFC_HD int crc() const { return (int)((w >> 7) & 1u); }
-    NFC_HD int n_extra() const { return (int)((w >> 8) & 31u); }
-    NFC_HD int xor_check() const { return (w >> 13) & 1u ? (int)((w >> 16) & 0xFFu) : -1; }
-    NFC_HD uint32_t h0() const { return w >> 24; }
-    NFC_HD int total() const { return n_header() + n_extra() + 2 * crc(); }
+    NFC_HD constexpr int stage() const { return (int)(w & 15u); }
+    NFC_HD constexpr int n_header() const { return (int)((w >> 4) & 3u); }
+    NFC_HD constexpr int type() const { return (int)((w >> 6) & 1u); }
+    NFC_HD constexpr int crc() const { return (int)((w >> 7) & 1u); }
+    NFC_HD constexpr int n_extra() const { return (int)((w >> 8) & 31u); }
+    NFC_HD constexpr int xor_check() const { return (w >> 13) & 1u ? (int)((w >> 16) & 0xFFu) : -1; }
+    NFC_HD constexpr uint32_t h0() const { return w >> 24; }
+    NFC_HD constexpr int total() const { return n_header() + n_extra() + 2 * crc(); }
 };
-NFC_HD Def def_of(int cmd) {
+NFC_HD constexpr Def def_of(int cmd) {
     switch (cmd) {
     case C_REQA: return Def{def_word(0, 1, 0x26, 1, 0, 0, -1), 0};
     case C_WUPA: return Def{def_word(0, 1, 0x52, 1, 0, 0, -1), 0};
@@ -78,7 +96,15 @@ NFC_HD Def def_of(int cmd) {
     default: return Def{def_word(7, 0, 0, 1, 1, 16, -1), 0};   // C_COMPW2
     }
 }
-// candidates per protocol stage and direction, in the reference's order (protocol.h: TAG_STAGE, READER_STAGE), four to a word, 0xFF: none
+constexpr int longest_command() {
+    int m = 0;
+    for (int c = 0; c < C_COUNT; c++) m = def_of(c).total() > m ? def_of(c).total() : m;
+    return m;
+}
+static_assert(longest_command() == MAX_COMMAND_BYTES, "the lookup inspects frames of up to MAX_COMMAND_BYTES bytes: the longest command");
+// candidates per protocol stage and direction, in the reference's order (command.py:120-137), four to a word, 0xFF: none.  The reader
+// table has stages 0 .. 7 and 10: the reference tests `stage < number of entries (9)` and then indexes by stage (stage 8 would raise
+// KeyError there; no command has stage 7 + 1 as its successor in a trace)
 constexpr uint32_t cand4(int a, int b = 0xFF, int c = 0xFF, int d = 0xFF) {
     return (uint32_t)a | (uint32_t)b << 8 | (uint32_t)c << 16 | (uint32_t)d << 24;
 }
@@ -107,7 +133,9 @@ NFC_HD uint32_t reader_stage(int v) {
     }
 }
 
-// ---- CRYPTO1 (protocol.h: Crypto1; cipher.py) ----
+// ---- CRYPTO1 (cipher.py) ----
+// A 48-bit shift register, bit i of st the i-th oldest bit (cipher.py keeps the whole bit history and looks at its last 48); a key's bytes
+// least significant bit first ARE the register (cipher.py:11-12).  One filter bit per clock; a clock shifts in L(st) ^ input.
 constexpr int fa(int a, int b, int c, int d) { return ((a | b) ^ (a & d)) ^ (c & ((a ^ b) | d)); }
 constexpr int fb(int a, int b, int c, int d) { return ((a & b) | c) ^ ((a ^ b) & (c | d)); }
 constexpr int fc(int a, int b, int c, int d, int e) { return (a | ((b | e) & (d ^ e))) ^ ((a ^ (b & d)) & ((c ^ d) | (b & e))); }
@@ -128,7 +156,7 @@ constexpr uint32_t table_fc() {
     return t;
 }
 constexpr uint64_t taps_mask() {
-    const int taps[18] = {0, 5, 9, 10, 12, 14, 15, 17, 19, 24, 25, 27, 29, 35, 39, 41, 42, 43};   // protocol.h: Crypto1::feedback
+    const int taps[18] = {0, 5, 9, 10, 12, 14, 15, 17, 19, 24, 25, 27, 29, 35, 39, 41, 42, 43};   // cipher.py:75-76
     uint64_t m = 0;
     for (int i = 0; i < 18; i++) m |= 1ull << taps[i];
     return m;
@@ -141,14 +169,15 @@ NFC_HD uint32_t quad(uint64_t st, int p) {
     const uint32_t x = (uint32_t)(st >> p);
     return (x & 1u) | ((x >> 1) & 2u) | ((x >> 2) & 4u) | ((x >> 3) & 8u);
 }
-NFC_HD uint32_t filter(uint64_t st) {   // protocol.h: Crypto1::filter
+NFC_HD uint32_t filter(uint64_t st) {   // cipher.py:110-118
     const uint32_t a = (TT_FA >> quad(st, 9)) & 1u, b = (TT_FB >> quad(st, 17)) & 1u, c = (TT_FB >> quad(st, 25)) & 1u;
     const uint32_t d = (TT_FA >> quad(st, 33)) & 1u, e = (TT_FB >> quad(st, 41)) & 1u;
     return (TT_FC >> (a | b << 1 | c << 2 | d << 3 | e << 4)) & 1u;
 }
 NFC_HD uint32_t feedback(uint64_t st) { return (uint32_t)__builtin_popcountll(st & TAPS) & 1u; }
 NFC_HD uint64_t shift_in(uint64_t st, uint32_t in) { return (st >> 1) | ((uint64_t)((feedback(st) ^ in) & 1u) << 47); }
-// the nonce register 64 and 96 clocks on (protocol.h: set_answers): bit j of x is the j-th oldest of the 32 bits
+// the nonce register (lfsr.py, taps 16 18 19 21) `ticks` clocks on: bit j of x is the j-th oldest of the 32 bits.  The expected reader /
+// tag answers are the tag nonce after 64 and after 96 clocks (cipher.py:37-42)
 NFC_HD uint32_t nonce_advance(uint32_t x, int ticks) {
     for (int t = 0; t < ticks; t++) x = (x >> 1) | ((((x >> 16) ^ (x >> 18) ^ (x >> 19) ^ (x >> 21)) & 1u) << 31);
     return x;
@@ -196,8 +225,11 @@ NFC_HD void machine_init(Machine &M) {   // nfc_fsm_reset
     uid_clear(M);
 }
 
-// a frame's first 20 bytes in five words
+// a frame's first 20 bytes.  On the device five words reached through select chains (no array a lane would index); on the host, where an
+// index costs nothing and a select chain per byte is what a clear-text frame would spend most of its time in, twenty bytes.  Only the
+// storage differs: at / put / word_at mean the same in both.
 struct Bytes {
+#if defined(__HIP_DEVICE_COMPILE__)
     uint32_t w0, w1, w2, w3, w4;
     NFC_HD uint32_t at(uint32_t i) const {
         const uint32_t j = i >> 2;
@@ -212,6 +244,11 @@ struct Bytes {
         w3 |= j == 3 ? v : 0u;
         w4 |= j == 4 ? v : 0u;
     }
+#else
+    uint8_t b[20];
+    uint32_t at(uint32_t i) const { return b[i < 20u ? i : 19u]; }
+    void put(uint32_t i, uint32_t v) { b[i] = (uint8_t)v; }   // (i < 20)
+#endif
     NFC_HD uint32_t word_at(uint32_t i) const { return at(i) | at(i + 1) << 8 | at(i + 2) << 16 | at(i + 3) << 24; }   // i + 3 < 20
 };
 
@@ -220,7 +257,7 @@ struct Rec {
     uint32_t flags, n_bytes, n_header, n_extra, n_crc, n_enc;
 };
 
-// protocol.h: compatible.  crc_ok: the last two of the n bytes are the CRC_A of those before them.
+// command.py:44-67.  crc_ok: the last two of the n bytes are the CRC_A of those before them.
 NFC_HD bool compatible(const Def &c, const Bytes &B, int n, bool crc_ok) {
     if (c.total() != n) return false;
     if (c.n_header() >= 1 && c.h0() != B.at(0)) return false;
@@ -247,14 +284,16 @@ NFC_HD int first_compatible(uint32_t cands, const Bytes &B, int n, bool crc_ok) 
     }
     return -1;
 }
-// protocol.h: find_command, for 1 <= n <= MAX_COMMAND_BYTES
+// command.py:166-199, for 1 <= n <= MAX_COMMAND_BYTES: by the stage of the previous command and the one behind it, then by leading bytes
 NFC_HD int find_command(const Bytes &B, int n, int type, int prev_cmd, bool crc_ok) {
     const int ind = def_of(prev_cmd).stage();
     for (int v = ind; v <= ind + 1; v++) {
         const int c = first_compatible(type == 0 ? tag_stage(v) : reader_stage(v), B, n, crc_ok);
         if (c >= 0) return c;
     }
-    int o0 = -1, o1 = -1;   // by leading bytes: the first listed option, or the second when the second byte names it
+    // command.py:139-164: the first listed option, or the second when the second byte names it (no second byte, or one that names nothing:
+    // IndexError / KeyError in the reference, caught: no command)
+    int o0 = -1, o1 = -1;
     switch (B.at(0)) {
     case 0x00: o0 = C_SEL2T; break;
     case 0x02: o0 = C_ATQA4K; break;
@@ -290,7 +329,9 @@ NFC_HD int find_command(const Bytes &B, int n, int type, int prev_cmd, bool crc_
     return compatible(def_of(option), B, n, crc_ok) ? option : -1;
 }
 
-// the UID grows by the n bytes at B[from ..): not made when it would pass UID_CAP (the host machine's vector is unbounded)
+// The rest of the UID accessor for the Machine's own eight words (uid_byte and uid_clear: above).
+NFC_HD uint32_t uid_len(const Machine &M) { return M.uid_len; }
+// the UID grows by the n bytes at B[from ..): not made when it would pass UID_CAP (the host machine's holder is unbounded)
 NFC_HD void uid_append(Machine &M, const Bytes &B, uint32_t from, uint32_t n) {
     if (M.uid_len + n > UID_CAP) {
         M.flags |= NFC_FSM_UID_OVERFLOW;
@@ -300,11 +341,12 @@ NFC_HD void uid_append(Machine &M, const Bytes &B, uint32_t from, uint32_t n) {
     M.uid_len += n;
 }
 
-// protocol.h: fsm_finish.  nb plaintext bytes (0: a parity error, or nothing left), the first 20 of them in B.  tab: the stream's sector
-// key table (sector_keys.h), read only where an AUTH command is recognised and where a nonce loads the register.
-template <class Table>
-NFC_HD void finish(Machine &M, uint32_t nb, int type, Rec &out, const Bytes &B, bool crc_ok, const Table &tab) {
-    if (nb == 0) {
+// The bytes -> command, record, tag type / UID / session state (fsm.py:165-216, 225-238).  nb plaintext bytes (0: a parity error, or
+// nothing left), the first 20 of them in B.  Mach: a Machine, or one derived from it with a UID holder of its own.  tab: the stream's
+// sector key table (sector_keys.h), read only where an AUTH command is recognised and where a nonce loads the register.
+template <class Mach, class Table>
+NFC_HD void finish(Mach &M, uint32_t nb, int type, Rec &out, const Bytes &B, bool crc_ok, const Table &tab) {
+    if (nb == 0) {   // `if not bytes` (fsm.py:225)
         out.cmd = NFC_CMD_PARITY_ERROR;
         return;
     }
@@ -324,12 +366,12 @@ NFC_HD void finish(Machine &M, uint32_t nb, int type, Rec &out, const Bytes &B, 
     out.n_crc = c.crc() ? 2u : 0u;
     out.n_extra = nb - h - out.n_crc;
     switch (cmd) {
-    case C_REQA: case C_WUPA: case C_HALT:
+    case C_REQA: case C_WUPA: case C_HALT:   // fsm.py:20-24
         uid_clear(M);
         M.tag_type = -1;
         M.encrypted = 0;
         break;
-    case C_ATQAUL: M.tag_type = 0; break;
+    case C_ATQAUL: M.tag_type = 0; break;   // command.py:70-74
     case C_ATQA1K: M.tag_type = 1; break;
     case C_ATQA4K: M.tag_type = 2; break;
     case C_ATQADS: M.tag_type = 3; break;
@@ -337,20 +379,19 @@ NFC_HD void finish(Machine &M, uint32_t nb, int type, Rec &out, const Bytes &B, 
     case C_ANTI1G: uid_append(M, B, h, 4); break;
     case C_SEL1R: {
         const uint32_t start = M.tag_type == 0 ? 1u : 0u, n = 4u - start;
-        bool same = M.uid_len == n;
+        bool same = uid_len(M) == n;
         for (uint32_t j = 0; j < n; j++) same = same && uid_byte(M, j) == B.at(h + start + j);
         if (!same) {
             out.flags |= NFC_FRAME_UID_MISMATCH;
             uid_clear(M);
-            for (uint32_t j = 0; j < n; j++) uid_put(M, j, B.at(h + start + j));
-            M.uid_len = n;
+            uid_append(M, B, h + start, n);
         }
         break;
     }
     case C_ANTI2T: uid_append(M, B, h, 4); break;
-    case C_SEL2R: {
-        bool same = M.uid_len >= 4u;
-        for (uint32_t j = 0; j < 4u; j++) same = same && uid_byte(M, (M.uid_len - 4u + j) & (UID_CAP - 1u)) == B.at(h + j);
+    case C_SEL2R: {   // (uid_byte of an index at or past the holder's end is some byte or none, never a fault: `same` is false by then)
+        bool same = uid_len(M) >= 4u;
+        for (uint32_t j = 0; j < 4u; j++) same = same && uid_byte(M, uid_len(M) - 4u + j) == B.at(h + j);
         if (!same) {
             out.flags |= NFC_FRAME_UID_MISMATCH;
             uid_append(M, B, h, 4);
@@ -363,8 +404,8 @@ NFC_HD void finish(Machine &M, uint32_t nb, int type, Rec &out, const Bytes &B, 
         if (!M.encrypted) {   // first authentication: the tag nonce came in the clear; uid ^ nonce goes into a fresh register
             M.st = skeys::resolve(tab, M.cur_key, M.key_a, M.key_b);
             M.ar = M.at = 0;
-            const uint32_t nonce = B.word_at(h), nu = M.uid_len;
-            if (nu <= 4u) {   // the UID bytes there are go in, none included (set_tag: nothing at all with more UID bits than the nonce has)
+            const uint32_t nonce = B.word_at(h), nu = uid_len(M);
+            if (nu <= 4u) {   // the UID bytes there are go in, none included (nothing at all with more UID bits than the nonce has: the reference raises)
                 for (uint32_t i = 0; i < nu; i++) {
                     const uint32_t x = uid_byte(M, i) ^ ((nonce >> (8u * i)) & 0xFFu);
                     for (int k = 0; k < 8; k++) M.st = shift_in(M.st, (x >> k) & 1u);
@@ -381,10 +422,13 @@ NFC_HD void finish(Machine &M, uint32_t nb, int type, Rec &out, const Bytes &B, 
     }
 }
 
-// One frame (protocol.h: fsm_process_frame): raw_flags / n its nfc_raw_frame's flags and n_bytes, bytes / par its data bytes and ninth
-// bits as received.  data / enc: the frame's slot, n entries each, ALL written: the plaintext bytes and the enc entries first, 0 behind.
-template <class Table>
-NFC_HD Rec process_frame(Machine &M, int type, uint32_t raw_flags, uint32_t n, const uint8_t *__restrict__ bytes, const uint8_t *__restrict__ par,
+// One frame: raw_flags / n its nfc_raw_frame's flags and n_bytes (the repair's messages, the parity and CRC verdicts of assemble_frame),
+// bytes / par its data bytes and ninth bits as received.  Outside a session the bytes are taken as they are; inside one every byte is
+// decrypted first (fsm.py:133-154) and the parity and the CRC are those of the plaintext.  data / enc: the frame's slot, n entries each,
+// ALL written: the plaintext bytes and the enc entries first, 0 behind.  An enc entry is what was on the air: the byte in the low half,
+// bit 8 set when the parity bit equals the data parity (the '!' of fsm._print_enc, fsm.py:113-131).
+template <class Mach, class Table>
+NFC_HD Rec process_frame(Mach &M, int type, uint32_t raw_flags, uint32_t n, const uint8_t *__restrict__ bytes, const uint8_t *__restrict__ par,
                          uint8_t *__restrict__ data, uint16_t *__restrict__ enc, const Table &tab) {
     Rec out = {NFC_CMD_UNKNOWN, type, 0u, 0u, 0u, 0u, 0u, 0u};
     if (raw_flags & NFC_RAW_CUT) {   // its bits are not there: the machine is not touched, the keystream of a session is out of step from here
@@ -393,7 +437,7 @@ NFC_HD Rec process_frame(Machine &M, int type, uint32_t raw_flags, uint32_t n, c
         return out;
     }
     out.flags = raw_flags & (uint32_t)(NFC_FRAME_EXTRA_ERROR | NFC_FRAME_MANY_MORE_ERROR);
-    Bytes B = {0u, 0u, 0u, 0u, 0u};
+    Bytes B = {};
     uint32_t nb;
     bool crc_ok;
     if (!M.encrypted) {
@@ -405,7 +449,7 @@ NFC_HD Rec process_frame(Machine &M, int type, uint32_t raw_flags, uint32_t n, c
             enc[i] = 0;
             if (i < 20u) B.put(i, b);
         }
-    } else {   // protocol.h: fsm_strip inside a session
+    } else {
         out.flags |= NFC_FRAME_ENCRYPTED;
         out.n_enc = n;
         // {nr}{ar}: the reader nonce (the first half) is fed back into the register while it is decrypted
@@ -416,8 +460,8 @@ NFC_HD Rec process_frame(Machine &M, int type, uint32_t raw_flags, uint32_t n, c
         if (nested) {
             M.st = skeys::resolve(tab, M.cur_key, M.key_a, M.key_b);
             M.ar = M.at = 0;
-            const uint32_t nu = M.uid_len;
-            todo = (nu >= 1u && nu <= n) ? nu : 0u;   // (set_tag: nothing at all with no UID or a frame shorter than the UID)
+            const uint32_t nu = uid_len(M);
+            todo = (nu >= 1u && nu <= n) ? nu : 0u;   // (nothing at all with no UID or a frame shorter than the UID: the reference raises)
         }
         bool bad = false;
         uint32_t crc = 0x6363u, p1 = 0, p2 = 0, nonce = 0;
@@ -460,6 +504,33 @@ NFC_HD Rec process_frame(Machine &M, int type, uint32_t raw_flags, uint32_t n, c
     }
     finish(M, nb, type, out, B, crc_ok, tab);
     return out;
+}
+
+// ---- host only: CRYPTO1 over a bit list, for the frames an emulator is about to send (protocol.h: fsm_process_outgoing) ----
+// cipher.py:20-35 on a frame with its parity bits: every bit is xored with the filter output; the ninth bit of a group reuses the keystream
+// bit of the next data bit -- the register does not move for it.  feed_in: the plaintext is fed back into the register ({nr}).
+inline void crypt_bits(uint64_t &st, const uint8_t *in, size_t n, uint8_t *out, bool feed_in) {
+    for (size_t k = 0; k < n; k++) {
+        const uint32_t b = in[k] & 1u;
+        out[k] = (uint8_t)(filter(st) ^ b);
+        if (k % 9 != 8) st = shift_in(st, feed_in ? b : 0u);
+    }
+}
+// cipher.py:62-72 with a plain tag nonce of n bits (bit(j): its j-th): uid ^ nonce goes into the register M.st, which holds the key -- the
+// UID bits THERE ARE.  -> what `encrypted` becomes: 1 with a nonce register of 32 bits, M.ar / M.at set; 2 with another bit count -- the
+// reference's answers then have that many bits, so that no {ar} / {at} ever equals them; 0 where the reference raises -- more UID bits
+// than nonce bits (IndexError), a nonce of no bits (ZeroDivisionError in lfsr.py) -- with the register left at the key.
+template <class Mach, class Bit>
+inline int set_tag_plain(Mach &M, size_t n, Bit bit) {
+    const size_t ll = 8 * (size_t)uid_len(M);
+    if (n < ll || n == 0) return 0;
+    for (size_t i = 0; i < ll; i++) M.st = shift_in(M.st, ((uid_byte(M, (uint32_t)(i >> 3)) >> (i & 7)) ^ bit(i)) & 1u);
+    if (n != 32) return 2;
+    uint32_t nonce = 0;
+    for (uint32_t i = 0; i < 32; i++) nonce |= (bit(i) & 1u) << i;
+    M.ar = nonce_advance(nonce, 64);
+    M.at = nonce_advance(M.ar, 32);
+    return 1;
 }
 
 // ---- Machine <-> nfc_fsm_state ----

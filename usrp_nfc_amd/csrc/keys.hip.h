@@ -2,7 +2,7 @@
 // device, and the three kernels that run it (k_keys_count, k_keys_fill_odd, k_keys_probe_even).  nfc_keys.hip holds the host side: the
 // CPU twin (nfc_host_recover_keys), the batching and the scratch (nfc_recover_keys_device), and nfc_find_auths.
 //
-// Conventions are protocol.h's / fsm.hip.h's: the 48-bit register `st`, bit i the i-th oldest bit; a clock is st = st >> 1 | nx << 47;
+// Conventions are fsm.hip.h's: the 48-bit register `st`, bit i the i-th oldest bit; a clock is st = st >> 1 | nx << 47;
 // the filter reads bits 9, 11, .. 47; fsmd::TAPS is the feedback.  With b_0 .. b_47 the key bits and b_{t+48} the bit shifted in at
 // clock t, the clocks of a first authentication are: 0-31 uid ^ nt fed in, no keystream; 32-63 the plaintext nr fed in; 64-95 nothing
 // fed, ks_t encrypts ar; 96-127 nothing fed, ks_t encrypts at.  Parity bits do not clock the register.  A 32-bit word of a frame has
@@ -51,7 +51,7 @@ NFC_HD uint32_t filter20(uint32_t w) {
 // Relation r (t = 73 + r) over the places j = r + tap (and r + 48, the bit shifted in): an even j is O_{j / 2}, an odd j E_{(j - 1) / 2}.
 // The masks of r = 2 i + p are those of r = p shifted left by i: half 0 = O, half 1 = E.
 constexpr uint64_t sig_base(int half, int p) {
-    const int taps[19] = {0, 5, 9, 10, 12, 14, 15, 17, 19, 24, 25, 27, 29, 35, 39, 41, 42, 43, 48};   // protocol.h: Crypto1::feedback, and the new bit
+    const int taps[19] = {0, 5, 9, 10, 12, 14, 15, 17, 19, 24, 25, 27, 29, 35, 39, 41, 42, 43, 48};   // fsm.hip.h: taps_mask, and the new bit
     uint64_t m = 0;
     for (int i = 0; i < 19; i++) {
         const int j = p + taps[i];

@@ -11,8 +11,8 @@
 //   (batches up to 2^18 samples: the three stages after the threshold stage in ONE launch, small.hip.h)
 // then one wait; the edge / decode stages are repeated if the certification failed or a capacity estimate was short.
 // Tile prefixes: folded by every tile's own workgroup while the tiles are few, by a prefix launch beyond (scan.hip.h).
-// Outputs stay in HBM until read through nfc_read_*.  Host-only: the protocol layer of protocol.h (nfc_fsm_*), the
-// encoders of tx.hip.h; its renderer (row f4) is a kernel of its own outside the batch.
+// Outputs stay in HBM until read through nfc_read_*.  Host-only: the encoders of tx.hip.h; its renderer (row f4) is a kernel
+// of its own outside the batch.  (The protocol layer, nfc_fsm_*: nfc_commands.hip.)
 //
 // The host side in parts, included below into this one translation unit:
 //   host_context.h    the test build's switches, nfc_ctx (every HIP resource a member that releases itself: dev_buf.h), the mirrored state block, launch helpers
@@ -44,7 +44,6 @@
 #include "decode.hip.h"
 #include "decoder_tables.h"
 #include "edges.hip.h"
-#include "protocol.h"
 #include "scan.hip.h"
 #include "small.hip.h"
 #include "threshold.hip.h"
@@ -1079,94 +1078,6 @@ int nfc_get_stats(nfc_ctx *c, nfc_stats *out) {
     // (noted when the batch was adopted -- process_batch / wait_batch -- from the mirror that belongs to THAT batch: by now the
     // device's summary may have been rewritten by a batch submitted behind it)
     out->ring_slots_carried = c->ring_carried;
-    return NFC_OK;
-}
-
-// ---- row f1: packets -> bytes -> commands (host only, protocol.h) ----
-int nfc_fsm_create(nfc_fsm **out) {
-    if (!out) return NFC_ERR_ARG;
-    *out = new nfc_fsm();
-    return NFC_OK;
-}
-void nfc_fsm_destroy(nfc_fsm *f) { delete f; }
-int nfc_fsm_reset(nfc_fsm *f) {
-    if (!f) return NFC_ERR_ARG;
-    *f = nfc_fsm();
-    return NFC_OK;
-}
-int nfc_fsm_process(nfc_fsm *f, const uint8_t *bits, size_t n_bits, int packet_type, nfc_frame *out, uint8_t *bytes_out, size_t bytes_cap,
-                    uint16_t *enc_out) {
-    if (!f || !out || !bytes_out || (n_bits && !bits) || (packet_type != 0 && packet_type != 1)) return NFC_ERR_ARG;
-    if (bytes_cap < n_bits / 9 + 1) return NFC_ERR_ARG;
-    fsm_process(*f, bits, n_bits, packet_type, out, bytes_out, enc_out);
-    return NFC_OK;
-}
-int nfc_fsm_process_outgoing(nfc_fsm *f, const uint8_t *bits, size_t n_bits, int cmd, uint8_t *bits_out) {
-    if (!f || (n_bits && (!bits || !bits_out)) || cmd < 0 || cmd >= CMD_COUNT) return NFC_ERR_ARG;
-    return fsm_process_outgoing(*f, bits, n_bits, cmd, bits_out);
-}
-int nfc_fsm_set_keys(nfc_fsm *f, const uint8_t key_a[6], const uint8_t key_b[6]) {
-    if (!f || !key_a || !key_b) return NFC_ERR_ARG;
-    memcpy(f->key_a, key_a, 6);
-    memcpy(f->key_b, key_b, 6);
-    return NFC_OK;
-}
-int nfc_fsm_process_packets(nfc_fsm *f, const nfc_packet *packets, size_t n_packets, const uint8_t *bits0, const uint8_t *bits1,
-                            nfc_frame *frames_out, uint8_t *bytes_out, size_t bytes_cap, size_t *bytes_used, uint16_t *enc_out) {
-    if (!f || (n_packets && (!packets || !frames_out || !bytes_out))) return NFC_ERR_ARG;
-    size_t used = 0;
-    for (size_t i = 0; i < n_packets; i++) {
-        const nfc_packet &p = packets[i];
-        if (p.type != 0 && p.type != 1) return NFC_ERR_ARG;
-        const uint8_t *bits = p.type ? bits1 : bits0;
-        if (p.n_bits && !bits) return NFC_ERR_ARG;
-        if (used + p.n_bits / 9 + 1 > bytes_cap) return NFC_ERR_ARG;
-        fsm_process(*f, bits ? bits + p.bit_off : nullptr, p.n_bits, p.type, &frames_out[i], bytes_out + used, enc_out ? enc_out + used : nullptr);
-        frames_out[i].byte_off = (uint32_t)used;
-        used += std::max<size_t>(frames_out[i].n_bytes, frames_out[i].n_enc);
-    }
-    if (bytes_used) *bytes_used = used;
-    return NFC_OK;
-}
-int nfc_fsm_process_frames(nfc_fsm *f, const nfc_raw_frame *frames, size_t n, const uint8_t *bytes0, const uint8_t *par0, const uint8_t *bytes1,
-                           const uint8_t *par1, nfc_frame *frames_out, uint8_t *bytes_out, size_t bytes_cap, size_t *bytes_used, uint16_t *enc_out) {
-    if (!f || (n && (!frames || !frames_out || !bytes_out))) return NFC_ERR_ARG;
-    size_t used = 0;
-    for (size_t i = 0; i < n; i++) {
-        const nfc_raw_frame &r = frames[i];
-        if ((r.type != 0 && r.type != 1) || (r.flags & NFC_RAW_CUT)) return NFC_ERR_ARG;
-        const uint8_t *b = r.type ? bytes1 : bytes0, *p = r.type ? par1 : par0;
-        if (r.n_bytes && (!b || !p)) return NFC_ERR_ARG;
-        if (used + r.n_bits / 9 + 1 > bytes_cap) return NFC_ERR_ARG;
-        fsm_process_frame(*f, r, b ? b + r.byte_off : nullptr, p ? p + r.byte_off : nullptr, &frames_out[i], bytes_out + used,
-                          enc_out ? enc_out + used : nullptr);
-        frames_out[i].byte_off = (uint32_t)used;
-        used += std::max<size_t>(frames_out[i].n_bytes, frames_out[i].n_enc);
-    }
-    if (bytes_used) *bytes_used = used;
-    return NFC_OK;
-}
-int nfc_command_count(void) { return CMD_COUNT; }
-int nfc_command_get(int cmd, nfc_command_info *out) {
-    if (cmd < 0 || cmd >= CMD_COUNT || !out) return NFC_ERR_ARG;
-    const CommandDef &c = COMMANDS[cmd];
-    memset(out, 0, sizeof *out);
-    strncpy(out->name, c.name, sizeof out->name - 1);
-    out->stage = c.stage;
-    out->type = c.type;
-    out->crc = c.crc;
-    out->n_header = c.n_header;
-    out->n_extra = c.n_extra;
-    out->xor_check = c.xor_check;
-    out->header[0] = c.header[0];
-    out->header[1] = c.header[1];
-    return NFC_OK;
-}
-int nfc_crc_a(const uint8_t *data, size_t n, uint8_t out[2]) {
-    if ((n && !data) || !out) return NFC_ERR_ARG;
-    const uint16_t c = crc_a(data, n);
-    out[0] = (uint8_t)(c & 0xFF);
-    out[1] = (uint8_t)(c >> 8);
     return NFC_OK;
 }
 

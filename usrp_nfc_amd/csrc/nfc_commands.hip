@@ -1,6 +1,7 @@
 // nfc_commands.hip -- k_multi_commands and its small companions in a translation unit of their own (multi_commands.hip.h says what
-// they compute, DESIGN.md 8g why they have this form), and the host side of the restated machine (fsm.hip.h): nfc_host_commands, the
-// kernel's twin, and the hand-over of a host machine (protocol.h: nfc_fsm) to and from the plain state.
+// they compute, DESIGN.md 8g why they have this form), and the C ABI of the protocol layer, all of it over the one machine of
+// fsm.hip.h: the host machine (protocol.h: nfc_fsm -- nfc_fsm_create .. nfc_crc_a), its hand-over to and from the plain state, the
+// sector key table, and nfc_host_commands, the kernel's twin.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -16,7 +17,6 @@
 static_assert(sizeof(nfc_fsm_state) == 88 && sizeof(nfc_fsm_state) % 8 == 0, "nfc_fsm_state is 88 bytes");
 static_assert(sizeof(nfc_frame) == 28, "nfc_frame is seven words");
 static_assert(sizeof(nfc_fsm_key_table) == 560, "nfc_fsm_key_table is 560 bytes");
-static_assert((int)nfc::fsmd::C_COUNT == (int)nfc::CMD_COUNT && (int)nfc::fsmd::C_COMPW2 == (int)nfc::CMD_COMPW2, "one command order");
 
 namespace nfc {
 namespace commands {
@@ -49,71 +49,132 @@ void launch_table_io(uint32_t *tables, uint32_t K, uint32_t k, int set, uint32_t
 }  // namespace commands
 }  // namespace nfc
 
-namespace {
-// the restated command table against protocol.h's, field by field, and the stage tables entry by entry
-bool tables_agree() {
-    using namespace nfc;
-    for (int c = 0; c < CMD_COUNT; c++) {
-        const CommandDef &h = COMMANDS[c];
-        const fsmd::Def d = fsmd::def_of(c);
-        if (d.stage() != h.stage || d.n_header() != h.n_header || d.type() != h.type || d.crc() != h.crc || d.n_extra() != h.n_extra ||
-            d.xor_check() != h.xor_check || d.total() != h.total() || h.total() > fsmd::MAX_COMMAND_BYTES)
-            return false;
-        if ((h.n_header >= 1 && d.h0() != h.header[0]) || (h.n_header >= 2 && d.h1 != h.header[1])) return false;
-    }
-    for (int v = 0; v < 12; v++) {
-        const uint32_t tw = fsmd::tag_stage(v), rw = fsmd::reader_stage(v);
-        for (int k = 0; k < 4; k++) {
-            const int want_t = v < 6 ? TAG_STAGE[v][k] : -1, want_r = (v < 8 && k < 3) ? READER_STAGE[v][k] : -1;
-            const int got_t = (int)((tw >> (8 * k)) & 0xFFu), got_r = (int)((rw >> (8 * k)) & 0xFFu);
-            if ((got_t == 0xFF ? -1 : got_t) != want_t || (got_r == 0xFF ? -1 : got_r) != want_r) return false;
-        }
-    }
-    return true;
-}
-}  // namespace
+using namespace nfc;
 
 extern "C" {
 
+// ---- the host machine: packets -> bytes -> commands ("next" row f1, host only: protocol.h) ----
+int nfc_fsm_create(nfc_fsm **out) {
+    if (!out) return NFC_ERR_ARG;
+    *out = new nfc_fsm();
+    return NFC_OK;
+}
+void nfc_fsm_destroy(nfc_fsm *f) { delete f; }
+int nfc_fsm_reset(nfc_fsm *f) {   // (the table is emptied, both keys are FF..FF again)
+    if (!f) return NFC_ERR_ARG;
+    *f = nfc_fsm();
+    return NFC_OK;
+}
+int nfc_fsm_process(nfc_fsm *f, const uint8_t *bits, size_t n_bits, int packet_type, nfc_frame *out, uint8_t *bytes_out, size_t bytes_cap,
+                    uint16_t *enc_out) {
+    if (!f || !out || !bytes_out || (n_bits && !bits) || (packet_type != 0 && packet_type != 1)) return NFC_ERR_ARG;
+    if (n_bits > 0xFFFFFFFFull || bytes_cap < n_bits / 9 + 1) return NFC_ERR_ARG;
+    fsm_process(*f, bits, n_bits, packet_type, out, bytes_out, enc_out);
+    return NFC_OK;
+}
+int nfc_fsm_process_outgoing(nfc_fsm *f, const uint8_t *bits, size_t n_bits, int cmd, uint8_t *bits_out) {
+    if (!f || (n_bits && (!bits || !bits_out)) || cmd < 0 || cmd >= fsmd::C_COUNT) return NFC_ERR_ARG;
+    return fsm_process_outgoing(*f, bits, n_bits, cmd, bits_out);
+}
+int nfc_fsm_set_keys(nfc_fsm *f, const uint8_t key_a[6], const uint8_t key_b[6]) {
+    if (!f || !key_a || !key_b) return NFC_ERR_ARG;
+    f->key_a = fsmd::key_of(key_a);
+    f->key_b = fsmd::key_of(key_b);
+    return NFC_OK;
+}
+// (both batch forms pack their outputs: a frame's bytes and enc entries start where the longer of the previous frame's two ended)
+int nfc_fsm_process_packets(nfc_fsm *f, const nfc_packet *packets, size_t n_packets, const uint8_t *bits0, const uint8_t *bits1,
+                            nfc_frame *frames_out, uint8_t *bytes_out, size_t bytes_cap, size_t *bytes_used, uint16_t *enc_out) {
+    if (!f || (n_packets && (!packets || !frames_out || !bytes_out))) return NFC_ERR_ARG;
+    size_t used = 0;
+    for (size_t i = 0; i < n_packets; i++) {
+        const nfc_packet &p = packets[i];
+        if (p.type != 0 && p.type != 1) return NFC_ERR_ARG;
+        const uint8_t *bits = p.type ? bits1 : bits0;
+        if (p.n_bits && !bits) return NFC_ERR_ARG;
+        if (used + p.n_bits / 9 + 1 > bytes_cap) return NFC_ERR_ARG;
+        fsm_process(*f, bits ? bits + p.bit_off : nullptr, p.n_bits, p.type, &frames_out[i], bytes_out + used, enc_out ? enc_out + used : nullptr);
+        frames_out[i].byte_off = (uint32_t)used;
+        used += frames_out[i].n_bytes > frames_out[i].n_enc ? frames_out[i].n_bytes : frames_out[i].n_enc;
+    }
+    if (bytes_used) *bytes_used = used;
+    return NFC_OK;
+}
+int nfc_fsm_process_frames(nfc_fsm *f, const nfc_raw_frame *frames, size_t n, const uint8_t *bytes0, const uint8_t *par0, const uint8_t *bytes1,
+                           const uint8_t *par1, nfc_frame *frames_out, uint8_t *bytes_out, size_t bytes_cap, size_t *bytes_used, uint16_t *enc_out) {
+    if (!f || (n && (!frames || !frames_out || !bytes_out))) return NFC_ERR_ARG;
+    size_t used = 0;
+    for (size_t i = 0; i < n; i++) {
+        const nfc_raw_frame &r = frames[i];
+        if ((r.type != 0 && r.type != 1) || (r.flags & NFC_RAW_CUT)) return NFC_ERR_ARG;
+        const uint8_t *b = r.type ? bytes1 : bytes0, *p = r.type ? par1 : par0;
+        if (r.n_bytes && (!b || !p)) return NFC_ERR_ARG;
+        // (the whole slot of n_bytes is written: a frame has no more bytes than its bits make)
+        if (r.n_bytes > r.n_bits / 9 + 1 || used + r.n_bits / 9 + 1 > bytes_cap) return NFC_ERR_ARG;
+        fsm_process_frame(*f, r.type, r.flags, r.n_bytes, b ? b + r.byte_off : nullptr, p ? p + r.byte_off : nullptr, &frames_out[i],
+                          bytes_out + used, enc_out ? enc_out + used : nullptr);
+        frames_out[i].byte_off = (uint32_t)used;
+        used += frames_out[i].n_bytes > frames_out[i].n_enc ? frames_out[i].n_bytes : frames_out[i].n_enc;
+    }
+    if (bytes_used) *bytes_used = used;
+    return NFC_OK;
+}
+
+int nfc_command_count(void) { return fsmd::C_COUNT; }
+int nfc_command_get(int cmd, nfc_command_info *out) {
+    static const char *const NAMES[fsmd::C_COUNT] = {"REQA",   "WUPA",   "ATQAUL", "ATQA1K", "ATQA1K", "ATQADS", "ANTI1R", "ANTI1U", "ANTI1G",
+                                                     "SEL1R",  "SEL1U",  "SEL1K",  "ANTI2R", "ANTI2T", "AUTHA",  "AUTHB",  "RANDTA", "RANDRB",
+                                                     "RANDTB", "SEL2R",  "SEL2T",  "READR",  "READT",  "HALT",   "WRITE",  "COMPW1", "COMPW2"};
+    if (cmd < 0 || cmd >= fsmd::C_COUNT || !out) return NFC_ERR_ARG;
+    const fsmd::Def c = fsmd::def_of(cmd);
+    memset(out, 0, sizeof *out);
+    strncpy(out->name, NAMES[cmd], sizeof out->name - 1);
+    out->stage = c.stage();
+    out->type = c.type();
+    out->crc = c.crc();
+    out->n_header = c.n_header();
+    out->n_extra = c.n_extra();
+    out->xor_check = c.xor_check();
+    out->header[0] = (uint8_t)c.h0();
+    out->header[1] = (uint8_t)c.h1;
+    return NFC_OK;
+}
+int nfc_crc_a(const uint8_t *data, size_t n, uint8_t out[2]) {
+    if ((n && !data) || !out) return NFC_ERR_ARG;
+    const uint16_t c = crc_a(data, n);
+    out[0] = (uint8_t)(c & 0xFF);
+    out[1] = (uint8_t)(c >> 8);
+    return NFC_OK;
+}
+
+// ---- the plain state, and the hand-over of a host machine to and from it ----
 int nfc_fsm_state_init(nfc_fsm_state *st) {
     if (!st) return NFC_ERR_ARG;
-    nfc::fsmd::Machine M;
-    nfc::fsmd::machine_init(M);
+    fsmd::Machine M;
+    fsmd::machine_init(M);
     memset(st, 0, sizeof *st);
-    nfc::fsmd::machine_to_state(M, *st);
+    fsmd::machine_to_state(M, *st);
     return NFC_OK;
 }
 
 int nfc_fsm_get_state(const nfc_fsm *f, nfc_fsm_state *st) {
     if (!f || !st) return NFC_ERR_ARG;
-    if (f->uid.size() > nfc::fsmd::UID_CAP) return NFC_ERR_ARG;
+    if (f->uid.size() > fsmd::UID_CAP) return NFC_ERR_ARG;   // the plain state holds 32 UID bytes
+    fsmd::Machine M = *f;   // (the Machine of it: the UID goes into its words)
+    for (size_t i = 0; i < f->uid.size(); i++) fsmd::uid_put(M, (uint32_t)i, f->uid[i]);
+    M.uid_len = (uint32_t)f->uid.size();
     memset(st, 0, sizeof *st);
-    st->cur_cmd = f->cur_cmd;
-    st->tag_type = f->tag_type;
-    st->encrypted = f->encrypted;
-    st->cur_key = f->cur_key;
-    st->cipher = f->cipher.st;
-    memcpy(st->ar, f->cipher.ar, 4);
-    memcpy(st->at, f->cipher.at, 4);
-    memcpy(st->key_a, f->key_a, 6);
-    memcpy(st->key_b, f->key_b, 6);
-    st->uid_len = (uint32_t)f->uid.size();
-    if (!f->uid.empty()) memcpy(st->uid, f->uid.data(), f->uid.size());
+    fsmd::machine_to_state(M, *st);
     return NFC_OK;
 }
 
 int nfc_fsm_set_state(nfc_fsm *f, const nfc_fsm_state *st) {
-    if (!f || !st || nfc::fsmd::state_fault(*st)) return NFC_ERR_ARG;
-    f->cur_cmd = st->cur_cmd;
-    f->tag_type = st->tag_type;
-    f->encrypted = st->encrypted;
-    f->cipher.st = st->cipher;
-    memcpy(f->cipher.ar, st->ar, 4);
-    memcpy(f->cipher.at, st->at, 4);
-    memcpy(f->key_a, st->key_a, 6);
-    memcpy(f->key_b, st->key_b, 6);
-    f->cur_key = st->cur_key;
+    if (!f || !st || fsmd::state_fault(*st)) return NFC_ERR_ARG;
+    fsmd::Machine &M = *f;
+    fsmd::machine_from_state(M, *st);
     f->uid.assign(st->uid, st->uid + st->uid_len);
+    fsmd::uid_clear(M);   // (the holder is the vector; and the host machine keeps no flags)
+    M.flags = 0;
     return NFC_OK;
 }
 
@@ -154,13 +215,10 @@ int nfc_host_commands(nfc_fsm_state *st, const nfc_raw_frame *merged, size_t n, 
 int nfc_host_commands_keyed(nfc_fsm_state *st, const nfc_fsm_key_table *table, const nfc_raw_frame *merged, size_t n, const uint8_t *bytes0,
                             const uint8_t *par0, const uint8_t *bytes1, const uint8_t *par1, nfc_frame *out, uint8_t *data, uint16_t *enc,
                             size_t cap, size_t *used) {
-    using namespace nfc;
-    static const bool agree = tables_agree();
-    if (!agree) return NFC_ERR_INTERNAL;
     if (!st || fsmd::state_fault(*st) || (n && (!merged || !out))) return NFC_ERR_ARG;
     if (table && skeys::table_fault(*table)) return NFC_ERR_ARG;
     const skeys::HostTable keys = {table};
-    fsmd::Machine M;
+    fsmd::Machine M;   // (the kernel's UID holder, capped: this is its twin)
     fsmd::machine_from_state(M, *st);
     size_t at = 0;
     for (size_t i = 0; i < n; i++) {

@@ -1,5 +1,5 @@
-// sector_keys.h -- the per-sector key table of the protocol machines, stated once for the host machine (protocol.h), its restatement
-// (fsm.hip.h: nfc_host_commands on the CPU) and k_multi_commands (multi_commands.hip.h).  DESIGN.md 8j.
+// sector_keys.h -- the per-sector key table of the protocol machine (fsm.hip.h), stated once for its three holders: the host machine
+// (protocol.h), nfc_host_commands on the CPU and k_multi_commands (multi_commands.hip.h).  DESIGN.md 8j.
 //
 // The rule.  A Classic card has at most 40 sectors: blocks 0 .. 127 lie four to a sector, blocks 128 .. 255 sixteen.  A table has 80
 // slots, slot = (key_type & 1) * 40 + sector, each empty or six key bytes.  A machine that recognises AUTHA / AUTHB takes the block from

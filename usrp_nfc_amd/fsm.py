@@ -2,7 +2,7 @@
 
 `fsm(callback)` keeps the reference's constructor and `process_bits(bits, packet_type)` entry point, so
 `background` / `CombinedPacketProcessor` hand packets to it unchanged; frame repair, parity, CRC_A, command lookup
-and UID tracking run in the shared library (csrc/protocol.h).  `process_packets` is the batch form for the
+and UID tracking run in the shared library (csrc/fsm.hip.h, the host machine over it: csrc/protocol.h).  `process_packets` is the batch form for the
 packet tables a GPU batch produces.  MIFARE Classic sessions are decrypted (CRYPTO1: cipher.py, lfsr.py) with the
 keys of set_keys (default FF..FF), nested authentications included; as in the reference, the ciphertext of every
 frame of a session is printed before its decoded command.  A card whose sectors have different keys takes a table
@@ -20,7 +20,7 @@ from .command import CommandStructure, CommandType
 NFC_CMD_UNKNOWN, NFC_CMD_PARITY_ERROR = -1, -2
 FRAME_EXTRA_ERROR, FRAME_MANY_MORE_ERROR, FRAME_UID_MISMATCH, FRAME_ENCRYPTED = 1, 2, 4, 8
 FRAME_AR_OK, FRAME_AR_ERROR, FRAME_AT_OK, FRAME_AT_ERROR = 16, 32, 64, 128
-_SEL2R = 19   # csrc/protocol.h: CMD_SEL2R
+_SEL2R = 19   # csrc/fsm.hip.h: C_SEL2R
 FRAME_DTYPE = np.dtype([('cmd', '<i4'), ('type', '<i4'), ('byte_off', '<u4'), ('n_bytes', '<u2'), ('n_header', '<u2'),
                         ('n_extra', '<u2'), ('n_crc', '<u2'), ('flags', '<u4'), ('n_enc', '<u2'), ('pad', '<u2')])
 

@@ -32,7 +32,7 @@ class CRC:
     @staticmethod
     def calculate_crc(data, cktp=0x6363):
         if cktp == CRC.CRC_14443_A:
-            from .fsm import crc_a     # the shared library's (csrc/protocol.h: nfc_crc_a), pinned by the reference's traces
+            from .fsm import crc_a     # the shared library's (csrc/fsm.hip.h: crc_a), pinned by the reference's traces
             return crc_a(data)
         reg = cktp & 0xFFFF
         for byte in data:
