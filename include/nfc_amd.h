@@ -160,7 +160,7 @@ typedef struct {
     uint32_t device_allocs;   /* device / pinned buffers (re)allocated while the last batch was submitted and processed: 0 in the steady state
                                * of a stream -- the buffers are sized when a stream's first batch of a length is seen, with room for four
                                * times the transition density of a clean capture, so a stream that turns dense does not pay hipMalloc */
-    uint32_t tail_fused;      /* 1: the last batch's edge, decode and framing stages ran as ONE launch (test build, NFC_TAIL=1); the product build: 0 */
+    uint32_t tail_fused;      /* always 0, kept for the layout: until its removal the test build's fused tail (one launch for the edge, decode and framing stages) set it */
     uint32_t chunks_rerun_in_place; /* ... of chunks_rerun: re-runs by the workgroup kernel in the form that evaluates a failed round in place
                                      * (up to a machine-full of failing chunks per round), the rest by the one-wave exact kernel */
 } nfc_stats;

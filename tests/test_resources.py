@@ -89,11 +89,6 @@ def test_single_context_end_to_end():
     single_context(api.NFC_IN_IQ_F32, capture(), 2)
 
 
-def test_single_context_with_the_fused_tail(monkeypatch):
-    monkeypatch.setenv('NFC_TAIL', '1')   # buffers of its own: the look-back status words, the ticket, the alternate bit arrays
-    single_context(api.NFC_IN_IQ_F32, capture(), 2)
-
-
 def test_single_context_of_an_int16_kind():
     single_context(api.NFC_IN_IQ_I16, synth.quantise_sc16(capture()), 2)   # (another kind's kernel table)
 

@@ -26,18 +26,16 @@ done
 [ -x tools/ubench/stream_chunks ] && tools/ubench/stream_chunks > $out/${tag}_stream_ceiling.txt 2>&1
 # where the workgroups of the later stages spend their time (a build with -DNFC_TAIL_PROF: scratch/r5/tailprof.so), and the waves of
 # the re-run kernel on the stress captures (-DNFC_GEN_PROF: scratch/r5/genprof.so)
-# (the switches -- NFC_DEC_SPEC, NFC_TAIL -- exist in the test build only: the profiling builds carry -DNFC_TEST_HOOKS too)
+# (the switch -- NFC_DEC_SPEC -- exists in the test build only: the profiling builds carry -DNFC_TEST_HOOKS too)
 if [ -f scratch/r6/tailprof.so ]; then
-  { echo "# NFC_AMD_LIB=<-DNFC_TEST_HOOKS -DNFC_TAIL_PROF build> python tools/tailprof.py miller 1e8   (s_memtime ticks, thread 0 of every workgroup)"; NFC_AMD_LIB=scratch/r6/tailprof.so python3 tools/tailprof.py miller 1e8; echo "# ... NFC_DEC_SPEC=0: the three-launch decode"; NFC_DEC_SPEC=0 NFC_AMD_LIB=scratch/r6/tailprof.so python3 tools/tailprof.py miller 1e8;
-    echo "# ... NFC_TAIL=1: the fused tail (tail.hip.h: built, measured, not adopted), ticks summed over a workgroup's tiles"; NFC_TAIL=1 NFC_AMD_LIB=scratch/r6/tailprof.so python3 tools/tailprof6.py miller 1e8; } > $out/${tag}_tail_phases.txt 2>&1
+  { echo "# NFC_AMD_LIB=<-DNFC_TEST_HOOKS -DNFC_TAIL_PROF build> python tools/tailprof.py miller 1e8   (s_memtime ticks, thread 0 of every workgroup)"; NFC_AMD_LIB=scratch/r6/tailprof.so python3 tools/tailprof.py miller 1e8; echo "# ... NFC_DEC_SPEC=0: the three-launch decode"; NFC_DEC_SPEC=0 NFC_AMD_LIB=scratch/r6/tailprof.so python3 tools/tailprof.py miller 1e8; } > $out/${tag}_tail_phases.txt 2>&1
 fi
 if [ -f scratch/r6/genprof.so ]; then
   { echo "# NFC_AMD_LIB=<-DNFC_GEN_PROF build> python tools/genprof.py hover / dropsteps   (the atomics of the iteration counter stretch the ticks: read the counts)"; NFC_AMD_LIB=scratch/r6/genprof.so python3 tools/genprof.py hover; NFC_AMD_LIB=scratch/r6/genprof.so python3 tools/genprof.py dropsteps; } > $out/${tag}_rerun_phases.txt 2>&1
 fi
-# the fused tail against the five launches it would replace: same call, alternating (tools/ab.py env: the test build)
-{ echo "# python tools/ab.py env miller --rounds 3 NFC_TAIL=0 NFC_TAIL=1"; python3 tools/ab.py env miller --rounds 3 "NFC_TAIL=0" "NFC_TAIL=1";
-  echo "# per kernel under rocprofv3, NFC_TAIL=1 (test build)"; NFC_TAIL=1 NFC_AMD_LIB=usrp_nfc_amd/libnfc_amd_hooks.so bash tools/kstats.sh miller tail1 | grep -v "^$";
-  echo "# chunks cut by dispatch row against the equal cut, same call, alternating"; python3 tools/ab.py env miller --rounds 4 "NFC_WG_ROWBAL=0" "NFC_WG_ROWBAL=1"; } > $out/${tag}_tail_fused_ab.txt 2>&1
+# chunks cut by dispatch row against the equal cut (the file keeps the name the committed records have: profiles/r06_tail_fused_ab.txt
+# also holds the A/B of the fused tail, whose source is no longer in the tree -- DESIGN.md 6c)
+{ echo "# chunks cut by dispatch row against the equal cut, same call, alternating"; python3 tools/ab.py env miller --rounds 4 "NFC_WG_ROWBAL=0" "NFC_WG_ROWBAL=1"; } > $out/${tag}_tail_fused_ab.txt 2>&1
 # per-wave counters instead of the first barrier of a round (k_threshold_wg<KIND, NR, false, true>, test build): same call, alternating
 { echo "# python tools/ab.py env miller --rounds 4 NFC_WG_FLAGS=0 NFC_WG_FLAGS=1"; python3 tools/ab.py env miller --rounds 4 "NFC_WG_FLAGS=0" "NFC_WG_FLAGS=1";
   echo "# python tools/ab.py env manchester --rounds 2 NFC_WG_FLAGS=0 NFC_WG_FLAGS=1"; python3 tools/ab.py env manchester --rounds 2 "NFC_WG_FLAGS=0" "NFC_WG_FLAGS=1";

@@ -10,22 +10,6 @@ namespace {
 
 std::string g_create_error;
 
-// (the round-5 form of the tail: the certification shares the edge writer's launch -- kept beside k_tail for the A/B)
-__global__ __launch_bounds__(256) void k_certify_and_write(CertLaunch C, EdgeArgs E, size_t nwords, const EdgeAgg *partials, const EdgeAgg *supers,
-                                                          const EdgeRec *recs, uint32_t *epos, uint16_t *ecode, uint32_t cap, bool own_prefix, uint32_t *total_out,
-                                                          Last2 *last2_total, EdgeCarry *carry_out) {
-    const uint32_t tiles = gridDim.x - C.blocks;
-    if (blockIdx.x == 0) {
-        certify_block(C.A, C.cert, nullptr, C.ring_next, C.carry, C.sum, C.blocks - 1, C.blocks);
-        return;
-    }
-    if (blockIdx.x > tiles) {
-        certify_block(C.A, C.cert, nullptr, C.ring_next, C.carry, C.sum, blockIdx.x - tiles - 1, C.blocks);
-        return;
-    }
-    write_edges_tile(E, nwords, partials, supers, recs, epos, ecode, cap, own_prefix, total_out, last2_total, carry_out, tiles - blockIdx.x, tiles);
-}
-
 }  // namespace
 
 // totals layout (device scalars inside DevState)
@@ -68,7 +52,7 @@ namespace {
 // nfc_record_pcm16_device).  README.md lists them.  A value is unset or what the variable parsed to; nfc_create clamps and applies it.
 struct Switches {
     std::optional<std::string> debug_clk;
-    std::optional<int> no_small, debug_bad_launch, debug_redo_submitted, debug, trace, trace_alloc, no_submit_ahead, tail, wg, wg_rounds, wg_bulk, wg_rerun, wg_rowbal, wg_nr, wg_flags, wg_per_cu, wg_per_cu_ahead, wg_ex, lean, lean_rounds,
+    std::optional<int> no_small, debug_bad_launch, debug_redo_submitted, debug, trace, trace_alloc, no_submit_ahead, wg, wg_rounds, wg_bulk, wg_rerun, wg_rowbal, wg_nr, wg_flags, wg_per_cu, wg_per_cu_ahead, wg_ex, lean, lean_rounds,
         lean_waves, edge_prefix, dec_spec, dec_runin, spin_wait, chunk_adapt, chunk_mult;
     std::optional<double> lean_gfac, lean_gmin, eps;
     std::optional<unsigned long> own_prefix_max;
@@ -82,7 +66,7 @@ inline Switches read_switches() {
     const struct { const char *name; std::optional<int> Switches::*at; } ints[] = {
         {"NFC_NO_SMALL", &Switches::no_small}, {"NFC_DEBUG_BAD_LAUNCH", &Switches::debug_bad_launch}, {"NFC_DEBUG_REDO_SUBMITTED", &Switches::debug_redo_submitted},
         {"NFC_DEBUG", &Switches::debug}, {"NFC_TRACE", &Switches::trace}, {"NFC_TRACE_ALLOC", &Switches::trace_alloc}, {"NFC_NO_SUBMIT_AHEAD", &Switches::no_submit_ahead},
-        {"NFC_TAIL", &Switches::tail}, {"NFC_WG", &Switches::wg}, {"NFC_WG_ROUNDS", &Switches::wg_rounds}, {"NFC_WG_BULK", &Switches::wg_bulk},
+        {"NFC_WG", &Switches::wg}, {"NFC_WG_ROUNDS", &Switches::wg_rounds}, {"NFC_WG_BULK", &Switches::wg_bulk},
         {"NFC_WG_RERUN", &Switches::wg_rerun}, {"NFC_WG_NR", &Switches::wg_nr}, {"NFC_WG_FLAGS", &Switches::wg_flags}, {"NFC_WG_PER_CU", &Switches::wg_per_cu},
         {"NFC_WG_PER_CU_AHEAD", &Switches::wg_per_cu_ahead}, {"NFC_WG_EX", &Switches::wg_ex}, {"NFC_LEAN", &Switches::lean}, {"NFC_LEAN_ROUNDS", &Switches::lean_rounds},
         {"NFC_LEAN_WAVES", &Switches::lean_waves}, {"NFC_EDGE_PREFIX", &Switches::edge_prefix}, {"NFC_DEC_SPEC", &Switches::dec_spec}, {"NFC_DEC_RUNIN", &Switches::dec_runin},
@@ -175,7 +159,7 @@ struct nfc_ctx {
     Carry dirty_carry;
     EdgeCarry dirty_ecarry;
     DecCarry dirty_dcarry;
-    bool cert_pending = false;   // the first certification waits to share a launch with the edge stage (k_certify_and_count)
+    bool cert_pending = false;   // the first certification waits to share a launch with the edge writer (host_stages.h: k_certify_and_write)
     CertLaunch cert;
     // debugging switches, read ONCE for nfc_create (read_switches: an inherited environment must not reach the per-launch path)
     bool dbg_bad_launch = false, dbg_redo_submitted = false, dbg_no_submit_ahead = false, dbg_any = false, dbg_clk = false, dbg_trace = false;
@@ -220,7 +204,7 @@ struct nfc_ctx {
         uint64_t g0 = 0;
         int slot = 0, planes = -1, ring_in = 0, timing = 0;   // (timing: nfc_set_timing's level when the batch was submitted)
         uint32_t allocs = 0;   // buffers (re)allocated on its behalf so far (nfc_stats.device_allocs)
-        bool fast = false, b_enqueued = false, timed = false, spec = false, tail = false;   // (spec: its decode stage ran in the speculative form)
+        bool fast = false, b_enqueued = false, timed = false, spec = false;   // (spec: its decode stage ran in the speculative form)
     } sub[NSUB];
     int sub_count = 0;             // batches submitted and not yet waited for (sub[0] the oldest)
     uint32_t slot_next = 0;
@@ -252,17 +236,6 @@ struct nfc_ctx {
     // records' 12.5 MB of traffic cost more than the writer's instructions (measured: profiles/edge_prefix_ab.txt) and the writer scans.
     // -1: that rule; the test build's NFC_EDGE_PREFIX=0 / 1: never / always
     int edge_prefix = -1;
-    // the fused tail (tail.hip.h: k_tail): status words of its look-backs, the ticket counter, the launch epoch; the packed bit arrays
-    // alternate between two buffers -- a batch's launch clears the one the NEXT batch's tiles will or into
-    DevBuf d_tail_st, d_tail_ticket, d_bits_alt[2];
-    uint32_t tail_epoch = 0, tail_ticket_base = 0, tail_seq = 0xFFFFFFFFu;
-    bool tail_on = false, tail_reset = true, tail_now = false;   // (tail_on: NFC_TAIL=1 in the test build)
-    uint32_t tail_tw_used = 512, tail_dense_repeats = 0, tail_peak = 0, tail_peak_tw = 512;
-    bool sym_from_tail = false;            // the last batch's out-bytes came from k_tail: the symbol reader builds its tile aggregates first
-    uint32_t tail_tw = 512;         // words per tile: halves when a tile's entries did not fit the staging, grows back after calm batches
-    int tail_tw_hold = 0;
-    uint32_t bits_clean[2] = {0, 0}, alt_clean[2] = {0, 0};   // words of d_bits / d_bits_alt known to be zero
-    int tail_occ[2] = {0, 0};                // resident workgroups per CU of k_tail<false / true>
     DevBuf d_spec;                           // per decode tile: its map, the state it assumed (decode.hip.h: DecSpec)
     DevBuf d_stage_bits[2], d_stage_cb[2], d_stage_ci[2], d_stage_q[2], d_stage_own;   // ... and what it stages for k_concat (TileStage)
     DevBuf d_pack;                           // nfc_get_state staging
@@ -308,7 +281,7 @@ int fail(nfc_ctx *c, int code, const char *fmt, ...) {
     va_start(ap, fmt);
     vsnprintf(buf, sizeof buf, fmt, ap);
     va_end(ap);
-    if (c) c->err = buf, c->tail_reset = true;   // (after any failure the fused tail's ticket counter is re-armed: tail.hip.h)
+    if (c) c->err = buf;
     else g_create_error = buf;
     return code;
 }

@@ -47,9 +47,6 @@
 #include "scan.hip.h"
 #include "small.hip.h"
 #include "threshold.hip.h"
-#ifdef NFC_TEST_HOOKS
-#include "tail.hip.h"   // the fused tail: built, measured, not adopted -- the test build keeps it exact
-#endif
 #include "threshold_lean.hip.h"
 #include "threshold_wg.hip.h"
 #include "kind_kernels.h"   // (every kind's threshold-stage kernels; the complex integer kinds': nfc_iq16.hip, nfc_iq8.hip)
@@ -120,7 +117,6 @@ int create_plan_params(nfc_ctx *c, const nfc_params *p, const Switches &sw, floa
     C = std::max(C, c->mx + 2);
     c->rows_per_step = 4;
     c->use_small = sw.no_small ? 0 : 1;   // (the first seven: set by being there, whatever the value)
-    if (sw.tail) c->tail_on = *sw.tail != 0;
     c->dbg_bad_launch = sw.debug_bad_launch.has_value();
     c->dbg_redo_submitted = sw.debug_redo_submitted.has_value();
     c->dbg_any = sw.debug.has_value();
@@ -526,7 +522,6 @@ int nfc_push_edges(nfc_ctx *c, const nfc_edge *host_edges, size_t n64) {
         HIPCHK(c, hipMemcpyAsync(c->d_ecode.p, code.data(), (size_t)n * 2, hipMemcpyHostToDevice, c->st));
     }
     HIPCHK(c, hipMemcpyAsync(dT(c) + TOT_EDGES, &n, 4, hipMemcpyHostToDevice, c->st));
-    c->tail_now = false;
     const int rc = run_decode(c);   // k_dec_spec (or k_dec_reduce -> k_dec_apply) -> k_frame_write -> k_pkt_finish (mirrors the state block)
     if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(c->st));
@@ -1386,14 +1381,6 @@ extern "C" int nfc_debug_tail_prof(unsigned long long *out, int reset) {
         if (hipGetSymbolAddress(&p, HIP_SYMBOL(nfc::g_tail_prof)) != hipSuccess || hipMemset(p, 0, bytes) != hipSuccess) return -1;
     }
     return 0;
-}
-#endif
-#ifdef NFC_TAIL_PROF
-extern "C" int nfc_debug_lb_tries(int reset) {
-    uint32_t v = 0, z = 0;
-    if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(nfc::g_lb_tries), 4) != hipSuccess) return -1;
-    if (reset && hipMemcpyToSymbol(HIP_SYMBOL(nfc::g_lb_tries), &z, 4) != hipSuccess) return -1;
-    return (int)v;
 }
 #endif
 #ifdef NFC_GEN_PROF
