@@ -141,7 +141,7 @@ def nr8():
 
 def route_valu(text, kind, nr):
     """VALU instructions per 64-sample row of each route of k_threshold_wg<kind, nr>: the blocks behind the regular round's take."""
-    name = '_ZN3nfc14k_threshold_wgILi%dELi%dELb0ELb0EEEvNS_7ThrArgsE' % (kind, nr)
+    name = '_ZN3nfc14k_threshold_wgILi%dELi%dELb0EEEvNS_7ThrArgsE' % (kind, nr)
     body = re.search(r'^%s:(.*?)\.end_amdhsa_kernel' % name, text, re.S | re.M).group(1).split('\n')
     takes = [i for i, l in enumerate(body) if 's_waitcnt vmcnt(0)' in l and 'v_accvgpr_read_b32' in body[i + 1] and 'a0' in body[i + 1]]
     out = {}

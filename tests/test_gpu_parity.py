@@ -826,17 +826,14 @@ def _wg_torture(seed, n=1_500_000):
     return synth.iq_from_profile(m, seed=seed, sigma=0.0015)
 
 
-@pytest.mark.parametrize('flags', ['0', '1'])
 @pytest.mark.parametrize('nr', ['4', '8'])
 @pytest.mark.parametrize('chunk', [0, 4096 * 3])
-def test_workgroup_kernel_low_runs_time_outs_and_seams(monkeypatch, nr, chunk, flags):
+def test_workgroup_kernel_low_runs_time_outs_and_seams(monkeypatch, nr, chunk):
     # k_threshold_wg against the C oracle where its reasoning is thinnest (threshold_wg.hip.h): LOW runs longer than max_len whose
     # last sample may have ended on a time-out with HIGH samples in reach of it, runs and HIGH bursts across the seams of steps,
     # rounds and chunks, level steps between supersteps; every step height, the library's chunk length and a short one (many
     # chunk seams: speculation, certification, chunks that start inside a run).  Per-sample val, edges, symbols, packets.
-    # flags = 1 (test build, round 6): the form whose waves wait for each other's counters instead of at a round's first barrier.
     monkeypatch.setenv('NFC_WG_NR', nr)
-    monkeypatch.setenv('NFC_WG_FLAGS', flags)
     L = {'4': 2000, '6': 2000, '8': 2560}[nr]
     iq = _wg_torture(int(nr) * 10 + (1 if chunk else 0))
     params = dict(hi_val=1.1, av_window=L)
@@ -850,19 +847,16 @@ def test_workgroup_kernel_low_runs_time_outs_and_seams(monkeypatch, nr, chunk, f
     assert r['stats'].used_sequential == 0 and len(o.transitions()) > 30000
 
 
-@pytest.mark.parametrize('flags', ['0', '1'])
 @pytest.mark.parametrize('bulk', ['1', '0'])
 @pytest.mark.parametrize('nr', ['4', '8'])
-def test_workgroup_kernel_plane_staging(monkeypatch, bulk, nr, flags):
+def test_workgroup_kernel_plane_staging(monkeypatch, bulk, nr):
     # k_threshold_wg keeps the plane words of its regular rounds in LDS (threshold_wg.hip.h): a whole chunk's, stored when the chunk
     # is done (bulk), or a ring of 2 FR rounds stored FR at a time by one wave as whole lines (NFC_WG_BULK=0; batches submitted ahead
     # always).  Chunks of many rounds -- the ring wraps several times, its last flush is a partial one --, a ragged batch end, a
     # stream that becomes stable in the middle of a chunk (rounds that are not regular store directly, between two flushes), and
     # the same stream submitted ahead.  Per-sample val, edges, symbols, packets against the C oracle.
-    # (flags = 1: the waves of the counter form may be a round apart -- the ring's flush waits a round longer)
     monkeypatch.setenv('NFC_WG_BULK', bulk)
     monkeypatch.setenv('NFC_WG_NR', nr)
-    monkeypatch.setenv('NFC_WG_FLAGS', flags)
     L = {'4': 2000, '8': 2560}[nr]
     rnd = 256 * int(nr)
     iq = _wg_torture(500 + int(nr), 1_000_000 + 12_345)
@@ -1205,11 +1199,11 @@ def _every_kind_oracle(kind, n):
 @pytest.mark.parametrize('kind', sorted(api._KIND_DTYPE))
 def test_every_kind_every_form(monkeypatch, kind):
     # Every slot of an input kind's kernel table (csrc/kind_kernels.h) on one capture: the workgroup kernel with eight and four rows per
-    # step, the lean kernel, the general one with the ring in LDS and in global memory, the per-wave-counter form with four and eight
-    # rows, the sequential kernel; k_fill in all of them.  37 chunks of whole eight-row rounds in a batch of more than 2^18 samples (the
-    # multi-launch stages); the window holds an eight-row round and two steps of the global ring.  A kind without a slot (eight rows: the
-    # float32 real and int16 PCM kinds; the flag form: the complex integer kinds) ignores the switch and is as exact.  Expected: the C
-    # oracle on api.host_envelope of the same raw samples.
+    # step, the lean kernel, the general one with the ring in LDS and in global memory, the sequential kernel; k_fill in all of them.
+    # (The in-place form of the workgroup kernel: test_failed_rounds_are_evaluated_in_place and the iq16 / iq8 modules.)  37 chunks of whole
+    # eight-row rounds in a batch of more than 2^18 samples (the multi-launch stages); the window holds an eight-row round and two steps of
+    # the global ring.  A kind without the eight-row slot (the float32 real and int16 PCM kinds) ignores the switch and is as exact.
+    # Expected: the C oracle on api.host_envelope of the same raw samples.
     n = 600_000
     per = api._KIND_DTYPE[kind][1]
     raw = _every_kind_raw(kind)
@@ -1217,8 +1211,7 @@ def test_every_kind_every_form(monkeypatch, kind):
     assert len(want[3]) > 10 and len(want[0]) > 1000
     # (the product library first -- the default and the sequential form --, then the switches, which bring the test build)
     forms = [({}, 0), ({}, api.NFC_FLAG_FORCE_SEQUENTIAL), (dict(NFC_WG_NR='8'), 0), (dict(NFC_WG_NR='4'), 0), (dict(NFC_WG='0'), 0),
-             (dict(NFC_LEAN='0'), 0), (dict(NFC_RING='global'), 0), (dict(NFC_WG_FLAGS='1', NFC_WG_NR='4'), 0),
-             (dict(NFC_WG_FLAGS='1', NFC_WG_NR='8'), 0)]
+             (dict(NFC_LEAN='0'), 0), (dict(NFC_RING='global'), 0)]
 
     def decode(x, flags):
         with api.NfcContext(input_kind=kind, flags=flags, chunk_samples=16384, **_EVERY_PARAMS) as ctx:

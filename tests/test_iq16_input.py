@@ -34,8 +34,8 @@ def test_iq16_translation_unit_isa_audit(tmp_path):
         m = re.match(r'(_ZN3nfc1[46]k_threshold_(?:lean|wg)\w+):', line)
         if m:
             got[m.group(1)] = line
-    want = {'_ZN3nfc14k_threshold_wgILi4ELi4ELb0ELb0EEEvNS_7ThrArgsE', '_ZN3nfc14k_threshold_wgILi4ELi8ELb0ELb0EEEvNS_7ThrArgsE',
-            '_ZN3nfc14k_threshold_wgILi4ELi4ELb1ELb0EEEvNS_7ThrArgsE', '_ZN3nfc16k_threshold_leanILi4ELi4ELb1EEEvNS_7ThrArgsE',
+    want = {'_ZN3nfc14k_threshold_wgILi4ELi4ELb0EEEvNS_7ThrArgsE', '_ZN3nfc14k_threshold_wgILi4ELi8ELb0EEEvNS_7ThrArgsE',
+            '_ZN3nfc14k_threshold_wgILi4ELi4ELb1EEEvNS_7ThrArgsE', '_ZN3nfc16k_threshold_leanILi4ELi4ELb1EEEvNS_7ThrArgsE',
             '_ZN3nfc16k_threshold_leanILi4ELi4ELb0EEEvNS_7ThrArgsE'}
     assert set(got) == want, r.stdout
     assert all(l.endswith(' 0 findings') for l in got.values()), r.stdout

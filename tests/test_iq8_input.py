@@ -48,15 +48,15 @@ def test_iq8_translation_unit_isa_audit(tmp_path):
             got[m.group(1)] = line
     want = set()
     for k in (5, 6):
-        want |= {'_ZN3nfc14k_threshold_wgILi%dELi4ELb0ELb0EEEvNS_7ThrArgsE' % k, '_ZN3nfc14k_threshold_wgILi%dELi8ELb0ELb0EEEvNS_7ThrArgsE' % k,
-                 '_ZN3nfc14k_threshold_wgILi%dELi4ELb1ELb0EEEvNS_7ThrArgsE' % k, '_ZN3nfc16k_threshold_leanILi%dELi4ELb1EEEvNS_7ThrArgsE' % k,
+        want |= {'_ZN3nfc14k_threshold_wgILi%dELi4ELb0EEEvNS_7ThrArgsE' % k, '_ZN3nfc14k_threshold_wgILi%dELi8ELb0EEEvNS_7ThrArgsE' % k,
+                 '_ZN3nfc14k_threshold_wgILi%dELi4ELb1EEEvNS_7ThrArgsE' % k, '_ZN3nfc16k_threshold_leanILi%dELi4ELb1EEEvNS_7ThrArgsE' % k,
                  '_ZN3nfc16k_threshold_leanILi%dELi4ELb0EEEvNS_7ThrArgsE' % k}
     assert set(got) == want, r.stdout
     assert all(l.endswith(' 0 findings') for l in got.values()), r.stdout
     # both routes are in every workgroup kernel: the integer route's dot products and the float route's packed multiplies
     text = open(asm).read()
     for k, dot in ((5, 'v_dot4c_i32_i8'), (6, 'v_dot4_u32_u8')):
-        body = re.search(r'^_ZN3nfc14k_threshold_wgILi%dELi4ELb0ELb0EEEvNS_7ThrArgsE:(.*?)\.end_amdhsa_kernel' % k, text, re.S | re.M).group(1)
+        body = re.search(r'^_ZN3nfc14k_threshold_wgILi%dELi4ELb0EEEvNS_7ThrArgsE:(.*?)\.end_amdhsa_kernel' % k, text, re.S | re.M).group(1)
         assert dot in body and 'v_pk_mul_f32' in body, k
 
 

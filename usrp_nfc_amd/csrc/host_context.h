@@ -1,4 +1,5 @@
 // host_context.h -- the test build's switches (Switches, read_switches), the context (nfc_ctx), the mirrored state block, launch helpers
+// (the threshold kernels' own launch: host_threshold.h, launch_threshold)
 // (part of nfc_amd.hip: included there, in this order, into one translation unit)
 // Who owns what: every HIP resource of a context -- device and pinned buffers, events, its two streams -- is a member of nfc_ctx of one of
 // dev_buf.h's owning types, so `delete c` is the whole release (nfc_destroy waits for the streams first) and a context that nfc_create could
@@ -41,6 +42,9 @@ struct DevState {
 // what the threshold kernel of a batch submitted ahead may hold of a CU's 160 KB of LDS: the later stages of the batch before it run
 // beside it (the writer stages 12 KB per workgroup, the speculative decode 25 KB)
 constexpr size_t AHEAD_LDS_MAX = 96 * 1024;
+// The one-wave kernels walk steps of STEP samples -- four rows of 64: what kind_kernels.h instantiates (8-row steps measured slower: 126
+// VGPRs, four waves per SIMD) --, and k_threshold_lean takes them four at a time (four steps ahead, 104 registers: nfc_amd.hip, create_plan_device).
+constexpr int LEAN_STEPS_AHEAD = 4;
 constexpr int NRING = 4;   // window buffers: the carried one + one per batch that may be in flight (they rotate)
 constexpr int NSUB = 3;    // batches that may be submitted and not yet waited for
 
@@ -52,7 +56,7 @@ namespace {
 // nfc_record_pcm16_device).  README.md lists them.  A value is unset or what the variable parsed to; nfc_create clamps and applies it.
 struct Switches {
     std::optional<std::string> debug_clk;
-    std::optional<int> no_small, debug_bad_launch, debug_redo_submitted, debug, trace, trace_alloc, no_submit_ahead, wg, wg_rounds, wg_bulk, wg_rerun, wg_rowbal, wg_nr, wg_flags, wg_per_cu, wg_per_cu_ahead, wg_ex, lean, lean_rounds,
+    std::optional<int> no_small, debug_bad_launch, debug_redo_submitted, debug, trace, trace_alloc, no_submit_ahead, wg, wg_rounds, wg_bulk, wg_rerun, wg_rowbal, wg_nr, wg_per_cu, wg_per_cu_ahead, wg_ex, lean, lean_rounds,
         lean_waves, edge_prefix, dec_spec, dec_runin, spin_wait, chunk_adapt, chunk_mult;
     std::optional<double> lean_gfac, lean_gmin, eps;
     std::optional<unsigned long> own_prefix_max;
@@ -67,7 +71,7 @@ inline Switches read_switches() {
         {"NFC_NO_SMALL", &Switches::no_small}, {"NFC_DEBUG_BAD_LAUNCH", &Switches::debug_bad_launch}, {"NFC_DEBUG_REDO_SUBMITTED", &Switches::debug_redo_submitted},
         {"NFC_DEBUG", &Switches::debug}, {"NFC_TRACE", &Switches::trace}, {"NFC_TRACE_ALLOC", &Switches::trace_alloc}, {"NFC_NO_SUBMIT_AHEAD", &Switches::no_submit_ahead},
         {"NFC_WG", &Switches::wg}, {"NFC_WG_ROUNDS", &Switches::wg_rounds}, {"NFC_WG_BULK", &Switches::wg_bulk},
-        {"NFC_WG_RERUN", &Switches::wg_rerun}, {"NFC_WG_NR", &Switches::wg_nr}, {"NFC_WG_FLAGS", &Switches::wg_flags}, {"NFC_WG_PER_CU", &Switches::wg_per_cu},
+        {"NFC_WG_RERUN", &Switches::wg_rerun}, {"NFC_WG_NR", &Switches::wg_nr}, {"NFC_WG_PER_CU", &Switches::wg_per_cu},
         {"NFC_WG_PER_CU_AHEAD", &Switches::wg_per_cu_ahead}, {"NFC_WG_EX", &Switches::wg_ex}, {"NFC_LEAN", &Switches::lean}, {"NFC_LEAN_ROUNDS", &Switches::lean_rounds},
         {"NFC_LEAN_WAVES", &Switches::lean_waves}, {"NFC_EDGE_PREFIX", &Switches::edge_prefix}, {"NFC_DEC_SPEC", &Switches::dec_spec}, {"NFC_DEC_RUNIN", &Switches::dec_runin},
         {"NFC_SPIN_WAIT", &Switches::spin_wait}, {"NFC_CHUNK_ADAPT", &Switches::chunk_adapt}, {"NFC_CHUNK_MULT", &Switches::chunk_mult}};
@@ -101,10 +105,11 @@ inline Switches read_switches() {
 struct nfc_ctx {
     nfc_params P;
     const KindKernels *kk = nullptr;   // the threshold-stage kernels of P.input_kind (kind_kernels.h)
-    int L, mx, C, Lpad, wpb, twords;
+    int L, mx, Lpad, wpb, twords;
     double factor;
     double hi_plus, lo_a, lo_b, hi_a, hi_b;
-    int bands_ok, fast_ok, nfold, rows_per_step, C_min, wave_slots, lds_per_slot;
+    int bands_ok, fast_ok, nfold, wave_slots, lds_per_slot;
+    int C_min;   // the configured chunk length, or the smallest one thr_prepare chooses (a batch's own: ThrPlan.chunk, host_threshold.h)
     uint32_t ring_carried = 0;   // nfc_stats.ring_slots_carried of the last batch adopted
     // the decode stage's speculative form (decode.hip.h: k_dec_spec): on unless NFC_DEC_SPEC=0; run-in edges per thread (2 / 4 / 8);
     // after a batch whose check failed the next batches take the three-launch form (spec_off_left counts them down)
@@ -117,27 +122,27 @@ struct nfc_ctx {
     FrameOut sym_P;
     uint32_t sym_n = 0, sym_tiles = 0;
     uint32_t decode_respeculated = 0;   // batches whose decode stage was repeated with the three-launch form (nfc_stats)
-    int lean = 1, lean_k = 0, lean_rounds = 0, lean_slots = 0;   // pass 0 by k_threshold_lean (NFC_LEAN=0 turns it off), steps per superstep (NFC_LEAN_K)
+    int lean = 1, lean_rounds = 0, lean_slots = 0;   // pass 0 by k_threshold_lean (NFC_LEAN=0 turns it off), the longest superstep (NFC_LEAN_ROUNDS), resident waves
     int n_cus = 1;                                             // compute units of the device
     // ... the rows' chunk lengths over the equal cut's, all but the last row's, by workgroups per CU (measured: host_threshold.h); [0]: NFC_WG_ROWBAL=a,b,c
     double rowbal_f[5][3] = {{1, 1, 1}, {1, 1, 1}, {1.02, 1, 1}, {1.045, 1.004, 1}, {1.036, 1.015, 0.990}};
     bool rowbal_set = false;
-    bool wg_rowbal = true, rowbal_now = false;                 // chunks cut by dispatch row (host_threshold.h: thr_prepare; NFC_WG_ROWBAL=0: the equal cut); this batch is
-    int wg = 1, wg_ok = 0, wg_nr = 4, wg_slots = 0, wg_slots_ahead = 0, wg_now = 0, wg_rounds = 0;
-    int fine_left = 0, fine_adapt = 1, fine_mult = 4;   // batches still to be cut into fine_mult times as many chunks (after a batch that needed re-runs); NFC_CHUNK_ADAPT=0 turns it off   // pass 0 by k_threshold_wg (a chunk per workgroup; NFC_WG=0 turns it off), rounds
-                                                                 // rows of 64 samples per step (NFC_WG_NR), resident workgroups, this batch uses it, rounds per superstep
+    bool wg_rowbal = true;                                     // chunks cut by dispatch row (host_threshold.h: thr_prepare; NFC_WG_ROWBAL=0: the equal cut)
+    // pass 0 by k_threshold_wg (a chunk per workgroup; NFC_WG=0 turns it off): it applies to this stream, rows of 64 samples per step (NFC_WG_NR),
+    // resident workgroups (one batch at a time / for a batch submitted ahead), the longest superstep in rounds (NFC_WG_ROUNDS)
+    int wg = 1, wg_ok = 0, wg_nr = 4, wg_slots = 0, wg_slots_ahead = 0, wg_rounds = 0;
+    // batches still to be cut into fine_mult times as many chunks (after a batch that needed re-runs); NFC_CHUNK_ADAPT=0 turns it off
+    int fine_left = 0, fine_adapt = 1, fine_mult = 4;
     size_t wg_lds = 0, wg_lds_base = 0, wg_lds_bulk_max = 0;   // dynamic LDS of k_threshold_wg: with the staging ring / without any staging / the most a whole chunk's planes may bring it to
-    bool wg_bulk = true, wg_bulk_now = false;                  // a chunk's plane words leave when the chunk is done (NFC_WG_BULK=0: always the ring); this launch may
+    bool wg_bulk = true;                                       // a chunk's plane words leave when the chunk is done (NFC_WG_BULK=0: always the ring)
     int wg_lone_max = 4, wg_lone_div = 64;   // ... how many failing chunks still count as lone: at most this many, and at most one in wg_lone_div
     int wg_rerun_lone = 1;   // a lone failing chunk of a clean batch is re-run by k_threshold_wg, gave up or not (host_threshold.h; NFC_WG_RERUN=0 in the test build: never)
     // re-runs by k_threshold_wg<KIND, 4, true> (failed rounds evaluated in place): where it applies, its LDS, up to how many failing chunks
-    // of a round take it (more: k_threshold, whose one wave per chunk fills the machine where every chunk fails), the launch in progress
+    // of a round take it (more: k_threshold, whose one wave per chunk fills the machine where every chunk fails)
     int wg_ex_ok = 0, wg_ex_max = 0;
     size_t wg_ex_lds = 0;
-    bool wg_ex_launch = false;
-    bool wg_flags = false;   // test build: pass 0 by the instantiations with per-wave counters instead of a round's first barrier
     float lean_gfac = 1.3f, lean_gmin = 9.765625e-4f;   // drift allowance of the next superstep: max(gfac * B, gmin * ss)
-    int gring = 0;   // this batch: the ring of a chunk in global memory instead of LDS
+    // the ring of a chunk in global memory instead of LDS (which batch takes it: thr_prepare)
     int gring_ok = 0, gring_force = 0, wave_slots_g = 0;   // long windows qualify (NFC_RING=lds|global overrides the choice)
     uint32_t own_prefix_max = OWN_PREFIX_MAX_TILES;   // tile counts up to this need no prefix launches (NFC_OWN_PREFIX_MAX overrides)
     int use_small = 1;   // short batches take the one-launch edge / decode / framing kernel (NFC_NO_SMALL=1 turns it off)
@@ -376,66 +381,6 @@ int batch_ok(nfc_ctx *c, bool with_mirror) {
         if (int rc__ = batch_ok((c), (with_mirror))) return rc__;  \
     } while (0)
 
-// Timed launches (nfc_set_timing >= 1) hand the kernel its own start / stop events (hipExtLaunchKernelGGL): the
-// events take the kernel's begin and end, not the position of a marker in the stream, so they neither measure nor add
-// inter-launch gaps.
-void launch_threshold(nfc_ctx *c, const ThrArgs &A, uint32_t nwork, hipEvent_t e0, hipEvent_t e1) {
-    const uint32_t wpb = c->gring ? 4u : (uint32_t)c->wpb;
-    const uint32_t blocks = (nwork + wpb - 1) / wpb;
-    const size_t lds = c->gring ? 0 : (size_t)wpb * c->Lpad * c->lds_per_slot;
-    const ThrKernel kern = c->kk->thr[c->gring ? 1 : 0];
-    if (e0) NFC_LAUNCH_EXT(kern, dim3(blocks), dim3(64 * wpb), lds, c->st, e0, e1, 0, A);
-    else NFC_LAUNCH(kern, dim3(blocks), dim3(64 * wpb), lds, c->st, A);
-}
-// Pass 0 with the LDS ring: the lean optimistic kernel (threshold_lean.hip.h); chunks it gives up on are re-run by k_threshold.
-// ... or, where it applies, with a chunk per workgroup (threshold_wg.hip.h)
-void launch_wg(nfc_ctx *c, const ThrArgs &A, uint32_t nwork, hipEvent_t e0, hipEvent_t e1) {
-    // the staging of the plane words (threshold_wg.hip.h): the whole chunk's when this launch may and the LDS has room, else the ring
-    ThrArgs B = A;
-    size_t lds = c->wg_lds;
-    B.wg_stage_rounds = 2 * wg_flush_rounds(c->wg_nr);
-    {
-        const int rounds = A.C_max / wg_round_samples(c->wg_nr) + 2;   // (the longest chunk of the cut: thr_prepare)
-        const size_t need = c->wg_lds_base + wg_stage_bytes(c->wg_nr, rounds);
-        if (c->wg_bulk_now && c->wg_lds_bulk_max && need <= c->wg_lds_bulk_max) {
-            B.wg_stage_rounds = rounds;
-            lds = need;
-        }
-    }
-    if (c->wg_ex_launch) {   // (re-runs that evaluate failed rounds in place: four rows per step whatever pass 0 ran with)
-        B.wg_stage_rounds = 2 * wg_flush_rounds(4);
-        lds = c->wg_ex_lds;
-    }
-    if (c->dbg_bad_launch) lds += (size_t)1 << 20;
-    // pass 0: eight rows per step where nfc_create chose them (a kind without that slot runs four)
-    ThrKernel kern = c->kk->wg[c->wg_nr == 8 && c->kk->wg[1] ? 1 : 0];
-    // (NFC_WG_FLAGS=1, test build: per-wave counters instead of a round's first barrier -- built and measured, threshold_wg.hip.h)
-    if (c->wg_flags) kern = c->kk->wg_flags[c->wg_nr == 8 && c->kk->wg_flags[1] ? 1 : 0];
-    if (c->wg_ex_launch) kern = c->kk->wg_ex;
-    if (e0) NFC_LAUNCH_EXT(kern, dim3(nwork), dim3(256), lds, c->st, e0, e1, 0, B);
-    else NFC_LAUNCH(kern, dim3(nwork), dim3(256), lds, c->st, B);
-}
-void launch_lean(nfc_ctx *c, const ThrArgs &A, uint32_t nwork, hipEvent_t e0, hipEvent_t e1) {
-    if (c->wg_now) return launch_wg(c, A, nwork, e0, e1);
-    const uint32_t wpb = (uint32_t)c->wpb;
-    const uint32_t blocks = (nwork + wpb - 1) / wpb;
-    // (NFC_DEBUG_BAD_LAUNCH: a dynamic-LDS request the runtime must reject -- the test of the launch checks)
-    const size_t lds = (size_t)wpb * c->Lpad * c->lds_per_slot + (c->dbg_bad_launch ? (size_t)1 << 20 : 0);
-    const ThrKernel kern = c->kk->lean[(1 << c->nfold) == 16 ? 1 : 0];
-    if (e0) NFC_LAUNCH_EXT(kern, dim3(blocks), dim3(64 * wpb), lds, c->st, e0, e1, 0, A);
-    else NFC_LAUNCH(kern, dim3(blocks), dim3(64 * wpb), lds, c->st, A);
-}
-void launch_threshold_kind(nfc_ctx *c, const ThrArgs &A, uint32_t nwork, bool lean = false, const Event *own_events = nullptr) {
-    const bool timed = !own_events && c->timing >= 1 && c->n_kev < 6;
-    hipEvent_t e0 = timed ? (hipEvent_t)c->kev[2 * c->n_kev] : nullptr, e1 = timed ? (hipEvent_t)c->kev[2 * c->n_kev + 1] : nullptr;
-    if (timed) c->n_kev++;
-    if (own_events) {
-        e0 = own_events[0];
-        e1 = own_events[1];
-    }
-    if (lean) launch_lean(c, A, nwork, e0, e1);
-    else launch_threshold(c, A, nwork, e0, e1);
-}
 void launch_fill_kind(nfc_ctx *c, const void *in, uint32_t n, int nchunks, int ring_idx = -1) {
     float *ring = c->d_ring[ring_idx < 0 ? c->ring_cur : ring_idx].as<float>();
     Carry *cr = dC(c);

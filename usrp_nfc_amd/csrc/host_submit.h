@@ -44,35 +44,23 @@ int enqueue_threshold_ahead(nfc_ctx *c, nfc_ctx::Submitted &b) {
     const int rc_prep = thr_prepare(c, b.d_in, b.n, b.n, 0u, 0u, b.g0, unused, b.ring_in, c->d_neg_alt[b.planes], c->d_pos_alt[b.planes], true, A, P);
     c->stats = keep_stats;
     if (rc_prep) return rc_prep;
-    if (!P.lean_applies || c->gring || P.nch < 2) {   // (the general kernel's passes keep the synchronous path)
+    if (P.form != ThrForm::Lean && P.form != ThrForm::Workgroup) {   // (the general kernel's passes keep the synchronous path)
         b.fast = false;
         c->alt_free |= 1u << b.planes;
         b.planes = -1;
         return NFC_OK;
     }
     b.nch = P.nch;
-    b.chunk = (uint32_t)c->C;
+    b.chunk = (uint32_t)P.chunk;
     hipStream_t keep = c->st;
     c->st = c->st_a;
     c->batch_seq = b.seq;
     launch_fill_kind(c, b.d_in, b.n, (int)P.nch, b.ring_in);
-    A.list = nullptr;
-    A.nlist = 0;
-    A.mode = 0;
-    A.cert = P.d_cert;
-    A.sum = (CertSummary *)(dT(c) + TOT_CERT);
-    A.ksteps = c->wg_now ? c->wg_rounds : c->lean_rounds;
-    A.gfac = c->lean_gfac;
-    A.gfloor = c->lean_gmin;
-    A.blk = 1 << c->nfold;
     b.timed = b.timing >= 1;
-    c->wg_bulk_now = false;   // (the other stages' workgroups run beside this kernel: its LDS stays small)
-    launch_threshold_kind(c, A, P.nch, true, b.timed ? c->kev_sub[b.slot] : nullptr);
-    const uint32_t np = P.nch - 1;
-    A.nlist = np;
+    enqueue_pass0(c, P, A, b.timed ? c->kev_sub[b.slot] : nullptr);   // (P.bulk is off: the other stages' workgroups run beside this kernel)
+    A.nlist = P.nch - 1;
     A.ver_zero = 1;   // (pass 0 only: every summary is in buffer 0)
-    NFC_LAUNCH(k_certify, dim3(cert_grid(np)), dim3(256), 0, c->st, A, P.d_cert, (CertInfo *)nullptr,
-               c->d_ring[(b.ring_in + 1) % NRING].as<float>(), dC(c), A.sum);
+    enqueue_certify(c, P, A, nullptr, c->d_ring[(b.ring_in + 1) % NRING].as<float>(), A.sum);
     hipError_t e = hipMemcpyAsync(c->hs_a[b.slot].p, c->d_state.p, sizeof(DevState), hipMemcpyDeviceToHost, c->st);
     if (e == hipSuccess) e = hipEventRecord(c->ev_a[b.slot], c->st);
     c->st = keep;

@@ -88,9 +88,17 @@ static hipError_t wait_for_stamp(nfc_ctx *c) {
     return hipStreamSynchronize(c->st);
 }
 
+// What thr_prepare decides about one attempt, as a value: the context keeps what was configured, a batch in work and a batch submitted
+// ahead each hold their own plan, and a launch is told which plan it belongs to (launch_threshold).
+enum class ThrForm { General, GeneralGlobalRing, Lean, Workgroup };   // pass 0's kernel: k_threshold with the LDS ring / the ring in global
+                                                                      // memory, k_threshold_lean, k_threshold_wg (a chunk per workgroup)
 struct ThrPlan {
+    ThrForm form;
+    int chunk;       // samples per chunk of the equal cut (ThrArgs.C, nfc_stats.chunk_samples)
+    bool by_row;     // the chunks' lengths differ by dispatch row (chunk_cut.h)
+    bool bulk;       // k_threshold_wg may keep a whole chunk's plane words in LDS: nothing else wants the CU's LDS (one batch at a time, NFC_WG_BULK)
+    bool in_place;   // failing chunks may be re-run by k_threshold_wg<KIND, 4, true>, which evaluates a failed round in place
     uint32_t nch;
-    bool lean_applies;
     uint8_t *d_cert, *d_gflags, *d_gmin, *d_gmax;
     const uint8_t *h_cert, *h_gflags, *h_gmin, *h_gmax;
     // pinned staging behind the flag sections (one block, c->h_cflags): the chunks' sum bounds as the device left them, and what the
@@ -99,6 +107,62 @@ struct ThrPlan {
     uint32_t *h_gvtop, *h_list_a, *h_list_b;
     uint8_t *h_ver;
 };
+// What a threshold launch is for.  Together with the plan it names the kernel: pass 0 runs the plan's form; a lone failing chunk of a
+// workgroup batch is re-run by pass 0's own kernel with pass 0's staging; the in-place form has its own kernel and LDS; k_threshold
+// (with the ring where the plan put it) re-runs whatever is left and never gives up.
+enum class ThrLaunch { Pass0, RerunLone, RerunInPlace, RerunGeneral };
+// Timed launches (nfc_set_timing >= 1) hand the kernel its own start / stop events (hipExtLaunchKernelGGL): the
+// events take the kernel's begin and end, not the position of a marker in the stream, so they neither measure nor add
+// inter-launch gaps.  own_events: a batch submitted ahead brings its pair.
+static void launch_threshold(nfc_ctx *c, const ThrPlan &P, ThrLaunch what, const ThrArgs &A, uint32_t nwork, const Event *own_events = nullptr) {
+    const bool timed = !own_events && c->timing >= 1 && c->n_kev < 6;
+    hipEvent_t e0 = timed ? (hipEvent_t)c->kev[2 * c->n_kev] : nullptr, e1 = timed ? (hipEvent_t)c->kev[2 * c->n_kev + 1] : nullptr;
+    if (timed) c->n_kev++;
+    if (own_events) {
+        e0 = own_events[0];
+        e1 = own_events[1];
+    }
+    const ThrForm form = what == ThrLaunch::RerunGeneral ? (P.form == ThrForm::GeneralGlobalRing ? P.form : ThrForm::General) : P.form;
+    ThrKernel kern;
+    uint32_t blocks, threads;
+    size_t lds;
+    ThrArgs B;   // (the workgroup kernels' block: how many rounds of plane words their staging holds travels in it)
+    const ThrArgs *args = &A;
+    if (what == ThrLaunch::RerunInPlace || form == ThrForm::Workgroup) {
+        B = A;
+        args = &B;
+        blocks = nwork;   // a chunk per workgroup
+        threads = 256;
+        if (what == ThrLaunch::RerunInPlace) {   // (four rows per step whatever pass 0 ran with, always the staging ring)
+            kern = c->kk->wg_ex;
+            B.wg_stage_rounds = 2 * wg_flush_rounds(4);
+            lds = c->wg_ex_lds;
+        } else {
+            // eight rows per step where nfc_create chose them (a kind without that slot runs four)
+            kern = c->kk->wg[c->wg_nr == 8 && c->kk->wg[1] ? 1 : 0];
+            // the staging of the plane words (threshold_wg.hip.h): the whole of the cut's longest chunk where the plan allows it and
+            // the LDS has room, else the ring
+            const int rounds = A.C_max / wg_round_samples(c->wg_nr) + 2;
+            const size_t need = c->wg_lds_base + wg_stage_bytes(c->wg_nr, rounds);
+            const bool whole = P.bulk && c->wg_lds_bulk_max && need <= c->wg_lds_bulk_max;
+            B.wg_stage_rounds = whole ? rounds : 2 * wg_flush_rounds(c->wg_nr);
+            lds = whole ? need : c->wg_lds;
+        }
+    } else {   // a chunk per wave
+        const bool gring = form == ThrForm::GeneralGlobalRing;
+        const uint32_t wpb = gring ? 4u : (uint32_t)c->wpb;
+        kern = form == ThrForm::Lean ? c->kk->lean[(1 << c->nfold) == 16 ? 1 : 0] : c->kk->thr[gring ? 1 : 0];
+        blocks = (nwork + wpb - 1) / wpb;
+        threads = 64 * wpb;
+        lds = gring ? 0 : (size_t)wpb * c->Lpad * c->lds_per_slot;
+    }
+    // (NFC_DEBUG_BAD_LAUNCH: a dynamic-LDS request the runtime must reject -- the test of the launch checks)
+    if (c->dbg_bad_launch) lds += (size_t)1 << 20;
+    if (e0) NFC_LAUNCH_EXT(kern, dim3(blocks), dim3(threads), lds, c->st, e0, e1, 0, *args);
+    else NFC_LAUNCH(kern, dim3(blocks), dim3(threads), lds, c->st, *args);
+}
+
+// low_on_device: a batch submitted ahead -- the LOW bookkeeping is read on the device, and the other stages' workgroups run beside its kernel.
 static int thr_prepare(nfc_ctx *c, const void *d_in, uint32_t n, uint32_t n_all, uint32_t skip, uint32_t base, uint64_t nseen,
                        const EdgeCarry &ec, int ring_in, DevBuf &planes_neg, DevBuf &planes_pos, bool low_on_device, ThrArgs &A, ThrPlan &P) {
     const int L = c->L;
@@ -112,28 +176,28 @@ static int thr_prepare(nfc_ctx *c, const void *d_in, uint32_t n, uint32_t n_all,
     // line adds a read and a write per sample; a lone wave is bound by its own instruction stream, which the lean kernel
     // shortened).  So the global ring is only taken on request (NFC_RING=global) or where the lean kernel does not apply.
     const bool lean_applies = c->lean && c->mx <= 500;   // (every input kind: a raw envelope that turns out negative makes its chunk give up)
-    c->gring = c->gring_ok && (c->gring_force || (!lean_applies && (uint64_t)n >= (uint64_t)c->wave_slots_g * 8u * (uint64_t)c->L));
+    const bool gring = c->gring_ok && (c->gring_force || (!lean_applies && (uint64_t)n >= (uint64_t)c->wave_slots_g * 8u * (uint64_t)c->L));
     // ... with a chunk per WORKGROUP where that kernel applies (threshold_wg.hip.h: max_len within one step, a ring that holds a round)
-    c->wg_now = lean_applies && c->wg && c->wg_ok && !c->gring;
+    bool wg = lean_applies && c->wg && c->wg_ok && !gring;
+    int C = c->C_min;
     if (!c->P.chunk_samples) {
-        uint64_t slots = (uint64_t)(c->gring ? c->wave_slots_g : (c->wg_now ? (low_on_device ? c->wg_slots_ahead : c->wg_slots) : (lean_applies ? c->lean_slots : c->wave_slots)));
+        uint64_t slots = (uint64_t)(gring ? c->wave_slots_g : (wg ? (low_on_device ? c->wg_slots_ahead : c->wg_slots) : (lean_applies ? c->lean_slots : c->wave_slots)));
         // A stream whose last batches needed re-runs (a level that steps, load modulation at the threshold) is cut finer: a re-run
         // pass is ONE wave walking a chunk, so it costs what a chunk is long -- measured on the stress captures, 1e8 samples:
         // 4 x as many chunks take 2.14 -> 1.34 ms (level steps) and 7.3 -> 4.0 ms (hovering), 8 x is worse again (the rounds' fixed
         // costs); a clean stream pays 0.353 -> 0.406 ms for it, so the cut goes back after eight batches without a re-run.
-        if (c->fine_left > 0 && c->wg_now) slots *= (uint64_t)c->fine_mult;
+        if (c->fine_left > 0 && wg) slots *= (uint64_t)c->fine_mult;
         // (every chunk owns three windows of summaries -- ring_in, ring_out[2] -- in device memory: however fine the cut, they stay
         // within 1 GiB, 4 x 1024 chunks of a 10 000-sample window take 0.5 GB)
         slots = std::min<uint64_t>(slots, std::max<uint64_t>(256, ((uint64_t)1 << 30) / ((uint64_t)12 * (uint64_t)c->L)));
-        // (the lean kernel walks whole supersteps of lean_k steps: a chunk that is not a multiple of them ends on slow single steps;
+        // (the lean kernel walks its supersteps four steps at a time: a chunk that is not a multiple of them ends on slow single steps;
         // the workgroup kernel whole rounds of four)
-        const int stp = c->wg_now ? wg_round_samples(c->wg_nr) : 64 * c->rows_per_step * ((c->lean && !c->gring) ? c->lean_k : 1);
+        const int stp = wg ? wg_round_samples(c->wg_nr) : STEP * ((c->lean && !gring) ? LEAN_STEPS_AHEAD : 1);
         uint64_t want = ((uint64_t)n + slots - 1) / slots;
         want = (want + stp - 1) / stp * stp;
-        c->C = (int)std::max<uint64_t>(want, (uint64_t)c->C_min);
+        C = (int)std::max<uint64_t>(want, (uint64_t)c->C_min);
     }
-    if (c->wg_now && c->C % wg_round_samples(c->wg_nr) != 0) c->wg_now = 0;   // (a configured chunk length that is not whole rounds: the one-wave kernel)
-    const uint32_t off = 0u;   // (chunk c covers samples [c*C - off, (c+1)*C - off): the kernels here use off = 0)
+    if (wg && C % wg_round_samples(c->wg_nr) != 0) wg = false;   // (a configured chunk length that is not whole rounds: the one-wave kernel)
     // The cut by dispatch row (threshold.hip.h: chunk_span).  The k-th workgroup the dispatcher hands a CU starts behind the k-1
     // before it and shares the CU with them for its whole life: measured with the cycle counter (round 5), the lives of the rows of
     // 256 workgroups are 0.965 / 0.985 / 1.010 / 1.042 of their mean with four per CU (1e8 samples, 1018 chunks of 98 304) and
@@ -142,25 +206,24 @@ static int thr_prepare(nfc_ctx *c, const void *d_in, uint32_t n, uint32_t n_all,
     // whatever covers the batch -- when the batch is one full wave of resident workgroups and the chunk length is this file's own
     // choice.  NFC_WG_ROWBAL=0: the equal cut.
     const uint32_t cus = (uint32_t)std::max(1, c->n_cus);
-    RowCut cut = equal_cut(n, (uint32_t)c->C, cus);
+    RowCut cut = equal_cut(n, (uint32_t)C, cus);
     const uint32_t slots_now = (uint32_t)(low_on_device ? c->wg_slots_ahead : c->wg_slots);   // (as the chunk length was chosen above)
     const uint32_t R = slots_now / cus;   // rows of a full wave: workgroups per CU
     // (the factors were measured on a 256-CU MI355X -- same-call A/Bs on three boxes, DESIGN.md 5.1c: on any other device the cut is equal)
-    if (c->wg_rowbal && (c->n_cus == 256 || c->rowbal_set) && c->wg_now && !c->P.chunk_samples && !low_on_device && c->fine_left == 0 && slots_now == R * cus &&
+    if (c->wg_rowbal && (c->n_cus == 256 || c->rowbal_set) && wg && !c->P.chunk_samples && !low_on_device && c->fine_left == 0 && slots_now == R * cus &&
         R >= 2 && R <= 4) {
         const uint32_t rs = (uint32_t)wg_round_samples(c->wg_nr);
-        // (where the equal cut's chunks keep their planes in the LDS beside the ring, the longest chunk's must still fit: launch_wg)
+        // (where the equal cut's chunks keep their planes in the LDS beside the ring, the longest chunk's must still fit: launch_threshold)
         uint32_t max_len = 0;
-        if (c->wg_lds_bulk_max && c->wg_lds_base + wg_stage_bytes(c->wg_nr, c->C / (int)rs + 2) <= c->wg_lds_bulk_max) {
+        if (c->wg_lds_bulk_max && c->wg_lds_base + wg_stage_bytes(c->wg_nr, C / (int)rs + 2) <= c->wg_lds_bulk_max) {
             const size_t rounds = (c->wg_lds_bulk_max - c->wg_lds_base) / wg_stage_bytes(c->wg_nr, 1);
             max_len = rounds > 2 ? (uint32_t)(rounds - 2) * rs : rs;
         }
-        cut = plan_row_cut(n, (uint32_t)c->C, rs, cus, R, c->rowbal_set ? c->rowbal_f[0] : c->rowbal_f[R], max_len);
+        cut = plan_row_cut(n, (uint32_t)C, rs, cus, R, c->rowbal_set ? c->rowbal_f[0] : c->rowbal_f[R], max_len);
     }
-    c->rowbal_now = cut.by_row;
     const uint32_t nch = cut.nch;
     c->stats.n_chunks = nch;
-    c->stats.chunk_samples = (uint32_t)c->C;
+    c->stats.chunk_samples = (uint32_t)C;
     const size_t nwords = ((size_t)n_all + 63) / 64 + 8;
     HIPCHK(c, planes_neg.ensure(nwords * 8));
     HIPCHK(c, planes_pos.ensure(nwords * 8));
@@ -168,7 +231,7 @@ static int thr_prepare(nfc_ctx *c, const void *d_in, uint32_t n, uint32_t n_all,
     // re-runs is cut fine_mult times finer, host_threshold.h: fine_left -- from within the batch that finds out: an allocation in
     // the middle of a batch costs milliseconds).  Three windows of summaries per chunk: bounded by the cap on the chunk count.
     size_t nal = nch;
-    if (c->fine_adapt && c->wg_now && !c->P.chunk_samples && c->fine_left == 0)
+    if (c->fine_adapt && wg && !c->P.chunk_samples && c->fine_left == 0)
         nal = std::min<size_t>((size_t)nch * (size_t)c->fine_mult, std::max<size_t>(nch, ((size_t)1 << 30) / ((size_t)12 * (size_t)L)));
     for (int b = 0; b < 2; b++) {
         HIPCHK(c, c->d_ringout[b].ensure(nal * L * sizeof(float)));
@@ -196,7 +259,7 @@ static int thr_prepare(nfc_ctx *c, const void *d_in, uint32_t n, uint32_t n_all,
     }
     HIPCHK(c, c->d_list.ensure((size_t)nal * 8));   // two lists: the chunks a round re-runs, the chunks it certifies
     HIPCHK(c, c->d_gvtop.ensure((size_t)nal * 4));
-    if (c->gring) HIPCHK(c, c->d_gring.ensure((size_t)nch * c->Lpad * c->lds_per_slot));
+    if (gring) HIPCHK(c, c->d_gring.ensure((size_t)nch * c->Lpad * c->lds_per_slot));
     c->h_ver.assign(nch, 0);
 
     // carried "HIGH ignored" bookkeeping from (_current_state, _last_bit, _dur) at the first stable sample
@@ -222,7 +285,7 @@ static int thr_prepare(nfc_ctx *c, const void *d_in, uint32_t n, uint32_t n_all,
     A.L = L;
     A.Lpad = c->Lpad;
     A.mx = c->mx;
-    A.C = c->C;
+    A.C = C;
     for (int r = 0; r < 4; r++) {
         A.row_len[r] = cut.row_len[r];
         A.row_start[r] = cut.row_start[r];
@@ -267,10 +330,16 @@ static int thr_prepare(nfc_ctx *c, const void *d_in, uint32_t n, uint32_t n_all,
     A.neg = planes_neg.as<uint64_t>() + base / 64;
     A.pos = planes_pos.as<uint64_t>() + base / 64;
     A.twords = c->twords;
-    A.off = (int32_t)off;
+    A.off = 0;   // (chunk c covers samples [c*C - off, (c+1)*C - off): the kernels here use off = 0)
     A.nrows = (L + 63) / 64;
+    // the lean kernel or the workgroup kernel wherever they apply: the LDS ring, and more than one chunk (chunk 0's verdict travels with
+    // the certification).  max_len beyond 500 samples: not exercised, left to k_threshold
+    P.form = gring ? ThrForm::GeneralGlobalRing : (!lean_applies || nch < 2) ? ThrForm::General : wg ? ThrForm::Workgroup : ThrForm::Lean;
+    P.chunk = C;
+    P.by_row = cut.by_row;
+    P.bulk = !low_on_device && c->wg_bulk;
+    P.in_place = P.form == ThrForm::Workgroup && c->wg_ex_ok;
     P.nch = nch;
-    P.lean_applies = lean_applies;
     P.d_cert = d_cert;
     P.d_gflags = d_gflags;
     P.d_gmin = d_gmin;
@@ -280,6 +349,26 @@ static int thr_prepare(nfc_ctx *c, const void *d_in, uint32_t n, uint32_t n_all,
     P.h_gmin = h_gmin;
     P.h_gmax = h_gmax;
     return NFC_OK;
+}
+
+// Pass 0: every chunk from a speculated incoming state (chunk 0: the carried, exact one).  The synchronous path and a batch submitted
+// ahead enqueue it alike, and the first certification behind it (the synchronous path may hand that one to the edge writer's launch instead).
+static void enqueue_pass0(nfc_ctx *c, const ThrPlan &P, ThrArgs &A, const Event *own_events = nullptr) {
+    A.list = nullptr;
+    A.nlist = 0;
+    A.mode = 0;
+    A.cert = P.d_cert;
+    A.sum = (CertSummary *)(dT(c) + TOT_CERT);
+    A.ksteps = P.form == ThrForm::Workgroup ? c->wg_rounds : c->lean_rounds;
+    A.gfac = c->lean_gfac;
+    A.gfloor = c->lean_gmin;
+    A.blk = 1 << c->nfold;
+    launch_threshold(c, P, ThrLaunch::Pass0, A, P.nch, own_events);
+}
+// Certification of the A.nlist chunks of A.list (null: chunks 1 .. nlist) against their predecessors' summaries.  sum: the first round's,
+// which also resolves the end-of-batch state (last workgroup) into ring_out and leaves its verdict as a summary in the state block.
+static void enqueue_certify(nfc_ctx *c, const ThrPlan &P, const ThrArgs &A, CertInfo *info, float *ring_out, CertSummary *sum) {
+    NFC_LAUNCH(k_certify, dim3(cert_grid(A.nlist)), dim3(256), 0, c->st, A, P.d_cert, info, ring_out, dC(c), sum);
 }
 
 // *recut_out (optional): pass 0's verdict says the stream is in the regime that needs re-runs and the batch is still on the coarse
@@ -298,7 +387,7 @@ static int threshold_span(nfc_ctx *c, const void *d_in_all, uint32_t n_all, uint
     ThrPlan P;
     if (int rc = thr_prepare(c, d_in, n, n_all, skip, base, nseen, ec, c->ring_cur, c->d_neg, c->d_pos, false, A, P)) return rc;
     const uint32_t nch = P.nch;
-    const bool lean_applies = P.lean_applies;
+    const bool wg = P.form == ThrForm::Workgroup;
     uint8_t *d_cert = P.d_cert;
     const uint8_t *h_cert = P.h_cert, *h_gflags = P.h_gflags, *h_gmin = P.h_gmin, *h_gmax = P.h_gmax;
 
@@ -309,25 +398,13 @@ static int threshold_span(nfc_ctx *c, const void *d_in_all, uint32_t n_all, uint
     const bool force_seq = (c->P.flags & NFC_FLAG_FORCE_SEQUENTIAL) != 0 || L < STEP;
     bool need_seq = force_seq;
     if (!force_seq) {
-        // pass 0: every chunk from a speculated incoming state (chunk 0: the carried, exact one)
-        A.list = nullptr;
-        A.nlist = 0;
-        A.mode = 0;
-        // the lean kernel wherever it applies (LDS ring, more than one chunk: chunk 0's verdict travels with the certification)
-        const bool lean = lean_applies && !c->gring && nch > 1;   // (max_len beyond 500 samples: not exercised, left to k_threshold)
-        A.cert = d_cert;
-        A.sum = (CertSummary *)(dT(c) + TOT_CERT);
-        A.ksteps = c->wg_now ? c->wg_rounds : c->lean_rounds;
-        A.gfac = c->lean_gfac;
-        A.gfloor = c->lean_gmin;
-        A.blk = 1 << c->nfold;
+        const bool lean = wg || P.form == ThrForm::Lean;   // (pass 0 by a kernel that may give up on a chunk, chunk 0 included)
         const bool dbg_clk = lean && c->dbg_clk;
         if (dbg_clk) {
             HIPCHK(c, c->d_certinfo.ensure((size_t)nch * 32 * 5));   // (+ 4 waves x 4 counters per chunk in a profiling build)
             A.dbg_clk = c->d_certinfo.as<unsigned long long>();
         }
-        c->wg_bulk_now = c->wg_bulk;   // (one batch at a time: nothing else wants the CU's LDS)
-        launch_threshold_kind(c, A, nch, lean);
+        enqueue_pass0(c, P, A);
         if (dbg_clk) {
             std::vector<unsigned long long> h((size_t)nch * 4);
             HIPCHK(c, hipStreamSynchronize(c->st));
@@ -346,7 +423,7 @@ static int threshold_span(nfc_ctx *c, const void *d_in_all, uint32_t n_all, uint
                 maxstart = std::max(maxstart, (double)(h[4 * k] - t0));
             }
 #ifdef NFC_WG_PROF
-            if (c->wg_now) {
+            if (wg) {
                 std::vector<unsigned long long> pf((size_t)nch * 16);
                 HIPCHK(c, hipMemcpy(pf.data(), (char *)c->d_certinfo.p + (size_t)nch * 32, (size_t)nch * 128, hipMemcpyDeviceToHost));
                 double tk = 0, b1 = 0, b2 = 0, rr = 0;
@@ -405,9 +482,8 @@ static int threshold_span(nfc_ctx *c, const void *d_in_all, uint32_t n_all, uint
             // summary in the mirrored state block; later rounds (after re-runs) read the per-chunk flags
             CertSummary *d_sum = (CertSummary *)(tot + TOT_CERT);
             auto launch_certify = [&]() {
-                NFC_LAUNCH(k_certify, dim3(cert_grid(np)), dim3(256), 0, c->st, A, d_cert,
-                                   dbg ? c->d_certinfo.as<CertInfo>() : nullptr, c->d_ring[(c->ring_cur + 1) % NRING].as<float>(), dC(c),
-                                   first_round ? d_sum : (CertSummary *)nullptr);
+                enqueue_certify(c, P, A, dbg ? c->d_certinfo.as<CertInfo>() : nullptr, c->d_ring[(c->ring_cur + 1) % NRING].as<float>(),
+                                first_round ? d_sum : (CertSummary *)nullptr);
             };
             bool stamped_last = false;   // the round's last launch is the one that stamps the mirror (k_pkt_finish behind the writer)
             bool flags_with_verdict = false;
@@ -454,7 +530,7 @@ static int threshold_span(nfc_ctx *c, const void *d_in_all, uint32_t n_all, uint
                 // More than one chunk in 64 failed and the batch was cut for a clean stream: re-running those long chunks one wave
                 // each is the expensive way round (a re-run pass costs what a chunk is long) -- pass 0 again on the fine cut costs
                 // 0.2 ms and leaves short chunks to re-run.  (The next batches are cut fine from the start: fine_left.)
-                if (recut_out && c->fine_adapt && c->wg_now && c->fine_left == 0 && !c->P.chunk_samples && c->fine_mult > 1 &&
+                if (recut_out && c->fine_adapt && wg && c->fine_left == 0 && !c->P.chunk_samples && c->fine_mult > 1 &&
                     (uint64_t)summary.n_fail * 64u > (uint64_t)nch) {
                     *recut_out = true;
                     A.ver_zero = 0;
@@ -537,14 +613,14 @@ static int threshold_span(nfc_ctx *c, const void *d_in_all, uint32_t n_all, uint
                     if (tried_wg[k] == 1) ran++, gave += (h_gflags[k] & 4) ? 1 : 0;
                 if (gave * 4 > ran) ex_off = true;
             }
-            const bool ex = c->wg_now && c->wg_ex_ok && !ex_off && failing.size() <= (size_t)c->wg_ex_max;
+            const bool ex = P.in_place && !ex_off && failing.size() <= (size_t)c->wg_ex_max;
             std::vector<uint32_t> by_wg, by_general;
             for (uint32_t k : failing) {
                 // (a chunk the in-place form has re-run and that did NOT give up may take it again -- what failed is its incoming state;
                 // one it gave up on is k_threshold's for the rest of the batch: that kernel never gives up, so the rounds converge)
                 if (tried_wg[k] == 1 && (h_gflags[k] & 4)) tried_wg[k] = 2;
                 const bool ex_again = ex && tried_wg[k] == 1;
-                if (c->wg_now && (!tried_wg[k] || ex_again) && (ex || lone)) {
+                if (wg && (!tried_wg[k] || ex_again) && (ex || lone)) {
                     by_wg.push_back(k);
                     tried_wg[k] = 1;
                 } else {
@@ -570,15 +646,13 @@ static int threshold_span(nfc_ctx *c, const void *d_in_all, uint32_t n_all, uint
                 A.list = c->d_list.as<uint32_t>();
                 A.nlist = (uint32_t)by_wg.size();
                 A.ksteps = 2;
-                c->wg_ex_launch = ex;
-                launch_threshold_kind(c, A, A.nlist, true);
-                c->wg_ex_launch = false;
+                launch_threshold(c, P, ex ? ThrLaunch::RerunInPlace : ThrLaunch::RerunLone, A, A.nlist);
                 A.ksteps = c->wg_rounds;
             }
             if (!by_general.empty()) {
                 A.list = c->d_list.as<uint32_t>() + by_wg.size();
                 A.nlist = (uint32_t)by_general.size();
-                launch_threshold_kind(c, A, A.nlist);
+                launch_threshold(c, P, ThrLaunch::RerunGeneral, A, A.nlist);
             }
             A.nlist = (uint32_t)failing.size();
             c->stats.threshold_passes++;

@@ -2,7 +2,8 @@
 // the kind's instantiations: nfc_amd.hip for the four original kinds, nfc_iq16.hip for the complex int16 kind, nfc_iq8.hip for the
 // complex 8-bit kinds -- so each unit's device code is what it is without the others' (tests/test_isa_audit.py pins nfc_amd.hip's).
 // The host side launches through a context's table (host_context.h) and asks the runtime about its entries (nfc_create: LDS attribute,
-// occupancy); whether a kind has an optional form is whether its slot is filled, and is decided here alone.
+// occupancy); which entry a launch takes is launch_threshold's choice (host_threshold.h), from the batch's plan and what the launch is for.
+// The one optional form is eight rows per step: whether a kind has it is whether wg[1] is filled, and is decided here alone.
 // Included after threshold.hip.h, threshold_lean.hip.h and threshold_wg.hip.h.
 #pragma once
 #include "input_kind.h"
@@ -19,20 +20,14 @@ struct KindKernels {
     ThrKernel lean[2];       // [blk16]   k_threshold_lean<KIND, 4, blk16>
     ThrKernel wg[2];         // [nr == 8] k_threshold_wg<KIND, nr>: pass 0, four or eight rows per step; [1] null where eight rows are not instantiated
     ThrKernel wg_ex;         //           k_threshold_wg<KIND, 4, true>: re-runs with failed rounds evaluated in place
-    ThrKernel wg_flags[2];   // [nr == 8] k_threshold_wg<KIND, nr, false, true>: test build only; null where not instantiated (every slot in the product build)
     FillKernel fill;         // k_fill<KIND>
     SeqKernel seq;           // k_threshold_seq<KIND>
 };
 
 // Eight rows per step: fc32, sc16, sc8 and cu8 IQ and the float32 envelope -- what a capture at a rate that wants a window of thousands
-// of samples arrives as.  The per-wave-counter form of the test build (NFC_WG_FLAGS): the four original kinds; the switch is ignored
-// for the complex integer kinds.
+// of samples arrives as.
 template <int KIND>
 constexpr bool has_nr8 = KIND == IN_IQ_F32 || KIND == IN_ENV_F32 || KIND == IN_IQ_I16 || is_iq8(KIND);
-#ifdef NFC_TEST_HOOKS
-template <int KIND>
-constexpr bool has_wg_flags = KIND != IN_IQ_I16 && !is_iq8(KIND);
-#endif
 
 template <int KIND>
 KindKernels make_kind_kernels() {
@@ -44,12 +39,6 @@ KindKernels make_kind_kernels() {
     k.wg[0] = k_threshold_wg<KIND, 4>;
     if constexpr (has_nr8<KIND>) k.wg[1] = k_threshold_wg<KIND, 8>;
     k.wg_ex = k_threshold_wg<KIND, 4, true>;
-#ifdef NFC_TEST_HOOKS
-    if constexpr (has_wg_flags<KIND>) {
-        k.wg_flags[0] = k_threshold_wg<KIND, 4, false, true>;
-        if constexpr (has_nr8<KIND>) k.wg_flags[1] = k_threshold_wg<KIND, 8, false, true>;
-    }
-#endif
     k.fill = k_fill<KIND>;
     k.seq = k_threshold_seq<KIND>;
     return k;

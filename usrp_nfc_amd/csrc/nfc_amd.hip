@@ -115,7 +115,6 @@ int create_plan_params(nfc_ctx *c, const nfc_params *p, const Switches &sw, floa
     int C = p->chunk_samples > 0 ? p->chunk_samples : 4096;   // smallest chunk of the adaptive rule (run_threshold)
     C = std::max(C, 2 * c->L);
     C = std::max(C, c->mx + 2);
-    c->rows_per_step = 4;
     c->use_small = sw.no_small ? 0 : 1;   // (the first seven: set by being there, whatever the value)
     c->dbg_bad_launch = sw.debug_bad_launch.has_value();
     c->dbg_redo_submitted = sw.debug_redo_submitted.has_value();
@@ -133,7 +132,6 @@ int create_plan_params(nfc_ctx *c, const nfc_params *p, const Switches &sw, floa
     if (sw.wg_rerun) c->wg_rerun_lone = *sw.wg_rerun != 0;
     if (sw.wg_lone) c->wg_lone_max = std::max(0, sw.wg_lone->first), c->wg_lone_div = std::max(1, sw.wg_lone->second);
     if (sw.lean) c->lean = *sw.lean != 0;
-    c->lean_k = 0;        // chosen in create_plan_device from the occupancy the LDS ring allows
     c->lean_rounds = 0;
     if (sw.lean_rounds) c->lean_rounds = std::max(1, *sw.lean_rounds);
     if (sw.lean_gfac) c->lean_gfac = (float)*sw.lean_gfac;
@@ -145,12 +143,7 @@ int create_plan_params(nfc_ctx *c, const nfc_params *p, const Switches &sw, floa
     if (sw.rowbal_f) memcpy(c->rowbal_f[0], sw.rowbal_f->data(), sizeof c->rowbal_f[0]), c->rowbal_set = true;
     if (sw.wg_rowbal) c->wg_rowbal = *sw.wg_rowbal != 0;
     if (sw.dec_runin) c->dec_runin = *sw.dec_runin >= 2048 ? 8 : (*sw.dec_runin >= 1024 ? 4 : 2);
-    {
-        c->rows_per_step = 4;   // (8-row steps measured slower: 126 VGPRs, four waves per SIMD)
-        const int stp = 64 * c->rows_per_step;
-        C = (C + stp - 1) / stp * stp;
-    }
-    c->C = C;
+    C = (C + STEP - 1) / STEP * STEP;
     c->C_min = C;
     c->lds_per_slot = (p->input_kind == NFC_IN_ENV_F32) ? 5 : 4;   // ring (+ touched byte map for raw envelopes)
     c->wpb = std::max(1, std::min(4, (int)(65536 / ((size_t)c->Lpad * c->lds_per_slot))));
@@ -209,10 +202,9 @@ int create_plan_device(nfc_ctx *c, const Switches &sw) {
     // Measured (configs[1] / [2], 1e8 samples): two waves per SIMD with four steps ahead beat five waves with three --
     // 0.206 / 0.196 ms against 0.237 / 0.230 on the same box: a chunk's fixed cost (the window before it read and
     // summarised, its summary written) is paid half as often, and two waves already keep a SIMD's issue slots busy.
-    if (!c->lean_k) c->lean_k = 4;
     c->lean_slots = std::min(c->wave_slots, prop.multiProcessorCount * 8);
     if (sw.lean_waves) c->lean_slots = std::min(c->wave_slots, prop.multiProcessorCount * 4 * std::max(1, *sw.lean_waves));
-    if (!c->lean_rounds) c->lean_rounds = std::max(1, (int)(0.4 * c->L / (256.0 * c->lean_k)));
+    if (!c->lean_rounds) c->lean_rounds = std::max(1, (int)(0.4 * c->L / (256.0 * LEAN_STEPS_AHEAD)));
     c->wave_slots_g = prop.multiProcessorCount * 20;   // VGPR-bound: five waves per SIMD
     // LDS the lean kernel's resident waves hold per CU: a batch is only run ahead of its predecessor's edge / decode stages
     // (nfc_submit_device) while those stages' workgroups (25 KB each) still fit beside it
@@ -230,13 +222,11 @@ int create_plan_device(nfc_ctx *c, const Switches &sw) {
         const int v = *sw.wg_nr;
         if ((v == 4 || (v == 8 && nr8_kind)) && c->L >= wg_round_samples(v)) c->wg_nr = v;
     }
-    // (+ the staging of the plane words: a ring of 2 FR rounds; a whole chunk's where the LDS has room, launch_wg)
+    // (+ the staging of the plane words: a ring of 2 FR rounds; a whole chunk's where the LDS has room, launch_threshold)
     c->wg_lds = c->wg_lds_base + wg_stage_bytes(c->wg_nr, 2 * wg_flush_rounds(c->wg_nr));
     c->wg_ok = c->mx <= 64 * c->wg_nr - 2 && c->L >= wg_round_samples(c->wg_nr) && c->wg_lds <= 160 * 1024;
     if (!c->wg_ok) return NFC_OK;
     const void *kern = (const void *)c->kk->wg[c->wg_nr == 8 ? 1 : 0];
-    if (sw.wg_flags) c->wg_flags = *sw.wg_flags != 0 && c->kk->wg_flags[0] != nullptr;   // (ignored for a kind without that form: the complex integer kinds)
-    if (c->wg_flags) kern = (const void *)c->kk->wg_flags[c->wg_nr == 8 && c->kk->wg_flags[1] ? 1 : 0];
     if (!kern) return fail(nullptr, NFC_ERR_INTERNAL, "no workgroup kernel for input kind %d", c->P.input_kind);
     if (c->wg_lds > 64 * 1024) CRT(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->wg_lds));
     int per_cu_wg = 0;
@@ -247,7 +237,7 @@ int create_plan_device(nfc_ctx *c, const Switches &sw) {
     if (sw.wg_per_cu) per_cu_wg = std::max(1, std::min(per_cu_max, *sw.wg_per_cu));
     c->wg_slots = prop.multiProcessorCount * per_cu_wg;
     // the most dynamic LDS a workgroup may ask for with per_cu_wg of them still resident per CU: what a chunk's planes may
-    // take when they are kept until the chunk is done (one batch at a time only: launch_wg)
+    // take when they are kept until the chunk is done (one batch at a time only: ThrPlan.bulk)
     c->wg_lds_bulk_max = 0;
     if (c->wg_bulk) {
         size_t cand = ((size_t)160 * 1024 / (size_t)per_cu_wg) & ~(size_t)1023;

@@ -142,7 +142,7 @@ struct ThrArgs {
     float gfac, gfloor;    // drift allowance = max(gfac * (largest B needed so far), gfloor * ss)
     int32_t blk;           // a LOW run longer than max_len covers an aligned block of blk samples (a power of two)
     int32_t ver_zero;              // every version byte is 0 (the certification right behind pass 0): its launches need not load them
-    int32_t wg_stage_rounds;       // k_threshold_wg: rounds of plane words its LDS staging holds per plane (threshold_wg.hip.h; launch_wg sets it)
+    int32_t wg_stage_rounds;       // k_threshold_wg: rounds of plane words its LDS staging holds per plane (threshold_wg.hip.h; launch_threshold sets it)
     unsigned long long *dbg_clk;   // debugging aid (NFC_DEBUG_CLK): per chunk four s_memtime stamps -- start, incoming state ready, loop done, end
     // Chunks of UNEQUAL length by dispatch row (round 5; chunk_span below).  The k-th workgroup a CU is given is the k-th slowest
     // (measured: the lives of k_threshold_wg's workgroups fall in four steps by block index -- 0.965, 0.985, 1.010, 1.042 of the mean
@@ -150,7 +150,7 @@ struct ThrArgs {
     // long, row r begins at sample row_start[r] and holds row_div chunks; rows past the third go on like the third.  With every
     // row_len = C and row_start[r] = r * row_div * C this is the equal cut, c * C.
     uint32_t row_len[4], row_start[4], row_div;
-    int C_max;   // the longest row's chunk length (the sizing of a workgroup's plane staging: launch_wg)
+    int C_max;   // the longest row's chunk length (the sizing of a workgroup's plane staging: launch_threshold)
 };
 // chunk c covers the batch's samples [m_chunk, m_chunk + len)
 __device__ __forceinline__ void chunk_span(const ThrArgs &A, uint32_t c, uint32_t &m_chunk, uint32_t &len) {

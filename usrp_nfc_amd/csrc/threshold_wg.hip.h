@@ -53,9 +53,6 @@ constexpr int WG_NR_MAX = 8;
 #ifndef NFC_WG_FR
 #define NFC_WG_FR 8
 #endif
-#ifndef NFC_WG_FLAGS_SLEEP
-#define NFC_WG_FLAGS_SLEEP 0   // s_sleep between two looks at the counters (FLG; 0: none)
-#endif
 constexpr int wg_flush_rounds(int nr) { return nr == 4 ? NFC_WG_FR : NFC_WG_FR / 2; }   // 1 KB per plane and flush
 constexpr size_t wg_stage_bytes(int nr, int rounds) { return (size_t)rounds * (size_t)(2 * WG_WAVES * 2 * nr * 4); }   // both planes
 // LDS behind the ring: LOW masks of the rounds' steps, the close exchange, scratch for workgroup reductions
@@ -74,7 +71,6 @@ struct WgShared {
     // (f32 bits; lane 0 takes them into what it hands in when the superstep closes, and resets them).
     uint32_t cold[WG_WAVES][8];
     float bc[8];                       // ... and what wave 0 makes of them: the next thresholds, the sum, the allowance, the verdict
-    uint32_t pha[WG_WAVES];            // FLG: rounds whose phase A (LOW masks) each wave has published
 };
 constexpr size_t WG_SHARED_BYTES = (sizeof(WgShared) + 15) & ~(size_t)15;
 
@@ -242,14 +238,9 @@ __device__ __forceinline__ void wg_row_once(const ThrArgs &A, int lane, int m, f
 // round at once, see the block behind the close), leave the masks and plane words where the round's waves would have, and the chunk
 // goes on in the tracked form from the exact sum.  One-round supersteps; rounds of whole steps only (a ragged end, the stream's first
 // stable sample: the chunk gives up as before and k_threshold takes it).
-// FLG (round 6, VERDICT r5 item 3: built and measured): the first barrier of a round of whole steps is replaced by
-// per-wave counters -- a wave publishes its step's LOW masks, bumps its counter and goes on as soon as the waves BEFORE it in the round
-// have published this round and the waves BEHIND it the round before (so that every step whose ring slots its own may share -- four and
-// more steps back -- is complete, and the mask buffer it writes next is read by nobody).  The close of a superstep keeps its barrier.
-template <int KIND, int NR, bool EX = false, bool FLG = false>
+template <int KIND, int NR, bool EX = false>
 __global__ __launch_bounds__(256) void k_threshold_wg(ThrArgs A) {
     static_assert(!EX || NR == 4, "the samples of an exact round travel through sh->acc: sixteen rows");
-    static_assert(!(EX && FLG), "the form that re-runs keeps the barriers");
     constexpr uint32_t STEPN = 64u * NR;
     constexpr int WG_ROUND = wg_round_samples(NR);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -302,16 +293,6 @@ __global__ __launch_bounds__(256) void k_threshold_wg(ThrArgs A) {
     // (steps before the chunk's first one have published nothing: their masks read as "no LOW sample"; the barriers of the
     // prologue order this before the first round)
     for (int i = tid; i < (int)(sizeof(sh->msk) / 4); i += 256) ((uint32_t *)sh->msk)[i] = 0u;
-    if (tid < WG_WAVES) sh->pha[tid] = 0u;
-    // FLG: rounds done (every wave counts them alike) and, per lane, which wave's counter it looks at and how far that one must have got
-    // relative to this -- in VECTOR registers, laundered through asm: the kernel has no scalar register to spare (measured: with these
-    // in scalars the round loop gained 77 spill moves and the launch 18 %)
-    uint32_t rno = 0u;
-    uint32_t pha_addr = (uint32_t)(uintptr_t)(lean_lds_u32 *)&sh->pha[lane & 3];
-    uint32_t pha_bias = ((lane & 3) < wave) ? 1u : 0u;                 // the waves before this one in the round: this round; behind it: the round before
-    uint32_t pha_self = ((lane & 3) == wave) ? 0xFFFFFFFFu : 0u;       // (its own counter: anything)
-    uint32_t pha_mine = (uint32_t)(uintptr_t)(lean_lds_u32 *)&sh->pha[wave];
-    if constexpr (FLG) asm volatile("" : "+v"(rno), "+v"(pha_addr), "+v"(pha_bias), "+v"(pha_self), "+v"(pha_mine));
     if (lane == 0) {
         sh->cold[wave][0] = (uint32_t)LL_NONE;
         sh->cold[wave][1] = (uint32_t)LL_NONE;
@@ -838,8 +819,7 @@ __global__ __launch_bounds__(256) void k_threshold_wg(ThrArgs A) {
                 // the plane words of the round before leave, and the registers take the next round (if the chunk has one: past
                 // its end may be past the caller's buffer)
                 // (the plane words of the rounds before: staged in LDS, see flush_block)
-                // (FLG: a wave may be a round behind -- what it staged two rounds ago is complete)
-                if (!bulk && st_cnt > FR + (FLG ? 1 : 0)) {   // (uniform) the FR oldest staged rounds are complete in every wave: one wave sends them off
+                if (!bulk && st_cnt > FR) {   // (uniform) the FR oldest staged rounds are complete in every wave: one wave sends them off
                     if (wave == st_flusher) flush_block(st_a, st_base);
                     st_a = (st_a == FR) ? 0 : FR;
                     st_base += (uint32_t)(FR * WG_ROUND);
@@ -886,26 +866,7 @@ __global__ __launch_bounds__(256) void k_threshold_wg(ThrArgs A) {
             }
             if (lane <= 4 * NR) *(uint32_t *)((char *)&sh->msk[0][wave][0] + mo + 4u * (uint32_t)lane) = (uint32_t)pk;
             WG_PF_BEGIN();
-            if constexpr (FLG) {
-                // (LDS takes a wave's instructions in order: whoever sees the counter sees the masks)
-                asm volatile("" ::: "memory");
-                if (lane == 0) asm volatile("ds_write_b32 %0, %1" ::"v"(pha_mine), "v"(rno + 1u) : "memory");
-                if constexpr (REG) {
-                    for (;;) {
-                        uint32_t pv;
-                        asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(pv) : "v"(pha_addr) : "memory");
-                        if (__ballot(((pv | pha_self) >= rno + pha_bias) ? 0 : 1) == 0ull) break;
-#if NFC_WG_FLAGS_SLEEP
-                        __builtin_amdgcn_s_sleep(NFC_WG_FLAGS_SLEEP);
-#endif
-                    }
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                } else {
-                    wg_barrier();
-                }
-            } else {
-                wg_barrier();
-            }
+            wg_barrier();
             WG_PF_END(pf_b1);
             if constexpr (EX && REG) {
 #pragma unroll
@@ -1042,7 +1003,6 @@ __global__ __launch_bounds__(256) void k_threshold_wg(ThrArgs A) {
             pf_rounds++;
 #endif
             rbase += (uint32_t)WG_ROUND;
-            if constexpr (FLG) asm volatile("v_add_u32 %0, 1, %0" : "+v"(rno));
             mo_prev = mo;
             mo = (mo == 2u * (uint32_t)sizeof(sh->msk[0])) ? 0u : mo + (uint32_t)sizeof(sh->msk[0]);
         };
