@@ -48,6 +48,9 @@ extern "C" {
 /* (still 4, only new names: nfc_fsm_key_table, NFC_KEY_SECTORS, nfc_sector_of_block, nfc_fsm_key_table_init, nfc_fsm_set_sector_key,
  *  nfc_fsm_get_key_table, nfc_fsm_set_key_table, nfc_host_commands_keyed, nfc_multi_set_sector_keys, nfc_multi_get_sector_keys;
  *  nfc_fsm_state.cur_key also takes 2 + slot of such a table, its layout unchanged) */
+/* (still 4, only new names: nfc_emu_state, nfc_emu_card, nfc_emu_frame, nfc_emu_pair_result, nfc_emu_config, NFC_EMU_*, nfc_emu_state_init,
+ *  nfc_emu_last_error, nfc_host_emu_step, nfc_host_emulate, nfc_emu_answer, nfc_host_emulate_pairs, nfc_emulate_pairs_device,
+ *  nfc_multi_emulate, nfc_multi_fetch_answers, nfc_multi_answers, nfc_multi_get_emu_state, nfc_multi_set_emu_state) */
 #define NFC_AMD_ABI_VERSION 4
 
 typedef enum {
@@ -825,6 +828,174 @@ int nfc_host_recover_nested_keys(const nfc_nested_trace *traces, size_t n, const
                                  nfc_key_stats *stats);
 int nfc_recover_nested_keys_device(int device, const nfc_nested_trace *traces, size_t n, const nfc_nested_config *cfg,
                                    nfc_nested_result *out, nfc_key_stats *stats);
+
+/* ---- emulation: a tag machine and a reader machine, and K cards read by K readers with no signal at all ---------------------------
+ * The reference's second half (tag.py, reader.py, the closed loop of usrp_nfc.py:116-136), one text for host and device
+ * (csrc/emu.hip.h).  A TAG answers what it hears from its memory, its nonces and its access bits; a READER walks a card:
+ * anticollision, then an Ultralight's pages or every sector of a Classic 1K from the last down, an authentication per sector.
+ * WHAT IS EMULATED is an nfc_emu_card.  mem: exactly 64 bytes (Ultralight) or 1024 (Classic 1K) -- the reference's slices would
+ * silently shorten an answer otherwise; a reader has none.  rands: four bytes each, handed out in turn and from the first again; a
+ * Classic tag and every reader need 1 .. 64 of them (the reference's `random` fallback stays on the Python side).  key_a / key_b and
+ * table: a reader's keys (a tag's come from its memory).  The reader's UID holds 32 bytes (NFC_EMU_UID_OVERFLOW beyond).
+ * THE MODE travels in the card.  NFC_EMU_REFERENCE is the reference with its quirks: AUTHB served with key A and recorded as key A
+ * (tag.py:364-366); both keys from the trailer of sector 0 whatever block is authenticated (tag.py:52-57); the access bytes read at
+ * 16 * the AUTH's BLOCK number + 54 (tag.py:194-197,225-229), the trailer's only when the AUTH named the sector's first block; only
+ * reads are served; the reader always uses key A (reader.py:25); a nested tag nonce leaves under the OLD session's keystream
+ * (fsm.py:96-99).  NFC_EMU_CARD is what a MIFARE Classic does where that differs: the keys of the authenticated block's own sector,
+ * AUTHB with key B and the access conditions that depend on it, a nested tag nonce under the NEW key's keystream while uid ^ nt is
+ * fed in, a reader that takes its sector's key from `table` where the slot is filled (key_a / key_b otherwise).
+ * Where the reference raises -- a frame it does not know, a parity error, RANDRB before any AUTH, more UID bits than nonce bits --
+ * the machine gives no answer and sets the sticky NFC_EMU_RAISED; its prints are flags too.
+ * ARGUMENT ERRORS are NFC_ERR_ARG, raised before the device is touched; nfc_emu_last_error() names the argument. */
+enum { NFC_EMU_TAG = 0, NFC_EMU_READER = 1 };                 /* nfc_emu_card.role */
+enum { NFC_EMU_REFERENCE = 0, NFC_EMU_CARD = 1 };             /* nfc_emu_card.mode */
+enum { NFC_EMU_LINK_PLAIN = 0, NFC_EMU_LINK_AIR = 1 };        /* nfc_emu_config.link */
+enum { NFC_EMU_RAISED = 1,                                     /* the reference raises here: no answer */
+       NFC_EMU_UNEXPECTED = 2,                                 /* "ERROR, Unexpected command!!" (reader.py:146): HALT was sent */
+       NFC_EMU_ERR_ONES = 4, NFC_EMU_ERR_TWOS = 8, NFC_EMU_ERR_THREES = 16,   /* "ERROR WITH ONES / TWOS / THREES" (tag.py:207-212) */
+       NFC_EMU_UID_OVERFLOW = 32,                              /* the reader's UID would pass 32 bytes: not extended */
+       NFC_EMU_FLAGS_ALL = 63 };
+typedef struct nfc_emu_state {      /* 88 bytes; sticky flags apart, what tag.py / reader.py keep between two frames */
+    int32_t halted, selected;       /* tag */
+    int32_t auth;                   /* tag: the authenticated block (the AUTH's own number), -1 none */
+    int32_t auth_key;               /* tag: 0 none, 1 key A, 2 key B (tag.py:27-30) */
+    int32_t auth_prosp;             /* tag: the block of the AUTH in flight, -1 none */
+    int32_t at_set;                 /* tag: `at` holds the answer of the AUTH in flight */
+    uint8_t at[4];
+    uint32_t rand_idx;              /* both: the next nonce */
+    int32_t tag_type;               /* reader: -1 none, 0 .. 3 as nfc_fsm_state.tag_type */
+    int32_t cur_addr, auth_addr;    /* reader */
+    uint32_t uid_len;               /* reader: 0 .. 32 */
+    uint8_t uid[32];
+    uint32_t flags;                 /* NFC_EMU_* */
+    uint32_t reserved;              /* 0 */
+} nfc_emu_state;
+typedef struct nfc_emu_card {       /* 64 bytes */
+    int32_t role;                   /* NFC_EMU_TAG / NFC_EMU_READER */
+    int32_t tag_type;               /* tag: 0 Ultralight, 1 Classic 1K; reader: ignored */
+    int32_t mode;                   /* NFC_EMU_REFERENCE / NFC_EMU_CARD */
+    uint32_t mem_len;
+    const uint8_t *mem;
+    const uint8_t *rands;           /* n_rands * 4 bytes */
+    uint32_t n_rands;
+    uint32_t reserved;              /* 0 */
+    uint8_t key_a[6], key_b[6];     /* reader */
+    uint32_t reserved2;             /* 0 */
+    const nfc_fsm_key_table *table; /* reader, NFC_EMU_CARD: may be NULL */
+} nfc_emu_card;
+int nfc_emu_state_init(nfc_emu_state *st);
+const char *nfc_emu_last_error(void);   /* of the calling thread's last failed nfc_*emu* call */
+/* One step of one machine, host only: the heard command `cmd` (an index for nfc_command_info, or NFC_CMD_UNKNOWN / NFC_CMD_PARITY_ERROR)
+ * with its extra bytes -> *cmd_out the answer's command (-1: none) and frame_out / *n_out its whole plain frame, header | extra | CRC_A
+ * (frame_out holds 18 bytes).  What Tag.process_packet / Reader.process_packet do with (cmd, struct). */
+int nfc_host_emu_step(const nfc_emu_card *card, nfc_emu_state *st, int cmd, const uint8_t *extra, size_t n_extra, int *cmd_out,
+                      uint8_t *frame_out, size_t *n_out);
+/* REPLAY, host only: nfc_host_commands_keyed with an emulator behind the machine, as tag_emulate / reader_emulate wire one
+ * (usrp_nfc.py:35-100, packets.py:88-90).  After every command whose type is the OTHER side's (a tag card hears reader frames, a reader
+ * card tag frames) the emulator of `card` runs, and its answer passes through the SAME machine's process_outgoing -- in the card's mode
+ * -- so the machine has advanced before the next heard frame is decrypted.  `st` / `table` / the frames and out / data / enc / cap / used
+ * are nfc_host_commands_keyed's; `est` is the emulator's state, advanced in place.  answers: one record per answer (at most n), src the
+ * index of the command it answers; ans_plain / ans_air / ans_par: 18 * n entries each, an answer's plain bytes and what goes on the air
+ * with its ninth bits at byte_off (an answer owns 18 entries, zeros behind its n_bytes).  A stream is meant to decode only the side it
+ * hears; with both decoded the machine hears the real answer AND sends its own, as the reference's would.  On the device: nfc_multi_emulate,
+ * below. */
+typedef struct nfc_emu_answer {         /* 24 bytes */
+    uint32_t src;                       /* index of the command (in `out`) this answers */
+    int32_t cmd;                        /* index for nfc_command_info */
+    uint32_t byte_off;
+    uint16_t n_bytes;
+    uint16_t n_bits;                    /* 9 * n_bytes; 7 for a short frame (no machine answers with one today) */
+    uint32_t flags;                     /* NFC_EMU_FRAME_ENCRYPTED */
+    uint32_t reserved;                  /* 0 */
+} nfc_emu_answer;
+int nfc_host_emulate(nfc_fsm_state *st, const nfc_fsm_key_table *table, const nfc_emu_card *card, nfc_emu_state *est, const nfc_raw_frame *merged,
+                     size_t n, const uint8_t *bytes0, const uint8_t *par0, const uint8_t *bytes1, const uint8_t *par1, nfc_frame *out, uint8_t *data,
+                     uint16_t *enc, size_t cap, size_t *used, nfc_emu_answer *answers, uint8_t *ans_plain, uint8_t *ans_air, uint8_t *ans_par,
+                     size_t *n_answers);
+/* REPLAY ON THE DEVICE: a stream of a multi-stream context that answers.  nfc_multi_emulate gives stream `stream` (-1: every stream)
+ * a card -- a role per stream is allowed -- or, with NULL, takes it away; a card implies nfc_multi_track_commands(on).  From then on a
+ * tracked push runs the EMULATING form of the machine kernel (csrc/multi_commands.hip.h: k_multi_commands_emu): the same walk, and after
+ * every command whose type is the other side's the lane runs its emulator and passes the answer through its own machine's
+ * process_outgoing, in the same launch that decodes the commands -- nfc_host_emulate is its twin, stream by stream.  Cards and the
+ * emulators' state (nfc_emu_state; nfc_multi_get_emu_state / _set_emu_state) live on the device from push to push; a new card, and
+ * nfc_multi_reset(stream), return the emulator to nfc_emu_state_init's state.  A reader card's key_a / key_b / table are NOT used here:
+ * the stream's machine has its own (nfc_multi_set_keys, nfc_multi_set_sector_keys).  A context that never calls nfc_multi_emulate
+ * allocates and launches exactly what it did; while no stream holds a card a tracked push launches k_multi_commands as ever.
+ * nfc_multi_fetch_answers: the answers of the last push, as sections of the buffer nfc_multi_fetch_commands copies -- the same single
+ * copy; after a fetch of the commands (or a second call) no device call.  Stream k's answers are records ans[cmd_off[k] ..
+ * cmd_off[k] + ans_n[k]) (at most one answer per command, so the commands' offsets place them; there is no ans_off of its own); a
+ * record's src is the index of the command it answers among the stream's commands, its bytes are plain / air / par[18 * (cmd_off[k] + j)
+ * + i] for answer j.  emulated == 0: the last push ran without a card (or stored nothing): no answers, NULL arrays.  The sections are
+ * on 16 bytes each and followed by the guard word; the test build's guard check covers them.  As in the reference, a stream is meant to
+ * decode only the side it hears; with both decoded the machine hears the real answer and sends its own.
+ * Errors as nfc_multi_set_keys': NFC_ERR_ARG before the device is touched, the argument's name in the message.
+ * COST, measured with K copies of the reader side of a 24-frame Classic capture, 12 answers per stream (README.md,
+ * profiles/emulate_bench.json): the machine kernel takes 0.509 ms with a card per stream against 0.025 ms without at 1 024 streams, 0.543
+ * against 0.033 ms at 16 384; the push 7.75 against 7.28 ms and 9.09 against 8.29 ms. */
+typedef struct nfc_multi_answers {
+    uint32_t n_streams, emulated;
+    uint64_t n_answers;
+    const uint64_t *cmd_off;            /* n_streams + 1: as nfc_multi_commands.cmd_off */
+    const uint32_t *ans_n;              /* n_streams */
+    const nfc_emu_answer *ans;
+    const uint8_t *plain, *air, *par;
+    uint64_t reserved[4];
+} nfc_multi_answers;
+int nfc_multi_emulate(nfc_multi *m, int64_t stream /* -1: every stream */, const nfc_emu_card *card /* NULL: take the card away */);
+int nfc_multi_fetch_answers(nfc_multi *m, nfc_multi_answers *out);
+int nfc_multi_get_emu_state(nfc_multi *m, uint32_t stream, nfc_emu_state *st);
+int nfc_multi_set_emu_state(nfc_multi *m, uint32_t stream, const nfc_emu_state *st);
+/* THE CLOSED LOOP.  Pair i is tags[i] read by readers[i]: REQA, then every answer is the other side's next frame; after a frame that
+ * gets no answer the loop sends REQA again and wakes the tag (usrp_nfc.py:125-131) -- `rounds` of those restarts, 1 .. 64.
+ * NFC_EMU_LINK_PLAIN is emulate.run literally: command and structure are handed over, no protocol machine is involved, nothing is
+ * encrypted.  NFC_EMU_LINK_AIR gives each side a protocol machine of its own, as tag_emulate / reader_emulate do: a frame leaves through
+ * the sender's process_outgoing and arrives through the receiver's process_frame, so it is looked up by stage and decrypted there.  The
+ * tag's machine has its two keys from the trailer of sector 0 and, in CARD mode, every trailer as its sector key table; the reader's has
+ * key_a / key_b and, in CARD mode, `table`.  The loop's own REQA passes no machine (binary_src repeats it); in CARD mode the reader's
+ * machine starts every round without a session, in REFERENCE mode it keeps what it had, as the reference's does.
+ * THE TRANSCRIPT.  Pair i owns cap_frames records at frames + i * cap_frames and cap_bytes bytes at plain / air / par + i * cap_bytes:
+ * per frame put on the air (the loop's REQAs included) its command, type, the plain bytes, and the on-air bytes with their ninth
+ * bits in the form nfc_raw_frame's bytes / par have.  A short frame (REQA) has n_bits 7 and the ninth bit the frame-end repair assumes.
+ * A pair that outgrows its slab keeps TRUE counts in its result, stores the frames before the first that did not fit and says so in
+ * its flags; a round of more than 1024 frames is ended (NFC_EMU_PAIR_RUNAWAY).
+ * nfc_host_emulate_pairs is the CPU twin of the kernel behind nfc_emulate_pairs_device (a lane per pair, csrc/nfc_emu.hip): the
+ * same bytes in every output.  The device call checks every argument before the device is touched, returns complete results, and
+ * fails with NFC_ERR_INTERNAL when a guard word behind one of its device sections was overwritten.  No CPU fallback.
+ * n above 65 536, cap_frames above 2^16, cap_bytes above 2^20, n * cap_bytes above 2^30, a non-zero reserved word: NFC_ERR_ARG.
+ * COST, measured with K different Classic 1K cards read whole, 199 frames each, AIR / CARD (README.md, profiles/emulate_bench.json): the
+ * kernel takes 9.2 ms whatever K is (one lane's serial cipher clocks); per card the host twin costs 273 us against 9 753 us on the GPU
+ * for ONE card (the GPU loses, 36 x), 308 us against 12.5 us at 1 024 cards and 3.71 us at 16 384 (the call: 61 ms, of it 9.2 the kernel). */
+enum { NFC_EMU_FRAME_SEED = 1,          /* the loop's own REQA */
+       NFC_EMU_FRAME_ENCRYPTED = 2 };   /* the on-air bytes differ from the plain ones */
+typedef struct nfc_emu_frame {          /* 16 bytes */
+    int16_t cmd;                        /* index for nfc_command_info */
+    uint8_t type;                       /* 0 tag -> reader, 1 reader -> tag */
+    uint8_t flags;                      /* NFC_EMU_FRAME_* */
+    uint32_t byte_off;                  /* in the pair's part of plain / air / par */
+    uint16_t n_bytes;
+    uint16_t n_bits;                    /* on the air: 9 * n_bytes, or 7 for a short frame */
+    uint32_t round;
+} nfc_emu_frame;
+enum { NFC_EMU_PAIR_CUT_FRAMES = 1, NFC_EMU_PAIR_CUT_BYTES = 2, NFC_EMU_PAIR_RUNAWAY = 4 };
+typedef struct nfc_emu_pair_result {    /* 32 bytes */
+    uint32_t n_frames, n_bytes;         /* the TRUE counts; stored: what fits before the first frame that did not */
+    uint32_t flags;                     /* NFC_EMU_PAIR_* */
+    uint32_t rounds;
+    uint32_t tag_flags, reader_flags;   /* NFC_EMU_* of the two emulators */
+    uint32_t tag_fsm_flags, reader_fsm_flags;   /* NFC_FSM_* of the two protocol machines (AIR) */
+} nfc_emu_pair_result;
+typedef struct nfc_emu_config {         /* 32 bytes */
+    uint32_t link;                      /* NFC_EMU_LINK_* */
+    uint32_t rounds;                    /* 1 .. 64 */
+    uint32_t cap_frames, cap_bytes;     /* per pair; at least 1 */
+    const uint32_t *pair_cap_frames;    /* NULL, or n entries, each at least 1 (NFC_ERR_ARG): pair i stores at most min(cap_frames, pair_cap_frames[i]) frames in its slab of cap_frames */
+    uint32_t reserved[2];
+} nfc_emu_config;
+int nfc_host_emulate_pairs(const nfc_emu_card *tags, const nfc_emu_card *readers, size_t n, const nfc_emu_config *cfg,
+                           nfc_emu_pair_result *results, nfc_emu_frame *frames, uint8_t *plain, uint8_t *air, uint8_t *par);
+int nfc_emulate_pairs_device(int device, const nfc_emu_card *tags, const nfc_emu_card *readers, size_t n, const nfc_emu_config *cfg,
+                             nfc_emu_pair_result *results, nfc_emu_frame *frames, uint8_t *plain, uint8_t *air, uint8_t *par,
+                             float *kernel_ms /* NULL, or the kernel's duration by HIP events */);
 
 /* one stream's boundary state, in the form an nfc_ctx exports and imports it */
 int nfc_multi_get_state(nfc_multi *m, uint32_t stream, nfc_state_header *hdr, float *ring, size_t ring_cap, uint8_t *pending, size_t pending_cap);

@@ -100,6 +100,42 @@ class NestedConfig(C.Structure):   # nfc_nested_config
     _fields_ = [('search', KeyConfig), ('cand_first', C.c_uint32), ('cand_count', C.c_uint32), ('reserved', C.c_uint32 * 2)]
 
 
+class EmuState(C.Structure):   # nfc_emu_state
+    _fields_ = [('halted', C.c_int32), ('selected', C.c_int32), ('auth', C.c_int32), ('auth_key', C.c_int32), ('auth_prosp', C.c_int32),
+                ('at_set', C.c_int32), ('at', C.c_uint8 * 4), ('rand_idx', C.c_uint32), ('tag_type', C.c_int32), ('cur_addr', C.c_int32),
+                ('auth_addr', C.c_int32), ('uid_len', C.c_uint32), ('uid', C.c_uint8 * 32), ('flags', C.c_uint32), ('reserved', C.c_uint32)]
+
+
+class EmuCard(C.Structure):   # nfc_emu_card
+    _fields_ = [('role', C.c_int32), ('tag_type', C.c_int32), ('mode', C.c_int32), ('mem_len', C.c_uint32), ('mem', C.c_void_p),
+                ('rands', C.c_void_p), ('n_rands', C.c_uint32), ('reserved', C.c_uint32), ('key_a', C.c_uint8 * 6), ('key_b', C.c_uint8 * 6),
+                ('reserved2', C.c_uint32), ('table', C.c_void_p)]
+
+
+class MultiAnswers(C.Structure):   # nfc_multi_answers
+    _fields_ = [('n_streams', C.c_uint32), ('emulated', C.c_uint32), ('n_answers', C.c_uint64), ('cmd_off', C.c_void_p), ('ans_n', C.c_void_p),
+                ('ans', C.c_void_p), ('plain', C.c_void_p), ('air', C.c_void_p), ('par', C.c_void_p), ('reserved', C.c_uint64 * 4)]
+
+
+class EmuConfig(C.Structure):   # nfc_emu_config
+    _fields_ = [('link', C.c_uint32), ('rounds', C.c_uint32), ('cap_frames', C.c_uint32), ('cap_bytes', C.c_uint32), ('pair_cap_frames', C.c_void_p),
+                ('reserved', C.c_uint32 * 2)]
+
+
+NFC_EMU_TAG, NFC_EMU_READER = 0, 1
+NFC_EMU_REFERENCE, NFC_EMU_CARD = 0, 1
+NFC_EMU_LINK_PLAIN, NFC_EMU_LINK_AIR = 0, 1
+NFC_EMU_RAISED, NFC_EMU_UNEXPECTED, NFC_EMU_ERR_ONES, NFC_EMU_ERR_TWOS, NFC_EMU_ERR_THREES, NFC_EMU_UID_OVERFLOW = 1, 2, 4, 8, 16, 32
+NFC_EMU_FRAME_SEED, NFC_EMU_FRAME_ENCRYPTED = 1, 2
+NFC_EMU_PAIR_CUT_FRAMES, NFC_EMU_PAIR_CUT_BYTES, NFC_EMU_PAIR_RUNAWAY = 1, 2, 4
+EMU_FRAME_DTYPE = np.dtype([('cmd', '<i2'), ('type', 'u1'), ('flags', 'u1'), ('byte_off', '<u4'), ('n_bytes', '<u2'), ('n_bits', '<u2'),
+                            ('round', '<u4')])   # nfc_emu_frame
+EMU_ANSWER_DTYPE = np.dtype([('src', '<u4'), ('cmd', '<i4'), ('byte_off', '<u4'), ('n_bytes', '<u2'), ('n_bits', '<u2'), ('flags', '<u4'),
+                             ('reserved', '<u4')])   # nfc_emu_answer
+EMU_RESULT_DTYPE = np.dtype([('n_frames', '<u4'), ('n_bytes', '<u4'), ('flags', '<u4'), ('rounds', '<u4'), ('tag_flags', '<u4'),
+                             ('reader_flags', '<u4'), ('tag_fsm_flags', '<u4'), ('reader_fsm_flags', '<u4')])   # nfc_emu_pair_result
+
+
 class Frame(C.Structure):   # nfc_frame
     _fields_ = [('cmd', C.c_int32), ('type', C.c_int32), ('byte_off', C.c_uint32), ('n_bytes', C.c_uint16),
                 ('n_header', C.c_uint16), ('n_extra', C.c_uint16), ('n_crc', C.c_uint16), ('flags', C.c_uint32),
@@ -169,7 +205,9 @@ SYMBOLS = ['nfc_abi_version', 'nfc_device_count', 'nfc_create', 'nfc_destroy', '
            'nfc_host_commands_keyed', 'nfc_multi_set_sector_keys', 'nfc_multi_get_sector_keys',
            'nfc_find_auths', 'nfc_host_recover_keys', 'nfc_recover_keys_device',
            'nfc_find_nested_auths', 'nfc_host_nested_candidates', 'nfc_nested_candidates_device', 'nfc_host_recover_nested_keys',
-           'nfc_recover_nested_keys_device']
+           'nfc_recover_nested_keys_device',
+           'nfc_emu_state_init', 'nfc_emu_last_error', 'nfc_host_emu_step', 'nfc_host_emulate', 'nfc_multi_emulate', 'nfc_multi_fetch_answers', 'nfc_multi_get_emu_state',
+           'nfc_multi_set_emu_state', 'nfc_host_emulate_pairs', 'nfc_emulate_pairs_device']
 
 _libs = {}
 
@@ -310,6 +348,17 @@ def load(path=None):
     L.nfc_nested_candidates_device.argtypes = [C.c_int, vp, sz, vp, vp]
     L.nfc_host_recover_nested_keys.argtypes = [vp, sz, C.POINTER(NestedConfig), vp, C.POINTER(KeyStats)]
     L.nfc_recover_nested_keys_device.argtypes = [C.c_int, vp, sz, C.POINTER(NestedConfig), vp, C.POINTER(KeyStats)]
+    L.nfc_emu_state_init.argtypes = [C.POINTER(EmuState)]
+    L.nfc_emu_last_error.restype = C.c_char_p
+    L.nfc_host_emu_step.argtypes = [C.POINTER(EmuCard), C.POINTER(EmuState), C.c_int, vp, sz, C.POINTER(C.c_int), vp, psz]
+    L.nfc_host_emulate.argtypes = [C.POINTER(FsmState), C.POINTER(FsmKeyTable), C.POINTER(EmuCard), C.POINTER(EmuState), vp, sz, vp, vp, vp, vp, vp, vp, vp,
+                                   sz, psz, vp, vp, vp, vp, psz]
+    L.nfc_multi_emulate.argtypes = [vp, C.c_int64, C.POINTER(EmuCard)]
+    L.nfc_multi_fetch_answers.argtypes = [vp, C.POINTER(MultiAnswers)]
+    L.nfc_multi_get_emu_state.argtypes = [vp, u32, C.POINTER(EmuState)]
+    L.nfc_multi_set_emu_state.argtypes = [vp, u32, C.POINTER(EmuState)]
+    L.nfc_host_emulate_pairs.argtypes = [vp, vp, sz, C.POINTER(EmuConfig), vp, vp, vp, vp, vp]
+    L.nfc_emulate_pairs_device.argtypes = [C.c_int, vp, vp, sz, C.POINTER(EmuConfig), vp, vp, vp, vp, vp, C.POINTER(C.c_float)]
     for name in SYMBOLS:
         getattr(L, name)
     _libs[path] = L

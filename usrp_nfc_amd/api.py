@@ -478,6 +478,40 @@ class NfcMultiContext(object):
         self._chk(self.L.nfc_multi_fetch_commands(self.h, C.byref(c)), 'nfc_multi_fetch_commands')
         return NfcMultiCommands(c, copy)
 
+    def emulate(self, cards, stream=-1):
+        """Give stream `stream` a card (an emulate.Card; -1: every stream; a list: one per stream, None for none), or None to take it away
+        (nfc_multi_emulate).  From then on a tracked push -- tracking is switched on -- runs the emulating form of the machine kernel: the
+        stream answers what it hears, in the launch that decodes its commands; fetch_answers() brings the answers."""
+        if isinstance(cards, (list, tuple)):
+            if len(cards) != self.n_streams:
+                raise NfcError('emulate: a list of cards has one entry per stream')
+            for k, c in enumerate(cards):
+                self.emulate(c, k)
+            return
+        c = None if cards is None else cards.struct()
+        self._chk(self.L.nfc_multi_emulate(self.h, int(stream), None if c is None else C.byref(c)), 'nfc_multi_emulate')
+
+    def fetch_answers(self, copy=True):
+        """The answers of the last push (nfc_multi_fetch_answers): sections of the buffer fetch_commands() copies, so after a fetch of the
+        commands, or a second call, no device call -> NfcMultiAnswers."""
+        a = _lib.MultiAnswers()
+        self._chk(self.L.nfc_multi_fetch_answers(self.h, C.byref(a)), 'nfc_multi_fetch_answers')
+        return NfcMultiAnswers(a, copy)
+
+    def emu_state(self, k):
+        """Stream k's emulator as a plain nfc_emu_state (an _lib.EmuState)."""
+        if not 0 <= int(k) < self.n_streams:
+            raise NfcError('emu_state: stream %d out of range (n_streams %d)' % (k, self.n_streams))
+        st = _lib.EmuState()
+        self._chk(self.L.nfc_multi_get_emu_state(self.h, int(k), C.byref(st)), 'nfc_multi_get_emu_state')
+        return st
+
+    def set_emu_state(self, k, st):
+        """Stream k's emulator continues from `st` (emulate.state_init(), another stream's emu_state())."""
+        if not 0 <= int(k) < self.n_streams:
+            raise NfcError('set_emu_state: stream %d out of range (n_streams %d)' % (k, self.n_streams))
+        self._chk(self.L.nfc_multi_set_emu_state(self.h, int(k), C.byref(st)), 'nfc_multi_set_emu_state')
+
     def counts_all(self):
         """Every stream's counts and flags of the last push from one call: a COUNTS_FLAGS_DTYPE array of n_streams records."""
         cnt, flags = np.zeros(self.n_streams, COUNTS_DTYPE), np.zeros(self.n_streams, np.uint32)
@@ -813,6 +847,47 @@ class NfcMultiFrames(object):
     def crc_ok_mask(self):
         """Per type, over ALL frames of frames[t]: parity held and the CRC_A matched."""
         return [(self.frames[t]['flags'] & NFC_RAW_CRC_A_OK) != 0 for t in (0, 1)]
+
+
+class NfcMultiAnswers(object):
+    """What the streams of a multi-stream context answered in the last push (nfc_multi_fetch_answers).  `n[k]` answers of stream k;
+    answers_of(k) -> (records, plain, air, par): EMU_ANSWER_DTYPE records (src: the index of the command it answers among the stream's
+    commands) and the stream's bytes, a record's at its byte_off -- numpy views of the fetched arrays (copies with copy=True)."""
+
+    def __init__(self, a, copy=True):
+        K = int(a.n_streams)
+        self.n_streams, self.emulated, self.n_answers = K, bool(a.emulated), int(a.n_answers)
+
+        def arr(ptr, n, dtype):
+            dtype = np.dtype(dtype)
+            if not ptr or n == 0:
+                return np.zeros(0, dtype)
+            v = np.frombuffer((C.c_uint8 * (n * dtype.itemsize)).from_address(ptr), dtype)
+            return v.copy() if copy else v
+        self.cmd_off = arr(a.cmd_off, K + 1, '<u8')
+        total = int(self.cmd_off[K]) if len(self.cmd_off) else 0
+        self.n = arr(a.ans_n, K, '<u4') if self.emulated else np.zeros(K, np.uint32)
+        self.records = arr(a.ans, total, _lib.EMU_ANSWER_DTYPE) if self.emulated else np.zeros(0, _lib.EMU_ANSWER_DTYPE)
+        self.plain, self.air, self.par = ((arr(p, 18 * total, 'u1') if self.emulated else np.zeros(0, np.uint8)) for p in (a.plain, a.air, a.par))
+
+    def answers_of(self, k):
+        if not self.emulated or int(self.n[k]) == 0:
+            z = np.zeros(0, np.uint8)
+            return np.zeros(0, _lib.EMU_ANSWER_DTYPE), z, z, z
+        c0, n = int(self.cmd_off[k]), int(self.n[k])
+        sl = slice(18 * c0, 18 * (c0 + n))
+        return self.records[c0:c0 + n], self.plain[sl], self.air[sl], self.par[sl]
+
+    def bits(self, k, i):
+        """Answer i of stream k as the bit list the reference's emulator hands binary_src.set_bits (what tx.encode takes)."""
+        rec, _, air, par = self.answers_of(k)
+        o, n = int(rec[i]['byte_off']), int(rec[i]['n_bytes'])
+        if int(rec[i]['n_bits']) == 7:
+            return [(int(air[o]) >> j) & 1 for j in range(7)]
+        out = []
+        for v, q in zip(air[o:o + n].tolist(), par[o:o + n].tolist()):
+            out += [(v >> j) & 1 for j in range(8)] + [q & 1]
+        return out
 
 
 class NfcMultiCommands(object):

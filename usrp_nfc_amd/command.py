@@ -130,3 +130,18 @@ class CommandStructure(object):   # command.py:204-265
 
     def display(self, out=None):
         (out or sys.stdout).write(self.text())
+
+    @staticmethod
+    def encode_command(cmd, bytes):
+        """command.py:256-265: the structure of a command that is about to be sent -- its header, the extra bytes and, where the
+        command carries one, the CRC_A of both; without a command, UNKNOWN around the bytes."""
+        bytes = [int(b) & 0xFF for b in bytes]
+        if not cmd:
+            return CommandStructure('UNKNOWN', [], bytes)
+        header, crc = cmd.header(), []
+        if cmd.needs_crc():
+            data, out = (C.c_uint8 * (len(header) + len(bytes)))(*(header + bytes)), (C.c_uint8 * 2)()
+            if _lib.load().nfc_crc_a(data, len(data), out) != 0:
+                raise ValueError('nfc_crc_a failed')
+            crc = [int(out[0]), int(out[1])]
+        return CommandStructure(cmd.name(), header, bytes, crc)

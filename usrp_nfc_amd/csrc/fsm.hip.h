@@ -506,14 +506,18 @@ NFC_HD Rec process_frame(Mach &M, int type, uint32_t raw_flags, uint32_t n, cons
     return out;
 }
 
-// ---- host only: CRYPTO1 over a bit list, for the frames an emulator is about to send (protocol.h: fsm_process_outgoing) ----
-// cipher.py:20-35 on a frame with its parity bits: every bit is xored with the filter output; the ninth bit of a group reuses the keystream
-// bit of the next data bit -- the register does not move for it.  feed_in: the plaintext is fed back into the register ({nr}).
-inline void crypt_bits(uint64_t &st, const uint8_t *in, size_t n, uint8_t *out, bool feed_in) {
-    for (size_t k = 0; k < n; k++) {
-        const uint32_t b = in[k] & 1u;
-        out[k] = (uint8_t)(filter(st) ^ b);
-        if (k % 9 != 8) st = shift_in(st, feed_in ? b : 0u);
+// ---- what an EMULATOR is about to send: fsm.process_outgoing (fsm.py:68-112) ----
+// A frame is a list of bits, its ninth bits included, reached through accessors -- in(k) the k-th bit, out(k, v) the k-th bit to put on the
+// air, every k < n written once, in order -- so that one text serves the host machine's bit list (protocol.h: fsm_process_outgoing) and
+// the bytes-plus-ninth-bits form of a lane's emulator (emu.hip.h: FrameIn / FrameOut).
+// cipher.py:20-35 on bits [from, to) of a frame: every bit is xored with the filter output; the ninth bit of a group -- counted from `from`
+// -- reuses the keystream bit of the next data bit: the register does not move for it.  feed_in: the plaintext is fed back ({nr}).
+template <class In, class Out>
+NFC_HD void crypt_bits(uint64_t &st, size_t from, size_t to, const In &in, Out &out, bool feed_in) {
+    for (size_t k = from; k < to; k++) {
+        const uint32_t b = in(k) & 1u;
+        out(k, filter(st) ^ b);
+        if ((k - from) % 9 != 8) st = shift_in(st, feed_in ? b : 0u);
     }
 }
 // cipher.py:62-72 with a plain tag nonce of n bits (bit(j): its j-th): uid ^ nonce goes into the register M.st, which holds the key -- the
@@ -521,7 +525,7 @@ inline void crypt_bits(uint64_t &st, const uint8_t *in, size_t n, uint8_t *out, 
 // reference's answers then have that many bits, so that no {ar} / {at} ever equals them; 0 where the reference raises -- more UID bits
 // than nonce bits (IndexError), a nonce of no bits (ZeroDivisionError in lfsr.py) -- with the register left at the key.
 template <class Mach, class Bit>
-inline int set_tag_plain(Mach &M, size_t n, Bit bit) {
+NFC_HD int set_tag_plain(Mach &M, size_t n, Bit bit) {
     const size_t ll = 8 * (size_t)uid_len(M);
     if (n < ll || n == 0) return 0;
     for (size_t i = 0; i < ll; i++) M.st = shift_in(M.st, ((uid_byte(M, (uint32_t)(i >> 3)) >> (i & 7)) ^ bit(i)) & 1u);
@@ -531,6 +535,78 @@ inline int set_tag_plain(Mach &M, size_t n, Bit bit) {
     M.ar = nonce_advance(nonce, 64);
     M.at = nonce_advance(M.ar, 32);
     return 1;
+}
+// The machine follows the frame as if it had been heard -- tag type from an ATQA, the command in flight -- and, while a MIFARE Classic
+// session is up, encrypts it.  Returns 1 when the tag is an Ultralight, nothing written: the reference then runs the frame through
+// process_bits "to update state" (fsm.py:71-72) -- the caller does.
+// card: what a MIFARE Classic and its reader do where the reference's hook differs (emu.hip.h: NFC_EMU_CARD) -- an outgoing AUTH sets the
+// key choice even where the table has no slot (key A / key B), and a NESTED tag nonce of four bytes under a four-byte UID leaves under
+// the NEW key's keystream while uid ^ nt is fed in, its ninth bits included: the frame process_frame's nested route decrypts.
+template <class Mach, class Table, class In, class Out>
+NFC_HD int outgoing(Mach &M, size_t n, int cmd, const In &in, Out &out, const Table &tab, bool card) {
+    if (M.tag_type == 0) return 1;
+    if (M.tag_type == 1) {   // CLASSIC1K (fsm.py:73-99)
+        M.cur_cmd = cmd;
+        if ((cmd == C_AUTHA || cmd == C_AUTHB) && n >= 17) {
+            // the sector's key from the table, as a heard AUTH chooses it; with no slot present the choice stays the caller's, as ever
+            uint32_t block = 0;
+            for (int k = 0; k < 8; k++) block |= (uint32_t)(in((size_t)(9 + k)) & 1u) << k;
+            const int c = skeys::choose(tab, cmd == C_AUTHB, block);
+            if (c >= 2 || card) M.cur_key = c;
+        }
+        if (M.encrypted && cmd != C_RANDTA) {
+            // ({nr}{ar}: the reader's own nonce, the first half, feeds the register as it is encrypted)
+            const size_t ll = cmd == C_RANDRB ? n / 2 : 0;
+            crypt_bits(M.st, 0, ll, in, out, true);
+            crypt_bits(M.st, ll, n, in, out, false);
+        } else if (cmd == C_RANDTA && card && M.encrypted && n == 36 && uid_len(M) == 4u) {
+            M.st = skeys::resolve(tab, M.cur_key, M.key_a, M.key_b);
+            uint32_t nonce = 0;
+            for (uint32_t i = 0; i < 4u; i++) {
+                const uint32_t ub = uid_byte(M, i);
+                for (uint32_t k = 0; k < 8u; k++) {
+                    const uint32_t b = in((size_t)(9u * i + k)) & 1u;
+                    out((size_t)(9u * i + k), b ^ filter(M.st));
+                    M.st = shift_in(M.st, b ^ ((ub >> k) & 1u));
+                    nonce |= b << (8u * i + k);
+                }
+                out((size_t)(9u * i + 8u), (in((size_t)(9u * i + 8u)) & 1u) ^ filter(M.st));
+            }
+            M.ar = nonce_advance(nonce, 64);
+            M.at = nonce_advance(M.ar, 32);
+            M.encrypted = 1;
+        } else if (cmd == C_RANDTA) {
+            // the tag's nonce: a fresh register keyed for the sector takes uid ^ nonce -- the UID bits there are, the nonce bits there are
+            // (fsm.py:86-97) -- and becomes the session; under a session that is already up (nested authentication) the OLD register
+            // encrypts what goes on the air.  Where the reference raises it has installed nothing: the session stays as it was.
+            const uint64_t st = M.st;
+            const uint32_t ar = M.ar, at = M.at;
+            if (M.encrypted) {
+                uint64_t old = st;
+                crypt_bits(old, 0, n, in, out, false);
+            } else {
+                for (size_t i = 0; i < n; i++) out(i, in(i) & 1u);
+            }
+            M.st = skeys::resolve(tab, M.cur_key, M.key_a, M.key_b);
+            M.ar = M.at = 0;
+            // (the nonce's j-th bit: the frame's without its ninth bits)
+            const int session = set_tag_plain(M, n - n / 9, [&](size_t j) { return (uint32_t)(in(j + j / 8) & 1u); });
+            if (session) M.encrypted = session;
+            else M.st = st, M.ar = ar, M.at = at;
+        } else {
+            for (size_t i = 0; i < n; i++) out(i, in(i) & 1u);
+        }
+        return 0;
+    }
+    for (size_t i = 0; i < n; i++) out(i, in(i) & 1u);
+    switch (cmd) {   // no tag type yet: an ATQA sets it (fsm.py:101-108)
+    case C_ATQAUL: M.tag_type = 0; break;
+    case C_ATQA1K: M.tag_type = 1; break;
+    case C_ATQA4K: M.tag_type = 2; break;
+    case C_ATQADS: M.tag_type = 3; break;
+    default: break;
+    }
+    return 0;
 }
 
 // ---- Machine <-> nfc_fsm_state ----

@@ -16,6 +16,7 @@
 
 #include "../../include/nfc_amd.h"
 #include "frames.hip.h"
+#include "emu.hip.h"
 #include "fsm.hip.h"
 
 namespace nfc {
@@ -33,6 +34,26 @@ struct Args {
     const uint32_t *sector_keys;   // [skeys::SLOTS][2][K] (sector_keys.h), or null: no stream of the context was ever given a sector key
 };
 constexpr int THREADS = 64;
+
+// The EMULATING form: a stream that was given a card (nfc_multi_emulate) answers what it hears.  k_multi_commands_emu is
+// k_multi_commands' walk with one step more per frame: after a command of the OTHER side's type the lane runs the card's emulator
+// (emu.hip.h: replay_step) and passes the answer through its OWN machine's outgoing, so the machine has advanced before the next heard
+// frame is decrypted -- which is why this cannot be a kernel behind the machine kernel.  A context launches it only while a stream holds a
+// card; otherwise it launches k_multi_commands, whose text is not touched.
+// The cards live on the device from push to push: memory [64][K] units of 16 bytes and nonces [64][K] words as emu.hip.h's DevCard
+// reads them (lanes that serve the same block load neighbouring units), params [EP_WORDS][K], the emulators' state [emu::EW_WORDS][K].
+// The answers go behind the commands' sections, each on 16 bytes and followed by the guard word: stream k's answers are records
+// [cmd_off[k], cmd_off[k] + ans_n[k]) -- at most one per command, so the commands' own offsets place them and no scan is needed --, a
+// record's bytes at 18 * its index in ans_plain / ans_air / ans_par.
+enum { EP_PRESENT, EP_ROLE, EP_TAG_TYPE, EP_MODE, EP_N_RANDS, EP_WORDS };
+enum { ESEC_N, ESEC_REC, ESEC_PLAIN, ESEC_AIR, ESEC_PAR, ESEC_SCRATCH, ESEC_COUNT };
+constexpr uint32_t ANS_BYTES = 18;
+struct EmuArgs {
+    const uint32_t *mem, *rands, *params;
+    uint32_t *state;
+    uint64_t at[ESEC_COUNT], end[ESEC_COUNT];
+};
+void launch_emu(const Args &A, const EmuArgs &E, hipStream_t stream, hipEvent_t e0, hipEvent_t e1);
 
 void launch(const Args &A, hipStream_t stream, hipEvent_t e0, hipEvent_t e1);
 // streams [k0, k1): the state of nfc_fsm_state_init / the two keys (48 bits, byte 0 lowest)
@@ -134,6 +155,125 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(3))) vo
     }
     ((uint32_t *)(buf + L.at[SEC_FLAGS]))[k] = M.flags;
     fsmd::store_machine(M, A.state, K, k);
+}
+
+__global__ __launch_bounds__(THREADS) void k_multi_commands_emu(Args A, EmuArgs E) {
+    const frames::MultiArgs &R = A.R;
+    const Layout &L = A.L;
+    uint8_t *__restrict__ buf = R.packed;
+    if (blockIdx.x == 0)
+        for (uint32_t i = threadIdx.x; i < (uint32_t)(SEC_COUNT + ESEC_COUNT) * R.guard_bytes; i += THREADS) {
+            const uint32_t s = i / R.guard_bytes, b = i % R.guard_bytes;
+            buf[(s < (uint32_t)SEC_COUNT ? L.end[s] : E.end[s - SEC_COUNT]) + b] = (uint8_t)(R.guard_word >> (8 * (b & 3u)));
+        }
+    const uint32_t K = R.K, k = blockIdx.x * THREADS + threadIdx.x;
+    if (k >= K) return;
+    const size_t T = (size_t)K + 1;
+    const uint64_t *__restrict__ tab = R.table;
+    uint32_t nfr0, nfr1;
+    const nfc_raw_frame *rec0, *rec1;
+    const uint8_t *rb0, *rb1, *rp0, *rp1;
+    uint64_t room0, room1;
+#define NFC_STREAM_PART(t, nfr, rec, rb, rp, room)                                     \
+    {                                                                                  \
+        uint64_t fe = tab[(size_t)t * T + k + 1], fb = tab[(size_t)t * T + k];         \
+        fe = fe < R.F.total_frames[t] ? fe : R.F.total_frames[t];                      \
+        fb = fb < fe ? fb : fe;                                                        \
+        uint64_t bb = tab[(size_t)(2 + t) * T + k];                                    \
+        bb = bb < R.F.total_bytes[t] ? bb : R.F.total_bytes[t];                        \
+        nfr = (uint32_t)(fe - fb);                                                     \
+        rec = (const nfc_raw_frame *)(buf + R.F.at_fr[t]) + fb;                        \
+        rb = buf + R.F.at_bytes[t] + bb;                                               \
+        rp = buf + R.F.at_par[t] + bb;                                                 \
+        room = R.F.total_bytes[t] - bb;                                                \
+    }
+    NFC_STREAM_PART(0, nfr0, rec0, rb0, rp0, room0)
+    NFC_STREAM_PART(1, nfr1, rec1, rb1, rp1, room1)
+#undef NFC_STREAM_PART
+    const uint64_t c0 = tab[0 * T + k] + tab[1 * T + k], b0 = tab[2 * T + k] + tab[3 * T + k];
+    uint64_t *cmd_off = (uint64_t *)(buf + L.at[SEC_CMD_OFF]), *cbyte_off = (uint64_t *)(buf + L.at[SEC_CBYTE_OFF]);
+    cmd_off[k] = c0;
+    cbyte_off[k] = b0;
+    if (k == K - 1u) {
+        cmd_off[K] = tab[0 * T + K] + tab[1 * T + K];
+        cbyte_off[K] = tab[2 * T + K] + tab[3 * T + K];
+    }
+    fsmd::Machine M;
+    fsmd::load_machine(M, A.state, K, k);
+    const skeys::DeviceTable keys = {A.sector_keys, K, k};
+    {
+        const uint32_t *c = R.counts + (size_t)k * R.cnt_words;
+        if (c[R.cnt_pk0] > R.cap_packets || c[R.cnt_pk0 + 1] > R.cap_packets || c[R.cnt_bits0] > R.cap_bits || c[R.cnt_bits0 + 1] > R.cap_bits)
+            M.flags |= NFC_FSM_LOST;
+    }
+    // the stream's card, if it has one, and its emulator
+    const bool present = E.params[(size_t)EP_PRESENT * K + k] != 0;
+    const int role = (int)E.params[(size_t)EP_ROLE * K + k];
+    const uint32_t n_rands = E.params[(size_t)EP_N_RANDS * K + k];
+    const emu::DevCard C = {E.mem, E.rands, K, k, n_rands < emu::MAX_RANDS ? n_rands : emu::MAX_RANDS, (int32_t)E.params[(size_t)EP_TAG_TYPE * K + k],
+                            (int32_t)E.params[(size_t)EP_MODE * K + k]};
+    emu::State S;
+    emu::load_state(S, E.state, K, k);
+    uint32_t *__restrict__ out_cmd = (uint32_t *)(buf + L.at[SEC_CMD]);
+    uint32_t *__restrict__ out_src = (uint32_t *)(buf + L.at[SEC_SRC]);
+    uint8_t *__restrict__ out_data = buf + L.at[SEC_DATA];
+    uint16_t *__restrict__ out_enc = (uint16_t *)(buf + L.at[SEC_ENC]);
+    nfc_emu_answer *__restrict__ ans = (nfc_emu_answer *)(buf + E.at[ESEC_REC]);
+    uint8_t *__restrict__ scratch = buf + E.at[ESEC_SCRATCH] + (size_t)k * emu::SCRATCH_BYTES;
+    uint32_t i0 = 0, i1 = 0, run = 0, na = 0;
+    while (i0 < nfr0 || i1 < nfr1) {
+        int t;
+        if (i1 >= nfr1) t = 0;
+        else if (i0 >= nfr0) t = 1;
+        else t = rec0[i0].idx <= rec1[i1].idx ? 0 : 1;
+        const uint32_t i = t ? i1 : i0;
+        const uint4 *q = (const uint4 *)(t ? rec1 + i1 : rec0 + i0);
+        const uint4 q0 = q[0], q1 = q[1];
+        uint32_t byte_off = q0.z, n = q1.x, flags = q1.y;
+        const uint8_t *rbt = t ? rb1 : rb0, *rpt = t ? rp1 : rp0;
+        const uint64_t roomt = t ? room1 : room0;
+        const uint64_t c = c0 + i0 + i1;
+        if (c >= L.total_cmds) break;
+        if ((uint64_t)byte_off + n > roomt || b0 + run + n > L.total_bytes) flags = NFC_RAW_CUT;
+        if (flags & NFC_RAW_CUT) n = 0;
+        const fsmd::Rec r = fsmd::process_frame(M, t, flags, n, rbt + byte_off, rpt + byte_off, out_data + b0 + run, out_enc + b0 + run, keys);
+        uint32_t *w = out_cmd + c * (sizeof(nfc_frame) / 4);
+        w[0] = (uint32_t)r.cmd;
+        w[1] = (uint32_t)r.type;
+        w[2] = run;
+        w[3] = r.n_bytes | r.n_header << 16;
+        w[4] = r.n_extra | r.n_crc << 16;
+        w[5] = r.flags;
+        w[6] = r.n_enc;
+        out_src[c] = (uint32_t)t << 31 | i;
+        if (present && c0 + na < L.total_cmds) {   // (an answer per command at the most: c0 + na <= c)
+            const uint64_t slot = (c0 + na) * ANS_BYTES;
+            uint8_t *air = buf + E.at[ESEC_AIR] + slot, *par = buf + E.at[ESEC_PAR] + slot, *plain = buf + E.at[ESEC_PLAIN] + slot;
+            emu::Ans a;
+            const int cmd = emu::replay_step(S, C, role, M, keys, r, out_data + b0 + run, a, air, par, scratch);
+            if (cmd >= 0) {
+                bool differs = false;
+                for (uint32_t j = 0; j < ANS_BYTES; j++) {
+                    const uint32_t pb = j < a.n ? a.B.at(j) : 0u;
+                    plain[j] = (uint8_t)pb;
+                    differs = differs || pb != air[j];
+                }
+                nfc_emu_answer rec;
+                rec.src = (uint32_t)(i0 + i1), rec.cmd = cmd, rec.byte_off = na * ANS_BYTES, rec.n_bytes = (uint16_t)a.n;
+                rec.n_bits = (uint16_t)((cmd == fsmd::C_REQA || cmd == fsmd::C_WUPA) ? 7u : 9u * a.n);
+                rec.flags = differs ? NFC_EMU_FRAME_ENCRYPTED : 0u, rec.reserved = 0;
+                ans[c0 + na] = rec;
+                na++;
+            }
+        }
+        run += n;
+        if (t) i1++;
+        else i0++;
+    }
+    ((uint32_t *)(buf + E.at[ESEC_N]))[k] = na;
+    ((uint32_t *)(buf + L.at[SEC_FLAGS]))[k] = M.flags;
+    fsmd::store_machine(M, A.state, K, k);
+    if (present) emu::store_state(S, E.state, K, k);
 }
 
 __global__ __launch_bounds__(256) void k_commands_init(uint32_t *state, uint32_t K, uint32_t k0, uint32_t k1) {

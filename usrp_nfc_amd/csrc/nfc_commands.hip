@@ -26,6 +26,11 @@ void launch(const Args &A, hipStream_t stream, hipEvent_t e0, hipEvent_t e1) {
     if (e0 || e1) NFC_LAUNCH_EXT(k_multi_commands, grid, block, 0, stream, e0, e1, 0, A);
     else NFC_LAUNCH(k_multi_commands, grid, block, 0, stream, A);
 }
+void launch_emu(const Args &A, const EmuArgs &E, hipStream_t stream, hipEvent_t e0, hipEvent_t e1) {
+    const dim3 grid((A.R.K + THREADS - 1) / THREADS), block(THREADS);
+    if (e0 || e1) NFC_LAUNCH_EXT(k_multi_commands_emu, grid, block, 0, stream, e0, e1, 0, A, E);
+    else NFC_LAUNCH(k_multi_commands_emu, grid, block, 0, stream, A, E);
+}
 void launch_init(uint32_t *state, uint32_t K, uint32_t k0, uint32_t k1, hipStream_t stream) {
     if (k1 <= k0) return;
     NFC_LAUNCH(k_commands_init, dim3((k1 - k0 + 255) / 256), dim3(256), 0, stream, state, K, k0, k1);

@@ -110,6 +110,15 @@ struct nfc_multi {
     // nfc_multi_set_sector_keys on, never before -- a null d_keys is "every table empty" to the kernel and to the calls
     DevBuf d_keys, d_keys_blob;
     PinBuf h_keys_blob;
+    // emulation (multi_commands.hip.h: EmuArgs): the cards and the emulators' state, there from the first nfc_multi_emulate on, never
+    // before; has_card mirrors params' PRESENT word, n_cards counts it: while it is 0 a tracked push launches k_multi_commands as ever
+    DevBuf d_emu;
+    size_t emu_mem = 0, emu_rands = 0, emu_params = 0, emu_state = 0;   // offsets into d_emu
+    std::vector<uint8_t> has_card;
+    uint32_t n_cards = 0;
+    bool cmd_emulated = false;   // the last launched push ran the emulating form: its buffer holds the answers' sections
+    commands::EmuArgs cmd_emu;
+    nfc_multi_answers aout;
     Packed cmd;
     size_t cmd_bytes = 0;
     CmdState cmd_state = CMD_NONE;
@@ -385,6 +394,40 @@ int ensure_fsm(nfc_multi *m, const char *fn) {
     return launch_ok(m);
 }
 
+// ---- emulation ----
+// the emulators of streams [k0, k1) to nfc_emu_state_init's state: one strided copy of [EW_WORDS][k1 - k0] words, and a wait (the source is the caller's)
+int emu_state_init_range(nfc_multi *m, uint32_t k0, uint32_t k1) {
+    if (k1 <= k0) return NFC_OK;
+    emu::State S;
+    emu::state_init(S);
+    const size_t n = k1 - k0;
+    std::vector<uint32_t> img((size_t)emu::EW_WORDS * n);
+    for (size_t k = 0; k < n; k++) emu::store_state(S, img.data(), n, k);
+    uint32_t *state = (uint32_t *)(m->d_emu.as<uint8_t>() + m->emu_state);
+    MCHK(m, hipMemcpy2DAsync(state + k0, (size_t)m->K * 4, img.data(), n * 4, n * 4, emu::EW_WORDS, hipMemcpyHostToDevice, m->st));
+    MCHK(m, hipStreamSynchronize(m->st));
+    return NFC_OK;
+}
+// the cards' buffer, zeroed (no stream has a card), and the emulators' state, at the first nfc_multi_emulate of a context
+int ensure_emu(nfc_multi *m, const char *fn) {
+    if (m->d_emu.p) return NFC_OK;
+    const size_t K = m->K;
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t o_rands = up(K * emu::CLASSIC_BYTES), o_params = o_rands + up(K * emu::MAX_RANDS * 4), o_state = o_params + up(K * commands::EP_WORDS * 4),
+                 bytes = o_state + up(K * emu::EW_WORDS * 4);
+    DevBuf fresh;
+    if (fresh.ensure(bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return mfail(m, NFC_ERR_NOMEM, "%s: no device memory for %zu bytes", fn, bytes);
+    }
+    MCHK(m, hipMemsetAsync(fresh.p, 0, fresh.cap, m->st));
+    std::swap(m->d_emu, fresh);
+    m->emu_mem = 0, m->emu_rands = o_rands, m->emu_params = o_params, m->emu_state = o_state;
+    m->has_card.assign(K, 0);
+    m->n_cards = 0;
+    return emu_state_init_range(m, 0, m->K);
+}
+
 // the three launches of a tracked push, behind the push's own kernel and its counts; no host wait
 int enqueue_commands(nfc_multi *m) {
     m->cmd_state = nfc_multi::CMD_NONE;
@@ -406,6 +449,18 @@ int enqueue_commands(nfc_multi *m) {
     const size_t sizes[commands::SEC_COUNT] = {T * 8, T * 8, (size_t)K * 4, (size_t)L.total_cmds * sizeof(nfc_frame), (size_t)L.total_cmds * 4,
                                                (size_t)L.total_bytes, (size_t)L.total_bytes * 2};
     for (int s = 0; s < commands::SEC_COUNT; s++) S.place(L.at[s], L.end[s], sizes[s]);
+    const bool emulating = m->n_cards > 0;
+    commands::EmuArgs E;
+    memset(&E, 0, sizeof E);
+    if (emulating) {   // the answers behind the commands: at most one per command and 18 bytes each (READT is the longest), and a lane's scratch
+        const size_t esizes[commands::ESEC_COUNT] = {(size_t)K * 4, (size_t)L.total_cmds * sizeof(nfc_emu_answer), (size_t)L.total_cmds * commands::ANS_BYTES,
+                                                     (size_t)L.total_cmds * commands::ANS_BYTES, (size_t)L.total_cmds * commands::ANS_BYTES,
+                                                     (size_t)K * emu::SCRATCH_BYTES};
+        for (int s = 0; s < commands::ESEC_COUNT; s++) S.place(E.at[s], E.end[s], esizes[s]);
+        uint8_t *e = m->d_emu.as<uint8_t>();
+        E.mem = (const uint32_t *)(e + m->emu_mem), E.rands = (const uint32_t *)(e + m->emu_rands), E.params = (const uint32_t *)(e + m->emu_params);
+        E.state = (uint32_t *)(e + m->emu_state);
+    }
     const size_t bytes = S.at;
     if (int rc = grow_packed(m, m->cmd, bytes, "nfc_multi_push")) return rc;
     commands::Args A;
@@ -415,7 +470,10 @@ int enqueue_commands(nfc_multi *m) {
     A.sector_keys = m->d_keys.as<uint32_t>();
     const bool timed = m->timing != 0;
     frames::launch_multi(A.R, m->st, timed ? m->evc[0] : nullptr, timed ? m->evc[1] : nullptr);
-    commands::launch(A, m->st, timed ? m->evc[2] : nullptr, timed ? m->evc[3] : nullptr);
+    if (emulating) commands::launch_emu(A, E, m->st, timed ? m->evc[2] : nullptr, timed ? m->evc[3] : nullptr);
+    else commands::launch(A, m->st, timed ? m->evc[2] : nullptr, timed ? m->evc[3] : nullptr);
+    m->cmd_emulated = emulating;
+    m->cmd_emu = E;
     m->cmd.guards = std::move(S.guards);
     m->cmd_timed = timed;
     m->cmd_bytes = bytes;
@@ -1060,6 +1118,8 @@ int nfc_multi_reset(nfc_multi *m, int64_t stream) {
     NFC_LAUNCH(k_multi_reset, dim3((unsigned)std::min<size_t>(1024, (work + 255) / 256)), dim3(256), 0, m->st, m->A.S, m->K, k0, k1, m->L, m->A.O.counts);
     if (m->d_fsm.p) commands::launch_init(m->d_fsm.as<uint32_t>(), m->K, k0, k1, m->st);   // the machines too, keys included, as nfc_fsm_reset
     if (m->d_keys.p) commands::launch_set_table(m->d_keys.as<uint32_t>(), m->K, k0, k1, nullptr, m->st);   // ... and their sector keys
+    if (m->d_emu.p)   // ... and the emulators: nfc_emu_state_init's state (the cards stay)
+        if (int rc = emu_state_init_range(m, k0, k1)) return rc;
     m->cmd_state = nfc_multi::CMD_NONE;
     m->cmd_fetched = false;
     if (int rc = launch_ok(m)) return rc;
@@ -1268,6 +1328,117 @@ int nfc_multi_fetch_commands(nfc_multi *m, nfc_multi_commands *out) {
     frames_view(m, h, m->cmd_frlay, base, stored, c.raw);
     m->cmd_fetched = true;
     if (out) *out = c;
+    return NFC_OK;
+}
+
+// ---- emulation: a stream that answers (multi_commands.hip.h: k_multi_commands_emu) ----
+int nfc_multi_emulate(nfc_multi *m, int64_t stream, const nfc_emu_card *card) {
+    if (!m) return NFC_ERR_ARG;
+    LaunchScope scope(&m->launch_err);
+    uint32_t k0, k1;
+    if (int rc = stream_range(m, stream, k0, k1)) return rc;
+    if (card) {
+        if (card->role != NFC_EMU_TAG && card->role != NFC_EMU_READER) return mfail(m, NFC_ERR_ARG, "card.role must be NFC_EMU_TAG or NFC_EMU_READER");
+        if (const char *bad = emu::card_fault(*card, card->role)) return mfail(m, NFC_ERR_ARG, "card%s", bad);
+    }
+    if (hipSetDevice(m->P.device) != hipSuccess) return mfail(m, NFC_ERR_DEVICE, "hipSetDevice failed");
+    if (!card && !m->d_emu.p) return NFC_OK;   // nothing to take away, and nothing is allocated for it
+    if (int rc = ensure_fsm(m, "nfc_multi_emulate")) return rc;
+    if (int rc = ensure_emu(m, "nfc_multi_emulate")) return rc;
+    MCHK(m, hipStreamSynchronize(m->st));
+    // one stream's column of each array, as the host builds it: 64 units of memory, 64 nonces, the parameters
+    std::vector<uint32_t> mem(emu::CLASSIC_BYTES / 4, 0), rands(emu::MAX_RANDS, 0), par(commands::EP_WORDS, 0);
+    if (card) {
+        const emu::HostCard H = {card->mem, card->rands, card->n_rands, card->role == NFC_EMU_TAG ? card->tag_type : -1, card->mode};
+        if (card->role == NFC_EMU_TAG)
+            for (uint32_t i = 0; i < card->mem_len / 4; i++) mem[i] = H.mem_word(i);
+        for (uint32_t i = 0; i < card->n_rands; i++) rands[i] = H.rand(i);
+        par[commands::EP_PRESENT] = 1, par[commands::EP_ROLE] = (uint32_t)card->role, par[commands::EP_TAG_TYPE] = (uint32_t)H.tag_type;
+        par[commands::EP_MODE] = (uint32_t)card->mode, par[commands::EP_N_RANDS] = card->n_rands;
+    }
+    uint8_t *e = m->d_emu.as<uint8_t>();
+    const size_t K = m->K;
+    for (uint32_t k = k0; k < k1; k++) {
+        MCHK(m, hipMemcpy2DAsync(e + m->emu_mem + (size_t)k * 16, K * 16, mem.data(), 16, 16, emu::CLASSIC_BYTES / 16, hipMemcpyHostToDevice, m->st));
+        MCHK(m, hipMemcpy2DAsync(e + m->emu_rands + (size_t)k * 4, K * 4, rands.data(), 4, 4, emu::MAX_RANDS, hipMemcpyHostToDevice, m->st));
+        MCHK(m, hipMemcpy2DAsync(e + m->emu_params + (size_t)k * 4, K * 4, par.data(), 4, 4, commands::EP_WORDS, hipMemcpyHostToDevice, m->st));
+        m->n_cards += (card ? 1u : 0u) - (uint32_t)m->has_card[k];
+        m->has_card[k] = card ? 1 : 0;
+    }
+    MCHK(m, hipStreamSynchronize(m->st));   // (the sources are this call's)
+    if (int rc = emu_state_init_range(m, k0, k1)) return rc;   // a new card starts from the initial state
+    if (card) m->track = true;   // answering implies tracking
+    return NFC_OK;
+}
+
+static int emu_state_io(nfc_multi *m, uint32_t stream, int set, uint32_t *words) {
+    uint32_t *state = (uint32_t *)(m->d_emu.as<uint8_t>() + m->emu_state) + stream;
+    if (set) MCHK(m, hipMemcpy2DAsync(state, (size_t)m->K * 4, words, 4, 4, emu::EW_WORDS, hipMemcpyHostToDevice, m->st));
+    else MCHK(m, hipMemcpy2DAsync(words, 4, state, (size_t)m->K * 4, 4, emu::EW_WORDS, hipMemcpyDeviceToHost, m->st));
+    MCHK(m, hipStreamSynchronize(m->st));
+    return NFC_OK;
+}
+
+int nfc_multi_get_emu_state(nfc_multi *m, uint32_t stream, nfc_emu_state *st) {
+    if (!m) return NFC_ERR_ARG;
+    LaunchScope scope(&m->launch_err);
+    if (stream >= m->K) return mfail(m, NFC_ERR_ARG, "stream %u out of range (n_streams %u)", stream, m->K);
+    if (!st) return mfail(m, NFC_ERR_ARG, "st is null");
+    emu::State S;
+    emu::state_init(S);
+    if (m->d_emu.p) {
+        if (hipSetDevice(m->P.device) != hipSuccess) return mfail(m, NFC_ERR_DEVICE, "hipSetDevice failed");
+        uint32_t words[emu::EW_WORDS];
+        if (int rc = emu_state_io(m, stream, 0, words)) return rc;
+        emu::load_state(S, words, 1, 0);
+    }
+    memset(st, 0, sizeof *st);
+    emu::state_to_public(S, *st);
+    return NFC_OK;
+}
+
+int nfc_multi_set_emu_state(nfc_multi *m, uint32_t stream, const nfc_emu_state *st) {
+    if (!m) return NFC_ERR_ARG;
+    LaunchScope scope(&m->launch_err);
+    if (stream >= m->K) return mfail(m, NFC_ERR_ARG, "stream %u out of range (n_streams %u)", stream, m->K);
+    if (!st) return mfail(m, NFC_ERR_ARG, "st is null");
+    if (const char *bad = emu::state_fault(*st)) return mfail(m, NFC_ERR_ARG, "st: %s", bad);
+    if (hipSetDevice(m->P.device) != hipSuccess) return mfail(m, NFC_ERR_DEVICE, "hipSetDevice failed");
+    if (int rc = ensure_fsm(m, "nfc_multi_set_emu_state")) return rc;
+    if (int rc = ensure_emu(m, "nfc_multi_set_emu_state")) return rc;
+    emu::State S;
+    emu::state_from_public(S, *st);
+    uint32_t words[emu::EW_WORDS];
+    emu::store_state(S, words, 1, 0);
+    return emu_state_io(m, stream, 1, words);
+}
+
+// The answers of the last push: sections of the buffer nfc_multi_fetch_commands copies -- the SAME single copy; when the commands were
+// fetched since the push, no device call at all.
+int nfc_multi_fetch_answers(nfc_multi *m, nfc_multi_answers *out) {
+    if (!m) return NFC_ERR_ARG;
+    if (!out) return mfail(m, NFC_ERR_ARG, "out is null");
+    nfc_multi_commands c;
+    if (int rc = nfc_multi_fetch_commands(m, &c)) return rc;
+    nfc_multi_answers &a = m->aout;
+    memset(&a, 0, sizeof a);
+    a.n_streams = m->K;
+    a.cmd_off = c.cmd_off;
+    if (m->cmd_state == nfc_multi::CMD_LAUNCHED && m->cmd_emulated) {
+        const uint8_t *h = m->cmd.h.as<uint8_t>();
+        const commands::EmuArgs &E = m->cmd_emu;
+        a.emulated = 1;
+        a.ans_n = (const uint32_t *)(h + E.at[commands::ESEC_N]);
+        a.ans = (const nfc_emu_answer *)(h + E.at[commands::ESEC_REC]);
+        a.plain = h + E.at[commands::ESEC_PLAIN], a.air = h + E.at[commands::ESEC_AIR], a.par = h + E.at[commands::ESEC_PAR];
+        for (uint32_t k = 0; k < m->K; k++) {
+            if ((uint64_t)a.ans_n[k] > c.cmd_off[k + 1] - c.cmd_off[k])
+                return mfail(m, NFC_ERR_INTERNAL, "nfc_multi_fetch_answers: stream %u has %u answers to %llu commands", k, a.ans_n[k],
+                             (unsigned long long)(c.cmd_off[k + 1] - c.cmd_off[k]));
+            a.n_answers += a.ans_n[k];
+        }
+    }
+    *out = a;
     return NFC_OK;
 }
 

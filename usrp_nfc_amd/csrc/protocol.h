@@ -72,56 +72,17 @@ inline void fsm_process(nfc_fsm &F, const uint8_t *bits, size_t n_bits, int type
     fsm_process_frame(F, type, flags, n, b, p, out, bytes_out, enc_out);
 }
 
-// fsm.process_outgoing (fsm.py:68-112): what an EMULATOR is about to send.  The machine follows the frame as if it had been heard --
-// tag type from an ATQA, the command in flight -- and, while a MIFARE Classic session is up, encrypts it: the frame's bits (parity
-// bits included, as the encoders take them) in, the bits to put on the air out.  Returns 1 when the tag is an Ultralight: the
-// reference then runs the frame through process_bits "to update state" (fsm.py:71-72) -- the caller does, with its callback.
+// fsm.process_outgoing (fsm.py:68-112): what an EMULATOR is about to send, the frame's bits (parity bits included, as the encoders take
+// them) in, the bits to put on the air out: fsmd::outgoing over the two bit lists, the reference's hook (not NFC_EMU_CARD's).  Returns 1
+// when the tag is an Ultralight: the reference then runs the frame through process_bits "to update state" (fsm.py:71-72) -- the caller
+// does, with its callback.
+struct BitListOut {
+    uint8_t *o;
+    void operator()(size_t k, uint32_t v) { o[k] = (uint8_t)(v & 1u); }
+};
 inline int fsm_process_outgoing(nfc_fsm &M, const uint8_t *bits, size_t n, int cmd, uint8_t *out) {
-    using namespace fsmd;
-    if (M.tag_type == 0) return 1;
-    for (size_t i = 0; i < n; i++) out[i] = bits[i] & 1;
-    if (M.tag_type == 1) {   // CLASSIC1K (fsm.py:73-99)
-        M.cur_cmd = cmd;
-        const skeys::HostTable tab = {&M.table};
-        if ((cmd == C_AUTHA || cmd == C_AUTHB) && n >= 17) {
-            // the sector's key from the table, as a heard AUTH chooses it; with no slot present the choice stays the caller's, as ever
-            uint32_t block = 0;
-            for (int k = 0; k < 8; k++) block |= (uint32_t)(bits[9 + k] & 1) << k;
-            const int c = skeys::choose(tab, cmd == C_AUTHB, block);
-            if (c >= 2) M.cur_key = c;
-        }
-        if (M.encrypted && cmd != C_RANDTA) {
-            // ({nr}{ar}: the reader's own nonce, the first half, feeds the register as it is encrypted)
-            const size_t ll = cmd == C_RANDRB ? n / 2 : 0;
-            crypt_bits(M.st, bits, ll, out, true);
-            crypt_bits(M.st, bits + ll, n - ll, out + ll, false);
-        } else if (cmd == C_RANDTA) {
-            // the tag's nonce: a fresh register keyed for the sector takes uid ^ nonce -- the UID bits there are, the nonce bits there are
-            // (fsm.py:86-97) -- and becomes the session; under a session that is already up (nested authentication) the OLD register
-            // encrypts what goes on the air.  Where the reference raises it has installed nothing: the session stays as it was.
-            const uint64_t st = M.st;
-            const uint32_t ar = M.ar, at = M.at;
-            if (M.encrypted) {
-                uint64_t old = st;
-                crypt_bits(old, bits, n, out, false);
-            }
-            M.st = skeys::resolve(tab, M.cur_key, M.key_a, M.key_b);
-            M.ar = M.at = 0;
-            // (the nonce's j-th bit: the frame's without its ninth bits)
-            const int session = set_tag_plain(M, n - n / 9, [&](size_t j) { return (uint32_t)(bits[j + j / 8] & 1); });
-            if (session) M.encrypted = session;
-            else M.st = st, M.ar = ar, M.at = at;
-        }
-        return 0;
-    }
-    switch (cmd) {   // no tag type yet: an ATQA sets it (fsm.py:101-108)
-    case C_ATQAUL: M.tag_type = 0; break;
-    case C_ATQA1K: M.tag_type = 1; break;
-    case C_ATQA4K: M.tag_type = 2; break;
-    case C_ATQADS: M.tag_type = 3; break;
-    default: break;
-    }
-    return 0;
+    BitListOut o = {out};
+    return fsmd::outgoing(M, n, cmd, [bits](size_t k) { return (uint32_t)bits[k]; }, o, skeys::HostTable{&M.table}, false);
 }
 
 }  // namespace nfc

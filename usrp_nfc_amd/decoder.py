@@ -99,7 +99,7 @@ def _per_source_keys(keys, n):
 
 
 def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None, keep=None, device=0, push_stats=None, frames=False, commands=False,
-                keys=None, nested=False, **sink_kwargs):
+                keys=None, nested=False, emulate=None, **sink_kwargs):
     """Decode many recordings at once: every source is a stream of one api.NfcMultiContext, a GPU lane each, one kernel launch per
     round of pieces (include/nfc_amd.h: nfc_multi) -- what a loop of ``decoder(src=s).run()`` does capture by capture.
 
@@ -124,6 +124,10 @@ def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None,
     gets ``recovered_keys``: (key_type, block) -> six key bytes.  The cost is the doubled push.
     nested=True (with keys='recover'): the nested authentications are searched too (usrp_nfc_amd.keys.recover_streams), and
     ``recovered_keys`` holds every sector key whose AUTH command could be decrypted and labelled.
+    emulate: a card per source (emulate.tag_card / reader_card; a list, None for a source that only listens; one card: for all) --
+    every source's stream ANSWERS what it hears, on the GPU in the launch that decodes its commands (api.NfcMultiContext.emulate), and
+    after every push each source's ``(records, plain, air, par)`` (NfcMultiAnswers.answers_of) is appended to its background's ``answers``.
+    It implies the tracking of commands=True; give reader=/tag= so that a source decodes only the side it hears.
     With keys='recover' every stream gets ``first_keys(...)`` as its two keys AND ``keys.sector_table(recovered_keys)`` as its table
     (DESIGN.md 8j), so a card whose sectors have different keys is decrypted through every authentication whose key was found.  Two
     blocks of one sector with different keys: the lower block's is used and the others are the background's ``key_conflicts``, a dict
@@ -144,6 +148,12 @@ def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None,
     if frames:
         for b in backs:
             b.frames = []
+    if emulate is not None:   # a card per source (an emulate.Card, or None for a source that only listens), or one card for all
+        cards = list(emulate) if isinstance(emulate, (list, tuple)) else [emulate] * len(loaded)
+        if len(cards) != len(loaded):
+            raise ValueError('decode_many: emulate is one card, or a list with one entry per source')
+        for b in backs:
+            b.answers = []
     if commands:
         for b in backs:
             b.commands = []
@@ -201,6 +211,8 @@ def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None,
                             for k in range(len(group)):
                                 if tables[k] is not None:
                                     m.set_sector_keys(tables[k], stream=k)
+                if emulate is not None:   # (after the untracked recovery pass, which must not answer; implies tracking)
+                    m.emulate(cards[g0:g0 + len(group)])
                 done = numpy.zeros(len(group), numpy.int64)
                 while True:
                     n = numpy.minimum(lens - done, piece)
@@ -219,6 +231,10 @@ def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None,
                         cm = m.fetch_commands()
                         for k in numpy.nonzero(n)[0]:
                             backs[g0 + int(k)].commands.append(cm.commands_of(int(k)))
+                    if emulate is not None:
+                        an = m.fetch_answers()
+                        for k in numpy.nonzero(n)[0]:
+                            backs[g0 + int(k)].answers.append(an.answers_of(int(k)))
                     if push_stats is not None:
                         st = m.stats()
                         push_stats.append((int(st.n_fetches), int(st.n_reads_device)))

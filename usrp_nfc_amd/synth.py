@@ -179,6 +179,13 @@ def txn_frames(txn=ULTRALIGHT_TXN, directions=(READER, TAG)):
     return [(d, frame_bits(data, sb)) for d, _, data, sb in txn if d in directions]
 
 
+def transaction_frames(transcript):
+    """The frames of an emulated transaction (emulate.Transcript: one pair of emulate.pairs_host / pairs_device) as the
+    (direction, on-air data bits) list modulation_profile takes, ciphertext and its ninth bits as they went out."""
+    from . import emulate
+    return emulate.synth_frames(transcript)
+
+
 def iq_from_profile(m, amp=0.5, phase=0.3, sigma=0.002, seed=SEED):
     """m[n] -> interleaved float32 I,Q (len 2N)."""
     rng = np.random.Generator(np.random.PCG64(seed))
