@@ -51,6 +51,7 @@ extern "C" {
 /* (still 4, only new names: nfc_emu_state, nfc_emu_card, nfc_emu_frame, nfc_emu_pair_result, nfc_emu_config, NFC_EMU_*, nfc_emu_state_init,
  *  nfc_emu_last_error, nfc_host_emu_step, nfc_host_emulate, nfc_emu_answer, nfc_host_emulate_pairs, nfc_emulate_pairs_device,
  *  nfc_multi_emulate, nfc_multi_fetch_answers, nfc_multi_answers, nfc_multi_get_emu_state, nfc_multi_set_emu_state) */
+/* (still 4, only new names: nfc_air_frame, nfc_air_config, nfc_host_air_render, nfc_air_render_device) */
 #define NFC_AMD_ABI_VERSION 4
 
 typedef enum {
@@ -996,6 +997,63 @@ int nfc_host_emulate_pairs(const nfc_emu_card *tags, const nfc_emu_card *readers
 int nfc_emulate_pairs_device(int device, const nfc_emu_card *tags, const nfc_emu_card *readers, size_t n, const nfc_emu_config *cfg,
                              nfc_emu_pair_result *results, nfc_emu_frame *frames, uint8_t *plain, uint8_t *air, uint8_t *par,
                              float *kernel_ms /* NULL, or the kernel's duration by HIP events */);
+
+/* ---- the air interface: K ragged lists of on-air frames -> K IQ captures in one device buffer (csrc/air.hip.h) ----------
+ * What an eavesdropper's radio records of a transaction, in any of the four IQ input kinds, laid out for nfc_multi_push_device: the
+ * stage between nfc_emulate_pairs_device and a multi-stream context.  The yardstick is synth.py -- with sigma 0 the bytes are those of
+ * iq_from_profile over modulation_profile, through quantise_sc16 / _sc8 / _cu8 for the quantised kinds.
+ * A STREAM's capture: per frame idle_before unmodulated samples, then the frame's runs; `tail` unmodulated samples behind the last frame.
+ * A reader frame (type 1) has the runs of synth.miller_pulses, a tag frame (type 0) those of synth.manchester_pulses -- the lists
+ * nfc_tx_encode gives -- and a run of d us has int(d * rate_msps) samples (NOT nfc_tx_sample_count's dur * samp_rate / 1e6).
+ * A SAMPLE is I = fl(fl(carrier_i * m) + nI), Q = fl(fl(carrier_q * m) + nQ) in float32 without contraction, m = 1 when idle, the level
+ * in a reader frame (0 in a pause), fl(1 + fl(depth) * level) in a tag frame.  The noise is counter-based: n = fl((float)(u0 + u1 + u2 +
+ * u3 - 131070) * unit), unit = (float)(sigma / sqrt((65536^2 - 1) / 3)), u0 .. u3 the four 16-bit fields of ONE 64-bit hash of (seed,
+ * the stream's seed, the sample's index in its stream, the component): SplitMix64 in counter form, stated in csrc/air.hip.h.  A
+ * sample depends on nothing else -- not on K, on where the stream lies or on how the kernel tiles it.  sigma == 0 adds nothing.
+ * The quantised kinds: rint in double of x * full_scale (NFC_IN_IQ_U8: of 127.5 + x * full_scale), clipped to the type's range, I first.
+ * THE LAYOUT.  Streams are packed in stream order; first_sample[k] is rounded up to align_samples (a power of two, at most 2^20), and
+ * the padding between two streams is idle carrier without noise: no byte of [0, first_sample[K-1] + n_samples[K-1]) is left unwritten.
+ * A stream without frames is `tail` idle samples.
+ * A frame's bits come from air / par, in the form nfc_raw_frame's bytes / par and an nfc_emu_frame transcript have, at byte_base[k] +
+ * byte_off of stream k; frames[frame_off[k] .. frame_off[k+1]) are stream k's.  n_bits 1 .. 8: a short frame from the low bits of its
+ * first byte; else a multiple of 9 up to 2304; 0: only idle_before is rendered.
+ * nfc_host_air_render is the CPU twin of the kernels behind nfc_air_render_device: the same bytes.  With out == NULL it only fills
+ * first_sample and n_samples: the sizing call.  The device call checks every argument before the device is touched; dev_out is device
+ * memory, 16-byte aligned, of cap_samples samples; kernel_ms: NULL, or TWO floats, the layout kernels' and the render kernel's
+ * duration by HIP events.  No CPU fallback: without a GPU it fails with NFC_ERR_DEVICE.
+ * ERRORS are NFC_ERR_ARG with the argument's name in the message nfc_last_error gives for a NULL context: an out_kind that is no IQ
+ * kind, an align_samples that is no power of two, a bad n_bits, a frame whose bytes leave its stream's part of air / par, a non-zero
+ * flags or reserved word, K above 65 536, a type above 1, a rate_msps outside (0, 1000], an idle_before, tail or stream above 2^30
+ * samples.  A layout that needs more than cap_samples renders nothing, fills first_sample and n_samples with the true need and is
+ * NFC_ERR_ARG naming cap_samples, as nfc_tx_render_device's.  A guard word behind a device section the call allocates that was
+ * overwritten: NFC_ERR_INTERNAL. */
+typedef struct nfc_air_frame {          /* 16 bytes */
+    uint8_t type;                       /* 0 tag -> reader, 1 reader -> tag */
+    uint8_t flags;                      /* 0 */
+    uint16_t n_bits;
+    uint32_t byte_off;                  /* in the stream's part of air / par */
+    uint32_t idle_before;               /* unmodulated samples in front of the frame */
+    uint32_t reserved;
+} nfc_air_frame;
+typedef struct nfc_air_config {         /* 72 bytes */
+    double rate_msps;                   /* samples per microsecond, used as it is */
+    float carrier_i, carrier_q;         /* float32(amp cos phi), float32(amp sin phi) */
+    float depth;                        /* of the tag's load modulation */
+    float sigma;                        /* of the noise on I and on Q; 0: none */
+    float full_scale;                   /* the quantised kinds: the integer value of 1.0 */
+    uint32_t out_kind;                  /* NFC_IN_IQ_F32, NFC_IN_IQ_I16, NFC_IN_IQ_I8 or NFC_IN_IQ_U8 */
+    uint64_t seed;
+    const uint64_t *stream_seeds;       /* NULL: stream k's seed is k */
+    uint32_t tail;                      /* idle samples behind a stream's last frame */
+    uint32_t align_samples;             /* a power of two: every first_sample[k] is a multiple of it */
+    uint32_t reserved[4];
+} nfc_air_config;
+int nfc_host_air_render(const nfc_air_config *cfg, const nfc_air_frame *frames, const uint32_t *frame_off /* [K + 1] */, const uint8_t *air,
+                        const uint8_t *par, const uint32_t *byte_base /* [K + 1] */, size_t K, void *out, size_t cap_samples,
+                        uint64_t *first_sample /* [K] */, uint32_t *n_samples /* [K] */);
+int nfc_air_render_device(int device, const nfc_air_config *cfg, const nfc_air_frame *frames, const uint32_t *frame_off, const uint8_t *air,
+                          const uint8_t *par, const uint32_t *byte_base, size_t K, void *dev_out, size_t cap_samples, uint64_t *first_sample,
+                          uint32_t *n_samples, float *kernel_ms /* NULL, or two floats */);
 
 /* one stream's boundary state, in the form an nfc_ctx exports and imports it */
 int nfc_multi_get_state(nfc_multi *m, uint32_t stream, nfc_state_header *hdr, float *ring, size_t ring_cap, uint8_t *pending, size_t pending_cap);

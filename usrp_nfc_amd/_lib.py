@@ -122,6 +122,14 @@ class EmuConfig(C.Structure):   # nfc_emu_config
                 ('reserved', C.c_uint32 * 2)]
 
 
+class AirConfig(C.Structure):   # nfc_air_config
+    _fields_ = [('rate_msps', C.c_double), ('carrier_i', C.c_float), ('carrier_q', C.c_float), ('depth', C.c_float), ('sigma', C.c_float),
+                ('full_scale', C.c_float), ('out_kind', C.c_uint32), ('seed', C.c_uint64), ('stream_seeds', C.c_void_p), ('tail', C.c_uint32),
+                ('align_samples', C.c_uint32), ('reserved', C.c_uint32 * 4)]
+
+
+AIR_FRAME_DTYPE = np.dtype([('type', 'u1'), ('flags', 'u1'), ('n_bits', '<u2'), ('byte_off', '<u4'), ('idle_before', '<u4'),
+                            ('reserved', '<u4')])   # nfc_air_frame
 NFC_EMU_TAG, NFC_EMU_READER = 0, 1
 NFC_EMU_REFERENCE, NFC_EMU_CARD = 0, 1
 NFC_EMU_LINK_PLAIN, NFC_EMU_LINK_AIR = 0, 1
@@ -207,7 +215,8 @@ SYMBOLS = ['nfc_abi_version', 'nfc_device_count', 'nfc_create', 'nfc_destroy', '
            'nfc_find_nested_auths', 'nfc_host_nested_candidates', 'nfc_nested_candidates_device', 'nfc_host_recover_nested_keys',
            'nfc_recover_nested_keys_device',
            'nfc_emu_state_init', 'nfc_emu_last_error', 'nfc_host_emu_step', 'nfc_host_emulate', 'nfc_multi_emulate', 'nfc_multi_fetch_answers', 'nfc_multi_get_emu_state',
-           'nfc_multi_set_emu_state', 'nfc_host_emulate_pairs', 'nfc_emulate_pairs_device']
+           'nfc_multi_set_emu_state', 'nfc_host_emulate_pairs', 'nfc_emulate_pairs_device',
+           'nfc_host_air_render', 'nfc_air_render_device']
 
 _libs = {}
 
@@ -359,6 +368,8 @@ def load(path=None):
     L.nfc_multi_set_emu_state.argtypes = [vp, u32, C.POINTER(EmuState)]
     L.nfc_host_emulate_pairs.argtypes = [vp, vp, sz, C.POINTER(EmuConfig), vp, vp, vp, vp, vp]
     L.nfc_emulate_pairs_device.argtypes = [C.c_int, vp, vp, sz, C.POINTER(EmuConfig), vp, vp, vp, vp, vp, C.POINTER(C.c_float)]
+    L.nfc_host_air_render.argtypes = [C.POINTER(AirConfig), vp, vp, vp, vp, vp, sz, vp, sz, vp, vp]
+    L.nfc_air_render_device.argtypes = [C.c_int, C.POINTER(AirConfig), vp, vp, vp, vp, vp, sz, vp, sz, vp, vp, C.POINTER(C.c_float * 2)]
     for name in SYMBOLS:
         getattr(L, name)
     _libs[path] = L

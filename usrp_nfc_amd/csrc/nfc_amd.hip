@@ -407,6 +407,10 @@ int nfc_device_count(void) {
 }
 
 const char *nfc_last_error(const nfc_ctx *ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
+// (C++ linkage, no part of the ABI: a call without a context that lives in another translation unit -- nfc_air.hip -- leaves its message here)
+extern "C++" {
+namespace nfc { void note_call_error(const char *text) { g_create_error = text; } }
+}
 
 int nfc_create(const nfc_params *p, nfc_ctx **out) {
     if (!p || !out) return fail(nullptr, NFC_ERR_ARG, "null argument");

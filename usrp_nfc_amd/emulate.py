@@ -256,6 +256,12 @@ class Transcripts(object):
         """Every output array, for a byte-for-byte comparison of two calls."""
         return self.results, self.frames, self.plain, self.air, self.par
 
+    def render_device(self, **kw):
+        """What an eavesdropper's radio would have recorded of the K transactions, rendered on the GPU into one device buffer
+        (air.render_device, its keywords) -> air.AirCaptures, ready for NfcMultiContext.push_device."""
+        from . import air
+        return air.render_device(self, **kw)
+
 
 def _pairs(call, name, tags, readers, link, rounds, cap_frames, cap_bytes, pair_cap_frames, extra=()):
     tags, readers = list(tags), list(readers)
