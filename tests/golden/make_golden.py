@@ -397,8 +397,22 @@ def corners():
     np.savez_compressed(os.path.join(HERE, 'fx_nonfinite_iq.npz'), **out)
 
 
+def dense_small():
+    """A short DENSE capture for the one-launch stage of short batches (`python3 tests/golden/make_golden.py --dense-small` writes it alone):
+    max_len = 1, so every sample behind the window fill is an entry, and the samples flicker between a LOW, an accepted and a HIGH
+    level from one to the next.  Pushed whole, its first 16 384 samples hold four times the 4 096 entries the entry writer of
+    csrc/small.hip.h lists per round (tests/test_small_stage.py reads the constants and asserts that).  Three levels only: it compresses well."""
+    n = 20000
+    x = np.full(n, 0.25, np.float32)
+    x[600:n - 1500] = np.array([0.01, 0.25, 0.25 * 1.3], np.float32)[np.random.default_rng(2015).integers(0, 3, n - 2100)]
+    res = make_case('fx_dense_small', x, av_window=500, max_len=1)
+    assert len(res[0]) == n - 501, len(res[0])   # (the sample that completes the window reports nothing: transition_sink.py:109-125)
+
+
 if __name__ == '__main__':
     if '--corners' in sys.argv:
         corners()
+    elif '--dense-small' in sys.argv:
+        dense_small()
     else:
         main()
