@@ -35,7 +35,7 @@ struct DevState {
     EdgeCarry ecarry;
     DecCarry dcarry;
     uint8_t totals[TOT_BYTES];
-    uint32_t seq[4];   // seq[0]: the batch the block belongs to, stamped by the batch's first kernel (k_fill): a mirror that
+    uint32_t seq[4];   // seq[0]: the batch the block belongs to, stamped by the batch's window fill (k_fill, or fill_rider behind pass 0): a mirror that
                        // does not carry the current number was not written by this batch's kernels
 };
 
@@ -57,7 +57,7 @@ namespace {
 struct Switches {
     std::optional<std::string> debug_clk;
     std::optional<int> no_small, debug_bad_launch, debug_redo_submitted, debug, trace, trace_alloc, no_submit_ahead, wg, wg_rounds, wg_bulk, wg_rerun, wg_rowbal, wg_nr, wg_per_cu, wg_per_cu_ahead, wg_ex, lean, lean_rounds,
-        lean_waves, edge_prefix, dec_spec, dec_runin, spin_wait, chunk_adapt, chunk_mult;
+        lean_waves, edge_prefix, dec_spec, dec_runin, spin_wait, chunk_adapt, chunk_mult, fill_front;
     std::optional<double> lean_gfac, lean_gmin, eps;
     std::optional<unsigned long> own_prefix_max;
     std::optional<std::pair<int, int>> wg_lone;        // max,div
@@ -74,7 +74,7 @@ inline Switches read_switches() {
         {"NFC_WG_RERUN", &Switches::wg_rerun}, {"NFC_WG_NR", &Switches::wg_nr}, {"NFC_WG_PER_CU", &Switches::wg_per_cu},
         {"NFC_WG_PER_CU_AHEAD", &Switches::wg_per_cu_ahead}, {"NFC_WG_EX", &Switches::wg_ex}, {"NFC_LEAN", &Switches::lean}, {"NFC_LEAN_ROUNDS", &Switches::lean_rounds},
         {"NFC_LEAN_WAVES", &Switches::lean_waves}, {"NFC_EDGE_PREFIX", &Switches::edge_prefix}, {"NFC_DEC_SPEC", &Switches::dec_spec}, {"NFC_DEC_RUNIN", &Switches::dec_runin},
-        {"NFC_SPIN_WAIT", &Switches::spin_wait}, {"NFC_CHUNK_ADAPT", &Switches::chunk_adapt}, {"NFC_CHUNK_MULT", &Switches::chunk_mult}};
+        {"NFC_SPIN_WAIT", &Switches::spin_wait}, {"NFC_CHUNK_ADAPT", &Switches::chunk_adapt}, {"NFC_CHUNK_MULT", &Switches::chunk_mult}, {"NFC_FILL_FRONT", &Switches::fill_front}};
     const struct { const char *name; std::optional<double> Switches::*at; } reals[] = {
         {"NFC_LEAN_GFAC", &Switches::lean_gfac}, {"NFC_LEAN_GMIN", &Switches::lean_gmin}, {"NFC_EPS", &Switches::eps}};
     for (const auto &v : ints)
@@ -166,6 +166,13 @@ struct nfc_ctx {
     DecCarry dirty_dcarry;
     bool cert_pending = false;   // the first certification waits to share a launch with the edge writer (host_stages.h: k_certify_and_write)
     CertLaunch cert;
+    // The window fill of a fresh stream's first batch leaves the head of the batch: pass 0 starts at once (ThrArgs.own_window) and the fill's
+    // work rides with the edge stage's reduce pass, the first launch behind pass 0 (host_stages.h: k_edge_reduce_and_fill).  fill_can_ride:
+    // the batch in work will launch that pass (process_batch); fill_front: never (NFC_FILL_FRONT=1 in the test build); the counters: batches
+    // that took the new order / that were repeated with k_fill in front because their window's sum depends on the order (test build)
+    bool fill_pending = false, fill_can_ride = false, fill_front = false;
+    FillRider fill;
+    uint32_t dbg_fill_rode = 0, dbg_fill_refront = 0;
     // debugging switches, read ONCE for nfc_create (read_switches: an inherited environment must not reach the per-launch path)
     bool dbg_bad_launch = false, dbg_redo_submitted = false, dbg_no_submit_ahead = false, dbg_any = false, dbg_clk = false, dbg_trace = false;
     std::string dbg_clk_path;
@@ -381,7 +388,9 @@ int batch_ok(nfc_ctx *c, bool with_mirror) {
         if (int rc__ = batch_ok((c), (with_mirror))) return rc__;  \
     } while (0)
 
-void launch_fill_kind(nfc_ctx *c, const void *in, uint32_t n, int nchunks, int ring_idx = -1) {
+// ride_cert0 (threshold_span: where pass 0 may start without it): chunk 0's verdict byte -- a fresh stream's fill is then not launched
+// but left pending for the edge stage's reduce pass (true), any other stream's is launched as ever.
+bool launch_fill_kind(nfc_ctx *c, const void *in, uint32_t n, int nchunks, int ring_idx = -1, const uint8_t *ride_cert0 = nullptr) {
     float *ring = c->d_ring[ring_idx < 0 ? c->ring_cur : ring_idx].as<float>();
     Carry *cr = dC(c);
     EdgeCarryInit eci{(int32_t *)dE(c), c->L % c->mx};
@@ -407,8 +416,15 @@ void launch_fill_kind(nfc_ctx *c, const void *in, uint32_t n, int nchunks, int r
         // (a stream that starts here with a whole window in the batch: k_fill's short form)
         fresh = h.carry.stable == 0 && h.carry.filled == 0 && n >= (uint32_t)c->L && (void *)cr == c->d_state.p;
     }
+    uint32_t *const seq_dst = &((DevState *)c->d_state.p)->seq[0];
+    if (fresh && ride_cert0) {
+        c->fill = FillRider{c->L, nchunks, ring, cr, eci, ver, ride_cert0, sum, seq_dst, c->batch_seq, init};
+        c->fill_pending = true;
+        return true;
+    }
     NFC_LAUNCH(c->kk->fill, dim3(1), dim3(FILL_BLOCK), (size_t)c->Lpad * 4, c->st, in, n, c->i16_scale, c->L, ring, cr, eci, ver, nchunks, sum, init,
-               &((DevState *)c->d_state.p)->seq[0], c->batch_seq, fresh);
+               seq_dst, c->batch_seq, fresh);
+    return false;
 }
 void launch_seq_kind(nfc_ctx *c, const SeqArgs &A) { NFC_LAUNCH(c->kk->seq, dim3(1), dim3(64), 0, c->st, A); }
 

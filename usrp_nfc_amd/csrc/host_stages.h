@@ -22,6 +22,18 @@ __global__ __launch_bounds__(256) void k_certify_and_write(CertLaunch C, EdgeArg
     write_edges_tile(E, nwords, partials, supers, recs, epos, ecode, cap, own_prefix, total_out, last2_total, carry_out, tiles - blockIdx.x, tiles);
 }
 
+// The edge stage's reduce pass and a fresh stream's window fill in one launch: workgroup 0 does what k_fill's short form does
+// (threshold.hip.h: fill_rider -- the launch's longest chain of loads, so it is dispatched first), the others reduce a super each.
+// run_edges launches it in place of k_edge_reduce while a fill is pending (host_context.h).
+static_assert(ER_BLOCK == FILL_BLOCK, "the rider is one workgroup of the reduce pass");
+__global__ __launch_bounds__(ER_BLOCK) void k_edge_reduce_and_fill(FillRider F, EdgeArgs E, size_t nwords, EdgeAgg *partials, EdgeAgg *supers, EdgeRec *recs) {
+    if (blockIdx.x == 0) {
+        fill_rider(F);
+        return;
+    }
+    edge_reduce_super(E, nwords, blockIdx.x - 1, partials, supers, recs);
+}
+
 // ---------------------------------------------------------------------------
 // edge stage
 // ---------------------------------------------------------------------------
@@ -66,7 +78,13 @@ int run_edges(nfc_ctx *c, uint32_t n, uint32_t skip, uint64_t g0, bool beside_th
     uint32_t *edges_total = (uint32_t *)(tot + TOT_EDGES);
     const EdgeAggOp op{E.mx, E.mx_magic};
     // (the first certification of the batch, when it is still to be launched, rides with the WRITER below: k_certify_and_write)
-    if (tiles) NFC_LAUNCH(k_edge_reduce, dim3((unsigned)supers), dim3(ER_BLOCK), 0, c->st, E, nwords, parts, sups, recs);
+    // (a fresh stream's window fill, left behind pass 0, rides with this launch -- once: a repeat of the stage finds none pending)
+    if (tiles && c->fill_pending) {
+        c->fill_pending = false;
+        NFC_LAUNCH(k_edge_reduce_and_fill, dim3((unsigned)supers + 1u), dim3(ER_BLOCK), 0, c->st, c->fill, E, nwords, parts, sups, recs);
+    } else if (tiles) {
+        NFC_LAUNCH(k_edge_reduce, dim3((unsigned)supers), dim3(ER_BLOCK), 0, c->st, E, nwords, parts, sups, recs);
+    }
     if (!own || !tiles)   // (long batches: the prefix launch over the SUPER-aggregates; the totals and the carry in its epilogue)
         scan_partials_with(c->st, op, supers, nullptr, (uint32_t)(EW_WORDS * EW_SUPER), sups, op.identity(), (EdgeAgg *)nullptr,
                            EdgeTotalEpilogue{E, edges_total, last2_total, dE(c)});
@@ -484,6 +502,9 @@ int process_batch(nfc_ctx *c, const void *d_in, size_t n64) {
     };
     const std::function<int()> ahead = edges_and_decode;
     bool clean = false;
+    // (whether a window fill left behind pass 0 would find the reduce pass of the multi-launch edge stage to ride with: host_threshold.h)
+    c->fill_pending = false;
+    c->fill_can_ride = want_edges && !(c->use_small && n <= SM_MAX_SAMPLES);
     int rc = run_threshold(c, d_in, n, skip, want_edges ? &ahead : nullptr, &clean);
     if (rc) return rc;
     if (want_edges) {

@@ -373,8 +373,11 @@ static void enqueue_certify(nfc_ctx *c, const ThrPlan &P, const ThrArgs &A, Cert
 
 // *recut_out (optional): pass 0's verdict says the stream is in the regime that needs re-runs and the batch is still on the coarse
 // cut -- nothing of the attempt stands, the caller cuts finer and tries again.
+// *refront_out (optional; without it the window fill always goes in front of pass 0): the fill rode behind pass 0 and its window's sum
+// turned out to depend on the order -- nothing of the attempt stands, the caller tries again with the fill in front.
 static int threshold_span(nfc_ctx *c, const void *d_in_all, uint32_t n_all, uint32_t skip_all, uint32_t base, const EdgeCarry &ec,
-                          const std::function<int()> *ahead, bool *clean, bool *need_seq_out, bool *recut_out = nullptr) {
+                          const std::function<int()> *ahead, bool *clean, bool *need_seq_out, bool *recut_out = nullptr,
+                          bool *refront_out = nullptr) {
     bool ran_ahead = false;
     *clean = false;
     const int L = c->L;
@@ -391,11 +394,16 @@ static int threshold_span(nfc_ctx *c, const void *d_in_all, uint32_t n_all, uint
     uint8_t *d_cert = P.d_cert;
     const uint8_t *h_cert = P.h_cert, *h_gflags = P.h_gflags, *h_gmin = P.h_gmin, *h_gmax = P.h_gmax;
 
-    // fill (if the window is not full yet) + per-batch preparation (delta, guard span, version bytes): one launch
-    launch_fill_kind(c, d_in, n, (int)nch);
-
     // a 256-sample step must not wrap the ring onto itself: short windows take the sequential kernel
     const bool force_seq = (c->P.flags & NFC_FLAG_FORCE_SEQUENTIAL) != 0 || L < STEP;
+    // fill (if the window is not full yet) + per-batch preparation (delta, guard span, version bytes): one launch, in front of pass 0 --
+    // or, for a fresh stream with a whole window in the batch, one workgroup of the edge stage's reduce pass BEHIND pass 0 (launch_fill_kind
+    // decides on `fresh`): where pass 0 is k_threshold_wg, whose chunk 0 then takes the window from the samples itself, and the stages
+    // are about to be enqueued behind pass 0 by `ahead` with the multi-launch edge stage among them (process_batch: fill_can_ride).
+    // Pass 0 then reads nothing of the state block: delta = 0 by value, which is the fill's own figure unless the window's sum depends on
+    // the order of its additions -- seen in the mirror below, and the batch is repeated with the fill in front (*refront_out).
+    const bool may_ride = wg && !force_seq && ahead && !c->dbg_any && c->fill_can_ride && !c->fill_front && refront_out;
+    const bool rode = launch_fill_kind(c, d_in, n, (int)nch, -1, may_ride ? P.d_cert : nullptr);
     bool need_seq = force_seq;
     if (!force_seq) {
         const bool lean = wg || P.form == ThrForm::Lean;   // (pass 0 by a kernel that may give up on a chunk, chunk 0 included)
@@ -404,7 +412,10 @@ static int threshold_span(nfc_ctx *c, const void *d_in_all, uint32_t n_all, uint
             HIPCHK(c, c->d_certinfo.ensure((size_t)nch * 32 * 5));   // (+ 4 waves x 4 counters per chunk in a profiling build)
             A.dbg_clk = c->d_certinfo.as<unsigned long long>();
         }
+        A.delta_by_value = A.own_window = rode ? 1 : 0;   // (pass 0 only: a re-run reads the carry the rider has written by then)
+        A.delta_val = 0.0;
         enqueue_pass0(c, P, A);
+        A.delta_by_value = A.own_window = 0;
         if (dbg_clk) {
             std::vector<unsigned long long> h((size_t)nch * 4);
             HIPCHK(c, hipStreamSynchronize(c->st));
@@ -519,6 +530,19 @@ static int threshold_span(nfc_ctx *c, const void *d_in_all, uint32_t n_all, uint
             if (stamped_last) HIPCHK(c, wait_for_stamp(c));
             else HIPCHK(c, hipStreamSynchronize(c->st));
             BATCHCHK(c, true);   // (the verdict summary and the totals are about to be read out of the mirror)
+            if (first_round && rode) {
+                if (c->fill_pending) return fail(c, NFC_ERR_INTERNAL, "the window fill was left behind pass 0 and no launch took it");
+                c->dbg_fill_rode++;
+                // the window's sum depends on the order of its additions and the reference's order gave another figure than the
+                // parallel one: chunks 1 .. of pass 0 ran with the wrong delta.  Rare (a stream that starts inside a transaction), and
+                // nothing of the attempt stands: the caller runs the batch again, k_fill in front, from the state the rider left.
+                if (!(c->hs->carry.delta == 0.0)) {
+                    c->dbg_fill_refront++;
+                    *refront_out = true;
+                    A.ver_zero = 0;
+                    return NFC_OK;
+                }
+            }
             std::vector<uint32_t> failing;
             if (first_round) {
                 memcpy(&summary, c->hs->totals + TOT_CERT, sizeof summary);
@@ -779,13 +803,13 @@ int run_threshold(nfc_ctx *c, const void *d_in, uint32_t n, uint32_t skip, const
         // (while the stream is in the regime that needs re-runs, the later stages are not enqueued behind pass 0 on the chance that
         // it stands: they would run -- 0.17 ms of the machine -- before the host has seen the verdict, and run again after the re-runs)
         const bool optimistic = base == 0 && !(c->fine_adapt && c->fine_left > 0);
-        bool recut = false;
-        int rc = threshold_span(c, d_in, n, skip, base, ec, optimistic ? ahead : nullptr, &span_clean, &need_seq, &recut);
+        bool recut = false, refront = false;
+        int rc = threshold_span(c, d_in, n, skip, base, ec, optimistic ? ahead : nullptr, &span_clean, &need_seq, &recut, &refront);
         if (rc) return rc;
-        if (recut) {
+        if (recut || refront) {
             // the attempt's end-of-batch sum is void (k_fill's preparation would take it for the carried one), everything else it
             // wrote is written again
-            c->fine_left = 8;
+            if (recut) c->fine_left = 8;
             c->cert_pending = false;
             HIPCHK(c, hipMemsetAsync((char *)dC(c) + offsetof(Carry, fin_valid), 0, sizeof(int32_t), c->st));
             span_clean = false;

@@ -285,6 +285,7 @@ int create_plan_device(nfc_ctx *c, const Switches &sw) {
     if (!c->wg_rounds) c->wg_rounds = 8;
     if (sw.chunk_adapt) c->fine_adapt = *sw.chunk_adapt != 0;
     if (sw.chunk_mult) c->fine_mult = std::max(1, std::min(16, *sw.chunk_mult));
+    if (sw.fill_front) c->fill_front = *sw.fill_front != 0;
     return NFC_OK;
 }
 
@@ -1415,6 +1416,14 @@ extern "C" int nfc_debug_dec_lds(const nfc_ctx *c, int which, uint32_t *dyn_byte
     *dyn_bytes = (uint32_t)c->dec_lds[which];
     if (hipSetDevice(c->P.device) != hipSuccess) return NFC_ERR_DEVICE;
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(wgs_per_cu, k, nfc::SCAN_BLOCK, c->dec_lds[which]) == hipSuccess ? NFC_OK : NFC_ERR_DEVICE;
+}
+// how many batches of this context started pass 0 without the window fill in front of it (the fill rode with the edge stage's reduce
+// pass: host_context.h, fill_pending), and how many of those were repeated with k_fill in front (a window whose sum depends on the order)
+extern "C" int nfc_debug_fill_order(const nfc_ctx *c, uint32_t *out2) {
+    if (!c || !out2) return NFC_ERR_ARG;
+    out2[0] = c->dbg_fill_rode;
+    out2[1] = c->dbg_fill_refront;
+    return NFC_OK;
 }
 // the decode stage's shapes: edges per tile, the tile count up to which a tile's workgroup folds its predecessors itself (this
 // context's), packet ends staged per tile, LUT rows staged in LDS at most, the longest run-in in edges; and whether the last batch's

@@ -151,6 +151,11 @@ struct ThrArgs {
     // row_len = C and row_start[r] = r * row_div * C this is the equal cut, c * C.
     uint32_t row_len[4], row_start[4], row_div;
     int C_max;   // the longest row's chunk length (the sizing of a workgroup's plane staging: launch_threshold)
+    // k_threshold_wg, pass 0 of a batch whose window fill rides behind it (fill_rider below; host_threshold.h says when): the carry's
+    // delta by value -- nothing of the state block is read --, and chunk 0 takes the stream's first window from samples [0, L) itself
+    double delta_val;
+    int32_t delta_by_value;
+    int32_t own_window;
 };
 // chunk c covers the batch's samples [m_chunk, m_chunk + len)
 __device__ __forceinline__ void chunk_span(const ThrArgs &A, uint32_t c, uint32_t &m_chunk, uint32_t &len) {
@@ -1489,6 +1494,44 @@ struct StateInit {
     uint32_t words[32];
 };
 
+// A fresh stream's window is in place (win: its L values, LDS or global) and summed (S, emin, emax over the workgroup): one lane
+// finishes the carry in registers from the state head in `init`, stores it once, and leaves the edge stage's carry and the
+// certification summary as a batch starts from them.  n_fail0: failures counted before this ran (fill_rider below).
+__device__ __forceinline__ void fresh_finish(const StateInit &init, int L, const float *win, double S, uint32_t emin, uint32_t emax, Carry *carry,
+                                             EdgeCarryInit eci, CertSummary *sum, uint32_t n_fail0) {
+    constexpr int CW = (int)(sizeof(Carry) / 4);
+    int lg = 0;
+    while ((1 << lg) < L) lg++;
+    const bool exact = (emax < 255u) && ((int)emax + 2 + lg - ((int)emin - 23) <= 52);
+    double s = S, err = 0;
+    if (!exact) {
+        s = 0;
+        for (int i = 0; i < L; i++) {
+            const double v = (double)win[i];
+            const double t = s + v;            // transition_sink.py:122, sequential
+            const double bv = t - s;           // TwoSum residue: was the addition exact?
+            err += fabs((s - (t - bv)) + (v - bv));
+            s = t;
+        }
+    }
+    Carry nc;
+    uint32_t cw[CW];
+#pragma unroll
+    for (int k = 0; k < CW; k++) cw[k] = init.words[k];
+    memcpy(&nc, cw, sizeof nc);
+    nc.filled = L;
+    nc.ss = s;
+    nc.stable = 1;
+    if (err != 0.0) nc.inexact = 1;
+    batch_guard(nc, S, emin, emax);
+    *carry = nc;
+    // work has just been rebound to work_stable: _dur = length % max (transition_sink.py:123)
+    eci.dst[0] = 0;
+    eci.dst[1] = 0;
+    eci.dst[2] = eci.dur0;
+    if (sum) *sum = CertSummary{n_fail0, 255u, 0u, 0u, 0u, 0u};
+}
+
 template <int KIND>
 __global__ __launch_bounds__(FILL_BLOCK) void k_fill(const void *in, uint32_t n, float i16_scale, int L, float *ring, Carry *carry,
                                                      EdgeCarryInit eci, uint8_t *ver, int nchunks, CertSummary *sum, StateInit init,
@@ -1531,39 +1574,7 @@ __global__ __launch_bounds__(FILL_BLOCK) void k_fill(const void *in, uint32_t n,
             for (int i = L + tid; i < init.ring_len; i += FILL_BLOCK) ring[i] = 0.f;
         for (int i = tid; i < nchunks; i += FILL_BLOCK) ver[i] = 0;
         fill_reduce(red, part, emin, emax);   // (its barriers also publish lr)
-        if (tid == 0) {
-            const double S = part;
-            int lg = 0;
-            while ((1 << lg) < L) lg++;
-            const bool exact = (emax < 255u) && ((int)emax + 2 + lg - ((int)emin - 23) <= 52);
-            double s = S, err = 0;
-            if (!exact) {
-                s = 0;
-                for (int i = 0; i < L; i++) {
-                    const double v = (double)lr[i];
-                    const double t = s + v;            // transition_sink.py:122, sequential
-                    const double bv = t - s;           // TwoSum residue: was the addition exact?
-                    err += fabs((s - (t - bv)) + (v - bv));
-                    s = t;
-                }
-            }
-            Carry nc;
-            uint32_t cw[CW];
-#pragma unroll
-            for (int k = 0; k < CW; k++) cw[k] = init.words[k];
-            memcpy(&nc, cw, sizeof nc);
-            nc.filled = L;
-            nc.ss = s;
-            nc.stable = 1;
-            if (err != 0.0) nc.inexact = 1;
-            batch_guard(nc, S, emin, emax);
-            *carry = nc;
-            // work has just been rebound to work_stable: _dur = length % max (transition_sink.py:123)
-            eci.dst[0] = 0;
-            eci.dst[1] = 0;
-            eci.dst[2] = eci.dur0;
-            if (sum) *sum = CertSummary{0u, 255u, 0u, 0u, 0u, 0u};
-        }
+        if (tid == 0) fresh_finish(init, L, lr, part, emin, emax, carry, eci, sum, 0u);
         return;
     }
     if (init.apply) {
@@ -1638,6 +1649,48 @@ __global__ __launch_bounds__(FILL_BLOCK) void k_fill(const void *in, uint32_t n,
     // the per-batch preparation: the window was summed just now (S, emin, emax are every thread's), only the resets are left
     for (int i = tid; i < nchunks; i += FILL_BLOCK) ver[i] = 0;
     prepare_batch_finish(carry, sum, S, emin, emax);
+}
+
+// k_fill's short form as ONE workgroup of a launch BEHIND pass 0 (k_edge_reduce_and_fill, host_stages.h), for a fresh stream whose pass 0
+// is k_threshold_wg with ThrArgs.own_window: chunk 0 of that launch has left the window's L values in the carried ring, so this needs no
+// input kind.  Everything k_fill's short form writes, in its order -- the state head, the ring's padding, the carry stored once, the
+// edge stage's carry, the version bytes, the certification summary, the batch's stamp -- and nothing pass 0 has read: its first reader
+// is the certification, a launch later.  cert0: chunk 0's verdict, which pass 0 has already counted into the summary this resets.
+// Once per batch: an edge stage that is repeated launches its reduce pass without it (the summary holds the certification's counts by then).
+struct FillRider {
+    int32_t L, nchunks;
+    float *ring;
+    Carry *carry;
+    EdgeCarryInit eci;
+    uint8_t *ver;
+    const uint8_t *cert0;
+    CertSummary *sum;
+    uint32_t *seq_dst;
+    uint32_t seq;
+    StateInit init;
+};
+__device__ __forceinline__ void fill_rider(const FillRider &F) {
+    __shared__ FillRed red;
+    constexpr int CW = (int)(sizeof(Carry) / 4);
+    const int tid = threadIdx.x;
+    if (tid == 0) *F.seq_dst = F.seq;
+    if (tid >= CW && tid < F.init.n_words) F.init.dst[tid] = F.init.words[tid];   // (the carry's words: thread 0, fresh_finish)
+    double part = 0;
+    uint32_t emin = 255u, emax = 0u;
+    for (int i = tid; i < F.L; i += FILL_BLOCK) {
+        const float v = F.ring[i];
+        part += (double)v;
+        if (v != 0.f) {
+            const uint32_t e = max(f32_expfield(v), 1u);
+            emin = min(emin, e);
+            emax = max(emax, e);
+        }
+    }
+    if (F.init.fill_ring)
+        for (int i = F.L + tid; i < F.init.ring_len; i += FILL_BLOCK) F.ring[i] = 0.f;
+    for (int i = tid; i < F.nchunks; i += FILL_BLOCK) F.ver[i] = 0;
+    fill_reduce(red, part, emin, emax);
+    if (tid == 0) fresh_finish(F.init, F.L, F.ring, part, emin, emax, F.carry, F.eci, F.sum, *F.cert0 ? 0u : 1u);
 }
 
 // After the passes converged: the ring at the end of the batch (look-back over all

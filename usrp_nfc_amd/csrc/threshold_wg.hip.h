@@ -272,7 +272,16 @@ __global__ __launch_bounds__(256) void k_threshold_wg(ThrArgs A) {
         wg_load_step<KIND, NR>(voff, in_first);
         primed = true;
     }
-    const Carry cr = *A.carry;
+    // the carried sums: two fields of the state block -- or, in a launch the batch's window fill rides behind (ThrArgs.delta_by_value),
+    // the delta by value: the state block is not written yet, and nothing of it is read
+    struct { double ss, delta; } cr;
+    if (A.delta_by_value) {
+        cr.ss = 0.0;
+        cr.delta = A.delta_val;
+    } else {
+        cr.ss = A.carry->ss;
+        cr.delta = A.carry->delta;
+    }
     uint64_t *const neg_p = A.neg, *const pos_p = A.pos;
     // lanes 0 .. 2 NR - 1 hold the neg plane's dwords of a step, 2 NR .. 4 NR - 1 the pos plane's
     const uintptr_t plane_of_lane = (lane >= 2 * NR) ? (uintptr_t)pos_p : (uintptr_t)neg_p;
@@ -330,7 +339,41 @@ __global__ __launch_bounds__(256) void k_threshold_wg(ThrArgs A) {
     float ssf, eps = 0.f;
     {
         double ss0;
-        if (c == 0) {
+        if (c == 0 && A.own_window) {
+            // a fresh stream whose first batch holds a whole window, the fill riding behind this launch (fill_rider): the window is the
+            // batch's first L samples, taken as the speculation below takes a chunk's (no level replacement: they ARE the window), left
+            // in the carried ring for the rider and the certification, and summed here.  The sum is the reference's only where no
+            // order of additions rounds: the rider's test, made below on the exponents every chunk folds anyway.
+            float *const rc = const_cast<float *>(A.ring_carry);
+            double part = 0;
+            for (int i0 = 0; i0 < L; i0 += 2048) {
+                typename RawOf<KIND>::T rw[8];
+#pragma unroll
+                for (int k = 0; k < 8; k++) {
+                    const int i = i0 + 256 * k + tid;
+                    rw[k] = (i < L) ? load_raw<KIND>(A.in, (size_t)i) : raw_zero<KIND>();
+                }
+#pragma unroll
+                for (int k = 0; k < 8; k++) {
+                    const int i = i0 + 256 * k + tid;
+                    if (i < L) {
+                        const float x = env_of<KIND>(rw[k], A.i16_scale);
+                        ring[i] = x;
+                        rc[i] = x;
+                        part += (double)x;
+                    }
+                }
+            }
+            const double ps = wave_sum_f64(part);
+            uint32_t v[8], g[WG_WAVES][8];
+            v[0] = (uint32_t)__double2loint(ps);
+            v[1] = (uint32_t)__double2hiint(ps);
+            wg_gather(v, 2, g);   // (its barrier also completes the ring)
+            ss0 = 0;
+            for (int w = 0; w < WG_WAVES; w++) ss0 += __hiloint2double((int)g[w][1], (int)g[w][0]);
+            nl_in = carried_nl(A);
+            kl_in = carried_kl(A);
+        } else if (c == 0) {
             for (int s = tid; s < L; s += 256) ring[s] = A.ring_carry[s];
             ss0 = cr.ss;
             nl_in = carried_nl(A);
@@ -471,6 +514,13 @@ __global__ __launch_bounds__(256) void k_threshold_wg(ThrArgs A) {
     // bits, so a negative sample, an infinity or a NaN -- raw bits 0x7F800000 and up -- makes the chunk give up (k_threshold takes
     // it, as it took every chunk of this kind before): in the state it starts from (here), in a round's samples (below).
     if constexpr (KIND == IN_ENV_F32) good_run = good_run && vtop0 < 0x7F800000u;
+    if (c == 0 && A.own_window) {
+        // k_fill's test: emax + 2 + lg - (emin - 23) <= 52 proves every order of the window's additions exact.  Where it does not hold the
+        // chunk gives up and is re-run from the carried state, which the rider has written by then
+        int lg = 0;
+        while ((1 << lg) < L) lg++;
+        good_run = good_run && emax < 255u && (int)emax + 2 + lg - ((int)emin - 23) <= 52;
+    }
     uint32_t why = good_run ? 0u : 1u;   // 1 parameters / sums out of range, 2 a sample inside a band, 3 LOW run, 4 allowance, 5 first stable sample
     float min_ss = 3.0e38f;
     uint32_t vmin = 0xFFFFFFFFu, vmax = vtop0;   // (wave 0's: what the superstep closes add; the general steps' share is in sh->cold)
@@ -1461,7 +1511,8 @@ __global__ __launch_bounds__(256) void k_threshold_wg(ThrArgs A) {
         v[0] = min(wave_min_u32(vmin), rfl(sh->cold[wave][2]));
         v[1] = max(wave_max_u32(vmax), rfl(sh->cold[wave][3]));
         // pass 0 fills the buffer the version byte names (0: prepare_batch zeroes them), a re-run the other one
-        const int vb_new = (A.mode == 1) ? 1 - (int)A.ver[c] : (int)A.ver[c];
+        // (a launch the fill rides behind: buffer 0 without looking -- the version bytes are the last batch's still)
+        const int vb_new = A.delta_by_value ? 0 : (A.mode == 1) ? 1 - (int)A.ver[c] : (int)A.ver[c];
         float *ro = (vb_new ? A.ring_out[1] : A.ring_out[0]) + (size_t)c * L;
         uint32_t *to = (vb_new ? A.touched[1] : A.touched[0]) + (size_t)c * A.twords;
         uint32_t untouched = 0;
