@@ -1055,6 +1055,84 @@ int nfc_air_render_device(int device, const nfc_air_config *cfg, const nfc_air_f
                           const uint8_t *par, const uint32_t *byte_base, size_t K, void *dev_out, size_t cap_samples, uint64_t *first_sample,
                           uint32_t *n_samples, float *kernel_ms /* NULL, or two floats */);
 
+/* ---- transmitting what the streams answer: K timed TX captures from one push (csrc/answers_tx.hip.h) ------------------
+ * What tag_emulate / reader_emulate hand to binary_src -> multiplier -> the radio, for the answers of every stream of a tracked,
+ * emulated push, rendered on the device from the tracking buffer: no answer byte goes through the host, no run table through HBM.
+ * THE TWO TIMELINES.  r counts a stream's received samples since its last reset (a raw frame's idx as nfc_multi_fetch_commands gives
+ * it); TX index T(r) = floor(r * rate_num / rate_den) in 64-bit integers (r * rate_num must stay below 2^64), rate_num / rate_den the
+ * reduced ratio of output to input rate.  A push that gave a stream the samples [b, b + n) owns the TX span [T(b), T(b + n)): the spans
+ * of consecutive pushes tile the TX timeline.
+ * AN ANSWER's samples: its bits from air / par (n_bits 1 .. 8: a short frame from the low bits of its first byte; else a multiple of 9 up
+ * to 162), the runs nfc_tx_encode gives for them -- NFC_TX_MANCHESTER for a tag card (idle level 0, usrp_nfc.py:75), NFC_TX_MILLER for
+ * a reader card (idle level 1, usrp_nfc.py:45) -- and per run the samples nfc_tx_sample_count gives at samp_rate (binary_src.work's
+ * rule, NOT the air interface's int(d * rate_msps)).  L: the answer's samples in all.
+ * THE SCHEDULE of one stream and push: the pending entry carried in (if any), then the push's answers in order.  Entry j answers the
+ * command whose raw frame closed at idx_j; it starts at S_j = T(idx_j) + delay_samples (a pending entry keeps its stored start), is cut
+ * at C_j = T(idx_j+1), the moment the next answered command closed (never for the last entry), and owns [S_j, min(S_j + L_j, C_j)) --
+ * which may be empty -- intersected with the push's span.  Every other sample of the span is the idle level.  Afterwards the stream's
+ * pending entry is the last entry if its interval reaches beyond the span's end, else none: a stream carries at most one answer from
+ * push to push, as long as it takes.  A push that is never transmitted drops its answers.
+ * A SAMPLE is nfc_tx_render_device's: (level, 0) with the carrier off, else level * amp * exp(j 2 pi phase) with the phase of TX index
+ * t taken from (first_index + t) * phase_inc in 64-bit fixed point (the device: sincospif of the top 24 bits, k_tx_render's own device
+ * function; the twin: cos / sin in double, equal within 1.5e-7 of amp).  It depends on the stream's answers, the configuration and t
+ * alone -- not on K, the stream's place, the tiling or how the pushes were cut.
+ * THE LAYOUT is the air interface's: streams packed in stream order, first_sample[k] rounded up to align_samples, n_samples[k] =
+ * T(b + n) - T(b), or 0 for a stream without a card, padding (0, 0); no byte of [0, first_sample[K-1] + n_samples[K-1]) is left
+ * unwritten and none beyond is touched.  All sizes follow from the push's own arguments: no device read, no host wait.
+ * NOT MODELLED: reader_emulate's REQA repeat after a HALT, tag_emulate's threshold / float-to-complex chain in front of the UHD sink;
+ * ISO 14443-3 frame-delay conformance is not claimed (idx lies behind the frame's last pause by the decoder's timeout: DESIGN.md 8m).
+ * ERRORS are NFC_ERR_ARG, raised before the device is touched, the argument's name in the message: a rate_num / rate_den outside
+ * 1 .. 65 536, a samp_rate outside (0, 1e9], an align_samples that is no power of two (up to 2^20), a non-zero reserved word, a dev_out
+ * that is not 32-byte aligned, a stream span above 2^30 samples; in the twin an n_bits outside the domain and bytes that leave the
+ * stream's part.  A layout that needs more than cap_samples renders nothing, leaves every pending entry as it was, fills first_sample /
+ * n_samples with the true need and is NFC_ERR_ARG naming cap_samples. */
+typedef struct nfc_answers_tx_config {  /* 64 bytes */
+    double samp_rate;                   /* of the output, Hz, in (0, 1e9] */
+    double freq;                        /* of the carrier, Hz */
+    uint64_t first_index;               /* carrier index of TX index 0 */
+    uint64_t delay_samples;             /* from T(idx) to an answer's first sample */
+    uint32_t rate_num, rate_den;        /* output rate : input rate, 1 .. 65 536 each */
+    int32_t carrier;                    /* 0: (level, 0) */
+    float amp;
+    uint32_t align_samples;             /* a power of two: every first_sample[k] is a multiple of it */
+    uint32_t reserved[3];               /* 0 */
+} nfc_answers_tx_config;
+typedef struct nfc_tx_pending {         /* 64 bytes, plain; n_bits == 0: none (then every byte is 0) */
+    uint64_t start;                     /* S, a TX index */
+    uint16_t n_bits;
+    uint8_t role;                       /* NFC_EMU_TAG / NFC_EMU_READER: the encoding */
+    uint8_t reserved0;
+    uint32_t reserved1;
+    uint8_t air[18], par[18];           /* zero behind the answer's bytes */
+    uint8_t reserved2[12];
+} nfc_tx_pending;
+typedef struct nfc_tx_answer {          /* 16 bytes: the twin's input, one per answer */
+    uint64_t idx;                       /* r of the answered command's raw frame */
+    uint32_t byte_off;                  /* in the stream's part of air / par */
+    uint32_t n_bits;
+} nfc_tx_answer;
+/* The CPU twin (no GPU needed).  role[k]: NFC_EMU_TAG, NFC_EMU_READER, or -1 for a stream without a card (no samples; its pending
+ * entry is left alone); the push gave stream k the samples [rx_base[k], rx_base[k] + rx_n[k]); its answers are answers[ans_off[k] ..
+ * ans_off[k + 1]), their bytes in air / par [byte_base[k] .. byte_base[k + 1]).  pending[K] is read and advanced in place.
+ * out == NULL is the sizing call: it fills first_sample and n_samples and touches no pending entry. */
+int nfc_host_answers_tx(const nfc_answers_tx_config *cfg, size_t K, const int32_t *role, const uint64_t *rx_base, const uint32_t *rx_n,
+                        const uint32_t *ans_off /* [K + 1] */, const nfc_tx_answer *answers, const uint8_t *air, const uint8_t *par,
+                        const uint32_t *byte_base /* [K + 1] */, nfc_tx_pending *pending /* [K] */, void *out, size_t cap_samples,
+                        uint64_t *first_sample /* [K] */, uint32_t *n_samples /* [K] */);
+/* Renders the last push's answers of every stream that holds a card into dev_out (complex64, cap_samples entries) and advances the
+ * pending entries on the device: a schedule pass, a lane per stream, and a render pass over flat tiles of the packed output, enqueued
+ * on the context's stream behind the machine kernel with no host wait.  kernel_ms: NULL, or TWO floats, the two passes' durations by
+ * HIP events -- which implies the wait.  Once per push: a second call before the next push is NFC_ERR_STATE, as is a call with
+ * tracking off, with no completed push (or a reset / set_state since), or with no stream holding a card.  A push in which nothing was
+ * stored still renders: idle samples and whatever is pending.  The device sections of the call are followed by the guard word (the
+ * test build's guard check covers them); a context that never calls this allocates and launches exactly what it did.
+ * nfc_multi_get_tx_state / _set_tx_state: a stream's pending entry (set: NFC_ERR_ARG for an n_bits outside the domain, a role above 1,
+ * a non-zero reserved byte); both complete the device first.  nfc_multi_reset(stream) and nfc_multi_emulate clear the stream's entry. */
+int nfc_multi_transmit_device(nfc_multi *m, const nfc_answers_tx_config *cfg, void *dev_out, size_t cap_samples, uint64_t *first_sample,
+                              uint32_t *n_samples, float *kernel_ms /* NULL, or two floats */);
+int nfc_multi_get_tx_state(nfc_multi *m, uint32_t stream, nfc_tx_pending *st);
+int nfc_multi_set_tx_state(nfc_multi *m, uint32_t stream, const nfc_tx_pending *st);
+
 /* one stream's boundary state, in the form an nfc_ctx exports and imports it */
 int nfc_multi_get_state(nfc_multi *m, uint32_t stream, nfc_state_header *hdr, float *ring, size_t ring_cap, uint8_t *pending, size_t pending_cap);
 int nfc_multi_set_state(nfc_multi *m, uint32_t stream, const nfc_state_header *hdr, const float *ring, size_t ring_len, const uint8_t *pending, size_t pending_len);

@@ -128,6 +128,19 @@ class AirConfig(C.Structure):   # nfc_air_config
                 ('align_samples', C.c_uint32), ('reserved', C.c_uint32 * 4)]
 
 
+class AnswersTxConfig(C.Structure):   # nfc_answers_tx_config
+    _fields_ = [('samp_rate', C.c_double), ('freq', C.c_double), ('first_index', C.c_uint64), ('delay_samples', C.c_uint64), ('rate_num', C.c_uint32),
+                ('rate_den', C.c_uint32), ('carrier', C.c_int32), ('amp', C.c_float), ('align_samples', C.c_uint32), ('reserved', C.c_uint32 * 3)]
+
+
+class TxPending(C.Structure):   # nfc_tx_pending
+    _fields_ = [('start', C.c_uint64), ('n_bits', C.c_uint16), ('role', C.c_uint8), ('reserved0', C.c_uint8), ('reserved1', C.c_uint32),
+                ('air', C.c_uint8 * 18), ('par', C.c_uint8 * 18), ('reserved2', C.c_uint8 * 12)]
+
+
+TX_PENDING_DTYPE = np.dtype([('start', '<u8'), ('n_bits', '<u2'), ('role', 'u1'), ('reserved0', 'u1'), ('reserved1', '<u4'), ('air', 'u1', (18,)),
+                             ('par', 'u1', (18,)), ('reserved2', 'u1', (12,))])   # nfc_tx_pending as a record
+TX_ANSWER_DTYPE = np.dtype([('idx', '<u8'), ('byte_off', '<u4'), ('n_bits', '<u4')])   # nfc_tx_answer
 AIR_FRAME_DTYPE = np.dtype([('type', 'u1'), ('flags', 'u1'), ('n_bits', '<u2'), ('byte_off', '<u4'), ('idle_before', '<u4'),
                             ('reserved', '<u4')])   # nfc_air_frame
 NFC_EMU_TAG, NFC_EMU_READER = 0, 1
@@ -216,7 +229,8 @@ SYMBOLS = ['nfc_abi_version', 'nfc_device_count', 'nfc_create', 'nfc_destroy', '
            'nfc_recover_nested_keys_device',
            'nfc_emu_state_init', 'nfc_emu_last_error', 'nfc_host_emu_step', 'nfc_host_emulate', 'nfc_multi_emulate', 'nfc_multi_fetch_answers', 'nfc_multi_get_emu_state',
            'nfc_multi_set_emu_state', 'nfc_host_emulate_pairs', 'nfc_emulate_pairs_device',
-           'nfc_host_air_render', 'nfc_air_render_device']
+           'nfc_host_air_render', 'nfc_air_render_device',
+           'nfc_host_answers_tx', 'nfc_multi_transmit_device', 'nfc_multi_get_tx_state', 'nfc_multi_set_tx_state']
 
 _libs = {}
 
@@ -370,6 +384,10 @@ def load(path=None):
     L.nfc_emulate_pairs_device.argtypes = [C.c_int, vp, vp, sz, C.POINTER(EmuConfig), vp, vp, vp, vp, vp, C.POINTER(C.c_float)]
     L.nfc_host_air_render.argtypes = [C.POINTER(AirConfig), vp, vp, vp, vp, vp, sz, vp, sz, vp, vp]
     L.nfc_air_render_device.argtypes = [C.c_int, C.POINTER(AirConfig), vp, vp, vp, vp, vp, sz, vp, sz, vp, vp, C.POINTER(C.c_float * 2)]
+    L.nfc_host_answers_tx.argtypes = [C.POINTER(AnswersTxConfig), sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp]
+    L.nfc_multi_transmit_device.argtypes = [vp, C.POINTER(AnswersTxConfig), vp, sz, vp, vp, C.POINTER(C.c_float * 2)]
+    L.nfc_multi_get_tx_state.argtypes = [vp, u32, C.POINTER(TxPending)]
+    L.nfc_multi_set_tx_state.argtypes = [vp, u32, C.POINTER(TxPending)]
     for name in SYMBOLS:
         getattr(L, name)
     _libs[path] = L

@@ -512,6 +512,56 @@ class NfcMultiContext(object):
             raise NfcError('set_emu_state: stream %d out of range (n_streams %d)' % (k, self.n_streams))
         self._chk(self.L.nfc_multi_set_emu_state(self.h, int(k), C.byref(st)), 'nfc_multi_set_emu_state')
 
+    def transmit(self, samp_rate=2e6, in_rate=None, delay_us=0.0, carrier=False, freq=13.56e6, amp=1.0, first_index=0, align_samples=8,
+                 out=None, timed=False, _reserved=0):
+        """What the streams that hold a card transmit for the last push, rendered on the GPU (nfc_multi_transmit_device): every answer as
+        the reference's binary_src -> multiplier chain would send it, delay_us behind the moment the answered command closed, idle level
+        elsewhere; an answer that reaches beyond the push's span is carried to the next transmit().  Once per push, enqueued behind the
+        push's kernels with no host wait.  samp_rate: of the output, in_rate: of the input (None: the same).  out: a DeviceBuffer (or
+        (pointer, cap_samples)) to render into, 32-byte aligned; None: a buffer of the needed size is allocated and owned by the result.
+        timed: the two passes' durations -> .kernel_ms (waits).  -> tx.TxCaptures, whose wait() completes the rendering."""
+        from . import tx
+        cfg = tx.answers_tx_config(samp_rate, in_rate, delay_us, carrier, freq, amp, first_index, align_samples, _reserved)
+        first, n = np.zeros(self.n_streams, np.uint64), np.zeros(self.n_streams, np.uint32)
+        ms = (C.c_float * 2)()
+        call = lambda ptr, cap: self.L.nfc_multi_transmit_device(self.h, C.byref(cfg), ptr, int(cap), first.ctypes.data, n.ctypes.data,
+                                                                 C.byref(ms) if timed else None)
+        buf, owned = out, False
+        if out is None:   # the sizing call: a layout that does not fit renders nothing and reports the need
+            rc = call(None, 0)
+            if rc == 0:   # (nothing to render: no stream with a card was given a sample)
+                return tx.TxCaptures(first, n, None, False, samp_rate, self.device, tuple(ms) if timed else None, self)
+            if rc != -1 or b'cap_samples' not in self.L.nfc_multi_last_error(self.h):
+                self._chk(rc, 'nfc_multi_transmit_device')
+            cap = int(first[-1]) + int(n[-1])
+            buf, owned = DeviceBuffer(np.zeros(0, np.float32), self.device, nbytes=max(8 * cap, 32)), True
+            ptr = buf.ptr
+        elif isinstance(out, DeviceBuffer):
+            ptr, cap = out.ptr, out.nbytes // 8
+        else:
+            ptr, cap = _as_pointer(out[0]), int(out[1])
+        rc = call(ptr, cap)
+        if rc != 0 and owned:
+            buf.free()
+        self._chk(rc, 'nfc_multi_transmit_device')
+        return tx.TxCaptures(first, n, buf if isinstance(buf, DeviceBuffer) else ptr, owned, samp_rate, self.device, tuple(ms) if timed else None, self)
+
+    def tx_state(self, k):
+        """Stream k's pending answer as a plain nfc_tx_pending (an _lib.TxPending; n_bits 0: none)."""
+        if not 0 <= int(k) < self.n_streams:
+            raise NfcError('tx_state: stream %d out of range (n_streams %d)' % (k, self.n_streams))
+        st = _lib.TxPending()
+        self._chk(self.L.nfc_multi_get_tx_state(self.h, int(k), C.byref(st)), 'nfc_multi_get_tx_state')
+        return st
+
+    def set_tx_state(self, k, st):
+        """Stream k continues with the pending answer `st` (another stream's tx_state(), emulate.host_transmit's)."""
+        if not 0 <= int(k) < self.n_streams:
+            raise NfcError('set_tx_state: stream %d out of range (n_streams %d)' % (k, self.n_streams))
+        if isinstance(st, np.void):
+            st = _lib.TxPending.from_buffer_copy(st.tobytes())
+        self._chk(self.L.nfc_multi_set_tx_state(self.h, int(k), C.byref(st)), 'nfc_multi_set_tx_state')
+
     def counts_all(self):
         """Every stream's counts and flags of the last push from one call: a COUNTS_FLAGS_DTYPE array of n_streams records."""
         cnt, flags = np.zeros(self.n_streams, COUNTS_DTYPE), np.zeros(self.n_streams, np.uint32)

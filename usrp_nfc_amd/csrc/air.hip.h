@@ -175,7 +175,7 @@ __host__ __device__ __forceinline__ uint64_t pack(uint32_t kind, float i, float 
 }
 __host__ __device__ __forceinline__ uint64_t align_up(uint64_t n, uint32_t align) { return (n + align - 1) & ~(uint64_t)(align - 1); }
 
-#ifdef __HIPCC__
+#if defined(__HIPCC__) && !defined(NFC_AIR_PIECES_ONLY)   // (answers_tx.hip.h takes the pieces alone: the kernels are nfc_air.hip's)
 // ---- the kernels -------------------------------------------------------------------------------------------------------------------
 struct AddU64 {
     using T = uint64_t;

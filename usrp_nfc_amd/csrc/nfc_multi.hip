@@ -37,6 +37,8 @@
 #include "frames.hip.h"   // (the frame assembly kernels: nfc_frames.hip)
 #include "multi_commands.hip.h"   // (the protocol machine a lane per stream: nfc_commands.hip)
 #include "input_kind.h"
+#define NFC_ANSWERS_TX_KERNELS
+#include "answers_tx.hip.h"   // (the answers as TX samples: the schedule and render kernels; their twin is nfc_answers_tx.hip)
 
 using namespace nfc;
 using namespace nfc::multi;
@@ -119,6 +121,14 @@ struct nfc_multi {
     bool cmd_emulated = false;   // the last launched push ran the emulating form: its buffer holds the answers' sections
     commands::EmuArgs cmd_emu;
     nfc_multi_answers aout;
+    // transmission (answers_tx.hip.h), there from the first nfc_multi_transmit_device / nfc_multi_set_tx_state on, never before: the
+    // pending entries [K], one section with its guard; the buffer of one call -- the streams' records, the tile table, the span table, the
+    // span counts -- and the pinned staging of the two the host makes.  card_role: -1 none, else the card's role (ensure_emu sizes it)
+    std::vector<int8_t> card_role;
+    Packed txpend, tx;
+    PinBuf h_tx;
+    Event evt[4];
+    bool tx_done = false;   // the last push was transmitted
     Packed cmd;
     size_t cmd_bytes = 0;
     CmdState cmd_state = CMD_NONE;
@@ -424,6 +434,7 @@ int ensure_emu(nfc_multi *m, const char *fn) {
     std::swap(m->d_emu, fresh);
     m->emu_mem = 0, m->emu_rands = o_rands, m->emu_params = o_params, m->emu_state = o_state;
     m->has_card.assign(K, 0);
+    m->card_role.assign(K, -1);
     m->n_cards = 0;
     return emu_state_init_range(m, 0, m->K);
 }
@@ -743,6 +754,7 @@ int nfc_multi_push_device(nfc_multi *m, const void *dev_base, const uint64_t *fi
     m->stats.n_launches = 1;
     m->stats.n_streams_truncated = cut;
     m->stats.n_fetches = m->stats.n_reads_device = 0;
+    m->tx_done = false;
     m->cmd_state = nfc_multi::CMD_NONE;
     m->cmd_fetched = false;
     if (m->track) return enqueue_commands(m);
@@ -1120,6 +1132,7 @@ int nfc_multi_reset(nfc_multi *m, int64_t stream) {
     if (m->d_keys.p) commands::launch_set_table(m->d_keys.as<uint32_t>(), m->K, k0, k1, nullptr, m->st);   // ... and their sector keys
     if (m->d_emu.p)   // ... and the emulators: nfc_emu_state_init's state (the cards stay)
         if (int rc = emu_state_init_range(m, k0, k1)) return rc;
+    if (m->txpend.d.p) MCHK(m, hipMemsetAsync(m->txpend.d.as<nfc_tx_pending>() + k0, 0, (size_t)(k1 - k0) * sizeof(nfc_tx_pending), m->st));   // ... and what they were still to transmit
     m->cmd_state = nfc_multi::CMD_NONE;
     m->cmd_fetched = false;
     if (int rc = launch_ok(m)) return rc;
@@ -1364,7 +1377,9 @@ int nfc_multi_emulate(nfc_multi *m, int64_t stream, const nfc_emu_card *card) {
         MCHK(m, hipMemcpy2DAsync(e + m->emu_params + (size_t)k * 4, K * 4, par.data(), 4, 4, commands::EP_WORDS, hipMemcpyHostToDevice, m->st));
         m->n_cards += (card ? 1u : 0u) - (uint32_t)m->has_card[k];
         m->has_card[k] = card ? 1 : 0;
+        m->card_role[k] = card ? (int8_t)card->role : (int8_t)-1;
     }
+    if (m->txpend.d.p) MCHK(m, hipMemsetAsync(m->txpend.d.as<nfc_tx_pending>() + k0, 0, (size_t)(k1 - k0) * sizeof(nfc_tx_pending), m->st));   // (a new card has nothing pending)
     MCHK(m, hipStreamSynchronize(m->st));   // (the sources are this call's)
     if (int rc = emu_state_init_range(m, k0, k1)) return rc;   // a new card starts from the initial state
     if (card) m->track = true;   // answering implies tracking
@@ -1442,6 +1457,194 @@ int nfc_multi_fetch_answers(nfc_multi *m, nfc_multi_answers *out) {
     return NFC_OK;
 }
 
+// ---- transmission: the answers of the last push as TX samples (answers_tx.hip.h) ----
+// the pending entries, zeroed (no stream has one), with their guard: at the first call that needs them
+static int ensure_txpend(nfc_multi *m, const char *fn) {
+    if (m->txpend.d.p) return NFC_OK;
+    const size_t bytes = (size_t)m->K * sizeof(nfc_tx_pending);
+    DevBuf fresh;
+    if (fresh.ensure(bytes + GUARD_BYTES) != hipSuccess) {
+        (void)hipGetLastError();
+        return mfail(m, NFC_ERR_NOMEM, "%s: no device memory for %zu bytes", fn, bytes + GUARD_BYTES);
+    }
+    MCHK(m, hipMemsetAsync(fresh.p, 0, bytes, m->st));
+    MCHK(m, hipMemsetD32Async((hipDeviceptr_t)(fresh.as<uint8_t>() + bytes), (int)GUARD_WORD, GUARD_BYTES / 4, m->st));
+    std::swap(m->txpend.d, fresh);
+    m->txpend.guards.assign(1, bytes);
+    return NFC_OK;
+}
+
+static const char *tx_pending_fault(const nfc_tx_pending &p) {
+    if (p.n_bits && !atx::n_bits_ok(p.n_bits)) return "n_bits is neither 0, 1 .. 8 nor a multiple of 9 up to 162";
+    if (p.role > 1) return "role is neither NFC_EMU_TAG nor NFC_EMU_READER";
+    if (p.reserved0 || p.reserved1) return "reserved must be 0";
+    for (int i = 0; i < 12; i++)
+        if (p.reserved2[i]) return "reserved must be 0";
+    return nullptr;
+}
+
+int nfc_multi_get_tx_state(nfc_multi *m, uint32_t stream, nfc_tx_pending *st) {
+    if (!m) return NFC_ERR_ARG;
+    LaunchScope scope(&m->launch_err);
+    if (stream >= m->K) return mfail(m, NFC_ERR_ARG, "stream %u out of range (n_streams %u)", stream, m->K);
+    if (!st) return mfail(m, NFC_ERR_ARG, "st is null");
+    memset(st, 0, sizeof *st);
+    if (!m->txpend.d.p) return NFC_OK;   // nothing was ever transmitted or set: no stream has a pending entry
+    if (hipSetDevice(m->P.device) != hipSuccess) return mfail(m, NFC_ERR_DEVICE, "hipSetDevice failed");
+    MCHK(m, hipStreamSynchronize(m->st));
+    if (int rc = launch_ok(m)) return rc;
+    MCHK(m, hipMemcpy(st, m->txpend.d.as<nfc_tx_pending>() + stream, sizeof *st, hipMemcpyDeviceToHost));
+    return NFC_OK;
+}
+
+int nfc_multi_set_tx_state(nfc_multi *m, uint32_t stream, const nfc_tx_pending *st) {
+    if (!m) return NFC_ERR_ARG;
+    LaunchScope scope(&m->launch_err);
+    if (stream >= m->K) return mfail(m, NFC_ERR_ARG, "stream %u out of range (n_streams %u)", stream, m->K);
+    if (!st) return mfail(m, NFC_ERR_ARG, "st is null");
+    if (const char *bad = tx_pending_fault(*st)) return mfail(m, NFC_ERR_ARG, "st: %s", bad);
+    if (hipSetDevice(m->P.device) != hipSuccess) return mfail(m, NFC_ERR_DEVICE, "hipSetDevice failed");
+    if (int rc = ensure_txpend(m, "nfc_multi_set_tx_state")) return rc;
+    nfc_tx_pending p;
+    memset(&p, 0, sizeof p);
+    if (st->n_bits) {   // (canonical: zero behind the answer's bytes, every byte zero without one)
+        const uint32_t nb = air::frame_bytes(st->n_bits);
+        p.start = st->start, p.n_bits = st->n_bits, p.role = st->role;
+        memcpy(p.air, st->air, nb);
+        memcpy(p.par, st->par, nb);
+    }
+    MCHK(m, hipStreamSynchronize(m->st));
+    MCHK(m, hipMemcpy(m->txpend.d.as<nfc_tx_pending>() + stream, &p, sizeof p, hipMemcpyHostToDevice));
+    return NFC_OK;
+}
+
+int nfc_multi_transmit_device(nfc_multi *m, const nfc_answers_tx_config *cfg, void *dev_out, size_t cap_samples, uint64_t *first_sample,
+                              uint32_t *n_samples, float *kernel_ms) {
+    if (!m) return NFC_ERR_ARG;
+    LaunchScope scope(&m->launch_err);
+    char msg[256];
+    if (atx::config_fault(cfg, msg, sizeof msg)) return mfail(m, NFC_ERR_ARG, "%s", msg);
+    if (!first_sample || !n_samples) return mfail(m, NFC_ERR_ARG, "first_sample or n_samples is null");
+    if ((uintptr_t)dev_out & 31u) return mfail(m, NFC_ERR_ARG, "dev_out must be 32-byte aligned");
+    if (!m->have_outputs) return mfail(m, NFC_ERR_STATE, "no completed push");
+    if (!m->track || m->cmd_state == nfc_multi::CMD_NONE)
+        return mfail(m, NFC_ERR_STATE, "command tracking was off at the last push (nfc_multi_track_commands), or a stream was reset or set since");
+    if (m->n_cards == 0) return mfail(m, NFC_ERR_STATE, "no stream holds a card (nfc_multi_emulate)");
+    if (m->tx_done) return mfail(m, NFC_ERR_STATE, "the last push was transmitted already: once per push");
+    const uint32_t K = m->K;
+    const atx::Consts C = atx::make_consts(*cfg);
+    // the layout, from the push's own arguments
+    const bool have_answers = m->cmd_state == nfc_multi::CMD_LAUNCHED && m->cmd_emulated;
+    std::vector<atx::StreamIn> streams((size_t)K + 1);
+    uint64_t at = 0, need = 0, n_span = 0;
+    for (uint32_t k = 0; k < K; k++) {
+        atx::StreamIn &S = streams[k];
+        memset(&S, 0, sizeof S);
+        S.role = m->has_card[k] ? (int32_t)m->card_role[k] : -1;
+        S.rx_base = m->g0[k], S.rx_n = m->last_n[k];
+        S.t0 = atx::tx_index(C, S.rx_base);
+        const uint64_t n = S.role < 0 ? 0ull : atx::tx_index(C, S.rx_base + S.rx_n) - S.t0;
+        if (n > atx::MAX_SPAN) return mfail(m, NFC_ERR_ARG, "stream %u: a span of %llu samples exceeds 2^30", k, (unsigned long long)n);
+        S.first_sample = first_sample[k] = at;
+        S.n_samples = n_samples[k] = (uint32_t)n;
+        need = at + n;
+        at += air::align_up(n, C.align);
+        // room in the span table: an answer per command at the most, and the entry carried in
+        uint64_t ncmd = 0;
+        if (have_answers && S.role >= 0) {
+            const uint32_t *c = m->h_counts.as<uint32_t>() + (size_t)k * CNT_WORDS;
+            for (int t = 0; t < 2; t++) ncmd += std::min(c[CNT_PK0 + t], m->C.packets);
+        }
+        S.span_off = (uint32_t)n_span;
+        S.span_cap = S.role < 0 ? 0u : (uint32_t)ncmd + 1u;
+        n_span += S.span_cap;
+    }
+    memset(&streams[K], 0, sizeof(atx::StreamIn));
+    streams[K].first_sample = need, streams[K].role = -1, streams[K].span_off = (uint32_t)n_span;
+    if (need > cap_samples) return mfail(m, NFC_ERR_ARG, "cap_samples: the layout needs %llu samples, %zu do not hold them", (unsigned long long)need, cap_samples);
+    if (need && !dev_out) return mfail(m, NFC_ERR_ARG, "dev_out is null");
+    if (n_span > 0xFFFFFFFFull) return mfail(m, NFC_ERR_ARG, "more than 2^32 span records");
+    if (hipSetDevice(m->P.device) != hipSuccess) return mfail(m, NFC_ERR_DEVICE, "hipSetDevice failed");
+    if (int rc = ensure_txpend(m, "nfc_multi_transmit_device")) return rc;
+    // the call's sections: streams [K + 1] | tile_stream [n_tiles] | spans | n_spans [K]
+    const uint64_t n_tiles = (need + atx::TILE - 1) / atx::TILE;
+    if (n_tiles > 0x7FFFFFFFull) return mfail(m, NFC_ERR_ARG, "cap_samples: more than 2^31 tiles");
+    Sections S{0, {}};
+    uint64_t o_streams, o_tiles, o_spans, o_ns, e_streams, e_tiles, e_spans, e_ns;
+    S.place(o_streams, e_streams, ((size_t)K + 1) * sizeof(atx::StreamIn));
+    S.place(o_tiles, e_tiles, (size_t)n_tiles * 4);
+    S.place(o_spans, e_spans, (size_t)n_span * sizeof(atx::Span));
+    S.place(o_ns, e_ns, (size_t)K * 4);
+    if (int rc = grow_packed(m, m->tx, S.at, "nfc_multi_transmit_device")) return rc;
+    const size_t up_bytes = (size_t)o_spans;   // the two sections the host makes, guards and all
+    if (grow(m, m->h_tx, up_bytes, "nfc_multi_transmit_device") < 0) return NFC_ERR_NOMEM;
+    if (kernel_ms)
+        for (Event &e : m->evt)
+            if (!e && e.create() != hipSuccess) {
+                (void)hipGetLastError();
+                return mfail(m, NFC_ERR_DEVICE, "hipEventCreate failed");
+            }
+    uint8_t *h = m->h_tx.as<uint8_t>(), *d = m->tx.d.as<uint8_t>();
+    memset(h, 0, up_bytes);
+    memcpy(h + o_streams, streams.data(), ((size_t)K + 1) * sizeof(atx::StreamIn));
+    {   // per tile the first stream whose part of the buffer, the padding behind it included, reaches into the tile
+        uint32_t *tile = (uint32_t *)(h + o_tiles);
+        uint32_t k = 0;
+        for (uint64_t t = 0; t < n_tiles; t++) {
+            while (k + 1 < K && streams[k + 1].first_sample <= t * atx::TILE) k++;
+            tile[t] = k;
+        }
+    }
+    MCHK(m, hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, m->st));
+    atx::ScheduleArgs SA;
+    memset(&SA, 0, sizeof SA);
+    SA.C = C;
+    if (have_answers) {
+        const commands::Layout &L = m->cmd_lay;
+        const commands::EmuArgs &E = m->cmd_emu;
+        const frames::MultiLayout &F = m->cmd_frlay;
+        atx::Tracked &T = SA.T;
+        T.buf = m->cmd.d.as<uint8_t>();
+        T.table = (const uint64_t *)(T.buf + frames::MULTI_HEADER_BYTES);
+        for (int t = 0; t < 2; t++) T.at_fr[t] = F.at_fr[t], T.total_frames[t] = F.total_frames[t];
+        T.at_cmd_off = L.at[commands::SEC_CMD_OFF], T.at_src = L.at[commands::SEC_SRC], T.total_cmds = L.total_cmds;
+        T.at_ans_n = E.at[commands::ESEC_N], T.at_ans = E.at[commands::ESEC_REC], T.at_air = E.at[commands::ESEC_AIR], T.at_par = E.at[commands::ESEC_PAR];
+    }
+    SA.streams = (const atx::StreamIn *)(d + o_streams);
+    SA.spans = (atx::Span *)(d + o_spans);
+    SA.n_spans = (uint32_t *)(d + o_ns);
+    SA.pending = m->txpend.d.as<nfc_tx_pending>();
+    SA.K = K;
+    SA.packed = d;
+    SA.guard_at[0] = e_streams, SA.guard_at[1] = e_tiles, SA.guard_at[2] = e_spans, SA.guard_at[3] = e_ns;
+    SA.guard_word = GUARD_WORD, SA.guard_bytes = GUARD_BYTES;
+    const bool timed = kernel_ms != nullptr;
+    NFC_LAUNCH_EXT(atx::k_answers_tx_schedule, dim3((K + atx::SCHED_BLOCK - 1) / atx::SCHED_BLOCK), dim3(atx::SCHED_BLOCK), 0, m->st,
+                   timed ? (hipEvent_t)m->evt[0] : nullptr, timed ? (hipEvent_t)m->evt[1] : nullptr, 0, SA);
+    m->tx.guards = std::move(S.guards);
+    uint32_t launches = 1;
+    if (n_tiles) {
+        atx::RenderArgs RA;
+        memset(&RA, 0, sizeof RA);
+        RA.C = C;
+        RA.streams = SA.streams, RA.tile_stream = (const uint32_t *)(d + o_tiles), RA.spans = SA.spans, RA.n_spans = SA.n_spans;
+        RA.K = K, RA.total = need, RA.out = (float2 *)dev_out;
+        NFC_LAUNCH_EXT(atx::k_answers_tx_render, dim3((unsigned)n_tiles), dim3(atx::BLOCK), 0, m->st, timed ? (hipEvent_t)m->evt[2] : nullptr,
+                       timed ? (hipEvent_t)m->evt[3] : nullptr, 0, RA);
+        launches++;
+    }
+    if (int rc = launch_ok(m)) return rc;
+    m->tx_done = true;
+    m->stats.n_launches += launches;
+    if (timed) {
+        kernel_ms[0] = kernel_ms[1] = 0.f;
+        MCHK(m, hipStreamSynchronize(m->st));
+        MCHK(m, hipEventElapsedTime(&kernel_ms[0], m->evt[0], m->evt[1]));
+        if (n_tiles) MCHK(m, hipEventElapsedTime(&kernel_ms[1], m->evt[2], m->evt[3]));
+    }
+    return NFC_OK;
+}
+
 int nfc_multi_get_stats(nfc_multi *m, nfc_multi_stats *out) {
     if (!m) return NFC_ERR_ARG;
     if (!out) return mfail(m, NFC_ERR_ARG, "null output");
@@ -1484,7 +1687,7 @@ extern "C" int nfc_debug_multi_guards(nfc_multi *m) {
     if (launch_ok(m) || hipMemcpyAsync(m->h_blob.p, bad, 4, hipMemcpyDeviceToHost, m->st) != hipSuccess || hipStreamSynchronize(m->st) != hipSuccess) return -1;
     memcpy(&h, m->h_blob.p, 4);
     // ... and the guards behind the sections of the three packed buffers, where the launches that last filled each left them
-    for (const Packed *p : {&m->fetch, &m->frames, &m->cmd}) {
+    for (const Packed *p : {&m->fetch, &m->frames, &m->cmd, &m->txpend, &m->tx}) {
         const int bad_bytes = packed_guards_damaged(m, *p);
         if (bad_bytes < 0) return -1;
         h += (uint32_t)bad_bytes;

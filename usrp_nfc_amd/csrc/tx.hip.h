@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/nfc_amd.h"
+#include "tx_sample.hip.h"
 
 namespace nfc {
 
@@ -118,18 +119,7 @@ __global__ __launch_bounds__(TX_BLOCK) void k_tx_render(TxArgs A) {
     const uint64_t s0 = t0 + (uint64_t)threadIdx.x * TX_PER_THREAD;
     if (s0 >= t1) return;
     float2 v[TX_PER_THREAD];
-    auto sample = [&](uint64_t s, float lvl) {
-        float re = lvl, im = 0.f;
-        if (A.carrier) {
-            const uint64_t ph = (A.first_index + s) * A.phase_inc;
-            const float turn = (float)(uint32_t)(ph >> 40) * 5.9604644775390625e-08f;   // top 24 bits: [0, 1) exactly
-            float sn, cs;
-            sincospif(2.0f * turn, &sn, &cs);
-            re = lvl * (A.amp * cs);
-            im = lvl * (A.amp * sn);
-        }
-        return make_float2(re, im);
-    };
+    auto sample = [&](uint64_t s, float lvl) { return tx_sample(A.first_index + s, A.phase_inc, A.amp, A.carrier, lvl); };
     if (staged) {   // the tile's runs from LDS
         uint32_t r = tx_find_run(s_ends, 0u, nr, s0);
         uint64_t end = s_ends[r];

@@ -171,6 +171,85 @@ def host_emulate(card, emu_state, fsm_state, frames, data=None, par=None, sector
     return (out, buf[:used.value], enc[:used.value]), Answers(ans[:n_ans.value], ap, aa, aq)
 
 
+def tx_inputs(commands, answers):
+    """What fetch_commands() and fetch_answers() brought of one push, as host_transmit takes it: per stream (records, air, par) of its
+    answers and, per answer, the idx of the raw frame of the command it answers (commands.raw and commands.src) -> (answers, frames_idx)."""
+    out, idx = [], []
+    raw = commands.raw
+    for k in range(answers.n_streams):
+        rec, _, air, par = answers.answers_of(k)
+        out.append((rec, air, par))
+        if len(rec) == 0:
+            idx.append(np.zeros(0, np.uint64))
+            continue
+        t, i = commands.src_of(k)
+        t, i = t[rec['src'].astype(np.int64)], i[rec['src'].astype(np.int64)]
+        idx.append(np.array([raw.frames[int(a)][int(raw.frame_off[int(a)][k]) + int(b)]['idx'] for a, b in zip(t, i)], np.uint64))
+    return out, idx
+
+
+def host_transmit(answers, frames_idx, roles, rx_base, rx_n, pending=None, out=None, cap_samples=None, **kw):
+    """The CPU twin of NfcMultiContext.transmit (nfc_host_answers_tx), one push of K streams.  answers[k]: (records, air, par) of stream
+    k's answers -- records with byte_off and n_bits (EMU_ANSWER_DTYPE: what answers_of(k) and host_emulate's Answers hold), their bytes in
+    air / par -- or None; frames_idx[k]: per answer the idx of the answered command's raw frame, in the stream's own sample count;
+    roles[k]: NFC_EMU_TAG, NFC_EMU_READER or None (no card); the push gave stream k the samples [rx_base[k], rx_base[k] + rx_n[k]).
+    pending: the TX_PENDING_DTYPE array an earlier call returned (None: no stream has a pending answer).  kw: transmit's keywords.
+    out: a complex64 array to render into (cap_samples: how much of it the call may use, default all of it); None: one of the needed
+    size.  -> (samples, first_sample, n_samples, pending): the layout's complex64 samples and the advanced pending entries."""
+    from . import tx
+    K = len(roles)
+    cfg = kw.pop('cfg', None) or tx.answers_tx_config(**kw)   # (cfg: an _lib.AnswersTxConfig made by hand, in place of the keywords)
+    role = np.array([-1 if r is None else int(r) for r in roles], np.int32)
+    base, n = np.ascontiguousarray(rx_base, np.uint64), np.ascontiguousarray(rx_n, np.uint32)
+    if base.size != K or n.size != K or len(answers) != K or len(frames_idx) != K:
+        raise ValueError('host_transmit: one entry per stream in answers, frames_idx, roles, rx_base and rx_n')
+    ans_off, byte_base = np.zeros(K + 1, np.uint32), np.zeros(K + 1, np.uint32)
+    recs, airs, pars = [], [], []
+    for k in range(K):
+        rec, air, par = answers[k] if answers[k] is not None else (np.zeros(0, _lib.EMU_ANSWER_DTYPE), [], [])
+        air, par = np.ascontiguousarray(air, np.uint8).reshape(-1), np.ascontiguousarray(par, np.uint8).reshape(-1)
+        r = np.zeros(len(rec), _lib.TX_ANSWER_DTYPE)
+        if len(rec):
+            r['idx'], r['byte_off'], r['n_bits'] = np.asarray(frames_idx[k], np.uint64), rec['byte_off'], rec['n_bits']
+        recs.append(r), airs.append(air), pars.append(par)
+        ans_off[k + 1], byte_base[k + 1] = ans_off[k] + len(r), byte_base[k] + max(air.size, par.size)
+        if air.size != par.size:
+            raise ValueError('host_transmit: stream %d: air and par differ in length' % k)
+    rec = np.concatenate(recs) if K else np.zeros(0, _lib.TX_ANSWER_DTYPE)
+    air = np.concatenate(airs + [np.zeros(1, np.uint8)])
+    par = np.concatenate(pars + [np.zeros(1, np.uint8)])
+    pend = np.zeros(K, _lib.TX_PENDING_DTYPE) if pending is None else np.array(pending, _lib.TX_PENDING_DTYPE)
+    if pend.shape != (K,):
+        raise ValueError('host_transmit: pending has one entry per stream')
+    first, ns = np.zeros(K, np.uint64), np.zeros(K, np.uint32)
+    L = _lib.load()
+    ptr = lambda a: a.ctypes.data if a.size else None
+    call = lambda o, cap: L.nfc_host_answers_tx(C.byref(cfg), K, ptr(role), ptr(base), ptr(n), ans_off.ctypes.data, ptr(rec), air.ctypes.data, par.ctypes.data,
+                                                byte_base.ctypes.data, ptr(pend), o, int(cap), ptr(first), ptr(ns))
+    rc = call(None, 0)
+    if rc != 0:
+        _tx_fail(rc, pend)
+    need = int(first[-1]) + int(ns[-1]) if K else 0
+    if out is None:
+        out = np.zeros(max(need, 1), np.complex64)
+        cap_samples = need
+    elif cap_samples is None:
+        cap_samples = out.size
+    if out.dtype != np.complex64 or not out.flags['C_CONTIGUOUS'] or cap_samples > out.size:
+        raise ValueError('host_transmit: out is a contiguous complex64 array of at least cap_samples entries')
+    rc = call(out.ctypes.data, cap_samples)
+    if rc != 0:
+        _tx_fail(rc, pend)
+    return out[:need], first, ns, pend
+
+
+def _tx_fail(rc, pending):
+    msg = _lib.load().nfc_last_error(None)
+    e = (ValueError if rc == -1 else EmulationError)('nfc_host_answers_tx status %d: %s' % (rc, (msg or b'').decode()))
+    e.pending = pending   # the entries as the failed call left them
+    raise e
+
+
 def synth_frames(transcript):
     """(type, on-air bits) per stored frame: synth.transaction_frames"""
     return [(int(f['type']), transcript.bits(i)) for i, f in enumerate(transcript.frames)]

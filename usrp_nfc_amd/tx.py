@@ -62,6 +62,73 @@ def render_device(runs, samp_rate, dev_ptr, cap_samples, carrier=False, freq=13.
     return int(n.value), (float(ms.value) if timed else None)
 
 
+def answers_tx_config(samp_rate=2e6, in_rate=None, delay_us=0.0, carrier=False, freq=13.56e6, amp=1.0, first_index=0, align_samples=8,
+                      _reserved=0):
+    """The nfc_answers_tx_config of NfcMultiContext.transmit / emulate.host_transmit: the ratio of the two rates from
+    fractions.Fraction (in_rate None: the same rate, 1/1), delay_samples = int(delay_us * samp_rate / 1e6)."""
+    from fractions import Fraction
+    ratio = Fraction(1) if in_rate is None else Fraction(samp_rate) / Fraction(in_rate)
+    if ratio.numerator >= 1 << 32 or ratio.denominator >= 1 << 32:
+        raise ValueError('samp_rate / in_rate: neither term of the reduced ratio fits 32 bits')
+    c = _lib.AnswersTxConfig(float(samp_rate), float(freq), int(first_index), int(delay_us * samp_rate / 1e6), ratio.numerator, ratio.denominator,
+                             1 if carrier else 0, float(amp), int(align_samples))
+    c.reserved[0] = int(_reserved)   # (must be 0: the argument only lets a test see the library refuse it)
+    return c
+
+
+class TxCaptures(object):
+    """K TX captures in one device buffer (NfcMultiContext.transmit): stream k's complex64 samples are the n_samples[k] entries from
+    first_sample[k] on.  `buf` is the device buffer, owned (and freed by free()) unless the caller gave it; kernel_ms: with timed=True the
+    schedule and the render pass, by HIP events.  The rendering is only ENQUEUED on the context's stream: wait() completes it (download
+    and record do so themselves); work of another stream or context that reads the buffer comes after a wait()."""
+
+    def __init__(self, first_sample, n_samples, buf, owned, samp_rate, device=0, kernel_ms=None, multi=None):
+        self.first_sample, self.n_samples, self.buf, self.owned = first_sample, n_samples, buf, owned
+        self.samp_rate, self.device, self.kernel_ms, self._multi = float(samp_rate), int(device), kernel_ms, multi
+
+    def wait(self):
+        """Complete the rendering (nfc_multi_get_tx_state completes the context's stream before it reads)."""
+        if self._multi is not None and getattr(self._multi, 'h', None):
+            self._multi.tx_state(0)
+        return self
+
+    def __len__(self):
+        return len(self.n_samples)
+
+    @property
+    def total(self):
+        """samples of the layout: first_sample[K-1] + n_samples[K-1]"""
+        return int(self.first_sample[-1]) + int(self.n_samples[-1]) if len(self.n_samples) else 0
+
+    def ptr(self, k=None):
+        """The device address of the buffer (k None) or of stream k's first sample."""
+        from . import api
+        base = api._as_pointer(self.buf).value or 0
+        return C.c_void_p(base + (0 if k is None else 8 * int(self.first_sample[k])))
+
+    def download(self, k=None):
+        """Stream k's samples (k None: the whole layout, padding included) as a complex64 array."""
+        first, n = (0, self.total) if k is None else (int(self.first_sample[k]), int(self.n_samples[k]))
+        out = np.zeros(n, np.complex64)
+        self.wait()
+        if n and _lib.load().nfc_device_download(self.device, out.ctypes.data, C.c_void_p((self.ptr().value or 0) + 8 * first), 8 * n) != 0:
+            raise RuntimeError('nfc_device_download failed')
+        return out
+
+    def record(self, k, path, gain=32767.0):
+        """Stream k's real part as a 16-bit WAV, converted on the GPU (record.record(path).write_device).  Needs first_sample[k] on 16
+        bytes: an even align_samples."""
+        from . import record
+        self.wait()
+        with record.record(path, self.samp_rate, gain, self.device) as w:
+            return w.write_device(self.ptr(k), int(self.n_samples[k]))
+
+    def free(self):
+        if self.owned and self.buf is not None:
+            self.buf.free()
+        self.buf = None
+
+
 def render(runs, samp_rate, carrier=False, freq=13.56e6, amp=1.0, first_index=0, device=0):
     """Render on the GPU and bring the samples back: complex64 array."""
     from . import api
