@@ -52,6 +52,8 @@ extern "C" {
  *  nfc_emu_last_error, nfc_host_emu_step, nfc_host_emulate, nfc_emu_answer, nfc_host_emulate_pairs, nfc_emulate_pairs_device,
  *  nfc_multi_emulate, nfc_multi_fetch_answers, nfc_multi_answers, nfc_multi_get_emu_state, nfc_multi_set_emu_state) */
 /* (still 4, only new names: nfc_air_frame, nfc_air_config, nfc_host_air_render, nfc_air_render_device) */
+/* (still 4, only new names: nfc_reader_pair, nfc_reader_key_result, nfc_reader_key_config, NFC_RKEY_VERIFY_INLINE, nfc_find_reader_auths,
+ *  nfc_host_recover_reader_keys, nfc_recover_reader_keys_device) */
 #define NFC_AMD_ABI_VERSION 4
 
 typedef enum {
@@ -705,7 +707,7 @@ int nfc_multi_get_sector_keys(nfc_multi *m, uint32_t stream, nfc_fsm_key_table *
  * A 32-bit word of a frame has bit i = bit (i & 7) of byte (i >> 3) -- byte 0 lowest.  par: bit i the ninth bit, as received, of byte i of
  * {nr}{ar} (i = 0 .. 7) and of byte i - 8 of {at} (i = 8 .. 11).  40 bytes: five words, the parity bits, key type and block, stream and
  * frame as 32-bit counts and the 64-bit sample index at their natural widths.
- * NOT PROMISED: recovery without {at}, 7-byte UIDs.  (Nested authentications, whose nt is encrypted, are not nfc_find_auths' but
+ * NOT PROMISED: 7-byte UIDs.  (Without {at}: two authentications of one key, nfc_recover_reader_keys_device below.)  (Nested authentications, whose nt is encrypted, are not nfc_find_auths' but
  * nfc_find_nested_auths': the section below.) */
 typedef struct nfc_auth_trace {
     uint32_t uid, nt, nr_enc, ar_enc, at_enc;
@@ -775,8 +777,8 @@ int nfc_recover_keys_device(int device, const nfc_auth_trace *traces, size_t n, 
  * nfc_nested_trace, 40 bytes in nfc_auth_trace's layout with nt_enc for nt.  par: bits 0 .. 11 as in nfc_auth_trace, bits 12 .. 15 the
  * ninth bits, as received, of {nt} bytes 0 .. 3.  key_type / block: 0 / 0xFF while the AUTH command is not known in plaintext (the
  * search reads neither).
- * NOT PROMISED: cards whose nested nonces are not on the 16-bit sequence (no candidates: NFC_KEY_NONE with n_nt 0), recovery without
- * {at}, 7-byte UIDs, a search that uses ks1 alone. */
+ * NOT PROMISED: cards whose nested nonces are not on the 16-bit sequence (no candidates: NFC_KEY_NONE with n_nt 0), a nested {nt} without
+ * {at} (the reader-pair search below takes first authentications only), 7-byte UIDs, a search that uses ks1 alone. */
 typedef struct nfc_nested_trace {
     uint32_t uid, nt_enc, nr_enc, ar_enc, at_enc;
     uint16_t par;
@@ -829,6 +831,61 @@ int nfc_host_recover_nested_keys(const nfc_nested_trace *traces, size_t n, const
                                  nfc_key_stats *stats);
 int nfc_recover_nested_keys_device(int device, const nfc_nested_trace *traces, size_t n, const nfc_nested_config *cfg,
                                    nfc_nested_result *out, nfc_key_stats *stats);
+
+/* ---- key recovery from TWO reader-side authentications, without {at} (the "reader attack") ------------------------------------------
+ * A stream that emulates a tag, or a sniffer that hears the reader only, gets nt and {nr}{ar} of a first authentication but no genuine
+ * {at}.  ks2 = {ar} ^ suc64(nt) alone is 32 known keystream bits: about 2^16 registers fit ONE such authentication; a second one with
+ * the same key and another nt or nr singles one out.  The search is the one above at half the depth (16 keystream bits per half, a
+ * 22-bit signature: csrc/keys.hip.h); about 1e5 candidates join and each is checked against both sessions: the key must
+ * decrypt {nr} to four right ninth bits, reproduce ar, and fit the four ninth bits of {ar} (the last under ks3 bit 0) -- in the SEARCHED
+ * session, whose keystream started the search, and in the CHECK session.
+ * PROMISED: pairs only; 4-byte UIDs; first authentications only (nt in the clear).  The two UIDs may differ: a UID enters only as
+ * uid ^ nt.  at_enc and par bits 8 .. 11 of both traces are ignored.
+ * NOT PROMISED: a single authentication without {at} (about 2^16 keys fit); a nested {nt} without {at}; 7-byte UIDs.
+ * Two IDENTICAL sessions (same uid ^ nt, same {nr}{ar}) cannot single a key out: every register that fits the one fits the other, and
+ * the result is NFC_KEY_AMBIGUOUS with n_candidates > 1 (keys.pair_reader_auths never pairs two such).
+ * COST (MI355X, measured: profiles/reader_keys_bench.json): 1.60 ms per pair at 256 pairs and 1.68 ms at 16 (5.7 ms for a
+ * single pair), against 214 ms for the twin on one core and 4.74 ms per authentication for the full search above on the same sessions
+ * with their {at}; with NFC_RKEY_VERIFY_INLINE 3.31 ms and 3.67 ms.  Device memory: the tables as above plus max_batch x
+ * stage_capacity x 8 bytes (32 MiB at the defaults). */
+typedef struct nfc_reader_pair {   /* 80 bytes */
+    nfc_auth_trace search, check;
+} nfc_reader_pair;
+typedef struct nfc_reader_key_result { /* 32 bytes */
+    uint8_t key[6];
+    uint8_t status;                /* NFC_KEY_*; AMBIGUOUS reports the lowest key; OVERFLOW as above: nothing searched, n_odd / n_even exact */
+    uint8_t pad;
+    uint32_t n_candidates;         /* joined candidates that passed both sessions, saturating */
+    uint32_t n_joined;             /* pairs of sequences with equal signatures: what was verified */
+    uint32_t n_odd, n_even;        /* the exact sizes of the two lists */
+    uint32_t nr_search, nr_check;  /* the decrypted reader nonces of the two sessions under `key` (0 without a key) */
+} nfc_reader_key_result;
+/* search: as for first authentications, its limits and defaults; capacity counts table slots and max_batch pairs.  stage_capacity: the
+ * joined candidates per pair that the probe launch hands to the verify launch (8 bytes each, max_batch sections); 0: the default,
+ * 2^18.  A pair that joins more verifies the rest where they were found: the result does not depend on stage_capacity.  Above 2^24 is
+ * NFC_ERR_ARG.  NFC_RKEY_VERIFY_INLINE: no stage and no verify launch, every candidate is verified by the lane that found it (the form
+ * of the full search; kept for comparison).  Unknown flags or non-zero reserved words are NFC_ERR_ARG. */
+enum { NFC_RKEY_VERIFY_INLINE = 1 };
+typedef struct nfc_reader_key_config { /* 48 bytes */
+    nfc_key_config search;
+    uint32_t stage_capacity;
+    uint32_t flags;
+    uint32_t reserved[2];
+} nfc_reader_key_config;
+/* Host only, nfc_find_auths' arguments and rule LESS its fourth frame: the UID of the last NFC_RAW_CRC_A_OK 93 70 .., a plain
+ * NFC_RAW_CRC_A_OK 60|61 blk crc, a tag frame of 4 bytes with NFC_RAW_PARITY_OK, a reader frame of 8 bytes, consecutive and none
+ * NFC_RAW_CUT.  What follows is not looked at -- no {at}, a noise {at}, the end of the list -- so by `frame` the result is a superset
+ * of nfc_find_auths'.  at_enc and par bits 8 .. 11 are written 0. */
+int nfc_find_reader_auths(const nfc_raw_frame *frames, size_t n, const uint8_t *bytes0, const uint8_t *par0, const uint8_t *bytes1,
+                          const uint8_t *par1, nfc_auth_trace *out, size_t cap, size_t *n_out);
+/* The CPU twin and the device call, as nfc_host_recover_keys / nfc_recover_keys_device: the same batching and capacity rules over
+ * pairs, the same statuses and statistics by construction.  Per group a fill launch, a probe launch and -- unless
+ * NFC_RKEY_VERIFY_INLINE -- a verify launch, whose time counts in ms_probe.  n == 0 launches nothing and touches no device; every
+ * argument (key_type of all four traces included) is checked before the device is touched; no CPU fallback.  cfg and stats may be NULL. */
+int nfc_host_recover_reader_keys(const nfc_reader_pair *pairs, size_t n, const nfc_reader_key_config *cfg, nfc_reader_key_result *out,
+                                 nfc_key_stats *stats);
+int nfc_recover_reader_keys_device(int device, const nfc_reader_pair *pairs, size_t n, const nfc_reader_key_config *cfg,
+                                   nfc_reader_key_result *out, nfc_key_stats *stats);
 
 /* ---- emulation: a tag machine and a reader machine, and K cards read by K readers with no signal at all ---------------------------
  * The reference's second half (tag.py, reader.py, the closed loop of usrp_nfc.py:116-136), one text for host and device

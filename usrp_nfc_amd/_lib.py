@@ -100,6 +100,10 @@ class NestedConfig(C.Structure):   # nfc_nested_config
     _fields_ = [('search', KeyConfig), ('cand_first', C.c_uint32), ('cand_count', C.c_uint32), ('reserved', C.c_uint32 * 2)]
 
 
+class ReaderKeyConfig(C.Structure):   # nfc_reader_key_config
+    _fields_ = [('search', KeyConfig), ('stage_capacity', C.c_uint32), ('flags', C.c_uint32), ('reserved', C.c_uint32 * 2)]
+
+
 class EmuState(C.Structure):   # nfc_emu_state
     _fields_ = [('halted', C.c_int32), ('selected', C.c_int32), ('auth', C.c_int32), ('auth_key', C.c_int32), ('auth_prosp', C.c_int32),
                 ('at_set', C.c_int32), ('at', C.c_uint8 * 4), ('rand_idx', C.c_uint32), ('tag_type', C.c_int32), ('cur_addr', C.c_int32),
@@ -204,6 +208,11 @@ NESTED_RESULT_DTYPE = np.dtype([('key', 'u1', (6,)), ('status', 'u1'), ('reserve
 NESTED_CANDS = 64
 NFC_KEY_OK, NFC_KEY_NONE, NFC_KEY_AMBIGUOUS, NFC_KEY_OVERFLOW = 0, 1, 2, 3
 NFC_KEY_TIMING = 1
+# nfc_reader_pair: two reader-side first authentications of one key (at_enc and par bits 8 .. 11 ignored), and nfc_reader_key_result
+READER_PAIR_DTYPE = np.dtype([('search', AUTH_DTYPE), ('check', AUTH_DTYPE)])
+READER_KEY_RESULT_DTYPE = np.dtype([('key', 'u1', (6,)), ('status', 'u1'), ('pad', 'u1'), ('n_candidates', '<u4'), ('n_joined', '<u4'), ('n_odd', '<u4'),
+                                    ('n_even', '<u4'), ('nr_search', '<u4'), ('nr_check', '<u4')])
+NFC_RKEY_VERIFY_INLINE = 1
 COUNTS_DTYPE = np.dtype([('n_samples', '<u8'), ('n_edges', '<u8'), ('n_symbols', '<u8', (2,)), ('n_packets', '<u8', (2,)),
                          ('n_packet_bits', '<u8', (2,))])   # nfc_counts
 
@@ -227,6 +236,7 @@ SYMBOLS = ['nfc_abi_version', 'nfc_device_count', 'nfc_create', 'nfc_destroy', '
            'nfc_find_auths', 'nfc_host_recover_keys', 'nfc_recover_keys_device',
            'nfc_find_nested_auths', 'nfc_host_nested_candidates', 'nfc_nested_candidates_device', 'nfc_host_recover_nested_keys',
            'nfc_recover_nested_keys_device',
+           'nfc_find_reader_auths', 'nfc_host_recover_reader_keys', 'nfc_recover_reader_keys_device',
            'nfc_emu_state_init', 'nfc_emu_last_error', 'nfc_host_emu_step', 'nfc_host_emulate', 'nfc_multi_emulate', 'nfc_multi_fetch_answers', 'nfc_multi_get_emu_state',
            'nfc_multi_set_emu_state', 'nfc_host_emulate_pairs', 'nfc_emulate_pairs_device',
            'nfc_host_air_render', 'nfc_air_render_device',
@@ -371,6 +381,9 @@ def load(path=None):
     L.nfc_nested_candidates_device.argtypes = [C.c_int, vp, sz, vp, vp]
     L.nfc_host_recover_nested_keys.argtypes = [vp, sz, C.POINTER(NestedConfig), vp, C.POINTER(KeyStats)]
     L.nfc_recover_nested_keys_device.argtypes = [C.c_int, vp, sz, C.POINTER(NestedConfig), vp, C.POINTER(KeyStats)]
+    L.nfc_find_reader_auths.argtypes = [vp, sz, vp, vp, vp, vp, vp, sz, psz]
+    L.nfc_host_recover_reader_keys.argtypes = [vp, sz, C.POINTER(ReaderKeyConfig), vp, C.POINTER(KeyStats)]
+    L.nfc_recover_reader_keys_device.argtypes = [C.c_int, vp, sz, C.POINTER(ReaderKeyConfig), vp, C.POINTER(KeyStats)]
     L.nfc_emu_state_init.argtypes = [C.POINTER(EmuState)]
     L.nfc_emu_last_error.restype = C.c_char_p
     L.nfc_host_emu_step.argtypes = [C.POINTER(EmuCard), C.POINTER(EmuState), C.c_int, vp, sz, C.POINTER(C.c_int), vp, psz]

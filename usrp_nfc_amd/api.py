@@ -442,19 +442,27 @@ class NfcMultiContext(object):
         self._chk(self.L.nfc_multi_get_sector_keys(self.h, int(k), C.byref(t)), 'nfc_multi_get_sector_keys')
         return keys.table_dict(t)
 
-    def recover_keys(self, nested=False, **cfg):
+    def recover_keys(self, nested=False, reader_pairs=False, **cfg):
         """The sector keys of the last push's first authentications: fetch_frames() + NfcMultiFrames.auths() + ONE keys.recover call on
         this context's device (cfg: keys.recover's).  -> per stream a dict (key_type, block) -> six key bytes (keys.keys_by_stream).
         nested=True: the nested authentications too (keys.recover_streams: one more call, keys.recover_nested, and keys.label_auths per
-        stream), so the dicts also hold every later sector's key whose AUTH command could be decrypted."""
+        stream), so the dicts also hold every later sector's key whose AUTH command could be decrypted.
+        reader_pairs: True, or a dict of keys.recover_reader's OWN options (stage_capacity, verify_inline) -- the first authentications
+        that are left without a key (no {at}, or a noise one) are paired and searched besides (keys.recover_reader_streams: ONE more
+        call, with the same cfg)."""
         from . import keys
         if nested:
             fr = self.fetch_frames()
             have = (np.diff(fr.frame_off[0]) > 0) & (np.diff(fr.frame_off[1]) > 0)
-            return keys.recover_streams([fr.frames_of(k) if have[k] else None for k in range(self.n_streams)], device=self.device, **cfg)
-        traces = self.fetch_frames().auths()
+            return keys.recover_streams([fr.frames_of(k) if have[k] else None for k in range(self.n_streams)], device=self.device,
+                                        reader_pairs=reader_pairs, **cfg)
+        fr = self.fetch_frames()
+        traces = fr.auths()
         results, _ = keys.recover(traces, device=self.device, **cfg)
-        return keys.keys_by_stream(traces, results, self.n_streams)
+        found = keys.keys_by_stream(traces, results, self.n_streams)
+        if reader_pairs:
+            found = keys.recover_reader_streams(fr.reader_auths(), found, device=self.device, **keys.reader_options(reader_pairs, cfg))
+        return found
 
     def fsm_state(self, k):
         """Stream k's protocol machine as a plain nfc_fsm_state (an _lib.FsmState): what fsm.set_state takes."""
@@ -875,6 +883,17 @@ class NfcMultiFrames(object):
         parts = []
         for k in np.nonzero((np.diff(self.frame_off[0]) > 0) & (np.diff(self.frame_off[1]) > 0))[0]:
             a = keys.find_auths(self.frames_of(int(k)))
+            a['stream'] = int(k)
+            parts.append(a)
+        return np.concatenate(parts) if parts else np.zeros(0, _lib.AUTH_DTYPE)
+
+    def reader_auths(self):
+        """Every stream's first authentications as far as the reader's {nr}{ar} (keys.find_reader_auths per stream, in stream order) as
+        ONE AUTH_DTYPE array, `stream` filled in: what keys.pair_reader_auths and keys.recover_reader_streams take."""
+        from . import keys
+        parts = []
+        for k in np.nonzero((np.diff(self.frame_off[0]) > 0) & (np.diff(self.frame_off[1]) > 0))[0]:
+            a = keys.find_reader_auths(self.frames_of(int(k)))
             a['stream'] = int(k)
             parts.append(a)
         return np.concatenate(parts) if parts else np.zeros(0, _lib.AUTH_DTYPE)

@@ -24,6 +24,12 @@
 // {at} are encrypted with keystream bits that follow from the candidate alone (nested_candidate): 64 seeds pass, or none.
 // k_nested_candidates writes the survivors as Prepared records in ascending seed order; the three search kernels run over (nested
 // trace, candidate) pairs -- virtual traces -- through an index (`map`), and verify additionally asks for ks1 and the {nt} ninth bits.
+//
+// READER PAIRS.  Without {at} only ks_64 .. ks_95 are known: the same walk and join at half the depth (walk<16>, a 22-bit
+// signature) leave about 1e5 joined candidates, and a SECOND session of the same key decides (verify_pair).  The searches are KINDS
+// (FullKind, PairKind) and the kernels templates over a kind; the pair kind's probe stages the joined registers for
+// k_keys_verify_stage instead of verifying inside the walk's loop.
+// NOT PROMISED: a single authentication without {at}, a nested {nt} without {at}, 7-byte UIDs.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -61,19 +67,19 @@ constexpr uint64_t sig_base(int half, int p) {
 }
 constexpr uint64_t SIG_O0 = sig_base(0, 0), SIG_O1 = sig_base(0, 1), SIG_E0 = sig_base(1, 0), SIG_E1 = sig_base(1, 1);
 NFC_HD uint64_t parity64(uint64_t x) { return (uint64_t)(__builtin_popcountll(x) & 1); }
-template <int HALF>
+template <int HALF, int NREL = N_REL>
 NFC_HD uint64_t signature(uint64_t seq) {
     constexpr uint64_t B0 = HALF ? SIG_E0 : SIG_O0, B1 = HALF ? SIG_E1 : SIG_O1;
     uint64_t s = 0;
 #pragma unroll
-    for (int i = 0; i < N_REL / 2; i++) s |= parity64((seq >> i) & B0) << (2 * i) | parity64((seq >> i) & B1) << (2 * i + 1);
+    for (int i = 0; i < NREL / 2; i++) s |= parity64((seq >> i) & B0) << (2 * i) | parity64((seq >> i) & B1) << (2 * i + 1);
     return s;
 }
 
 // The extensions of one starting window, depth first and iteratively.  `seq` holds the sequence (bit j = O_j or E_j) AND the branches
 // tried: at depth k the candidate bit is bit k + 19, 0 first, then 1; every bit above it is 0.  No array, so no scratch memory.
-// emit(seq) sees every complete 51-bit sequence; -> how many there were.
-template <class Emit>
+// emit(seq) sees every complete sequence (DEPTH keystream bits: 19 + DEPTH places, 51 for the full search); -> how many there were.
+template <int DEPTH = N_KS, class Emit>
 NFC_HD uint32_t walk(uint32_t window, uint32_t ks, Emit &&emit) {
     if (filter20(window) != (ks & 1u)) return 0u;
     uint64_t seq = window;
@@ -81,7 +87,7 @@ NFC_HD uint32_t walk(uint32_t window, uint32_t ks, Emit &&emit) {
     uint32_t n = 0;
     for (;;) {
         if (filter20((uint32_t)(seq >> k) & (WINDOWS - 1u)) == ((ks >> k) & 1u)) {
-            if (k < N_KS - 1) {
+            if (k < DEPTH - 1) {
                 k++;
                 continue;
             }
@@ -214,6 +220,79 @@ NFC_HD bool verify(uint64_t key, const Prepared &P, uint32_t *nr_out) {
     return !bad && (P.ar_enc ^ ks2) == P.ar && (P.at_enc ^ ks3) == P.at;
 }
 
+// ---- reader pairs: two authentications WITHOUT {at} ----
+// Only ks_64 .. ks_95 are known: per half k = 0 .. 15, a 35-bit sequence, and the relations whose places all lie in the two sequences
+// are t = 73 .. 94: a 22-bit signature.  About 1e5 pairs join; the register at clock 73 still needs only O_0 .. O_23 / E_0 .. E_23, so
+// rollback is the full search's.  What singles the key out is a SECOND session of the same key (the check session).
+constexpr int PAIR_KS = 16, PAIR_REL = 22;
+struct PairRecord {
+    Prepared s;   // the searched session: ks_odd / ks_even hold 16 bits each; at_enc, at 0; par: the eight ninth bits of {nr}{ar}
+    uint32_t c_uid_nt, c_nr_enc, c_ar_enc, c_ar, c_par;   // the check session: uid ^ nt, {nr}, {ar}, suc64(nt), its eight ninth bits
+    uint32_t pad;
+};
+NFC_HD PairRecord prepare_pair(const nfc_reader_pair &p) {
+    PairRecord R;
+    nfc_auth_trace t = p.search;
+    t.at_enc = 0, t.par &= 0xFFu;
+    R.s = prepare(t);
+    R.s.ks_odd &= 0xFFFFu, R.s.ks_even &= 0xFFFFu;   // (the upper halves came from {at}: unknown)
+    R.s.at = 0;
+    R.c_uid_nt = p.check.uid ^ p.check.nt;
+    R.c_nr_enc = p.check.nr_enc, R.c_ar_enc = p.check.ar_enc;
+    R.c_ar = fsmd::nonce_advance(p.check.nt, 64);
+    R.c_par = p.check.par & 0xFFu;
+    R.pad = 0;
+    return R;
+}
+// One reader-side session forward under `key`: {nr} decrypts to four right ninth bits, ks2 reproduces ar, and the four ninth bits of {ar}
+// fit -- bytes 0 .. 2 under ks2 bits 8, 16, 24, byte 3 under ks3 bit 0 (the filter after the 32 free-running clocks).
+NFC_HD bool verify_reader(uint64_t key, uint32_t uid_nt, uint32_t nr_enc, uint32_t ar_enc, uint32_t ar, uint32_t par, uint32_t *nr_out) {
+    uint64_t st = key & fsmd::ST_MASK;
+    for (int i = 0; i < 32; i++) st = fsmd::shift_in(st, (uid_nt >> i) & 1u);
+    bool ok = true;
+    uint32_t nr = 0;
+    for (int b = 0; b < 4; b++) {
+        uint32_t pt = 0;
+        for (int k = 0; k < 8; k++) {
+            const uint32_t bit = ((nr_enc >> (8 * b + k)) & 1u) ^ fsmd::filter(st);
+            pt |= bit << k;
+            st = fsmd::shift_in(st, bit);
+        }
+        ok = ok && ninth_fits(par >> b, fsmd::filter(st), pt);
+        nr |= pt << (8 * b);
+    }
+    uint32_t ks2 = 0;
+    for (int i = 0; i < 32; i++) ks2 |= fsmd::filter(st) << i, st = fsmd::shift_in(st, 0u);
+    for (int b = 0; b < 3; b++) ok = ok && ninth_fits(par >> (4 + b), ks2 >> (8 * b + 8), ar >> (8 * b));
+    ok = ok && ninth_fits(par >> 7, fsmd::filter(st), ar >> 24);
+    if (nr_out) *nr_out = nr;
+    return ok && (ar_enc ^ ks2) == ar;
+}
+// a joined candidate counts when it passes BOTH sessions.  nr_search / nr_check: the decrypted reader nonces (may be null)
+NFC_HD bool verify_pair(uint64_t key, const PairRecord &R, uint32_t *nr_search, uint32_t *nr_check) {
+    const bool a = verify_reader(key, R.s.uid_nt, R.s.nr_enc, R.s.ar_enc, R.s.ar, R.s.par, nr_search);
+    if (!a && !nr_check) return false;
+    const bool b = verify_reader(key, R.c_uid_nt, R.c_nr_enc, R.c_ar_enc, R.c_ar, R.c_par, nr_check);
+    return a && b;
+}
+
+// The two searches as KINDS: the record, the walk's depth, the signature's width and the verification.  host_search, device_search and
+// the kernels are stated once over a kind.
+struct FullKind {
+    using Record = Prepared;
+    static constexpr int DEPTH = N_KS, NREL = N_REL;
+    static constexpr bool PAIR = false;
+    static NFC_HD const Prepared &base(const Record &r) { return r; }
+    static NFC_HD bool check(uint64_t key, const Record &r) { return verify(key, r, nullptr); }
+};
+struct PairKind {
+    using Record = PairRecord;
+    static constexpr int DEPTH = PAIR_KS, NREL = PAIR_REL;
+    static constexpr bool PAIR = true;
+    static NFC_HD const Prepared &base(const Record &r) { return r.s; }
+    static NFC_HD bool check(uint64_t key, const Record &r) { return verify_pair(key, r, nullptr, nullptr); }
+};
+
 // the table of a trace: a power of two, at least twice its odd list (at least 2)
 inline uint32_t table_log2(uint64_t n_odd) {
     uint32_t l = 1;
@@ -230,7 +309,8 @@ NFC_HD uint64_t slot_of(uint64_t sig, uint32_t log2) { return (sig * 0x9E3779B97
 // never where anything is written: the memory-safety argument does not depend on how many records there are.
 constexpr int KEYS_BLOCK = 256;
 enum { KEYS_ERR_TABLE_FULL = 1, KEYS_ERR_CANDIDATES = 2 };
-__device__ __forceinline__ const Prepared &record_of(const Prepared *__restrict__ prep, const uint32_t *__restrict__ map, uint32_t tr) {
+template <class Record>
+__device__ __forceinline__ const Record &record_of(const Record *__restrict__ prep, const uint32_t *__restrict__ map, uint32_t tr) {
     return prep[map ? map[tr] : tr];
 }
 
@@ -273,11 +353,12 @@ struct Place {
     uint32_t log2, pad;
 };
 
-__global__ __launch_bounds__(KEYS_BLOCK) void k_keys_count(const Prepared *__restrict__ prep, const uint32_t *__restrict__ map,
+template <class Kind>
+__global__ __launch_bounds__(KEYS_BLOCK) void k_keys_count(const typename Kind::Record *__restrict__ prep, const uint32_t *__restrict__ map,
                                                            uint32_t *__restrict__ counts /* [trace][half] */) {
     const uint32_t tr = blockIdx.z, half = blockIdx.y, w = blockIdx.x * KEYS_BLOCK + threadIdx.x;
-    const uint32_t ks = half ? record_of(prep, map, tr).ks_even : record_of(prep, map, tr).ks_odd;
-    uint32_t n = walk(w, ks, [](uint64_t) {});
+    const uint32_t ks = half ? Kind::base(record_of(prep, map, tr)).ks_even : Kind::base(record_of(prep, map, tr)).ks_odd;
+    uint32_t n = walk<Kind::DEPTH>(w, ks, [](uint64_t) {});
     __shared__ uint32_t total;
     if (threadIdx.x == 0) total = 0;
     __syncthreads();
@@ -289,14 +370,15 @@ __global__ __launch_bounds__(KEYS_BLOCK) void k_keys_count(const Prepared *__res
 
 // Every slot index is masked to the trace's table, so nothing is written outside its section whatever the counts were; a table that
 // turns out full (it cannot, the host sized it from the exact count) raises KEYS_ERR_TABLE_FULL and the sequence is dropped.
-__global__ __launch_bounds__(KEYS_BLOCK) void k_keys_fill_odd(const Prepared *__restrict__ prep, const uint32_t *__restrict__ map,
+template <class Kind>
+__global__ __launch_bounds__(KEYS_BLOCK) void k_keys_fill_odd(const typename Kind::Record *__restrict__ prep, const uint32_t *__restrict__ map,
                                                               const Place *__restrict__ place, uint32_t t0, uint64_t *__restrict__ sig_tab, uint64_t *__restrict__ seq_tab, uint32_t *__restrict__ err) {
     const uint32_t tr = t0 + blockIdx.z, w = blockIdx.x * KEYS_BLOCK + threadIdx.x;
     const Place pl = place[tr];
     if (pl.log2 == 0) return;
     const uint64_t mask = (1ull << pl.log2) - 1ull;
-    walk(w, record_of(prep, map, tr).ks_odd, [&](uint64_t seq) {
-        const uint64_t sig = signature<0>(seq);
+    walk<Kind::DEPTH>(w, Kind::base(record_of(prep, map, tr)).ks_odd, [&](uint64_t seq) {
+        const uint64_t sig = signature<0, Kind::NREL>(seq);
         uint64_t slot = slot_of(sig, pl.log2);
         for (uint64_t tries = 0; tries <= mask; tries++) {
             const uint64_t old = atomicCAS((unsigned long long *)&sig_tab[pl.off + slot], (unsigned long long)SIG_EMPTY, (unsigned long long)sig);
@@ -310,30 +392,77 @@ __global__ __launch_bounds__(KEYS_BLOCK) void k_keys_fill_odd(const Prepared *__
     });
 }
 
-__global__ __launch_bounds__(KEYS_BLOCK) void k_keys_probe_even(const Prepared *__restrict__ prep, const uint32_t *__restrict__ map,
+// The lanes of a wave that stand here together take consecutive places from ONE atomic of the first of them (every lane of a workgroup
+// has the same trace, so the same counter) -> this lane's place.  Inside the walk's divergent loop __ballot(1) is the set of lanes
+// that execute THIS call together, whichever that is; the ballot, the leader's atomic and the shuffle are straight-line code under
+// one execution mask, so any such set gets distinct consecutive places (n_joined equals the twin's in the tests).
+__device__ __forceinline__ uint32_t wave_append(uint32_t *counter) {
+    const uint64_t here = __ballot(1);
+    const uint32_t lane = threadIdx.x & 63u, first = (uint32_t)__ffsll((unsigned long long)here) - 1u;
+    uint32_t base = 0;
+    if (lane == first) base = atomicAdd(counter, (uint32_t)__popcll(here));
+    return (uint32_t)__shfl((int)base, (int)first, 64) + (uint32_t)__popcll(here & ((1ull << lane) - 1ull));
+}
+// what a verified candidate leaves: its trace's count and lowest key
+template <class Kind>
+__device__ __forceinline__ void settle(uint64_t joined, const typename Kind::Record &R, uint32_t *n_found, unsigned long long *min_key) {
+    const uint64_t key = rollback(joined, Kind::base(R));
+    if (Kind::check(key, R)) {
+        atomicAdd(n_found, 1u);
+        atomicMin(min_key, (unsigned long long)key);
+    }
+}
+
+// STAGED false: every joined pair is rolled back and verified by the lane that found it (the full search joins about one).  STAGED
+// true (reader pairs: about 1e5 join, and the 170 cipher clocks of a verification inside the walk's loop would hold a whole wave): the
+// joined register goes into the trace's section of `stage`, [trace of the batch][cap] words, at the place the trace's n_joined counter
+// gives, and k_keys_verify_stage settles a candidate per lane.  A place that is not below cap -- the stage is full -- is never written:
+// that candidate is settled here, so nothing is truncated.  n_joined counts every equal signature (a kind that reports it: PAIR).
+template <class Kind, bool STAGED>
+__global__ __launch_bounds__(KEYS_BLOCK) void k_keys_probe_even(const typename Kind::Record *__restrict__ prep, const uint32_t *__restrict__ map,
                                                                 const Place *__restrict__ place, uint32_t t0, const uint64_t *__restrict__ sig_tab, const uint64_t *__restrict__ seq_tab,
-                                                                uint32_t *__restrict__ n_found, unsigned long long *__restrict__ min_key) {
+                                                                uint32_t *__restrict__ n_found, unsigned long long *__restrict__ min_key,
+                                                                uint32_t *__restrict__ n_joined, uint64_t *__restrict__ stage, uint32_t cap) {
     const uint32_t tr = t0 + blockIdx.z, w = blockIdx.x * KEYS_BLOCK + threadIdx.x;
     const Place pl = place[tr];
     if (pl.log2 == 0) return;
     const uint64_t mask = (1ull << pl.log2) - 1ull;
-    const Prepared P = record_of(prep, map, tr);
-    walk(w, P.ks_even, [&](uint64_t seq) {
-        const uint64_t sig = signature<1>(seq);
+    const typename Kind::Record R = record_of(prep, map, tr);
+    walk<Kind::DEPTH>(w, Kind::base(R).ks_even, [&](uint64_t seq) {
+        const uint64_t sig = signature<1, Kind::NREL>(seq);
         uint64_t slot = slot_of(sig, pl.log2);
         for (uint64_t tries = 0; tries <= mask; tries++) {
             const uint64_t s = sig_tab[pl.off + slot];
             if (s == SIG_EMPTY) return;
             if (s == sig) {
-                const uint64_t key = rollback(join_state(seq_tab[pl.off + slot], seq), P);
-                if (verify(key, P, nullptr)) {
-                    atomicAdd(&n_found[tr], 1u);
-                    atomicMin(&min_key[tr], (unsigned long long)key);
+                const uint64_t joined = join_state(seq_tab[pl.off + slot], seq);
+                if (STAGED) {
+                    const uint32_t at = wave_append(&n_joined[tr]);
+                    if (at < cap) stage[(size_t)tr * cap + at] = joined;
+                    else settle<Kind>(joined, R, &n_found[tr], &min_key[tr]);
+                } else {
+                    if (Kind::PAIR) atomicAdd(&n_joined[tr], 1u);
+                    settle<Kind>(joined, R, &n_found[tr], &min_key[tr]);
                 }
             }
             slot = (slot + 1) & mask;
         }
     });
+}
+
+// The dense follow-up of a STAGED probe: a lane per staged candidate of the trace, min(n_joined, cap) of them, in strides of the grid.
+template <class Kind>
+__global__ __launch_bounds__(KEYS_BLOCK) void k_keys_verify_stage(const typename Kind::Record *__restrict__ prep, const uint32_t *__restrict__ map,
+                                                                  const Place *__restrict__ place, uint32_t t0, const uint32_t *__restrict__ n_joined,
+                                                                  const uint64_t *__restrict__ stage, uint32_t cap, uint32_t *__restrict__ n_found,
+                                                                  unsigned long long *__restrict__ min_key) {
+    const uint32_t tr = t0 + blockIdx.z;
+    if (place[tr].log2 == 0) return;
+    const uint32_t n = n_joined[tr] < cap ? n_joined[tr] : cap;
+    if (blockIdx.x * KEYS_BLOCK >= n) return;
+    const typename Kind::Record R = record_of(prep, map, tr);
+    for (uint32_t i = blockIdx.x * KEYS_BLOCK + threadIdx.x; i < n; i += gridDim.x * KEYS_BLOCK)
+        settle<Kind>(stage[(size_t)tr * cap + i], R, &n_found[tr], &min_key[tr]);
 }
 #endif   // __HIPCC__
 

@@ -22,7 +22,10 @@ static_assert(sizeof(nfc_auth_trace) == 40 && sizeof(nfc_key_result) == 24 && si
               "the key recovery's public structures");
 static_assert(sizeof(nfc_nested_trace) == 40 && sizeof(nfc_nested_result) == 48 && sizeof(nfc_nested_config) == 48,
               "the nested key recovery's public structures");
+static_assert(sizeof(nfc_reader_pair) == 80 && sizeof(nfc_reader_key_result) == 32 && sizeof(nfc_reader_key_config) == 48,
+              "the reader-pair key recovery's public structures");
 static_assert(sizeof(nfc::keys::Prepared) == 48, "a record is twelve words");
+static_assert(sizeof(nfc::keys::PairRecord) == 72, "a pair record is eighteen words");
 
 namespace {
 using namespace nfc;
@@ -30,14 +33,16 @@ using namespace nfc::keys;
 
 constexpr uint64_t DEFAULT_INITIAL = 1ull << 26, DEFAULT_MAX = 1ull << 28, LIMIT_MAX = 1ull << 32;
 constexpr uint32_t DEFAULT_BATCH = 16, LIMIT_BATCH = 4096;
+constexpr uint32_t DEFAULT_STAGE = 1u << 18, LIMIT_STAGE = 1u << 24;   // joined candidates per pair (reader pairs: DESIGN.md 8n)
 
 struct Limits {
     uint64_t initial, max;
     uint32_t max_batch;
     bool timing;
+    uint32_t stage = DEFAULT_STAGE;   // reader pairs only: 0 verifies in the walking lane
 };
 bool limits_of(const nfc_key_config *c, Limits &L) {
-    L = Limits{DEFAULT_INITIAL, DEFAULT_MAX, DEFAULT_BATCH, false};
+    L = Limits{DEFAULT_INITIAL, DEFAULT_MAX, DEFAULT_BATCH, false, DEFAULT_STAGE};
     if (!c) return true;
     if (c->reserved[0] || c->reserved[1] || (c->flags & ~(uint32_t)NFC_KEY_TIMING)) return false;
     if (c->max_capacity) L.max = c->max_capacity;
@@ -95,6 +100,8 @@ struct Verdict {
     bool overflow;
     uint32_t n_found, n_odd, n_even;
     uint64_t min_key;
+    uint32_t n_joined;   // equal signatures.  Only the PAIR kind reports it: the twin counts it for both kinds (it costs nothing there),
+                         // the kernels only where Kind::PAIR, and result_of, the full search's, never reads it
 };
 
 void result_of(nfc_key_result &r, const Verdict &v, const Prepared &P) {
@@ -112,8 +119,8 @@ void result_of(nfc_key_result &r, const Verdict &v, const Prepared &P) {
     }
 }
 
-// ---- the CPU twin over records: record_of(v) -> Prepared, sink(v, verdict, record) ----
-template <class RecordOf, class Sink>
+// ---- the CPU twin over records of a kind: record_of(v) -> Kind::Record, sink(v, verdict, record) ----
+template <class Kind, class RecordOf, class Sink>
 void host_search(const Limits &L, nfc_key_stats &S, size_t nv, RecordOf &&record_of, Sink &&sink) {
     uint64_t capacity = L.initial;
     std::vector<std::pair<uint64_t, uint64_t>> odd;   // (signature, sequence)
@@ -122,25 +129,28 @@ void host_search(const Limits &L, nfc_key_stats &S, size_t nv, RecordOf &&record
         const uint32_t nb = (uint32_t)std::min<size_t>(L.max_batch, nv - b0);
         n_odd.assign(nb, 0);
         for (uint32_t i = 0; i < nb; i++) {
-            const Prepared P = record_of(b0 + i);
+            const typename Kind::Record R = record_of(b0 + i);
+            const Prepared &P = Kind::base(R);
             odd.clear();
-            for (uint32_t w = 0; w < WINDOWS; w++) walk(w, P.ks_odd, [&](uint64_t seq) { odd.emplace_back(signature<0>(seq), seq); });
+            for (uint32_t w = 0; w < WINDOWS; w++)
+                walk<Kind::DEPTH>(w, P.ks_odd, [&](uint64_t seq) { odd.emplace_back(signature<0, Kind::NREL>(seq), seq); });
             n_odd[i] = (uint32_t)odd.size();
-            Verdict V{(1ull << table_log2(odd.size())) > L.max, 0u, n_odd[i], 0u, ~0ull};
+            Verdict V{(1ull << table_log2(odd.size())) > L.max, 0u, n_odd[i], 0u, ~0ull, 0u};
             if (!V.overflow) std::sort(odd.begin(), odd.end());
             for (uint32_t w = 0; w < WINDOWS; w++)
-                V.n_even += walk(w, P.ks_even, [&](uint64_t seq) {
+                V.n_even += walk<Kind::DEPTH>(w, P.ks_even, [&](uint64_t seq) {
                     if (V.overflow) return;
-                    const uint64_t sig = signature<1>(seq);
+                    const uint64_t sig = signature<1, Kind::NREL>(seq);
                     for (auto it = std::lower_bound(odd.begin(), odd.end(), std::make_pair(sig, (uint64_t)0)); it != odd.end() && it->first == sig; ++it) {
+                        V.n_joined++;
                         const uint64_t key = rollback(join_state(it->second, seq), P);
-                        if (verify(key, P, nullptr)) {
+                        if (Kind::check(key, R)) {
                             if (V.n_found != 0xFFFFFFFFu) V.n_found++;
                             V.min_key = std::min(V.min_key, key);
                         }
                     }
                 });
-            sink(b0 + i, V, P);
+            sink(b0 + i, V, R);
         }
         account(plan_batch(n_odd.data(), nb, L.max), capacity, S);
         S.n_batches++;
@@ -193,11 +203,15 @@ struct DeviceSearch {
     }
 };
 
-template <class Prelude, class RecordOf, class Sink>
+// A kind whose probe STAGES (reader pairs with L.stage > 0) has besides a section of L.stage words per trace of the batch, and a verify
+// launch after every probe launch; both count in ms_probe.
+template <class Kind, class Prelude, class RecordOf, class Sink>
 int device_search(int device, const Limits &L, nfc_key_stats &S, Prelude &&prelude, RecordOf &&record_of, Sink &&sink) {
+    using Record = typename Kind::Record;
     if (hipSetDevice(device) != hipSuccess) return NFC_ERR_DEVICE;
     DeviceSearch D{L, S};
-    DevBuf small_buf, scratch;
+    DevBuf small_buf, scratch, stage_buf;
+    const bool staged = Kind::PAIR && L.stage > 0;
     uint64_t capacity = L.initial;
     auto bad = [&](hipError_t e) { return D.bad(e); };
     const bool searched = [&] {   // (false: it ended before there was anything to search; D.rc holds the status)
@@ -205,33 +219,38 @@ int device_search(int device, const Limits &L, nfc_key_stats &S, Prelude &&prelu
         if (!prelude(D) || D.nv == 0) return false;
         const size_t nv = D.nv;
         const uint32_t mb = (uint32_t)std::min<size_t>(L.max_batch, nv);
-        // the small per-batch arrays in one allocation: prep | place | counts [2 mb] | n_found [mb] | err [1] (padded) | min_key [mb] | map [mb]
-        const size_t o_place = sizeof(Prepared) * mb, o_counts = o_place + sizeof(Place) * mb, o_found = o_counts + 8 * (size_t)mb,
-                     o_err = o_found + 4 * (size_t)mb, o_min = (o_err + 4 + 7) & ~(size_t)7, o_map = o_min + 8 * (size_t)mb,
-                     small_bytes = o_map + 4 * (size_t)mb;
+        // the small per-batch arrays in one allocation:
+        // prep | place | counts [2 mb] | n_found [mb] | n_joined [mb] | err [1] (padded) | min_key [mb] | map [mb]
+        const size_t o_place = sizeof(Record) * mb, o_counts = o_place + sizeof(Place) * mb, o_found = o_counts + 8 * (size_t)mb,
+                     o_joined = o_found + 4 * (size_t)mb, o_err = o_joined + 4 * (size_t)mb, o_min = (o_err + 4 + 7) & ~(size_t)7,
+                     o_map = o_min + 8 * (size_t)mb, small_bytes = o_map + 4 * (size_t)mb;
+        static_assert(sizeof(Record) % 8 == 0, "place, an array of 64-bit words, follows the records");
         if (bad(small_buf.ensure(small_bytes)) || bad(scratch.ensure(capacity * 16))) return true;
+        if (staged && bad(stage_buf.ensure(8 * (size_t)L.stage * mb))) return true;
         uint8_t *const small = small_buf.as<uint8_t>();
-        Prepared *d_prep = (Prepared *)small;
+        Record *d_prep = (Record *)small;
         Place *d_place = (Place *)(small + o_place);
         uint32_t *d_counts = (uint32_t *)(small + o_counts), *d_found = (uint32_t *)(small + o_found), *d_err = (uint32_t *)(small + o_err);
+        uint32_t *d_joined = (uint32_t *)(small + o_joined);
         unsigned long long *d_min = (unsigned long long *)(small + o_min);
         uint32_t *d_map_buf = (uint32_t *)(small + o_map);
-        const Prepared *k_prep = D.d_records ? D.d_records : d_prep;
+        uint64_t *d_stage = staged ? stage_buf.as<uint64_t>() : nullptr;
+        const Record *k_prep = D.d_records ? reinterpret_cast<const Record *>(D.d_records) : d_prep;   // (only the full kind's prelude leaves records)
         const uint32_t *k_map = D.d_records ? d_map_buf : nullptr;
         const dim3 block(KEYS_BLOCK);
-        std::vector<Prepared> prep(mb);
+        std::vector<Record> prep(mb);
         std::vector<Place> place(mb);
-        std::vector<uint32_t> counts(2 * (size_t)mb), n_odd(mb), found(mb);
+        std::vector<uint32_t> counts(2 * (size_t)mb), n_odd(mb), found(mb), joined(mb);
         std::vector<uint64_t> min_key(mb);
         for (size_t b0 = 0; b0 < nv && D.rc == NFC_OK; b0 += mb) {
             const uint32_t nb = (uint32_t)std::min<size_t>(mb, nv - b0);
             for (uint32_t i = 0; i < nb; i++) prep[i] = record_of(b0 + i);
             // the batch's records, or where they lie; counts, found and err to 0, min_key to all ones
             if (D.d_records ? bad(hipMemcpy(d_map_buf, D.map + b0, 4 * (size_t)nb, hipMemcpyHostToDevice))
-                            : bad(hipMemcpy(d_prep, prep.data(), sizeof(Prepared) * nb, hipMemcpyHostToDevice)))
+                            : bad(hipMemcpy(d_prep, prep.data(), sizeof(Record) * nb, hipMemcpyHostToDevice)))
                 return true;
             if (bad(hipMemsetAsync(d_counts, 0, o_min - o_counts, 0)) || bad(hipMemsetAsync(d_min, 0xFF, 8 * (size_t)mb, 0))) return true;
-            if (!D.timed(S.ms_count, [&] { NFC_LAUNCH(k_keys_count, dim3(WINDOWS / KEYS_BLOCK, 2, nb), block, 0, 0, k_prep, k_map, d_counts); })) return true;
+            if (!D.timed(S.ms_count, [&] { NFC_LAUNCH(k_keys_count<Kind>, dim3(WINDOWS / KEYS_BLOCK, 2, nb), block, 0, 0, k_prep, k_map, d_counts); })) return true;
             if (bad(hipMemcpy(counts.data(), d_counts, 8 * (size_t)nb, hipMemcpyDeviceToHost))) return true;   // (waits for the launch)
             for (uint32_t i = 0; i < nb; i++) n_odd[i] = counts[2 * i];
             const Plan plan = plan_batch(n_odd.data(), nb, L.max);
@@ -251,22 +270,40 @@ int device_search(int device, const Limits &L, nfc_key_stats &S, Prelude &&prelu
                     bad(hipMemsetAsync(sig_tab, 0xFF, g.slots * 8, 0)))
                     return true;
                 const dim3 grid(WINDOWS / KEYS_BLOCK, 1, g.t1 - g.t0);
-                if (!D.timed(S.ms_fill, [&] { NFC_LAUNCH(k_keys_fill_odd, grid, block, 0, 0, k_prep, k_map, d_place, g.t0, sig_tab, seq_tab, d_err); }))
+                if (!D.timed(S.ms_fill, [&] { NFC_LAUNCH(k_keys_fill_odd<Kind>, grid, block, 0, 0, k_prep, k_map, d_place, g.t0, sig_tab, seq_tab, d_err); }))
                     return true;
-                if (!D.timed(S.ms_probe,
-                             [&] { NFC_LAUNCH(k_keys_probe_even, grid, block, 0, 0, k_prep, k_map, d_place, g.t0, sig_tab, seq_tab, d_found, d_min); }))
+                bool probed = false;
+                if constexpr (Kind::PAIR) if (staged) {
+                    probed = true;
+                    // the verify grid: a lane per place of the stage, at most VERIFY_BLOCKS workgroups per trace (they stride)
+                    constexpr uint32_t VERIFY_BLOCKS = 1024;
+                    const dim3 vgrid(std::min<uint32_t>((L.stage + KEYS_BLOCK - 1) / KEYS_BLOCK, VERIFY_BLOCKS), 1, g.t1 - g.t0);
+                    if (!D.timed(S.ms_probe, [&] {
+                            NFC_LAUNCH((k_keys_probe_even<Kind, true>), grid, block, 0, 0, k_prep, k_map, d_place, g.t0, sig_tab, seq_tab, d_found, d_min,
+                                       d_joined, d_stage, L.stage);
+                        }) ||
+                        !D.timed(S.ms_probe, [&] {
+                            NFC_LAUNCH(k_keys_verify_stage<Kind>, vgrid, block, 0, 0, k_prep, k_map, d_place, g.t0, d_joined, d_stage, L.stage, d_found, d_min);
+                        }))
+                        return true;
+                }
+                if (!probed && !D.timed(S.ms_probe, [&] {
+                        NFC_LAUNCH((k_keys_probe_even<Kind, false>), grid, block, 0, 0, k_prep, k_map, d_place, g.t0, sig_tab, seq_tab, d_found, d_min,
+                                   d_joined, d_stage, 0u);
+                    }))
                     return true;
                 if (bad(hipStreamSynchronize(0))) return true;   // (the next group rewrites d_place and the tables)
             }
             uint32_t err = 0;
             if (bad(hipMemcpy(found.data(), d_found, 4 * (size_t)nb, hipMemcpyDeviceToHost)) ||
+                bad(hipMemcpy(joined.data(), d_joined, 4 * (size_t)nb, hipMemcpyDeviceToHost)) ||
                 bad(hipMemcpy(min_key.data(), d_min, 8 * (size_t)nb, hipMemcpyDeviceToHost)) || bad(hipMemcpy(&err, d_err, 4, hipMemcpyDeviceToHost)))
                 return true;
             if (err) {
                 D.rc = NFC_ERR_INTERNAL;
                 return true;
             }
-            for (uint32_t i = 0; i < nb; i++) sink(b0 + i, Verdict{plan.log2[i] == 0, found[i], counts[2 * i], counts[2 * i + 1], min_key[i]}, prep[i]);
+            for (uint32_t i = 0; i < nb; i++) sink(b0 + i, Verdict{plan.log2[i] == 0, found[i], counts[2 * i], counts[2 * i + 1], min_key[i], joined[i]}, prep[i]);
             S.n_batches++;
         }
         return true;
@@ -374,12 +411,10 @@ constexpr size_t NESTED_MAX_TRACES = (1ull << 32) / NESTED_CANDS;   // a record'
 
 bool key_type_ok(const nfc_auth_trace &t) { return t.key_type == 0x60 || t.key_type == 0x61; }
 
-}  // namespace
-
-extern "C" {
-
-int nfc_find_auths(const nfc_raw_frame *frames, size_t n, const uint8_t *bytes0, const uint8_t *par0, const uint8_t *bytes1, const uint8_t *par1,
-                   nfc_auth_trace *out, size_t cap, size_t *n_out) {
+// nfc_find_auths (with_at) and nfc_find_reader_auths (without: the fourth frame is not looked at, at_enc and its ninth bits stay 0)
+int find_first_auths(bool with_at, const nfc_raw_frame *frames, size_t n, const uint8_t *bytes0, const uint8_t *par0, const uint8_t *bytes1,
+                     const uint8_t *par1, nfc_auth_trace *out, size_t cap, size_t *n_out) {
+    const size_t tail = with_at ? 3 : 2;   // frames after the AUTH
     if (!n_out || (n && !frames) || (cap && !out)) return NFC_ERR_ARG;
     *n_out = 0;
     for (size_t i = 0; i < n; i++)
@@ -401,21 +436,24 @@ int nfc_find_auths(const nfc_raw_frame *frames, size_t n, const uint8_t *bytes0,
             if (b[0] == 0x93 && b[1] == 0x70) have_uid = true, uid = word(b + 2);
             continue;
         }
-        if (!have_uid || i + 3 >= n || !is(i, 1, 4, NFC_RAW_CRC_A_OK)) continue;
+        if (!have_uid || i + tail >= n || !is(i, 1, 4, NFC_RAW_CRC_A_OK)) continue;
         const uint8_t *a = bytes_of(frames[i]);
         if (a[0] != 0x60 && a[0] != 0x61) continue;
-        if (!is(i + 1, 0, 4, NFC_RAW_PARITY_OK) || !is(i + 2, 1, 8, 0) || !is(i + 3, 0, 4, 0)) continue;
+        if (!is(i + 1, 0, 4, NFC_RAW_PARITY_OK) || !is(i + 2, 1, 8, 0) || (with_at && !is(i + 3, 0, 4, 0))) continue;
         if (found < cap) {
             nfc_auth_trace &t = out[found];
             memset(&t, 0, sizeof t);
-            const uint8_t *rb = bytes_of(frames[i + 2]), *rp = par_of(frames[i + 2]), *tp = par_of(frames[i + 3]);
+            const uint8_t *rb = bytes_of(frames[i + 2]), *rp = par_of(frames[i + 2]);
             t.uid = uid;
             t.nt = word(bytes_of(frames[i + 1]));
             t.nr_enc = word(rb);
             t.ar_enc = word(rb + 4);
-            t.at_enc = word(bytes_of(frames[i + 3]));
             for (int k = 0; k < 8; k++) t.par |= (uint16_t)((rp[k] & 1u) << k);
-            for (int k = 0; k < 4; k++) t.par |= (uint16_t)((tp[k] & 1u) << (8 + k));
+            if (with_at) {
+                const uint8_t *tp = par_of(frames[i + 3]);
+                t.at_enc = word(bytes_of(frames[i + 3]));
+                for (int k = 0; k < 4; k++) t.par |= (uint16_t)((tp[k] & 1u) << (8 + k));
+            }
             t.key_type = a[0];
             t.block = a[1];
             t.frame = (uint32_t)i;
@@ -427,6 +465,80 @@ int nfc_find_auths(const nfc_raw_frame *frames, size_t n, const uint8_t *bytes0,
     return NFC_OK;
 }
 
+// ---- reader pairs ----
+bool pair_limits_of(const nfc_reader_key_config *c, Limits &L) {
+    if (!c) return limits_of(nullptr, L);
+    if (!limits_of(&c->search, L) || (c->flags & ~(uint32_t)NFC_RKEY_VERIFY_INLINE) || c->reserved[0] || c->reserved[1] || c->stage_capacity > LIMIT_STAGE)
+        return false;
+    if (c->stage_capacity) L.stage = c->stage_capacity;
+    if (c->flags & NFC_RKEY_VERIFY_INLINE) L.stage = 0;
+    return true;
+}
+bool pairs_ok(const nfc_reader_pair *pairs, size_t n) {
+    for (size_t i = 0; i < n; i++)
+        if (!key_type_ok(pairs[i].search) || !key_type_ok(pairs[i].check)) return false;
+    return true;
+}
+void pair_result_of(nfc_reader_key_result &r, const Verdict &v, const PairRecord &R) {
+    memset(&r, 0, sizeof r);
+    r.n_odd = v.n_odd, r.n_even = v.n_even;
+    if (v.overflow) {
+        r.status = NFC_KEY_OVERFLOW;
+        return;
+    }
+    r.n_candidates = v.n_found, r.n_joined = v.n_joined;
+    r.status = v.n_found == 0 ? NFC_KEY_NONE : v.n_found == 1 ? NFC_KEY_OK : NFC_KEY_AMBIGUOUS;
+    if (v.n_found) {
+        for (int i = 0; i < 6; i++) r.key[i] = (uint8_t)(v.min_key >> (8 * i));
+        (void)verify_pair(v.min_key, R, &r.nr_search, &r.nr_check);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int nfc_find_auths(const nfc_raw_frame *frames, size_t n, const uint8_t *bytes0, const uint8_t *par0, const uint8_t *bytes1, const uint8_t *par1,
+                   nfc_auth_trace *out, size_t cap, size_t *n_out) {
+    return find_first_auths(true, frames, n, bytes0, par0, bytes1, par1, out, cap, n_out);
+}
+
+int nfc_find_reader_auths(const nfc_raw_frame *frames, size_t n, const uint8_t *bytes0, const uint8_t *par0, const uint8_t *bytes1,
+                          const uint8_t *par1, nfc_auth_trace *out, size_t cap, size_t *n_out) {
+    return find_first_auths(false, frames, n, bytes0, par0, bytes1, par1, out, cap, n_out);
+}
+
+int nfc_host_recover_reader_keys(const nfc_reader_pair *pairs, size_t n, const nfc_reader_key_config *cfg, nfc_reader_key_result *out,
+                                 nfc_key_stats *stats) {
+    Limits L;
+    if (!pair_limits_of(cfg, L) || (n && (!pairs || !out)) || !pairs_ok(pairs, n)) return NFC_ERR_ARG;
+    nfc_key_stats S;
+    memset(&S, 0, sizeof S);
+    host_search<PairKind>(L, S, n, [&](size_t v) { return prepare_pair(pairs[v]); },
+                          [&](size_t v, const Verdict &V, const PairRecord &R) { pair_result_of(out[v], V, R); });
+    if (stats) *stats = S;
+    return NFC_OK;
+}
+
+int nfc_recover_reader_keys_device(int device, const nfc_reader_pair *pairs, size_t n, const nfc_reader_key_config *cfg,
+                                   nfc_reader_key_result *out, nfc_key_stats *stats) {
+    Limits L;
+    if (!pair_limits_of(cfg, L) || (n && (!pairs || !out)) || device < 0 || !pairs_ok(pairs, n)) return NFC_ERR_ARG;
+    nfc_key_stats S;
+    memset(&S, 0, sizeof S);
+    if (stats) *stats = S;
+    if (n == 0) return NFC_OK;
+    const int rc = device_search<PairKind>(
+        device, L, S,
+        [&](DeviceSearch &D) {
+            D.nv = n;
+            return true;
+        },
+        [&](size_t v) { return prepare_pair(pairs[v]); }, [&](size_t v, const Verdict &V, const PairRecord &R) { pair_result_of(out[v], V, R); });
+    if (stats) *stats = S;
+    return rc;
+}
+
 int nfc_host_recover_keys(const nfc_auth_trace *traces, size_t n, const nfc_key_config *cfg, nfc_key_result *out, nfc_key_stats *stats) {
     Limits L;
     if (!limits_of(cfg, L) || (n && (!traces || !out))) return NFC_ERR_ARG;
@@ -434,7 +546,7 @@ int nfc_host_recover_keys(const nfc_auth_trace *traces, size_t n, const nfc_key_
         if (!key_type_ok(traces[i])) return NFC_ERR_ARG;
     nfc_key_stats S;
     memset(&S, 0, sizeof S);
-    host_search(L, S, n, [&](size_t v) { return prepare(traces[v]); }, [&](size_t v, const Verdict &V, const Prepared &P) { result_of(out[v], V, P); });
+    host_search<FullKind>(L, S, n, [&](size_t v) { return prepare(traces[v]); }, [&](size_t v, const Verdict &V, const Prepared &P) { result_of(out[v], V, P); });
     if (stats) *stats = S;
     return NFC_OK;
 }
@@ -449,7 +561,7 @@ int nfc_recover_keys_device(int device, const nfc_auth_trace *traces, size_t n, 
     memset(&S, 0, sizeof S);
     if (stats) *stats = S;
     if (n == 0) return NFC_OK;
-    const int rc = device_search(
+    const int rc = device_search<FullKind>(
         device, L, S,
         [&](DeviceSearch &D) {
             D.nv = n;
@@ -531,7 +643,7 @@ int nfc_nested_candidates_device(int device, const nfc_nested_trace *traces, siz
     nfc_key_stats S;
     memset(&S, 0, sizeof S);
     std::vector<Prepared> rec;
-    return device_search(
+    return device_search<FullKind>(
         device, L, S,
         [&](DeviceSearch &D) {   // the prelude alone: no record is searched
             Prepared *d_rec = nullptr;
@@ -553,7 +665,7 @@ int nfc_host_recover_nested_keys(const nfc_nested_trace *traces, size_t n, const
     for (size_t p = 0; p < n; p++) n_nt[p] = nested_records(traces[p], (uint32_t)p, rec.data() + p * NESTED_CANDS);
     const std::vector<uint32_t> map = virtual_traces(N, n_nt.data(), n);
     NestedFolds folds(n_nt.data(), n);
-    host_search(N.search, S, map.size(), [&](size_t v) { return rec[map[v]]; }, [&](size_t v, const Verdict &V, const Prepared &P) { folds.add(map[v], V, P); });
+    host_search<FullKind>(N.search, S, map.size(), [&](size_t v) { return rec[map[v]]; }, [&](size_t v, const Verdict &V, const Prepared &P) { folds.add(map[v], V, P); });
     folds.done(out);
     if (stats) *stats = S;
     return NFC_OK;
@@ -570,7 +682,7 @@ int nfc_recover_nested_keys_device(int device, const nfc_nested_trace *traces, s
     std::vector<Prepared> rec;   // the device's records, read back for the fold (key -> nt, nr); never sent up
     std::vector<uint32_t> n_nt(n), map;
     std::vector<NestedFolds> folds;   // (made once n_nt is known)
-    const int rc = device_search(
+    const int rc = device_search<FullKind>(
         device, N.search, S,
         [&](DeviceSearch &D) {
             Prepared *d_rec = nullptr;

@@ -99,7 +99,7 @@ def _per_source_keys(keys, n):
 
 
 def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None, keep=None, device=0, push_stats=None, frames=False, commands=False,
-                keys=None, nested=False, emulate=None, **sink_kwargs):
+                keys=None, nested=False, emulate=None, reader_pairs=False, **sink_kwargs):
     """Decode many recordings at once: every source is a stream of one api.NfcMultiContext, a GPU lane each, one kernel launch per
     round of pieces (include/nfc_amd.h: nfc_multi) -- what a loop of ``decoder(src=s).run()`` does capture by capture.
 
@@ -124,6 +124,8 @@ def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None,
     gets ``recovered_keys``: (key_type, block) -> six key bytes.  The cost is the doubled push.
     nested=True (with keys='recover'): the nested authentications are searched too (usrp_nfc_amd.keys.recover_streams), and
     ``recovered_keys`` holds every sector key whose AUTH command could be decrypted and labelled.
+    reader_pairs (with keys='recover'; True, or a dict of keys.recover_reader's own options): the first authentications the full search leaves without a key -- no {at}, or a noise
+    one -- are paired and searched as reader pairs (usrp_nfc_amd.keys.recover_reader_streams), one more recovery call.
     emulate: a card per source (emulate.tag_card / reader_card; a list, None for a source that only listens; one card: for all) --
     every source's stream ANSWERS what it hears, on the GPU in the launch that decodes its commands (api.NfcMultiContext.emulate), and
     after every push each source's ``(records, plain, air, par)`` (NfcMultiAnswers.answers_of) is appended to its background's ``answers``.
@@ -165,8 +167,8 @@ def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None,
         for b in backs:
             b.recovered_keys = {}
             b.key_conflicts = {}
-    elif nested:
-        raise ValueError("decode_many: nested is for keys='recover'")
+    elif nested or reader_pairs:
+        raise ValueError("decode_many: nested and reader_pairs are for keys='recover'")
     elif keys is not None:
         if not commands:
             raise ValueError('decode_many: keys are for commands=True')
@@ -187,7 +189,7 @@ def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None,
             with api.NfcMultiContext(len(group), piece, samp_rate=samp_rate, hi_val=_hi_val(kind), reader=reader, tag=tag, input_kind=kind,
                                      device=device, i16_scale=scale if kind in _SCALED_KINDS else 0.0, **sink) as m:
                 if recover:
-                    _recover_group_keys(m, buf, starts, lens, piece, backs[g0:g0 + len(group)], device, nested)
+                    _recover_group_keys(m, buf, starts, lens, piece, backs[g0:g0 + len(group)], device, nested, reader_pairs)
                 if commands:
                     m.track_commands(True)
                     if recover:
@@ -260,7 +262,7 @@ def _joined_frames(parts):
                          [cat(par[t], numpy.uint8) for t in (0, 1)])
 
 
-def _recover_group_keys(m, buf, starts, lens, piece, backs, device, nested=False):
+def _recover_group_keys(m, buf, starts, lens, piece, backs, device, nested=False, reader_pairs=False):
     """The untracked pass of decode_many(keys='recover') over one group: every source's frames across its pushes, one recovery call for
     all of them, the context reset afterwards.  Fills every background's ``recovered_keys``."""
     parts = [[] for _ in backs]
@@ -275,18 +277,23 @@ def _recover_group_keys(m, buf, starts, lens, piece, backs, device, nested=False
         for k in numpy.nonzero(n)[0]:
             parts[int(k)].append((fr.frames_of(int(k)), int(fr.base[k]) if len(fr.base) else 0))
     if nested:
-        for b, found in zip(backs, _keys.recover_streams([_joined_frames(ps) if ps else None for ps in parts], device=device)):
+        for b, found in zip(backs, _keys.recover_streams([_joined_frames(ps) if ps else None for ps in parts], device=device, reader_pairs=reader_pairs)):
             b.recovered_keys = found
         m.reset()
         return
-    traces = []
+    traces, reader_traces = [], []
     for k, ps in enumerate(parts):
-        a = _keys.find_auths(_joined_frames(ps))
-        a['stream'] = k
-        traces.append(a)
+        joined = _joined_frames(ps)
+        for find, into in ((_keys.find_auths, traces),) + (((_keys.find_reader_auths, reader_traces),) if reader_pairs else ()):
+            a = find(joined)
+            a['stream'] = k
+            into.append(a)
     traces = numpy.concatenate(traces) if traces else numpy.zeros(0, _keys.AUTH_DTYPE)
     results, _ = _keys.recover(traces, device=device)
-    for b, found in zip(backs, _keys.keys_by_stream(traces, results, len(backs))):
+    found_all = _keys.keys_by_stream(traces, results, len(backs))
+    if reader_pairs and reader_traces:   # the sessions the full search left without a key, in pairs
+        found_all = _keys.recover_reader_streams(numpy.concatenate(reader_traces), found_all, device=device, **_keys.reader_options(reader_pairs, {}))
+    for b, found in zip(backs, found_all):
         b.recovered_keys = found
     m.reset()
 

@@ -10,6 +10,11 @@ Every later authentication of a session is NESTED, its tag nonce encrypted: ``fi
 search one key per candidate and report a NESTED_RESULT_DTYPE record per trace, and ``label_auths`` decrypts the AUTH commands with the
 recovered keys to say which sector each key belongs to.
 
+WITHOUT {at} -- a stream that emulates a tag, a sniffer that hears the reader only -- one authentication is not enough and two are
+(DESIGN.md 8n): ``find_reader_auths(frames)`` is find_auths less the {at} frame, ``pair_reader_auths(traces)`` pairs two sessions of
+one (stream, uid, key type, sector), ``recover_reader(pairs)`` / ``host_recover_reader`` search a READER_KEY_RESULT_DTYPE record per
+pair, and ``recover_reader_streams`` merges the keys into the per-stream dicts.
+
 A card has a key A and a key B PER SECTOR: ``sector_of(block)`` is the mapping, ``sector_table(found)`` turns the recovered
 ``(key_type, block) -> key`` into the ``(key_type, sector) -> key`` table that the protocol machines take (fsm.set_sector_keys,
 NfcMultiContext.set_sector_keys, fsm.host_commands(..., sector_keys=)), ``key_table`` / ``table_dict`` go between that dict and the C
@@ -20,19 +25,20 @@ import numpy as np
 
 from . import _lib
 from ._lib import (AUTH_DTYPE, KEY_RESULT_DTYPE, NESTED_CANDS, NESTED_DTYPE, NESTED_RESULT_DTYPE, NFC_KEY_AMBIGUOUS,  # noqa: F401
-                   NFC_KEY_NONE, NFC_KEY_OK, NFC_KEY_OVERFLOW, NFC_KEY_TIMING)
+                   NFC_KEY_NONE, NFC_KEY_OK, NFC_KEY_OVERFLOW, NFC_KEY_TIMING, NFC_RKEY_VERIFY_INLINE, READER_KEY_RESULT_DTYPE,
+                   READER_PAIR_DTYPE)
 
 
 class KeyRecoveryError(RuntimeError):
     pass
 
 
-def _find(name, dtype, frames):
+def _find(name, dtype, frames, per=4):
     L = _lib.load()
     t = np.ascontiguousarray(frames.table, _lib.RAW_FRAME_DTYPE)
     b = [np.ascontiguousarray(a, np.uint8) for a in frames.bytes]
     p = [np.ascontiguousarray(a, np.uint8) for a in frames.par]
-    out = np.zeros(len(t) // 4 + 1, dtype)   # (an authentication is four frames)
+    out = np.zeros(len(t) // per + 1, dtype)   # (an authentication is `per` frames)
     n = C.c_size_t(0)
     ptr = lambda a: a.ctypes.data if a.size else None
     rc = getattr(L, name)(ptr(t), len(t), ptr(b[0]), ptr(p[0]), ptr(b[1]), ptr(p[1]), out.ctypes.data, len(out), C.byref(n))
@@ -76,6 +82,85 @@ def recover(traces, device=0, **cfg):
 def host_recover(traces, **cfg):
     """The CPU twin (nfc_host_recover_keys): the same results, statuses and capacity rules, no GPU."""
     return _run(_lib.load().nfc_host_recover_keys, traces, cfg)
+
+
+def find_reader_auths(frames):
+    """The first authentications of one stream as far as the READER's {nr}{ar} (nfc_find_reader_auths): find_auths' rule less the {at}
+    frame, so a superset of find_auths' by `frame` -> AUTH_DTYPE records, at_enc and par bits 8 .. 11 zero."""
+    return _find('nfc_find_reader_auths', AUTH_DTYPE, frames, per=3)
+
+
+def pair_reader_auths(traces):
+    """Pairs for recover_reader: the traces are grouped by (stream, uid, key_type, sector_of(block)) in order of first appearance, and
+    per group the FIRST TWO sessions that differ in nt or nr_enc make one pair (search: the earlier) -- two identical sessions single
+    nothing out and are never paired.  -> (READER_PAIR_DTYPE records, the unpaired traces as AUTH_DTYPE records, in order)."""
+    t = np.ascontiguousarray(traces, AUTH_DTYPE).reshape(-1)
+    groups = {}
+    for i, a in enumerate(t):
+        groups.setdefault((int(a['stream']), int(a['uid']), int(a['key_type']), sector_of(int(a['block']))), []).append(i)
+    pairs, used = [], set()
+    for idx in groups.values():
+        first = t[idx[0]]
+        other = next((j for j in idx[1:] if (int(t[j]['nt']), int(t[j]['nr_enc'])) != (int(first['nt']), int(first['nr_enc']))), None)
+        if other is not None:
+            pairs.append((idx[0], other))
+            used.update((idx[0], other))
+    out = np.zeros(len(pairs), READER_PAIR_DTYPE)
+    for k, (a, b) in enumerate(pairs):
+        out[k]['search'], out[k]['check'] = t[a], t[b]
+    return out, t[[i for i in range(len(t)) if i not in used]]
+
+
+def _run_reader(call, pairs, stage_capacity, verify_inline, cfg):
+    p = np.ascontiguousarray(pairs, READER_PAIR_DTYPE).reshape(-1)
+    out, stats = np.zeros(len(p), READER_KEY_RESULT_DTYPE), _lib.KeyStats()
+    c = _lib.ReaderKeyConfig(_config(**cfg), int(stage_capacity), NFC_RKEY_VERIFY_INLINE if verify_inline else 0)
+    rc = call(p.ctypes.data if len(p) else None, len(p), C.byref(c), out.ctypes.data if len(p) else None, C.byref(stats))
+    if rc != 0:
+        raise KeyRecoveryError('reader key recovery failed with status %d' % rc)
+    return out, stats
+
+
+def recover_reader(pairs, device=0, stage_capacity=0, verify_inline=False, **cfg):
+    """Every pair's key on the GPU (nfc_recover_reader_keys_device): two reader-side authentications of one key, no {at} needed.
+    stage_capacity: joined candidates per pair handed to the verify launch (0: the default); verify_inline: no stage, the walking lane
+    verifies (NFC_RKEY_VERIFY_INLINE).  cfg: recover's.  -> (READER_KEY_RESULT_DTYPE records, _lib.KeyStats)."""
+    L = _lib.load()
+    return _run_reader(lambda *a: L.nfc_recover_reader_keys_device(int(device), *a), pairs, stage_capacity, verify_inline, cfg)
+
+
+def host_recover_reader(pairs, stage_capacity=0, verify_inline=False, **cfg):
+    """The CPU twin (nfc_host_recover_reader_keys): the same results, statuses and capacity rules, about a second per pair on one core."""
+    return _run_reader(_lib.load().nfc_host_recover_reader_keys, pairs, stage_capacity, verify_inline, cfg)
+
+
+def reader_options(reader_pairs, cfg):
+    """The keywords of the reader-pair call of a combined recovery: `cfg` (the search options every recovery call takes) and, where the
+    `reader_pairs` switch is a dict and not just True, recover_reader's OWN options out of it (stage_capacity, verify_inline)."""
+    own = dict(reader_pairs) if isinstance(reader_pairs, dict) else {}
+    unknown = sorted(set(own) - {'stage_capacity', 'verify_inline'})
+    if unknown:
+        raise TypeError('reader_pairs: unknown options %s' % unknown)
+    return dict(cfg, **own)
+
+
+def recover_reader_streams(reader_traces, found, device=0, host=False, **cfg):
+    """The reader-pair branch of a key recovery over several streams.  `reader_traces`: every stream's find_reader_auths records with
+    `stream` filled in; `found`: per stream the dict (key_type, block) -> key that the full search already gave.  The sessions whose
+    (key_type, block) has no key yet are paired (pair_reader_auths) and searched in ONE recover_reader call (host=True: the twin); a key
+    found exactly (NFC_KEY_OK) goes into its stream's dict under the SEARCHED session's (key_type, block), an earlier entry winning.
+    -> the new list of dicts (`found` is not changed)."""
+    out = [dict(d) for d in found]
+    t = np.ascontiguousarray(reader_traces, AUTH_DTYPE).reshape(-1)
+    todo = [i for i, a in enumerate(t) if (int(a['key_type']), int(a['block'])) not in out[int(a['stream'])]]
+    pairs, _ = pair_reader_auths(t[todo])
+    if len(pairs):
+        results, _ = host_recover_reader(pairs, **cfg) if host else recover_reader(pairs, device=device, **cfg)
+        for p, r in zip(pairs, results):
+            if int(r['status']) == NFC_KEY_OK:
+                s = p['search']
+                out[int(s['stream'])].setdefault((int(s['key_type']), int(s['block'])), bytes(bytearray(r['key'].tolist())))
+    return out
 
 
 def keys_by_stream(traces, results, n_streams):
@@ -233,10 +318,12 @@ def label_auths(frames, firsts, first_results, nested, nested_results):
     return found
 
 
-def recover_streams(frames_by_stream, device=0, **cfg):
+def recover_streams(frames_by_stream, device=0, reader_pairs=False, **cfg):
     """First AND nested authentications of several streams: `frames_by_stream` one api.NfcFrames (or None) per stream -> per stream the
     dict of label_auths.  ONE keys.recover call over all first authentications, ONE keys.recover_nested call over all nested ones (cfg:
-    recover's), then label_auths per stream on the host."""
+    recover's), then label_auths per stream on the host.  reader_pairs (True, or a dict of recover_reader's own options, see
+    reader_options): the first authentications that are left without a key -- no {at}, or a noise one -- are paired and searched
+    besides (recover_reader_streams: ONE more call, the same cfg)."""
     firsts, nested = [], []
     for k, fr in enumerate(frames_by_stream):
         if fr is None:
@@ -253,4 +340,13 @@ def recover_streams(frames_by_stream, device=0, **cfg):
     for k, fr in enumerate(frames_by_stream):
         a, b = firsts['stream'] == k, nested['stream'] == k
         out.append(label_auths(fr, firsts[a], first_results[a], nested[b].copy(), nested_results[b]) if fr is not None and a.any() else {})
+    if reader_pairs:
+        parts = []
+        for k, fr in enumerate(frames_by_stream):
+            if fr is not None:
+                a = find_reader_auths(fr)
+                a['stream'] = k
+                parts.append(a)
+        out = recover_reader_streams(np.concatenate(parts) if parts else np.zeros(0, AUTH_DTYPE), out, device=device,
+                                     **reader_options(reader_pairs, cfg))
     return out
