@@ -1110,7 +1110,7 @@ def test_in_place_reruns_with_a_long_window_and_hovering_samples(monkeypatch):
 def test_a_lone_failure_is_rerun_by_the_workgroup_kernel(monkeypatch, where):
     # One level step of +15 % in an otherwise clean stream: the chunk that holds it gives up, the one behind it cannot be certified
     # against a summary that is worth nothing.  Few failures on a clean batch take k_threshold_wg in mode 1 (from the exact state,
-    # four waves per chunk) instead of the general kernel's one wave (host_threshold.h: `lone`; round 6) -- same result, bit for bit,
+    # four waves per chunk) instead of the general kernel's one wave (rerun_plan.h: `lone`; round 6) -- same result, bit for bit,
     # as the oracle's and as with the general kernel re-running everything (NFC_WG_RERUN=0).
     iq = synth.workload('miller', 3_000_000).copy()
     iq[2 * where:] *= np.float32(np.sqrt(1.15))

@@ -136,7 +136,7 @@ struct nfc_ctx {
     size_t wg_lds = 0, wg_lds_base = 0, wg_lds_bulk_max = 0;   // dynamic LDS of k_threshold_wg: with the staging ring / without any staging / the most a whole chunk's planes may bring it to
     bool wg_bulk = true;                                       // a chunk's plane words leave when the chunk is done (NFC_WG_BULK=0: always the ring)
     int wg_lone_max = 4, wg_lone_div = 64;   // ... how many failing chunks still count as lone: at most this many, and at most one in wg_lone_div
-    int wg_rerun_lone = 1;   // a lone failing chunk of a clean batch is re-run by k_threshold_wg, gave up or not (host_threshold.h; NFC_WG_RERUN=0 in the test build: never)
+    int wg_rerun_lone = 1;   // a lone failing chunk of a clean batch is re-run by k_threshold_wg, gave up or not (rerun_plan.h; NFC_WG_RERUN=0 in the test build: never)
     // re-runs by k_threshold_wg<KIND, 4, true> (failed rounds evaluated in place): where it applies, its LDS, up to how many failing chunks
     // of a round take it (more: k_threshold, whose one wave per chunk fills the machine where every chunk fails)
     int wg_ex_ok = 0, wg_ex_max = 0;
@@ -263,8 +263,7 @@ struct nfc_ctx {
     double edge_rate = 0.125;                      // entries per sample seen lately (peak-hold with slow decay)
     double sym_rate[2] = {1.0, 2.0};               // symbols per entry, per type (start at the upper bounds)
     int pend_cur = 0;                               // which half of d_pending holds the open packets' bits
-    std::vector<uint8_t> h_ver;
-    std::vector<uint32_t> h_list;
+    RerunBook book;                                 // the rounds of the attempt in work (rerun_plan.h; reset per attempt, capacity kept)
 
     // last batch
     const void *last_in = nullptr;

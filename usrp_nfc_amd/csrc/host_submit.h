@@ -58,8 +58,7 @@ int enqueue_threshold_ahead(nfc_ctx *c, nfc_ctx::Submitted &b) {
     launch_fill_kind(c, b.d_in, b.n, (int)P.nch, b.ring_in);
     b.timed = b.timing >= 1;
     enqueue_pass0(c, P, A, b.timed ? c->kev_sub[b.slot] : nullptr);   // (P.bulk is off: the other stages' workgroups run beside this kernel)
-    A.nlist = P.nch - 1;
-    A.ver_zero = 1;   // (pass 0 only: every summary is in buffer 0)
+    first_certification(A, P);
     enqueue_certify(c, P, A, nullptr, c->d_ring[(b.ring_in + 1) % NRING].as<float>(), A.sum);
     hipError_t e = hipMemcpyAsync(c->hs_a[b.slot].p, c->d_state.p, sizeof(DevState), hipMemcpyDeviceToHost, c->st);
     if (e == hipSuccess) e = hipEventRecord(c->ev_a[b.slot], c->st);
@@ -241,7 +240,7 @@ int wait_batch(nfc_ctx *c) {
     memcpy(ns, c->hs->totals + TOT_NSYM, 8);
     eps_adapt(c, summary);
     if (summary.n_fail != 0) regular = false, why = "a chunk was not certified";
-    else if (summary.flagged || !sums_exact(after, (int)(summary.eminmax & 0xFFFFu), (int)(summary.eminmax >> 16), summary.vtop)) regular = false, why = "sums not provably exact";
+    else if (summary.flagged || !sums_exact(after.ss_emin, after.ss_emax, (int)(summary.eminmax & 0xFFFFu), (int)(summary.eminmax >> 16), summary.vtop)) regular = false, why = "sums not provably exact";
     else if (!(ne <= c->cap_edges && ns[0] + 2 <= c->cap_sym[0] && ns[1] + 2 <= c->cap_sym[1])) regular = false, why = "a capacity estimate was too small";
     else if (b.spec) {   // (decode.hip.h: dec_verify's verdict on the speculative decode of THIS batch, in the mirror its last launch wrote)
         uint32_t v;

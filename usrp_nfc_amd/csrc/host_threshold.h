@@ -7,26 +7,11 @@ namespace {
 // ---------------------------------------------------------------------------
 // threshold stage
 // ---------------------------------------------------------------------------
-// `ahead`, when given, enqueues the stages that follow (edges, decode) behind the first certification WITHOUT
-// waiting for its verdict: certification almost always succeeds, so the host round trip that reads the verdict
-// overlaps those stages instead of idling the GPU.  *clean reports that the verdict let that work stand.
-// One parallel attempt at the samples [base, n_all) of the batch (base a multiple of the step; the planes, the ring and
-// the carried sums already hold everything before base).  *need_seq: the attempt cannot vouch for its sums (or the
-// sequential kernel was asked for): nothing of it stands and the caller replays sequentially.
-// Every fp64 sum of a batch is exact -- hence independent of the order it was added in -- when all
-// operands are multiples of 2^low and no sum reaches 2^(low + 53).  Operands: ring values (24-bit mantissas)
-// and the carried ss / delta (their lowest set bits); sums: the window sums (bounded by the kernel from the sums
-// it tracked) and the carried ss itself.  hc: the carried values after the batch; emin / emax / vtop: what its chunks measured.
-static bool sums_exact(const Carry &hc, int emin, int emax, uint32_t vtop) {
-    int low = emin - 23;
-    if (hc.ss_emin != 255) low = std::min(low, hc.ss_emin);
-    float vtf;
-    memcpy(&vtf, &vtop, 4);
-    int high = 255 + 64;   // vtop: f32 bits of an upper bound of every window sum the batch saw
-    if (std::isfinite(vtf) && vtf >= 0.f) high = vtf > 0.f ? std::ilogb((double)vtf) + 127 : 0;
-    high = std::max(high, hc.ss_emax);
-    return (emax < 255) && (high - low <= 52);
-}
+// What happens when speculation does not certify is decided in rerun_plan.h (host only, checked on the CPU: tools/rerun_plan_check),
+// each rule stated there once: which failing chunks a round re-runs and which wait (the wait rule), whether the failures count as lone,
+// when the in-place form is switched off (ex_off), whether the round is in place, which kernel takes which chunk (tried_wg), the
+// list of chunks to certify next (pending_after), and the exactness guard (sums_exact).  This file runs the rounds: what is
+// launched, copied and waited for, and in which order.
 
 // What one parallel attempt at [base, n_all) needs before anything is launched: the chunking, room in every per-chunk
 // buffer, and the kernels' argument block.  (Shared by the synchronous path and by a batch submitted ahead, which works
@@ -260,7 +245,6 @@ static int thr_prepare(nfc_ctx *c, const void *d_in, uint32_t n, uint32_t n_all,
     HIPCHK(c, c->d_list.ensure((size_t)nal * 8));   // two lists: the chunks a round re-runs, the chunks it certifies
     HIPCHK(c, c->d_gvtop.ensure((size_t)nal * 4));
     if (gring) HIPCHK(c, c->d_gring.ensure((size_t)nch * c->Lpad * c->lds_per_slot));
-    c->h_ver.assign(nch, 0);
 
     // carried "HIGH ignored" bookkeeping from (_current_state, _last_bit, _dur) at the first stable sample
     const int s0 = (int)skip;
@@ -371,6 +355,284 @@ static void enqueue_certify(nfc_ctx *c, const ThrPlan &P, const ThrArgs &A, Cert
     NFC_LAUNCH(k_certify, dim3(cert_grid(A.nlist)), dim3(256), 0, c->st, A, P.d_cert, info, ring_out, dC(c), sum);
 }
 
+// The first certification of pass 0, for the synchronous path and a batch submitted ahead alike: chunks 1 .. nch - 1 without a list,
+// and no version byte to load (pass 0 wrote every chunk's summary into buffer 0: k_fill zeroed the version bytes).
+static inline void first_certification(ThrArgs &A, const ThrPlan &P) {
+    A.list = nullptr;
+    A.nlist = P.nch - 1;
+    A.ver_zero = 1;
+}
+
+// One parallel attempt as the steps of threshold_span hand it on: what thr_prepare decided, and what the rounds have seen so far
+// (the rounds' own state -- pending list, version bytes, which kernel has tried which chunk -- is the context's RerunBook).
+struct ThrAttempt {
+    ThrArgs A;
+    ThrPlan P;
+    uint32_t base = 0;
+    const std::function<int()> *ahead = nullptr;
+    bool *recut_out = nullptr, *refront_out = nullptr;
+    bool wg = false, lean = false;   // pass 0 by k_threshold_wg / by a kernel that may give up on a chunk, chunk 0 included
+    bool rode = false;               // the window fill rides behind pass 0 (launch_fill_kind)
+    bool dbg = false;
+    bool first_round = true, flags_with_verdict = false, have_summary = false, ran_ahead = false;
+    enum { Go, Clean, Void } verdict = Go;   // of the round just certified: re-run what failed / pass 0 stands as it is / nothing of the attempt stands
+    CertSummary summary{};
+    uint32_t passes = 0;
+    int rounds = 0;
+};
+
+// The test build's tick counter: pass 0 stamps its phases per chunk (ThrArgs.dbg_clk); the report waits for it, sums the ticks up on
+// stderr and leaves the raw stamps in a file.
+static int pass0_ticks_report(nfc_ctx *c, ThrAttempt &T) {
+    const uint32_t nch = T.P.nch;
+    std::vector<unsigned long long> h((size_t)nch * 4);
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    HIPCHK(c, hipMemcpy(h.data(), c->d_certinfo.p, (size_t)nch * 32, hipMemcpyDeviceToHost));
+    unsigned long long t0 = ~0ull, t1 = 0;
+    double pro = 0, loop = 0, epi = 0, maxtot = 0, maxstart = 0;
+    for (uint32_t k = 0; k < nch; k++) {
+        t0 = std::min(t0, h[4 * k]);
+        t1 = std::max(t1, h[4 * k + 3]);
+    }
+    for (uint32_t k = 0; k < nch; k++) {
+        pro += (double)(h[4 * k + 1] - h[4 * k]);
+        loop += (double)(h[4 * k + 2] - h[4 * k + 1]);
+        epi += (double)(h[4 * k + 3] - h[4 * k + 2]);
+        maxtot = std::max(maxtot, (double)(h[4 * k + 3] - h[4 * k]));
+        maxstart = std::max(maxstart, (double)(h[4 * k] - t0));
+    }
+#ifdef NFC_WG_PROF
+    if (T.wg) {
+        std::vector<unsigned long long> pf((size_t)nch * 16);
+        HIPCHK(c, hipMemcpy(pf.data(), (char *)c->d_certinfo.p + (size_t)nch * 32, (size_t)nch * 128, hipMemcpyDeviceToHost));
+        double tk = 0, b1 = 0, b2 = 0, rr = 0;
+        for (size_t k = 0; k < (size_t)nch * 4; k++) {
+            tk += (double)pf[4 * k];
+            b1 += (double)pf[4 * k + 1];
+            b2 += (double)pf[4 * k + 2];
+            rr += (double)pf[4 * k + 3];
+        }
+        const double nw = (double)nch * 4;
+        fprintf(stderr, "[nfc] wg kernel, per wave: %.0f rounds; ticks waiting for samples %.0f, at the first barrier %.0f, at the closing barrier %.0f\n",
+                rr / nw, tk / nw, b1 / nw, b2 / nw);
+    }
+#endif
+    fprintf(stderr, "[nfc] lean kernel, %u chunks, s_memtime ticks: first start .. last end %llu; per wave: incoming state %.0f, loop %.0f, "
+            "summary %.0f, longest wave %.0f, latest start %.0f\n", nch, t1 - t0, pro / nch, loop / nch, epi / nch, maxtot, maxstart);
+    if (const char *path = c->dbg_clk_path.c_str()) {
+        if (path[0] == '/' || path[0] == '.' || path[0] == 'g') {   // a file name: the raw stamps
+            if (FILE *f = fopen(path, "wb")) {
+                fwrite(h.data(), 8, h.size(), f);
+                fclose(f);
+            }
+        }
+    }
+    T.A.dbg_clk = nullptr;
+    return NFC_OK;
+}
+
+// The first round's verdict, out of the mirror: pass 0 stands as it is (Clean), the batch is to be cut finer (Void, *recut_out), or
+// there are failing chunks, whose flags are fetched now unless they came with the verdict.
+static int first_verdict(nfc_ctx *c, ThrAttempt &T) {
+    const uint32_t nch = T.P.nch;
+    memcpy(&T.summary, c->hs->totals + TOT_CERT, sizeof T.summary);
+    if (T.base == 0) eps_adapt(c, T.summary);
+    if (T.summary.n_fail == 0 && !T.dbg) {
+        T.have_summary = true;
+        T.verdict = ThrAttempt::Clean;
+        return NFC_OK;
+    }
+    // More than one chunk in 64 failed and the batch was cut for a clean stream: re-running those long chunks one wave
+    // each is the expensive way round (a re-run pass costs what a chunk is long) -- pass 0 again on the fine cut costs
+    // 0.2 ms and leaves short chunks to re-run.  (The next batches are cut fine from the start: fine_left.)
+    if (T.recut_out && c->fine_adapt && T.wg && c->fine_left == 0 && !c->P.chunk_samples && c->fine_mult > 1 &&
+        (uint64_t)T.summary.n_fail * 64u > (uint64_t)nch) {
+        *T.recut_out = true;
+        T.verdict = ThrAttempt::Void;
+        return NFC_OK;
+    }
+    if (!T.flags_with_verdict) HIPCHK(c, hipMemcpy(c->h_cflags.p, c->d_cflags.p, (size_t)4 * nch, hipMemcpyDeviceToHost));
+    return NFC_OK;
+}
+
+// Certify the pending chunks (RerunBook.pending) against their predecessors' summaries and wait for the verdict.  The first round
+// also resolves the end-of-batch state (last workgroup) and leaves its verdict as a summary in the mirrored state block; later rounds
+// (after re-runs) read the per-chunk flags.
+static int certify_round(nfc_ctx *c, ThrAttempt &T) {
+    ThrArgs &A = T.A;
+    const ThrPlan &P = T.P;
+    const uint32_t nch = P.nch, np = (uint32_t)c->book.pending.size();
+    if (T.first_round) {
+        first_certification(A, P);
+    } else {   // (the list to certify: the second half of d_list, sent from pinned staging)
+        memcpy(P.h_list_b, c->book.pending.data(), (size_t)np * 4);
+        HIPCHK(c, hipMemcpyAsync(c->d_list.as<uint32_t>() + nch, P.h_list_b, (size_t)np * 4, hipMemcpyHostToDevice, c->st));
+        A.list = c->d_list.as<uint32_t>() + nch;
+        A.nlist = np;
+        A.ver_zero = 0;
+    }
+    if (T.dbg) HIPCHK(c, c->d_certinfo.ensure((size_t)nch * sizeof(CertInfo)));
+    CertSummary *d_sum = (CertSummary *)(dT(c) + TOT_CERT);
+    float *ring_next = c->d_ring[(c->ring_cur + 1) % NRING].as<float>();
+    bool stamped_last = false;   // the round's last launch is the one that stamps the mirror (k_pkt_finish behind the writer)
+    T.flags_with_verdict = false;
+    if (T.first_round && T.ahead && !T.dbg) {
+        // the stages that follow are enqueued now; their first full-width kernel takes the certification along
+        c->cert = CertLaunch{A, P.d_cert, ring_next, dC(c), d_sum, cert_grid(np)};
+        c->cert_pending = true;
+        const int rc = (*T.ahead)();
+        if (c->cert_pending) {   // (a short batch's one-launch stage, or no edge stage at all: on its own then)
+            c->cert_pending = false;
+            enqueue_certify(c, P, A, nullptr, ring_next, d_sum);
+            HIPCHK(c, mirror_async(c));
+        } else {
+            stamped_last = c->timing < 2;   // (stream markers behind the stages: the stream is waited for)
+        }
+        if (rc) return rc;
+        T.ran_ahead = true;
+    } else {
+        // This branch always ends in hipStreamSynchronize (stamped_last stays false): the asynchronous copies below are complete
+        // when the flags and the mirror are read.
+        enqueue_certify(c, P, A, T.dbg ? c->d_certinfo.as<CertInfo>() : nullptr, ring_next, T.first_round ? d_sum : (CertSummary *)nullptr);
+        // (a stream whose batches have needed re-runs: the first round's flags travel with its verdict too -- one host turn less)
+        T.flags_with_verdict = T.first_round && c->fine_left > 0;
+        if (!T.first_round || T.flags_with_verdict) {   // (the flags, and the chunks' sum bounds for the exactness guard: all in the round's one host turn)
+            HIPCHK(c, hipMemcpyAsync(c->h_cflags.p, c->d_cflags.p, (size_t)4 * nch, hipMemcpyDeviceToHost, c->st));
+            HIPCHK(c, hipMemcpyAsync(P.h_gvtop, c->d_gvtop.p, (size_t)nch * 4, hipMemcpyDeviceToHost, c->st));
+        }
+        HIPCHK(c, mirror_async(c));
+        if (T.first_round && T.ahead) {
+            const int rc = (*T.ahead)();
+            if (rc) return rc;
+            T.ran_ahead = true;
+        }
+    }
+    if (stamped_last) HIPCHK(c, wait_for_stamp(c));
+    else HIPCHK(c, hipStreamSynchronize(c->st));
+    BATCHCHK(c, true);   // (the verdict summary and the totals are about to be read out of the mirror)
+    if (T.first_round && T.rode) {
+        if (c->fill_pending) return fail(c, NFC_ERR_INTERNAL, "the window fill was left behind pass 0 and no launch took it");
+        c->dbg_fill_rode++;
+        // the window's sum depends on the order of its additions and the reference's order gave another figure than the
+        // parallel one: chunks 1 .. of pass 0 ran with the wrong delta.  Rare (a stream that starts inside a transaction), and
+        // nothing of the attempt stands: the caller runs the batch again, k_fill in front, from the state the rider left.
+        if (!(c->hs->carry.delta == 0.0)) {
+            c->dbg_fill_refront++;
+            *T.refront_out = true;
+            T.verdict = ThrAttempt::Void;
+            return NFC_OK;
+        }
+    }
+    return T.first_round ? first_verdict(c, T) : NFC_OK;
+}
+
+// NFC_TRACE / the debugging switches (test build): what a round found, on stderr.
+static int trace_round(nfc_ctx *c, const ThrAttempt &T, const std::vector<uint32_t> &failing) {
+    const ThrPlan &P = T.P;
+    const uint32_t nch = P.nch, np = (uint32_t)c->book.pending.size();
+    if (c->dbg_trace) {
+        fprintf(stderr, "[nfc] round %d: n_fail %u, %zu failing of %u pending (cert[0] %d):", T.rounds, T.summary.n_fail, failing.size(), np, (int)P.h_cert[0]);
+        for (size_t i = 0; i < failing.size() && i < 12; i++) fprintf(stderr, " %u(%x)", failing[i], (unsigned)P.h_gflags[failing[i]]);
+        int why[8] = {0};
+        for (uint32_t k : failing) why[(P.h_gflags[k] >> 4) & 7]++;
+        fprintf(stderr, "; gave up by code:");
+        for (int i = 0; i < 8; i++) fprintf(stderr, " %d", why[i]);
+        fprintf(stderr, "\n");
+    }
+    if (!T.dbg) return NFC_OK;
+    std::vector<CertInfo> ci(nch);
+    HIPCHK(c, hipMemcpy(ci.data(), c->d_certinfo.p, (size_t)nch * sizeof(CertInfo), hipMemcpyDeviceToHost));
+    double worst = 0;
+    for (uint32_t k : c->book.pending) worst = std::max(worst, (double)ci[k].d / std::max(1e-30f, ci[k].allowed));
+    fprintf(stderr, "[nfc] certify round %d: %u pending, %zu failing, worst d/allowed %.3f\n", T.rounds, np, failing.size(), worst);
+    if (T.first_round && T.lean) {
+        std::vector<ChunkInfo> inf(nch);
+        HIPCHK(c, hipMemcpy(inf.data(), c->d_info[0].p, (size_t)nch * sizeof(ChunkInfo), hipMemcpyDeviceToHost));
+        int why[8] = {0};
+        for (uint32_t k : failing) why[(inf[k].flags >> 4) & 7]++;
+        fprintf(stderr, "[nfc]   lean gave up: range %d, band %d, low run %d, allowance %d, first sample %d; not lean %d\n", why[1], why[2],
+                why[3], why[4], why[5], why[0]);
+    }
+    for (size_t i = 0; i < failing.size() && i < 8; i++) {
+        const CertInfo &x = ci[failing[i]];
+        fprintf(stderr, "[nfc]   chunk %u: d %.6g allowed %.6g all_robust %u low_ok %u\n", failing[i], x.d, x.allowed, x.all_robust, x.low_ok);
+    }
+    return NFC_OK;
+}
+
+// Enqueue a round's re-runs as rerun_plan.h planned them.
+// One host turn per round (round 4: two before -- the re-runs were waited for before their certification was enqueued,
+// and every small copy came out of pageable memory): the lists travel from pinned staging, the version bytes of the
+// re-run chunks are flipped here and sent right behind the re-run launch, and the list to certify is made up before the
+// re-runs have run (pending_after).
+static int enqueue_reruns(nfc_ctx *c, ThrAttempt &T, const RerunRound &R) {
+    ThrArgs &A = T.A;
+    const ThrPlan &P = T.P;
+    if (c->dbg_trace) fprintf(stderr, "[nfc]   re-run: %zu by the workgroup kernel%s, %zu by k_threshold\n", R.by_wg.size(), R.in_place ? " (in-place form)" : "", R.by_general.size());
+    A.mode = 1;
+    size_t nl = 0;
+    for (uint32_t k : R.by_wg) P.h_list_a[nl++] = k;
+    for (uint32_t k : R.by_general) P.h_list_a[nl++] = k;
+    HIPCHK(c, hipMemcpyAsync(c->d_list.p, P.h_list_a, nl * 4, hipMemcpyHostToDevice, c->st));
+    if (!R.by_wg.empty()) {
+        A.list = c->d_list.as<uint32_t>();
+        A.nlist = (uint32_t)R.by_wg.size();
+        A.ksteps = 2;
+        launch_threshold(c, P, R.in_place ? ThrLaunch::RerunInPlace : ThrLaunch::RerunLone, A, A.nlist);
+        A.ksteps = c->wg_rounds;
+    }
+    if (!R.by_general.empty()) {
+        A.list = c->d_list.as<uint32_t>() + R.by_wg.size();
+        A.nlist = (uint32_t)R.by_general.size();
+        launch_threshold(c, P, ThrLaunch::RerunGeneral, A, A.nlist);
+    }
+    A.nlist = (uint32_t)nl;
+    c->stats.threshold_passes++;
+    T.passes++;
+    c->stats.chunks_rerun += A.nlist;
+    if (R.in_place) c->stats.chunks_rerun_in_place += (uint32_t)R.by_wg.size();
+    for (uint32_t k : c->book.failing) c->book.ver[k] ^= 1;
+    memcpy(P.h_ver, c->book.ver.data(), P.nch);
+    HIPCHK(c, hipMemcpyAsync(c->d_ver.p, P.h_ver, P.nch, hipMemcpyHostToDevice, c->st));
+    return NFC_OK;
+}
+
+// Can every fp64 sum of this batch be proven exact?  (otherwise the summation order matters: *need_seq)  From the summary when one
+// clean pass stood, else from the per-chunk flags and bounds.
+static int exactness_guard(nfc_ctx *c, const ThrAttempt &T, bool *need_seq) {
+    const ThrPlan &P = T.P;
+    SumBounds s;
+    if (T.have_summary && T.passes == 1) {
+        s.emin = (int)(T.summary.eminmax & 0xFFFFu);
+        s.emax = (int)(T.summary.eminmax >> 16);
+        s.flagged = T.summary.flagged != 0;
+        s.vtop = T.summary.vtop;
+    } else {
+        if (T.first_round) {   // (no round of re-runs has fetched them: the debugging path)
+            HIPCHK(c, hipMemcpyAsync(c->h_cflags.p, c->d_cflags.p, (size_t)4 * P.nch, hipMemcpyDeviceToHost, c->st));
+            HIPCHK(c, hipMemcpyAsync(P.h_gvtop, c->d_gvtop.p, (size_t)P.nch * 4, hipMemcpyDeviceToHost, c->st));
+            HIPCHK(c, mirror_async(c));
+            HIPCHK(c, hipStreamSynchronize(c->st));
+            BATCHCHK(c, true);
+        }
+        // (otherwise the last round's certification brought flags, bounds and the mirror along: nothing ran since)
+        s = fold_sum_bounds(P.nch, P.h_gmin, P.h_gmax, P.h_gflags, P.h_gvtop);
+    }
+    c->h_carry = c->hs->carry;
+    carry_apply_fin(c->h_carry);
+    const bool exact = sums_exact(c->h_carry.ss_emin, c->h_carry.ss_emax, s.emin, s.emax, s.vtop);
+    if (T.dbg) fprintf(stderr, "[nfc] guard: emin %d emax %d ss_emin %d ss_emax %d flagged %d exact %d\n", s.emin, s.emax,
+                       c->h_carry.ss_emin, c->h_carry.ss_emax, (int)s.flagged, (int)exact);
+    if (!exact || s.flagged) *need_seq = true;
+    return NFC_OK;
+}
+
+// One parallel attempt at the samples [base, n_all) of the batch (base a multiple of the step; the planes, the ring and
+// the carried sums already hold everything before base).  *need_seq: the attempt cannot vouch for its sums (or the
+// sequential kernel was asked for): nothing of it stands and the caller replays sequentially.
+// `ahead`, when given, enqueues the stages that follow (edges, decode) behind the first certification WITHOUT
+// waiting for its verdict: certification almost always succeeds, so the host round trip that reads the verdict
+// overlaps those stages instead of idling the GPU.  *clean reports that the verdict let that work stand.
 // *recut_out (optional): pass 0's verdict says the stream is in the regime that needs re-runs and the batch is still on the coarse
 // cut -- nothing of the attempt stands, the caller cuts finer and tries again.
 // *refront_out (optional; without it the window fill always goes in front of pass 0): the fill rode behind pass 0 and its window's sum
@@ -378,371 +640,81 @@ static void enqueue_certify(nfc_ctx *c, const ThrPlan &P, const ThrArgs &A, Cert
 static int threshold_span(nfc_ctx *c, const void *d_in_all, uint32_t n_all, uint32_t skip_all, uint32_t base, const EdgeCarry &ec,
                           const std::function<int()> *ahead, bool *clean, bool *need_seq_out, bool *recut_out = nullptr,
                           bool *refront_out = nullptr) {
-    bool ran_ahead = false;
     *clean = false;
-    const int L = c->L;
     const uint32_t n = n_all - base;
     const uint32_t skip = skip_all > base ? skip_all - base : 0u;
     const void *d_in = (const char *)d_in_all + (size_t)base * c->in_bytes_per_sample;
-    const uint64_t nseen = c->nseen + base;
-    uint32_t passes = 0;
-    ThrArgs A;
-    ThrPlan P;
-    if (int rc = thr_prepare(c, d_in, n, n_all, skip, base, nseen, ec, c->ring_cur, c->d_neg, c->d_pos, false, A, P)) return rc;
+    ThrAttempt T;
+    T.base = base;
+    T.ahead = ahead;
+    T.recut_out = recut_out;
+    T.refront_out = refront_out;
+    T.dbg = c->dbg_any;
+    ThrArgs &A = T.A;
+    const ThrPlan &P = T.P;
+    if (int rc = thr_prepare(c, d_in, n, n_all, skip, base, c->nseen + base, ec, c->ring_cur, c->d_neg, c->d_pos, false, A, T.P)) return rc;
     const uint32_t nch = P.nch;
-    const bool wg = P.form == ThrForm::Workgroup;
-    uint8_t *d_cert = P.d_cert;
-    const uint8_t *h_cert = P.h_cert, *h_gflags = P.h_gflags, *h_gmin = P.h_gmin, *h_gmax = P.h_gmax;
+    T.wg = P.form == ThrForm::Workgroup;
+    T.lean = T.wg || P.form == ThrForm::Lean;
 
     // a 256-sample step must not wrap the ring onto itself: short windows take the sequential kernel
-    const bool force_seq = (c->P.flags & NFC_FLAG_FORCE_SEQUENTIAL) != 0 || L < STEP;
+    const bool force_seq = (c->P.flags & NFC_FLAG_FORCE_SEQUENTIAL) != 0 || c->L < STEP;
     // fill (if the window is not full yet) + per-batch preparation (delta, guard span, version bytes): one launch, in front of pass 0 --
     // or, for a fresh stream with a whole window in the batch, one workgroup of the edge stage's reduce pass BEHIND pass 0 (launch_fill_kind
     // decides on `fresh`): where pass 0 is k_threshold_wg, whose chunk 0 then takes the window from the samples itself, and the stages
     // are about to be enqueued behind pass 0 by `ahead` with the multi-launch edge stage among them (process_batch: fill_can_ride).
     // Pass 0 then reads nothing of the state block: delta = 0 by value, which is the fill's own figure unless the window's sum depends on
-    // the order of its additions -- seen in the mirror below, and the batch is repeated with the fill in front (*refront_out).
-    const bool may_ride = wg && !force_seq && ahead && !c->dbg_any && c->fill_can_ride && !c->fill_front && refront_out;
-    const bool rode = launch_fill_kind(c, d_in, n, (int)nch, -1, may_ride ? P.d_cert : nullptr);
+    // the order of its additions -- seen in the mirror (certify_round), and the batch is repeated with the fill in front (*refront_out).
+    const bool may_ride = T.wg && !force_seq && ahead && !c->dbg_any && c->fill_can_ride && !c->fill_front && refront_out;
+    T.rode = launch_fill_kind(c, d_in, n, (int)nch, -1, may_ride ? P.d_cert : nullptr);
     bool need_seq = force_seq;
     if (!force_seq) {
-        const bool lean = wg || P.form == ThrForm::Lean;   // (pass 0 by a kernel that may give up on a chunk, chunk 0 included)
-        const bool dbg_clk = lean && c->dbg_clk;
+        const bool dbg_clk = T.lean && c->dbg_clk;
         if (dbg_clk) {
             HIPCHK(c, c->d_certinfo.ensure((size_t)nch * 32 * 5));   // (+ 4 waves x 4 counters per chunk in a profiling build)
             A.dbg_clk = c->d_certinfo.as<unsigned long long>();
         }
-        A.delta_by_value = A.own_window = rode ? 1 : 0;   // (pass 0 only: a re-run reads the carry the rider has written by then)
+        A.delta_by_value = A.own_window = T.rode ? 1 : 0;   // (pass 0 only: a re-run reads the carry the rider has written by then)
         A.delta_val = 0.0;
         enqueue_pass0(c, P, A);
         A.delta_by_value = A.own_window = 0;
-        if (dbg_clk) {
-            std::vector<unsigned long long> h((size_t)nch * 4);
-            HIPCHK(c, hipStreamSynchronize(c->st));
-            HIPCHK(c, hipMemcpy(h.data(), c->d_certinfo.p, (size_t)nch * 32, hipMemcpyDeviceToHost));
-            unsigned long long t0 = ~0ull, t1 = 0;
-            double pro = 0, loop = 0, epi = 0, maxtot = 0, maxstart = 0;
-            for (uint32_t k = 0; k < nch; k++) {
-                t0 = std::min(t0, h[4 * k]);
-                t1 = std::max(t1, h[4 * k + 3]);
-            }
-            for (uint32_t k = 0; k < nch; k++) {
-                pro += (double)(h[4 * k + 1] - h[4 * k]);
-                loop += (double)(h[4 * k + 2] - h[4 * k + 1]);
-                epi += (double)(h[4 * k + 3] - h[4 * k + 2]);
-                maxtot = std::max(maxtot, (double)(h[4 * k + 3] - h[4 * k]));
-                maxstart = std::max(maxstart, (double)(h[4 * k] - t0));
-            }
-#ifdef NFC_WG_PROF
-            if (wg) {
-                std::vector<unsigned long long> pf((size_t)nch * 16);
-                HIPCHK(c, hipMemcpy(pf.data(), (char *)c->d_certinfo.p + (size_t)nch * 32, (size_t)nch * 128, hipMemcpyDeviceToHost));
-                double tk = 0, b1 = 0, b2 = 0, rr = 0;
-                for (size_t k = 0; k < (size_t)nch * 4; k++) {
-                    tk += (double)pf[4 * k];
-                    b1 += (double)pf[4 * k + 1];
-                    b2 += (double)pf[4 * k + 2];
-                    rr += (double)pf[4 * k + 3];
-                }
-                const double nw = (double)nch * 4;
-                fprintf(stderr, "[nfc] wg kernel, per wave: %.0f rounds; ticks waiting for samples %.0f, at the first barrier %.0f, at the closing barrier %.0f\n",
-                        rr / nw, tk / nw, b1 / nw, b2 / nw);
-            }
-#endif
-            fprintf(stderr, "[nfc] lean kernel, %u chunks, s_memtime ticks: first start .. last end %llu; per wave: incoming state %.0f, loop %.0f, "
-                    "summary %.0f, longest wave %.0f, latest start %.0f\n", nch, t1 - t0, pro / nch, loop / nch, epi / nch, maxtot, maxstart);
-            if (const char *path = c->dbg_clk_path.c_str()) {
-                if (path[0] == '/' || path[0] == '.' || path[0] == 'g') {   // a file name: the raw stamps
-                    if (FILE *f = fopen(path, "wb")) {
-                        fwrite(h.data(), 8, h.size(), f);
-                        fclose(f);
-                    }
-                }
-            }
-            A.dbg_clk = nullptr;
-        }
+        if (dbg_clk)
+            if (int rc = pass0_ticks_report(c, T)) return rc;
         c->stats.threshold_passes++;
-        passes++;
+        T.passes++;
 
         // certify; re-run what cannot be proven from the exact (look-back) state; certify again what can
         // see a re-run chunk.  Every round makes at least the first pending chunk final.
-        const bool dbg = c->dbg_any;
-        bool first_round = true;
-        c->h_list.clear();
-        std::vector<uint8_t> tried_wg;   // 1: the workgroup kernel ran the chunk's latest re-run; 2: it has given up on it (or k_threshold has taken it since)
-        bool ex_off = false;             // the in-place form is not used for the rest of this batch
-        std::vector<uint8_t> ever_rerun; // chunks re-run at least once in this batch
-        for (uint32_t k = 1; k < nch; k++) c->h_list.push_back(k);
-        int rounds = 0;
-        bool have_summary = false;
-        CertSummary summary{};
-        uint8_t *tot = dT(c);
-        while (!c->h_list.empty()) {
-            const uint32_t np = (uint32_t)c->h_list.size();
-            if (first_round) {
-                A.list = nullptr;   // k_certify: chunks 1 .. nch-1
-            } else {   // (the list to certify: the second half of d_list, sent from pinned staging)
-                memcpy(P.h_list_b, c->h_list.data(), (size_t)np * 4);
-                HIPCHK(c, hipMemcpyAsync(c->d_list.as<uint32_t>() + nch, P.h_list_b, (size_t)np * 4, hipMemcpyHostToDevice, c->st));
-                A.list = c->d_list.as<uint32_t>() + nch;
+        RerunBook &book = c->book;
+        book.reset(nch);
+        const RerunPolicy policy{T.wg, P.in_place, c->wg_rerun_lone != 0, (size_t)c->wg_lone_max, (uint64_t)c->wg_lone_div, (size_t)c->wg_ex_max, nch};
+        while (!book.pending.empty()) {
+            if (int rc = certify_round(c, T)) return rc;
+            if (T.verdict == ThrAttempt::Void) {   // (recut / refront: the caller tries again)
+                A.ver_zero = 0;
+                return NFC_OK;
             }
-            A.nlist = np;
-            A.ver_zero = first_round ? 1 : 0;   // (pass 0 wrote every chunk's summary into buffer 0: k_fill zeroed the version bytes)
-            if (dbg) HIPCHK(c, c->d_certinfo.ensure((size_t)nch * sizeof(CertInfo)));
-            // the first round also resolves the end-of-batch state (last workgroup) and leaves its verdict as a
-            // summary in the mirrored state block; later rounds (after re-runs) read the per-chunk flags
-            CertSummary *d_sum = (CertSummary *)(tot + TOT_CERT);
-            auto launch_certify = [&]() {
-                enqueue_certify(c, P, A, dbg ? c->d_certinfo.as<CertInfo>() : nullptr, c->d_ring[(c->ring_cur + 1) % NRING].as<float>(),
-                                first_round ? d_sum : (CertSummary *)nullptr);
-            };
-            bool stamped_last = false;   // the round's last launch is the one that stamps the mirror (k_pkt_finish behind the writer)
-            bool flags_with_verdict = false;
-            if (first_round && ahead && !dbg) {
-                // the stages that follow are enqueued now; their first full-width kernel takes the certification along
-                c->cert = CertLaunch{A, d_cert, c->d_ring[(c->ring_cur + 1) % NRING].as<float>(), dC(c), d_sum, cert_grid(np)};
-                c->cert_pending = true;
-                const int rc = (*ahead)();
-                if (c->cert_pending) {   // (a short batch's one-launch stage, or no edge stage at all: on its own then)
-                    c->cert_pending = false;
-                    launch_certify();
-                    HIPCHK(c, mirror_async(c));
-                } else {
-                    stamped_last = c->timing < 2;   // (stream markers behind the stages: the stream is waited for)
-                }
-                if (rc) return rc;
-                ran_ahead = true;
-            } else {
-                launch_certify();
-                // (a stream whose batches have needed re-runs: the first round's flags travel with its verdict too -- one host turn less)
-                flags_with_verdict = first_round && c->fine_left > 0;
-                if (!first_round || flags_with_verdict) {   // (the flags, and the chunks' sum bounds for the exactness guard: all in the round's one host turn)
-                    HIPCHK(c, hipMemcpyAsync(c->h_cflags.p, c->d_cflags.p, (size_t)4 * nch, hipMemcpyDeviceToHost, c->st));
-                    HIPCHK(c, hipMemcpyAsync(P.h_gvtop, c->d_gvtop.p, (size_t)nch * 4, hipMemcpyDeviceToHost, c->st));
-                }
-                HIPCHK(c, mirror_async(c));
-                if (first_round && ahead) {
-                    const int rc = (*ahead)();
-                    if (rc) return rc;
-                    ran_ahead = true;
-                }
-            }
-            if (stamped_last) HIPCHK(c, wait_for_stamp(c));
-            else HIPCHK(c, hipStreamSynchronize(c->st));
-            BATCHCHK(c, true);   // (the verdict summary and the totals are about to be read out of the mirror)
-            if (first_round && rode) {
-                if (c->fill_pending) return fail(c, NFC_ERR_INTERNAL, "the window fill was left behind pass 0 and no launch took it");
-                c->dbg_fill_rode++;
-                // the window's sum depends on the order of its additions and the reference's order gave another figure than the
-                // parallel one: chunks 1 .. of pass 0 ran with the wrong delta.  Rare (a stream that starts inside a transaction), and
-                // nothing of the attempt stands: the caller runs the batch again, k_fill in front, from the state the rider left.
-                if (!(c->hs->carry.delta == 0.0)) {
-                    c->dbg_fill_refront++;
-                    *refront_out = true;
-                    A.ver_zero = 0;
-                    return NFC_OK;
-                }
-            }
-            std::vector<uint32_t> failing;
-            if (first_round) {
-                memcpy(&summary, c->hs->totals + TOT_CERT, sizeof summary);
-                if (base == 0) eps_adapt(c, summary);
-                if (summary.n_fail == 0 && !dbg) {
-                    have_summary = true;
-                    break;
-                }
-                // More than one chunk in 64 failed and the batch was cut for a clean stream: re-running those long chunks one wave
-                // each is the expensive way round (a re-run pass costs what a chunk is long) -- pass 0 again on the fine cut costs
-                // 0.2 ms and leaves short chunks to re-run.  (The next batches are cut fine from the start: fine_left.)
-                if (recut_out && c->fine_adapt && wg && c->fine_left == 0 && !c->P.chunk_samples && c->fine_mult > 1 &&
-                    (uint64_t)summary.n_fail * 64u > (uint64_t)nch) {
-                    *recut_out = true;
-                    A.ver_zero = 0;
-                    return NFC_OK;
-                }
-                if (!flags_with_verdict) HIPCHK(c, hipMemcpy(c->h_cflags.p, c->d_cflags.p, (size_t)4 * nch, hipMemcpyDeviceToHost));
-            }
-            if (first_round && lean && !h_cert[0]) failing.push_back(0);   // chunk 0 gave up: re-run from the carried state
-            for (uint32_t k : c->h_list)
-                if (!h_cert[k]) failing.push_back(k);
-            if (c->dbg_trace) {
-                fprintf(stderr, "[nfc] round %d: n_fail %u, %zu failing of %u pending (cert[0] %d):", rounds, summary.n_fail, failing.size(), np, (int)h_cert[0]);
-                for (size_t i = 0; i < failing.size() && i < 12; i++) fprintf(stderr, " %u(%x)", failing[i], (unsigned)h_gflags[failing[i]]);
-                int why[8] = {0};
-                for (uint32_t k : failing) why[(h_gflags[k] >> 4) & 7]++;
-                fprintf(stderr, "; gave up by code:");
-                for (int i = 0; i < 8; i++) fprintf(stderr, " %d", why[i]);
-                fprintf(stderr, "\n");
-            }
-            if (dbg) {
-                std::vector<CertInfo> ci(nch);
-                HIPCHK(c, hipMemcpy(ci.data(), c->d_certinfo.p, (size_t)nch * sizeof(CertInfo), hipMemcpyDeviceToHost));
-                double worst = 0;
-                for (uint32_t k : c->h_list) worst = std::max(worst, (double)ci[k].d / std::max(1e-30f, ci[k].allowed));
-                fprintf(stderr, "[nfc] certify round %d: %u pending, %zu failing, worst d/allowed %.3f\n", rounds, np,
-                        failing.size(), worst);
-                if (first_round && lean) {
-                    std::vector<ChunkInfo> inf(nch);
-                    HIPCHK(c, hipMemcpy(inf.data(), c->d_info[0].p, (size_t)nch * sizeof(ChunkInfo), hipMemcpyDeviceToHost));
-                    int why[8] = {0};
-                    for (uint32_t k : failing) why[(inf[k].flags >> 4) & 7]++;
-                    fprintf(stderr, "[nfc]   lean gave up: range %d, band %d, low run %d, allowance %d, first sample %d; not lean %d\n", why[1], why[2],
-                            why[3], why[4], why[5], why[0]);
-                }
-                for (size_t i = 0; i < failing.size() && i < 8; i++) {
-                    const CertInfo &x = ci[failing[i]];
-                    fprintf(stderr, "[nfc]   chunk %u: d %.6g allowed %.6g all_robust %u low_ok %u\n", failing[i], x.d,
-                            x.allowed, x.all_robust, x.low_ok);
-                }
-            }
+            if (T.verdict == ThrAttempt::Clean) break;
+            const std::vector<uint32_t> &failing = failing_of(book, T.first_round, T.lean, P.h_cert);
+            if (int rc = trace_round(c, T, failing)) return rc;
             if (failing.empty()) break;
-            first_round = false;
+            T.first_round = false;
             A.ver_zero = 0;
-            // A chunk right behind one that is re-run now and that did not give up itself is NOT re-run in this round: its own
-            // evaluation may well be sound -- what failed is the comparison with a predecessor whose summary was worthless -- and
-            // from the state resolved now it would only be evaluated against that worthless summary again.  It stays pending
-            // (below: it can see a re-run chunk) and is certified against the predecessor's new summary in the next round.
-            {
-                std::vector<uint32_t> now;
-                uint32_t last = 0xFFFFFFFFu;
-                if (ever_rerun.empty()) ever_rerun.assign(nch, 0);
-                for (uint32_t k : failing) {   // (ascending)
-                    // (only a chunk still standing on its pass-0 evaluation: one that has been re-run already was evaluated from a
-                    // resolved state that has moved since -- waiting would only cost it a round, measured: 3 general passes
-                    // instead of 2 when every chunk fails)
-                    const bool gave_up = (h_gflags[k] & 4) != 0;
-                    if (!gave_up && !ever_rerun[k] && last != 0xFFFFFFFFu && k == last + 1) continue;
-                    now.push_back(k);
-                    last = k;
-                }
-                for (uint32_t k : now) ever_rerun[k] = 1;
-                failing.swap(now);
-            }
-            // Re-runs from the exact state: by the workgroup kernel's in-place form where it applies and the round's failures fit the
-            // machine (below), else by k_threshold, which decides everything in place and never gives up (so the rounds converge).
-            // (The pass-0 form of the workgroup kernel re-running whatever did not give up was measured on the stress captures in rounds 4-6 --
-            // the chunks behind a chunk that gave up mostly give up themselves, 6 passes / 4.7 ms against 3 / 2.1 -- and went in round 6.)
-            // A LONE failure on an otherwise clean batch (round 6) -- a superstep that grew on the head-room it saw and met the next frame:
-            // one chunk in a thousand -- takes the workgroup kernel too, gave up or not: from the exact state (no margin for a speculated
-            // window) and with supersteps of at most two rounds it mostly gets through, and four waves walk a 98 304-sample chunk in 70 us
-            // where the general kernel's one wave takes 670 (measured on configs[2] with the margin set to make a chunk give up: the step
-            // 0.927 -> 0.526 ms, same call).  If it gives up again the general kernel takes it in the next round (tried_wg).
-            const bool lone = c->wg_rerun_lone && failing.size() <= (size_t)c->wg_lone_max && (uint64_t)failing.size() * (uint64_t)c->wg_lone_div <= (uint64_t)nch;
-            // Up to a machine-full of failing chunks (round 6): the workgroup kernel in the form that evaluates a failed round IN PLACE
-            // (k_threshold_wg<KIND, 4, true>) -- it gives up only where a round is not four whole steps or a LOW run is out of sight.
-            if (tried_wg.empty()) tried_wg.assign(nch, 0);
-            {   // (a stream it keeps giving up on -- values out of range, a stream's first chunk: k_threshold alone for the rest of the batch)
-                size_t ran = 0, gave = 0;
-                for (uint32_t k : failing)
-                    if (tried_wg[k] == 1) ran++, gave += (h_gflags[k] & 4) ? 1 : 0;
-                if (gave * 4 > ran) ex_off = true;
-            }
-            const bool ex = P.in_place && !ex_off && failing.size() <= (size_t)c->wg_ex_max;
-            std::vector<uint32_t> by_wg, by_general;
-            for (uint32_t k : failing) {
-                // (a chunk the in-place form has re-run and that did NOT give up may take it again -- what failed is its incoming state;
-                // one it gave up on is k_threshold's for the rest of the batch: that kernel never gives up, so the rounds converge)
-                if (tried_wg[k] == 1 && (h_gflags[k] & 4)) tried_wg[k] = 2;
-                const bool ex_again = ex && tried_wg[k] == 1;
-                if (wg && (!tried_wg[k] || ex_again) && (ex || lone)) {
-                    by_wg.push_back(k);
-                    tried_wg[k] = 1;
-                } else {
-                    by_general.push_back(k);
-                    if (tried_wg[k]) tried_wg[k] = 2;
-                }
-            }
-            if (c->dbg_trace) fprintf(stderr, "[nfc]   re-run: %zu by the workgroup kernel%s, %zu by k_threshold\n", by_wg.size(), ex ? " (in-place form)" : "", by_general.size());
-            A.mode = 1;
-            // One host turn per round (round 4: two before -- the re-runs were waited for before their certification was enqueued,
-            // and every small copy came out of pageable memory): the lists travel from pinned staging, the version bytes of the
-            // re-run chunks are flipped here and sent right behind the re-run launch, and the list to certify is made up before the
-            // re-runs have run -- a re-run chunk is taken to leave slots untouched (which its new summary will say): a superset of
-            // what has to be certified, and certifying a chunk nothing has changed for gives the verdict it had.
-            {
-                uint32_t *la = P.h_list_a;
-                size_t nl_ = 0;
-                for (uint32_t k : by_wg) la[nl_++] = k;
-                for (uint32_t k : by_general) la[nl_++] = k;
-                HIPCHK(c, hipMemcpyAsync(c->d_list.p, la, nl_ * 4, hipMemcpyHostToDevice, c->st));
-            }
-            if (!by_wg.empty()) {
-                A.list = c->d_list.as<uint32_t>();
-                A.nlist = (uint32_t)by_wg.size();
-                A.ksteps = 2;
-                launch_threshold(c, P, ex ? ThrLaunch::RerunInPlace : ThrLaunch::RerunLone, A, A.nlist);
-                A.ksteps = c->wg_rounds;
-            }
-            if (!by_general.empty()) {
-                A.list = c->d_list.as<uint32_t>() + by_wg.size();
-                A.nlist = (uint32_t)by_general.size();
-                launch_threshold(c, P, ThrLaunch::RerunGeneral, A, A.nlist);
-            }
-            A.nlist = (uint32_t)failing.size();
-            c->stats.threshold_passes++;
-            passes++;
-            c->stats.chunks_rerun += A.nlist;
-            if (ex) c->stats.chunks_rerun_in_place += (uint32_t)by_wg.size();
-            std::vector<uint8_t> ran(nch, 0);
-            for (uint32_t k : failing) {
-                ran[k] = 1;
-                c->h_ver[k] ^= 1;
-            }
-            memcpy(P.h_ver, c->h_ver.data(), nch);
-            HIPCHK(c, hipMemcpyAsync(c->d_ver.p, P.h_ver, nch, hipMemcpyHostToDevice, c->st));
-            // pending: the re-run chunks (a predecessor may have been re-run beside them) and every
-            // chunk that can see one of them through predecessors that left ring slots untouched
-            c->h_list.clear();
-            bool vis = false;
-            for (uint32_t k = 0; k < nch; k++) {
-                if (vis || ran[k]) c->h_list.push_back(k);
-                const bool full = !ran[k] && !(h_gflags[k] & 2);   // (a re-run chunk: not known yet -- taken as not full)
-                vis = ran[k] || (vis && !full);
-            }
-            if (++rounds > 2 * (int)nch + 2) return fail(c, NFC_ERR_INTERNAL, "threshold passes did not converge");
+            if (int rc = enqueue_reruns(c, T, plan_round(policy, book, P.h_gflags))) return rc;
+            pending_after(book, nch, P.h_gflags);
+            if (++T.rounds > 2 * (int)nch + 2) return fail(c, NFC_ERR_INTERNAL, "threshold passes did not converge");
         }
-
-        // can every fp64 sum of this batch be proven exact?  (otherwise the summation order matters)
-        int emin = 255, emax = 0;
-        bool flagged = false;
-        uint32_t vtop = 0;
-        if (have_summary && passes == 1) {
-            emin = (int)(summary.eminmax & 0xFFFFu);
-            emax = (int)(summary.eminmax >> 16);
-            flagged = summary.flagged != 0;
-            vtop = summary.vtop;
-        } else {
-            if (first_round) {   // (no round of re-runs has fetched them: the debugging path)
-                HIPCHK(c, hipMemcpyAsync(c->h_cflags.p, c->d_cflags.p, (size_t)4 * nch, hipMemcpyDeviceToHost, c->st));
-                HIPCHK(c, hipMemcpyAsync(P.h_gvtop, c->d_gvtop.p, (size_t)nch * 4, hipMemcpyDeviceToHost, c->st));
-                HIPCHK(c, mirror_async(c));
-                HIPCHK(c, hipStreamSynchronize(c->st));
-                BATCHCHK(c, true);
-            }
-            // (otherwise the last round's certification brought flags, bounds and the mirror along: nothing ran since)
-            for (uint32_t k = 0; k < nch; k++) {
-                emin = std::min(emin, (int)h_gmin[k]);
-                emax = std::max(emax, (int)h_gmax[k]);
-                if (h_gflags[k] & 1) flagged = true;
-                vtop = std::max(vtop, P.h_gvtop[k]);
-            }
-        }
-        c->h_carry = c->hs->carry;
-        carry_apply_fin(c->h_carry);
-        const bool exact = sums_exact(c->h_carry, emin, emax, vtop);
-        if (dbg) fprintf(stderr, "[nfc] guard: emin %d emax %d ss_emin %d ss_emax %d flagged %d exact %d\n", emin, emax,
-                         c->h_carry.ss_emin, c->h_carry.ss_emax, (int)flagged, (int)exact);
-        if (!exact || flagged) need_seq = true;
+        if (int rc = exactness_guard(c, T, &need_seq)) return rc;
     }
 
     A.ver_zero = 0;
     *need_seq_out = need_seq;
     if (!need_seq) {
         // the end-of-batch ring was resolved beside the last certification unless chunks were re-run after it
-        if (passes > 1 || nch == 1)
+        if (T.passes > 1 || nch == 1)
             NFC_LAUNCH(k_finalize_state, dim3(1), dim3(FIN_BLOCK), 0, c->st, A, c->d_ring[(c->ring_cur + 1) % NRING].as<float>(), dC(c));
         c->ring_cur = (c->ring_cur + 1) % NRING;
-        *clean = ran_ahead && passes == 1;
+        *clean = T.ran_ahead && T.passes == 1;
     }
     return NFC_OK;
 }

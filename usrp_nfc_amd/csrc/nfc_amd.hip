@@ -17,6 +17,7 @@
 // The host side in parts, included below into this one translation unit:
 //   host_context.h    the test build's switches, nfc_ctx (every HIP resource a member that releases itself: dev_buf.h), the mirrored state block, launch helpers
 //   host_threshold.h  the threshold stage: plan, pass 0, certification rounds, re-runs, sequential fallback
+//                     (host only, before them: chunk_cut.h, how a batch is cut by dispatch row; rerun_plan.h, what a round of re-runs does)
 //   host_stages.h     edge stage, decode + framing stage, short batches in one launch, process_batch
 //   host_submit.h     batches submitted ahead (nfc_submit_device / nfc_wait)
 // and, in this file, the C-ABI entry points.
@@ -57,6 +58,7 @@
 using namespace nfc;
 
 #include "chunk_cut.h"
+#include "rerun_plan.h"
 #include "dev_buf.h"
 #include "host_context.h"
 #include "host_threshold.h"

@@ -1183,7 +1183,7 @@ struct CertSummary {
     uint32_t n_fail;            // chunks whose certification failed (atomic; zeroed by k_fill)
     uint32_t eminmax;           // exponent fields over every chunk's accepted values: emin | emax << 16
     uint32_t worst;             // f32 bits (atomic max): the largest L1 distance between a chunk's speculated and true incoming window, over the
-                                // chunk's smallest window sum -- how much of the margin eps the speculation used (the host sizes eps by it)
+                                // chunk's smallest window sum -- how much of the margin eps the speculation used (a kept diagnostic: eps stays fixed)
     uint32_t flagged;           // some chunk met a value it cannot vouch for
     uint32_t vtop;              // raw bits of an upper bound of every ring value of the batch
     uint32_t n_carried;         // window slots that no chunk of the batch accepted a sample into (their value is the incoming ring's)
