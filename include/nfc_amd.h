@@ -505,8 +505,9 @@ int nfc_multi_fetch(nfc_multi *m, uint32_t what, nfc_multi_fetched *out /* may b
  * bits to a byte plus the odd-parity check (fsm.py:28-47) and the ISO 14443-3 CRC_A (utilities.py:30-41).  Two kernel launches
  * (csrc/frames.hip.h, nfc_frames.hip): a scan over the packet closes gives every frame its place, then a lane per frame reads its
  * nine-bit fields from the bit array the decode stage left (packed 32 to a word, or a byte per bit) and writes the record, the bytes
- * and the parity bits.  What stays on the host is the sequential protocol machine: nfc_fsm_process_frames (for the many streams of an
- * nfc_multi it runs on the GPU too, a lane per stream: nfc_multi_fetch_commands below).
+ * and the parity bits.  Behind them the sequential protocol machine: nfc_fsm_process_frames on the host, or on the GPU -- for the many
+ * streams of an nfc_multi a lane per stream (nfc_multi_fetch_commands below), for this one stream a lane per transaction
+ * (nfc_track_commands / nfc_read_commands below).
  * REPAIR, with rem = n_bits % 9 and start_bit = (type == 0 ? 1 : 0):
  *   rem 0: nothing;  rem 8: the last byte's parity bit is start_bit;  rem 1: the last bit is dropped, NFC_FRAME_EXTRA_ERROR iff it
  *   differs from start_bit;  rem 2..7: rem bits are dropped, NFC_FRAME_MANY_MORE_ERROR.
@@ -698,6 +699,69 @@ int nfc_host_commands_keyed(nfc_fsm_state *st, const nfc_fsm_key_table *table, c
                             size_t cap, size_t *used);
 int nfc_multi_set_sector_keys(nfc_multi *m, int64_t stream /* -1: every stream */, const nfc_fsm_key_table *table);
 int nfc_multi_get_sector_keys(nfc_multi *m, uint32_t stream, nfc_fsm_key_table *table);
+
+/* ---- commands on the GPU for ONE long stream: a lane per transaction ----------------------------------------------------------------
+ * A single context's frames go through the same machine (csrc/fsm.hip.h) on the device, although one stream is one sequence: a plain
+ * REQA / WUPA heard outside a CRYPTO1 session leaves the machine in a state that does not depend on where it was, so a long capture is
+ * thousands of transactions that can each be walked by a lane of their own (csrc/ctx_commands.hip.h).  "Outside a session"
+ * is a guess until the transaction before has been walked: every segment -- from one such reader frame to the next -- is walked
+ * speculatively, then one wave goes through the segments' summaries in order and walks again, from the true machine, every segment
+ * whose guess was wrong.
+ * nfc_track_commands(ctx, on): off at create.  While it is on, every batch that completes -- the return of nfc_push / nfc_push_device /
+ * nfc_push_edges, nfc_wait for a submitted batch -- enqueues, with no further host wait, the frames' two launches (the context's own
+ * lazy assembly: a later nfc_read_frames of that batch launches nothing more) and four launches behind them on the context's stream:
+ * merged order and cuts, segment numbering, the speculative walk, the resolve.  The machine advances exactly once per batch whether or
+ * not anybody reads.  A batch that closed no packet launches nothing.  A context that never turns tracking on allocates and launches
+ * exactly what it did before.
+ * nfc_read_commands: ONE copy to pinned memory, then one wait.  cmd / src / data / enc as in nfc_multi_commands for one stream: the
+ * frames of both types merged by idx (type 0 first on a tie), src = type << 31 | index among the batch's raw frames of that type, a
+ * record's byte_off into data / enc, a slot of the RAW n_bytes per frame.  A second call before the next batch returns the same data and
+ * touches no machine.  No completed batch, or tracking off when the last batch completed: NFC_ERR_STATE.  A batch without frames:
+ * n_launches == 0, n_commands == 0, NULL arrays.  The pointers live until the next batch completes, nfc_read_commands, nfc_reset,
+ * nfc_set_fsm_state or nfc_destroy.
+ * THE MACHINE: nfc_set_fsm_keys, nfc_set_fsm_sector_keys / nfc_get_fsm_sector_keys, nfc_get_fsm_state / nfc_set_fsm_state as their
+ * nfc_multi_* namesakes for one stream; they complete the device first.  nfc_reset returns the machine to nfc_fsm_state_init's state
+ * and empties the table.  The table's device buffer is allocated by the first nfc_set_fsm_sector_keys.  Argument errors are
+ * NFC_ERR_ARG, raised before the device is touched, the argument's name in the message.
+ * PROMISED: records, data, enc and the state afterwards equal nfc_host_commands_keyed's on the same raw frames, bit for bit, on every
+ * input -- sessions that span batches, nested authentications, malformed traffic.
+ * NOT PROMISED: more than one stream (nfc_multi_* is that); cuts anywhere but at a plain REQA / WUPA; speed on a capture that never
+ * leaves a session: a REQA inside a session is ciphertext to the machine, the guess fails from there on, and ONE lane walks the rest
+ * of the batch (n_rerun_frames says how much).
+ * nfc_host_commands_segmented: the twin on the CPU (no GPU needed) -- nfc_host_commands_keyed's arguments and results, computed by
+ * the kernels' own text: cuts, speculative walks in the order segment_order names (n_order entries; those below n_segments must name
+ * every segment once, larger ones are skipped; NULL: ascending), resolve.  counters may be NULL. */
+typedef struct nfc_ctx_command_counters {   /* 16 bytes */
+    uint32_t n_segments;            /* 0 for no frames */
+    uint32_t n_rerun_segments;      /* segments whose guess was wrong: walked again from the true machine */
+    uint32_t n_rerun_frames;        /* ... and the frames in them */
+    uint32_t n_keydep_segments;     /* speculative walks that read cur_key before writing it */
+} nfc_ctx_command_counters;
+typedef struct nfc_ctx_commands {
+    const nfc_frame *cmd;
+    const uint32_t *src;
+    const uint8_t *data;
+    const uint16_t *enc;
+    uint64_t n_commands, n_bytes;
+    uint32_t flags;                 /* NFC_FSM_* of the machine behind the batch */
+    uint32_t n_launches;            /* of the batch's tracking: 6, or 0 for a batch without frames */
+    nfc_ctx_command_counters counters;
+    uint64_t bytes_copied;          /* device -> host, of this call */
+    double ms_kernels;              /* with nfc_set_timing >= 1 when the batch completed: the six launches by HIP events; else all 0 */
+    double ms_frames, ms_merge, ms_walk, ms_resolve;   /* ... the frames' two / merged order and segment numbering / the speculative walk / the resolve */
+    uint64_t reserved[4];
+} nfc_ctx_commands;
+int nfc_track_commands(nfc_ctx *ctx, int on);
+int nfc_read_commands(nfc_ctx *ctx, nfc_ctx_commands *out);
+int nfc_set_fsm_keys(nfc_ctx *ctx, const uint8_t key_a[6], const uint8_t key_b[6]);
+int nfc_set_fsm_sector_keys(nfc_ctx *ctx, const nfc_fsm_key_table *table /* NULL: an empty one */);
+int nfc_get_fsm_sector_keys(nfc_ctx *ctx, nfc_fsm_key_table *table);
+int nfc_get_fsm_state(nfc_ctx *ctx, nfc_fsm_state *st);
+int nfc_set_fsm_state(nfc_ctx *ctx, const nfc_fsm_state *st);
+int nfc_host_commands_segmented(nfc_fsm_state *st, const nfc_fsm_key_table *table, const nfc_raw_frame *merged, size_t n,
+                                const uint8_t *bytes0, const uint8_t *par0, const uint8_t *bytes1, const uint8_t *par1, nfc_frame *out,
+                                uint8_t *data, uint16_t *enc, size_t cap, size_t *used, const uint32_t *segment_order, size_t n_order,
+                                nfc_ctx_command_counters *counters);
 
 /* ---- key recovery: a MIFARE Classic sector key from one sniffed first authentication --------------------------------------------------
  * An eavesdropper who has no keys still sees everything the recovery needs: the UID (SEL1R), the tag nonce nt in the clear (RANDTA),

@@ -85,6 +85,17 @@ class MultiCommands(C.Structure):   # nfc_multi_commands
                 ('bytes_copied', C.c_uint64), ('ms_kernels', C.c_double), ('ms_machine', C.c_double), ('reserved', C.c_uint64 * 4)]
 
 
+class CtxCommandCounters(C.Structure):   # nfc_ctx_command_counters
+    _fields_ = [('n_segments', C.c_uint32), ('n_rerun_segments', C.c_uint32), ('n_rerun_frames', C.c_uint32), ('n_keydep_segments', C.c_uint32)]
+
+
+class CtxCommands(C.Structure):   # nfc_ctx_commands
+    _fields_ = [('cmd', C.c_void_p), ('src', C.c_void_p), ('data', C.c_void_p), ('enc', C.c_void_p), ('n_commands', C.c_uint64),
+                ('n_bytes', C.c_uint64), ('flags', C.c_uint32), ('n_launches', C.c_uint32), ('counters', CtxCommandCounters),
+                ('bytes_copied', C.c_uint64), ('ms_kernels', C.c_double), ('ms_frames', C.c_double), ('ms_merge', C.c_double), ('ms_walk', C.c_double),
+                ('ms_resolve', C.c_double), ('reserved', C.c_uint64 * 4)]
+
+
 class KeyConfig(C.Structure):   # nfc_key_config
     _fields_ = [('initial_capacity', C.c_uint64), ('max_capacity', C.c_uint64), ('max_batch', C.c_uint32), ('flags', C.c_uint32),
                 ('reserved', C.c_uint32 * 2)]
@@ -233,6 +244,8 @@ SYMBOLS = ['nfc_abi_version', 'nfc_device_count', 'nfc_create', 'nfc_destroy', '
            'nfc_multi_set_keys', 'nfc_multi_get_fsm_state', 'nfc_multi_set_fsm_state',
            'nfc_sector_of_block', 'nfc_fsm_key_table_init', 'nfc_fsm_set_sector_key', 'nfc_fsm_get_key_table', 'nfc_fsm_set_key_table',
            'nfc_host_commands_keyed', 'nfc_multi_set_sector_keys', 'nfc_multi_get_sector_keys',
+           'nfc_track_commands', 'nfc_read_commands', 'nfc_set_fsm_keys', 'nfc_set_fsm_sector_keys', 'nfc_get_fsm_sector_keys', 'nfc_get_fsm_state',
+           'nfc_set_fsm_state', 'nfc_host_commands_segmented',
            'nfc_find_auths', 'nfc_host_recover_keys', 'nfc_recover_keys_device',
            'nfc_find_nested_auths', 'nfc_host_nested_candidates', 'nfc_nested_candidates_device', 'nfc_host_recover_nested_keys',
            'nfc_recover_nested_keys_device',
@@ -373,6 +386,15 @@ def load(path=None):
     L.nfc_host_commands_keyed.argtypes = [C.POINTER(FsmState), C.POINTER(FsmKeyTable), vp, sz, vp, vp, vp, vp, vp, vp, vp, sz, psz]
     L.nfc_multi_set_sector_keys.argtypes = [vp, C.c_int64, C.POINTER(FsmKeyTable)]
     L.nfc_multi_get_sector_keys.argtypes = [vp, u32, C.POINTER(FsmKeyTable)]
+    L.nfc_track_commands.argtypes = [vp, C.c_int]
+    L.nfc_read_commands.argtypes = [vp, C.POINTER(CtxCommands)]
+    L.nfc_set_fsm_keys.argtypes = [vp, vp, vp]
+    L.nfc_set_fsm_sector_keys.argtypes = [vp, C.POINTER(FsmKeyTable)]
+    L.nfc_get_fsm_sector_keys.argtypes = [vp, C.POINTER(FsmKeyTable)]
+    L.nfc_get_fsm_state.argtypes = [vp, C.POINTER(FsmState)]
+    L.nfc_set_fsm_state.argtypes = [vp, C.POINTER(FsmState)]
+    L.nfc_host_commands_segmented.argtypes = [C.POINTER(FsmState), C.POINTER(FsmKeyTable), vp, sz, vp, vp, vp, vp, vp, vp, vp, sz, psz, vp, sz,
+                                              C.POINTER(CtxCommandCounters)]
     L.nfc_find_auths.argtypes = [vp, sz, vp, vp, vp, vp, vp, sz, psz]
     L.nfc_host_recover_keys.argtypes = [vp, sz, C.POINTER(KeyConfig), vp, C.POINTER(KeyStats)]
     L.nfc_recover_keys_device.argtypes = [C.c_int, vp, sz, C.POINTER(KeyConfig), vp, C.POINTER(KeyStats)]

@@ -230,6 +230,54 @@ class NfcContext(object):
             recs.append(r), data.append(b), par.append(p)
         return NfcFrames(recs, data, par)
 
+    def track_commands(self, on=True):
+        """While on, every batch that completes also assembles its frames and runs the protocol machine over them on the GPU, CRYPTO1
+        included, a lane per transaction (nfc_track_commands, csrc/ctx_commands.hip.h): six launches behind the batch's own, no host
+        wait.  The machine's state stays on the device from batch to batch; commands() brings the last batch's commands to the host."""
+        self._chk(self.L.nfc_track_commands(self.h, int(bool(on))), 'nfc_track_commands')
+
+    def set_keys(self, key_a=(0xFF,) * 6, key_b=(0xFF,) * 6):
+        """MIFARE Classic keys A / B of the context's machine, six bytes each, as fsm.set_keys (nfc_set_fsm_keys)."""
+        a, b = np.ascontiguousarray(key_a, np.uint8), np.ascontiguousarray(key_b, np.uint8)
+        if a.size != 6 or b.size != 6:
+            raise NfcError('set_keys: key_a and key_b are six bytes each')
+        self._chk(self.L.nfc_set_fsm_keys(self.h, a.ctypes.data, b.ctypes.data), 'nfc_set_fsm_keys')
+
+    def set_sector_keys(self, table):
+        """The per-sector key table of the context's machine, as fsm.set_sector_keys: a dict (key_type, sector) -> six key bytes or an
+        _lib.FsmKeyTable; None or {} empties it (nfc_set_fsm_sector_keys).  The first call allocates the table's device buffer."""
+        from . import keys
+        try:
+            t = keys.key_table(table)
+        except ValueError as e:
+            raise NfcError('set_sector_keys: %s' % e)
+        self._chk(self.L.nfc_set_fsm_sector_keys(self.h, C.byref(t)), 'nfc_set_fsm_sector_keys')
+
+    def sector_keys(self):
+        """The machine's key table as the dict (key_type, sector) -> six key bytes of its present slots (nfc_get_fsm_sector_keys)."""
+        from . import keys
+        t = _lib.FsmKeyTable()
+        self._chk(self.L.nfc_get_fsm_sector_keys(self.h, C.byref(t)), 'nfc_get_fsm_sector_keys')
+        return keys.table_dict(t)
+
+    def fsm_state(self):
+        """The context's protocol machine as a plain nfc_fsm_state (an _lib.FsmState): what fsm.set_state takes."""
+        st = _lib.FsmState()
+        self._chk(self.L.nfc_get_fsm_state(self.h, C.byref(st)), 'nfc_get_fsm_state')
+        return st
+
+    def set_fsm_state(self, st):
+        """The context's machine continues from `st` (fsm.get_state(), another context's fsm_state())."""
+        self._chk(self.L.nfc_set_fsm_state(self.h, C.byref(st)), 'nfc_set_fsm_state')
+
+    def commands(self, copy=True):
+        """The commands of the last batch, tracked on the GPU (track_commands), in ONE copy (nfc_read_commands) -> NfcCommands.
+        copy=False: views of the context's pinned memory, valid until the next batch completes, commands(), reset, set_fsm_state or
+        close of this context."""
+        c = _lib.CtxCommands()
+        self._chk(self.L.nfc_read_commands(self.h, C.byref(c)), 'nfc_read_commands')
+        return NfcCommands(c, copy)
+
     def val(self):
         return self._read(self.L.nfc_read_val, self.counts().n_samples, np.int8, 0)
 
@@ -1010,6 +1058,55 @@ class NfcMultiCommands(object):
         """Over ALL commands: true where the command's definition carries a CRC_A.  A command is only found when its CRC matches -- inside
         a session: the CRC of the PLAINTEXT -- so no byte is touched."""
         return (self.cmd['cmd'] >= 0) & (self.cmd['n_crc'] == 2)
+
+
+class NfcCommands(object):
+    """What nfc_read_commands brings: one batch's commands of a single context, found by the protocol machine on the GPU.
+    table: fsm.FRAME_DTYPE records, both directions merged by idx; data / enc: the plaintext bytes and, inside a CRYPTO1 session, the
+    on-air entries (byte | 0x100 where the parity bit equals the data parity), indexed by a record's byte_off; every frame owns a slot
+    of its raw n_bytes entries in both.  flags: NFC_FSM_LOST / NFC_FSM_UID_OVERFLOW of the machine behind the batch.  The counters
+    (n_segments, n_rerun_segments, n_rerun_frames, n_keydep_segments) say how the batch was spread over lanes.
+    ``fsm.dispatch(*c.commands())`` prints the reference's trace."""
+
+    def __init__(self, c, copy=True):
+        from .fsm import FRAME_DTYPE
+        n, nb = int(c.n_commands), int(c.n_bytes)
+        self.n_commands, self.n_bytes, self.flags = n, nb, int(c.flags)
+        self.n_launches, self.bytes_copied = int(c.n_launches), int(c.bytes_copied)
+        self.ms_kernels, self.ms_frames, self.ms_merge = float(c.ms_kernels), float(c.ms_frames), float(c.ms_merge)
+        self.ms_walk, self.ms_resolve = float(c.ms_walk), float(c.ms_resolve)
+        self.counters = {k: int(getattr(c.counters, k)) for k, _ in _lib.CtxCommandCounters._fields_}
+        for k, v in self.counters.items():
+            setattr(self, k, v)
+
+        def arr(ptr, count, dtype):
+            dtype = np.dtype(dtype)
+            if not ptr or not count:
+                return np.zeros(0, dtype)
+            a = np.frombuffer((C.c_char * (int(count) * dtype.itemsize)).from_address(ptr), dtype)
+            return a.copy() if copy else a
+
+        self.table = arr(c.cmd, n, FRAME_DTYPE)
+        self._src = arr(c.src, n, '<u4')
+        self.data = arr(c.data, nb, np.uint8)
+        self.enc = arr(c.enc, nb, '<u2')
+
+    def commands(self):
+        """(table, data, enc): what fsm.dispatch takes."""
+        return self.table, self.data, self.enc
+
+    def src(self):
+        """Per command: (type, index among the batch's raw frames of that type)."""
+        return (self._src >> 31).astype(np.int64), (self._src & 0x7FFFFFFF).astype(np.int64)
+
+    def cmd_mask(self, index):
+        """True where the command is `index` (an index of the command table, or NFC_CMD_*)."""
+        return self.table['cmd'] == int(index)
+
+    def plain_crc_ok_mask(self):
+        """True where the command's definition carries a CRC_A: a command is only found when its CRC matches -- inside a session the
+        CRC of the PLAINTEXT -- so no byte is touched."""
+        return (self.table['cmd'] >= 0) & (self.table['n_crc'] == 2)
 
 
 def host_frames(table, bits, ptype):

@@ -282,6 +282,20 @@ struct nfc_ctx {
     uint64_t fr_frames[2] = {0, 0}, fr_bytes[2] = {0, 0};
     Event fr_ev[2];   // around the two launches (nfc_set_timing >= 1)
     float fr_ms = 0.f;
+    bool fr_enqueued = false, fr_timed = false;   // the two launches of this batch are on the stream; the totals are not read yet
+    frames::CtxArgs fr_args;                      // ... with these arguments
+    // tracked commands (ctx_commands.hip.h; nfc_track_commands ...): nothing of it exists until the machine is first touched
+    struct Commands {
+        bool on = false;
+        bool batch = false;        // tracking was on when the last batch completed
+        bool launched = false;     // ... and it had closes: the six launches are on the stream
+        bool timed = false, read = false;
+        DevBuf d_state, d_keys, d_out, d_scratch;
+        PinBuf h_out;
+        size_t at_cmd = 0, at_src = 0, at_data = 0, at_enc = 0, out_bytes = 0;
+        uint32_t cap_cmds = 0, cap_bytes = 0;
+        Event ev[5];               // before the frames' scan, behind the assembly, the segment numbering, the walk, the resolve
+    } cc;
 };
 
 namespace {

@@ -421,7 +421,7 @@ int process_batch(nfc_ctx *c, const void *d_in, size_t n64) {
     if (c->sub_count && !c->in_wait) return fail(c, NFC_ERR_STATE, "batches submitted with nfc_submit_device are in flight: nfc_wait for them first");
     c->low_valid = false;
     c->have_outputs = false;
-    c->pk_ready[0] = c->pk_ready[1] = c->frames_ready = false;
+    c->pk_ready[0] = c->pk_ready[1] = c->frames_ready = c->fr_enqueued = false;
     c->n_edges = 0;
     for (int t = 0; t < 2; t++) c->n_sym[t] = c->n_close[t] = c->n_bits[t] = 0;
     memset(&c->stats, 0, sizeof c->stats);
@@ -435,7 +435,7 @@ int process_batch(nfc_ctx *c, const void *d_in, size_t n64) {
     c->stats.bytes_in = (uint64_t)n * c->in_bytes_per_sample;
     if (n == 0) {
         c->have_outputs = true;
-        return NFC_OK;
+        return track_batch(c);
     }
     if (((uintptr_t)d_in & 15u) != 0) return fail(c, NFC_ERR_ARG, "device input must be 16-byte aligned");
     c->batch_seq++;
@@ -470,7 +470,7 @@ int process_batch(nfc_ctx *c, const void *d_in, size_t n64) {
         note_carried(c);
         c->nseen += n;
         c->have_outputs = true;
-        return NFC_OK;
+        return track_batch(c);
     }
 
     if (c->timing >= 2) HIPCHK(c, hipEventRecord(c->ev[1], c->st));
@@ -591,7 +591,7 @@ int process_batch(nfc_ctx *c, const void *d_in, size_t n64) {
     // (the end-of-batch LOW bookkeeping on the device is what a batch submitted ahead may start from: only when the whole
     // batch went through one parallel attempt, whose last certification workgroup or k_finalize_state wrote it)
     c->low_valid = skip == 0 && c->stats.used_sequential == 0 && c->h_carry.stable;
-    return NFC_OK;
+    return track_batch(c);
 }
 
 

@@ -85,7 +85,7 @@ int enqueue_stages_behind(nfc_ctx *c, nfc_ctx::Submitted &b) {
     HIPCHK(c, hipStreamWaitEvent(c->st, c->ev_a[b.slot], 0));
     if (b.planes >= 0) take_planes(c, b);
     c->have_outputs = false;
-    c->pk_ready[0] = c->pk_ready[1] = c->frames_ready = false;
+    c->pk_ready[0] = c->pk_ready[1] = c->frames_ready = c->fr_enqueued = false;
     c->n_edges = 0;
     for (int t = 0; t < 2; t++) c->n_sym[t] = c->n_close[t] = c->n_bits[t] = 0;
     memset(&c->stats, 0, sizeof c->stats);
@@ -303,7 +303,7 @@ int wait_batch(nfc_ctx *c) {
         c->low_valid = true;
         if (c->fine_adapt && c->fine_left > 0) c->fine_left--;   // (a batch without a re-run: run_threshold's bookkeeping, for this path)
         pop();
-        return NFC_OK;
+        return track_batch(c);
     }
     // The optimistic result does not stand: everything in flight is drained, the batch goes through the synchronous path
     // from the state before it (the host mirrors were last adopted there; its window buffer was not written since), and

@@ -4,6 +4,7 @@
 // failure is kept in the CONTEXT until the batch that made it reports it (host_context.h: batch_ok -> NFC_ERR_DEVICE).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stdint.h>
 
 namespace nfc {
 
@@ -30,7 +31,13 @@ struct LaunchScope {
     LaunchScope(const LaunchScope &) = delete;
     LaunchScope &operator=(const LaunchScope &) = delete;
 };
+// launches the calling thread has made through NFC_LAUNCH / NFC_LAUNCH_EXT (the test build hands it out: nfc_debug_launch_count)
+inline uint64_t &launch_count() {
+    static thread_local uint64_t n = 0;
+    return n;
+}
 inline void note_launch(const char *file, int line) {
+    launch_count()++;
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess && launch_error().err == hipSuccess) launch_error() = LaunchError{e, file, line};
 }

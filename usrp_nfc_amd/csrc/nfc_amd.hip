@@ -54,6 +54,7 @@
 #include "tx.hip.h"
 #include "record.hip.h"   // (the recording kernel: nfc_record.hip)
 #include "frames.hip.h"   // (the frame assembly kernels: nfc_frames.hip)
+#include "ctx_commands.hip.h"   // (commands for one long stream, a lane per transaction: nfc_ctx_commands.hip)
 
 using namespace nfc;
 
@@ -61,6 +62,7 @@ using namespace nfc;
 #include "rerun_plan.h"
 #include "dev_buf.h"
 #include "host_context.h"
+#include "host_commands.h"
 #include "host_threshold.h"
 #include "host_stages.h"
 #include "host_submit.h"
@@ -489,7 +491,7 @@ int nfc_push_edges(nfc_ctx *c, const nfc_edge *host_edges, size_t n64) {
     if (hipSetDevice(c->P.device) != hipSuccess) return fail(c, NFC_ERR_DEVICE, "hipSetDevice failed");
     const uint32_t n = (uint32_t)n64;
     c->have_outputs = false;
-    c->pk_ready[0] = c->pk_ready[1] = c->frames_ready = false;
+    c->pk_ready[0] = c->pk_ready[1] = c->frames_ready = c->fr_enqueued = false;
     c->n_edges = 0;
     for (int t = 0; t < 2; t++) c->n_sym[t] = c->n_close[t] = c->n_bits[t] = 0;
     memset(&c->stats, 0, sizeof c->stats);
@@ -548,7 +550,7 @@ int nfc_push_edges(nfc_ctx *c, const nfc_edge *host_edges, size_t n64) {
     }
     c->pend_cur = 1 - c->pend_cur;
     c->have_outputs = true;
-    return NFC_OK;
+    return track_batch(c);
 }
 
 int nfc_sync(nfc_ctx *c) {
@@ -773,31 +775,9 @@ int ensure_frames(nfc_ctx *c) {
     if (c->frames_ready) return NFC_OK;
     if (hipSetDevice(c->P.device) != hipSuccess) return fail(c, NFC_ERR_DEVICE, "hipSetDevice failed");
     c->fr_frames[0] = c->fr_frames[1] = c->fr_bytes[0] = c->fr_bytes[1] = 0;
-    c->fr_ms = 0.f;
-    if (c->n_close[0] || c->n_close[1]) {   // (a batch that closed no packet launches nothing)
-        frames::CtxArgs A;
-        memset(&A, 0, sizeof A);
-        HIPCHK(c, c->d_fr_tot.ensure(64));
-        for (int t = 0; t < 2; t++) {
-            // a frame has at most (n_bits + 1) / 9 bytes: the type's bits and one more per close bound the section
-            const size_t byte_cap = ((size_t)c->n_bits[t] + c->n_close[t]) / 9 + 16;
-            HIPCHK(c, c->d_fr_rec[t].ensure(((size_t)c->n_close[t] + 1) * sizeof(nfc_raw_frame)));
-            HIPCHK(c, c->d_fr_bytes[t].ensure(byte_cap));
-            HIPCHK(c, c->d_fr_par[t].ensure(byte_cap));
-            A.close_end[t] = c->d_close_end[t].as<uint32_t>();
-            A.close_idx[t] = c->d_close_idx[t].as<uint64_t>();
-            A.n_close[t] = c->n_close[t];
-            A.bits[t] = c->d_bits[t].p;
-            A.records[t] = c->d_fr_rec[t].as<nfc_raw_frame>();
-            A.bytes[t] = c->d_fr_bytes[t].as<uint8_t>();
-            A.par[t] = c->d_fr_par[t].as<uint8_t>();
-            A.byte_cap[t] = (uint32_t)std::min<size_t>(byte_cap, 0xFFFFFFFFu);
-        }
-        A.totals = c->d_fr_tot.as<uint64_t>();
-        const bool timed = c->timing >= 1;
-        if (timed)
-            for (auto &e : c->fr_ev) HIPCHK(c, e.create());
-        frames::launch_ctx(A, c->bits_packed, c->st, timed ? (hipEvent_t)c->fr_ev[0] : nullptr, timed ? (hipEvent_t)c->fr_ev[1] : nullptr);
+    if (int rc = enqueue_frames(c)) return rc;
+    if (c->fr_enqueued) {
+        const frames::CtxArgs &A = c->fr_args;
         if (int rc = pk_stage(c, 64)) return rc;
         HIPCHK(c, hipMemcpyAsync(c->h_pk_stage.p, c->d_fr_tot.p, 32, hipMemcpyDeviceToHost, c->st));
         HIPCHK(c, hipStreamSynchronize(c->st));
@@ -810,7 +790,7 @@ int ensure_frames(nfc_ctx *c) {
                 return fail(c, NFC_ERR_INTERNAL, "frame scan of type %d: %llu frames, %llu bytes from %u closes and %u bits", t,
                             (unsigned long long)c->fr_frames[t], (unsigned long long)c->fr_bytes[t], c->n_close[t], c->n_bits[t]);
         }
-        if (timed) HIPCHK(c, hipEventElapsedTime(&c->fr_ms, c->fr_ev[0], c->fr_ev[1]));
+        if (c->fr_timed) HIPCHK(c, hipEventElapsedTime(&c->fr_ms, c->fr_ev[0], c->fr_ev[1]));
     }
     c->frames_ready = true;   // (only now: a launch or a wait that failed leaves nothing behind, and the next read tries again)
     return NFC_OK;
@@ -872,6 +852,153 @@ int nfc_read_frame_bytes(nfc_ctx *c, int type, size_t first, uint8_t *bytes_out,
     return NFC_OK;
 }
 
+// ---- tracked commands: the protocol machine on the device for this one stream (ctx_commands.hip.h, host_commands.h) ----
+int nfc_track_commands(nfc_ctx *c, int on) {
+    LaunchScope launch_scope_(c ? &c->launch_err : nullptr);
+    if (!c) return NFC_ERR_ARG;
+    NOSUB(c);
+    if (on) {
+        if (hipSetDevice(c->P.device) != hipSuccess) return fail(c, NFC_ERR_DEVICE, "hipSetDevice failed");
+        if (int rc = cc_ensure_state(c)) return rc;
+    }
+    c->cc.on = on != 0;
+    return NFC_OK;
+}
+
+int nfc_read_commands(nfc_ctx *c, nfc_ctx_commands *out) {
+    LaunchScope launch_scope_(c ? &c->launch_err : nullptr);
+    if (!c) return NFC_ERR_ARG;
+    if (!out) return fail(c, NFC_ERR_ARG, "out: null");
+    if (!c->have_outputs) return fail(c, NFC_ERR_STATE, "no completed batch");
+    nfc_ctx::Commands &cc = c->cc;
+    if (!cc.batch) return fail(c, NFC_ERR_STATE, "tracking was off when the last batch completed: nfc_track_commands before the batch");
+    if (hipSetDevice(c->P.device) != hipSuccess) return fail(c, NFC_ERR_DEVICE, "hipSetDevice failed");
+    memset(out, 0, sizeof *out);
+    if (!cc.launched) {   // a batch without frames: the machine as it stands
+        fsmd::Machine M;
+        if (int rc = cc_read_machine(c, M)) return rc;
+        out->flags = M.flags;
+        return NFC_OK;
+    }
+    HIPCHK(c, cc.h_out.ensure(cc.out_bytes));
+    HIPCHK(c, hipMemcpyAsync(cc.h_out.p, cc.d_out.p, cc.out_bytes, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    BATCHCHK(c, false);
+    const uint8_t *h = cc.h_out.as<uint8_t>();
+    const uint32_t *hdr = (const uint32_t *)h;
+    if (hdr[ctxcmd::H_N_CMDS] > cc.cap_cmds || hdr[ctxcmd::H_N_BYTES] > cc.cap_bytes || hdr[ctxcmd::H_N_SEGMENTS] > c->fr_args.n_close[1] + 1u)
+        return fail(c, NFC_ERR_INTERNAL, "tracked commands: %u commands, %u bytes, %u segments from %u closes", hdr[ctxcmd::H_N_CMDS],
+                    hdr[ctxcmd::H_N_BYTES], hdr[ctxcmd::H_N_SEGMENTS], cc.cap_cmds);
+    out->n_commands = hdr[ctxcmd::H_N_CMDS];
+    out->n_bytes = hdr[ctxcmd::H_N_BYTES];
+    out->flags = hdr[ctxcmd::H_FLAGS];
+    out->n_launches = 6;
+    out->counters.n_segments = hdr[ctxcmd::H_N_SEGMENTS];
+    out->counters.n_rerun_segments = hdr[ctxcmd::H_N_RERUN_SEGMENTS];
+    out->counters.n_rerun_frames = hdr[ctxcmd::H_N_RERUN_FRAMES];
+    out->counters.n_keydep_segments = hdr[ctxcmd::H_N_KEYDEP];
+    out->bytes_copied = cc.out_bytes;
+    if (out->n_commands) {
+        out->cmd = (const nfc_frame *)(h + cc.at_cmd);
+        out->src = (const uint32_t *)(h + cc.at_src);
+        out->data = h + cc.at_data;
+        out->enc = (const uint16_t *)(h + cc.at_enc);
+    }
+    if (cc.timed) {
+        out->ms_kernels = elapsed_ms(cc.ev[0], cc.ev[4]);
+        out->ms_frames = elapsed_ms(cc.ev[0], cc.ev[1]);
+        out->ms_merge = elapsed_ms(cc.ev[1], cc.ev[2]);
+        out->ms_walk = elapsed_ms(cc.ev[2], cc.ev[3]);
+        out->ms_resolve = elapsed_ms(cc.ev[3], cc.ev[4]);
+    }
+    cc.read = true;
+    return NFC_OK;
+}
+
+int nfc_set_fsm_keys(nfc_ctx *c, const uint8_t key_a[6], const uint8_t key_b[6]) {
+    LaunchScope launch_scope_(c ? &c->launch_err : nullptr);
+    if (!c) return NFC_ERR_ARG;
+    if (!key_a) return fail(c, NFC_ERR_ARG, "key_a: null");
+    if (!key_b) return fail(c, NFC_ERR_ARG, "key_b: null");
+    NOSUB(c);
+    if (hipSetDevice(c->P.device) != hipSuccess) return fail(c, NFC_ERR_DEVICE, "hipSetDevice failed");
+    if (int rc = cc_ensure_state(c)) return rc;
+    fsmd::Machine M;
+    if (int rc = cc_read_machine(c, M)) return rc;
+    M.key_a = fsmd::key_of(key_a);
+    M.key_b = fsmd::key_of(key_b);
+    return cc_write_machine(c, M);
+}
+
+int nfc_set_fsm_sector_keys(nfc_ctx *c, const nfc_fsm_key_table *table) {
+    LaunchScope launch_scope_(c ? &c->launch_err : nullptr);
+    if (!c) return NFC_ERR_ARG;
+    if (table)
+        if (const char *why = skeys::table_fault(*table)) return fail(c, NFC_ERR_ARG, "table: %s", why);
+    NOSUB(c);
+    if (!table && !c->cc.d_keys.p) return NFC_OK;   // (an empty table is what a context without one has)
+    if (hipSetDevice(c->P.device) != hipSuccess) return fail(c, NFC_ERR_DEVICE, "hipSetDevice failed");
+    if (c->cc.d_keys.ensure(skeys::WORDS * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, NFC_ERR_NOMEM, "no device memory for the sector key table");
+    }
+    uint32_t w[skeys::WORDS];
+    memset(w, 0, sizeof w);
+    if (table)
+        for (uint32_t slot = 0; slot < skeys::SLOTS; slot++) {
+            const uint32_t type = slot / skeys::SECTORS, sec = slot % skeys::SECTORS;
+            if (!table->present[type][sec]) continue;
+            const uint64_t key = skeys::key48(table->key[type][sec]);
+            w[2 * slot] = skeys::word_lo(key);
+            w[2 * slot + 1] = skeys::word_hi(key, true);
+        }
+    return cc_put_words(c, c->cc.d_keys, w, skeys::WORDS);
+}
+
+int nfc_get_fsm_sector_keys(nfc_ctx *c, nfc_fsm_key_table *table) {
+    LaunchScope launch_scope_(c ? &c->launch_err : nullptr);
+    if (!c) return NFC_ERR_ARG;
+    if (!table) return fail(c, NFC_ERR_ARG, "table: null");
+    memset(table, 0, sizeof *table);
+    if (!c->cc.d_keys.p) return NFC_OK;
+    if (hipSetDevice(c->P.device) != hipSuccess) return fail(c, NFC_ERR_DEVICE, "hipSetDevice failed");
+    uint32_t w[skeys::WORDS];
+    if (int rc = cc_get_words(c, c->cc.d_keys, w, skeys::WORDS)) return rc;
+    for (uint32_t slot = 0; slot < skeys::SLOTS; slot++) {
+        if (!(w[2 * slot + 1] & skeys::PRESENT)) continue;
+        const uint32_t type = slot / skeys::SECTORS, sec = slot % skeys::SECTORS;
+        const uint64_t key = (uint64_t)w[2 * slot] | (uint64_t)(w[2 * slot + 1] & 0xFFFFu) << 32;
+        table->present[type][sec] = 1;
+        for (int i = 0; i < 6; i++) table->key[type][sec][i] = (uint8_t)(key >> (8 * i));
+    }
+    return NFC_OK;
+}
+
+int nfc_get_fsm_state(nfc_ctx *c, nfc_fsm_state *st) {
+    LaunchScope launch_scope_(c ? &c->launch_err : nullptr);
+    if (!c) return NFC_ERR_ARG;
+    if (!st) return fail(c, NFC_ERR_ARG, "st: null");
+    if (c->cc.d_state.p && hipSetDevice(c->P.device) != hipSuccess) return fail(c, NFC_ERR_DEVICE, "hipSetDevice failed");
+    fsmd::Machine M;
+    if (int rc = cc_read_machine(c, M)) return rc;
+    memset(st, 0, sizeof *st);
+    fsmd::machine_to_state(M, *st);
+    return NFC_OK;
+}
+
+int nfc_set_fsm_state(nfc_ctx *c, const nfc_fsm_state *st) {
+    LaunchScope launch_scope_(c ? &c->launch_err : nullptr);
+    if (!c) return NFC_ERR_ARG;
+    if (!st) return fail(c, NFC_ERR_ARG, "st: null");
+    if (const char *why = fsmd::state_fault(*st)) return fail(c, NFC_ERR_ARG, "st: %s", why);
+    NOSUB(c);
+    if (hipSetDevice(c->P.device) != hipSuccess) return fail(c, NFC_ERR_DEVICE, "hipSetDevice failed");
+    if (int rc = cc_ensure_state(c)) return rc;
+    fsmd::Machine M;
+    fsmd::machine_from_state(M, *st);
+    return cc_write_machine(c, M);
+}
+
 int nfc_read_val(nfc_ctx *c, size_t first, int8_t *out, size_t cap, size_t *n_out) {
     LaunchScope launch_scope_(c ? &c->launch_err : nullptr);
     if (!c) return NFC_ERR_ARG;
@@ -926,6 +1053,18 @@ int nfc_reset(nfc_ctx *c) {
     init_carried(c);
     c->have_outputs = false;
     push_state(c, 0, true);   // carried values and a zeroed window in one launch
+    // the protocol machine, where the context has one: nfc_fsm_state_init's state, an empty table
+    c->cc.batch = c->cc.launched = false;
+    if (c->cc.d_state.p) {
+        fsmd::Machine M;
+        fsmd::machine_init(M);
+        if (int rc = cc_write_machine(c, M)) return rc;
+    }
+    if (c->cc.d_keys.p) {
+        uint32_t w[skeys::WORDS];
+        memset(w, 0, sizeof w);
+        if (int rc = cc_put_words(c, c->cc.d_keys, w, skeys::WORDS)) return rc;
+    }
     return NFC_OK;
 }
 
@@ -1402,6 +1541,8 @@ extern "C" int nfc_debug_gen_prof(unsigned long long *out, int reset) {
 // the frame assembly's two launches of the last batch by HIP events (nfc_set_timing >= 1 before the frames were first read; else 0):
 // what tests/frames_bench.py sets beside the batch's own time
 extern "C" float nfc_debug_frames_ms(const nfc_ctx *c) { return c && c->frames_ready ? c->fr_ms : -1.f; }
+// kernel launches the calling thread has made through this library so far (launch_check.h): what a call adds is what it launched
+extern "C" uint64_t nfc_debug_launch_count(void) { return nfc::launch_count(); }
 // the HIP resources the library's owning handles (dev_buf.h) hold right now, every context and call of the process together: device blocks,
 // pinned blocks, events, streams -- equal before and after a lifecycle when nothing leaked
 extern "C" void nfc_debug_live_resources(uint64_t out[4]) {

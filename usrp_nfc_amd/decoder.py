@@ -322,8 +322,12 @@ else:
     class decoder(object):
         def __init__(self, src="uhd", dst=None, repeat=False, reader=True, tag=True, samp_rate=2e6, emulator=None,
                      wav_scale=0.0, fsm=None, batch=1 << 22, device=0, lo_val=0.1, av_window=2000, max_len=50, keep=None,
-                     iq16_scale=0.0, iq8_scale=0.0, record_gain=32767.0):
-            """wav_scale: int16 PCM -> float.  0 (default): GNU Radio's wavfile_source normalisation, sample / 32767 (what the
+                     iq16_scale=0.0, iq8_scale=0.0, record_gain=32767.0, commands=False, keys=None):
+            """commands=True: the context tracks the commands on the GPU (api.NfcContext.track_commands: the protocol machine, CRYPTO1
+            included, a lane per transaction); after every batch they are read once and ``(table, data, enc)`` -- what fsm.dispatch
+            prints -- is appended to the background's ``commands``, as decode_many(..., commands=True) does per file.  keys:
+            ``(key_a, key_b)`` or ``(key_a, key_b, table)`` for the machine (default: FF..FF, no table).
+            wav_scale: int16 PCM -> float.  0 (default): GNU Radio's wavfile_source normalisation, sample / 32767 (what the
             reference's WAV branch feeds the path, decoder.py:25; third party, unpinned: nfc_amd.h); > 0: sample * wav_scale.
             lo_val / av_window / max_len: transition_sink's keyword arguments (transition_sink.py:12), e.g. scaled with the rate.
             iq16_scale: complex int16 -> float, I and Q each, with wav_scale's meaning (0: / 32767; UHD's own sc16 -> fc32 scaling
@@ -342,6 +346,19 @@ else:
             self._trans = transition_sink(samp_rate, self._back.append, lo_val=lo_val, hi_val=hi_val, av_window=av_window, max_len=max_len,
                                           batch=batch, device=device, input_kind=kind, i16_scale=scale if kind in _SCALED_KINDS else 0.0)
             self._batch = int(batch)
+            if keys is not None and not commands:
+                raise ValueError('decoder: keys are for commands=True')
+            self._commands = bool(commands)
+            if self._commands:
+                ctx = self._trans._ctx
+                if keys is not None:
+                    if len(keys) not in (2, 3) or not _is_key(keys[0]) or not _is_key(keys[1]):
+                        raise ValueError('decoder: keys is a (key_a, key_b) pair or a (key_a, key_b, table) triple')
+                    ctx.set_keys(keys[0], keys[1])
+                    if len(keys) == 3:
+                        ctx.set_sector_keys(keys[2])
+                ctx.track_commands(True)
+                self._back.commands = []
             self._dst = dst if (dst is not None and kind in _RECORDED_KINDS) else None
             self._rec = (kind, scale if kind in _SCALED_KINDS else 0.0, float(record_gain), int(device), samp_rate)
 
@@ -352,7 +369,12 @@ else:
             step = self._batch * self._per
             for i in range(0, len(self._data), step):
                 self._trans.push_now(self._data[i:i + step])
+                self._keep_commands()
             return self._back
+
+        def _keep_commands(self):
+            if self._commands:
+                self._back.commands.append(self._trans._ctx.commands().commands())
 
         def _run_recording(self):
             """run() with ``dst``: each batch is uploaded once, decoded from the device buffer (push_device) and converted to PCM by
@@ -374,6 +396,7 @@ else:
                         continue
                     src.upload(piece[:n * self._per])
                     self._trans.push_device_now(src, n)
+                    self._keep_commands()
                     api.record_pcm16_device(src, n, pcm, kind, scale, gain, api.NFC_REC_ENVELOPE, device)
                     wav.write_pcm(pcm.download(2 * n).view(numpy.int16))
             finally:

@@ -103,6 +103,33 @@ def host_commands(state, frames, data=None, par=None, sector_keys=None):
     return out, buf[:used.value], enc[:used.value]
 
 
+def host_commands_segmented(state, frames, data=None, par=None, sector_keys=None, segment_order=None):
+    """host_commands computed the way a tracked NfcContext computes it on the GPU (nfc_host_commands_segmented, csrc/ctx_commands.hip.h):
+    the frames cut into segments at every plain REQA / WUPA, every segment walked speculatively -- in the order `segment_order` names,
+    entries at or past the segment count skipped, None: ascending -- and a resolve that walks again what was guessed wrong.
+    -> (table, data, enc, counters): host_commands' outputs, bit for bit, and a dict of n_segments, n_rerun_segments, n_rerun_frames,
+    n_keydep_segments."""
+    if data is None:
+        frames, data, par = frames.table, frames.bytes, frames.par
+    t = np.ascontiguousarray(frames, _lib.RAW_FRAME_DTYPE)
+    b = [np.ascontiguousarray(a, np.uint8) for a in data]
+    p = [np.ascontiguousarray(a, np.uint8) for a in par]
+    cap = int(t['n_bytes'].sum()) + 1
+    out, buf, enc = np.zeros(len(t), FRAME_DTYPE), np.zeros(cap, np.uint8), np.zeros(cap, np.uint16)
+    used = C.c_size_t(0)
+    ptr = lambda a: a.ctypes.data if a.size else None
+    keyed = None if sector_keys is None else C.byref(_keys.key_table(sector_keys))
+    order = None if segment_order is None else np.ascontiguousarray(segment_order, np.uint32)
+    cn = _lib.CtxCommandCounters()
+    rc = _lib.load().nfc_host_commands_segmented(C.byref(state), keyed, ptr(t), len(t), ptr(b[0]), ptr(p[0]), ptr(b[1]), ptr(p[1]), out.ctypes.data,
+                                                 buf.ctypes.data, enc.ctypes.data, cap, C.byref(used),
+                                                 None if order is None else (order if order.size else np.zeros(1, np.uint32)).ctypes.data,
+                                                 0 if order is None else len(order), C.byref(cn))
+    if rc != 0:
+        raise ValueError('nfc_host_commands_segmented status %d' % rc)
+    return out, buf[:used.value], enc[:used.value], {k: int(getattr(cn, k)) for k, _ in _lib.CtxCommandCounters._fields_}
+
+
 class fsm(object):
     def __init__(self, callback=None, out=None):
         self.L = _lib.load()
