@@ -61,6 +61,15 @@ def _cut(streams, cuts, p):
     return [s[2 * e[p]:2 * e[p + 1]] if p + 1 < len(e) else s[:0] for s, e in zip(streams, edges)], max(len(e) for e in edges) - 1
 
 
+def _piece_cuts(idx0, idx1, names, delay=172):
+    """tests/test_emulate.py's cuts of the three streams, from the two captures' frame idx and stream 0's command names: one inside an
+    answer's interval, one between an idx and its S, and an empty push"""
+    auth, nrar = names.index(14), names.index(17)
+    cuts0 = sorted([int(idx0[auth]) + 60, int(idx0[nrar]) + 60, int(idx0[1]) + delay + 100, int(idx0[3]) + 20])
+    cuts0.insert(2, cuts0[1])   # the empty push
+    return [cuts0, [int(idx1[2]) + 60, int(idx1[4]) + delay + 33], []]
+
+
 # ---- 7. device equals twin, whole and in pieces ----
 def test_device_equals_the_twin_whole_and_in_pieces():
     from usrp_nfc_amd import synth
@@ -87,12 +96,7 @@ def test_device_equals_the_twin_whole_and_in_pieces():
             assert whole[k].real.max() == 1.0 and whole[k].real.min() == 0.0 and not whole[k].imag.any()
         # in pieces: tests/test_emulate.py's cuts, one inside an answer's interval, one between an idx and its S, and an empty push
         idx0, idx1 = (cm.raw.frames_of(k).table['idx'].astype(np.int64) for k in (0, 1))
-        names = cm.commands_of(0)[0]['cmd'].tolist()
-        auth, nrar = names.index(14), names.index(17)
-        delay = 172
-        cuts0 = sorted([int(idx0[auth]) + 60, int(idx0[nrar]) + 60, int(idx0[1]) + delay + 100, int(idx0[3]) + 20])
-        cuts0.insert(2, cuts0[1])   # the empty push
-        cuts = [cuts0, [int(idx1[2]) + 60, int(idx1[4]) + delay + 33], []]
+        cuts = _piece_cuts(idx0, idx1, cm.commands_of(0)[0]['cmd'].tolist())
         m.reset()
         assert not _pend_bytes(m, 3).strip(b'\0')
         parts, pend, n_push = [[] for _ in streams], None, _cut(streams, cuts, 0)[1]

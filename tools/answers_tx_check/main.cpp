@@ -1,7 +1,8 @@
 // answers_tx_check -- the host twin of the answers' transmission (include/nfc_amd.h: nfc_host_answers_tx; csrc/answers_tx.hip.h, DESIGN.md
 // 8m) over answers made here: ragged streams with a cardless and an empty one among them, answers of every n_bits in both roles, pushes
 // cut at every position class (inside an answer, at its S, at S + L, at S + L - 1, between idx and S, a zero-length push, a push of one
-// sample, one answer across three pushes) -- rendered into heap blocks of EXACTLY the size the sizing call reports, so that a sample
+// sample, one answer across three pushes), and pending entries given by hand over pushes of a few hundred samples (carried through many
+// pushes, waiting in front of one, ended before one, cut away by a command) -- rendered into heap blocks of EXACTLY the size the sizing call reports, so that a sample
 // written past the layout's end, or a bit read past an answer's bytes, is a sanitizer finding.  A stand-alone host program: the way to
 // run the twin's host code under a sanitizer.
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined tools/answers_tx_check/main.cpp \
@@ -159,6 +160,74 @@ int main() {
                 }
                 renders++;
             }
+    // pending entries given by hand (what nfc_multi_set_tx_state gives the device), over pushes of a few hundred samples (tests/
+    // test_answers_tx_trips.py, scenarios 2 and 5): stream 0's entry of the longest shape is carried THROUGH pushes that bring no answer,
+    // the same 64 bytes behind every one; stream 1's starts far behind the first pushes and waits untouched over idle samples; stream 2
+    // is given one that ended before its push began, which is dropped; stream 3's starts behind the moment its only command closes, and
+    // is cut away entirely by that command's answer
+    int carried = 0, waited = 0;
+    {
+        std::vector<Stream> Q(4);
+        Q[0].role = NFC_EMU_TAG, Q[1].role = NFC_EMU_READER, Q[2].role = NFC_EMU_TAG, Q[3].role = NFC_EMU_READER;
+        const uint64_t cmd = 2500, delay = 173, future = 5000, away = 2600;
+        Q[3].answer(cmd, 18, seed);
+        const nfc_answers_tx_config c = config(2e6, 1, 1, delay, 0, 1);
+        auto entry = [&](uint64_t start, uint32_t n_bits, uint32_t role) {
+            nfc_tx_pending p;
+            memset(&p, 0, sizeof p);
+            p.start = start, p.n_bits = (uint16_t)n_bits, p.role = (uint8_t)role;
+            for (uint32_t i = 0; i < (n_bits <= 8 ? 1 : n_bits / 9); i++) p.air[i] = (uint8_t)(lcg(seed) >> 24), p.par[i] = (uint8_t)(lcg(seed) >> 31);
+            return p;
+        };
+        const size_t K = Q.size();
+        std::vector<nfc_tx_pending> pend(K);
+        memset(pend.data(), 0, K * sizeof(nfc_tx_pending));
+        pend[0] = entry(37, 162, NFC_EMU_READER), pend[1] = entry(future, 45, NFC_EMU_TAG), pend[3] = entry(away, 27, NFC_EMU_READER);
+        const nfc_tx_pending first0 = pend[0], first1 = pend[1], first3 = pend[3];
+        std::vector<std::vector<float>> out(K);
+        std::vector<uint64_t> base(K, 0);
+        std::vector<uint32_t> n(K);
+        bool dropped = false, cut_away = false;
+        for (uint32_t p = 0; base[0] < 9000; p++) {
+            for (size_t k = 0; k < K; k++) n[k] = 301 + 2 * ((37 * (uint32_t)k + 11 * p) % 100);
+            const bool give = !dropped && base[2] > 400;   // an entry wholly in the past: [10, 10 + L) with L below 390 samples (11 pieces of 9.44 us)
+            if (give) pend[2] = entry(10, 9, NFC_EMU_TAG);
+            const size_t before2 = out[2].size(), before1 = out[1].size();
+            CHECK(push(Q, c, base, n, pend, out));
+            if (give) {
+                CHECK(pend[2].n_bits == 0 && pend[2].start == 0);
+                for (size_t i = before2; i < out[2].size(); i++) CHECK(out[2][i] == 0.f);
+                dropped = true;
+            }
+            if (pend[0].n_bits) {
+                CHECK(!memcmp(&pend[0], &first0, sizeof first0));
+                carried++;
+            }
+            if (base[1] + n[1] <= future) {   // the span ends in front of the entry: untouched, every sample the reader's idle level
+                CHECK(!memcmp(&pend[1], &first1, sizeof first1));
+                for (size_t i = before1; i < out[1].size(); i += 2) CHECK(out[1][i] == 1.f && out[1][i + 1] == 0.f);
+                waited++;
+            }
+            if (base[3] + n[3] <= cmd) CHECK(!memcmp(&pend[3], &first3, sizeof first3));
+            else if (!cut_away) {   // the push that holds the command: the entry is gone, the command's own answer is what is pending
+                CHECK(pend[3].start == cmd + delay && pend[3].n_bits == 18);
+                cut_away = true;
+            }
+            for (size_t k = 0; k < K; k++) base[k] += n[k];
+        }
+        CHECK(carried >= 5 && waited >= 5 && dropped && cut_away);
+        for (size_t k = 0; k < K; k++) CHECK(pend[k].n_bits == 0 && pend[k].start == 0 && out[k].size() == 2 * base[k]);
+        // stream 3: idle up to the answer's start (the entry that was cut away owned [2600, 2673) and left no sample there)
+        for (uint64_t t = 0; t < cmd + delay; t++) CHECK(out[3][2 * t] == 1.f);
+        bool low = false;
+        for (uint64_t t = cmd + delay; t < cmd + delay + 100; t++) low = low || out[3][2 * t] == 0.f;
+        CHECK(low);   // (a Miller answer begins with a pause)
+        // stream 1: idle up to the entry's start, then a tag's answer over the reader's idle level
+        for (uint64_t t = 0; t < future; t++) CHECK(out[1][2 * t] == 1.f);
+        low = false;
+        for (uint64_t t = future; t < future + 100; t++) low = low || out[1][2 * t] == 0.f;
+        CHECK(low);
+    }
     // argument errors
     {
         const size_t K = S.size();
@@ -196,6 +265,7 @@ int main() {
         n[3] = (1u << 30) + 1;
         CHECK(bad(c, "span"));
     }
-    printf("answers_tx_check ok: %d whole renderings and their pieces in blocks of the exact size, %zu streams\n", renders, S.size());
+    printf("answers_tx_check ok: %d whole renderings and their pieces in blocks of the exact size, %zu streams; an entry carried through %d pushes, one waiting through %d\n",
+           renders, S.size(), carried, waited);
     return 0;
 }
