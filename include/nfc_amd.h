@@ -54,6 +54,8 @@ extern "C" {
 /* (still 4, only new names: nfc_air_frame, nfc_air_config, nfc_host_air_render, nfc_air_render_device) */
 /* (still 4, only new names: nfc_reader_pair, nfc_reader_key_result, nfc_reader_key_config, NFC_RKEY_VERIFY_INLINE, nfc_find_reader_auths,
  *  nfc_host_recover_reader_keys, nfc_recover_reader_keys_device) */
+/* (still 4, only new names: nfc_image_cmd, nfc_image_info, nfc_card_image, nfc_multi_images, NFC_IMG_*, nfc_card_image_init, nfc_host_card_image,
+ *  nfc_multi_track_images, nfc_multi_fetch_images, nfc_multi_get_image, nfc_multi_set_image) */
 #define NFC_AMD_ABI_VERSION 4
 
 typedef enum {
@@ -1253,6 +1255,82 @@ int nfc_multi_transmit_device(nfc_multi *m, const nfc_answers_tx_config *cfg, vo
                               uint32_t *n_samples, float *kernel_ms /* NULL, or two floats */);
 int nfc_multi_get_tx_state(nfc_multi *m, uint32_t stream, nfc_tx_pending *st);
 int nfc_multi_set_tx_state(nfc_multi *m, uint32_t stream, const nfc_tx_pending *st);
+
+/* ---- the card rebuilt from what was heard: a memory image per stream -----------------------------------------------------------------
+ * What an eavesdropper wants of a capture is the card.  An IMAGE belongs to one stream of a multi-stream context: 1 024 bytes `mem` (an
+ * Ultralight uses the first 64), one source code per byte in `src` (0: never shown), a tag type (-1 until an ATQA is heard), sticky flags
+ * and the count of known bytes.  It is built from the stream's command records in stream order -- nfc_frame and its `data` slot, as
+ * k_multi_commands writes them -- by ONE text for host and device, csrc/image.hip.h:
+ *   ATQA*                     set tag_type; another one than was set: NFC_IMG_TAG_CHANGED
+ *   ANTI1U / ANTI2T / ANTI1G  bytes 0..3 / 4..8 / 0..4 (source ANTICOLL): the bytes an emulated tag sends from its memory
+ *   READT                     only when the command IMMEDIATELY before it is a READR, whose first extra byte is the block / page `val`:
+ *                             tag type 0: pages val .. val + 3, round the end of the 64 bytes (val > 0x0F: nothing).  Otherwise block val:
+ *                             a data block whole; a trailer bytes [6, 10), and [10, 16) only where the access bits in this same answer
+ *                             leave key B readable -- never [0, 6), which a card reads as zeros.  val >= 64: nothing, NFC_IMG_BEYOND
+ *   RANDTB with AT_OK         behind AUTHA / AUTHB, RANDTA, RANDRB with AR_OK (either side of a nested authentication counts): the key
+ *                             the machine held for (key type, sector of the AUTH's block) -- the table's slot where present, else key A /
+ *                             key B, the rule of the key table above -- into [0, 6) (AUTHA) or [10, 16) (AUTHB) of that sector's trailer,
+ *                             source KEY.  Sector >= 16: nothing, NFC_IMG_BEYOND
+ *   WRITE / COMPW1 / COMPW2   nothing, NFC_IMG_SAW_WRITE: the image records what the card SAID and what the authentications proved;
+ *                             applying writes is not built
+ *   cmd < 0                   (UNKNOWN, PARITY_ERROR, NFC_CMD_CUT) nothing; the record still counts as "the command before"
+ * Whatever is last in stream order wins a byte; a patch whose value differs from a byte that was already known sets NFC_IMG_CHANGED.
+ * THE TAIL: beside the image its stream keeps the summaries of its last three commands -- cmd, type, flags, first extra byte --, tail[0]
+ * the most recent, cmd NFC_CMD_UNKNOWN where there was none yet.  With it READR | READT and AUTH | nonce | {nr}{ar} | {at} may fall into
+ * different pushes or calls: commands cut anywhere give the image of the whole.
+ * nfc_host_card_image: the CPU twin (no GPU needed).  It advances `image` in place over n records; `data` holds data_len bytes, a record's
+ * bytes at its byte_off; key_a / key_b and `table` (NULL: an empty one) are the machine's.  NFC_ERR_ARG: a null argument that is needed, an
+ * image field out of range (tag_type, flags, a source code above 3, n_known other than the count of known bytes, a tail entry), a faulty
+ * table, a record whose bytes lie outside data.
+ * nfc_multi_track_images(m, on): off at create; on implies nfc_multi_track_commands(m, 1).  The images' buffer -- mem [K][1024] | src
+ * [K][1024] | info [K] | tail [K][3], 2 112 bytes per stream, each section followed by the guard word -- is allocated, holding
+ * nfc_card_image_init's images, by a context's FIRST call: a context that never switches it on allocates and launches what it always
+ * did.  While it is on, a tracked push enqueues k_multi_images (csrc/image.hip.h) behind the machine kernel, a workgroup of one wave per
+ * stream, with no host wait: four launches instead of three; a push in which nothing was stored launches nothing.  The images persist
+ * on the device from push to push whether or not anybody fetches.  nfc_multi_fetch_commands is not affected.
+ * nfc_multi_fetch_images: ONE copy of the buffer to pinned memory and one wait; a second call before the next push (or reset, or
+ * nfc_multi_set_image) returns the same data and makes no device call.  Images never switched on: NFC_ERR_STATE.  ms_kernel: with
+ * nfc_multi_set_timing(on), k_multi_images of the last push by HIP events, else 0.  The pointers live until the next
+ * nfc_multi_fetch_images that copies, or nfc_multi_destroy.
+ * nfc_multi_get_image / nfc_multi_set_image: one stream's image, tail included; both complete the device first, set checks the image as
+ * the twin does.  nfc_multi_reset(stream) returns that stream's image and tail to nfc_card_image_init's.
+ * Argument errors are NFC_ERR_ARG, raised before the device is touched.
+ * COST: README.md, profiles/images_bench.json. */
+#define NFC_IMG_BYTES 1024
+#define NFC_IMG_TAIL 3
+enum { NFC_IMG_SRC_UNKNOWN = 0, NFC_IMG_SRC_READ = 1, NFC_IMG_SRC_ANTICOLL = 2, NFC_IMG_SRC_KEY = 3 };   /* nfc_card_image.src */
+enum { NFC_IMG_TAG_CHANGED = 1, NFC_IMG_CHANGED = 2, NFC_IMG_BEYOND = 4, NFC_IMG_SAW_WRITE = 8, NFC_IMG_FLAGS_ALL = 15 };   /* nfc_image_info.flags, sticky */
+typedef struct nfc_image_cmd {      /* 16 bytes: what a command leaves to the three behind it */
+    int32_t cmd;                    /* index for nfc_command_info, or NFC_CMD_* */
+    uint32_t type, flags, val;      /* nfc_frame.type; NFC_FRAME_*; the first extra byte (0: none, or cmd < 0) */
+} nfc_image_cmd;
+typedef struct nfc_image_info {     /* 16 bytes */
+    int32_t tag_type;               /* -1 none heard, 0 Ultralight, 1 Classic 1K, 2 Classic 4K, 3 DESFire */
+    uint32_t flags;                 /* NFC_IMG_* */
+    uint32_t n_known;               /* bytes of src that are not 0 */
+    uint32_t reserved;              /* 0 */
+} nfc_image_info;
+typedef struct nfc_card_image {     /* 2 112 bytes */
+    uint8_t mem[NFC_IMG_BYTES], src[NFC_IMG_BYTES];
+    nfc_image_info info;
+    nfc_image_cmd tail[NFC_IMG_TAIL];
+} nfc_card_image;
+typedef struct {
+    const uint8_t *mem, *src;       /* [n_streams][1024] */
+    const nfc_image_info *info;     /* [n_streams] */
+    const nfc_image_cmd *tail;      /* [n_streams][3] */
+    uint32_t n_streams, n_launches; /* of the last push: 4 with images, 0 when nothing was stored */
+    uint64_t bytes_copied;          /* device -> host, of this call */
+    double ms_kernel;
+    uint64_t reserved[4];
+} nfc_multi_images;
+int nfc_card_image_init(nfc_card_image *image);   /* nothing known, no tag type, an empty tail */
+int nfc_host_card_image(nfc_card_image *image, const nfc_frame *cmds, size_t n, const uint8_t *data, size_t data_len, const uint8_t key_a[6],
+                        const uint8_t key_b[6], const nfc_fsm_key_table *table /* may be NULL */);
+int nfc_multi_track_images(nfc_multi *m, int on);
+int nfc_multi_fetch_images(nfc_multi *m, nfc_multi_images *out);
+int nfc_multi_get_image(nfc_multi *m, uint32_t stream, nfc_card_image *image);
+int nfc_multi_set_image(nfc_multi *m, uint32_t stream, const nfc_card_image *image);
 
 /* one stream's boundary state, in the form an nfc_ctx exports and imports it */
 int nfc_multi_get_state(nfc_multi *m, uint32_t stream, nfc_state_header *hdr, float *ring, size_t ring_cap, uint8_t *pending, size_t pending_cap);

@@ -153,6 +153,19 @@ class TxPending(C.Structure):   # nfc_tx_pending
                 ('air', C.c_uint8 * 18), ('par', C.c_uint8 * 18), ('reserved2', C.c_uint8 * 12)]
 
 
+class MultiImages(C.Structure):   # nfc_multi_images
+    _fields_ = [('mem', C.c_void_p), ('src', C.c_void_p), ('info', C.c_void_p), ('tail', C.c_void_p), ('n_streams', C.c_uint32),
+                ('n_launches', C.c_uint32), ('bytes_copied', C.c_uint64), ('ms_kernel', C.c_double), ('reserved', C.c_uint64 * 4)]
+
+
+# the memory images (nfc_image_cmd, nfc_image_info, nfc_card_image as records), a byte's source codes and an image's sticky flags
+NFC_IMG_BYTES, NFC_IMG_TAIL = 1024, 3
+NFC_IMG_SRC_UNKNOWN, NFC_IMG_SRC_READ, NFC_IMG_SRC_ANTICOLL, NFC_IMG_SRC_KEY = 0, 1, 2, 3
+NFC_IMG_TAG_CHANGED, NFC_IMG_CHANGED, NFC_IMG_BEYOND, NFC_IMG_SAW_WRITE = 1, 2, 4, 8
+IMAGE_CMD_DTYPE = np.dtype([('cmd', '<i4'), ('type', '<u4'), ('flags', '<u4'), ('val', '<u4')])
+IMAGE_INFO_DTYPE = np.dtype([('tag_type', '<i4'), ('flags', '<u4'), ('n_known', '<u4'), ('reserved', '<u4')])
+CARD_IMAGE_DTYPE = np.dtype([('mem', 'u1', (NFC_IMG_BYTES,)), ('src', 'u1', (NFC_IMG_BYTES,)), ('info', IMAGE_INFO_DTYPE),
+                             ('tail', IMAGE_CMD_DTYPE, (NFC_IMG_TAIL,))])
 TX_PENDING_DTYPE = np.dtype([('start', '<u8'), ('n_bits', '<u2'), ('role', 'u1'), ('reserved0', 'u1'), ('reserved1', '<u4'), ('air', 'u1', (18,)),
                              ('par', 'u1', (18,)), ('reserved2', 'u1', (12,))])   # nfc_tx_pending as a record
 TX_ANSWER_DTYPE = np.dtype([('idx', '<u8'), ('byte_off', '<u4'), ('n_bits', '<u4')])   # nfc_tx_answer
@@ -253,7 +266,8 @@ SYMBOLS = ['nfc_abi_version', 'nfc_device_count', 'nfc_create', 'nfc_destroy', '
            'nfc_emu_state_init', 'nfc_emu_last_error', 'nfc_host_emu_step', 'nfc_host_emulate', 'nfc_multi_emulate', 'nfc_multi_fetch_answers', 'nfc_multi_get_emu_state',
            'nfc_multi_set_emu_state', 'nfc_host_emulate_pairs', 'nfc_emulate_pairs_device',
            'nfc_host_air_render', 'nfc_air_render_device',
-           'nfc_host_answers_tx', 'nfc_multi_transmit_device', 'nfc_multi_get_tx_state', 'nfc_multi_set_tx_state']
+           'nfc_host_answers_tx', 'nfc_multi_transmit_device', 'nfc_multi_get_tx_state', 'nfc_multi_set_tx_state',
+           'nfc_card_image_init', 'nfc_host_card_image', 'nfc_multi_track_images', 'nfc_multi_fetch_images', 'nfc_multi_get_image', 'nfc_multi_set_image']
 
 _libs = {}
 
@@ -423,6 +437,12 @@ def load(path=None):
     L.nfc_multi_transmit_device.argtypes = [vp, C.POINTER(AnswersTxConfig), vp, sz, vp, vp, C.POINTER(C.c_float * 2)]
     L.nfc_multi_get_tx_state.argtypes = [vp, u32, C.POINTER(TxPending)]
     L.nfc_multi_set_tx_state.argtypes = [vp, u32, C.POINTER(TxPending)]
+    L.nfc_card_image_init.argtypes = [vp]
+    L.nfc_host_card_image.argtypes = [vp, vp, sz, vp, sz, vp, vp, C.POINTER(FsmKeyTable)]
+    L.nfc_multi_track_images.argtypes = [vp, C.c_int]
+    L.nfc_multi_fetch_images.argtypes = [vp, C.POINTER(MultiImages)]
+    L.nfc_multi_get_image.argtypes = [vp, u32, vp]
+    L.nfc_multi_set_image.argtypes = [vp, u32, vp]
     for name in SYMBOLS:
         getattr(L, name)
     _libs[path] = L

@@ -21,7 +21,7 @@ __all__ = ['NfcContext', 'NfcError', 'DeviceBuffer', 'host_decode_lut', 'host_en
            'NFC_MULTI_FETCH_PACKETS', 'NFC_MULTI_FETCH_ALL', 'NFC_MF_EDGES', 'NFC_MF_SYM0', 'NFC_MF_SYM1', 'NFC_MF_PK0', 'NFC_MF_PK1',
            'NFC_MF_BITS0', 'NFC_MF_BITS1', 'NFC_MF_ARRAYS', 'COUNTS_DTYPE', 'COUNTS_FLAGS_DTYPE', 'NfcFrames', 'NfcMultiFrames', 'host_frames',
            'RAW_FRAME_DTYPE', 'NFC_RAW_PARITY_OK', 'NFC_RAW_CRC_A_OK', 'NFC_RAW_CUT', 'NfcMultiCommands', 'NFC_FSM_LOST', 'NFC_FSM_UID_OVERFLOW',
-           'NFC_CMD_CUT']
+           'NFC_CMD_CUT', 'NfcMultiImages']
 
 _KIND_DTYPE = {NFC_IN_IQ_F32: (np.float32, 2), NFC_IN_ENV_F32: (np.float32, 1),
                NFC_IN_REAL_F32_SQ: (np.float32, 1), NFC_IN_I16_SQ: (np.int16, 1), NFC_IN_IQ_I16: (np.int16, 2),
@@ -534,6 +534,35 @@ class NfcMultiContext(object):
         self._chk(self.L.nfc_multi_fetch_commands(self.h, C.byref(c)), 'nfc_multi_fetch_commands')
         return NfcMultiCommands(c, copy)
 
+    def track_images(self, on=True):
+        """While on, every tracked push also rebuilds every stream's card from its commands (nfc_multi_track_images; it switches command
+        tracking on): one launch more, k_multi_images, a wave per stream, no host wait.  The images stay on the device from push to
+        push; fetch_images() brings them."""
+        self._chk(self.L.nfc_multi_track_images(self.h, int(bool(on))), 'nfc_multi_track_images')
+
+    def fetch_images(self, copy=True):
+        """Every stream's memory image in ONE copy (nfc_multi_fetch_images) -> NfcMultiImages.  copy=False: views of the context's pinned
+        memory, valid until the next fetch_images that copies, or close."""
+        f = _lib.MultiImages()
+        self._chk(self.L.nfc_multi_fetch_images(self.h, C.byref(f)), 'nfc_multi_fetch_images')
+        return NfcMultiImages(f, copy)
+
+    def image(self, k):
+        """Stream k's image, tail included, as an emulate.CardImage (nfc_multi_get_image)."""
+        from . import emulate
+        if not 0 <= int(k) < self.n_streams:
+            raise NfcError('image: stream %d out of range (n_streams %d)' % (k, self.n_streams))
+        rec = np.zeros((), _lib.CARD_IMAGE_DTYPE)
+        self._chk(self.L.nfc_multi_get_image(self.h, int(k), rec.ctypes.data), 'nfc_multi_get_image')
+        return emulate.CardImage(rec)
+
+    def set_image(self, k, image):
+        """Stream k's image continues from `image` (an emulate.CardImage: host_card_image's, another stream's)."""
+        if not 0 <= int(k) < self.n_streams:
+            raise NfcError('set_image: stream %d out of range (n_streams %d)' % (k, self.n_streams))
+        rec = np.ascontiguousarray(image.rec, _lib.CARD_IMAGE_DTYPE)
+        self._chk(self.L.nfc_multi_set_image(self.h, int(k), rec.ctypes.data), 'nfc_multi_set_image')
+
     def emulate(self, cards, stream=-1):
         """Give stream `stream` a card (an emulate.Card; -1: every stream; a list: one per stream, None for none), or None to take it away
         (nfc_multi_emulate).  From then on a tracked push -- tracking is switched on -- runs the emulating form of the machine kernel: the
@@ -1005,6 +1034,55 @@ class NfcMultiAnswers(object):
         for v, q in zip(air[o:o + n].tolist(), par[o:o + n].tolist()):
             out += [(v >> j) & 1 for j in range(8)] + [q & 1]
         return out
+
+
+class NfcMultiImages(object):
+    """What nfc_multi_fetch_images brings: every stream's card as it was heard.  mem_all / src_all: [n_streams][1024] bytes and their source
+    codes (_lib.NFC_IMG_SRC_*; 0: never shown); tag_type (-1: no ATQA heard), flags (_lib.NFC_IMG_*), n_known: one entry per stream; tail:
+    [n_streams][3] IMAGE_CMD_DTYPE, the summaries of each stream's last three commands."""
+
+    def __init__(self, f, copy=True):
+        K = int(f.n_streams)
+        self.n_streams, self.n_launches, self.bytes_copied, self.ms_kernel = K, int(f.n_launches), int(f.bytes_copied), float(f.ms_kernel)
+
+        def arr(ptr, n, dtype):
+            dtype = np.dtype(dtype)
+            a = np.frombuffer((C.c_char * (int(n) * dtype.itemsize)).from_address(ptr), dtype)
+            return a.copy() if copy else a
+        self.mem_all = arr(f.mem, K * _lib.NFC_IMG_BYTES, np.uint8).reshape(K, _lib.NFC_IMG_BYTES)
+        self.src_all = arr(f.src, K * _lib.NFC_IMG_BYTES, np.uint8).reshape(K, _lib.NFC_IMG_BYTES)
+        self.info = arr(f.info, K, _lib.IMAGE_INFO_DTYPE)
+        self.tail = arr(f.tail, K * _lib.NFC_IMG_TAIL, _lib.IMAGE_CMD_DTYPE).reshape(K, _lib.NFC_IMG_TAIL)
+        self.tag_type, self.flags, self.n_known = self.info['tag_type'], self.info['flags'], self.info['n_known']
+
+    def mem(self, k):
+        return self.mem_all[k]
+
+    def src(self, k):
+        return self.src_all[k]
+
+    def known_mask(self, k):
+        return self.src_all[k] != 0
+
+    def coverage(self):
+        """Per stream: the known share of the card's memory (64 bytes for an Ultralight, else 1 024)."""
+        size = np.where(self.tag_type == 0, 64, _lib.NFC_IMG_BYTES)
+        return self.n_known.astype(np.float64) / size
+
+    def image(self, k):
+        """Stream k's image as an emulate.CardImage (a copy): what host_card_image gives and set_image takes."""
+        from . import emulate
+        rec = np.zeros((), _lib.CARD_IMAGE_DTYPE)
+        rec['mem'], rec['src'], rec['info'], rec['tail'] = self.mem_all[k], self.src_all[k], self.info[k], self.tail[k]
+        return emulate.CardImage(rec)
+
+    def card(self, k, rands=None, mode=_lib.NFC_EMU_CARD):
+        """Stream k's image as a tag to emulate (emulate.tag_card), unknown bytes as zeros."""
+        return self.image(k).card(rands, mode)
+
+    def to_json(self, k, path, rands=None):
+        """Stream k's image as one of the reference's card files (parser.Parser reads it)."""
+        return self.image(k).to_json(path, rands)
 
 
 class NfcMultiCommands(object):

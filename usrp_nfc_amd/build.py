@@ -7,7 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 SO = os.path.join(HERE, 'libnfc_amd.so')
 SO_HOOKS = os.path.join(HERE, 'libnfc_amd_hooks.so')   # the same sources with -DNFC_TEST_HOOKS: test hooks and diagnostics (README.md)
-SOURCES = ['nfc_amd.hip', 'nfc_iq16.hip', 'nfc_iq8.hip', 'nfc_record.hip', 'nfc_multi.hip', 'nfc_frames.hip', 'nfc_commands.hip', 'nfc_keys.hip', 'nfc_emu.hip', 'nfc_air.hip', 'nfc_answers_tx.hip', 'nfc_ctx_commands.hip']   # (commands for one long stream, a lane per transaction, and their CPU twin: ctx_commands.hip.h; the answers' transmission, its CPU twin: answers_tx.hip.h -- the device call is nfc_multi.hip's; the air interface, frames to IQ captures: air.hip.h; the emulators and their closed loop: emu.hip.h; the key recovery: keys.hip.h; the protocol machine a lane per stream: fsm.hip.h, multi_commands.hip.h; the frame assembly kernels: frames.hip.h; the complex int16 and the complex 8-bit input kinds' kernels: csrc/kind_kernels.h; the recording kernel: record.hip.h; the multi-stream context: multi.hip.h, multi_fetch.hip.h)
+SOURCES = ['nfc_amd.hip', 'nfc_iq16.hip', 'nfc_iq8.hip', 'nfc_record.hip', 'nfc_multi.hip', 'nfc_frames.hip', 'nfc_commands.hip', 'nfc_keys.hip', 'nfc_emu.hip', 'nfc_air.hip', 'nfc_answers_tx.hip', 'nfc_ctx_commands.hip', 'nfc_image.hip']   # (the memory images per stream and their CPU twin: image.hip.h -- the kernel is nfc_multi.hip's; commands for one long stream, a lane per transaction, and their CPU twin: ctx_commands.hip.h; the answers' transmission, its CPU twin: answers_tx.hip.h -- the device call is nfc_multi.hip's; the air interface, frames to IQ captures: air.hip.h; the emulators and their closed loop: emu.hip.h; the key recovery: keys.hip.h; the protocol machine a lane per stream: fsm.hip.h, multi_commands.hip.h; the frame assembly kernels: frames.hip.h; the complex int16 and the complex 8-bit input kinds' kernels: csrc/kind_kernels.h; the recording kernel: record.hip.h; the multi-stream context: multi.hip.h, multi_fetch.hip.h)
 DEPS = sorted(f for f in os.listdir(CSRC) if f.endswith(('.h', '.hip'))) + [os.path.join('..', '..', 'include', 'nfc_amd.h')]
 
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared',

@@ -39,6 +39,8 @@
 #include "input_kind.h"
 #define NFC_ANSWERS_TX_KERNELS
 #include "answers_tx.hip.h"   // (the answers as TX samples: the schedule and render kernels; their twin is nfc_answers_tx.hip)
+#define NFC_IMAGE_KERNELS
+#include "image.hip.h"   // (the memory images: k_multi_images; its twin is nfc_image.hip)
 
 using namespace nfc;
 using namespace nfc::multi;
@@ -138,6 +140,17 @@ struct nfc_multi {
     uint64_t cmd_nfr[2] = {0, 0}, cmd_room[2] = {0, 0};
     Event evc[4];
     nfc_multi_commands cout;
+    // the memory images (image.hip.h), there from the first nfc_multi_track_images on, never before: the buffer of four sections with
+    // their guards, persistent from push to push; its pinned twin, filled by nfc_multi_fetch_images; one image's staging
+    bool track_img = false;
+    Packed img;
+    uint64_t img_at[image::ISEC_COUNT] = {0, 0, 0, 0};
+    size_t img_bytes = 0;
+    PinBuf h_img_one;
+    bool img_fetched = false, img_timed = false;
+    uint32_t img_launches = 0;   // of the last push
+    Event evi[2];
+    nfc_multi_images iout;
     nfc_multi_stats stats;
     std::string err;
     LaunchError launch_err;
@@ -491,6 +504,81 @@ int enqueue_commands(nfc_multi *m) {
     if (int rc = launch_ok(m)) return rc;
     m->cmd_state = nfc_multi::CMD_LAUNCHED;
     m->stats.n_launches += 3;
+    if (m->track_img) {   // the images behind the machines: a workgroup of one wave per stream
+        image::Args I;
+        memset(&I, 0, sizeof I);
+        I.img = m->img.d.as<uint8_t>();
+        for (int s = 0; s < image::ISEC_COUNT; s++) I.at[s] = m->img_at[s];
+        I.K = K;
+        I.cmds = m->cmd.d.as<uint8_t>();
+        I.L = L;
+        I.state = m->d_fsm.as<uint32_t>();
+        I.sector_keys = m->d_keys.as<uint32_t>();
+        if (timed) NFC_LAUNCH_EXT(image::k_multi_images, dim3(K), dim3(image::THREADS), 0, m->st, m->evi[0], m->evi[1], 0, I);
+        else NFC_LAUNCH(image::k_multi_images, dim3(K), dim3(image::THREADS), 0, m->st, I);
+        if (int rc = launch_ok(m)) return rc;
+        m->img_timed = timed;
+        m->img_launches = 4;
+        m->img_fetched = false;
+        m->stats.n_launches += 1;
+    }
+    return NFC_OK;
+}
+
+// ---- the memory images ----
+// streams [k0, k1) to nfc_card_image_init's image (guards: the guard word behind the four sections too)
+int images_init_range(nfc_multi *m, uint32_t k0, uint32_t k1, bool guards) {
+    image::InitArgs I;
+    memset(&I, 0, sizeof I);
+    I.img = m->img.d.as<uint8_t>();
+    for (int s = 0; s < image::ISEC_COUNT; s++) I.at[s] = m->img_at[s], I.end[s] = m->img.guards[s];
+    I.K = m->K, I.k0 = k0, I.k1 = k1;
+    I.guard_bytes = guards ? GUARD_BYTES : 0u, I.guard_word = GUARD_WORD;
+    const size_t work = (size_t)(k1 > k0 ? k1 - k0 : 0u) * (image::MEM_BYTES / 16);
+    NFC_LAUNCH(image::k_images_init, dim3((unsigned)std::max<size_t>(1, std::min<size_t>(4096, (work + 255) / 256))), dim3(256), 0, m->st, I);
+    m->img_fetched = false;
+    return launch_ok(m);
+}
+// the images' buffer, every image nfc_card_image_init's, at the first nfc_multi_track_images of a context
+int ensure_images(nfc_multi *m, const char *fn) {
+    if (m->img.d.p) return NFC_OK;
+    const size_t K = m->K;
+    for (Event &e : m->evi)
+        if (e.create() != hipSuccess) {
+            (void)hipGetLastError();
+            return mfail(m, NFC_ERR_DEVICE, "hipEventCreate failed");
+        }
+    if (grow(m, m->h_img_one, sizeof(nfc_card_image), fn, false) < 0) return NFC_ERR_NOMEM;
+    Sections S{0, {}};
+    const size_t sizes[image::ISEC_COUNT] = {K * image::MEM_BYTES, K * image::MEM_BYTES, K * sizeof(nfc_image_info), K * image::TAIL * sizeof(nfc_image_cmd)};
+    uint64_t at[image::ISEC_COUNT], end[image::ISEC_COUNT];
+    for (int s = 0; s < image::ISEC_COUNT; s++) S.place(at[s], end[s], sizes[s]);
+    if (grow(m, m->img.d, S.at, fn, false) < 0) return NFC_ERR_NOMEM;
+    for (int s = 0; s < image::ISEC_COUNT; s++) m->img_at[s] = at[s];
+    m->img.guards = std::move(S.guards);
+    m->img_bytes = S.at;
+    m->img_launches = 0;
+    if (int rc = images_init_range(m, 0, m->K, true)) {
+        m->img.d.release();
+        m->img.guards.clear();
+        return rc;
+    }
+    return NFC_OK;
+}
+// one stream's image between the device and the pinned staging: four copies, one per section
+int image_io(nfc_multi *m, uint32_t k, bool set) {
+    nfc_card_image *h = m->h_img_one.as<nfc_card_image>();
+    uint8_t *d = m->img.d.as<uint8_t>();
+    struct { void *host; uint8_t *dev; size_t n; } part[image::ISEC_COUNT] = {
+        {h->mem, d + m->img_at[image::ISEC_MEM] + (size_t)k * image::MEM_BYTES, image::MEM_BYTES},
+        {h->src, d + m->img_at[image::ISEC_SRC] + (size_t)k * image::MEM_BYTES, image::MEM_BYTES},
+        {&h->info, d + m->img_at[image::ISEC_INFO] + (size_t)k * sizeof(nfc_image_info), sizeof(nfc_image_info)},
+        {h->tail, d + m->img_at[image::ISEC_TAIL] + (size_t)k * image::TAIL * sizeof(nfc_image_cmd), image::TAIL * sizeof(nfc_image_cmd)}};
+    for (auto &p : part) {
+        if (set) MCHK(m, hipMemcpyAsync(p.dev, p.host, p.n, hipMemcpyHostToDevice, m->st));
+        else MCHK(m, hipMemcpyAsync(p.host, p.dev, p.n, hipMemcpyDeviceToHost, m->st));
+    }
+    MCHK(m, hipStreamSynchronize(m->st));
     return NFC_OK;
 }
 
@@ -757,6 +845,8 @@ int nfc_multi_push_device(nfc_multi *m, const void *dev_base, const uint64_t *fi
     m->tx_done = false;
     m->cmd_state = nfc_multi::CMD_NONE;
     m->cmd_fetched = false;
+    m->img_launches = 0;
+    if (m->track_img) m->img_fetched = false;
     if (m->track) return enqueue_commands(m);
     return NFC_OK;
 }
@@ -1133,6 +1223,8 @@ int nfc_multi_reset(nfc_multi *m, int64_t stream) {
     if (m->d_emu.p)   // ... and the emulators: nfc_emu_state_init's state (the cards stay)
         if (int rc = emu_state_init_range(m, k0, k1)) return rc;
     if (m->txpend.d.p) MCHK(m, hipMemsetAsync(m->txpend.d.as<nfc_tx_pending>() + k0, 0, (size_t)(k1 - k0) * sizeof(nfc_tx_pending), m->st));   // ... and what they were still to transmit
+    if (m->img.d.p)   // ... and their memory images, tails included
+        if (int rc = images_init_range(m, k0, k1, false)) return rc;
     m->cmd_state = nfc_multi::CMD_NONE;
     m->cmd_fetched = false;
     if (int rc = launch_ok(m)) return rc;
@@ -1342,6 +1434,81 @@ int nfc_multi_fetch_commands(nfc_multi *m, nfc_multi_commands *out) {
     m->cmd_fetched = true;
     if (out) *out = c;
     return NFC_OK;
+}
+
+// ---- the memory images (image.hip.h) ----
+int nfc_multi_track_images(nfc_multi *m, int on) {
+    if (!m) return NFC_ERR_ARG;
+    LaunchScope scope(&m->launch_err);
+    if (on) {
+        if (hipSetDevice(m->P.device) != hipSuccess) return mfail(m, NFC_ERR_DEVICE, "hipSetDevice failed");
+        if (int rc = ensure_fsm(m, "nfc_multi_track_images")) return rc;
+        if (int rc = ensure_images(m, "nfc_multi_track_images")) return rc;
+        m->track = true;   // images are made of commands
+    }
+    m->track_img = on != 0;
+    return NFC_OK;
+}
+
+// One copy of the images' buffer to pinned memory, one wait.
+int nfc_multi_fetch_images(nfc_multi *m, nfc_multi_images *out) {
+    if (!m) return NFC_ERR_ARG;
+    LaunchScope scope(&m->launch_err);
+    if (!m->img.d.p) return mfail(m, NFC_ERR_STATE, "the memory images were never switched on (nfc_multi_track_images)");
+    if (m->img_fetched) {   // the same data: no device call
+        if (out) *out = m->iout;
+        return NFC_OK;
+    }
+    if (hipSetDevice(m->P.device) != hipSuccess) return mfail(m, NFC_ERR_DEVICE, "hipSetDevice failed");
+    if (grow(m, m->img.h, m->img_bytes, "nfc_multi_fetch_images", false) < 0) return NFC_ERR_NOMEM;
+    uint8_t *h = m->img.h.as<uint8_t>();
+    MCHK(m, hipMemcpyAsync(h, m->img.d.p, m->img_bytes, hipMemcpyDeviceToHost, m->st));
+    MCHK(m, hipStreamSynchronize(m->st));
+    if (int rc = launch_ok(m)) return rc;
+    nfc_multi_images &o = m->iout;
+    memset(&o, 0, sizeof o);
+    o.mem = h + m->img_at[image::ISEC_MEM];
+    o.src = h + m->img_at[image::ISEC_SRC];
+    o.info = (const nfc_image_info *)(h + m->img_at[image::ISEC_INFO]);
+    o.tail = (const nfc_image_cmd *)(h + m->img_at[image::ISEC_TAIL]);
+    o.n_streams = m->K;
+    o.n_launches = m->img_launches;
+    o.bytes_copied = m->img_bytes;
+    if (m->img_launches && m->img_timed) {
+        float ms = 0.f;
+        MCHK(m, hipEventElapsedTime(&ms, m->evi[0], m->evi[1]));
+        o.ms_kernel = ms;
+    }
+    m->img_fetched = true;
+    if (out) *out = o;
+    return NFC_OK;
+}
+
+int nfc_multi_get_image(nfc_multi *m, uint32_t stream, nfc_card_image *image) {
+    if (!m) return NFC_ERR_ARG;
+    LaunchScope scope(&m->launch_err);
+    if (stream >= m->K) return mfail(m, NFC_ERR_ARG, "stream %u out of range (n_streams %u)", stream, m->K);
+    if (!image) return mfail(m, NFC_ERR_ARG, "image is null");
+    if (!m->img.d.p) return mfail(m, NFC_ERR_STATE, "the memory images were never switched on (nfc_multi_track_images)");
+    if (hipSetDevice(m->P.device) != hipSuccess) return mfail(m, NFC_ERR_DEVICE, "hipSetDevice failed");
+    if (int rc = image_io(m, stream, false)) return rc;
+    if (int rc = launch_ok(m)) return rc;
+    memcpy(image, m->h_img_one.p, sizeof *image);
+    return NFC_OK;
+}
+
+int nfc_multi_set_image(nfc_multi *m, uint32_t stream, const nfc_card_image *image) {
+    if (!m) return NFC_ERR_ARG;
+    LaunchScope scope(&m->launch_err);
+    if (stream >= m->K) return mfail(m, NFC_ERR_ARG, "stream %u out of range (n_streams %u)", stream, m->K);
+    if (!image) return mfail(m, NFC_ERR_ARG, "image is null");
+    if (const char *bad = image::image_fault(*image)) return mfail(m, NFC_ERR_ARG, "image: %s", bad);
+    if (!m->img.d.p) return mfail(m, NFC_ERR_STATE, "the memory images were never switched on (nfc_multi_track_images)");
+    if (hipSetDevice(m->P.device) != hipSuccess) return mfail(m, NFC_ERR_DEVICE, "hipSetDevice failed");
+    MCHK(m, hipStreamSynchronize(m->st));   // (the staging may still be on its way from an earlier call)
+    memcpy(m->h_img_one.p, image, sizeof *image);
+    m->img_fetched = false;
+    return image_io(m, stream, true);
 }
 
 // ---- emulation: a stream that answers (multi_commands.hip.h: k_multi_commands_emu) ----
@@ -1687,7 +1854,7 @@ extern "C" int nfc_debug_multi_guards(nfc_multi *m) {
     if (launch_ok(m) || hipMemcpyAsync(m->h_blob.p, bad, 4, hipMemcpyDeviceToHost, m->st) != hipSuccess || hipStreamSynchronize(m->st) != hipSuccess) return -1;
     memcpy(&h, m->h_blob.p, 4);
     // ... and the guards behind the sections of the three packed buffers, where the launches that last filled each left them
-    for (const Packed *p : {&m->fetch, &m->frames, &m->cmd, &m->txpend, &m->tx}) {
+    for (const Packed *p : {&m->fetch, &m->frames, &m->cmd, &m->txpend, &m->tx, &m->img}) {
         const int bad_bytes = packed_guards_damaged(m, *p);
         if (bad_bytes < 0) return -1;
         h += (uint32_t)bad_bytes;

@@ -99,7 +99,7 @@ def _per_source_keys(keys, n):
 
 
 def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None, keep=None, device=0, push_stats=None, frames=False, commands=False,
-                keys=None, nested=False, emulate=None, reader_pairs=False, **sink_kwargs):
+                keys=None, nested=False, emulate=None, reader_pairs=False, images=False, **sink_kwargs):
     """Decode many recordings at once: every source is a stream of one api.NfcMultiContext, a GPU lane each, one kernel launch per
     round of pieces (include/nfc_amd.h: nfc_multi) -- what a loop of ``decoder(src=s).run()`` does capture by capture.
 
@@ -134,6 +134,10 @@ def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None,
     (DESIGN.md 8j), so a card whose sectors have different keys is decrypted through every authentication whose key was found.  Two
     blocks of one sector with different keys: the lower block's is used and the others are the background's ``key_conflicts``, a dict
     (key_type, block) -> key (empty where there were none).
+    images=True: the context also rebuilds every source's card from its commands on the GPU (api.NfcMultiContext.track_images, which
+    implies the tracking; keys= are then allowed without commands=True) and, when a group is done, every background gets ``image``, an
+    emulate.CardImage (None for a source that no group reached) -- ``image.card()`` is the tag to emulate, ``image.to_json(path)`` the reference's card file.  With
+    keys='recover' the image is built in the tracked pass, which uses the recovered table.
     -> one ``background`` per source, in order: ``decode_many(srcs)[i].packets`` and its fsm's command trace are what
     ``decoder(src=srcs[i]).run()`` gives."""
     scales = {k: sink_kwargs.pop(k, 0.0) for k in ('wav_scale', 'iq16_scale', 'iq8_scale')}
@@ -159,10 +163,13 @@ def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None,
     if commands:
         for b in backs:
             b.commands = []
+    if images:
+        for b in backs:
+            b.image = None
     per_source_keys = None
     recover = isinstance(keys, str) and keys == 'recover'
     if recover:
-        if not commands:
+        if not (commands or images):
             raise ValueError('decode_many: keys are for commands=True')
         for b in backs:
             b.recovered_keys = {}
@@ -170,7 +177,7 @@ def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None,
     elif nested or reader_pairs:
         raise ValueError("decode_many: nested and reader_pairs are for keys='recover'")
     elif keys is not None:
-        if not commands:
+        if not (commands or images):
             raise ValueError('decode_many: keys are for commands=True')
         per_source_keys = _per_source_keys(keys, len(loaded))
     if not loaded:
@@ -190,8 +197,10 @@ def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None,
                                      device=device, i16_scale=scale if kind in _SCALED_KINDS else 0.0, **sink) as m:
                 if recover:
                     _recover_group_keys(m, buf, starts, lens, piece, backs[g0:g0 + len(group)], device, nested, reader_pairs)
-                if commands:
+                if commands or images:
                     m.track_commands(True)
+                    if images:
+                        m.track_images(True)
                     if recover:
                         for k, b in enumerate(backs[g0:g0 + len(group)]):
                             if b.recovered_keys:
@@ -240,6 +249,10 @@ def decode_many(sources, reader=True, tag=True, samp_rate=2e6, fsm_factory=None,
                     if push_stats is not None:
                         st = m.stats()
                         push_stats.append((int(st.n_fetches), int(st.n_reads_device)))
+                if images:
+                    im = m.fetch_images()
+                    for k, b in enumerate(backs[g0:g0 + len(group)]):
+                        b.image = im.image(k)
         finally:
             buf.free()
     return backs

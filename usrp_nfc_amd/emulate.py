@@ -100,6 +100,81 @@ def generate_1k():
     return block0 + zero * 2 + trailer + (zero * 3 + trailer) * 15
 
 
+class CardImage(object):
+    """A card as it was heard (nfc_card_image; include/nfc_amd.h says how commands patch it): `rec`, one CARD_IMAGE_DTYPE record.  mem / src:
+    views of its 1 024 bytes and their source codes (0: never shown); tag_type (-1: no ATQA heard), flags (NFC_IMG_*), n_known; tail: the
+    summaries of the stream's last three commands, with which a later call continues mid-chain."""
+
+    def __init__(self, rec=None):
+        if rec is None:
+            rec = np.zeros((), _lib.CARD_IMAGE_DTYPE)
+            if _lib.load().nfc_card_image_init(rec.ctypes.data) != 0:
+                raise EmulationError('nfc_card_image_init failed')
+        self.rec = np.array(rec, _lib.CARD_IMAGE_DTYPE).reshape(())
+
+    mem = property(lambda self: self.rec['mem'])
+    src = property(lambda self: self.rec['src'])
+    tail = property(lambda self: self.rec['tail'])
+    tag_type = property(lambda self: int(self.rec['info']['tag_type']))
+    flags = property(lambda self: int(self.rec['info']['flags']))
+    n_known = property(lambda self: int(self.rec['info']['n_known']))
+
+    def copy(self):
+        return CardImage(self.rec.copy())
+
+    def __eq__(self, other):
+        return isinstance(other, CardImage) and self.rec.tobytes() == other.rec.tobytes()
+
+    def __ne__(self, other):
+        return not self == other
+
+    __hash__ = None
+
+    def known_mask(self):
+        return self.src != 0
+
+    def size(self):
+        """bytes of the card's memory: 64 for an Ultralight, else 1 024"""
+        return 64 if self.tag_type == ULTRALIGHT else _lib.NFC_IMG_BYTES
+
+    def card(self, rands=None, mode=NFC_EMU_CARD):
+        """The image as a tag to emulate (tag_card), unknown bytes as zeros; a Classic without `rands` gets drawn_rands()."""
+        ul = self.tag_type == ULTRALIGHT
+        return tag_card(ULTRALIGHT if ul else CLASSIC1K, self.mem[:self.size()].copy(), rands if (rands is not None or ul) else drawn_rands(), mode)
+
+    def entries(self, rands=None):
+        """The image as the entries of one of the reference's card files (parser.Parser reads them, create_json writes them)."""
+        tag = {'entry': 'tag', 'type': 'ULTRALIGHT' if self.tag_type == ULTRALIGHT else 'CLASSIC1K', 'mem': self.mem[:self.size()].tolist()}
+        if rands is not None:
+            tag['rands'] = [list(map(int, r)) for r in rands]
+        return [tag]
+
+    def to_json(self, path, rands=None):
+        with open(path, 'w') as f:
+            json.dump(self.entries(rands), f)
+        return path
+
+
+def host_card_image(commands, data, keys=None, image=None):
+    """The CPU twin of the image kernel (nfc_host_card_image): a stream's command records (fsm.FRAME_DTYPE, as fsm.host_commands and
+    NfcMultiCommands.commands_of give them) and their data advance `image` in place (None: a fresh CardImage) -> the image.
+    keys: (key_a, key_b) or (key_a, key_b, table) -- the machine's two keys and its sector table, as decode_many takes them; None: FF..FF."""
+    from . import fsm as _fsm
+    img = CardImage() if image is None else image
+    t = np.ascontiguousarray(commands, _fsm.FRAME_DTYPE)
+    d = np.ascontiguousarray(data, np.uint8).reshape(-1)
+    keys = ((0xFF,) * 6, (0xFF,) * 6) if keys is None else keys
+    ka, kb = (np.ascontiguousarray(list(bytearray(k)), np.uint8) for k in keys[:2])
+    if ka.size != 6 or kb.size != 6:
+        raise ValueError('host_card_image: a key is six bytes')
+    table = _keys.key_table(keys[2]) if len(keys) > 2 and keys[2] is not None else None
+    rc = _lib.load().nfc_host_card_image(img.rec.ctypes.data, t.ctypes.data if len(t) else None, len(t), d.ctypes.data if d.size else None, d.size,
+                                         ka.ctypes.data, kb.ctypes.data, None if table is None else C.byref(table))
+    if rc != 0:
+        raise (ValueError if rc == -1 else EmulationError)('nfc_host_card_image status %d' % rc)
+    return img
+
+
 def state_init():
     st = _lib.EmuState()
     rc = _lib.load().nfc_emu_state_init(C.byref(st))
