@@ -174,11 +174,17 @@ typedef struct {
 } nfc_stats;
 
 /* Everything a successor time chunk needs from its predecessor:
- * fixed header; the ring (av_window float32) follows in the caller's buffer. */
+ * fixed header; the ring (av_window float32) follows in the caller's buffer.
+ * PINNED TO THE REFERENCE after every push (tests/test_carried_state.py, against the oracle's own state): n_seen, ss bit for bit -- the
+ * residue of sums that rounded included --, the ring bit for bit, filled, stable, cur_state, last_bit, dur, n_pending_bits and the pending
+ * bits.  Excepted: miller_state and manch_state (a short batch stores a class representative of the decoder's state, which the
+ * reference has no name for; the symbols and packets they lead to are pinned), pkt_started, and last_low (not carried, below). */
 typedef struct {
     uint64_t n_seen;       /* samples consumed so far */
     double ss;             /* transition_sink._sum */
-    int64_t last_low;      /* index of the last LOW sample, or -1 */
+    int64_t last_low;      /* always -1, kept for the layout; ignored by nfc_set_state.  What a successor needs of the last LOW sample
+                            * follows from cur_state, last_bit and dur: n_seen - 1 while last_bit is -1, n_seen - dur - 1 while
+                            * cur_state is 2, and nothing once a run-length time-out has reset the state */
     int32_t filled;        /* transition_sink._filled */
     int32_t stable;        /* work has been rebound to work_stable */
     int32_t cur_state;     /* transition_sink._current_state */
@@ -251,7 +257,8 @@ int nfc_read_packet_bits(nfc_ctx *ctx, int type, size_t first, uint8_t *out, siz
 /* per-sample classification of the last batch (-1 LOW, 0 accepted, +1 HIGH); debugging tap */
 int nfc_read_val(nfc_ctx *ctx, size_t first, int8_t *out, size_t cap, size_t *n_out);
 
-/* Boundary state for multi-GPU time sharding / restart.  ring holds av_window floats; pending_bits holds the
+/* Boundary state for multi-GPU time sharding / restart.  ring holds av_window floats, in slot order: ring[i] is the slot that
+ * the samples with stream index = i (mod av_window) land on -- for a stream counted from 0 the reference's _buffer[i]; pending_bits holds the
  * open packets' bits (PacketProcessor._cur), type 0 first, hdr->n_pending_bits[0] + [1] bytes.  ring and
  * pending_bits may be NULL in nfc_get_state to query the header (and the sizes) only. */
 int nfc_get_state(nfc_ctx *ctx, nfc_state_header *hdr, float *ring, size_t ring_cap, uint8_t *pending_bits,
@@ -407,7 +414,8 @@ int16_t nfc_host_record_pcm16(float x, float gain);
  *
  * PARITY.  After any sequence of pushes, stream k's outputs of the last push -- counts, edges with the 64-bit stream index in idx,
  * symbols per type, packets, packet bits -- and its state (the nfc_get_state triple) equal those of an nfc_ctx with the same
- * nfc_params after an nfc_push of the same samples; an nfc_ctx is in turn pinned to the reference.  The fill phase may span pushes.
+ * nfc_params after an nfc_push of the same samples; an nfc_ctx is in turn pinned to the reference, its outputs and -- after every push,
+ * with the exceptions named at nfc_state_header -- its state; so is a stream's state here, directly (tests/test_carried_state.py).  The fill phase may span pushes.
  * n[k] == 0 leaves stream k untouched and its outputs empty.  A state exported here and imported into an nfc_ctx (or the other way)
  * continues identically.
  * INPUT.  All seven nfc_input_kinds, i16_scale and its limits as in nfc_create.  dev_base is 16-byte aligned; first_sample[k] is

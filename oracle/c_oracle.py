@@ -53,6 +53,18 @@ def lib():
         L.orc_nseen.restype = C.c_int64
         L.orc_nseen.argtypes = [C.c_void_p]
         L.orc_clear_outputs.argtypes = [C.c_void_p]
+        L.orc_ring.restype = C.c_void_p
+        L.orc_ring.argtypes = [C.c_void_p]
+        for f in ('orc_index', 'orc_filled', 'orc_dur'):
+            getattr(L, f).restype = C.c_int64
+            getattr(L, f).argtypes = [C.c_void_p]
+        for f in ('orc_stable', 'orc_state', 'orc_last_bit'):
+            getattr(L, f).restype = C.c_int
+            getattr(L, f).argtypes = [C.c_void_p]
+        L.orc_n_open_bits.restype = C.c_size_t
+        L.orc_n_open_bits.argtypes = [C.c_void_p, C.c_int]
+        L.orc_open_bits.restype = C.c_void_p
+        L.orc_open_bits.argtypes = [C.c_void_p, C.c_int]
         _lib = L
     return _lib
 
@@ -72,6 +84,7 @@ class COracle(object):
         p = Params(samp_rate, lo_val, hi_val, av_window, max_len, int(reader), int(tag))
         self.h = self.L.orc_create(C.byref(p), int(trace))
         self.factor = 1e6 / samp_rate
+        self.av_window = int(av_window)
 
     def close(self):
         if self.h:
@@ -127,3 +140,13 @@ class COracle(object):
 
     def total(self):
         return self.L.orc_total(self.h)
+
+    def state(self):
+        """What the reference carries from one work() call to the next (transition_sink.py:20-34, packets.py:58-65), read only:
+        the ring as it lies (slot i is _buffer[i]; `index` is the slot the next stable sample lands on), the scalars, and per packet
+        type the open packet's bits."""
+        L, h = self.L, self.h
+        return dict(ring=_arr(L.orc_ring(h), max(self.av_window, 1), np.float64), index=int(L.orc_index(h)), filled=int(L.orc_filled(h)),
+                    stable=int(L.orc_stable(h)), state=int(L.orc_state(h)), last_bit=int(L.orc_last_bit(h)), dur=int(L.orc_dur(h)),
+                    nseen=int(L.orc_nseen(h)), total=float(L.orc_total(h)),
+                    open_bits=[_arr(L.orc_open_bits(h, t), L.orc_n_open_bits(h, t), np.uint8) for t in (0, 1)])

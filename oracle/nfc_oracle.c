@@ -377,6 +377,17 @@ size_t orc_n_trace(const orc *o) { return o->trace.n; }
 const int8_t *orc_trace(const orc *o) { return (const int8_t *)o->trace.p; }
 double orc_total(const orc *o) { return o->total; }
 int64_t orc_nseen(const orc *o) { return o->nseen; }
+/* The carried state, read only (tests/state_util.py): what transition_sink.py:20-34 and packets.py:58-65 keep between two work() calls.
+ * The ring is handed out as it lies: slot i is _buffer[i], orc_index the slot the next stable sample lands on. */
+const double *orc_ring(const orc *o) { return o->ring; }
+int64_t orc_index(const orc *o) { return o->index; }
+int64_t orc_filled(const orc *o) { return o->filled; }
+int orc_stable(const orc *o) { return o->stable; }
+int orc_state(const orc *o) { return o->state; }
+int orc_last_bit(const orc *o) { return o->last_bit; }
+int64_t orc_dur(const orc *o) { return o->dur; }
+size_t orc_n_open_bits(const orc *o, int type) { return o->pp[type].cur.n; }
+const uint8_t *orc_open_bits(const orc *o, int type) { return (const uint8_t *)o->pp[type].cur.p; }
 void orc_clear_outputs(orc *o) {
     o->edges.n = o->sym[0].n = o->sym[1].n = 0;
     o->pk_type.n = o->pk_len.n = o->pk_bits.n = o->trace.n = 0;

@@ -17,8 +17,11 @@
 //   (d) the pending list is ascending, contains every re-run chunk, and a chunk that was not re-run exactly when the chunk before it is
 //       pending and every chunk between it and the nearest re-run chunk below it is "not full";
 //   (e) the sequence ends within 2 * nch + 2 rounds, the bound the host enforces;
-// and the hand-written cases hold: two waves of failures, the lone thresholds, the exactness guard at its boundaries.
+// and the hand-written cases hold: two waves of failures, the lone thresholds, the exactness guard at its boundaries;
+//   (f) the guard's constant against fp64 itself (sum_model): operand sets that span 52 bits sum to one value in 1 000 random orders and
+//       count as exact, sets that span 53 do not count as exact and a fixed-seed search finds one with two orders that differ.
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <iterator>
@@ -275,6 +278,91 @@ static int hand_written() {
     return 0;
 }
 
+// The constant of sums_exact against fp64 itself.  The documented rule: every operand a multiple of 2^low, no sum of them reaching
+// 2^(low + 53).  Operand sets are drawn in units of 2^low (integers held in doubles, either sign, magnitudes from one unit to the whole
+// budget), their absolute values adding up to less than the budget 2^(span + 1) -- so no partial sum of any order reaches it -- and to at
+// least 2^span, so that the guard's `high - low` for the set is exactly `span` (high: the exponent of the bound the kernels would report,
+// here the sum of the absolute values rounded up to a float).
+//   span 52: sums_exact says exact, and 1 000 random orders of summation give one value, set after set;
+//   span 53: sums_exact says not exact, and the search finds a set and two orders whose sums differ -- the guard could not say more.
+static double sum_in_order(const std::vector<double> &v, const std::vector<uint32_t> &order) {
+    volatile double s = 0;   // (one rounding per addition, whatever the optimiser would like)
+    for (uint32_t i : order) s = s + v[i];
+    return s;
+}
+static void shuffle(std::vector<uint32_t> &o, Rng &g) {
+    for (size_t i = o.size(); i > 1; i--) std::swap(o[i - 1], o[g.next() % i]);
+}
+static std::vector<double> draw_operands(Rng &g, int span, double *abs_sum) {
+    const double budget = std::ldexp(1.0, span + 1), floor_ = std::ldexp(1.0, span);
+    for (;;) {
+        std::vector<double> v;
+        double used = 0;
+        const uint32_t n = 2 + g.next() % 63;
+        for (uint32_t i = 0; i < n; i++) {
+            const int mag = (int)(g.next() % (uint32_t)(span + 1));   // the operand's own exponent: anywhere in the span
+            const uint64_t mant = (((uint64_t)g.next() << 32) | g.next()) >> (63 - mag);   // up to mag + 1 bits: an integer below 2^(mag + 1)
+            const double x = (double)(mant | 1u);
+            if (used + x >= budget) continue;
+            used += x;
+            v.push_back((g.next() & 1u) ? -x : x);
+        }
+        if (used >= floor_ && used < budget && v.size() >= 2) {
+            *abs_sum = used;
+            return v;
+        }
+    }
+}
+static uint32_t float_bits_at_least(double x) {   // the smallest float >= x: what an upper bound kept in a float looks like
+    float f = (float)x;
+    if ((double)f < x) f = std::nextafter(f, INFINITY);
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    return u;
+}
+static int sum_model() {
+    Rng g{0xD1B54A32D192ED03ull};
+    const int low = 60;   // exponent-field scale of the unit (any value: the rule is about differences)
+    // span 52
+    int checked = 0;
+    for (int set = 0; set < 40; set++) {
+        double used;
+        const std::vector<double> v = draw_operands(g, 52, &used);
+        const uint32_t vtop = float_bits_at_least(std::ldexp(used, low - 127));
+        float vt;
+        memcpy(&vt, &vtop, 4);
+        if (std::ilogb((double)vt) + 127 - low != 52) continue;   // (the bound rounded up into the next binade: the guard sees 53, rightly cautious)
+        CHECK(sums_exact(255, 0, low + 23, low + 23 + 52, vtop), "sum model: span 52 must count as exact");
+        CHECK(sums_exact(low, 0, 254, 254, vtop) && sums_exact(low, low + 52, 254, 254, 0u), "sum model: span 52 through the carried sum");
+        std::vector<uint32_t> order(v.size());
+        for (uint32_t i = 0; i < order.size(); i++) order[i] = i;
+        const double first = sum_in_order(v, order);
+        for (int k = 0; k < 1000; k++) {
+            shuffle(order, g);
+            CHECK(sum_in_order(v, order) == first, "sum model: span 52, two orders of summation differ");
+        }
+        checked++;
+    }
+    CHECK(checked >= 30, "sum model: span 52, fewer than 30 of the 40 operand sets were checked");
+    // span 53
+    bool found = false;
+    for (int set = 0; set < 4000 && !found; set++) {
+        double used;
+        const std::vector<double> v = draw_operands(g, 53, &used);
+        const uint32_t vtop = float_bits_at_least(std::ldexp(used, low - 127));
+        CHECK(!sums_exact(255, 0, low + 23, low + 23 + 52, vtop), "sum model: span 53 must not count as exact");
+        std::vector<uint32_t> order(v.size());
+        for (uint32_t i = 0; i < order.size(); i++) order[i] = i;
+        const double first = sum_in_order(v, order);
+        for (int k = 0; k < 50 && !found; k++) {
+            shuffle(order, g);
+            found = sum_in_order(v, order) != first;
+        }
+    }
+    CHECK(found, "sum model: span 53, no operand set with two orders that differ was found");
+    return 0;
+}
+
 int main() {
     Rng g{0x9E3779B97F4A7C15ull};
     RerunBook b;   // (one book for every sequence, as the context keeps one for every batch)
@@ -298,6 +386,7 @@ int main() {
                                 }
                         }
     if (hand_written()) return 1;
+    if (sum_model()) return 1;
     printf("rerun_plan_check: %ld sequences (%d rounds at most), the hand-written cases and the exactness guard: every property held\n", sequences, rounds_max);
     return 0;
 }

@@ -173,6 +173,10 @@ struct nfc_ctx {
     bool fill_pending = false, fill_can_ride = false, fill_front = false;
     FillRider fill;
     uint32_t dbg_fill_rode = 0, dbg_fill_refront = 0;
+    // the route the last batch's threshold stage took (run_threshold; the test build's nfc_debug_threshold_route): parallel attempts, spans
+    // handed to the sequential kernel, the samples it took, and which exit sent the rest of the batch there (0 none: a parallel attempt
+    // stood; 1 the sequential kernel was configured or the window is shorter than a step; 2 round >= 6; 3 left <= 4 * span)
+    uint32_t route[4] = {0, 0, 0, 0};
     // debugging switches, read ONCE for nfc_create (read_switches: an inherited environment must not reach the per-launch path)
     bool dbg_bad_launch = false, dbg_redo_submitted = false, dbg_no_submit_ahead = false, dbg_any = false, dbg_clk = false, dbg_trace = false;
     std::string dbg_clk_path;

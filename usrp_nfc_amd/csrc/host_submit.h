@@ -98,6 +98,8 @@ int enqueue_stages_behind(nfc_ctx *c, nfc_ctx::Submitted &b) {
     c->stats.chunk_samples = b.chunk;
     c->stats.threshold_passes = 1;
     c->stats.ran_ahead = 1;
+    c->route[0] = 1;   // (one parallel attempt, enqueued ahead; a batch that does not stand goes through run_threshold, which counts anew)
+    c->route[1] = c->route[2] = c->route[3] = 0;
     c->stamp_b = b.seq;
     c->cert_pending = false;
     size_capacities(c, b.n);

@@ -770,8 +770,11 @@ int run_threshold(nfc_ctx *c, const void *d_in, uint32_t n, uint32_t skip, const
     const uint32_t span = (uint32_t)std::min<uint64_t>(((uint64_t)8 * c->L + STEP - 1) / STEP * STEP, 1u << 30);   // prefix per round
     EdgeCarry ec = c->h_ecarry;
     uint32_t base = 0;
+    const bool forced = (c->P.flags & NFC_FLAG_FORCE_SEQUENTIAL) != 0 || c->L < STEP;
+    c->route[0] = c->route[1] = c->route[2] = c->route[3] = 0;
     for (int round = 0;; round++) {
         bool need_seq = false, span_clean = false;
+        if (!forced) c->route[0]++;
         // (while the stream is in the regime that needs re-runs, the later stages are not enqueued behind pass 0 on the chance that
         // it stands: they would run -- 0.17 ms of the machine -- before the host has seen the verdict, and run again after the re-runs)
         const bool optimistic = base == 0 && !(c->fine_adapt && c->fine_left > 0);
@@ -785,6 +788,7 @@ int run_threshold(nfc_ctx *c, const void *d_in, uint32_t n, uint32_t skip, const
             c->cert_pending = false;
             HIPCHK(c, hipMemsetAsync((char *)dC(c) + offsetof(Carry, fin_valid), 0, sizeof(int32_t), c->st));
             span_clean = false;
+            c->route[0]++;
             rc = threshold_span(c, d_in, n, skip, base, ec, nullptr, &span_clean, &need_seq, nullptr);
             if (rc) return rc;
         }
@@ -796,9 +800,14 @@ int run_threshold(nfc_ctx *c, const void *d_in, uint32_t n, uint32_t skip, const
             }
             return NFC_OK;
         }
-        const bool forced = (c->P.flags & NFC_FLAG_FORCE_SEQUENTIAL) != 0 || c->L < STEP;
         const uint32_t left = n - base;
-        if (forced || round >= 6 || left <= 4 * span) return sequential_span(c, d_in, skip, base, left, ec, nullptr);
+        c->route[1]++;
+        if (forced || round >= 6 || left <= 4 * span) {
+            c->route[2] += left;
+            c->route[3] = forced ? 1u : round >= 6 ? 2u : 3u;
+            return sequential_span(c, d_in, skip, base, left, ec, nullptr);
+        }
+        c->route[2] += span;
         const int rs = sequential_span(c, d_in, skip, base, span, ec, &ec);
         if (rs) return rs;
         base += span;

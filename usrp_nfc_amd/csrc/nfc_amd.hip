@@ -1568,6 +1568,14 @@ extern "C" int nfc_debug_fill_order(const nfc_ctx *c, uint32_t *out2) {
     out2[1] = c->dbg_fill_refront;
     return NFC_OK;
 }
+// the route the last batch's threshold stage took (host_threshold.h: run_threshold): out4[0] parallel attempts, [1] spans handed to the
+// sequential kernel, [2] the samples it took, [3] the exit that sent the REST of the batch there: 0 none (a parallel attempt stood), 1 the
+// sequential kernel was configured (or av_window is shorter than a step), 2 round >= 6, 3 left <= 4 * span.  A batch that ran ahead and stood: 1, 0, 0, 0.
+extern "C" int nfc_debug_threshold_route(const nfc_ctx *c, uint32_t *out4) {
+    if (!c || !out4) return NFC_ERR_ARG;
+    for (int k = 0; k < 4; k++) out4[k] = c->route[k];
+    return NFC_OK;
+}
 // the decode stage's shapes: edges per tile, the tile count up to which a tile's workgroup folds its predecessors itself (this
 // context's), packet ends staged per tile, LUT rows staged in LDS at most, the longest run-in in edges; and whether the last batch's
 // tiles folded their predecessors themselves (1) or the single-workgroup prefix launch ran (0)
